@@ -3,7 +3,11 @@
 training step (BASELINE.json config C3: bs 16 per GPU, fp32), weak-scaled over
 N GPUs with one RCCL all-reduce per optimiser.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+K timed steps (K >= 1) after W warm-up steps; `ms_per_step` in the JSON line is the wall time of one timed
+step.  The inputs (weights and batch) are seeded, so the same arguments give the same inputs in every run, and
+--dump-outputs writes what the last timed step computed as .npy files for comparing two builds.
 
 N > 1 from a bare shell (no WORLD_SIZE in the environment): this process starts N fresh
 rank processes itself -- before it has made any GPU call -- waits for them and exits with
@@ -94,7 +98,14 @@ def parse_args(argv=None):
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="start the ranks, form the process group, all-reduce one number and print the JSON stub: "
                          "the launcher's own test (no GPU work)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy: the four "
+                         "logged losses, the generator's output, and each network's parameters, gradients and buffers; "
+                         "see write_outputs() for the sampling of large arrays")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def _free_port():
@@ -302,6 +313,49 @@ def phase_breakdown(gan, opts, batch, steps=3, on_phase=None):
     return [(nm, ms / steps, g, d) for nm, ms, g, d in tot]
 
 
+def step_outputs(gan, logs):
+    """What one `GAN.fit_batch` hands its caller: the logged losses it returns, the generator output of its G step
+    (`generated_imgs`, as the reference keeps it) and both networks as the step left them -- parameters (named
+    order), their gradients and the buffers (BatchNorm running statistics).  Tensors stay on the device."""
+    import torch
+    out = {k: v.detach().reshape(()) for k, v in sorted(logs.items())}
+    out["generated"] = gan.generated_imgs.detach()
+    for name, net in (("generator", gan.generator), ("discriminator", gan.discriminator)):
+        params = list(net.parameters())
+        out[f"{name}_params"] = torch.cat([p.detach().flatten().float() for p in params])
+        out[f"{name}_grads"] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().flatten().float()
+                                          for p in params])
+        out[f"{name}_buffers"] = torch.cat([b.detach().flatten().double() for b in net.buffers()] or
+                                           [torch.zeros(0, dtype=torch.float64)])
+    return out
+
+
+DUMP_MAX_ELEMS = 1 << 21          # per array (8 MiB in float32): larger arrays are written as a fixed sample
+DUMP_MAX_BYTES = 64_000_000
+
+
+def write_outputs(arrays, out_dir):
+    """`arrays` (name -> tensor) as `out_dir/<name>.npy`: float64 tensors stay float64, everything else is written as
+    float32.  An array of more than DUMP_MAX_ELEMS elements is flattened and cut down to the elements at
+    DUMP_MAX_ELEMS flat indices drawn without replacement by a generator seeded with 0, in increasing order: the same
+    indices for the same size, so the files of two runs compare element for element."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ELEMS]
+            t = t.flatten()[idx.sort().values]
+        a = t.numpy().astype(np.float64 if t.dtype == torch.float64 else np.float32)
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise RuntimeError(f"--dump-outputs: {total} bytes at {name}, over the {DUMP_MAX_BYTES}-byte budget")
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
+
+
 def family_of(name: str) -> str:
     if name.startswith("wgrad"):
         return "wgrad"
@@ -390,11 +444,14 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        gan.fit_batch(batch, args.warmup + i, opts)
+        logs = gan.fit_batch(batch, args.warmup + i, opts)
     barrier()
     dt = time.perf_counter() - t0
     engine.set_probe(None)
     note(f"timed region: {dt / args.steps * 1e3:.1f} ms/step")
+    if args.dump_outputs and rank == 0:            # before the side measurements below step or re-run the networks
+        nbytes = write_outputs(step_outputs(gan, logs), args.dump_outputs)
+        note(f"outputs of the last timed step: {nbytes / 1e6:.1f} MB in {args.dump_outputs}")
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

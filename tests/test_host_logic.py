@@ -199,3 +199,36 @@ def test_border_class_phases_cover_every_tap_pair_exactly_once(tmp_path):
                     os.path.join(ROOT, "tools", "check_phase_classes.hip"), "-o", exe], check=True, capture_output=True)
     out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
     assert " 0 errors" in out and "geometries used classes" in out, out
+
+
+def test_bench_dump_outputs_writer(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 .npy files; an array over the element cap becomes the same seeded,
+    increasing sample of its flat elements in every run; the byte budget is enforced."""
+    import bench
+    n = bench.DUMP_MAX_ELEMS
+    arrays = {"loss": torch.tensor(0.25), "small": torch.arange(6, dtype=torch.float16).view(2, 3),
+              "count": torch.tensor([7], dtype=torch.int64), "wide": torch.arange(n + 1000, dtype=torch.float64),
+              "big": torch.arange(n + 5, dtype=torch.float32)}
+    total = bench.write_outputs(arrays, str(tmp_path / "a"))
+    bench.write_outputs(arrays, str(tmp_path / "b"))
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in arrays}
+    assert total == sum(a.nbytes for a in got.values()) <= 64_000_000
+    assert got["loss"].dtype == np.float32 and got["loss"].shape == () and float(got["loss"]) == 0.25
+    assert got["small"].dtype == np.float32 and got["small"].shape == (2, 3) and got["small"][1, 2] == 5
+    assert got["count"].dtype == np.float32 and got["count"][0] == 7
+    assert got["wide"].dtype == np.float64 and got["wide"].shape == (n,)
+    assert got["big"].dtype == np.float32 and got["big"].shape == (n,)
+    for k in ("wide", "big"):                          # the values are the indices: a strictly increasing subset
+        assert (np.diff(got[k]) > 0).all() and got[k][0] >= 0 and got[k][-1] < n + 1000
+        assert np.array_equal(got[k], np.load(tmp_path / "b" / f"{k}.npy"))
+    assert not np.array_equal(got["big"], np.arange(n))   # a sample, not the first n elements
+    with pytest.raises(RuntimeError):
+        bench.write_outputs({f"x{i}": torch.zeros(n) for i in range(8)}, str(tmp_path / "c"))
+
+
+def test_bench_refuses_zero_steps():
+    import bench
+    assert bench.parse_args(["--steps", "3", "--warmup", "0"]).steps == 3
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)

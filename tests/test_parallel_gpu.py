@@ -64,18 +64,20 @@ def test_two_ranks_fit_batch_data_parallel(tmp_path):
     (["--size", "64", "--batch", "4"], "slices/s", "f32", 157.3, 4),
     (["--dims", "3", "--size", "40", "--batch", "2", "--dtype", "bf16"], "volumes/s", "bf16", 2500.0, 2),   # C5's path
 ])
-def test_bench_line_contract_small_size(extra, unit, dtype, peak, per_step):
+def test_bench_line_contract_small_size(extra, unit, dtype, peak, per_step, tmp_path):
     """bench.py at a small size (one rank, no CPU baseline): ONE JSON line on stdout with the driver's keys, the
     roofline object -- its kernel chosen by measured time and named as rocprofv3 would name it, the best kernel
-    beside it -- the per-pass `phases` of one step and the rank count seen by a collective.  Second case: the
-    3-D bf16-storage configuration (BASELINE config C5's code path)."""
+    beside it -- the per-pass `phases` of one step and the rank count seen by a collective; --dump-outputs writes
+    the last timed step's results.  Second case: the 3-D bf16-storage configuration (BASELINE config C5's code path)."""
     import json
     import subprocess
     import sys
+    import numpy as np
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dump = tmp_path / "outputs"
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), *extra, "--steps", "2", "--warmup", "1",
-                          "--no-cpu-baseline", "--no-gfwd", "--dense-min-gflop", "0.05"], capture_output=True, text=True,
-                         timeout=900)
+                          "--no-cpu-baseline", "--no-gfwd", "--dense-min-gflop", "0.05", "--dump-outputs", str(dump)],
+                         capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -105,3 +107,14 @@ def test_bench_line_contract_small_size(extra, unit, dtype, peak, per_step):
     assert 0.5 * j["ms_per_step"] <= total <= 2.0 * j["ms_per_step"], (total, j["ms_per_step"])
     assert all(ph["roofline_frac"] is None or 0.0 < ph["roofline_frac"] < 1.0 for ph in j["phases"])
     assert "workload" in j["config"] and "model" not in j["config"]
+    # --dump-outputs: the losses the JSON line reports (one rank: the rank mean is the rank's own value), the
+    # generator's output of the G step and both networks after the step, finite, in float32 / float64, <= 64 MB
+    got = {f.stem: np.load(f) for f in dump.glob("*.npy")}
+    nets = [f"{n}_{part}" for n in ("generator", "discriminator") for part in ("params", "grads", "buffers")]
+    assert set(got) == {"g_adv_loss", "g_recon_loss", "g_loss", "d_loss", "generated", *nets}, sorted(got)
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in got.values())
+    assert sum(f.stat().st_size for f in dump.glob("*.npy")) <= 64_000_000
+    for k, v in j["losses"].items():
+        assert float(got[k]) == v, (k, float(got[k]), v)
+    assert got["generated"].shape[0] == per_step and np.abs(got["generated"]).max() <= 1.0
+    assert np.abs(got["generator_grads"]).max() > 0 and np.abs(got["discriminator_grads"]).max() > 0
