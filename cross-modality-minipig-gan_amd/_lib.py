@@ -33,6 +33,12 @@ class PrologueC(C.Structure):
                 ("act", C.c_int32), ("slope", C.c_float), ("slope_ptr", C.c_void_p)]
 
 
+class SwGeomC(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("dhw", C.c_int32 * 3), ("pad_lo", C.c_int32 * 3), ("padded", C.c_int32 * 3),
+                ("roi", C.c_int32 * 3), ("num", C.c_int32 * 3), ("starts_dev", C.c_void_p),
+                ("starts_host", C.POINTER(C.c_int32))]
+
+
 _P = C.c_void_p
 _I = C.c_int32
 _L = C.c_int64
@@ -40,6 +46,7 @@ _F = C.c_float
 _G = C.POINTER(ConvGeomC)
 _PR = C.POINTER(PrologueC)
 _I3 = C.POINTER(C.c_int32)
+_SW = C.POINTER(SwGeomC)
 
 # name -> (restype, argtypes); must list EVERY symbol include/mpgan_hip.h declares
 SIGNATURES = {
@@ -127,6 +134,11 @@ SIGNATURES = {
     "mpgan_norm_bwd_rows_bf16": (_I, [_L, _I]),
     "mpgan_norm_bwd_reduce_bf16": (_I, [_P, _I, _I, _P, _I, _P, _P, _P, _P, _F, _L, _I, _P, _P]),
     "mpgan_norm_bwd_apply_bf16": (_I, [_P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _F, _L, _I, _P, _I, _P, _P]),
+    # sliding-window inference (inference.py)
+    "mpgan_sw_gather": (_I, [_SW, _P, _I, _I, _I, _F, _P, _P]),
+    "mpgan_sw_count": (_I, [_SW, _P, _P, _P]),
+    "mpgan_sw_blend": (_I, [_SW, _P, _I, _I, _I, _P, _P, _P]),
+    "mpgan_sw_finalize": (_I, [_SW, _P, _I, _P, _P, _P]),
 }
 
 

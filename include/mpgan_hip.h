@@ -517,6 +517,38 @@ int mpgan_norm_bwd_apply_bf16(const void* g, int32_t g_f32, int32_t ldg, const v
                               const float* c2, float slope, int64_t rows, int32_t c, void* dz, int32_t lddz,
                               float* bias_partials, void* stream);
 
+/* ---- sliding-window inference (MONAI 0.4.0 sliding_window_inference; code/GAN/minipig_inference.py:110-114) --
+ * An image batch (B, C, D, H, W) contiguous fp32 (2-D: D = 1) is padded per dim by pad_lo before / the rest after
+ * up to `padded` (never materialised: out-of-range reads give cval), covered by the windows start_z x start_y x
+ * start_x (meshgrid "ij": z slowest) and each window batch goes through the caller's predictor.  Global window
+ * index i = b * num_win + w (image-major).  The start table lives in device memory (`starts_dev`, the kernels read
+ * it) and is mirrored on the host (`starts_host`, validated before any launch: 0 <= start <= padded - roi).
+ * Element offsets are 64-bit.  Every thread owns its output elements: no atomics, deterministic results. */
+typedef struct {
+  int32_t batch;               /* B */
+  int32_t dhw[3];              /* image extent */
+  int32_t pad_lo[3];           /* padding before each dim */
+  int32_t padded[3];           /* padded extent (>= dhw + pad_lo, >= roi) */
+  int32_t roi[3];              /* window extent */
+  int32_t num[3];              /* window starts per dim */
+  const int32_t* starts_dev;   /* device int32[num[0] + num[1] + num[2]]: z starts, then y, then x (padded coords) */
+  const int32_t* starts_host;  /* the same table on the host */
+} mpgan_sw_geom;
+
+/* win[k] (k < n, contiguous (n, cin, roi)) = padded image of global window first + k. */
+int mpgan_sw_gather(const mpgan_sw_geom* g, const float* in, int32_t cin, int32_t first, int32_t n, float cval,
+                    float* win, void* stream);
+/* count[padded] (one spatial map for every image and channel) = sum of imp over the windows covering each voxel,
+ * in window order.  imp: device (roi) fp32 importance map; null => constant 1. */
+int mpgan_sw_count(const mpgan_sw_geom* g, const float* imp, float* count, void* stream);
+/* acc (B, cout, padded), zeroed by the caller before the first call: for global windows first .. first+n-1 in order,
+ * acc[b, :, win] = acc + imp * pred[k] (one rounded product, one rounded add).  pred: contiguous (n, cout, roi). */
+int mpgan_sw_blend(const mpgan_sw_geom* g, const float* pred, int32_t cout, int32_t first, int32_t n, const float* imp,
+                   float* acc, void* stream);
+/* out (B, cout, dhw) = acc / count over the unpadded region (IEEE division). */
+int mpgan_sw_finalize(const mpgan_sw_geom* g, const float* acc, int32_t cout, const float* count, float* out,
+                      void* stream);
+
 /* ---- development aids (no counterpart in the reference) ----------------------------------------------------
  * In-kernel phase stamps: a library built with `make STAMPS=1` records, for each of the next `launches`
  * gather-conv launches, the 100 MHz device clock at every block's phase boundaries into
