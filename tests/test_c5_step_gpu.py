@@ -94,9 +94,13 @@ def test_c5_step_bf16_storage_against_emulation_and_oracle():
     y_ref = rg(t1)
     y_pure = rg_pure(t1)
     e_y, cost_y = (captured["y"].cpu() - y_ref).abs().mean().item(), (y_ref - y_pure).abs().mean().item()
+    d_pure = (captured["y"].cpu() - y_pure).abs()
     print(f"G output L1: ours vs bf16-operand emulation {e_y:.3e}; emulation vs fp32 oracle (precision cost) {cost_y:.3e}; "
-          f"ours vs fp32 oracle {(captured['y'].cpu() - y_pure).abs().mean().item():.3e}")
+          f"ours vs fp32 oracle {d_pure.mean().item():.3e} (max abs {d_pure.max().item():.3e})")
     assert e_y <= 2 * cost_y + 1e-4, (e_y, cost_y)
+    # absolute cap beside the relative rule: C5 parity against the fp32 oracle (measured 3.5e-4) stays pinned even if the
+    # emulation and the kernels degrade together
+    assert d_pure.mean().item() <= 1e-3, d_pure.mean().item()
     assert (captured["y"].cpu() - y_ref).abs().max().item() <= 2 * (y_ref - y_pure).abs().max().item() + 2e-3
     adv = E.disc_step(rd, y_ref.detach(), 1.0)
     g_recon = F.l1_loss(y_ref, t2)
@@ -287,9 +291,11 @@ def test_c5_full_size_step_is_finite_deterministic_and_g_matches_oracle():
         y_ref = ref_g(t1[:1])
         y_pure = ref_pure(t1[:1])
     l1, cost = (y1 - y_ref).abs().mean().item(), (y_ref - y_pure).abs().mean().item()
+    d_pure = (y1 - y_pure).abs()
     print(f"G output L1 at 128^3: ours vs bf16-operand emulation {l1:.3e}; emulation vs fp32 oracle (precision cost) {cost:.3e}; "
-          f"ours vs fp32 oracle {(y1 - y_pure).abs().mean().item():.3e}")
+          f"ours vs fp32 oracle {d_pure.mean().item():.3e} (max abs {d_pure.max().item():.3e})")
     assert l1 <= 2 * cost + 1e-4, (l1, cost)
+    assert d_pure.mean().item() <= 1e-3, d_pure.mean().item()      # absolute cap (measured 3.65e-4), as at 72^3
     assert (y1 - y_ref).abs().max().item() <= 2 * (y_ref - y_pure).abs().max().item() + 2e-3
     for k in ("g_adv_loss", "g_recon_loss", "g_loss", "d_loss"):
         assert k in log and log[k] == log[k] and 0.0 <= log[k] <= 101.0, (k, log.get(k))      # BCE's -100 clamp bounds it
