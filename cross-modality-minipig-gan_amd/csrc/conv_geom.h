@@ -225,7 +225,7 @@ inline void set_geom_flags(GatherConv& p, const mpgan_conv_geom* g) {
 
 // conv_mm16.hip: the MM16 instances of the K-stepped kernel (conv_pipe.h)
 bool mm16_gather_ok(const GatherConv& p);
-int launch_gather_mm16(const GatherConv& p, int variant, bool ksplit2, long maxM, hipStream_t st);
+int launch_gather_mm16(const GatherConv& p, int bn, int wraps, int pro, int ks, long maxM, hipStream_t st);
 
 // forward-type gather: produced[o] = sum_k gathered[o*s - p + k] * W[k]
 inline void build_forward(GatherConv& p, int n, const int32_t* gath_dhw, int cg, const int32_t* prod_dhw, int cp,

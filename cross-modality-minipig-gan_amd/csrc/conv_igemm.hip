@@ -1199,122 +1199,6 @@ static bool thin_cin1_rows_ok(const GatherConv& p) {
          p.Ho == ph.My && p.Do == ph.Mz;
 }
 
-static int launch_thin(const GatherConv& p, long maxM, hipStream_t st) {
-  const int T = p.Kz * p.Ky * p.Kx;
-  if (p.out_bf16) {     // 1 -> C conv writing bf16 (D.conv1 of the bf16 path): all-channel kernel only
-    MPGAN_UNSUPPORTED(!(thin_cin1_ok(p) && (p.Cout == 16 || p.Cout == 32 || p.Cout == 64) && p.ldo % 4 == 0 &&
-                        (reinterpret_cast<uintptr_t>(p.out) & 7) == 0 && !p.resid && !p.tanh_out && !p.in_bf16 &&
-                        (!p.bias || (reinterpret_cast<uintptr_t>(p.bias) & 15) == 0)),
-                      "thin conv (bf16 out): needs Cin == 1, Cout in {16, 32, 64}, no resid/tanh, aligned output");
-    MPGAN_UNSUPPORTED(p.stats && p.Cout > 64, "thin conv (bf16 out): fused statistics up to 64 channels");
-    dim3 grid((unsigned)((maxM + 255) / 256), 1, (unsigned)p.nphase);
-    if (thin_cin1_rows_ok(p)) {
-      if (T == 9) hipLaunchKernelGGL((thin_cin1_rows_kernel<9, true>), grid, dim3(256), 0, st, p);
-      else hipLaunchKernelGGL((thin_cin1_rows_kernel<27, true>), grid, dim3(256), 0, st, p);
-      return check_launch("thin_cin1_rows_bf16");
-    }
-    const size_t smem = ((size_t)((T * p.Cout + 3) & ~3) + (p.stats ? 256 * (size_t)(p.Cout + 1) : 0)) * sizeof(float);
-    if (p.Cout == 16) hipLaunchKernelGGL((thin_cin1_full_kernel<4, true>), grid, dim3(256), smem, st, p);
-    else if (p.Cout == 32) hipLaunchKernelGGL((thin_cin1_full_kernel<8, true>), grid, dim3(256), smem, st, p);
-    else {
-      static bool attr_set = false;
-      if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(thin_cin1_full_kernel<16, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        if (e != hipSuccess) { set_error("thin_cin1_full: hipFuncSetAttribute: %s", hipGetErrorString(e)); return MPGAN_ERR_HIP; }
-        attr_set = true;
-      }
-      hipLaunchKernelGGL((thin_cin1_full_kernel<16, true>), grid, dim3(256), smem, st, p);
-    }
-    return check_launch("thin_cin1_full_bf16");
-  }
-  if (p.in_bf16) {      // C -> 1 gather over bf16 data (backward-data of D.conv1 in the bf16 path)
-    if (thin_cout1_mfma_bf16_ok(p)) return launch_thin_cout1_mfma_bf16(p, st);
-    const int lanes_b = p.Cin / 4;
-    MPGAN_UNSUPPORTED(!(p.Cout == 1 && !p.pro.scale && p.Cin % 4 == 0 && p.ldi % 4 == 0 &&
-                        (lanes_b == 4 || lanes_b == 8 || lanes_b == 16) && (reinterpret_cast<uintptr_t>(p.in) & 7) == 0 &&
-                        (long)T * p.Cin * 4 <= 48 * 1024 && !p.stats),
-                      "thin conv (bf16 in): needs Cout == 1 and 16, 32 or 64 gathered channels");
-    const long threads_b = maxM * lanes_b;
-    dim3 grid((unsigned)((threads_b + 255) / 256), 1, (unsigned)p.nphase);
-    const size_t smem = (size_t)T * p.Cin * sizeof(float);
-    if (lanes_b == 4) hipLaunchKernelGGL((thin_cout1_kernel<4, true>), grid, dim3(256), smem, st, p);
-    else if (lanes_b == 8) hipLaunchKernelGGL((thin_cout1_kernel<8, true>), grid, dim3(256), smem, st, p);
-    else hipLaunchKernelGGL((thin_cout1_kernel<16, true>), grid, dim3(256), smem, st, p);
-    return check_launch("thin_cout1_bf16");
-  }
-  if (thin_c1c1_ok(p)) {
-    const Phase& ph0 = p.ph[0];
-    const long threads4 = (long)p.N * ph0.Mz * ph0.My * ((ph0.Mx + 3) / 4);
-    if (p.dstep[2] < 0) hipLaunchKernelGGL(thin_c1c1_rows4_kernel<true>, dim3((unsigned)((threads4 + 255) / 256)), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(thin_c1c1_rows4_kernel<false>, dim3((unsigned)((threads4 + 255) / 256)), dim3(256), 0, st, p);
-    return check_launch("thin_c1c1_rows4");
-  }
-  if (thin_cin1_ok(p)) {
-    const bool v4 = (p.Cout % 4 == 0) && (p.ldo % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.out) & 15) == 0);
-    const bool full = v4 && (p.Cout == 16 || p.Cout == 32 || p.Cout == 64) &&
-                      (!p.bias || (reinterpret_cast<uintptr_t>(p.bias) & 15) == 0) &&
-                      (!p.resid || ((p.ldr % 4 == 0) && (reinterpret_cast<uintptr_t>(p.resid) & 15) == 0));
-    MPGAN_UNSUPPORTED((p.stats || p.stats_acc) && !(full && p.Cout <= 32),
-                      "thin conv: fused statistics need the all-channel kernel (Cout 16 or 32, 16-byte aligned output/bias)");
-    if (full) {
-      dim3 grid((unsigned)((maxM + 255) / 256), 1, (unsigned)p.nphase);
-      if (!p.stats && thin_cin1_rows_ok(p)) {
-        if (T == 9) hipLaunchKernelGGL((thin_cin1_rows_kernel<9, false>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((thin_cin1_rows_kernel<27, false>), grid, dim3(256), 0, st, p);
-        return check_launch("thin_cin1_rows");
-      }
-      const size_t smem = ((size_t)((T * p.Cout + 3) & ~3) + ((p.stats || p.stats_acc) ? 256 * (size_t)(p.Cout + 1) : 0)) * sizeof(float);
-      if (p.Cout == 16) hipLaunchKernelGGL(thin_cin1_full_kernel<4>, grid, dim3(256), smem, st, p);
-      else if (p.Cout == 32) hipLaunchKernelGGL(thin_cin1_full_kernel<8>, grid, dim3(256), smem, st, p);
-      else hipLaunchKernelGGL(thin_cin1_full_kernel<16>, grid, dim3(256), smem, st, p);
-      return check_launch("thin_cin1_full");
-    }
-    const int V = v4 ? 4 : 1;
-    const int CQ = (p.Cout + V - 1) / V;
-    const long threads = maxM * CQ;
-    dim3 grid((unsigned)((threads + 255) / 256), 1, (unsigned)p.nphase);
-    const size_t smem = (size_t)T * CQ * V * sizeof(float);
-    if (v4) hipLaunchKernelGGL(thin_cin1_kernel<4>, grid, dim3(256), smem, st, p);
-    else hipLaunchKernelGGL(thin_cin1_kernel<1>, grid, dim3(256), smem, st, p);
-    return check_launch("thin_cin1");
-  }
-  const int lanes = p.Cin / 4;
-  MPGAN_UNSUPPORTED((p.stats || p.stats_acc) && !convt_quad_ok(p),
-                    "thin conv: fused statistics of a 1-channel output exist for ConvTranspose2d(C -> 1, k3 s2) only");
-  if (convt_quad_ok(p)) {
-    const long qthreads = (long)p.N * p.Hi * p.Wi * lanes;
-    dim3 qgrid((unsigned)((qthreads + 255) / 256));
-    const size_t qsmem = (size_t)9 * p.Cin * sizeof(float);
-    if (lanes == 4) hipLaunchKernelGGL(convt_quad_cout1_kernel<4>, qgrid, dim3(256), qsmem, st, p);
-    else if (lanes == 8) hipLaunchKernelGGL(convt_quad_cout1_kernel<8>, qgrid, dim3(256), qsmem, st, p);
-    else hipLaunchKernelGGL(convt_quad_cout1_kernel<16>, qgrid, dim3(256), qsmem, st, p);
-    return check_launch("convt_quad_cout1");
-  }
-  if (convt_oct_ok(p)) {
-    const long othreads = (long)p.N * p.Di * p.Hi * p.Wi * lanes;
-    dim3 ogrid((unsigned)((othreads + 255) / 256));
-    const size_t osmem = (size_t)27 * p.Cin * sizeof(float);
-    if (lanes == 4) hipLaunchKernelGGL(convt_oct_cout1_kernel<4>, ogrid, dim3(256), osmem, st, p);
-    else if (lanes == 8) hipLaunchKernelGGL(convt_oct_cout1_kernel<8>, ogrid, dim3(256), osmem, st, p);
-    else hipLaunchKernelGGL(convt_oct_cout1_kernel<16>, ogrid, dim3(256), osmem, st, p);
-    return check_launch("convt_oct_cout1");
-  }
-  const long threads = maxM * lanes;
-  dim3 grid((unsigned)((threads + 255) / 256), 1, (unsigned)p.nphase);
-  const size_t smem = (size_t)T * p.Cin * sizeof(float);
-  switch (lanes) {
-    case 1: hipLaunchKernelGGL(thin_cout1_kernel<1>, grid, dim3(256), smem, st, p); break;
-    case 2: hipLaunchKernelGGL(thin_cout1_kernel<2>, grid, dim3(256), smem, st, p); break;
-    case 4: hipLaunchKernelGGL(thin_cout1_kernel<4>, grid, dim3(256), smem, st, p); break;
-    case 8: hipLaunchKernelGGL(thin_cout1_kernel<8>, grid, dim3(256), smem, st, p); break;
-    case 16: hipLaunchKernelGGL(thin_cout1_kernel<16>, grid, dim3(256), smem, st, p); break;
-    case 32: hipLaunchKernelGGL(thin_cout1_kernel<32>, grid, dim3(256), smem, st, p); break;
-    default: hipLaunchKernelGGL(thin_cout1_kernel<64>, grid, dim3(256), smem, st, p); break;
-  }
-  return check_launch("thin_cout1");
-}
-
 // ---------------------------------------------------------------------------
 // Patch kernel: 2-D layers with <= 32 output channels and 16/32/64 gathered channels
 // (the U-Net's stride-1 units, its stride-2 down convs up to 32 channels, the transposed
@@ -1347,6 +1231,49 @@ struct PatchLaunch {
   int tw_off;            // persistent form: LDS float offset of the output transpose staging (4 waves x 16 px x pitch), or -1:
                          //   the epilogue then leaves through it as 16-byte stores (vector output path)
   int dbg;               // MPGAN_DBG_PATCH_SKIP bits (what-if timing builds): 1 no output stores, 2 no MFMAs, 4 no patch loads, 8 no LDS patch stores
+};
+// the patch kernels take both structs by value: together they must fit the 4 KiB kernel-argument segment
+static_assert(sizeof(GatherConv) + sizeof(PatchLaunch) <= 4096, "gather_patch kernel arguments exceed 4 KiB");
+
+// ---------------------------------------------------------------------------
+// Which kernel serves a gather conv.  choose_gather() (below, after the last predicate) is the ONE place the form is
+// decided: launch_gather runs its choice, and every geometry query (mpgan_conv_variant, the statistics-row counts,
+// accumulator / fold support) reads the choice made for the stand-in GatherConv the entry point would build
+// (standin_conv), so a query cannot disagree with its launch.
+// ---------------------------------------------------------------------------
+enum class GForm {
+  ThinBf16OutRows,   // thin_cin1_rows_kernel<T, true>             (fp32 -> bf16, mpgan_conv_forward_f32_to_bf16)
+  ThinBf16OutFull,   // thin_cin1_full_kernel<CQ, true>
+  ThinBf16InMfma,    // conv_bf16.hip: launch_thin_cout1_mfma_bf16  (bf16 -> fp32, mpgan_conv_backward_data_bf16_to_f32)
+  ThinBf16In,        // thin_cout1_kernel<LANES, true>
+  C1C1Rows4,         // thin_c1c1_rows4_kernel<REVX>
+  Cin1Rows,          // thin_cin1_rows_kernel<T, false>
+  Cin1Full,          // thin_cin1_full_kernel<CQ>
+  Cin1,              // thin_cin1_kernel<V>
+  ConvtQuad,         // convt_quad_cout1_kernel<LANES>
+  ConvtOct,          // convt_oct_cout1_kernel<LANES>
+  Cout1,             // thin_cout1_kernel<LANES>
+  Patch3d,           // gather_patch3d_c16_kernel<HAS_PRO, MM16>
+  Patch,             // gather_patch_kernel<CIN, PRO, NARROW, MERGE>
+  PatchPersist,      // gather_patch_persist_kernel<CIN, PRO, NARROW, MERGE>
+  Mm16,              // gather_conv_pipe_kernel<..., MM16 = true>    (conv_mm16.hip)
+  Pipe,              // gather_conv_pipe_kernel<BN, ..., WRAPS, PRO, FAST, KS>
+  Dma,               // gather_conv_dma_kernel<BN, ...>
+  Kstep,             // gather_conv_kernel<BN, ..., SCALAR>
+};
+
+struct GatherChoice {
+  GForm form;
+  int rc;            // MPGAN_OK, or the status of a refusal whose message is `msg` (the launcher reports it)
+  const char* msg;
+  int code;          // mpgan_conv_variant's number (include/mpgan_hip.h); an Mm16 form keeps the code of the fp32 form
+                     //   it stands in for (same tiles, same rows)
+  int rows;          // partial rows of fused statistics / norm-backward sums the launch writes (0: the form has none)
+  int arg;           // template argument of a thin form (T, CQ, V, LANES or REVX) / of Patch3d (MM16) / of Kstep (SCALAR)
+  int bn, wraps, pro, ks;   // K-stepped forms: channel tile (select_variant), WRAPS, PRO, in-block split-K
+  bool fast;         // Pipe: the FAST instance
+  PatchLaunch pl;    // Patch / PatchPersist: the plan, its LDS bytes; PatchPersist: tiles and grid
+  int smem, ntiles, grid;
 };
 
 //   MERGE : one block walks ALL phases of its tile (strided backward-data / transposed convs): the
@@ -2287,9 +2214,7 @@ static bool patch_persist_plan(const GatherConv& p, const PatchLaunch& pl, Patch
     out->dbg = dbg_skip;
     static const int stag = dev_env("MPGAN_DBG_PATCH_STAGGER") ? atoi(dev_env("MPGAN_DBG_PATCH_STAGGER")) : 0;
     out->stagger = stag;
-    static void* zp = nullptr;          // address of the device-side zero page, looked up once
-    if (!zp && hipGetSymbolAddress(&zp, HIP_SYMBOL(g_patch_zero_page)) != hipSuccess) { zp = nullptr; return false; }
-    out->zero_page = zp;
+    out->zero_page = nullptr;           // set by the launcher (a runtime lookup: the plan stays a pure function)
   }
   const int nph = pl.merged ? p.nphase : 1;
   long floats = (long)out->w_floats + out->patch_floats + nph * 256 + 2 * p.Cin + 8 * p.Cin + 4;   // + fold scratch
@@ -2314,29 +2239,6 @@ static bool patch_persist_plan(const GatherConv& p, const PatchLaunch& pl, Patch
   if (g > *ntiles) g = *ntiles;
   *grid = g;
   return true;
-}
-
-static int launch_patch(const GatherConv& p, const PatchLaunch& pl, int smem, hipStream_t st) {
-  {
-    PatchLaunch pp;
-    int psmem = 0, ntiles = 0, grid = 0;
-    const bool persist = patch_persist_plan(p, pl, &pp, &psmem, &ntiles, &grid);
-    MPGAN_UNSUPPORTED(!persist && (p.fold.acc || p.stats_acc),
-                      "gather_patch: accumulator statistics / fold-on-load need the persistent patch kernel "
-                      "(mpgan_conv_acc_supported / mpgan_conv_fold_supported said otherwise?)");
-    if (persist) {
-      switch (p.Cin) {
-        case 16: return launch_patch_persist_cin<16>(p, pp, psmem, ntiles, grid, st);
-        case 32: return launch_patch_persist_cin<32>(p, pp, psmem, ntiles, grid, st);
-        default: return launch_patch_persist_cin<64>(p, pp, psmem, ntiles, grid, st);
-      }
-    }
-  }
-  switch (p.Cin) {
-    case 16: return launch_patch_cin<16>(p, pl, smem, st);
-    case 32: return launch_patch_cin<32>(p, pl, smem, st);
-    default: return launch_patch_cin<64>(p, pl, smem, st);
-  }
 }
 
 template <int BN, int TM, int TN, int WN, bool SCALAR>
@@ -2364,9 +2266,8 @@ static int launch_variant(const GatherConv& p, long maxM, hipStream_t st) {
   return check_launch("gather_conv");
 }
 
-// Kernel selection, shared by the launcher and mpgan_conv_variant():
-//   1 = thin_cin1, 2 = thin_cout1, 32/64/128 = gather_conv_kernel<BN>; mpgan_conv_variant() adds
-//   16 = gather_patch_kernel (see patch_plan).
+// First step of choose_gather: 1 = a thin (Cin == 1 / Cout == 1) kernel, else the channel tile BN = 32 / 64 / 128 of
+// the K-stepped kernels.
 
 static int select_variant(const GatherConv& p, long maxM, bool thin1, bool thin2) {
   if (thin1) return 1;
@@ -2484,36 +2385,29 @@ static int launch_dma_variant(const GatherConv& p, long maxM, hipStream_t st) {
 }
 
 template <int WRAPS, int PRO>
-static int launch_pipe_bn(const GatherConv& p, int variant, long maxM, hipStream_t st) {
+static int launch_pipe_bn(const GatherConv& p, const GatherChoice& c, long maxM, hipStream_t st) {
   if constexpr (WRAPS == 1 && PRO == 3) {
-    if (variant == 128 && fast_geometry(p, 128)) return launch_pipe_variant<128, 2, 2, 2, 1, 3, true>(p, maxM, st);
+    if (c.fast) return launch_pipe_variant<128, 2, 2, 2, 1, 3, true>(p, maxM, st);
   }
   if constexpr (WRAPS == 1 && PRO != 3) {
-    if (variant != 128 && pipe_wants_ksplit2(p, variant, maxM)) {
-      if (variant == 64) return launch_pipe_variant<64, 1, 2, 1, 1, PRO, false, 2>(p, maxM, st);
+    if (c.ks == 2) {
+      if (c.bn == 64) return launch_pipe_variant<64, 1, 2, 1, 1, PRO, false, 2>(p, maxM, st);
       return launch_pipe_variant<32, 1, 1, 1, 1, PRO, false, 2>(p, maxM, st);
     }
   }
-  if constexpr (WRAPS == 1 && PRO == 0) {
-    if (dma_form_ok(p, variant, maxM)) {
-      if (variant == 128) return launch_dma_variant<128, 2, 2, 2>(p, maxM, st);
-      if (variant == 64) return launch_dma_variant<64, 1, 2, 1>(p, maxM, st);
-      return launch_dma_variant<32, 1, 1, 1, 2>(p, maxM, st);
-    }
-  }
-  if (variant == 128) return launch_pipe_variant<128, 2, 2, 2, WRAPS, PRO>(p, maxM, st);
-  if (variant == 64) return launch_pipe_variant<64, 1, 2, 1, WRAPS, PRO>(p, maxM, st);
+  if (c.bn == 128) return launch_pipe_variant<128, 2, 2, 2, WRAPS, PRO>(p, maxM, st);
+  if (c.bn == 64) return launch_pipe_variant<64, 1, 2, 1, WRAPS, PRO>(p, maxM, st);
   return launch_pipe_variant<32, 1, 1, 1, WRAPS, PRO>(p, maxM, st);
 }
 
 template <int WRAPS>
-static int launch_pipe_pro(const GatherConv& p, int variant, long maxM, hipStream_t st) {
-  if (!p.pro.scale) return launch_pipe_bn<WRAPS, 0>(p, variant, maxM, st);
-  if (p.pro.n_stride == 0 && p.pro.act == MPGAN_ACT_LEAKY && !p.pro.slope_ptr && p.pro.slope >= 0.f &&
-      p.pro.slope <= 1.f)
-    return launch_pipe_bn<WRAPS, 3>(p, variant, maxM, st);
-  if (p.pro.n_stride == 0) return launch_pipe_bn<WRAPS, 1>(p, variant, maxM, st);
-  return launch_pipe_bn<WRAPS, 2>(p, variant, maxM, st);
+static int launch_pipe_pro(const GatherConv& p, const GatherChoice& c, long maxM, hipStream_t st) {
+  switch (c.pro) {
+    case 0: return launch_pipe_bn<WRAPS, 0>(p, c, maxM, st);
+    case 1: return launch_pipe_bn<WRAPS, 1>(p, c, maxM, st);
+    case 2: return launch_pipe_bn<WRAPS, 2>(p, c, maxM, st);
+    default: return launch_pipe_bn<WRAPS, 3>(p, c, maxM, st);
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -2799,7 +2693,7 @@ static P3Grid patch3d_grid(const GatherConv& p) {
   return P3Grid{(ph.Mz + P3_TZ - 1) / P3_TZ, (ph.My + P3_TY - 1) / P3_TY, (ph.Mx + P3_TX - 1) / P3_TX};
 }
 
-static int launch_patch3d(const GatherConv& p, hipStream_t st) {
+static int launch_patch3d(const GatherConv& p, const GatherChoice& c, hipStream_t st) {
   static bool attr_set = false;
   if (!attr_set) {
     hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(gather_patch3d_c16_kernel<true>),
@@ -2820,13 +2714,321 @@ static int launch_patch3d(const GatherConv& p, hipStream_t st) {
   const P3Grid tg = patch3d_grid(p);
   const long ntiles = (long)p.N * tg.tiles_z * tg.tiles_y * tg.tiles_x;
   dim3 grid((unsigned)(ntiles < 512 ? ntiles : 512));          // two resident blocks per CU, each walking its range of tiles
-  static const bool no_mm16 = dev_env("MPGAN_DBG_NO_MM16") != nullptr;
-  if (p.mm16 && !no_mm16) {
-    if (p.pro.scale) hipLaunchKernelGGL((gather_patch3d_c16_kernel<true, true>), grid, dim3(256), P3M_SMEM, st, p, tg);
+  if (c.arg) {
+    if (c.pro) hipLaunchKernelGGL((gather_patch3d_c16_kernel<true, true>), grid, dim3(256), P3M_SMEM, st, p, tg);
     else hipLaunchKernelGGL((gather_patch3d_c16_kernel<false, true>), grid, dim3(256), P3M_SMEM, st, p, tg);
-  } else if (p.pro.scale) hipLaunchKernelGGL(gather_patch3d_c16_kernel<true>, grid, dim3(256), P3_SMEM, st, p, tg);
+  } else if (c.pro) hipLaunchKernelGGL(gather_patch3d_c16_kernel<true>, grid, dim3(256), P3_SMEM, st, p, tg);
   else hipLaunchKernelGGL(gather_patch3d_c16_kernel<false>, grid, dim3(256), P3_SMEM, st, p, tg);
   return check_launch("gather_patch3d_c16");
+}
+
+#define CHOICE_REFUSE(cond, m)            \
+  do {                                    \
+    if (cond) {                           \
+      c.rc = MPGAN_ERR_UNSUPPORTED;       \
+      c.msg = (m);                        \
+      return c;                           \
+    }                                     \
+  } while (0)
+
+// The thin (VALU) forms: Cin == 1 or Cout == 1, and the two bf16 thin entries.
+static GatherChoice choose_thin(const GatherConv& p, long maxM, GatherChoice c) {
+  const int T = p.Kz * p.Ky * p.Kx;
+  const long block_rows = (maxM + 255) / 256 * p.nphase;   // one statistics row per 256-pixel block of a phase
+  if (p.out_bf16) {     // 1 -> C conv writing bf16 (D.conv1 of the bf16 path): all-channel kernel only
+    CHOICE_REFUSE(!(thin_cin1_ok(p) && (p.Cout == 16 || p.Cout == 32 || p.Cout == 64) && p.ldo % 4 == 0 &&
+                    (reinterpret_cast<uintptr_t>(p.out) & 7) == 0 && !p.resid && !p.tanh_out && !p.in_bf16 &&
+                    (!p.bias || (reinterpret_cast<uintptr_t>(p.bias) & 15) == 0)),
+                  "thin conv (bf16 out): needs Cin == 1, Cout in {16, 32, 64}, no resid/tanh, aligned output");
+    CHOICE_REFUSE(p.stats && p.Cout > 64, "thin conv (bf16 out): fused statistics up to 64 channels");
+    c.rows = (int)block_rows;
+    if (thin_cin1_rows_ok(p)) { c.form = GForm::ThinBf16OutRows; c.arg = T; return c; }
+    c.form = GForm::ThinBf16OutFull;
+    c.arg = p.Cout / 4;
+    return c;
+  }
+  if (p.in_bf16) {      // C -> 1 gather over bf16 data (backward-data of D.conv1 in the bf16 path)
+    if (thin_cout1_mfma_bf16_ok(p)) { c.form = GForm::ThinBf16InMfma; return c; }
+    const int lanes_b = p.Cin / 4;
+    CHOICE_REFUSE(!(p.Cout == 1 && !p.pro.scale && p.Cin % 4 == 0 && p.ldi % 4 == 0 &&
+                    (lanes_b == 4 || lanes_b == 8 || lanes_b == 16) && (reinterpret_cast<uintptr_t>(p.in) & 7) == 0 &&
+                    (long)T * p.Cin * 4 <= 48 * 1024 && !p.stats),
+                  "thin conv (bf16 in): needs Cout == 1 and 16, 32 or 64 gathered channels");
+    c.form = GForm::ThinBf16In;
+    c.arg = lanes_b;
+    return c;
+  }
+  if (thin_c1c1_ok(p)) { c.form = GForm::C1C1Rows4; c.arg = p.dstep[2] < 0; return c; }
+  if (thin_cin1_ok(p)) {
+    const bool v4 = (p.Cout % 4 == 0) && (p.ldo % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.out) & 15) == 0);
+    const bool full = v4 && (p.Cout == 16 || p.Cout == 32 || p.Cout == 64) &&
+                      (!p.bias || (reinterpret_cast<uintptr_t>(p.bias) & 15) == 0) &&
+                      (!p.resid || ((p.ldr % 4 == 0) && (reinterpret_cast<uintptr_t>(p.resid) & 15) == 0));
+    CHOICE_REFUSE((p.stats || p.stats_acc) && !(full && p.Cout <= 32),
+                  "thin conv: fused statistics need the all-channel kernel (Cout 16 or 32, 16-byte aligned output/bias)");
+    if (full) {
+      c.rows = (int)block_rows;
+      if (!p.stats && thin_cin1_rows_ok(p)) { c.form = GForm::Cin1Rows; c.arg = T; return c; }
+      c.form = GForm::Cin1Full;
+      c.arg = p.Cout / 4;
+      return c;
+    }
+    c.form = GForm::Cin1;
+    c.arg = v4 ? 4 : 1;
+    return c;
+  }
+  CHOICE_REFUSE((p.stats || p.stats_acc) && !convt_quad_ok(p),
+                "thin conv: fused statistics of a 1-channel output exist for ConvTranspose2d(C -> 1, k3 s2) only");
+  c.arg = p.Cin / 4;
+  if (convt_quad_ok(p)) {   // one statistics row per block
+    c.form = GForm::ConvtQuad;
+    c.rows = (int)(((long)p.N * p.Hi * p.Wi * c.arg + 255) / 256);
+  } else {
+    c.form = convt_oct_ok(p) ? GForm::ConvtOct : GForm::Cout1;
+  }
+  return c;
+}
+
+// The form, instance and statistics rows of this launch (or the refusal launch_gather reports).  Reads the
+// MPGAN_DBG_* form switches (through the predicates), so the DEV build's queries follow forced forms too.
+// Calls no runtime function and allocates nothing.
+static GatherChoice choose_gather(const GatherConv& p, long maxM) {
+  GatherChoice c{};
+  c.rc = MPGAN_OK;
+  if (p.out_bf16 || p.in_bf16) return choose_thin(p, maxM, c);
+  const int variant = select_variant(p, maxM, thin_cin1_ok(p), thin_cout1_ok(p));
+  c.code = c.bn = variant;
+  CHOICE_REFUSE(p.epi.scale && (p.stats || p.stats_acc || p.bwd.part || p.fold.acc || p.ksplit > 1 || p.in_bf16 || p.out_bf16),
+                "gather_conv: the epilogue activation goes with a plain forward (no fused statistics, split-K or bf16 storage)");
+  CHOICE_REFUSE(p.fold.acc && (p.pro.n_stride != 0 || p.fold.cstride < p.Cin),
+                "gather_conv: fold-on-load is per channel (BatchNorm) over >= Cin accumulator columns");
+  if (variant <= 2) {
+    CHOICE_REFUSE(p.fold.acc != nullptr, "thin conv: no fold-on-load");
+    CHOICE_REFUSE(p.bwd.part != nullptr, "thin conv: no fused norm-backward sums (mpgan_conv_bwd_stats_rows() == 0)");
+    return choose_thin(p, maxM, c);
+  }
+  if (patch3d_geom_ok(p)) {
+    if (patch3d_operands_ok(p)) {   // one statistics row per 2 x 8 x 8 tile
+      static const bool no_mm16 = dev_env("MPGAN_DBG_NO_MM16") != nullptr;
+      const P3Grid tg = patch3d_grid(p);
+      c.form = GForm::Patch3d;
+      c.code = 18;
+      c.rows = p.N * tg.tiles_z * tg.tiles_y * tg.tiles_x;
+      c.pro = p.pro.scale != nullptr;
+      c.arg = p.mm16 && !no_mm16;
+      return c;
+    }
+    // the caller sized its partial rows for one row per 2x8x8 tile (mpgan_conv_stats_rows): the K-stepped fallback
+    // would write a different number of them
+    CHOICE_REFUSE(p.stats != nullptr, "gather_conv: fused statistics of a 3-D patch-kernel geometry need 16-byte "
+                                      "aligned operands, a channel pitch % 4 == 0 and < 2^31 input elements");
+  }
+  if (patch_plan(p, &c.pl, &c.smem)) {
+    CHOICE_REFUSE(p.bwd.part != nullptr, "patch kernel: no fused norm-backward sums (mpgan_conv_bwd_stats_rows() == 0)");
+    const bool aligned = (p.ldi % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.in) & 15) == 0) &&
+                         ((reinterpret_cast<uintptr_t>(p.wp) & 15) == 0) &&
+                         (!p.pro.scale || ((reinterpret_cast<uintptr_t>(p.pro.scale) |
+                                            reinterpret_cast<uintptr_t>(p.pro.shift)) & 15) == 0);
+    if (aligned) {   // one statistics row per (tile, phase)
+      PatchLaunch pp;
+      int psmem = 0;
+      const bool persist = patch_persist_plan(p, c.pl, &pp, &psmem, &c.ntiles, &c.grid);
+      CHOICE_REFUSE(!persist && (p.fold.acc || p.stats_acc),
+                    "gather_patch: accumulator statistics / fold-on-load need the persistent patch kernel "
+                    "(mpgan_conv_acc_supported / mpgan_conv_fold_supported said otherwise?)");
+      c.code = c.pl.merged ? 17 : 16;
+      c.rows = c.pl.tiles_x * c.pl.tiles_y * p.N * p.nphase;
+      c.pro = p.pro.scale != nullptr;   // (never with the merged form: patch_plan)
+      c.form = persist ? GForm::PatchPersist : GForm::Patch;
+      if (persist) {
+        c.pl = pp;
+        c.smem = psmem;
+      }
+      return c;
+    }
+    CHOICE_REFUSE(p.stats != nullptr, "gather_conv: fused statistics of a patch-kernel geometry need 16-byte "
+                                      "aligned operands (the partial-row count differs otherwise)");
+  }
+  CHOICE_REFUSE(p.fold.acc != nullptr, "gather_conv: fold-on-load is served by the persistent patch kernel only");
+  c.rows = (int)phase_tile_rows(p, BM);   // the K-stepped forms: one row per (phase, m-tile)
+  c.ks = 1;
+  const bool vec = (p.Cin % 4 == 0) && (p.ldi % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.in) & 15) == 0) &&
+                   ((reinterpret_cast<uintptr_t>(p.wp) & 15) == 0) &&
+                   (!p.pro.scale || (((reinterpret_cast<uintptr_t>(p.pro.scale) |
+                                       reinterpret_cast<uintptr_t>(p.pro.shift)) & 15) == 0 &&
+                                     p.pro.n_stride % 4 == 0));
+  static const bool no_pipe = dev_env("MPGAN_DBG_NO_PIPE") != nullptr;
+  // the pipelined kernel addresses each operand as base + unsigned 32-bit byte offset
+  const bool small = (long)p.N * p.Di * p.Hi * p.Wi * p.ldi * 4 < (1L << 32) &&
+                     (long)p.Cout * p.Cin * p.Kz * p.Ky * p.Kx * 4 < (1L << 32) &&
+                     (long)p.N * (p.pro.n_stride > 0 ? p.pro.n_stride : 0) * 4 < (1L << 31);
+  const bool mm16 = p.mm16 && vec && small && mm16_gather_ok(p);   // bf16 matrix operands: same tiles, same rows
+  if (vec && small && (p.Cin % 32 == 0 || p.Cin == 16) && (!no_pipe || mm16)) {
+    c.form = GForm::Pipe;
+    c.wraps = p.Cin % 32 == 0 ? 1 : 2;
+    if (!p.pro.scale) c.pro = 0;
+    else if (p.pro.n_stride == 0 && p.pro.act == MPGAN_ACT_LEAKY && !p.pro.slope_ptr && p.pro.slope >= 0.f && p.pro.slope <= 1.f)
+      c.pro = 3;
+    else c.pro = p.pro.n_stride == 0 ? 1 : 2;
+    const bool ks2 = variant != 128 && pipe_wants_ksplit2(p, variant, maxM);   // (Cin % 32 == 0 only)
+    if (c.wraps == 1 && c.pro == 3 && variant == 128 && fast_geometry(p, 128)) {
+      c.fast = true;
+      c.code = 1128;
+    } else if (c.wraps == 1 && c.pro != 3 && ks2) {
+      c.ks = 2;
+      c.code = 2000 + variant;
+    } else if (c.wraps == 1 && c.pro == 0 && dma_form_ok(p, variant, maxM)) {
+      c.form = GForm::Dma;
+      c.code = 3000 + variant;
+    }
+    if (mm16) {
+      c.form = GForm::Mm16;
+      c.pro = p.pro.scale != nullptr;
+      c.ks = ks2 ? 2 : 1;
+      c.fast = false;
+    }
+    return c;
+  }
+  c.form = GForm::Kstep;
+  c.arg = !vec;
+  return c;
+}
+#undef CHOICE_REFUSE
+
+// Runs the instance a choice names.
+static int launch_chosen(const GatherConv& p, const GatherChoice& c, long maxM, hipStream_t st) {
+  if (c.rc != MPGAN_OK) {
+    set_error("%s", c.msg);
+    return c.rc;
+  }
+  const int T = p.Kz * p.Ky * p.Kx;
+  const dim3 block_grid((unsigned)((maxM + 255) / 256), 1, (unsigned)p.nphase);   // thin forms with a row per block
+  switch (c.form) {
+    case GForm::ThinBf16OutRows:
+    case GForm::Cin1Rows: {
+      const bool bf = c.form == GForm::ThinBf16OutRows;
+      if (bf && T == 9) hipLaunchKernelGGL((thin_cin1_rows_kernel<9, true>), block_grid, dim3(256), 0, st, p);
+      else if (bf) hipLaunchKernelGGL((thin_cin1_rows_kernel<27, true>), block_grid, dim3(256), 0, st, p);
+      else if (T == 9) hipLaunchKernelGGL((thin_cin1_rows_kernel<9, false>), block_grid, dim3(256), 0, st, p);
+      else hipLaunchKernelGGL((thin_cin1_rows_kernel<27, false>), block_grid, dim3(256), 0, st, p);
+      return check_launch(bf ? "thin_cin1_rows_bf16" : "thin_cin1_rows");
+    }
+    case GForm::ThinBf16OutFull: {
+      const size_t smem = ((size_t)((T * p.Cout + 3) & ~3) + (p.stats ? 256 * (size_t)(p.Cout + 1) : 0)) * sizeof(float);
+      if (c.arg == 4) hipLaunchKernelGGL((thin_cin1_full_kernel<4, true>), block_grid, dim3(256), smem, st, p);
+      else if (c.arg == 8) hipLaunchKernelGGL((thin_cin1_full_kernel<8, true>), block_grid, dim3(256), smem, st, p);
+      else {
+        static bool attr_set = false;
+        if (!attr_set) {
+          hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(thin_cin1_full_kernel<16, true>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+          if (e != hipSuccess) { set_error("thin_cin1_full: hipFuncSetAttribute: %s", hipGetErrorString(e)); return MPGAN_ERR_HIP; }
+          attr_set = true;
+        }
+        hipLaunchKernelGGL((thin_cin1_full_kernel<16, true>), block_grid, dim3(256), smem, st, p);
+      }
+      return check_launch("thin_cin1_full_bf16");
+    }
+    case GForm::ThinBf16InMfma: return launch_thin_cout1_mfma_bf16(p, st);
+    case GForm::ThinBf16In: {
+      dim3 grid((unsigned)((maxM * c.arg + 255) / 256), 1, (unsigned)p.nphase);
+      const size_t smem = (size_t)T * p.Cin * sizeof(float);
+      if (c.arg == 4) hipLaunchKernelGGL((thin_cout1_kernel<4, true>), grid, dim3(256), smem, st, p);
+      else if (c.arg == 8) hipLaunchKernelGGL((thin_cout1_kernel<8, true>), grid, dim3(256), smem, st, p);
+      else hipLaunchKernelGGL((thin_cout1_kernel<16, true>), grid, dim3(256), smem, st, p);
+      return check_launch("thin_cout1_bf16");
+    }
+    case GForm::C1C1Rows4: {
+      const Phase& ph0 = p.ph[0];
+      const long threads4 = (long)p.N * ph0.Mz * ph0.My * ((ph0.Mx + 3) / 4);
+      if (c.arg) hipLaunchKernelGGL(thin_c1c1_rows4_kernel<true>, dim3((unsigned)((threads4 + 255) / 256)), dim3(256), 0, st, p);
+      else hipLaunchKernelGGL(thin_c1c1_rows4_kernel<false>, dim3((unsigned)((threads4 + 255) / 256)), dim3(256), 0, st, p);
+      return check_launch("thin_c1c1_rows4");
+    }
+    case GForm::Cin1Full: {
+      const size_t smem = ((size_t)((T * p.Cout + 3) & ~3) + ((p.stats || p.stats_acc) ? 256 * (size_t)(p.Cout + 1) : 0)) * sizeof(float);
+      if (c.arg == 4) hipLaunchKernelGGL(thin_cin1_full_kernel<4>, block_grid, dim3(256), smem, st, p);
+      else if (c.arg == 8) hipLaunchKernelGGL(thin_cin1_full_kernel<8>, block_grid, dim3(256), smem, st, p);
+      else hipLaunchKernelGGL(thin_cin1_full_kernel<16>, block_grid, dim3(256), smem, st, p);
+      return check_launch("thin_cin1_full");
+    }
+    case GForm::Cin1: {
+      const int CQ = (p.Cout + c.arg - 1) / c.arg;
+      dim3 grid((unsigned)((maxM * CQ + 255) / 256), 1, (unsigned)p.nphase);
+      const size_t smem = (size_t)T * CQ * c.arg * sizeof(float);
+      if (c.arg == 4) hipLaunchKernelGGL(thin_cin1_kernel<4>, grid, dim3(256), smem, st, p);
+      else hipLaunchKernelGGL(thin_cin1_kernel<1>, grid, dim3(256), smem, st, p);
+      return check_launch("thin_cin1");
+    }
+    case GForm::ConvtQuad: {
+      dim3 qgrid((unsigned)(((long)p.N * p.Hi * p.Wi * c.arg + 255) / 256));
+      const size_t qsmem = (size_t)9 * p.Cin * sizeof(float);
+      if (c.arg == 4) hipLaunchKernelGGL(convt_quad_cout1_kernel<4>, qgrid, dim3(256), qsmem, st, p);
+      else if (c.arg == 8) hipLaunchKernelGGL(convt_quad_cout1_kernel<8>, qgrid, dim3(256), qsmem, st, p);
+      else hipLaunchKernelGGL(convt_quad_cout1_kernel<16>, qgrid, dim3(256), qsmem, st, p);
+      return check_launch("convt_quad_cout1");
+    }
+    case GForm::ConvtOct: {
+      dim3 ogrid((unsigned)(((long)p.N * p.Di * p.Hi * p.Wi * c.arg + 255) / 256));
+      const size_t osmem = (size_t)27 * p.Cin * sizeof(float);
+      if (c.arg == 4) hipLaunchKernelGGL(convt_oct_cout1_kernel<4>, ogrid, dim3(256), osmem, st, p);
+      else if (c.arg == 8) hipLaunchKernelGGL(convt_oct_cout1_kernel<8>, ogrid, dim3(256), osmem, st, p);
+      else hipLaunchKernelGGL(convt_oct_cout1_kernel<16>, ogrid, dim3(256), osmem, st, p);
+      return check_launch("convt_oct_cout1");
+    }
+    case GForm::Cout1: {
+      dim3 grid((unsigned)((maxM * c.arg + 255) / 256), 1, (unsigned)p.nphase);
+      const size_t smem = (size_t)T * p.Cin * sizeof(float);
+      switch (c.arg) {
+        case 1: hipLaunchKernelGGL(thin_cout1_kernel<1>, grid, dim3(256), smem, st, p); break;
+        case 2: hipLaunchKernelGGL(thin_cout1_kernel<2>, grid, dim3(256), smem, st, p); break;
+        case 4: hipLaunchKernelGGL(thin_cout1_kernel<4>, grid, dim3(256), smem, st, p); break;
+        case 8: hipLaunchKernelGGL(thin_cout1_kernel<8>, grid, dim3(256), smem, st, p); break;
+        case 16: hipLaunchKernelGGL(thin_cout1_kernel<16>, grid, dim3(256), smem, st, p); break;
+        case 32: hipLaunchKernelGGL(thin_cout1_kernel<32>, grid, dim3(256), smem, st, p); break;
+        default: hipLaunchKernelGGL(thin_cout1_kernel<64>, grid, dim3(256), smem, st, p); break;
+      }
+      return check_launch("thin_cout1");
+    }
+    case GForm::Patch3d: return launch_patch3d(p, c, st);
+    case GForm::Patch:
+      switch (p.Cin) {
+        case 16: return launch_patch_cin<16>(p, c.pl, c.smem, st);
+        case 32: return launch_patch_cin<32>(p, c.pl, c.smem, st);
+        default: return launch_patch_cin<64>(p, c.pl, c.smem, st);
+      }
+    case GForm::PatchPersist: {
+      static void* zp = nullptr;          // address of the device-side zero page, looked up once
+      if (!zp && hipGetSymbolAddress(&zp, HIP_SYMBOL(g_patch_zero_page)) != hipSuccess) {
+        zp = nullptr;
+        set_error("gather_patch_persist: no address for the zero page");
+        return MPGAN_ERR_HIP;
+      }
+      PatchLaunch pl = c.pl;
+      pl.zero_page = zp;
+      switch (p.Cin) {
+        case 16: return launch_patch_persist_cin<16>(p, pl, c.smem, c.ntiles, c.grid, st);
+        case 32: return launch_patch_persist_cin<32>(p, pl, c.smem, c.ntiles, c.grid, st);
+        default: return launch_patch_persist_cin<64>(p, pl, c.smem, c.ntiles, c.grid, st);
+      }
+    }
+    case GForm::Mm16: return launch_gather_mm16(p, c.bn, c.wraps, c.pro, c.ks, maxM, st);
+    case GForm::Pipe: return c.wraps == 1 ? launch_pipe_pro<1>(p, c, maxM, st) : launch_pipe_pro<2>(p, c, maxM, st);
+    case GForm::Dma:
+      if (c.bn == 128) return launch_dma_variant<128, 2, 2, 2>(p, maxM, st);
+      if (c.bn == 64) return launch_dma_variant<64, 1, 2, 1>(p, maxM, st);
+      return launch_dma_variant<32, 1, 1, 1, 2>(p, maxM, st);
+    case GForm::Kstep:
+      if (c.arg) {
+        if (c.bn == 128) return launch_variant<128, 2, 2, 2, true>(p, maxM, st);
+        if (c.bn == 64) return launch_variant<64, 1, 2, 1, true>(p, maxM, st);
+        return launch_variant<32, 1, 1, 1, true>(p, maxM, st);
+      }
+      if (c.bn == 128) return launch_variant<128, 2, 2, 2, false>(p, maxM, st);
+      if (c.bn == 64) return launch_variant<64, 1, 2, 1, false>(p, maxM, st);
+      return launch_variant<32, 1, 1, 1, false>(p, maxM, st);
+  }
+  return MPGAN_ERR_UNSUPPORTED;
 }
 
 #ifdef MPGAN_STAMPS
@@ -2853,70 +3055,12 @@ static int launch_gather(const GatherConv& p, hipStream_t st) {
                       maxM < (1L << 31) - 256,
                   "gather_conv: more than 2^31 pixels");
   MPGAN_CHECK_ARG((long)p.Cout * p.Cin * p.Kz * p.Ky * p.Kx < (1L << 31), "gather_conv: weight larger than 2^31");
-  const int variant = select_variant(p, maxM, thin_cin1_ok(p), thin_cout1_ok(p));
-  MPGAN_UNSUPPORTED(p.epi.scale && (p.stats || p.stats_acc || p.bwd.part || p.fold.acc || p.ksplit > 1 || p.in_bf16 || p.out_bf16),
-                    "gather_conv: the epilogue activation goes with a plain forward (no fused statistics, split-K or bf16 storage)");
-  MPGAN_UNSUPPORTED(p.fold.acc && (p.pro.n_stride != 0 || p.fold.cstride < p.Cin),
-                    "gather_conv: fold-on-load is per channel (BatchNorm) over >= Cin accumulator columns");
-  if (variant <= 2) {
-    MPGAN_UNSUPPORTED(p.fold.acc != nullptr, "thin conv: no fold-on-load");
-    MPGAN_UNSUPPORTED(p.bwd.part != nullptr, "thin conv: no fused norm-backward sums (mpgan_conv_bwd_stats_rows() == 0)");
-    return launch_thin(p, maxM, st);
-  }
-  if (patch3d_geom_ok(p)) {
-    if (patch3d_operands_ok(p)) return launch_patch3d(p, st);
-    // the caller sized its partial rows for one row per 2x8x8 tile (mpgan_conv_stats_rows): the K-stepped fallback
-    // would write a different number of them
-    MPGAN_UNSUPPORTED(p.stats != nullptr, "gather_conv: fused statistics of a 3-D patch-kernel geometry need 16-byte "
-                                          "aligned operands, a channel pitch % 4 == 0 and < 2^31 input elements");
-  }
-  {
-    PatchLaunch pl;
-    int smem = 0;
-    if (patch_plan(p, &pl, &smem)) {
-      MPGAN_UNSUPPORTED(p.bwd.part != nullptr, "patch kernel: no fused norm-backward sums (mpgan_conv_bwd_stats_rows() == 0)");
-      const bool aligned = (p.ldi % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.in) & 15) == 0) &&
-                           ((reinterpret_cast<uintptr_t>(p.wp) & 15) == 0) &&
-                           (!p.pro.scale || ((reinterpret_cast<uintptr_t>(p.pro.scale) |
-                                              reinterpret_cast<uintptr_t>(p.pro.shift)) & 15) == 0);
-      if (aligned) return launch_patch(p, pl, smem, st);
-      MPGAN_UNSUPPORTED(p.stats != nullptr, "gather_conv: fused statistics of a patch-kernel geometry need 16-byte "
-                                            "aligned operands (the partial-row count differs otherwise)");
-    }
-  }
-  MPGAN_UNSUPPORTED(p.fold.acc != nullptr, "gather_conv: fold-on-load is served by the persistent patch kernel only");
-  const bool vec = (p.Cin % 4 == 0) && (p.ldi % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.in) & 15) == 0) &&
-                   ((reinterpret_cast<uintptr_t>(p.wp) & 15) == 0) &&
-                   (!p.pro.scale || (((reinterpret_cast<uintptr_t>(p.pro.scale) |
-                                       reinterpret_cast<uintptr_t>(p.pro.shift)) & 15) == 0 &&
-                                     p.pro.n_stride % 4 == 0));
-  static const bool no_pipe = dev_env("MPGAN_DBG_NO_PIPE") != nullptr;
-  // the pipelined kernel addresses each operand as base + unsigned 32-bit byte offset
-  const bool small = (long)p.N * p.Di * p.Hi * p.Wi * p.ldi * 4 < (1L << 32) &&
-                     (long)p.Cout * p.Cin * p.Kz * p.Ky * p.Kx * 4 < (1L << 32) &&
-                     (long)p.N * (p.pro.n_stride > 0 ? p.pro.n_stride : 0) * 4 < (1L << 31);
-  if (p.mm16 && vec && small && mm16_gather_ok(p))       // bf16 matrix operands (conv_mm16.hip): same tiles, same rows
-    return launch_gather_mm16(p, variant, variant != 128 && pipe_wants_ksplit2(p, variant, maxM), maxM, st);
-  if (vec && !no_pipe && small) {
-    if (p.Cin % 32 == 0) return launch_pipe_pro<1>(p, variant, maxM, st);
-    if (p.Cin == 16) return launch_pipe_pro<2>(p, variant, maxM, st);
-  }
-  if (vec) {
-    if (variant == 128) return launch_variant<128, 2, 2, 2, false>(p, maxM, st);
-    if (variant == 64) return launch_variant<64, 1, 2, 1, false>(p, maxM, st);
-    return launch_variant<32, 1, 1, 1, false>(p, maxM, st);
-  }
-  if (variant == 128) return launch_variant<128, 2, 2, 2, true>(p, maxM, st);
-  if (variant == 64) return launch_variant<64, 1, 2, 1, true>(p, maxM, st);
-  return launch_variant<32, 1, 1, 1, true>(p, maxM, st);
+  return launch_chosen(p, choose_gather(p, maxM), maxM, st);
 }
 
 }  // namespace mpgan
 
 using namespace mpgan;
-
-extern "C" int32_t mpgan_conv_variant(const mpgan_conv_geom* g, int32_t backward_data, int32_t has_prologue);
-extern "C" int32_t mpgan_conv_acc_supported(const mpgan_conv_geom* g, int32_t has_prologue);
 
 static void build_for_forward(GatherConv& p, const mpgan_conv_geom* g) {
   set_geom_flags(p, g);
@@ -2966,36 +3110,67 @@ extern "C" int64_t mpgan_conv_splitk_workspace(const mpgan_conv_geom* g) {
   return (int64_t)ks * g->n * g->out_dhw[0] * g->out_dhw[1] * g->out_dhw[2] * g->cout * (int64_t)sizeof(float);
 }
 
-extern "C" int32_t mpgan_conv_stats_rows(const mpgan_conv_geom* g, int32_t has_prologue) {
-  const int v = mpgan_conv_variant(g, 0, has_prologue);
-  if (v == 1 && (g->cout == 16 || g->cout == 32)) {   // all-channel 1 -> C stencil: one partial row per 256-pixel block
-    GatherConv p1{};
-    build_for_forward(p1, g);
-    return (int32_t)((max_phase_pixels(p1) + 255) / 256) * p1.nphase;
-  }
-  if (v == 2) {           // quad kernel of ConvTranspose2d(C -> 1, k3 s2): one partial row per block
-    static const float dummy16[4] __attribute__((aligned(16))) = {0, 0, 0, 0};
-    GatherConv p2{};
-    build_for_forward(p2, g);
-    p2.in = dummy16;
-    p2.ldi = g->cin;
-    p2.pro = make_pro(nullptr);
-    if (!convt_quad_ok(p2)) return 0;
-    return (int32_t)(((long)p2.N * p2.Hi * p2.Wi * (p2.Cin / 4) + 255) / 256);
-  }
-  if (v < 16) return 0;   // other thin VALU kernels (or invalid geometry): no fused statistics
+// What a geometry query decides from: the GatherConv an entry point builds for this geometry and direction, with
+// compact pitches and 16-byte aligned stand-in operands (never dereferenced).  pro_code: 0 no prologue, 1 per-channel
+// scale / shift (BatchNorm), 2 per-(sample, channel) scale / shift (InstanceNorm), 3 per-channel with a LeakyReLU of
+// host slope in [0, 1].
+alignas(16) static float g_standin[4];
+static GatherConv standin_conv(const mpgan_conv_geom* g, bool backward_data, int pro_code) {
   GatherConv p{};
-  build_for_forward(p, g);
-  if (v == 16 || v == 17) {   // patch kernel: one partial row per (tile, phase)
-    PatchLaunch pl;
-    patch_plan(p, &pl, nullptr);
-    return (int32_t)(pl.tiles_x * pl.tiles_y * p.N * p.nphase);
-  }
-  if (v == 18) {              // 3-D patch kernel: one partial row per 2 x 8 x 8 tile
-    const P3Grid tg = patch3d_grid(p);
-    return (int32_t)(p.N * tg.tiles_z * tg.tiles_y * tg.tiles_x);
-  }
-  return (int32_t)phase_tile_rows(p, BM);
+  p.in = g_standin; p.wp = g_standin; p.out = g_standin;
+  p.pro = make_pro(nullptr);
+  p.fold = make_fold(nullptr);
+  if (pro_code) p.pro.scale = p.pro.shift = g_standin;
+  if (pro_code == 3) { p.pro.act = MPGAN_ACT_LEAKY; p.pro.slope = 0.2f; }
+  set_geom_flags(p, g);
+  const int cg = backward_data ? g->cout : g->cin, cp = backward_data ? g->cin : g->cout;
+  const int32_t* gd = backward_data ? g->out_dhw : g->in_dhw;
+  const int32_t* pd = backward_data ? g->in_dhw : g->out_dhw;
+  if (backward_data == !g->transposed) build_transposed(p, g->n, gd, cg, pd, cp, g->k, g->stride, g->pad);
+  else build_forward(p, g->n, gd, cg, pd, cp, g->k, g->stride, g->pad);
+  p.ldi = cg; p.ldo = cp; p.ldr = cp;
+  if (pro_code == 2) p.pro.n_stride = cg;
+  return p;
+}
+
+static GatherChoice choose_standin(const GatherConv& p) { return choose_gather(p, max_phase_pixels(p)); }
+
+extern "C" int32_t mpgan_conv_variant(const mpgan_conv_geom* g, int32_t backward_data, int32_t has_prologue) {
+  if (check_geom(g)) return -1;
+  return choose_standin(standin_conv(g, backward_data, has_prologue)).code;
+}
+
+extern "C" int32_t mpgan_conv_stats_rows(const mpgan_conv_geom* g, int32_t has_prologue) {
+  if (check_geom(g)) return 0;
+  GatherConv p = standin_conv(g, false, has_prologue);
+  p.stats = g_standin;
+  const GatherChoice c = choose_standin(p);
+  return c.rc == MPGAN_OK ? c.rows : 0;
+}
+
+extern "C" int32_t mpgan_conv_acc_supported(const mpgan_conv_geom* g, int32_t has_prologue) {
+  if (check_geom(g)) return 0;
+  GatherConv p = standin_conv(g, false, has_prologue);
+  p.stats_acc = reinterpret_cast<long long*>(g_standin);
+  p.acc_rep = 1;
+  return choose_standin(p).rc == MPGAN_OK ? 1 : 0;
+}
+
+extern "C" int32_t mpgan_conv_fold_supported(const mpgan_conv_geom* g) {
+  if (check_geom(g)) return 0;
+  GatherConv p = standin_conv(g, false, 1);
+  p.fold.acc = reinterpret_cast<const long long*>(g_standin);
+  p.fold.rep = 1;
+  p.fold.cstride = g->cin;
+  return choose_standin(p).rc == MPGAN_OK ? 1 : 0;
+}
+
+// Partial rows mpgan_conv_backward_data_stats leaves for this geometry; 0 = that launch is served by a thin or
+// patch kernel, which has no fused sums (run mpgan_norm_bwd_reduce instead).  The K-stepped forms fuse them.
+extern "C" int32_t mpgan_conv_bwd_stats_rows(const mpgan_conv_geom* g) {
+  if (check_geom(g)) return 0;
+  const GatherChoice c = choose_standin(standin_conv(g, true, 0));
+  return c.rc == MPGAN_OK && c.form >= GForm::Mm16 ? c.rows : 0;
 }
 
 extern "C" int mpgan_conv_forward_fold(const mpgan_conv_geom* g, const float* x, int32_t ldx, const float* w_packed,
@@ -3067,42 +3242,6 @@ extern "C" int mpgan_conv_forward(const mpgan_conv_geom* g, const float* x, int3
                                  0, y, ldy, stream);
 }
 
-// Which kernel would serve this forward conv: shared by the two queries below (geometry only, aligned operands).
-static int forward_kernel_class(const mpgan_conv_geom* g, int32_t has_prologue, bool* persist) {
-  *persist = false;
-  const int v = mpgan_conv_variant(g, 0, has_prologue);
-  if (v == 16 || v == 17) {
-    GatherConv p{};
-    static const float dummy[4] __attribute__((aligned(16))) = {0, 0, 0, 0};
-    p.in = dummy;
-    p.pro = make_pro(nullptr);
-    if (has_prologue) p.pro.scale = dummy;
-    build_for_forward(p, g);
-    p.ldi = g->cin;
-    if (has_prologue == 2) p.pro.n_stride = g->cin;
-    PatchLaunch pl, pp;
-    int smem = 0, psmem = 0, ntiles = 0, grid = 0;
-    if (patch_plan(p, &pl, &smem)) *persist = patch_persist_plan(p, pl, &pp, &psmem, &ntiles, &grid);
-  }
-  return v;
-}
-
-extern "C" int32_t mpgan_conv_acc_supported(const mpgan_conv_geom* g, int32_t has_prologue) {
-  bool persist;
-  const int v = forward_kernel_class(g, has_prologue, &persist);
-  if (v < 0) return 0;
-  if (v == 16 || v == 17) return persist ? 1 : 0;
-  if (v == 1) return (g->cout == 16 || g->cout == 32) ? 1 : 0;
-  if (v == 2) return mpgan_conv_stats_rows(g, has_prologue) > 0 ? 1 : 0;      // the quad kernel of ConvTranspose2d(C -> 1)
-  return 1;                                                                  // K-stepped kernels share conv_epilogue
-}
-
-extern "C" int32_t mpgan_conv_fold_supported(const mpgan_conv_geom* g) {
-  bool persist;
-  const int v = forward_kernel_class(g, 1, &persist);
-  return v == 16 && persist ? 1 : 0;
-}
-
 // y = conv(prologue(x)) + bias with the K axis split over blocks (small output grids).
 extern "C" int mpgan_conv_forward_splitk(const mpgan_conv_geom* g, const float* x, int32_t ldx, const float* w_packed,
                                          const float* bias, const mpgan_prologue* pro, void* workspace,
@@ -3155,18 +3294,6 @@ extern "C" int mpgan_conv_backward_data(const mpgan_conv_geom* g, const float* d
   return launch_gather(p, (hipStream_t)stream);
 }
 
-// Partial rows mpgan_conv_backward_data_stats leaves for this geometry; 0 = that launch is served by a thin or
-// patch kernel, which has no fused sums (run mpgan_norm_bwd_reduce instead).
-extern "C" int32_t mpgan_conv_bwd_stats_rows(const mpgan_conv_geom* g) {
-  const int v = mpgan_conv_variant(g, 1, 0);
-  if (v < 32 || v == 1128) return 0;
-  GatherConv p{};
-  set_geom_flags(p, g);
-  if (!g->transposed) build_transposed(p, g->n, g->out_dhw, g->cout, g->in_dhw, g->cin, g->k, g->stride, g->pad);
-  else build_forward(p, g->n, g->out_dhw, g->cout, g->in_dhw, g->cin, g->k, g->stride, g->pad);
-  return (int32_t)phase_tile_rows(p, BM);
-}
-
 // mpgan_conv_backward_data + the reduce pass of the norm layer in front of this conv's input, in one launch:
 // dx is the gradient w.r.t. a = act(scale * z + shift); partials[rows][3][Cin] receive the sums mpgan_norm_bwd_reduce
 // would form from dx and z (BatchNorm: scale / shift / mean / invstd hold Cin values; any number of rows feeds
@@ -3197,44 +3324,6 @@ extern "C" int mpgan_conv_backward_data_stats(const mpgan_conv_geom* g, const fl
   return launch_gather(p, (hipStream_t)stream);
 }
 
-extern "C" int32_t mpgan_conv_variant(const mpgan_conv_geom* g, int32_t backward_data, int32_t has_prologue) {
-  if (check_geom(g)) return -1;
-  GatherConv p{};
-  static const float dummy[4] = {0, 0, 0, 0};
-  p.in = dummy;  // 16-byte aligned stand-ins: only geometry drives the choice
-  p.pro = make_pro(nullptr);
-  if (has_prologue) p.pro.scale = dummy;
-  set_geom_flags(p, g);
-  const int cg = backward_data ? g->cout : g->cin, cp = backward_data ? g->cin : g->cout;
-  const int32_t* gd = backward_data ? g->out_dhw : g->in_dhw;
-  const int32_t* pd = backward_data ? g->in_dhw : g->out_dhw;
-  if (backward_data) {
-    if (!g->transposed) build_transposed(p, g->n, gd, cg, pd, cp, g->k, g->stride, g->pad);
-    else build_forward(p, g->n, gd, cg, pd, cp, g->k, g->stride, g->pad);
-  } else {
-    if (!g->transposed) build_forward(p, g->n, gd, cg, pd, cp, g->k, g->stride, g->pad);
-    else build_transposed(p, g->n, gd, cg, pd, cp, g->k, g->stride, g->pad);
-  }
-  p.ldi = cg;
-  if (has_prologue == 2) p.pro.n_stride = cg;   // per-(sample, channel) scale/shift (InstanceNorm)
-  const int T = p.Kz * p.Ky * p.Kx;
-  const bool t1 = p.Cin == 1 && !p.pro.scale && (long)T * ((p.Cout + 3) / 4 * 4) * 4 <= 48 * 1024;
-  const int lanes = p.Cin / 4;
-  const bool t2 = p.Cout == 1 && !p.pro.scale && p.Cin % 4 == 0 && lanes >= 1 && lanes <= 64 &&
-                  (lanes & (lanes - 1)) == 0 && (long)T * p.Cin * 4 <= 48 * 1024;
-  const int v = select_variant(p, max_phase_pixels(p), t1, t2);
-  if (v > 2 && patch3d_geom_ok(p)) return 18;                                     // 3-D patch kernel, 16 -> 16 channels
-  if (v > 2) {
-    PatchLaunch pl;
-    if (patch_plan(p, &pl, nullptr)) return pl.merged ? 17 : 16;
-  }
-  if (v == 128 && has_prologue == 3 && fast_geometry(p, 128)) return 1128;
-  if ((v == 32 || v == 64) && p.Cin % 32 == 0 && has_prologue != 3 && pipe_wants_ksplit2(p, v, max_phase_pixels(p)))
-    return 2000 + v;
-  if (!has_prologue && dma_form_ok(p, v, max_phase_pixels(p))) return 3000 + v;   // gather_conv_dma_kernel
-  return v;
-}
-
 
 // ---- thin layers of the bf16 path (D.conv1: 1 -> 64): fp32 image in, bf16 activations out, and back ----
 extern "C" int mpgan_conv_forward_f32_to_bf16(const mpgan_conv_geom* g, const float* x, int32_t ldx,
@@ -3254,7 +3343,7 @@ extern "C" int mpgan_conv_forward_f32_to_bf16(const mpgan_conv_geom* g, const fl
   build_forward(p, g->n, g->in_dhw, g->cin, g->out_dhw, g->cout, g->k, g->stride, g->pad);
   const long maxM = max_phase_pixels(p);
   MPGAN_CHECK_ARG(maxM < (1L << 31) - 256, "conv_forward_f32_to_bf16: more than 2^31 pixels");
-  return launch_thin(p, maxM, (hipStream_t)stream);
+  return launch_chosen(p, choose_gather(p, maxM), maxM, (hipStream_t)stream);
 }
 
 extern "C" int mpgan_conv_backward_data_bf16_to_f32(const mpgan_conv_geom* g, const void* dy, int32_t lddy,
@@ -3272,5 +3361,5 @@ extern "C" int mpgan_conv_backward_data_bf16_to_f32(const mpgan_conv_geom* g, co
   build_transposed(p, g->n, g->out_dhw, g->cout, g->in_dhw, g->cin, g->k, g->stride, g->pad);
   const long maxM = max_phase_pixels(p);
   MPGAN_CHECK_ARG(maxM < (1L << 31) - 256, "conv_backward_data_bf16_to_f32: more than 2^31 pixels");
-  return launch_thin(p, maxM, (hipStream_t)stream);
+  return launch_chosen(p, choose_gather(p, maxM), maxM, (hipStream_t)stream);
 }

@@ -60,10 +60,11 @@ bool mm16_gather_ok(const GatherConv& p) {
          !p.stats_acc && p.ksplit <= 1 && !p.in_bf16 && !p.out_bf16;
 }
 
-int launch_gather_mm16(const GatherConv& p, int variant, bool ksplit2, long maxM, hipStream_t st) {
-  if (p.Cin % 32 == 0)
-    return p.pro.scale ? launch_mm16_bn<1, 1>(p, variant, ksplit2, maxM, st) : launch_mm16_bn<1, 0>(p, variant, ksplit2, maxM, st);
-  return p.pro.scale ? launch_mm16_bn<2, 1>(p, variant, false, maxM, st) : launch_mm16_bn<2, 0>(p, variant, false, maxM, st);
+// The instance of an Mm16 choice (choose_gather, conv_igemm.hip): channel tile bn, WRAPS, PRO 0 / 1, in-block split-K ks.
+int launch_gather_mm16(const GatherConv& p, int bn, int wraps, int pro, int ks, long maxM, hipStream_t st) {
+  if (wraps == 1)
+    return pro ? launch_mm16_bn<1, 1>(p, bn, ks == 2, maxM, st) : launch_mm16_bn<1, 0>(p, bn, ks == 2, maxM, st);
+  return pro ? launch_mm16_bn<2, 1>(p, bn, false, maxM, st) : launch_mm16_bn<2, 0>(p, bn, false, maxM, st);
 }
 
 // ---- weight gradient -----------------------------------------------------------------------------------------------
