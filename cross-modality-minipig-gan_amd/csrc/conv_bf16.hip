@@ -478,25 +478,36 @@ __global__ __launch_bounds__(NW * 64, 1) void gather_conv_bf16_kernel(const Gath
   }
 }
 
-template <int BN, bool MASK, int NW>
-static int hb_launch(const GatherConv& p, long maxM, hipStream_t st) {
-  auto kern = gather_conv_bf16_kernel<BN, MASK, NW>;
-  constexpr int smem = HbTile<BN, NW>::SMEM;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (e != hipSuccess) {
-      set_error("gather_conv_bf16: hipFuncSetAttribute(%d): %s", smem, hipGetErrorString(e));
-      return MPGAN_ERR_HIP;
-    }
-    attr_set = true;
-  }
+// The one-time preamble of every bf16 gather launcher: the dynamic-LDS limit of the instance KERN and (once for the
+// family) the MPGAN_DBG_HB what-if bits, copied to the device.
+static void hb_copy_dbg() {
   static int dbg_set = -1;
   if (dbg_set < 0) {
     const char* e = dev_env("MPGAN_DBG_HB");
     dbg_set = e ? atoi(e) : 0;
     if (dbg_set) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_hb_dbg), &dbg_set, sizeof(int));
   }
+}
+template <auto KERN>
+static int hb_prepare(int smem, const char* name) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    if (e != hipSuccess) {
+      set_error("%s: hipFuncSetAttribute(%d): %s", name, smem, hipGetErrorString(e));
+      return MPGAN_ERR_HIP;
+    }
+    attr_set = true;
+  }
+  hb_copy_dbg();
+  return MPGAN_OK;
+}
+
+template <int BN, bool MASK, int NW>
+static int hb_launch(const GatherConv& p, long maxM, hipStream_t st) {
+  auto kern = gather_conv_bf16_kernel<BN, MASK, NW>;
+  constexpr int smem = HbTile<BN, NW>::SMEM;
+  if (const int rc = hb_prepare<gather_conv_bf16_kernel<BN, MASK, NW>>(smem, "gather_conv_bf16")) return rc;
   GatherConv q = p;
   const long pairs = set_tile_grid(q, HB_BM);
   q.ntiles = (p.Cout + BN - 1) / BN;
@@ -894,7 +905,7 @@ __global__ __launch_bounds__(512, 1) void gather_conv_bf16_wide_kernel(const Gat
 
 // Which K-stepped form serves a gather: 0 = 256 x 128/64 tile (gather_conv_bf16_kernel), 1 = 256 x 256, 2 = 512 x 128,
 // 3 = 256 x 256 over the phase pairs of a strided backward-data gather (gather_conv_bf16_wide_kernel).  The wide forms need enough tiles to fill the chip twice over; MPGAN_DBG_HB_WIDE=0
-// turns them off (A/B runs).  mpgan_conv_stats_rows_bf16 follows the same choice (rows = phases x m-tiles).
+// turns them off (A/B runs).  One step of choose_bf16.
 // (the threshold is the geometry's own `min_blocks`, include/mpgan_hip.h: sizing queries and launches see the same value)
 static bool hw_pairs_congruent(const GatherConv& p) {
   if (p.nphase < 2 || p.nphase % 2 || p.classes) return false;
@@ -932,27 +943,13 @@ static int hw_choice(const GatherConv& p, bool with_stats) {
   }
   return 0;
 }
-static int hw_bm(int choice) { return choice == 2 ? 512 : 256; }
 
 template <int WM, int WN, bool MASK, bool RING = true, bool PAIR = false>
 static int hw_launch(const GatherConv& p, long maxM, hipStream_t st) {
   auto kern = gather_conv_bf16_wide_kernel<WM, WN, MASK, RING, PAIR>;
   using T = HwTile<WM, WN, RING>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, T::SMEM);
-    if (e != hipSuccess) {
-      set_error("gather_conv_bf16_wide: hipFuncSetAttribute(%d): %s", T::SMEM, hipGetErrorString(e));
-      return MPGAN_ERR_HIP;
-    }
-    attr_set = true;
-  }
-  static int dbg_set = -1;
-  if (dbg_set < 0) {
-    const char* e = dev_env("MPGAN_DBG_HB");
-    dbg_set = e ? atoi(e) : 0;
-    if (dbg_set) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_hb_dbg), &dbg_set, sizeof(int));
-  }
+  if (const int rc = hb_prepare<gather_conv_bf16_wide_kernel<WM, WN, MASK, RING, PAIR>>(T::SMEM, "gather_conv_bf16_wide"))
+    return rc;
   GatherConv q = p;
   long pairs;
   if constexpr (PAIR) {                                // (congruent phases, never border classes: hw_pairs_congruent)
@@ -1252,21 +1249,9 @@ static bool hp_ok(const GatherConv& p) {
          ph.My >= 2 * HP_TY && ph.Mx >= 2 * HP_TX;
 }
 
-// Patch form or K-stepped form?  With 128 produced channels (D.conv2's forward at C5) the 512 x 128 wide K-stepped
-// kernel is the faster one since round 3 (4.33 -> 3.74 ms at 126^3 bs 4, same box, gpurun_out/r4/conv2_whatif.txt: the
-// patch kernel's 64 x 64 wave tiles read four fragments per four MFMAs and its one block per CU leaves every tile's
-// patch fill and epilogue exposed); with 64 produced channels (the backward-data) only the narrow K-stepped kernel
-// exists (6.5 ms) and a patch form stays (the big-patch kernel below where it applies).  Decided on the COMPACT geometry so that the statistics-row query
-// and the launch agree (hb_dispatch refuses a pitched operand that changes the wide form's availability).
-static bool hp8_use(const GatherConv& p, bool with_stats);
-static bool hp_use(const GatherConv& p, bool with_stats) {
-  if (p.Cin % HB_BK != 0 || !hp_ok(p)) return false;
-  static const bool always = dev_env("MPGAN_DBG_HB_PATCH_ALWAYS") != nullptr;   // (A/B runs, make DEV=1)
-  if (always) return true;
-  GatherConv c = p;
-  c.ldi = c.Cin;
-  return !(p.Cout > 64 && hw_choice(c, with_stats) == 2);
-}
+// The geometry of the patch forms: a one-phase stride-1 3x3x3 gather of whole 64-channel chunks.  build_gather_bf16
+// builds such a gather without border classes, and choose_bf16 offers it the patch forms.
+static bool hb_patch_geometry(const GatherConv& p) { return p.Cin % HB_BK == 0 && hp_ok(p); }
 
 static HpGrid hp_grid(const GatherConv& p) {
   const Phase& ph = p.ph[0];
@@ -1277,21 +1262,7 @@ template <int BN>
 static int hp_launch(const GatherConv& p, hipStream_t st) {
   auto kern = gather_patch_bf16_kernel<BN>;
   constexpr int smem = HpTile<BN>::SMEM;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (e != hipSuccess) {
-      set_error("gather_patch_bf16: hipFuncSetAttribute(%d): %s", smem, hipGetErrorString(e));
-      return MPGAN_ERR_HIP;
-    }
-    attr_set = true;
-  }
-  static int dbg_set = -1;
-  if (dbg_set < 0) {
-    const char* e = dev_env("MPGAN_DBG_HB");
-    dbg_set = e ? atoi(e) : 0;
-    if (dbg_set) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_hb_dbg), &dbg_set, sizeof(int));
-  }
+  if (const int rc = hb_prepare<gather_patch_bf16_kernel<BN>>(smem, "gather_patch_bf16")) return rc;
   const HpGrid tg = hp_grid(p);
   GatherConv q = p;
   q.mtiles = p.N * tg.tiles_z * tg.tiles_y * tg.tiles_x;
@@ -1305,7 +1276,7 @@ static int hp_launch(const GatherConv& p, hipStream_t st) {
 
 // ---------------------------------------------------------------------------
 // Big-patch form (round 4): the same idea on an 8 x 8 x 8 output tile with 32-channel chunks.
-// What the round-4 what-if runs of the 4 x 8 x 8 kernel above said (gpurun_out/r4/conv2_whatif.txt, D.conv2 at 126^3
+// What the round-4 what-if runs of the 4 x 8 x 8 kernel above said (profiles/r04_conv2_whatif.txt, D.conv2 at 126^3
 // bs 4): its fragment reads + MFMAs alone, no DMA and no epilogue, take 3.18 ms of the 4.33 ms forward -- 54 % of the
 // matrix rate with nothing to wait for -- because a 64 x 64 wave tile issues four ds_read_b128 per four MFMAs, and the
 // 512 x 128 K-stepped kernel (128 x 64 per wave: six reads per eight MFMAs) already beats it on the forward (3.74 ms)
@@ -1576,21 +1547,7 @@ template <int BN>
 static int hp8_launch(const GatherConv& p, hipStream_t st) {
   auto kern = gather_patch8_bf16_kernel<BN>;
   constexpr int smem = H8Tile<BN>::SMEM;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (e != hipSuccess) {
-      set_error("gather_patch8_bf16: hipFuncSetAttribute(%d): %s", smem, hipGetErrorString(e));
-      return MPGAN_ERR_HIP;
-    }
-    attr_set = true;
-  }
-  static int dbg_set = -1;
-  if (dbg_set < 0) {
-    const char* e = dev_env("MPGAN_DBG_HB");
-    dbg_set = e ? atoi(e) : 0;
-    if (dbg_set) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_hb_dbg), &dbg_set, sizeof(int));
-  }
+  if (const int rc = hb_prepare<gather_patch8_bf16_kernel<BN>>(smem, "gather_patch8_bf16")) return rc;
   const HpGrid tg = hp8_grid(p);
   GatherConv q = p;
   q.packed = 0;
@@ -1603,16 +1560,166 @@ static int hp8_launch(const GatherConv& p, hipStream_t st) {
   return check_launch("gather_patch8_bf16");
 }
 
-// Routing between the forms is decided on the COMPACT geometry (pitch = channels), like hp_use
-// Measured at D.conv2's size (126^3 bs 4, product code, same box, gpurun_out/r4/conv2_patch8_b.txt; ms): 128 produced
-// channels (forward): 512 x 128 K-stepped 3.85, big patch 4.14, 4 x 8 x 8 patch 4.25; 64 produced channels
-// (backward-data; no wide K-stepped form exists): big patch 4.08, 4 x 8 x 8 patch 4.57-4.63.
-static bool hp8_use(const GatherConv& p, bool with_stats) {
-  GatherConv c = p;
-  c.ldi = c.Cin;
-  if (!hp8_ok(c)) return false;
-  static const bool always = dev_env("MPGAN_DBG_HB_PATCH_ALWAYS") != nullptr;   // (A/B runs, make DEV=1)
-  return always || !(p.Cout > 64 && hw_choice(c, with_stats) == 2);
+// ---------------------------------------------------------------------------
+// Which kernel serves a bf16 gather.  choose_bf16() is the ONE place the form is decided: hb_dispatch runs its choice,
+// and every geometry query (mpgan_conv_variant_bf16, the partial-row counts, the profiling label) reads the choice made
+// for the stand-in GatherConv the entry point would build (standin_bf16), so a query cannot disagree with its launch.
+// ---------------------------------------------------------------------------
+enum class HForm {
+  Narrow,      // gather_conv_bf16_kernel<BN, MASK, NW>                     code 0
+  Patch,       // gather_patch_bf16_kernel<BN>                              code 1
+  Wide256,     // gather_conv_bf16_wide_kernel<2, 4, MASK, RING, false>     code 2
+  Wide512,     // gather_conv_bf16_wide_kernel<4, 2, MASK, true, false>     code 3
+  WidePairs,   // gather_conv_bf16_wide_kernel<2, 4, MASK, true, true>      code 4
+  Patch8,      // gather_patch8_bf16_kernel<BN>                             code 5
+};
+
+struct Bf16Choice {
+  HForm form;
+  int rc;            // MPGAN_OK, or the status of a refusal: `msg` is its format, with one %s for the entry point's name
+  const char* msg;
+  int code;          // mpgan_conv_variant_bf16's number (include/mpgan_hip.h)
+  int rows;          // partial rows the launch writes: statistics or norm-backward sums (Narrow has none of the latter)
+  int bm;            // output pixels per tile
+  int bn, nw;        // channel tile (Narrow and the patch forms), waves per block (Narrow)
+  bool mask, ring, pair;   // the K-stepped forms' MASK, the wide forms' RING and PAIR
+};
+
+#define BF16_REFUSE(cond, m)              \
+  do {                                    \
+    if (cond) {                           \
+      c.rc = MPGAN_ERR_UNSUPPORTED;       \
+      c.msg = (m);                        \
+      return c;                           \
+    }                                     \
+  } while (0)
+
+// The form, instance and partial rows of this launch (or its refusal), for a gather hb_check admits (the queries also
+// ask about geometries it refuses).  Reads the MPGAN_DBG_HB_* form switches (here and in the predicates), so the DEV
+// build's queries follow forced forms too.  Calls no runtime function and allocates nothing.
+static Bf16Choice choose_bf16(const GatherConv& p) {
+  Bf16Choice c{};
+  c.rc = MPGAN_OK;
+  c.bm = 256;
+  c.bn = p.Cout > 64 ? 128 : 64;
+  const bool with_stats = p.stats != nullptr;
+  // Patch form or K-stepped form?  With 128 produced channels (D.conv2's forward at C5) the 512 x 128 wide K-stepped
+  // kernel is the faster one since round 3 (4.33 -> 3.74 ms at 126^3 bs 4, same box, profiles/r04_conv2_whatif.txt:
+  // the patch kernel's 64 x 64 wave tiles read four fragments per four MFMAs and its one block per CU leaves every
+  // tile's patch fill and epilogue exposed); with 64 produced channels (the backward-data) only the narrow K-stepped
+  // kernel exists (6.5 ms) and a patch form stays (the big-patch kernel where it applies).  Measured at D.conv2's size
+  // (126^3 bs 4, product code, same box, profiles/r04_conv2_patch8_b.txt; ms): 128 produced channels (forward):
+  // 512 x 128 K-stepped 3.85, big patch 4.14, 4 x 8 x 8 patch 4.25; 64 produced channels (backward-data): big patch
+  // 4.08, 4 x 8 x 8 patch 4.57-4.63.  Decided on the COMPACT geometry (pitch = channels), which the row queries see.
+  GatherConv cp = p;
+  cp.ldi = cp.Cin;
+  static const bool patch_always = dev_env("MPGAN_DBG_HB_PATCH_ALWAYS") != nullptr;   // (A/B runs, make DEV=1)
+  const bool patch = patch_always || !(p.Cout > 64 && hw_choice(cp, with_stats) == 2);
+  if (patch && hp8_ok(cp)) {   // one row per 8 x 8 x 8 tile
+    const HpGrid tg = hp8_grid(p);
+    c.form = HForm::Patch8;
+    c.code = 5;
+    c.bm = H8_BM;
+    c.rows = p.N * tg.tiles_z * tg.tiles_y * tg.tiles_x;
+    BF16_REFUSE(!hp8_ok(p), "%s: the channel pitch of this operand takes it beyond the 32-bit offset range of the patch "
+                            "form the statistics rows were sized for: pass a compact tensor");
+    return c;
+  }
+  if (patch && hb_patch_geometry(p)) {   // one row per 4 x 8 x 8 tile
+    const HpGrid tg = hp_grid(p);
+    c.form = HForm::Patch;
+    c.code = 1;
+    c.rows = p.N * tg.tiles_z * tg.tiles_y * tg.tiles_x;
+    return c;
+  }
+  c.mask = !hb_all_in_range(p);
+  c.ring = true;
+  switch (hw_choice(p, with_stats)) {   // one row per (phase or phase pair, m-tile)
+    case 1: {
+      static const bool no_ring = dev_env("MPGAN_DBG_HB_NO_RING") != nullptr;   // development: two whole stages instead
+      c.form = HForm::Wide256;
+      c.code = 2;
+      c.ring = !no_ring;
+      c.rows = (int)phase_tile_rows(p, 256);
+      return c;
+    }
+    case 2:
+      c.form = HForm::Wide512;
+      c.code = 3;
+      c.bm = 512;
+      c.rows = (int)phase_tile_rows(p, 512);
+      return c;
+    case 3:
+      c.form = HForm::WidePairs;
+      c.code = 4;
+      c.pair = true;
+      c.rows = (int)((max_phase_pixels(p) + 255) / 256) * (p.nphase / 2);
+      return c;
+  }
+  static const char* nw_env = dev_env("MPGAN_DBG_HB_NW");   // development: force four or eight waves per block
+  c.form = HForm::Narrow;
+  c.nw = nw_env && atoi(nw_env) == 4 ? 4 : 8;
+  c.rows = p.bwd.part ? 0 : (int)phase_tile_rows(p, 256);
+  BF16_REFUSE(p.bwd.part != nullptr, "%s: no fused norm-backward sums on the narrow K-stepped kernel "
+                                     "(mpgan_conv_bwd_stats_rows_bf16() == 0)");
+  return c;
+}
+#undef BF16_REFUSE
+
+// A launch that writes partial rows had them sized by a query on the compact geometry (pitch = channels): a pitched
+// operand near the 4 GiB offset range must not change the row count or the tile height that query's choice has.
+static int hb_pitch_rule(const GatherConv& p, const Bf16Choice& c, const char* what) {
+  GatherConv cp = p;
+  cp.ldi = cp.Cin;
+  const Bf16Choice s = choose_bf16(cp);
+  if (s.rows == c.rows && s.bm == c.bm) return MPGAN_OK;
+  MPGAN_UNSUPPORTED(p.stats != nullptr, "%s: the channel pitch of this operand changes the tile height the statistics "
+                                        "rows were sized for (operand beyond the 32-bit offset range of the wide form): "
+                                        "pass a compact tensor", what);
+  set_error("%s: the channel pitch of dy changes the kernel form the partial rows were sized for: pass a compact tensor",
+            what);
+  return MPGAN_ERR_UNSUPPORTED;
+}
+
+// Runs the instance a choice names.
+static int launch_bf16_chosen(const GatherConv& p, const Bf16Choice& c, long maxM, hipStream_t st, const char* what) {
+  if (c.rc != MPGAN_OK) {
+    set_error(c.msg, what);
+    return c.rc;
+  }
+  const bool m = c.mask;
+  switch (c.form) {
+    case HForm::Patch8: return c.bn == 128 ? hp8_launch<128>(p, st) : hp8_launch<64>(p, st);
+    case HForm::Patch: return c.bn == 128 ? hp_launch<128>(p, st) : hp_launch<64>(p, st);
+    case HForm::WidePairs: return m ? hw_launch<2, 4, true, true, true>(p, maxM, st) : hw_launch<2, 4, false, true, true>(p, maxM, st);
+    case HForm::Wide256:
+      if (!c.ring) return m ? hw_launch<2, 4, true, false>(p, maxM, st) : hw_launch<2, 4, false, false>(p, maxM, st);
+      return m ? hw_launch<2, 4, true>(p, maxM, st) : hw_launch<2, 4, false>(p, maxM, st);
+    case HForm::Wide512: return m ? hw_launch<4, 2, true>(p, maxM, st) : hw_launch<4, 2, false>(p, maxM, st);
+    case HForm::Narrow:
+      if (c.nw == 4) {
+        if (c.bn == 128) return m ? hb_launch<128, true, 4>(p, maxM, st) : hb_launch<128, false, 4>(p, maxM, st);
+        return m ? hb_launch<64, true, 4>(p, maxM, st) : hb_launch<64, false, 4>(p, maxM, st);
+      }
+      if (c.bn == 128) return m ? hb_launch<128, true, 8>(p, maxM, st) : hb_launch<128, false, 8>(p, maxM, st);
+      return m ? hb_launch<64, true, 8>(p, maxM, st) : hb_launch<64, false, 8>(p, maxM, st);
+  }
+  return MPGAN_ERR_UNSUPPORTED;
+}
+
+// rocprofv3's name of the instance a choice names (without `void mpgan::` and the argument list).
+static int bf16_kernel_name(const Bf16Choice& c, char* buf, int len) {
+  const char* b[2] = {"false", "true"};
+  switch (c.form) {
+    case HForm::Patch8: return snprintf(buf, len, "gather_patch8_bf16_kernel<%d>", c.bn);
+    case HForm::Patch: return snprintf(buf, len, "gather_patch_bf16_kernel<%d>", c.bn);
+    case HForm::Narrow: return snprintf(buf, len, "gather_conv_bf16_kernel<%d, %s, %d>", c.bn, b[c.mask], c.nw);
+    default: {
+      const bool tall = c.form == HForm::Wide512;
+      return snprintf(buf, len, "gather_conv_bf16_wide_kernel<%d, %d, %s, %s, %s>", tall ? 4 : 2, tall ? 2 : 4,
+                      b[c.mask], b[c.ring], b[c.pair]);
+    }
+  }
 }
 
 static int hb_dispatch(const GatherConv& p, hipStream_t st, const char* what) {
@@ -1620,41 +1727,12 @@ static int hb_dispatch(const GatherConv& p, hipStream_t st, const char* what) {
   if (rc) return rc;
   const long maxM = max_phase_pixels(p);
   if (maxM == 0) return MPGAN_OK;
-  if (hp8_use(p, p.stats != nullptr)) {
-    MPGAN_UNSUPPORTED(!hp8_ok(p), "%s: the channel pitch of this operand takes it beyond the 32-bit offset range of the patch form "
-                      "the statistics rows were sized for: pass a compact tensor", what);
-    return p.Cout > 64 ? hp8_launch<128>(p, st) : hp8_launch<64>(p, st);
+  const Bf16Choice c = choose_bf16(p);
+  if (p.stats || p.bwd.part) {
+    rc = hb_pitch_rule(p, c, what);
+    if (rc) return rc;
   }
-  if (hp_use(p, p.stats != nullptr)) return p.Cout > 64 ? hp_launch<128>(p, st) : hp_launch<64>(p, st);
-  const bool mask = !hb_all_in_range(p);
-  const int wide = hw_choice(p, p.stats != nullptr);
-  if (p.stats) {
-    // mpgan_conv_stats_rows_bf16 sized the caller's partial rows from the compact geometry (pitch = Cin): a pitched
-    // operand close to the 4 GiB offset range can fall back to the narrower tile, which would write more rows
-    GatherConv c = p;
-    c.ldi = c.Cin;
-    MPGAN_UNSUPPORTED(hw_bm(hw_choice(c, true)) != hw_bm(wide),
-                      "%s: the channel pitch of this operand changes the tile height the statistics rows were sized for "
-                      "(operand beyond the 32-bit offset range of the wide form): pass a compact tensor", what);
-  }
-  if (wide == 3) return mask ? hw_launch<2, 4, true, true, true>(p, maxM, st) : hw_launch<2, 4, false, true, true>(p, maxM, st);
-  static const bool no_ring = dev_env("MPGAN_DBG_HB_NO_RING") != nullptr;     // development: two whole stages instead
-  if (wide == 1 && no_ring) return mask ? hw_launch<2, 4, true, false>(p, maxM, st) : hw_launch<2, 4, false, false>(p, maxM, st);
-  if (wide == 1) return mask ? hw_launch<2, 4, true>(p, maxM, st) : hw_launch<2, 4, false>(p, maxM, st);
-  if (wide == 2) return mask ? hw_launch<4, 2, true>(p, maxM, st) : hw_launch<4, 2, false>(p, maxM, st);
-  MPGAN_UNSUPPORTED(p.bwd.part != nullptr, "%s: no fused norm-backward sums on the narrow K-stepped kernel "
-                                            "(mpgan_conv_bwd_stats_rows_bf16() == 0)", what);
-  static int nw = 0;
-  if (!nw) {
-    const char* e = dev_env("MPGAN_DBG_HB_NW");      // development: force four or eight waves per block
-    nw = e ? atoi(e) : 8;
-  }
-  if (nw == 4) {
-    if (p.Cout > 64) return mask ? hb_launch<128, true, 4>(p, maxM, st) : hb_launch<128, false, 4>(p, maxM, st);
-    return mask ? hb_launch<64, true, 4>(p, maxM, st) : hb_launch<64, false, 4>(p, maxM, st);
-  }
-  if (p.Cout > 64) return mask ? hb_launch<128, true, 8>(p, maxM, st) : hb_launch<128, false, 8>(p, maxM, st);
-  return mask ? hb_launch<64, true, 8>(p, maxM, st) : hb_launch<64, false, 8>(p, maxM, st);
+  return launch_bf16_chosen(p, c, maxM, st, what);
 }
 
 // ---------------------------------------------------------------------------
@@ -2454,8 +2532,9 @@ static inline int hb_ew_blocks(long total) {
 using namespace mpgan;
 
 // Geometry of a bf16 gather.  A stride-1 transposed gather (backward-data of a conv) is first built as ONE phase: the
-// patch kernels stage out-of-image rows as zeros once per tile and have no use for border classes; only when neither
-// patch form serves it is it rebuilt with them (conv_geom.h) for the K-stepped kernels.
+// patch kernels stage out-of-image rows as zeros once per tile and have no use for border classes; only when the patch
+// forms' geometry does not hold is it rebuilt with them (conv_geom.h) for the K-stepped kernels -- even where
+// choose_bf16 then prefers a wide K-stepped form to the patch forms.
 static void build_gather_bf16(GatherConv& p, const mpgan_conv_geom* g, bool backward_data) {
   const bool fwd_type = backward_data ? g->transposed != 0 : g->transposed == 0;
   const int32_t *gd = backward_data ? g->out_dhw : g->in_dhw, *pd = backward_data ? g->in_dhw : g->out_dhw;
@@ -2465,47 +2544,51 @@ static void build_gather_bf16(GatherConv& p, const mpgan_conv_geom* g, bool back
     return;
   }
   build_transposed(p, g->n, gd, cg, pd, cp, g->k, g->stride, g->pad, false);
-  GatherConv c = p;
-  c.ldi = c.Cin;
-  if (c.Cin % HB_BK == 0 && (hp8_ok(c) || hp_ok(c))) return;
+  if (hb_patch_geometry(p)) return;
   build_transposed(p, g->n, gd, cg, pd, cp, g->k, g->stride, g->pad, true);
+}
+
+// What a geometry query decides from: the GatherConv the entry point builds for this geometry and direction, with
+// compact pitches and 16-byte aligned stand-in operands (never dereferenced).  The caller sets stats / bwd.part.
+alignas(16) static float g_standin[4];
+static GatherConv standin_bf16(const mpgan_conv_geom* g, bool backward_data) {
+  GatherConv p{};
+  p.in = g_standin; p.wp = g_standin; p.out = g_standin;
+  p.pro = make_pro(nullptr);
+  set_geom_flags(p, g);
+  build_gather_bf16(p, g, backward_data);
+  p.ldi = p.Cin; p.ldo = p.Cout;
+  return p;
+}
+
+// The choice the variant query and the label describe: the statistics-writing forward, the plain backward-data.
+static Bf16Choice choose_standin_bf16(const mpgan_conv_geom* g, bool backward_data) {
+  GatherConv p = standin_bf16(g, backward_data);
+  if (!backward_data) p.stats = g_standin;
+  return choose_bf16(p);
 }
 
 extern "C" int32_t mpgan_conv_stats_rows_bf16(const mpgan_conv_geom* g) {
   if (check_geom(g)) return -1;
-  GatherConv p{};
-  set_geom_flags(p, g);
-  build_gather_bf16(p, g, false);
-  if (hp8_use(p, true)) {    // big-patch form: one row per 8 x 8 x 8 tile
-    const HpGrid tg = hp8_grid(p);
-    return p.N * tg.tiles_z * tg.tiles_y * tg.tiles_x;
-  }
-  if (hp_use(p, true)) {     // patch form: one row per 4 x 8 x 8 tile
-    const HpGrid tg = hp_grid(p);
-    return p.N * tg.tiles_z * tg.tiles_y * tg.tiles_x;
-  }
-  p.ldi = p.Cin;
-  const int bm = hw_bm(g->cin % HB_BK == 0 ? hw_choice(p, true) : 0);
-  return (int32_t)phase_tile_rows(p, bm);
+  return choose_standin_bf16(g, false).rows;
 }
 
-// Which bf16 kernel serves this geometry (profiling labels): 0 = K-stepped gather_conv_bf16_kernel,
-// 1 = gather_patch_bf16_kernel (stride-1 3x3x3 gathers), 2 / 3 / 4 = gather_conv_bf16_wide_kernel 256 x 256 / 512 x 128 /
-// 256 x 256 over phase pairs, 5 = gather_patch8_bf16_kernel (stride-1 3x3x3 gathers on maps of >= 16 pixels per dimension).
+// Which bf16 kernel serves this geometry: 0 = K-stepped gather_conv_bf16_kernel, 1 = gather_patch_bf16_kernel
+// (stride-1 3x3x3 gathers), 2 / 3 / 4 = gather_conv_bf16_wide_kernel 256 x 256 / 512 x 128 / 256 x 256 over phase
+// pairs, 5 = gather_patch8_bf16_kernel (stride-1 3x3x3 gathers on maps of >= 16 pixels per dimension).  The forward
+// is the one that writes statistics.  Read from choose_bf16 (conv_bf16.hip), like mpgan_conv_kernel_name_bf16.
 extern "C" int32_t mpgan_conv_variant_bf16(const mpgan_conv_geom* g, int32_t backward_data) {
   if (check_geom(g)) return -1;
-  GatherConv p{};
-  set_geom_flags(p, g);
-  if (!backward_data) {
-    build_gather_bf16(p, g, false);
-  } else {
-    build_gather_bf16(p, g, true);
-  }
-  if (hp8_use(p, !backward_data)) return 5;
-  if (hp_use(p, !backward_data)) return 1;
-  p.ldi = p.Cin;
-  const int wide = p.Cin % HB_BK == 0 ? hw_choice(p, !backward_data) : 0;
-  return wide ? 1 + wide : 0;
+  return choose_standin_bf16(g, backward_data).code;
+}
+
+extern "C" int mpgan_conv_kernel_name_bf16(const mpgan_conv_geom* g, int32_t backward_data, char* buf, int32_t len) {
+  int rc = check_geom(g);
+  if (rc) return rc;
+  MPGAN_CHECK_ARG(buf && len > 0, "conv_kernel_name_bf16: no buffer");
+  const int n = bf16_kernel_name(choose_standin_bf16(g, backward_data), buf, len);
+  MPGAN_CHECK_ARG(n < len, "conv_kernel_name_bf16: the name needs %d bytes", n + 1);
+  return MPGAN_OK;
 }
 
 extern "C" int mpgan_conv_forward_bf16(const mpgan_conv_geom* g, const void* x, int32_t ldx, const void* w_packed,
@@ -2544,23 +2627,11 @@ extern "C" int mpgan_conv_backward_data_bf16(const mpgan_conv_geom* g, const voi
 // fused sums (run mpgan_norm_bwd_reduce_bf16).
 extern "C" int32_t mpgan_conv_bwd_stats_rows_bf16(const mpgan_conv_geom* g) {
   if (check_geom(g)) return -1;
-  GatherConv p{};
-  set_geom_flags(p, g);
-  build_gather_bf16(p, g, true);
+  GatherConv p = standin_bf16(g, true);
   if (p.Cin % HB_BK != 0 || p.Cout % 8 != 0) return 0;
-  p.ldi = p.Cin;
-  if (hp8_use(p, false)) {
-    const HpGrid tg = hp8_grid(p);
-    return p.N * tg.tiles_z * tg.tiles_y * tg.tiles_x;
-  }
-  if (hp_use(p, false)) {
-    const HpGrid tg = hp_grid(p);
-    return p.N * tg.tiles_z * tg.tiles_y * tg.tiles_x;
-  }
-  const int wide = hw_choice(p, false);
-  if (wide == 0) return 0;
-  if (wide == 3) return (int32_t)((max_phase_pixels(p) + 255) / 256) * (p.nphase / 2);
-  return (int32_t)phase_tile_rows(p, hw_bm(wide));
+  p.bwd.part = g_standin;
+  const Bf16Choice c = choose_bf16(p);
+  return c.rc == MPGAN_OK ? c.rows : 0;
 }
 
 // mpgan_conv_backward_data_bf16 + the reduce pass of the BatchNorm + LeakyReLU(slope) in front of this conv's input, in
@@ -2587,15 +2658,9 @@ extern "C" int mpgan_conv_backward_data_stats_bf16(const mpgan_conv_geom* g, con
   p.bwd.part = partials; p.bwd.leaky = 1; p.bwd.slope = slope;
   set_geom_flags(p, g);
   build_gather_bf16(p, g, true);
-  {   // the rows were sized on the compact geometry: a pitched operand must not change the form
-    GatherConv c = p;
-    c.ldi = c.Cin;
-    const bool a8 = hp8_use(c, false), a4 = !a8 && hp_use(c, false);
-    const bool b8 = hp8_use(p, false), b4 = !b8 && hp_use(p, false);
-    MPGAN_UNSUPPORTED(a8 != b8 || a4 != b4 || (!a8 && !a4 && hw_choice(c, false) != hw_choice(p, false)),
-                      "conv_backward_data_stats_bf16: the channel pitch of dy changes the kernel form the partial rows were "
-                      "sized for: pass a compact tensor");
-  }
+  // the pitch rule ahead of the operand checks too: a dy beyond the 4 GiB offset range reports its pitch
+  rc = hb_pitch_rule(p, choose_bf16(p), "conv_backward_data_stats_bf16");
+  if (rc) return rc;
   return hb_dispatch(p, (hipStream_t)stream, "conv_backward_data_stats_bf16");
 }
 

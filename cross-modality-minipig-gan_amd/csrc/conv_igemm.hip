@@ -3031,6 +3031,52 @@ static int launch_chosen(const GatherConv& p, const GatherChoice& c, long maxM, 
   return MPGAN_ERR_UNSUPPORTED;
 }
 
+// rocprofv3's name of the instance launch_chosen runs for a choice (without `void mpgan::` and the argument list).
+static int gather_kernel_name(const GatherConv& p, const GatherChoice& c, char* buf, int len) {
+  const char* b[2] = {"false", "true"};
+  const int a = c.arg, lanes16 = a == 4 || a == 8 ? a : 16;   // (the instances of the thin forms' switches)
+  const int T = p.Kz * p.Ky * p.Kx == 9 ? 9 : 27;
+  // K-stepped forms: BN, TM, TN, WN of the channel tile
+  const int tm = c.bn == 128 ? 2 : 1, tn = c.bn == 32 ? 1 : 2, wn = c.bn == 128 ? 2 : 1;
+  const int cin = p.Cin == 16 || p.Cin == 32 ? p.Cin : 64;
+  const int ppro = c.pl.merged ? 0 : c.pro;
+  switch (c.form) {
+    case GForm::ThinBf16OutRows: return snprintf(buf, len, "thin_cin1_rows_kernel<%d, true>", T);
+    case GForm::Cin1Rows: return snprintf(buf, len, "thin_cin1_rows_kernel<%d, false>", T);
+    case GForm::ThinBf16OutFull: return snprintf(buf, len, "thin_cin1_full_kernel<%d, true>", lanes16);
+    case GForm::Cin1Full: return snprintf(buf, len, "thin_cin1_full_kernel<%d, false>", lanes16);
+    case GForm::ThinBf16InMfma: return snprintf(buf, len, "thin_cout1_mfma_bf16_kernel");
+    case GForm::ThinBf16In: return snprintf(buf, len, "thin_cout1_kernel<%d, true>", lanes16);
+    case GForm::C1C1Rows4: return snprintf(buf, len, "thin_c1c1_rows4_kernel<%s>", b[a != 0]);
+    case GForm::Cin1: return snprintf(buf, len, "thin_cin1_kernel<%d>", a == 4 ? 4 : 1);
+    case GForm::ConvtQuad: return snprintf(buf, len, "convt_quad_cout1_kernel<%d>", lanes16);
+    case GForm::ConvtOct: return snprintf(buf, len, "convt_oct_cout1_kernel<%d>", lanes16);
+    case GForm::Cout1:
+      return snprintf(buf, len, "thin_cout1_kernel<%d, false>", a > 0 && a <= 32 && (a & (a - 1)) == 0 ? a : 64);
+    case GForm::Patch3d: return snprintf(buf, len, "gather_patch3d_c16_kernel<%s, %s>", b[c.pro != 0], b[a != 0]);
+    case GForm::Patch:
+    case GForm::PatchPersist:
+      return snprintf(buf, len, "%s<%d, %d, %s, %s>",
+                      c.form == GForm::Patch ? "gather_patch_kernel" : "gather_patch_persist_kernel", cin, ppro,
+                      b[p.Cout <= 16], b[c.pl.merged != 0]);
+    case GForm::Mm16: {   // (launch_gather_mm16: in-block split-K for one wrap and the 64 / 32 channel tiles only)
+      const int ks = c.wraps == 1 && c.ks == 2 && c.bn != 128 ? 2 : 1;
+      return snprintf(buf, len, "gather_conv_pipe_kernel<%d, %d, %d, %d, %d, %d, false, %d, true>", c.bn, tm, tn, wn,
+                      c.wraps, c.pro, ks);
+    }
+    case GForm::Pipe: {   // (launch_pipe_bn: FAST is the 128 tile, in-block split-K the 64 / 32 tiles)
+      const bool fast = c.wraps == 1 && c.pro == 3 && c.fast;
+      const int ks = !fast && c.wraps == 1 && c.pro != 3 && c.ks == 2 ? 2 : 1;
+      const int bn = fast ? 128 : (ks == 2 && c.bn != 64 ? 32 : c.bn);
+      return snprintf(buf, len, "gather_conv_pipe_kernel<%d, %d, %d, %d, %d, %d, %s, %d, false>", bn,
+                      bn == 128 ? 2 : 1, bn == 32 ? 1 : 2, bn == 128 ? 2 : 1, c.wraps, c.pro, b[fast], ks);
+    }
+    case GForm::Dma: return snprintf(buf, len, "gather_conv_dma_kernel<%d, %d, %d, %d, 2>", c.bn, tm, tn, wn);
+    case GForm::Kstep: return snprintf(buf, len, "gather_conv_kernel<%d, %d, %d, %d, %s>", c.bn, tm, tn, wn, b[a != 0]);
+  }
+  return snprintf(buf, len, "?");
+}
+
 #ifdef MPGAN_STAMPS
 static int launch_gather_impl(const GatherConv& p, hipStream_t st);
 static int launch_gather(const GatherConv& p0, hipStream_t st) {
@@ -3138,6 +3184,17 @@ static GatherChoice choose_standin(const GatherConv& p) { return choose_gather(p
 extern "C" int32_t mpgan_conv_variant(const mpgan_conv_geom* g, int32_t backward_data, int32_t has_prologue) {
   if (check_geom(g)) return -1;
   return choose_standin(standin_conv(g, backward_data, has_prologue)).code;
+}
+
+extern "C" int mpgan_conv_kernel_name(const mpgan_conv_geom* g, int32_t backward_data, int32_t pro_code, char* buf,
+                                      int32_t len) {
+  int rc = check_geom(g);
+  if (rc) return rc;
+  MPGAN_CHECK_ARG(buf && len > 0 && pro_code >= 0 && pro_code <= 3, "conv_kernel_name: no buffer / bad prologue code");
+  const GatherConv p = standin_conv(g, backward_data, pro_code);
+  const int n = gather_kernel_name(p, choose_standin(p), buf, len);
+  MPGAN_CHECK_ARG(n < len, "conv_kernel_name: the name needs %d bytes", n + 1);
+  return MPGAN_OK;
 }
 
 extern "C" int32_t mpgan_conv_stats_rows(const mpgan_conv_geom* g, int32_t has_prologue) {

@@ -257,36 +257,19 @@ def conv_bytes(g: ConvGeom, esize: int = 4) -> int:
 
 def gather_kernel_name(g: ConvGeom, backward_data: bool, has_pro: bool, per_sample_norm: bool = False,
                        fast_leaky: bool = False) -> str:
-    """The kernel symbol (as rocprofv3 prints it, minus `void mpgan::` and the argument list)
-    the C dispatcher picks for this conv (mpgan_conv_variant + launch_gather's rules)."""
+    """The kernel symbol (as rocprofv3 prints it, minus `void mpgan::` and the argument list) of the instance the
+    C dispatcher runs for this conv, from the same choice the launch makes (mpgan_conv_kernel_name)."""
     gc = g.c()
-    v = int(lib().mpgan_conv_variant(C.byref(gc), int(backward_data),
-                                     (2 if per_sample_norm else (3 if fast_leaky else 1)) if has_pro else 0))
-    dma = v >= 3000                              # DMA-staged form (prologue-free gathers with many tiles)
-    v = v - 3000 if dma else v
-    ks2 = v >= 2000                              # K axis split over two wave groups inside the block
-    v = v - 2000 if ks2 else v
-    fast = v >= 1000                             # mask-free instance of the pipelined kernel
-    v = v - 1000 if fast else v
-    if v == 1:
-        return "thin_cin1_kernel"
-    if v == 2:
-        return "thin_cout1_kernel"
-    if v == 18:
-        return f"gather_patch3d_c16_kernel<{'true' if has_pro else 'false'}, {'true' if g.mm_bf16 else 'false'}>"
-    cin_eff = g.cout if backward_data else g.cin
-    if v in (16, 17):
-        cout_eff = g.cin if backward_data else g.cout
-        return (f"gather_patch_kernel<{cin_eff}, {1 if has_pro else 0}, {'true' if cout_eff <= 16 else 'false'}, "
-                f"{'true' if v == 17 else 'false'}>")
-    tm, tn, wn = {128: (2, 2, 2), 64: (1, 2, 1), 32: (1, 1, 1)}[v]
-    if dma:
-        return f"gather_conv_dma_kernel<{v}, {tm}, {tn}, {wn}, 2>"
-    if cin_eff % 32 == 0 or cin_eff == 16:      # software-pipelined main kernel <BN, TM, TN, WN, WRAPS, PRO>
-        pro = 0 if not has_pro else (2 if per_sample_norm else (3 if fast_leaky else 1))
-        return (f"gather_conv_pipe_kernel<{v}, {tm}, {tn}, {wn}, {1 if cin_eff % 32 == 0 else 2}, {pro}, "
-                f"{'true' if fast else 'false'}, {2 if ks2 else 1}, {'true' if g.mm_bf16 else 'false'}>")
-    return f"gather_conv_kernel<{v}, {tm}, {tn}, {wn}, {'false' if cin_eff % 4 == 0 else 'true'}>"
+    pro = (2 if per_sample_norm else (3 if fast_leaky else 1)) if has_pro else 0
+    return kernel_label(lib().mpgan_conv_kernel_name, C.byref(gc), int(backward_data), pro)
+
+
+def kernel_label(entry, *args) -> str:
+    """The label a mpgan_conv_kernel_name* entry writes for these arguments."""
+    buf = C.create_string_buffer(160)
+    if entry(*args, buf, len(buf)):
+        raise RuntimeError(lib().mpgan_last_error().decode())
+    return buf.value.decode()
 
 
 def _ld(t):
@@ -1485,18 +1468,10 @@ class DiscPlan:
 # discriminator (variant A), bf16 storage (BASELINE config C5)
 # --------------------------------------------------------------------------
 def _bf16_kernel_name(g: ConvGeom, backward_data: bool) -> str:
-    """rocprofv3's name of the bf16 kernel that serves this layer (labels of bench.py's probe)."""
+    """rocprofv3's name of the bf16 kernel that serves this layer (labels of bench.py's probe), from the same choice
+    the launch makes (mpgan_conv_kernel_name_bf16; the forward is the one with statistics)."""
     gc = g.c()
-    bn = 128 if (g.cin if backward_data else g.cout) > 64 else 64
-    v = lib().mpgan_conv_variant_bf16(C.byref(gc), int(backward_data))
-    if v == 1:
-        return f"gather_patch_bf16_kernel<{bn}>"
-    if v == 5:
-        return f"gather_patch8_bf16_kernel<{bn}>"
-    if v in (2, 3, 4):
-        masked = "true" if backward_data or any(g.pad) else "false"
-        return f"gather_conv_bf16_wide_kernel<{'4, 2' if v == 3 else '2, 4'}, {masked}, true, {'true' if v == 4 else 'false'}>"
-    return f"gather_conv_bf16_kernel<{bn}, {'true' if backward_data else 'false'}, 8>"
+    return kernel_label(lib().mpgan_conv_kernel_name_bf16, C.byref(gc), int(backward_data))
 
 
 def _bf16_wgrad_kernel_name(g: ConvGeom) -> str:

@@ -148,6 +148,10 @@ int mpgan_conv_backward_data_stats(const mpgan_conv_geom* g, const float* dy, in
  * has_prologue: 0 none, 1 per-channel scale/shift, 2 per-(sample, channel), 3 per-channel +
  * LeakyReLU with a host-known slope in [0, 1]. */
 int32_t mpgan_conv_variant(const mpgan_conv_geom* g, int32_t backward_data, int32_t has_prologue);
+/* The profiling label of that launch: rocprofv3's name of the kernel instance it runs, without `void mpgan::` and the
+ * argument list, written NUL-terminated into buf[len].  pro_code is has_prologue's encoding.  Formatted from the same
+ * choice the launch makes (choose_gather, conv_igemm.hip); MPGAN_ERR_INVALID if the name needs more than len bytes. */
+int mpgan_conv_kernel_name(const mpgan_conv_geom* g, int32_t backward_data, int32_t pro_code, char* buf, int32_t len);
 
 /* Weight gradient: dW (torch layout, (Cout,Cin,k..) or (Cin,Cout,k..) for a
  * transposed conv) = beta*dW + sum over pixels.  x is the conv's input (with
@@ -461,11 +465,14 @@ int mpgan_norm_act_add_fold(const float* z, int32_t ldz, const mpgan_prologue* p
 int32_t mpgan_conv_stats_rows_bf16(const mpgan_conv_geom* g);
 int mpgan_conv_forward_bf16(const mpgan_conv_geom* g, const void* x, int32_t ldx, const void* w_packed,
                             const float* bias, float* stats_partials, void* y, int32_t ldy, void* stream);
-/* Which bf16 kernel serves this geometry (profiling labels only): 0 = the K-stepped gather kernel,
+/* Which bf16 kernel serves this geometry (the forward: with statistics): 0 = the K-stepped gather kernel,
  * 1 = the patch form for stride-1 3x3x3 gathers (D.conv2 forward / backward-data at config C5),
  * 2 / 3 / 4 = the wide K-stepped form: 256 x 256 tiles, 512 x 128 tiles, 256 x 256 tiles over pairs of phases of a
- * strided backward-data gather (D.conv3 / D.conv4 at config C5). */
+ * strided backward-data gather (D.conv3 / D.conv4 at config C5), 5 = the big-patch form (8 x 8 x 8 tiles).
+ * mpgan_conv_kernel_name_bf16 writes the profiling label of the same launch, like mpgan_conv_kernel_name.  Both, the
+ * row queries and the launch read one choice (choose_bf16, conv_bf16.hip). */
 int32_t mpgan_conv_variant_bf16(const mpgan_conv_geom* g, int32_t backward_data);
+int mpgan_conv_kernel_name_bf16(const mpgan_conv_geom* g, int32_t backward_data, char* buf, int32_t len);
 
 /* dx (bf16) = conv_backward_data(dy (bf16)); w_packed_bwd: bf16, layout 1 of mpgan_pack_weights_bf16. */
 int mpgan_conv_backward_data_bf16(const mpgan_conv_geom* g, const void* dy, int32_t lddy, const void* w_packed_bwd,
