@@ -3,11 +3,17 @@
 training step (BASELINE.json config C3: bs 16 per GPU, fp32), weak-scaled over
 N GPUs with one RCCL all-reduce per optimiser.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 K timed steps (K >= 1) after W warm-up steps; `ms_per_step` in the JSON line is the wall time of one timed
 step.  The inputs (weights and batch) are seeded, so the same arguments give the same inputs in every run, and
 --dump-outputs writes what the last timed step computed as .npy files for comparing two builds.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps (with the live roofline probe
+below), write the outputs and print the line.  --full adds, after the timed region, the side measurements that
+take runs of their own on the GPU or the host: `g_forward`, `phases` and `cpu_baseline` (below); in a plain run
+`g_forward` and `phases` are null and `cpu_baseline` is absent.  --no-gfwd / --no-phases / --no-cpu-baseline
+leave one of them out of a --full run.
 
 N > 1 from a bare shell (no WORLD_SIZE in the environment): this process starts N fresh
 rank processes itself -- before it has made any GPU call -- waits for them and exits with
@@ -27,7 +33,9 @@ batch already resident in HBM.  Rank 0 prints ONE JSON line.
                  their time, against the 157.3 TFLOP/s fp32 matrix peak.  `dense_families`
                  gives the same figure for each family of D's dense kernels (forward,
                  backward-data, weight gradient) and their time-weighted mean.
-  cpu_baseline : the CPU oracle (plain torch restatement, oracle/) timed on this host on
+  g_forward    : (--full) the generator's forward alone (config C2), 3 + 20 calls after the timed region.
+  phases       : (--full) 3 more G+D steps with an event between their network passes: where a step goes.
+  cpu_baseline : (--full, one rank) the CPU oracle (plain torch restatement, oracle/) timed on this host on
                  the SAME configuration (C3: 256x256, bs 16; 1 warm-up + 3 steps, all cores
                  of the affinity mask), plus the G-output L1 between the HIP path and it.
 """
@@ -80,11 +88,15 @@ def parse_args(argv=None):
     ap.add_argument("--dtype", default="f32", choices=("f32", "bf16"),
                     help="storage type of the discriminator's activations / packed weights (accumulation, statistics, "
                          "master weights and Adam stay fp32); bf16 is config C5")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the G forward alone (g_forward), the per-pass breakdown "
+                         "of a step (phases) and, on one rank, the CPU oracle (cpu_baseline); a plain run prints the "
+                         "headline and the live roofline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse "
                                                       "the N>1 code path where ranks must share one GPU)")
-    ap.add_argument("--no-gfwd", action="store_true", help="skip the side measurement of the G forward (clean profiles)")
-    ap.add_argument("--no-phases", action="store_true", help="skip the per-pass breakdown of one step (clean profiles)")
+    ap.add_argument("--no-gfwd", action="store_true", help="with --full: skip the side measurement of the G forward")
+    ap.add_argument("--no-phases", action="store_true", help="with --full: skip the per-pass breakdown of one step")
     ap.add_argument("--norm", default="batch", choices=("batch", "instance", "instance_affine"),
                     help="generator norm layers: the reference's BatchNorm (default, the headline) or north_star's InstanceNorm")
     ap.add_argument("--lr", type=float, default=1e-6,
@@ -517,14 +529,18 @@ def main():
                                     "tflops": rate(summ_all[best]) if summ_all else 0.0,
                                     "frac": rate(summ_all[best]) / peak if summ_all else 0.0},
                     "dense_kernels": per_kernel, "dense_families": fam_out}
-        # G-forward-only (config C2) on the side: not part of `value`
+        # the side measurements of --full: after the timed region, not part of `value`
+        side_gfwd = args.full and not args.no_gfwd
+        side_phases = args.full and not args.no_phases
+        side_cpu = args.full and not args.no_cpu_baseline and world == 1
+        # G-forward-only (config C2)
         g_fwd_ms = None
         with torch.no_grad():
-            for _ in range(0 if args.no_gfwd else 3):
+            for _ in range(3 if side_gfwd else 0):
                 gan.generator(batch["t1w"])
             torch.cuda.synchronize()
             t1 = time.perf_counter()
-            reps = 0 if args.no_gfwd else 20
+            reps = 20 if side_gfwd else 0
             for _ in range(reps):
                 gan.generator(batch["t1w"])
             torch.cuda.synchronize()
@@ -538,10 +554,10 @@ def main():
         g_fwd_flops = g_flops_sample * args.batch
         g_peak = PEAK_BF16_TFLOPS if (args.dtype == "bf16" and args.dims == 3) else PEAK_FP32_TFLOPS
         d_flops_sample = (step_flops_sample - 4 * g_flops_sample) / 8
-        # where the step's time goes: the same step once more with an event between its network passes (after the
-        # timed region: not part of `value`), each pass priced at the peak of the pipe it runs on
+        # where the step's time goes: the same step once more with an event between its network passes, each pass
+        # priced at the peak of the pipe it runs on
         phases = None
-        if not args.no_phases:
+        if side_phases:
             d_peak = PEAK_BF16_TFLOPS if args.dtype == "bf16" else PEAK_FP32_TFLOPS
             phases = []
             # (C5: the generator's matrix products run on the bf16 pipe too since round 4 -- priced there)
@@ -584,8 +600,9 @@ def main():
                 "mfma_frac": g_fwd_flops / (g_fwd_ms * 1e-3) / 1e12 / g_peak},
             "losses": losses,
         }
-        note(f"G forward {g_fwd_ms} ms")
-        if world == 1 and not args.no_cpu_baseline:
+        if side_gfwd:
+            note(f"G forward {g_fwd_ms} ms")
+        if side_cpu:
             out["cpu_baseline"] = (cpu_baseline_leg(gan, spatial) if args.dims == 2 else
                                    cpu_baseline_leg(gan, spatial, sample_bs=1, timed_steps=1, warmup=0))
             note("cpu baseline done")

@@ -232,3 +232,9 @@ def test_bench_refuses_zero_steps():
     for bad in (["--steps", "0"], ["--warmup", "-1"]):
         with pytest.raises(SystemExit):
             bench.parse_args(bad)
+
+
+def test_bench_side_measurements_are_opt_in():
+    """A plain bench run takes only the headline; g_forward, phases and cpu_baseline need --full."""
+    import bench
+    assert not bench.parse_args([]).full and bench.parse_args(["--full"]).full

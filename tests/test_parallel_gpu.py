@@ -65,8 +65,8 @@ def test_two_ranks_fit_batch_data_parallel(tmp_path):
     (["--dims", "3", "--size", "40", "--batch", "2", "--dtype", "bf16"], "volumes/s", "bf16", 2500.0, 2),   # C5's path
 ])
 def test_bench_line_contract_small_size(extra, unit, dtype, peak, per_step, tmp_path):
-    """bench.py at a small size (one rank, no CPU baseline): ONE JSON line on stdout with the driver's keys, the
-    roofline object -- its kernel chosen by measured time and named as rocprofv3 would name it, the best kernel
+    """bench.py --full at a small size (one rank, no CPU baseline): ONE JSON line on stdout with the driver's keys,
+    the roofline object -- its kernel chosen by measured time and named as rocprofv3 would name it, the best kernel
     beside it -- the per-pass `phases` of one step and the rank count seen by a collective; --dump-outputs writes
     the last timed step's results.  Second case: the 3-D bf16-storage configuration (BASELINE config C5's code path)."""
     import json
@@ -76,7 +76,8 @@ def test_bench_line_contract_small_size(extra, unit, dtype, peak, per_step, tmp_
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     dump = tmp_path / "outputs"
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), *extra, "--steps", "2", "--warmup", "1",
-                          "--no-cpu-baseline", "--no-gfwd", "--dense-min-gflop", "0.05", "--dump-outputs", str(dump)],
+                          "--full", "--no-cpu-baseline", "--no-gfwd", "--dense-min-gflop", "0.05",
+                          "--dump-outputs", str(dump)],
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -118,3 +119,38 @@ def test_bench_line_contract_small_size(extra, unit, dtype, peak, per_step, tmp_
         assert float(got[k]) == v, (k, float(got[k]), v)
     assert got["generated"].shape[0] == per_step and np.abs(got["generated"]).max() <= 1.0
     assert np.abs(got["generator_grads"]).max() > 0 and np.abs(got["discriminator_grads"]).max() > 0
+
+
+def test_bench_plain_run_leaves_the_side_measurements_to_full(tmp_path):
+    """A plain bench.py run prints the headline and the live roofline but takes none of the side measurements;
+    --full adds g_forward, phases and cpu_baseline after the timed region.  Both write the same outputs of the last
+    timed step, so the side measurements change nothing the headline run computes."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, dumps = {}, {}
+    for mode in ("plain", "full"):
+        dumps[mode] = tmp_path / mode
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--size", "64", "--batch", "4",
+                              "--steps", "2", "--warmup", "1", "--dense-min-gflop", "0.05",
+                              "--dump-outputs", str(dumps[mode])] + (["--full"] if mode == "full" else []),
+                             capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-2000:]
+        rows = [ln for ln in out.stdout.splitlines() if ln.strip()]
+        assert len(rows) == 1, rows
+        lines[mode] = json.loads(rows[0])
+    plain, full = lines["plain"], lines["full"]
+    for j in (plain, full):
+        assert j["metric"] == "T1->T2 256x256 slices/sec (G+D step)" and j["unit"] == "slices/s"
+        assert j["higher_is_better"] is True and j["dtype"] == "f32" and j["steps"] == 2 and j["warmup"] == 1
+        assert abs(j["value"] - 4 * 1000.0 / j["ms_per_step"]) < 1e-6 * j["value"]
+        assert 0.0 < j["roofline"]["frac"] < 1.0
+    assert plain["phases"] is None and plain["g_forward"] is None and "cpu_baseline" not in plain
+    assert len(full["phases"]) > 0 and full["g_forward"]["ms"] > 0.0
+    assert full["cpu_baseline"]["value"] > 0.0 and full["cpu_baseline"]["g_output_l1_vs_cpu"] < 1e-3
+    names = sorted(f.name for f in dumps["plain"].glob("*.npy"))
+    assert names and names == sorted(f.name for f in dumps["full"].glob("*.npy"))
+    for name in names:
+        assert np.array_equal(np.load(dumps["plain"] / name), np.load(dumps["full"] / name)), name

@@ -12,7 +12,7 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 SQ="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_VALU SQ_WAVES SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE"
 if [[ $PART == *a* ]]; then
-echo "[a1] default bench"; python3 $R/bench.py > $O/bench_default.json 2> $O/bench_default.err
+echo "[a1] default bench"; python3 $R/bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 cat $O/bench_default.err $O/bench_default.json > $O/bench_default.log
 echo "[a2] kernel stats, default bench"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_default -- python3 $R/bench.py --no-cpu-baseline --no-gfwd --no-phases > $O/stats_default.log 2>&1
@@ -44,7 +44,7 @@ rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_c5_write
 fi
 if [[ $PART == *c* ]]; then
 echo "[c1] C5: bf16 storage 3-D line + kernel stats"
-python3 $R/bench.py --dims 3 --size 128 --batch 4 --dtype bf16 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_c5_bf16.json 2> $O/bench_c5_bf16.err
+python3 $R/bench.py --dims 3 --size 128 --batch 4 --dtype bf16 --steps 5 --warmup 2 --full --no-cpu-baseline > $O/bench_c5_bf16.json 2> $O/bench_c5_bf16.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c5_bf16 -- python3 $R/bench.py --dims 3 --size 128 --batch 4 --dtype bf16 --steps 3 --warmup 1 --no-cpu-baseline --no-gfwd --no-phases > $O/stats_c5_bf16.log 2>&1
 python3 $R/tools/phase_times.py --dims 3 --size 128 --batch 4 --dtype bf16 --steps 3 --probe gfwd > $O/c5_gfwd_calls.txt 2>&1
 python3 $R/tools/phase_times.py --dims 3 --size 128 --batch 4 --dtype bf16 --steps 3 --probe gbwd > $O/c5_gbwd_calls.txt 2>&1
