@@ -87,29 +87,22 @@ static int launch_wgrad_mm16_variant(const WgradParams& p, hipStream_t st) {
 }
 
 template <int PRO>
-static int dispatch_wgrad_mm16(const WgradParams& p, int BD, int BG, hipStream_t st, bool& handled) {
-  handled = true;
-  const bool nopad = (p.pz | p.py | p.px) == 0;
-  if (BD == 128 && BG == 128) {
-    if (nopad) return launch_wgrad_mm16_variant<128, 128, 2, 2, 2, PRO, false>(p, st);
-    return launch_wgrad_mm16_variant<128, 128, 2, 2, 2, PRO, true>(p, st);
-  }
+static int launch_wgrad_mm16_pad(const WgradParams& p, int BD, int BG, hipStream_t st) {
+  if (BD == 128 && BG == 128) return launch_wgrad_mm16_variant<128, 128, 2, 2, 2, PRO, true>(p, st);
   if (BD == 128 && BG == 64) return launch_wgrad_mm16_variant<128, 64, 1, 2, 1, PRO, true>(p, st);
   if (BD == 64 && BG == 128) return launch_wgrad_mm16_variant<64, 128, 2, 1, 4, PRO, true>(p, st);
   if (BD == 64 && BG == 64) return launch_wgrad_mm16_variant<64, 64, 1, 1, 2, PRO, true>(p, st);
   if (BD == 32 && BG == 128) return launch_wgrad_mm16_variant<32, 128, 1, 1, 4, PRO, true>(p, st);
-  if (BD == 128 && BG == 32) return launch_wgrad_mm16_variant<128, 32, 1, 1, 1, PRO, true>(p, st);
-  handled = false;
-  return MPGAN_OK;
+  return launch_wgrad_mm16_variant<128, 32, 1, 1, 1, PRO, true>(p, st);
 }
 
-// The pipelined weight gradient with bf16 matrix operands; `handled` = false: this tile shape has no such instance
-// (the caller runs the fp32 kernel).  Same tiles, splits and slabs as the fp32 form: the reducer is unchanged.
-int launch_wgrad_mm16(const WgradParams& p, int BD, int BG, hipStream_t st, bool& handled) {
-  static const bool off = dev_env("MPGAN_DBG_NO_MM16") != nullptr;
-  handled = false;
-  if (off) return MPGAN_OK;
-  return p.pro.scale ? dispatch_wgrad_mm16<1>(p, BD, BG, st, handled) : dispatch_wgrad_mm16<0>(p, BD, BG, st, handled);
+// The instance of an Mm16 choice (choose_wgrad, conv_wgrad.hip): tile BD x BG (one of the six K-stepped tiles with one
+// wave per K-step), PRO 0 / 1, PAD = false for the 128 x 128 tile of a pad-free conv.  Same tiles, splits and slabs as
+// the fp32 form: the reducer is unchanged.
+int launch_wgrad_mm16(const WgradParams& p, int BD, int BG, int pro, bool pad, hipStream_t st) {
+  if (!pad) return pro ? launch_wgrad_mm16_variant<128, 128, 2, 2, 2, 1, false>(p, st)
+                       : launch_wgrad_mm16_variant<128, 128, 2, 2, 2, 0, false>(p, st);
+  return pro ? launch_wgrad_mm16_pad<1>(p, BD, BG, st) : launch_wgrad_mm16_pad<0>(p, BD, BG, st);
 }
 
 }  // namespace mpgan

@@ -404,7 +404,7 @@ __global__ __launch_bounds__(256) void wgrad_bias_reduce_kernel(const float* __r
 // through the same deterministic slab reducer as the MFMA path.
 // ---------------------------------------------------------------------------
 template <int V, int T, bool DENSE_BF16 = false>
-__global__ __launch_bounds__(256) void thin_wgrad_kernel(const WgradParams p) {
+__global__ __launch_bounds__(256) void wgrad_thin_kernel(const WgradParams p) {
   extern __shared__ float red[];                 // [PL][Cd*T + Cd]
   const int CQ = (p.Cd + V - 1) / V;
   const int PL = 256 / CQ;                       // pixel lanes
@@ -522,7 +522,7 @@ __global__ __launch_bounds__(256) void thin_wgrad_kernel(const WgradParams p) {
 // its already-counted pixels masked, so nothing is read past the row.
 // ---------------------------------------------------------------------------
 template <int T, bool DENSE_BF16>
-__global__ __launch_bounds__(256) void thin_wgrad_rows_kernel(const WgradParams p) {
+__global__ __launch_bounds__(256) void wgrad_thin_rows_kernel(const WgradParams p) {
   __shared__ float red[4][64 * T + 64];
   constexpr int KZ = T == 27 ? 3 : 1;
   const int lane = threadIdx.x & 63;
@@ -578,17 +578,11 @@ __global__ __launch_bounds__(256) void thin_wgrad_rows_kernel(const WgradParams 
   }
 }
 
+// The geometry wgrad_thin_rows_kernel walks (a 1 -> 64 pad-free stride-1 3x3 / 3x3x3 conv).
 static bool thin_rows_ok(const WgradParams& p, int T) {
-  static const bool off = dev_env("MPGAN_DBG_NO_THIN_ROWS") != nullptr;
-  return !off && p.Cd == 64 && p.Cg == 1 && p.ldg == 1 && !p.pro.scale && (T == 9 || T == 27) && p.Kx == 3 && p.Ky == 3 &&
+  return p.Cd == 64 && p.Cg == 1 && p.ldg == 1 && !p.pro.scale && (T == 9 || T == 27) && p.Kx == 3 && p.Ky == 3 &&
          p.Kz == (T == 27 ? 3 : 1) && p.sz == 1 && p.sy == 1 && p.sx == 1 && p.pz == 0 && p.py == 0 && p.px == 0 && p.Mx >= 4 &&
          p.Gx == p.Mx + 2 && p.Gy == p.My + 2 && p.Gz == p.Mz + (T == 27 ? 2 : 0);
-}
-
-template <bool DENSE_BF16>
-static void launch_thin_rows(const WgradParams& p, int T, int blocks, hipStream_t st) {
-  if (T == 9) hipLaunchKernelGGL((thin_wgrad_rows_kernel<9, DENSE_BF16>), dim3(blocks), dim3(256), 0, st, p);
-  else hipLaunchKernelGGL((thin_wgrad_rows_kernel<27, DENSE_BF16>), dim3(blocks), dim3(256), 0, st, p);
 }
 
 // ---------------------------------------------------------------------------
@@ -775,8 +769,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_patch3d_c16_kernel(const WgradPa
 }
 
 static bool wgrad_p3_geom_ok(const mpgan_conv_geom* g) {
-  static const bool off = dev_env("MPGAN_DBG_NO_PATCH3D") != nullptr;
-  if (off || g->transposed || g->cin != 16 || g->cout != 16) return false;
+  if (g->transposed || g->cin != 16 || g->cout != 16) return false;
   for (int d = 0; d < 3; ++d)
     if (g->k[d] != 3 || g->stride[d] != 1 || g->pad[d] < 0 || g->pad[d] > 1) return false;
   return g->out_dhw[0] >= 2 && g->out_dhw[1] >= 4 && g->out_dhw[2] >= 4;
@@ -981,12 +974,11 @@ __global__ __launch_bounds__(256, 2) void wgrad_patch2d_kernel(const WgradParams
   }
 }
 
-// Which instance (if any) serves this conv: 0 none, else an index into the dispatch below.
-struct WP2Plan { int inst, blocks, tiles_y, tiles_x, ntiles, Cd, Cg; };
-static WP2Plan wgrad_p2_plan(const mpgan_conv_geom* g) {
+// Which instance (if any) serves this conv: inst 0 none, else an index into launch_wgrad_p2 below.
+struct WP2Plan { int inst, blocks, tiles_y, tiles_x, ntiles, Cd, Cg, S, tx, smem; };
+static WP2Plan wgrad_p2_plan(const mpgan_conv_geom* g, int cap_override) {
   WP2Plan pl{};
-  static const bool off = dev_env("MPGAN_DBG_NO_WPATCH2D") != nullptr;
-  if (off || g->k[0] != 1 || g->k[1] != 3 || g->k[2] != 3 || g->in_dhw[0] != 1 || g->out_dhw[0] != 1) return pl;
+  if (g->k[0] != 1 || g->k[1] != 3 || g->k[2] != 3 || g->in_dhw[0] != 1 || g->out_dhw[0] != 1) return pl;
   if (g->pad[1] != 1 || g->pad[2] != 1 || g->stride[1] != g->stride[2] || g->stride[1] < 1 || g->stride[1] > 2) return pl;
   const int S = g->stride[1];
   int Cd, Cg, My, Mx;
@@ -1001,13 +993,12 @@ static WP2Plan wgrad_p2_plan(const mpgan_conv_geom* g) {
   // Blocks are capped so that the slabs (Cd x 9 x Cg floats per block) stay within ~4.7 MB: the reducer's time is
   // their traffic, and every block must still walk several tiles for the prefetch to pay.  32 -> 64 channels
   // (72 KB slabs: 64 blocks) is left to the K-stepped kernel.
-  int inst = 0, tx = 16, cap = 512;
-  if (S == 1 && Cd == 16 && Cg == 16) { inst = 1; cap = 512; }
-  else if (S == 1 && Cd == 32 && Cg == 32) { inst = 2; cap = 128; }
-  else if (S == 2 && Cd == 32 && Cg == 16) { inst = 3; cap = 256; }
-  else if (S == 2 && Cd == 64 && Cg == 16) { inst = 5; tx = 8; cap = 128; }
-  static const int cap_env = dev_env("MPGAN_DBG_WPATCH2D_BLOCKS") ? atoi(dev_env("MPGAN_DBG_WPATCH2D_BLOCKS")) : 0;
-  if (cap_env > 0) cap = cap_env;
+  int inst = 0, tx = 16, cap = 512, smem = 0;
+  if (S == 1 && Cd == 16 && Cg == 16) { inst = 1; cap = 512; smem = WP2<16, 16, 1, 16>::SMEM; }
+  else if (S == 1 && Cd == 32 && Cg == 32) { inst = 2; cap = 128; smem = WP2<32, 32, 1, 16>::SMEM; }
+  else if (S == 2 && Cd == 32 && Cg == 16) { inst = 3; cap = 256; smem = WP2<32, 16, 2, 16>::SMEM; }
+  else if (S == 2 && Cd == 64 && Cg == 16) { inst = 5; tx = 8; cap = 128; smem = WP2<64, 16, 2, 8>::SMEM; }
+  if (cap_override > 0) cap = cap_override;
   if (!inst || My < 4 || Mx < 4) return pl;
   pl.tiles_y = (My + WP2_TY - 1) / WP2_TY;
   pl.tiles_x = (Mx + tx - 1) / tx;
@@ -1015,7 +1006,7 @@ static WP2Plan wgrad_p2_plan(const mpgan_conv_geom* g) {
   if (nt >= (1L << 31)) return pl;
   pl.ntiles = (int)nt;
   pl.blocks = (int)(nt < cap ? nt : cap);                      // persistent blocks, each walking its range of tiles
-  pl.inst = inst; pl.Cd = Cd; pl.Cg = Cg;
+  pl.inst = inst; pl.Cd = Cd; pl.Cg = Cg; pl.S = S; pl.tx = tx; pl.smem = smem;
   return pl;
 }
 
@@ -1040,8 +1031,20 @@ static int launch_wgrad_p2(const WgradParams& p, const WP2Plan& pl, hipStream_t 
   return check_launch("wgrad_patch2d");
 }
 
-struct ThinWgradPlan { int blocks; long chunk; bool ok; int rounds; };
-static ThinWgradPlan plan_thin_wgrad(int Cd, int Cg, int T, long M, bool has_pro, long lds_cap = 64 * 1024) {
+// Lane-row fold rounds of wgrad_thin_kernel (PL rows of Cd * T + Cd floats): halve the rows until they fit lds_cap.
+static int thin_fold_rounds(int Cd, int T, int V, long lds_cap) {
+  const int PL = 256 / ((Cd + V - 1) / V);
+  int rounds = 1;
+  while (rounds < 8 && (PL / rounds) % 2 == 0 && (long)(PL / rounds) * (Cd * T + Cd) * 4 > lds_cap) rounds *= 2;
+  return rounds;
+}
+
+static long thin_lds_bytes(int Cd, int T, int V, int rounds) {
+  return (long)(256 / ((Cd + V - 1) / V) / rounds) * (Cd * T + Cd) * 4;
+}
+
+struct ThinWgradPlan { int blocks; long chunk; bool ok; };
+static ThinWgradPlan plan_thin_wgrad(int Cd, int Cg, int T, long M, bool has_pro, long lds_cap) {
   ThinWgradPlan t;
   t.ok = Cg == 1 && !has_pro && Cd <= 64 && (T == 1 || T == 9 || T == 27);   // kernel shape checked by the caller
   // latency-bound pixel walk: short chunks keep every CU busy, but each block pays a fixed LDS fold
@@ -1052,16 +1055,14 @@ static ThinWgradPlan plan_thin_wgrad(int Cd, int Cg, int T, long M, bool has_pro
   if (blocks < 1) blocks = 1;
   t.chunk = (M + blocks - 1) / blocks;
   t.blocks = (int)((M + t.chunk - 1) / t.chunk);
-  // LDS: PL * (Cd*T + Cd) floats must fit 64 KiB
+  // the lane rows must fit lds_cap for the V = 4 lanes of a 16-byte aligned operand (an unaligned one walks scalar
+  // lanes: fewer rows)
   const int V = Cd % 4 == 0 ? 4 : 1;
-  const int CQ = (Cd + V - 1) / V;
-  const int PL = 256 / CQ;
-  t.rounds = 1;                                  // fold rounds of the lane rows (thin_wgrad_kernel): halve the LDS rows until they fit
-  while (t.rounds < 4 && (PL / t.rounds) % 2 == 0 && (long)(PL / t.rounds) * (Cd * T + Cd) * 4 > lds_cap) t.rounds *= 2;
-  if ((long)(PL / t.rounds) * (Cd * T + Cd) * 4 > lds_cap) t.ok = false;
+  const int rounds = thin_fold_rounds(Cd, T, V, lds_cap);
+  if (thin_lds_bytes(Cd, T, V, rounds) > lds_cap) t.ok = false;
   // measured at C5 (128^3, bs 4): 1 -> 16 stride 2 (16 dense channels, two rounds) 136 -> 110 us against the generic
   // MFMA kernel, but ConvTranspose 32 -> 1 (32 dense channels: 108 accumulators over only 32 pixel lanes) 141 -> 187 us
-  if (t.rounds > 1 && Cd > 16) t.ok = false;
+  if (rounds > 1 && Cd > 16) t.ok = false;
   return t;
 }
 
@@ -1103,75 +1104,310 @@ static WgradPlan plan_wgrad(int Cd, int NC, long M) {
   return pl;
 }
 
+// Workspace of a form: `slabs` partial slabs of Cd x NC floats, then `bias_slabs` rows of Cd bias sums.
+static int64_t slab_bytes(int slabs, int bias_slabs, int Cd, int NC) {
+  return ((int64_t)slabs * Cd * NC + (int64_t)bias_slabs * Cd) * (int64_t)sizeof(float);
+}
+
+// The K-stepped instances' wave layout of a BD x BG tile: TM x TN MFMA tiles per wave, WN waves across the columns,
+// KW = 4: each wave owns the whole tile and a quarter of each K-step (plan_wgrad picks KW = 4 for the small tiles).
+struct WTile { int tm, tn, wn, kw; };
+static WTile wgrad_tile(int BD, int BG) {
+  if (BD == 128) return BG == 128 ? WTile{2, 2, 2, 1} : (BG == 64 ? WTile{1, 2, 1, 1} : WTile{1, 1, 1, 1});
+  if (BD == 64) return BG == 128 ? WTile{2, 1, 4, 1} : (BG == 64 ? WTile{1, 1, 2, 1} : WTile{2, 1, 1, 4});
+  return BG == 128 ? WTile{1, 1, 4, 1} : (BG == 64 ? WTile{1, 2, 1, 4} : WTile{1, 1, 1, 4});
+}
+
+// ---------------------------------------------------------------------------
+// Which kernel serves a weight gradient.  choose_wgrad() is the ONE place the form is decided: both entry points run
+// its choice, and the workspace and label queries read the choice made for the stand-in operands an entry point
+// would be given (standin_wgrad), so a query cannot disagree with its launch.
+// ---------------------------------------------------------------------------
+enum class WForm {
+  Patch3d,    // wgrad_patch3d_c16_kernel<HAS_PRO, MM16>
+  Patch2d,    // wgrad_patch2d_kernel<CD, CG, S, TX, HAS_PRO>
+  ThinRows,   // wgrad_thin_rows_kernel<T, DENSE_BF16>
+  Thin,       // wgrad_thin_kernel<V, T, DENSE_BF16>
+  Mm16,       // wgrad_pipe_kernel<BD, BG, TM, TN, WN, PRO, PAD, true>   (conv_mm16.hip)
+  Pipe,       // wgrad_pipe_kernel<BD, BG, TM, TN, WN, PRO, PAD>
+  Generic,    // wgrad_kernel<BD, BG, TM, TN, WN, KW, SCALAR_D, SCALAR_G>
+};
+
+struct WgradChoice {
+  WForm form;
+  int rc;              // MPGAN_OK, or the status of a refusal whose message is `msg` (the entry point reports it)
+  const char* msg;
+  int bd, bg, pro;     // K-stepped forms: the tile and PRO; the patch forms: HAS_PRO
+  bool pad, sd, sg;    // Pipe / Mm16: PAD; Generic: SCALAR_D, SCALAR_G
+  bool mm16;           // Patch3d: MM16
+  int v, t;            // thin forms: V (Thin), T
+  bool bf16;           // thin forms: DENSE_BF16
+  WP2Plan p2;          // Patch2d: instance and tiles
+  int grid, smem;      // blocks and dynamic LDS bytes of the form's launch
+  int fold_rounds;     // Thin
+  long chunk;          // K-stepped and thin forms: pixels per block / split
+  int nsplit, tiles_c, tiles_d;   // K-stepped forms
+  int slabs, bias_slabs;          // partial slabs and bias rows the reducer sums
+  bool narrow;         // the reducer: wgrad_reduce_narrow_kernel, else wgrad_reduce_kernel
+  int64_t ws;          // workspace bytes of the slabs
+};
+
+static bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+
+#define CHOICE_REFUSE(cond, m)            \
+  do {                                    \
+    if (cond) {                           \
+      c.rc = MPGAN_ERR_UNSUPPORTED;       \
+      c.msg = (m);                        \
+      return c;                           \
+    }                                     \
+  } while (0)
+
+static WgradChoice choose_wgrad(const mpgan_conv_geom* g, const WgradParams& p, bool bf16_dy) {
+  static const bool no_thin = dev_env("MPGAN_DBG_NO_THIN") != nullptr;
+  static const bool no_thin_rows = dev_env("MPGAN_DBG_NO_THIN_ROWS") != nullptr;
+  static const bool no_pipe = dev_env("MPGAN_DBG_NO_PIPE") != nullptr;
+  static const bool no_mm16 = dev_env("MPGAN_DBG_NO_MM16") != nullptr;
+  static const bool no_patch3d = dev_env("MPGAN_DBG_NO_PATCH3D") != nullptr;
+  static const bool no_patch2d = dev_env("MPGAN_DBG_NO_WPATCH2D") != nullptr;
+  static const int p2_blocks = dev_env("MPGAN_DBG_WPATCH2D_BLOCKS") ? atoi(dev_env("MPGAN_DBG_WPATCH2D_BLOCKS")) : 0;
+  WgradChoice c{};
+  c.rc = MPGAN_OK;
+  const int Cd = p.Cd, Cg = p.Cg, T = p.Kz * p.Ky * p.Kx;
+  const long M = (long)p.N * p.Mz * p.My * p.Mx;
+  const bool pro = p.pro.scale != nullptr;
+  // the thin kernels unroll 1, 3x3 and 3x3x3 taps only; a bf16 dy has the thin form alone (3-D 1 -> 64: 112 KiB of
+  // lane rows, one block per CU)
+  const bool kshape = T == 1 || (T == 9 && p.Kz == 1 && p.Ky == 3 && p.Kx == 3) || (T == 27 && p.Kz == 3 && p.Ky == 3 && p.Kx == 3);
+  const long thin_cap = bf16_dy ? 150 * 1024 : 64 * 1024;
+  const ThinWgradPlan tp = plan_thin_wgrad(Cd, Cg, T, M, pro, thin_cap);
+  if (bf16_dy)
+    CHOICE_REFUSE(!tp.ok || !kshape || Cd % 4 != 0 || p.ldd % 4 != 0 || (reinterpret_cast<uintptr_t>(p.dense) & 7),
+                  "conv_backward_weight_bf16dy: thin path only (Cout % 4 == 0, <= 64 channels, 1 / 3x3 / 3x3x3 kernel)");
+  // the patch forms read both operands (and the prologue's vectors) as 16-byte vectors
+  const bool vec = p.ldd % 4 == 0 && p.ldg % 4 == 0 && p.pro.n_stride == 0 && aligned16(p.dense) && aligned16(p.gath) &&
+                   (!pro || (aligned16(p.pro.scale) && aligned16(p.pro.shift)));
+  const WP2Plan p2 = bf16_dy || no_patch2d ? WP2Plan{} : wgrad_p2_plan(g, p2_blocks);
+  if (!bf16_dy && !no_patch3d && wgrad_p3_geom_ok(g) && vec) {   // one [16][432] slab + 16 bias sums per block
+    c.form = WForm::Patch3d;
+    c.pro = pro;
+    c.mm16 = (g->flags & MPGAN_CONV_MM_BF16) && !no_mm16;
+    c.grid = c.slabs = c.bias_slabs = wgrad_p3_blocks(g);
+  } else if (p2.inst && vec) {                                     // one [Cd][9 * Cg] slab + Cd bias sums per block
+    c.form = WForm::Patch2d;
+    c.pro = pro;
+    c.p2 = p2;
+    c.grid = c.slabs = c.bias_slabs = p2.blocks;
+    c.smem = p2.smem;
+  } else if (bf16_dy || (tp.ok && kshape && !no_thin)) {
+    c.form = !no_thin_rows && thin_rows_ok(p, T) ? WForm::ThinRows : WForm::Thin;
+    c.v = bf16_dy || (Cd % 4 == 0 && p.ldd % 4 == 0 && aligned16(p.dense)) ? 4 : 1;
+    c.t = T;
+    c.bf16 = bf16_dy;
+    c.fold_rounds = thin_fold_rounds(Cd, T, c.v, thin_cap);
+    const long lds = thin_lds_bytes(Cd, T, c.v, c.fold_rounds);
+    // (plan_thin_wgrad admitted these lane rows; beyond 64 KiB only the bf16-dy 3x3x3 instance is given more)
+    CHOICE_REFUSE(lds > 64 * 1024 && !(bf16_dy && T == 27), "conv_backward_weight: thin path lane rows exceed 64 KiB");
+    c.smem = c.form == WForm::Thin ? (int)lds : 0;
+    c.grid = c.slabs = c.bias_slabs = tp.blocks;
+    c.chunk = tp.chunk;
+  } else {
+    const WgradPlan pl = plan_wgrad(Cd, T * Cg, M);
+    const bool vd = Cd % 4 == 0 && p.ldd % 4 == 0 && aligned16(p.dense);
+    const bool vg = Cg % 4 == 0 && p.ldg % 4 == 0 && aligned16(p.gath) &&
+                    (!pro || (aligned16(p.pro.scale) && aligned16(p.pro.shift) && p.pro.n_stride % 4 == 0));
+    // the pipelined kernel addresses each operand as base + unsigned 32-bit byte offset
+    const bool small = M * p.ldd * 4 < (1L << 32) && (long)p.N * p.Gz * p.Gy * p.Gx * p.ldg * 4 < (1L << 32);
+    const bool piped = vd && vg && pl.kw == 1 && small && p.pro.n_stride == 0;
+    // PRO 3: LeakyReLU with a host-known slope in [0, 1] (the discriminator's layers); it and the pad-free variant
+    // exist for 128 x 128 tiles only
+    const bool fast_leaky = pro && p.pro.act == MPGAN_ACT_LEAKY && !p.pro.slope_ptr && p.pro.slope >= 0.f && p.pro.slope <= 1.f;
+    const bool nopad = (p.pz | p.py | p.px) == 0 && pl.BD == 128 && pl.BG == 128;
+    if (piped && (g->flags & MPGAN_CONV_MM_BF16) && !no_mm16) {   // bf16 matrix operands: same tiles, splits and slabs
+      c.form = WForm::Mm16;
+      c.pro = pro;
+      c.pad = !nopad;
+    } else if (piped && !no_pipe) {
+      c.form = WForm::Pipe;
+      c.pro = !pro ? 0 : (fast_leaky && nopad ? 3 : 1);
+      c.pad = !nopad;
+    } else {
+      c.form = WForm::Generic;
+      c.sd = !vd;
+      c.sg = !vg;
+    }
+    c.bd = pl.BD; c.bg = pl.BG;
+    c.smem = 2 * WBK * (pl.BD + pl.BG) * (int)sizeof(float) + (c.form == WForm::Generic ? 0 : 2 * 32 * 16);   // + row tables
+    c.nsplit = pl.nsplit; c.tiles_c = pl.tiles_c; c.tiles_d = pl.tiles_d;
+    c.grid = pl.tiles_c * pl.tiles_d * pl.nsplit;
+    c.chunk = pl.chunk;
+    c.slabs = pl.nsplit * pl.kw;
+    c.bias_slabs = pl.nsplit;
+  }
+  c.ws = slab_bytes(c.slabs, c.bias_slabs, Cd, T * Cg);
+  // the narrow reducer when the wide one would leave most CUs idle; a bf16 dy keeps the wide one (its summation order)
+  c.narrow = !bf16_dy && (long)Cd * Cg * T <= 32L * 512 && c.slabs >= 64;
+  return c;
+}
+#undef CHOICE_REFUSE
+
 template <int BD, int BG, int TM, int TN, int WN, int KW, bool SD, bool SG>
-static int launch_wgrad_variant(const WgradParams& p, const WgradPlan& pl, hipStream_t st) {
+static int launch_wgrad_variant(const WgradParams& p, const WgradChoice& c, hipStream_t st) {
   auto kern = wgrad_kernel<BD, BG, TM, TN, WN, KW, SD, SG>;
-  constexpr int smem = 2 * WBK * (BD + BG) * (int)sizeof(float);
   static bool attr_set = false;
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, c.smem);
     if (e != hipSuccess) {
       set_error("wgrad: hipFuncSetAttribute: %s", hipGetErrorString(e));
       return MPGAN_ERR_HIP;
     }
     attr_set = true;
   }
-  dim3 grid((unsigned)pl.tiles_c * pl.tiles_d * pl.nsplit);
-  hipLaunchKernelGGL(kern, grid, dim3(256), smem, st, p);
+  hipLaunchKernelGGL(kern, dim3(c.grid), dim3(256), c.smem, st, p);
   return check_launch("wgrad");
 }
 
 template <int BD, int BG, int TM, int TN, int WN, int PRO, bool PAD>
-static int launch_wgrad_pipe_variant(const WgradParams& p, const WgradPlan& pl, hipStream_t st) {
+static int launch_wgrad_pipe_variant(const WgradParams& p, const WgradChoice& c, hipStream_t st) {
   auto kern = wgrad_pipe_kernel<BD, BG, TM, TN, WN, PRO, PAD>;
-  constexpr int smem = 2 * WBK * (BD + BG) * (int)sizeof(float) + 2 * 32 * 16;   // + the row tables
   static bool attr_set = false;
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, c.smem);
     if (e != hipSuccess) {
       set_error("wgrad_pipe: hipFuncSetAttribute: %s", hipGetErrorString(e));
       return MPGAN_ERR_HIP;
     }
     attr_set = true;
   }
-  dim3 grid((unsigned)pl.tiles_c * pl.tiles_d * pl.nsplit);
-  hipLaunchKernelGGL(kern, grid, dim3(256), smem, st, p);
+  hipLaunchKernelGGL(kern, dim3(c.grid), dim3(256), c.smem, st, p);
   return check_launch("wgrad_pipe");
 }
 
-// PRO: 0 none, 1 per-channel norm + activation, 3 per-channel norm + LeakyReLU with a host-known
-// slope in [0, 1] (the discriminator's layers; 128 x 128 tiles only, as is the pad-free variant).
 template <int PRO>
-static int dispatch_wgrad_pipe(const WgradParams& p, const WgradPlan& pl, hipStream_t st, bool& handled) {
-  handled = true;
-  const bool nopad = (p.pz | p.py | p.px) == 0;
-  constexpr int P1 = PRO == 3 ? 1 : PRO;
-  if (pl.BD == 128 && pl.BG == 128) {
-    if (nopad) return launch_wgrad_pipe_variant<128, 128, 2, 2, 2, PRO, false>(p, pl, st);
-    return launch_wgrad_pipe_variant<128, 128, 2, 2, 2, P1, true>(p, pl, st);
-  }
-  if (pl.BD == 128 && pl.BG == 64) return launch_wgrad_pipe_variant<128, 64, 1, 2, 1, P1, true>(p, pl, st);
-  if (pl.BD == 64 && pl.BG == 128) return launch_wgrad_pipe_variant<64, 128, 2, 1, 4, P1, true>(p, pl, st);
-  if (pl.BD == 64 && pl.BG == 64) return launch_wgrad_pipe_variant<64, 64, 1, 1, 2, P1, true>(p, pl, st);
-  if (pl.BD == 32 && pl.BG == 128) return launch_wgrad_pipe_variant<32, 128, 1, 1, 4, P1, true>(p, pl, st);
-  if (pl.BD == 128 && pl.BG == 32) return launch_wgrad_pipe_variant<128, 32, 1, 1, 1, P1, true>(p, pl, st);
-  handled = false;
-  return MPGAN_OK;
+static int launch_wgrad_pipe(const WgradParams& p, const WgradChoice& c, hipStream_t st) {
+  if (c.bd == 128 && c.bg == 128) return launch_wgrad_pipe_variant<128, 128, 2, 2, 2, PRO, true>(p, c, st);
+  if (c.bd == 128 && c.bg == 64) return launch_wgrad_pipe_variant<128, 64, 1, 2, 1, PRO, true>(p, c, st);
+  if (c.bd == 64 && c.bg == 128) return launch_wgrad_pipe_variant<64, 128, 2, 1, 4, PRO, true>(p, c, st);
+  if (c.bd == 64 && c.bg == 64) return launch_wgrad_pipe_variant<64, 64, 1, 1, 2, PRO, true>(p, c, st);
+  if (c.bd == 32 && c.bg == 128) return launch_wgrad_pipe_variant<32, 128, 1, 1, 4, PRO, true>(p, c, st);
+  return launch_wgrad_pipe_variant<128, 32, 1, 1, 1, PRO, true>(p, c, st);
 }
 
 template <bool SD, bool SG>
-static int dispatch_wgrad(const WgradParams& p, const WgradPlan& pl, hipStream_t st) {
-  if (pl.BD == 128 && pl.BG == 128) return launch_wgrad_variant<128, 128, 2, 2, 2, 1, SD, SG>(p, pl, st);
-  if (pl.BD == 128 && pl.BG == 64) return launch_wgrad_variant<128, 64, 1, 2, 1, 1, SD, SG>(p, pl, st);
-  if (pl.BD == 128 && pl.BG == 32) return launch_wgrad_variant<128, 32, 1, 1, 1, 1, SD, SG>(p, pl, st);
-  if (pl.BD == 64 && pl.BG == 128) return launch_wgrad_variant<64, 128, 2, 1, 4, 1, SD, SG>(p, pl, st);
-  if (pl.BD == 64 && pl.BG == 64) return launch_wgrad_variant<64, 64, 1, 1, 2, 1, SD, SG>(p, pl, st);
-  if (pl.BD == 64 && pl.BG == 32) return launch_wgrad_variant<64, 32, 2, 1, 1, 4, SD, SG>(p, pl, st);
-  if (pl.BD == 32 && pl.BG == 128) return launch_wgrad_variant<32, 128, 1, 1, 4, 1, SD, SG>(p, pl, st);
-  if (pl.BD == 32 && pl.BG == 64) return launch_wgrad_variant<32, 64, 1, 2, 1, 4, SD, SG>(p, pl, st);
-  return launch_wgrad_variant<32, 32, 1, 1, 1, 4, SD, SG>(p, pl, st);
+static int launch_wgrad_generic(const WgradParams& p, const WgradChoice& c, hipStream_t st) {
+  if (c.bd == 128 && c.bg == 128) return launch_wgrad_variant<128, 128, 2, 2, 2, 1, SD, SG>(p, c, st);
+  if (c.bd == 128 && c.bg == 64) return launch_wgrad_variant<128, 64, 1, 2, 1, 1, SD, SG>(p, c, st);
+  if (c.bd == 128 && c.bg == 32) return launch_wgrad_variant<128, 32, 1, 1, 1, 1, SD, SG>(p, c, st);
+  if (c.bd == 64 && c.bg == 128) return launch_wgrad_variant<64, 128, 2, 1, 4, 1, SD, SG>(p, c, st);
+  if (c.bd == 64 && c.bg == 64) return launch_wgrad_variant<64, 64, 1, 1, 2, 1, SD, SG>(p, c, st);
+  if (c.bd == 64 && c.bg == 32) return launch_wgrad_variant<64, 32, 2, 1, 1, 4, SD, SG>(p, c, st);
+  if (c.bd == 32 && c.bg == 128) return launch_wgrad_variant<32, 128, 1, 1, 4, 1, SD, SG>(p, c, st);
+  if (c.bd == 32 && c.bg == 64) return launch_wgrad_variant<32, 64, 1, 2, 1, 4, SD, SG>(p, c, st);
+  return launch_wgrad_variant<32, 32, 1, 1, 1, 4, SD, SG>(p, c, st);
+}
+
+template <int V, bool BF16>
+static void launch_wgrad_thin(const WgradParams& p, const WgradChoice& c, hipStream_t st) {
+  if (c.t == 1) hipLaunchKernelGGL((wgrad_thin_kernel<V, 1, BF16>), dim3(c.grid), dim3(256), c.smem, st, p);
+  else if (c.t == 9) hipLaunchKernelGGL((wgrad_thin_kernel<V, 9, BF16>), dim3(c.grid), dim3(256), c.smem, st, p);
+  else hipLaunchKernelGGL((wgrad_thin_kernel<V, 27, BF16>), dim3(c.grid), dim3(256), c.smem, st, p);
+}
+
+// Runs the instance a choice names, then the fixed-order reducer over its slabs.
+static int launch_chosen(const WgradChoice& c, WgradParams p, float* dw, float* dbias, float beta, hipStream_t st) {
+  const int T = p.Kz * p.Ky * p.Kx;
+  p.chunk = c.chunk;
+  p.nsplit = c.nsplit; p.tiles_c = c.tiles_c; p.tiles_d = c.tiles_d;
+  p.fold_rounds = c.fold_rounds;
+  p.bias_partial = dbias ? p.partial + (int64_t)c.slabs * p.Cd * T * p.Cg : nullptr;
+  int rc = MPGAN_OK;
+  switch (c.form) {
+    case WForm::Patch3d: {
+      const WP3Grid tg{(p.Mz + WP3_TZ - 1) / WP3_TZ, (p.My + WP3_TY - 1) / WP3_TY, (p.Mx + WP3_TX - 1) / WP3_TX};
+      if (c.mm16 && c.pro) hipLaunchKernelGGL((wgrad_patch3d_c16_kernel<true, true>), dim3(c.grid), dim3(256), 0, st, p, tg);
+      else if (c.mm16) hipLaunchKernelGGL((wgrad_patch3d_c16_kernel<false, true>), dim3(c.grid), dim3(256), 0, st, p, tg);
+      else if (c.pro) hipLaunchKernelGGL(wgrad_patch3d_c16_kernel<true>, dim3(c.grid), dim3(256), 0, st, p, tg);
+      else hipLaunchKernelGGL(wgrad_patch3d_c16_kernel<false>, dim3(c.grid), dim3(256), 0, st, p, tg);
+      rc = check_launch("wgrad_patch3d_c16");
+      break;
+    }
+    case WForm::Patch2d:
+      switch (c.p2.inst) {
+        case 1: rc = launch_wgrad_p2<16, 16, 1, 16>(p, c.p2, st); break;
+        case 2: rc = launch_wgrad_p2<32, 32, 1, 16>(p, c.p2, st); break;
+        case 3: rc = launch_wgrad_p2<32, 16, 2, 16>(p, c.p2, st); break;
+        default: rc = launch_wgrad_p2<64, 16, 2, 8>(p, c.p2, st); break;
+      }
+      break;
+    case WForm::ThinRows:
+      if (c.bf16 && c.t == 9) hipLaunchKernelGGL((wgrad_thin_rows_kernel<9, true>), dim3(c.grid), dim3(256), 0, st, p);
+      else if (c.bf16) hipLaunchKernelGGL((wgrad_thin_rows_kernel<27, true>), dim3(c.grid), dim3(256), 0, st, p);
+      else if (c.t == 9) hipLaunchKernelGGL((wgrad_thin_rows_kernel<9, false>), dim3(c.grid), dim3(256), 0, st, p);
+      else hipLaunchKernelGGL((wgrad_thin_rows_kernel<27, false>), dim3(c.grid), dim3(256), 0, st, p);
+      rc = check_launch("wgrad_thin_rows");
+      break;
+    case WForm::Thin:
+      if (c.smem > 64 * 1024) {   // (the bf16-dy 3x3x3 instance only, see choose_wgrad)
+        static bool attr_set = false;
+        if (!attr_set) {
+          hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_thin_kernel<4, 27, true>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+          if (e != hipSuccess) { set_error("wgrad_thin: hipFuncSetAttribute: %s", hipGetErrorString(e)); return MPGAN_ERR_HIP; }
+          attr_set = true;
+        }
+      }
+      if (c.bf16) launch_wgrad_thin<4, true>(p, c, st);
+      else if (c.v == 4) launch_wgrad_thin<4, false>(p, c, st);
+      else launch_wgrad_thin<1, false>(p, c, st);
+      rc = check_launch("wgrad_thin");
+      break;
+    case WForm::Mm16: rc = launch_wgrad_mm16(p, c.bd, c.bg, c.pro, c.pad, st); break;
+    case WForm::Pipe:
+      if (!c.pad && c.pro == 3) rc = launch_wgrad_pipe_variant<128, 128, 2, 2, 2, 3, false>(p, c, st);
+      else if (!c.pad && c.pro) rc = launch_wgrad_pipe_variant<128, 128, 2, 2, 2, 1, false>(p, c, st);
+      else if (!c.pad) rc = launch_wgrad_pipe_variant<128, 128, 2, 2, 2, 0, false>(p, c, st);
+      else rc = c.pro ? launch_wgrad_pipe<1>(p, c, st) : launch_wgrad_pipe<0>(p, c, st);
+      break;
+    case WForm::Generic:
+      if (!c.sd && !c.sg) rc = launch_wgrad_generic<false, false>(p, c, st);
+      else if (!c.sd) rc = launch_wgrad_generic<false, true>(p, c, st);
+      else if (!c.sg) rc = launch_wgrad_generic<true, false>(p, c, st);
+      else rc = launch_wgrad_generic<true, true>(p, c, st);
+      break;
+  }
+  if (rc) return rc;
+  const long total = (long)p.Cd * p.Cg * T;
+  if (c.narrow) {
+    const int blocks = (int)((total + 7) / 8), bb = dbias ? (p.Cd + 7) / 8 : 0;
+    hipLaunchKernelGGL(wgrad_reduce_narrow_kernel, dim3(blocks + bb), dim3(256), 0, st, p.partial, dw, c.slabs, p.Cd, p.Cg,
+                       T, beta, p.bias_partial, c.bias_slabs, dbias, bb);
+  } else {
+    const int blocks = (int)((total + 31) / 32 < 8192 ? (total + 31) / 32 : 8192), bb = dbias ? (p.Cd + 31) / 32 : 0;
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks + bb), dim3(256), 0, st, p.partial, dw, c.slabs, p.Cd, p.Cg, T,
+                       beta, p.bias_partial, c.bias_slabs, dbias, bb);
+  }
+  return check_launch("wgrad_reduce");
+}
+
+// rocprofv3's name of the instance launch_chosen runs for a choice (without `void mpgan::` and the argument list).
+static int wgrad_kernel_name(const WgradChoice& c, char* buf, int len) {
+  const char* b[2] = {"false", "true"};
+  const WTile w = wgrad_tile(c.bd, c.bg);
+  switch (c.form) {
+    case WForm::Patch3d: return snprintf(buf, len, "wgrad_patch3d_c16_kernel<%s, %s>", b[c.pro != 0], b[c.mm16]);
+    case WForm::Patch2d:
+      return snprintf(buf, len, "wgrad_patch2d_kernel<%d, %d, %d, %d, %s>", c.p2.Cd, c.p2.Cg, c.p2.S, c.p2.tx, b[c.pro != 0]);
+    case WForm::ThinRows: return snprintf(buf, len, "wgrad_thin_rows_kernel<%d, %s>", c.t, b[c.bf16]);
+    case WForm::Thin: return snprintf(buf, len, "wgrad_thin_kernel<%d, %d, %s>", c.v, c.t, b[c.bf16]);
+    case WForm::Mm16:
+    case WForm::Pipe:
+      return snprintf(buf, len, "wgrad_pipe_kernel<%d, %d, %d, %d, %d, %d, %s, %s>", c.bd, c.bg, w.tm, w.tn, w.wn, c.pro,
+                      b[c.pad], b[c.form == WForm::Mm16]);
+    case WForm::Generic:
+      return snprintf(buf, len, "wgrad_kernel<%d, %d, %d, %d, %d, %d, %s, %s>", c.bd, c.bg, w.tm, w.tn, w.wn, w.kw, b[c.sd],
+                      b[c.sg]);
+  }
+  return snprintf(buf, len, "?");
 }
 
 }  // namespace mpgan
@@ -1189,30 +1425,87 @@ static void wgrad_dims(const mpgan_conv_geom* g, int& Cd, int& Cg, int& T, long&
   }
 }
 
-extern "C" int64_t mpgan_conv_wgrad_workspace(const mpgan_conv_geom* g) {
-  if (!g) return -1;
+// The workspace every fp32 launch checks first: the K-stepped form's.
+static int64_t generic_wgrad_bytes(const mpgan_conv_geom* g) {
   int Cd, Cg, T;
   long M;
   wgrad_dims(g, Cd, Cg, T, M);
-  WgradPlan pl = plan_wgrad(Cd, T * Cg, M);
-  int64_t need = ((int64_t)pl.nsplit * pl.kw * Cd * T * Cg + (int64_t)pl.nsplit * Cd) * (int64_t)sizeof(float);
-  ThinWgradPlan tp = plan_thin_wgrad(Cd, Cg, T, M, false);
-  if (tp.ok) {
-    const int64_t tneed = ((int64_t)tp.blocks * Cd * T + (int64_t)tp.blocks * Cd) * (int64_t)sizeof(float);
-    if (tneed > need) need = tneed;
+  const WgradPlan pl = plan_wgrad(Cd, T * Cg, M);
+  return slab_bytes(pl.nsplit * pl.kw, pl.nsplit, Cd, T * Cg);
+}
+
+// The GEMM view of a weight gradient (conv_wgrad.hip's head): dense = dy, gathered = x for a ConvNd, the other way
+// round for a ConvTransposeNd.  dy is bf16 data for the bf16-dy entry.
+static WgradParams wgrad_params(const mpgan_conv_geom* g, const float* x, int32_t ldx, const mpgan_prologue* pro,
+                                const void* dy, int32_t lddy, void* workspace, bool bf16_dy) {
+  WgradParams p{};
+  p.partial = static_cast<float*>(workspace);
+  p.Kz = g->k[0]; p.Ky = g->k[1]; p.Kx = g->k[2];
+  p.sz = g->stride[0]; p.sy = g->stride[1]; p.sx = g->stride[2];
+  p.pz = g->pad[0]; p.py = g->pad[1]; p.px = g->pad[2];
+  p.N = g->n;
+  if (!g->transposed) {
+    p.dense = static_cast<const float*>(dy); p.ldd = lddy; p.Cd = g->cout;
+    p.gath = x; p.ldg = ldx; p.Cg = g->cin;
+    p.pro = make_pro(pro);
+    p.Mz = g->out_dhw[0]; p.My = g->out_dhw[1]; p.Mx = g->out_dhw[2];
+    p.Gz = g->in_dhw[0]; p.Gy = g->in_dhw[1]; p.Gx = g->in_dhw[2];
+  } else {
+    p.dense = x; p.ldd = ldx; p.Cd = g->cin;
+    p.gath = static_cast<const float*>(dy); p.ldg = lddy; p.Cg = g->cout;
+    p.pro = make_pro(nullptr);
+    p.Mz = g->in_dhw[0]; p.My = g->in_dhw[1]; p.Mx = g->in_dhw[2];
+    p.Gz = g->out_dhw[0]; p.Gy = g->out_dhw[1]; p.Gx = g->out_dhw[2];
   }
-  if (wgrad_p3_geom_ok(g)) {                     // 3-D patch form: one [16][432] slab + 16 bias sums per persistent block
-    const int64_t pneed = (int64_t)wgrad_p3_blocks(g) * (16 * 432 + 16) * (int64_t)sizeof(float);
-    if (pneed > need) need = pneed;
-  }
-  {                                              // 2-D patch form: one [Cd][9 * Cg] slab + Cd bias sums per persistent block
-    const WP2Plan p2 = wgrad_p2_plan(g);
-    if (p2.inst) {
-      const int64_t pneed = (int64_t)p2.blocks * (p2.Cd * 9 * p2.Cg + p2.Cd) * (int64_t)sizeof(float);
-      if (pneed > need) need = pneed;
+  p.dense_bf16 = bf16_dy;
+  p.fMx = make_fastdiv(p.Mx); p.fMy = make_fastdiv(p.My); p.fMz = make_fastdiv(p.Mz);
+  return p;
+}
+
+// What a query decides from: the WgradParams an entry point builds for this geometry, with compact pitches and
+// 16-byte aligned stand-in operands (never dereferenced), or operands 4 bytes off that alignment.  pro_code as in
+// mpgan_conv_kernel_name: 0 none, 1 per channel, 2 per (sample, channel), 3 per channel with a LeakyReLU of host
+// slope in [0, 1].
+alignas(16) static float w_standin[8];
+static WgradChoice choose_standin(const mpgan_conv_geom* g, int pro_code, bool bf16_dy, bool aligned) {
+  mpgan_prologue pro{};
+  pro.scale = pro.shift = w_standin;
+  pro.n_stride = pro_code == 2 ? g->cin : 0;
+  pro.act = pro_code == 3 ? MPGAN_ACT_LEAKY : MPGAN_ACT_NONE;
+  pro.slope = pro_code == 3 ? 0.2f : 1.f;
+  float* op = aligned ? w_standin : w_standin + 1;
+  return choose_wgrad(g, wgrad_params(g, op, g->cin, pro_code ? &pro : nullptr, op, g->cout, w_standin, bf16_dy), bf16_dy);
+}
+
+extern "C" int64_t mpgan_conv_wgrad_workspace(const mpgan_conv_geom* g) {
+  if (!g) return -1;
+  int64_t need = generic_wgrad_bytes(g);
+  for (int pro_code = 0; pro_code <= (g->transposed ? 0 : 1); ++pro_code)
+    for (bool aligned : {true, false}) {
+      const WgradChoice c = choose_standin(g, pro_code, false, aligned);
+      if (c.rc == MPGAN_OK && c.ws > need) need = c.ws;
     }
-  }
   return need;
+}
+
+extern "C" int64_t mpgan_conv_wgrad_workspace_bf16dy(const mpgan_conv_geom* g) {
+  if (!g || g->transposed || g->cin != 1) return -1;
+  const WgradChoice c = choose_standin(g, 0, true, true);
+  return c.rc == MPGAN_OK ? c.ws : -1;
+}
+
+extern "C" int mpgan_conv_wgrad_kernel_name(const mpgan_conv_geom* g, int32_t pro_code, int32_t bf16_dy, char* buf,
+                                            int32_t len) {
+  MPGAN_CHECK_ARG(g && buf && len > 0 && pro_code >= 0 && pro_code <= 3,
+                  "conv_wgrad_kernel_name: no geometry / buffer or bad prologue code");
+  const WgradChoice c = choose_standin(g, bf16_dy ? 0 : pro_code, bf16_dy != 0, true);
+  if (c.rc != MPGAN_OK) {
+    set_error("%s", c.msg);
+    return c.rc;
+  }
+  const int n = wgrad_kernel_name(c, buf, len);
+  MPGAN_CHECK_ARG(n < len, "conv_wgrad_kernel_name: the name needs %d bytes", n + 1);
+  return MPGAN_OK;
 }
 
 extern "C" int mpgan_conv_backward_weight(const mpgan_conv_geom* g, const float* x, int32_t ldx,
@@ -1228,140 +1521,22 @@ extern "C" int mpgan_conv_backward_weight(const mpgan_conv_geom* g, const float*
                       (long)g->n * g->in_dhw[0] * g->in_dhw[1] * g->in_dhw[2] < (1L << 31) &&
                       (long)g->n * g->out_dhw[0] * g->out_dhw[1] * g->out_dhw[2] < (1L << 31),
                   "conv_backward_weight: more than 2^31 pixels");
-  WgradPlan pl = plan_wgrad(Cd, T * Cg, M);
-  const int64_t slab_floats = (int64_t)pl.nsplit * pl.kw * Cd * T * Cg;
-  const int64_t need = (slab_floats + (int64_t)pl.nsplit * Cd) * (int64_t)sizeof(float);
+  const int64_t need = generic_wgrad_bytes(g);
   MPGAN_CHECK_ARG(workspace_bytes >= need, "conv_backward_weight: workspace %lld < %lld bytes",
                   (long long)workspace_bytes, (long long)need);
-  WgradParams p{};
-  p.partial = static_cast<float*>(workspace);
   MPGAN_UNSUPPORTED(dbias && g->transposed,
                     "conv_backward_weight: fused bias gradient is for ConvNd only (dy is the gathered operand of a "
                     "transposed conv)");
-  p.bias_partial = dbias ? p.partial + slab_floats : nullptr;
-  p.Kz = g->k[0]; p.Ky = g->k[1]; p.Kx = g->k[2];
-  p.sz = g->stride[0]; p.sy = g->stride[1]; p.sx = g->stride[2];
-  p.pz = g->pad[0]; p.py = g->pad[1]; p.px = g->pad[2];
-  p.N = g->n;
-  p.nsplit = pl.nsplit; p.chunk = pl.chunk;
-  p.tiles_c = pl.tiles_c; p.tiles_d = pl.tiles_d;
-  if (!g->transposed) {
-    p.dense = dy; p.ldd = lddy; p.Cd = g->cout;
-    p.gath = x; p.ldg = ldx; p.Cg = g->cin;
-    p.pro = make_pro(pro);
-    p.Mz = g->out_dhw[0]; p.My = g->out_dhw[1]; p.Mx = g->out_dhw[2];
-    p.Gz = g->in_dhw[0]; p.Gy = g->in_dhw[1]; p.Gx = g->in_dhw[2];
-  } else {
-    MPGAN_UNSUPPORTED(pro && pro->scale, "conv_backward_weight: prologue on a transposed conv input");
-    p.dense = x; p.ldd = ldx; p.Cd = g->cin;
-    p.gath = dy; p.ldg = lddy; p.Cg = g->cout;
-    p.pro = make_pro(nullptr);
-    p.Mz = g->in_dhw[0]; p.My = g->in_dhw[1]; p.Mx = g->in_dhw[2];
-    p.Gz = g->out_dhw[0]; p.Gy = g->out_dhw[1]; p.Gx = g->out_dhw[2];
+  MPGAN_UNSUPPORTED(g->transposed && pro && pro->scale, "conv_backward_weight: prologue on a transposed conv input");
+  const WgradParams p = wgrad_params(g, x, ldx, pro, dy, lddy, workspace, false);
+  const WgradChoice c = choose_wgrad(g, p, false);
+  if (c.rc != MPGAN_OK) {
+    set_error("%s", c.msg);
+    return c.rc;
   }
-  p.fMx = make_fastdiv(p.Mx); p.fMy = make_fastdiv(p.My); p.fMz = make_fastdiv(p.Mz);
-  hipStream_t st0 = (hipStream_t)stream;
-  if (wgrad_p3_geom_ok(g) && p.ldd % 4 == 0 && p.ldg % 4 == 0 && p.pro.n_stride == 0 &&
-      ((reinterpret_cast<uintptr_t>(p.dense) | reinterpret_cast<uintptr_t>(p.gath)) & 15) == 0 &&
-      (!p.pro.scale || ((reinterpret_cast<uintptr_t>(p.pro.scale) | reinterpret_cast<uintptr_t>(p.pro.shift)) & 15) == 0)) {
-    const int nb = wgrad_p3_blocks(g);
-    const int64_t pslab = (int64_t)nb * 16 * 432;
-    MPGAN_CHECK_ARG(workspace_bytes >= (pslab + (int64_t)nb * 16) * (int64_t)sizeof(float),
-                    "conv_backward_weight: workspace too small for the 3-D patch form");
-    p.bias_partial = dbias ? p.partial + pslab : nullptr;
-    const WP3Grid tg{(p.Mz + WP3_TZ - 1) / WP3_TZ, (p.My + WP3_TY - 1) / WP3_TY, (p.Mx + WP3_TX - 1) / WP3_TX};
-    static const bool no_mm16 = dev_env("MPGAN_DBG_NO_MM16") != nullptr;
-    if ((g->flags & MPGAN_CONV_MM_BF16) && !no_mm16) {
-      if (p.pro.scale) hipLaunchKernelGGL((wgrad_patch3d_c16_kernel<true, true>), dim3(nb), dim3(256), 0, st0, p, tg);
-      else hipLaunchKernelGGL((wgrad_patch3d_c16_kernel<false, true>), dim3(nb), dim3(256), 0, st0, p, tg);
-    } else if (p.pro.scale) hipLaunchKernelGGL(wgrad_patch3d_c16_kernel<true>, dim3(nb), dim3(256), 0, st0, p, tg);
-    else hipLaunchKernelGGL(wgrad_patch3d_c16_kernel<false>, dim3(nb), dim3(256), 0, st0, p, tg);
-    int rcp = check_launch("wgrad_patch3d_c16");
-    if (rcp) return rcp;
-    launch_wgrad_reduce(st0, p.partial, dw, nb, 16, 16, 27, beta, p.bias_partial, nb, dbias);
-    return check_launch("wgrad_patch3d_reduce");
-  }
-  {
-    const WP2Plan p2 = wgrad_p2_plan(g);
-    if (p2.inst && p.ldd % 4 == 0 && p.ldg % 4 == 0 && p.pro.n_stride == 0 &&
-        ((reinterpret_cast<uintptr_t>(p.dense) | reinterpret_cast<uintptr_t>(p.gath)) & 15) == 0 &&
-        (!p.pro.scale || ((reinterpret_cast<uintptr_t>(p.pro.scale) | reinterpret_cast<uintptr_t>(p.pro.shift)) & 15) == 0)) {
-      const int64_t pslab = (int64_t)p2.blocks * Cd * 9 * Cg;
-      MPGAN_CHECK_ARG(workspace_bytes >= (pslab + (int64_t)p2.blocks * Cd) * (int64_t)sizeof(float),
-                      "conv_backward_weight: workspace too small for the 2-D patch form");
-      p.bias_partial = dbias ? p.partial + pslab : nullptr;
-      int rcp;
-      switch (p2.inst) {
-        case 1: rcp = launch_wgrad_p2<16, 16, 1, 16>(p, p2, st0); break;
-        case 2: rcp = launch_wgrad_p2<32, 32, 1, 16>(p, p2, st0); break;
-        case 3: rcp = launch_wgrad_p2<32, 16, 2, 16>(p, p2, st0); break;
-        default: rcp = launch_wgrad_p2<64, 16, 2, 8>(p, p2, st0); break;
-      }
-      if (rcp) return rcp;
-      launch_wgrad_reduce(st0, p.partial, dw, p2.blocks, Cd, Cg, 9, beta, p.bias_partial, p2.blocks, dbias);
-      return check_launch("wgrad_patch2d_reduce");
-    }
-  }
-  {
-    ThinWgradPlan tp = plan_thin_wgrad(Cd, Cg, T, M, p.pro.scale != nullptr);
-    const bool v4 = (p.Cd % 4 == 0) && (p.ldd % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.dense) & 15) == 0);
-    static const bool no_thin = dev_env("MPGAN_DBG_NO_THIN") != nullptr;
-    const bool kshape = (T == 1) || (T == 9 && p.Kz == 1 && p.Ky == 3 && p.Kx == 3) ||
-                        (T == 27 && p.Kz == 3 && p.Ky == 3 && p.Kx == 3);
-    if (tp.ok && kshape && !no_thin) {
-      const int64_t tslab = (int64_t)tp.blocks * Cd * T;
-      MPGAN_CHECK_ARG(workspace_bytes >= (tslab + (int64_t)tp.blocks * Cd) * (int64_t)sizeof(float),
-                      "conv_backward_weight: workspace too small for the thin path");
-      p.chunk = tp.chunk;
-      p.bias_partial = dbias ? p.partial + tslab : nullptr;
-      const int V = v4 ? 4 : 1;
-      const int CQ = (Cd + V - 1) / V, PL = 256 / CQ;
-      // (the plan assumed V = 4 where Cd % 4 == 0; an unaligned operand walks scalar lanes: more lane rows, same rule)
-      int rounds = 1;
-      while (rounds < 8 && (PL / rounds) % 2 == 0 && (size_t)(PL / rounds) * (Cd * T + Cd) * sizeof(float) > 64 * 1024) rounds *= 2;
-      p.fold_rounds = rounds;
-      const size_t smem = (size_t)(PL / rounds) * (Cd * T + Cd) * sizeof(float);
-      MPGAN_UNSUPPORTED(smem > 64 * 1024, "conv_backward_weight: thin path lane rows exceed 64 KiB");
-      dim3 grid(tp.blocks);
-#define THIN_LAUNCH(VV, TT) hipLaunchKernelGGL((thin_wgrad_kernel<VV, TT>), grid, dim3(256), smem, st0, p)
-      if (thin_rows_ok(p, T)) launch_thin_rows<false>(p, T, tp.blocks, st0);
-      else if (v4) { if (T == 1) THIN_LAUNCH(4, 1); else if (T == 9) THIN_LAUNCH(4, 9); else THIN_LAUNCH(4, 27); }
-      else    { if (T == 1) THIN_LAUNCH(1, 1); else if (T == 9) THIN_LAUNCH(1, 9); else THIN_LAUNCH(1, 27); }
-#undef THIN_LAUNCH
-      int rc0 = check_launch("thin_wgrad");
-      if (rc0) return rc0;
-      launch_wgrad_reduce(st0, p.partial, dw, tp.blocks, Cd, Cg, T, beta, p.bias_partial, tp.blocks, dbias);
-      return check_launch("thin_wgrad_reduce");
-    }
-  }
-  const bool vd = (p.Cd % 4 == 0) && (p.ldd % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.dense) & 15) == 0);
-  const bool vg = (p.Cg % 4 == 0) && (p.ldg % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.gath) & 15) == 0) &&
-                  (!p.pro.scale || (((reinterpret_cast<uintptr_t>(p.pro.scale) |
-                                      reinterpret_cast<uintptr_t>(p.pro.shift)) & 15) == 0 &&
-                                    p.pro.n_stride % 4 == 0));
-  hipStream_t st = (hipStream_t)stream;
-  int rc = MPGAN_OK;
-  bool handled = false;
-  static const bool no_pipe = dev_env("MPGAN_DBG_NO_PIPE") != nullptr;
-  // the pipelined kernel addresses each operand as base + unsigned 32-bit byte offset
-  const bool small = (long)M * p.ldd * 4 < (1L << 32) && (long)p.N * p.Gz * p.Gy * p.Gx * p.ldg * 4 < (1L << 32);
-  if ((g->flags & MPGAN_CONV_MM_BF16) && vd && vg && pl.kw == 1 && small && p.pro.n_stride == 0)
-    rc = launch_wgrad_mm16(p, pl.BD, pl.BG, st, handled);                // bf16 matrix operands (conv_mm16.hip)
-  if (!handled && vd && vg && pl.kw == 1 && small && p.pro.n_stride == 0 && !no_pipe) {
-    const bool fast_leaky = p.pro.scale && p.pro.act == MPGAN_ACT_LEAKY && !p.pro.slope_ptr && p.pro.slope >= 0.f &&
-                            p.pro.slope <= 1.f;
-    rc = !p.pro.scale ? dispatch_wgrad_pipe<0>(p, pl, st, handled)
-         : fast_leaky ? dispatch_wgrad_pipe<3>(p, pl, st, handled)
-                      : dispatch_wgrad_pipe<1>(p, pl, st, handled);
-  }
-  if (handled) { /* done */ }
-  else if (vd && vg) rc = dispatch_wgrad<false, false>(p, pl, st);
-  else if (vd) rc = dispatch_wgrad<false, true>(p, pl, st);
-  else if (vg) rc = dispatch_wgrad<true, false>(p, pl, st);
-  else rc = dispatch_wgrad<true, true>(p, pl, st);
-  if (rc) return rc;
-  launch_wgrad_reduce(st, p.partial, dw, pl.nsplit * pl.kw, Cd, Cg, T, beta, p.bias_partial, pl.nsplit, dbias);
-  return check_launch("wgrad_reduce");
+  MPGAN_CHECK_ARG(workspace_bytes >= c.ws, "conv_backward_weight: workspace too small for the %s",
+                  c.form == WForm::Patch3d ? "3-D patch form" : (c.form == WForm::Patch2d ? "2-D patch form" : "thin path"));
+  return launch_chosen(c, p, dw, dbias, beta, (hipStream_t)stream);
 }
 
 // Weight gradient of a 1 -> C ConvNd whose output gradient is stored as bf16 (D.conv1 in the bf16 path):
@@ -1375,64 +1550,12 @@ extern "C" int mpgan_conv_backward_weight_bf16dy(const mpgan_conv_geom* g, const
   long M;
   wgrad_dims(g, Cd, Cg, T, M);
   MPGAN_CHECK_ARG(M < (1L << 31) - 64, "conv_backward_weight_bf16dy: more than 2^31 pixels");
-  ThinWgradPlan tp = plan_thin_wgrad(Cd, Cg, T, M, false, 150 * 1024);   // 3-D 1 -> 64: 112 KiB of lane rows, one block per CU
-  const bool kshape = (T == 1) || (T == 9 && g->k[0] == 1) || (T == 27 && g->k[0] == 3 && g->k[1] == 3 && g->k[2] == 3);
-  MPGAN_UNSUPPORTED(!tp.ok || !kshape || Cd % 4 != 0 || lddy % 4 != 0 || (reinterpret_cast<uintptr_t>(dy) & 7),
-                    "conv_backward_weight_bf16dy: thin path only (Cout %% 4 == 0, <= 64 channels, 1 / 3x3 / 3x3x3 kernel)");
-  const int64_t tslab = (int64_t)tp.blocks * Cd * T;
-  MPGAN_CHECK_ARG(workspace_bytes >= (tslab + (int64_t)tp.blocks * Cd) * (int64_t)sizeof(float),
-                  "conv_backward_weight_bf16dy: workspace too small");
-  WgradParams p{};
-  p.partial = static_cast<float*>(workspace);
-  p.bias_partial = dbias ? p.partial + tslab : nullptr;
-  p.Kz = g->k[0]; p.Ky = g->k[1]; p.Kx = g->k[2];
-  p.sz = g->stride[0]; p.sy = g->stride[1]; p.sx = g->stride[2];
-  p.pz = g->pad[0]; p.py = g->pad[1]; p.px = g->pad[2];
-  p.N = g->n;
-  p.chunk = tp.chunk;
-  p.dense = static_cast<const float*>(dy); p.ldd = lddy; p.Cd = Cd; p.dense_bf16 = 1;
-  p.gath = x; p.ldg = ldx; p.Cg = 1;
-  p.pro = make_pro(nullptr);
-  p.Mz = g->out_dhw[0]; p.My = g->out_dhw[1]; p.Mx = g->out_dhw[2];
-  p.Gz = g->in_dhw[0]; p.Gy = g->in_dhw[1]; p.Gx = g->in_dhw[2];
-  p.fMx = make_fastdiv(p.Mx); p.fMy = make_fastdiv(p.My); p.fMz = make_fastdiv(p.Mz);
-  hipStream_t st = (hipStream_t)stream;
-  const int CQ = Cd / 4, PL = 256 / CQ;
-  const size_t smem = (size_t)PL * (Cd * T + Cd) * sizeof(float);
-  dim3 grid(tp.blocks);
-  if (thin_rows_ok(p, T)) {
-    launch_thin_rows<true>(p, T, tp.blocks, st);
-  } else {
-  if (smem > 64 * 1024) {
-    static bool attr_set = false;
-    if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(thin_wgrad_kernel<4, 27, true>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-      if (e != hipSuccess) { set_error("thin_wgrad: hipFuncSetAttribute: %s", hipGetErrorString(e)); return MPGAN_ERR_HIP; }
-      attr_set = true;
-    }
-    MPGAN_UNSUPPORTED(T != 27, "conv_backward_weight_bf16dy: more than 64 KiB of lane rows outside the 3x3x3 case");
+  const WgradParams p = wgrad_params(g, x, ldx, nullptr, dy, lddy, workspace, true);
+  const WgradChoice c = choose_wgrad(g, p, true);
+  if (c.rc != MPGAN_OK) {
+    set_error("%s", c.msg);
+    return c.rc;
   }
-  if (T == 1) hipLaunchKernelGGL((thin_wgrad_kernel<4, 1, true>), grid, dim3(256), smem, st, p);
-  else if (T == 9) hipLaunchKernelGGL((thin_wgrad_kernel<4, 9, true>), grid, dim3(256), smem, st, p);
-  else hipLaunchKernelGGL((thin_wgrad_kernel<4, 27, true>), grid, dim3(256), smem, st, p);
-  }
-  int rc = check_launch("thin_wgrad_bf16dy");
-  if (rc) return rc;
-  const long total = (long)Cd * T;
-  const int blocks = (int)((total + 31) / 32);
-  const int bb = dbias ? (Cd + 31) / 32 : 0;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks + bb), dim3(256), 0, st, p.partial, dw, tp.blocks, Cd, 1, T, beta,
-                     p.bias_partial, tp.blocks, dbias, bb);
-  return check_launch("thin_wgrad_bf16dy_reduce");
-}
-
-extern "C" int64_t mpgan_conv_wgrad_workspace_bf16dy(const mpgan_conv_geom* g) {
-  if (!g) return -1;
-  int Cd, Cg, T;
-  long M;
-  wgrad_dims(g, Cd, Cg, T, M);
-  ThinWgradPlan tp = plan_thin_wgrad(Cd, Cg, T, M, false, 150 * 1024);
-  if (!tp.ok) return -1;
-  return ((int64_t)tp.blocks * Cd * T + (int64_t)tp.blocks * Cd) * (int64_t)sizeof(float);
+  MPGAN_CHECK_ARG(workspace_bytes >= c.ws, "conv_backward_weight_bf16dy: workspace too small");
+  return launch_chosen(c, p, dw, dbias, beta, (hipStream_t)stream);
 }

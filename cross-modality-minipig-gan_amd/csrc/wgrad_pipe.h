@@ -42,7 +42,7 @@ __device__ __forceinline__ WBlockId wgrad_block_id(const WgradParams& p) {
 constexpr int WBK = 32;
 
 // conv_mm16.hip
-int launch_wgrad_mm16(const WgradParams& p, int BD, int BG, hipStream_t st, bool& handled);
+int launch_wgrad_mm16(const WgradParams& p, int BD, int BG, int pro, bool pad, hipStream_t st);
 
 // ---------------------------------------------------------------------------
 // Software-pipelined variant (both operands 16-byte vectorisable, coarse grid

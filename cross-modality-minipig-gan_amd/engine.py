@@ -264,6 +264,14 @@ def gather_kernel_name(g: ConvGeom, backward_data: bool, has_pro: bool, per_samp
     return kernel_label(lib().mpgan_conv_kernel_name, C.byref(gc), int(backward_data), pro)
 
 
+def wgrad_kernel_name(g: ConvGeom, pro=None, bf16_dy: bool = False) -> str:
+    """rocprofv3's name of the weight-gradient instance the C dispatcher runs for this conv (bf16_dy: the entry with a
+    bf16 dy), from the same choice the launch makes (mpgan_conv_wgrad_kernel_name)."""
+    gc = g.c()
+    code = (2 if pro.n_stride else (3 if _fast_leaky(pro) else 1)) if pro is not None else 0
+    return kernel_label(lib().mpgan_conv_wgrad_kernel_name, C.byref(gc), code, int(bf16_dy))
+
+
 def kernel_label(entry, *args) -> str:
     """The label a mpgan_conv_kernel_name* entry writes for these arguments."""
     buf = C.create_string_buffer(160)
@@ -600,7 +608,7 @@ def emit_conv_wgrad(prog, g: ConvGeom, x, dy, dw, ws, pro=None, dbias=None, lane
     prog.add("conv_backward_weight", lib().mpgan_conv_backward_weight, C.byref(gc), x.data_ptr(), _ld(x),
              C.byref(pc) if pc is not None else None, dy.data_ptr(), _ld(dy), dw.data_ptr(), _p(dbias), 1.0,
              ws.data_ptr(), ws.numel() * 4, keep=(gc, pc, x, dy, dw, dbias, ws, pro), desc=_gdesc(g),
-             tag=("wgrad_kernel", 2.0 * conv_macs(g), conv_bytes(g)), lane=lane)
+             tag=(wgrad_kernel_name(g, pro), 2.0 * conv_macs(g), conv_bytes(g)), lane=lane)
 
 
 def emit_bias_grad(prog, dy, db, partials):
@@ -1641,7 +1649,8 @@ class DiscPlanBF16:
                     b.add("conv_backward_weight_bf16dy", L.mpgan_conv_backward_weight_bf16dy, C.byref(gc),
                           self.x_in.data_ptr(), 1, dz.data_ptr(), c, gv(cv.weight).data_ptr(), gv(cv.bias).data_ptr(),
                           1.0, ws.data_ptr(), ws.numel() * 4, keep=(gc, ws), desc=_gdesc(g),
-                          tag=("wgrad_thin_kernel", 2.0 * conv_macs(g), conv_bytes(g, 2) + 2 * self.x_in.numel()))
+                          tag=(wgrad_kernel_name(g, bf16_dy=True), 2.0 * conv_macs(g),
+                               conv_bytes(g, 2) + 2 * self.x_in.numel()))
             if i > 0 and fused_rows[i - 1]:
                 # ... and the reduce pass of the layer in front (its norm-backward sums against z_{i-1}) in the same launch
                 zp, nbp = zs[i - 1], nbs[i - 1]

@@ -164,6 +164,10 @@ int mpgan_conv_backward_weight(const mpgan_conv_geom* g, const float* x, int32_t
                                float* dw, float* dbias /* nullable; ConvNd only: dbias = beta*dbias + colsum(dy), fused */,
                                float beta,
                                void* workspace, int64_t workspace_bytes, void* stream);
+/* The profiling label of the weight-gradient launch (bf16_dy: of mpgan_conv_backward_weight_bf16dy), written like
+ * mpgan_conv_kernel_name's; pro_code as there.  The launch, mpgan_conv_wgrad_workspace(_bf16dy) and this label read
+ * one choice (choose_wgrad, conv_wgrad.hip). */
+int mpgan_conv_wgrad_kernel_name(const mpgan_conv_geom* g, int32_t pro_code, int32_t bf16_dy, char* buf, int32_t len);
 
 /* Repack every conv / linear weight of a network in ONE launch.
  * table: device int64 [n_entries][8] = {src_off, dst_off, cout, cin, taps,

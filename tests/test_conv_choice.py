@@ -1,8 +1,11 @@
-"""The profiling labels, variant codes and partial-row counts of the gather convs come from one choice per family
-(choose_gather in conv_igemm.hip, choose_bf16 in conv_bf16.hip): they must name the instance the launch runs and agree
-with each other.  Library queries only: no GPU."""
+"""The profiling labels, variant codes and partial-row counts of the convs come from one choice per family
+(choose_gather in conv_igemm.hip, choose_bf16 in conv_bf16.hip, choose_wgrad in conv_wgrad.hip): they must name the
+instance the launch runs and agree with each other.  Library queries only: no GPU."""
 import ctypes as C
 import itertools
+import re
+import shutil
+import subprocess
 
 import pytest
 
@@ -114,3 +117,62 @@ def test_fp32_label_and_code_agree():
                         assert name.startswith("gather_conv_pipe_kernel<") and name.endswith(", 2, false>"), (g, name)
                     elif code == 1128:
                         assert name == "gather_conv_pipe_kernel<128, 2, 2, 2, 1, 3, true, 1, false>", (g, name)
+
+
+# The weight gradient (choose_wgrad in conv_wgrad.hip): labels of C3's discriminator (D.conv1 .. conv4; pro code 3 =
+# BatchNorm + LeakyReLU(0.2) of the producer) and of C5's generator (MM16 pipelined, 3-D patch and generic forms) and
+# discriminator (D.conv1 with a bf16 dy), as the launches of the parent's steps ran them.
+WGRAD_LABELS = [
+    (_g(16, (256, 256), 1, 64, 3, 1, 0), 0, False, "wgrad_thin_rows_kernel<9, false>"),
+    (_g(16, (254, 254), 64, 128, 3, 1, 0), 3, False, "wgrad_pipe_kernel<128, 128, 2, 2, 2, 3, false, false>"),
+    (_g(16, (252, 252), 128, 256, 4, 2, 0), 3, False, "wgrad_pipe_kernel<128, 128, 2, 2, 2, 3, false, false>"),
+    (_g(16, (125, 125), 256, 256, 4, 2, 0), 3, False, "wgrad_pipe_kernel<128, 128, 2, 2, 2, 3, false, false>"),
+    (_g(4, (32, 32, 32), 32, 32, 3, 1, 1, mm_bf16=True), 1, False, "wgrad_pipe_kernel<32, 128, 1, 1, 4, 1, true, true>"),
+    (_g(4, (16, 16, 16), 192, 32, 3, 2, 1, transposed=True, out_pad=(1, 1, 1), mm_bf16=True), 0, False,
+     "wgrad_pipe_kernel<128, 128, 2, 2, 2, 0, true, true>"),
+    (_g(4, (64, 64, 64), 16, 16, 3, 1, 1, mm_bf16=True), 1, False, "wgrad_patch3d_c16_kernel<true, true>"),
+    (_g(4, (64, 64, 64), 32, 1, 3, 2, 1, transposed=True, out_pad=(1, 1, 1), mm_bf16=True), 0, False,
+     "wgrad_kernel<32, 32, 1, 1, 1, 4, false, true>"),
+    (_g(4, (128, 128, 128), 1, 64, 3, 1, 0), 0, True, "wgrad_thin_rows_kernel<27, true>"),
+]
+
+
+def _wgrad_label(g, pro_code, bf16_dy):
+    gc = g.c()
+    return engine.kernel_label(lib().mpgan_conv_wgrad_kernel_name, C.byref(gc), pro_code, int(bf16_dy))
+
+
+@pytest.mark.parametrize("i", range(len(WGRAD_LABELS)))
+def test_wgrad_labels(i):
+    g, pro_code, bf16_dy, label = WGRAD_LABELS[i]
+    assert _wgrad_label(g, pro_code, bf16_dy) == label
+
+
+def _library_kernels():
+    from mpgan_amd import _lib
+    nm = shutil.which("nm") or shutil.which("llvm-nm")
+    assert nm, "no nm on PATH"
+    out = subprocess.run([nm, "-C", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    return set(re.findall(r"void mpgan::(\w+<[^()]*>)\(mpgan::WgradParams", out))
+
+
+def test_wgrad_labels_name_library_kernels():
+    kernels = _library_kernels()
+    seen = set()
+    for d, sp in [(2, (40, 36)), (2, (130, 126)), (3, (18, 17, 19)), (3, (34, 33, 32))]:
+        for cin, cout, (k, s, p), tr, mm in itertools.product((1, 16, 32, 64, 128), (1, 16, 32, 64, 128),
+                                                             [(1, 1, 0), (3, 1, 1), (3, 1, 0), (3, 2, 1), (4, 2, 1)],
+                                                             (False, True), (False, True)):
+            op = (1, 1, 1) if tr and (k, s) == (3, 2) else (0, 0, 0)
+            g = _g(2, sp, cin, cout, k, s, p, transposed=tr, out_pad=op, mm_bf16=mm)
+            if min(g.out_dhw) < 1:
+                continue
+            for pro_code in ((0,) if tr else (0, 1, 2, 3)):
+                name = _wgrad_label(g, pro_code, False)
+                assert name.startswith("wgrad") and name in kernels, (g, pro_code, name)
+                seen.add(name.split("<")[0])
+            if not tr and cin == 1 and cout % 4 == 0 and cout <= 64 and k != 4:   # what the bf16-dy entry takes
+                name = _wgrad_label(g, 0, True)
+                assert name.startswith("wgrad") and name in kernels and name.endswith(", true>"), (g, name)
+    assert seen == {"wgrad_patch3d_c16_kernel", "wgrad_patch2d_kernel", "wgrad_thin_rows_kernel", "wgrad_thin_kernel",
+                    "wgrad_pipe_kernel", "wgrad_kernel"}, seen

@@ -148,13 +148,12 @@ def _geom(r):
 
 
 def _dispatch(r, g):
+    from mpgan_amd import engine
     from mpgan_amd._lib import lib
     gc_ = g.c()
     e = r["entry"]
     if e == "mpgan_conv_backward_weight_bf16":
         return f"wgrad_bf16 v{lib().mpgan_conv_wgrad_variant_bf16(C.byref(gc_))}"
-    if r["kind"] == "wgrad":
-        return "wgrad"
     bwd = int(r["kind"] == "dgrad")
     if e in ("mpgan_conv_forward_bf16", "mpgan_conv_backward_data_bf16", "mpgan_conv_backward_data_stats_bf16"):
         return f"bf16 v{lib().mpgan_conv_variant_bf16(C.byref(gc_), bwd)}"
@@ -162,6 +161,9 @@ def _dispatch(r, g):
     if r["pro"] is not None:
         ns, act, sp, slope = r["pro"]
         code = 2 if ns else (3 if act == R.ACT_LEAKY and not sp and 0.0 <= slope <= 1.0 else 1)
+    if r["kind"] == "wgrad":
+        return engine.kernel_label(lib().mpgan_conv_wgrad_kernel_name, C.byref(gc_), code,
+                                   int(e == "mpgan_conv_backward_weight_bf16dy"))
     return f"f32 v{lib().mpgan_conv_variant(C.byref(gc_), bwd, code)}"
 
 
