@@ -21,6 +21,11 @@ class PeerTapsC(C.Structure):
                 ("shift_peer", C.c_void_p), ("coef", C.c_void_p)]
 
 
+class PeerTapsBF16C(C.Structure):
+    _fields_ = [("z_peer", C.c_void_p), ("ld_peer", C.c_int32), ("scale_peer", C.c_void_p),
+                ("shift_peer", C.c_void_p), ("coef", C.c_void_p)]
+
+
 class NormFoldC(C.Structure):
     _fields_ = [("acc", C.c_void_p), ("replicas", C.c_int32), ("cstride", C.c_int32), ("count", C.c_int64),
                 ("gamma", C.c_void_p), ("beta", C.c_void_p), ("eps", C.c_float), ("momentum", C.c_float),
@@ -137,6 +142,12 @@ SIGNATURES = {
     "mpgan_norm_bwd_rows_bf16": (_I, [_L, _I]),
     "mpgan_norm_bwd_reduce_bf16": (_I, [_P, _I, _I, _P, _I, _P, _P, _P, _P, _F, _L, _I, _P, _P]),
     "mpgan_norm_bwd_apply_bf16": (_I, [_P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _F, _L, _I, _P, _I, _P, _P]),
+    # variant B in bf16 storage: peer-tap terms of the norm backward, perceptual-tap L1 on bf16 z
+    "mpgan_norm_bwd_reduce_bf16_peer": (_I, [_P, _I, _I, _P, _I, _P, _P, _P, _P, C.POINTER(PeerTapsBF16C), _F, _L, _I,
+                                             _P, _P]),
+    "mpgan_norm_bwd_apply_bf16_peer": (_I, [_P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, C.POINTER(PeerTapsBF16C), _F,
+                                            _L, _I, _P, _I, _P, _P]),
+    "mpgan_tap_l1_bf16": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _F, _L, _I, _P, _P, _P]),
     # sliding-window inference (inference.py)
     "mpgan_sw_gather": (_I, [_SW, _P, _I, _I, _I, _F, _P, _P]),
     "mpgan_sw_count": (_I, [_SW, _P, _P, _P]),

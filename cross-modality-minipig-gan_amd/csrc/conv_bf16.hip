@@ -18,6 +18,7 @@
 #include "conv_geom.h"
 #include "lds_dma.h"
 #include <stdlib.h>
+#include <initializer_list>
 #include <type_traits>
 
 namespace mpgan {
@@ -2503,6 +2504,177 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_bf16_kernel(const TG* __re
   }
 }
 
+// The two kernels above with the perceptual taps of a peer pass (variant B): the fp32 path's formula (norm_ops.hip,
+// Peer) on the stored bf16 z of both passes,
+//   g_a = g - ca*sign(a_peer - a),  gy = g_a*act'(y) - cy*sign(y_peer - y),  dz += -cz*sign(z_peer - z),
+// with y = z*scale + shift and a = LeakyReLU_slope(y) in fp32 on each side.  Same grid, rows and partial layout.
+struct PeerBf16 {
+  const __bf16* z;     // the peer pass's stored raw conv output, [rows][ld]
+  int ld;
+  const float* scale;  // its norm scale / shift
+  const float* shift;
+  const float* coef;   // device float[3]: (cz, cy, ca)
+};
+
+__device__ __forceinline__ float peer_gy_bf16(float g, float y, float yp, float slope, float cy, float ca) {
+  const float ap = yp < 0.f ? yp * slope : yp;
+  const float a = y < 0.f ? y * slope : y;
+  const float ga = g - ca * sgn(ap - a);
+  return (y < 0.f ? ga * slope : ga) - cy * sgn(yp - y);
+}
+
+template <typename TG>
+__global__ __launch_bounds__(256) void norm_bwd_reduce_bf16_peer_kernel(const TG* __restrict__ g, int ldg,
+                                                                        const __bf16* __restrict__ z, int ldz,
+                                                                        const float* __restrict__ scale,
+                                                                        const float* __restrict__ shift,
+                                                                        const float* __restrict__ mean,
+                                                                        const float* __restrict__ invstd, PeerBf16 pr,
+                                                                        float slope, long rows, int C,
+                                                                        float* __restrict__ partials) {
+  extern __shared__ float red[];   // [R][2][C]
+  const int CG = C / 8, R = 256 / CG;
+  const int q = threadIdx.x % CG, r = threadIdx.x / CG, c = q * 8;
+  const long per = (rows + gridDim.x - 1) / gridDim.x;
+  const long beg = (long)blockIdx.x * per, end = beg + per < rows ? beg + per : rows;
+  float a0[8], a1[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) a0[e] = a1[e] = 0.f;
+  if (r < R) {
+    float sc[8], sh[8], mu[8], is[8], psc[8], psh[8];
+    ld8(scale + c, sc); ld8(shift + c, sh); ld8(mean + c, mu); ld8(invstd + c, is);
+    ld8(pr.scale + c, psc); ld8(pr.shift + c, psh);
+    const float cy = pr.coef[1], ca = pr.coef[2];
+    for (long row = beg + r; row < end; row += R) {
+      float zv[8], gv[8], zp[8];
+      ld8(z + row * ldz + c, zv);
+      ld8(g + row * ldg + c, gv);
+      ld8(pr.z + row * pr.ld + c, zp);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float y = zv[e] * sc[e] + sh[e];
+        const float gy = peer_gy_bf16(gv[e], y, zp[e] * psc[e] + psh[e], slope, cy, ca);
+        a0[e] += gy;
+        a1[e] = fmaf(gy, (zv[e] - mu[e]) * is[e], a1[e]);
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      red[(r * 2 + 0) * C + c + e] = a0[e];
+      red[(r * 2 + 1) * C + c + e] = a1[e];
+    }
+  }
+  __syncthreads();
+  float* out = partials + (long)blockIdx.x * 3 * C;
+  for (int i = threadIdx.x; i < 3 * C; i += 256) {
+    float s = 0.f;
+    if (i < 2 * C)
+      for (int rr = 0; rr < R; ++rr) s += red[rr * 2 * C + i];
+    out[i] = s;
+  }
+}
+
+template <typename TG>
+__global__ __launch_bounds__(256) void norm_bwd_apply_bf16_peer_kernel(const TG* __restrict__ g, int ldg,
+                                                                       const __bf16* __restrict__ z, int ldz,
+                                                                       const float* __restrict__ scale,
+                                                                       const float* __restrict__ shift,
+                                                                       const float* __restrict__ mean,
+                                                                       const float* __restrict__ invstd,
+                                                                       const float* __restrict__ c1,
+                                                                       const float* __restrict__ c2, PeerBf16 pr,
+                                                                       float slope, long rows, int C,
+                                                                       __bf16* __restrict__ dz, int lddz,
+                                                                       float* __restrict__ bias_partials) {
+  extern __shared__ float red[];   // [R][C]
+  const int CG = C / 8, R = 256 / CG;
+  const int q = threadIdx.x % CG, r = threadIdx.x / CG, c = q * 8;
+  float bs[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) bs[e] = 0.f;
+  if (r < R) {
+    float sc[8], sh[8], mu[8], is[8], k1[8], k2[8], psc[8], psh[8];
+    ld8(scale + c, sc); ld8(shift + c, sh); ld8(mean + c, mu); ld8(invstd + c, is); ld8(c1 + c, k1); ld8(c2 + c, k2);
+    ld8(pr.scale + c, psc); ld8(pr.shift + c, psh);
+    const float cz = pr.coef[0], cy = pr.coef[1], ca = pr.coef[2];
+    for (long row = (long)blockIdx.x * R + r; row < rows; row += (long)gridDim.x * R) {
+      float zv[8], gv[8], zp[8], o[8];
+      ld8(z + row * ldz + c, zv);
+      ld8(g + row * ldg + c, gv);
+      ld8(pr.z + row * pr.ld + c, zp);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float y = zv[e] * sc[e] + sh[e];
+        const float gy = peer_gy_bf16(gv[e], y, zp[e] * psc[e] + psh[e], slope, cy, ca);
+        o[e] = sc[e] * (gy - k1[e] - (zv[e] - mu[e]) * is[e] * k2[e]) - cz * sgn(zp[e] - zv[e]);
+        bs[e] += (float)(__bf16)o[e];
+      }
+      st8(dz + row * lddz + c, o);
+    }
+  }
+  if (bias_partials) {
+    if (r < R) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) red[r * C + c + e] = bs[e];
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < C; i += 256) {
+      float s = 0.f;
+      for (int rr = 0; rr < R; ++rr) s += red[rr * C + i];
+      bias_partials[(long)blockIdx.x * C + i] = s;
+    }
+  }
+}
+
+// Perceptual-loss value of one layer of two passes in bf16 storage (variant B): block partials [gridDim.x][3] of
+// sum |z_a - z_b|, |y_a - y_b|, |a_a - a_b|, with z the STORED bf16 raw conv outputs, y = z*scale + shift (fp32) and
+// a = LeakyReLU_slope(y).  Thread = 8 channels of one row (16-byte loads); fp32 sums in a fixed grid-stride order, a
+// fixed wave butterfly and a fixed order over the four waves: no atomics, the result is reproducible.
+__global__ __launch_bounds__(256) void tap_l1_bf16_kernel(const __bf16* __restrict__ za, int lda,
+                                                          const float* __restrict__ sca, const float* __restrict__ sha,
+                                                          const __bf16* __restrict__ zb, int ldb,
+                                                          const float* __restrict__ scb, const float* __restrict__ shb,
+                                                          float slope, long rows, int C, float* __restrict__ partials) {
+  __shared__ float red[3][4];
+  const int CG = C / 8;
+  const long total = rows * CG;
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const long row = i / CG;
+    const int c = (int)(i - row * CG) * 8;
+    float va[8], vb[8], ka[8], ha[8], kb[8], hb[8];
+    ld8(za + row * lda + c, va);
+    ld8(zb + row * ldb + c, vb);
+    ld8(sca + c, ka); ld8(sha + c, ha); ld8(scb + c, kb); ld8(shb + c, hb);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float ya = va[e] * ka[e] + ha[e], yb = vb[e] * kb[e] + hb[e];
+      const float aa = ya < 0.f ? ya * slope : ya, ab = yb < 0.f ? yb * slope : yb;
+      s0 += fabsf(va[e] - vb[e]);
+      s1 += fabsf(ya - yb);
+      s2 += fabsf(aa - ab);
+    }
+  }
+  s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (lane == 0) { red[0][w] = s0; red[1][w] = s1; red[2][w] = s2; }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const int q = threadIdx.x;
+    partials[blockIdx.x * 3 + q] = ((red[q][0] + red[q][1]) + red[q][2]) + red[q][3];
+  }
+}
+
+// out3[q] = (fp64 sum of the block partials in block order) / numel, rounded once to fp32
+__global__ __launch_bounds__(64) void tap_l1_bf16_final_kernel(const float* __restrict__ partials, int nblocks,
+                                                               double numel, float* __restrict__ out3) {
+  const int q = threadIdx.x;
+  if (q >= 3) return;
+  double s = 0.0;
+  for (int b = 0; b < nblocks; ++b) s += (double)partials[b * 3 + q];
+  out3[q] = (float)(s / numel);
+}
+
 // table-driven repack of fp32 master weights into bf16 [Cout][tap][Cin] / [Cin][tap][Cout] (pack_weights_kernel's twin)
 __global__ __launch_bounds__(256) void pack_weights_bf16_kernel(const float* __restrict__ src, __bf16* __restrict__ dst,
                                                                 const int64_t* __restrict__ table) {
@@ -2835,4 +3007,94 @@ extern "C" int mpgan_norm_bwd_apply_bf16(const void* g, int32_t g_f32, int32_t l
                        static_cast<const __bf16*>(g), ldg, static_cast<const __bf16*>(z), ldz, scale, shift, mean,
                        invstd, c1, c2, slope, (long)rows, c, static_cast<__bf16*>(dz), lddz, bias_partials);
   return check_launch("norm_bwd_apply_bf16");
+}
+
+static inline bool any_misaligned16(std::initializer_list<const void*> ps) {
+  for (const void* p : ps)
+    if (reinterpret_cast<uintptr_t>(p) & 15) return true;
+  return false;
+}
+
+static int peer_bf16_of(const mpgan_peer_taps_bf16* t, int32_t c, PeerBf16& pr, const char* what) {
+  MPGAN_CHECK_ARG(t && t->z_peer && t->scale_peer && t->shift_peer && t->coef && t->ld_peer >= c,
+                  "%s: bad peer descriptor", what);
+  MPGAN_UNSUPPORTED(t->ld_peer % 8 || any_misaligned16({t->z_peer, t->scale_peer, t->shift_peer}),
+                    "%s: peer pitch %% 8, 16-byte aligned peer tensors", what);
+  pr.z = static_cast<const __bf16*>(t->z_peer);
+  pr.ld = t->ld_peer;
+  pr.scale = t->scale_peer;
+  pr.shift = t->shift_peer;
+  pr.coef = t->coef;
+  return MPGAN_OK;
+}
+
+extern "C" int mpgan_norm_bwd_reduce_bf16_peer(const void* g, int32_t g_f32, int32_t ldg, const void* z, int32_t ldz,
+                                               const float* scale, const float* shift, const float* mean,
+                                               const float* invstd, const mpgan_peer_taps_bf16* peer, float slope,
+                                               int64_t rows, int32_t c, float* partials, void* stream) {
+  MPGAN_CHECK_ARG(g && z && scale && shift && mean && invstd && partials && rows > 0 && ldg >= c && ldz >= c,
+                  "norm_bwd_reduce_bf16_peer: bad argument");
+  const int nb = mpgan_norm_bwd_rows_bf16(rows, c);
+  MPGAN_UNSUPPORTED(nb < 0 || ldg % 8 || ldz % 8 || any_misaligned16({g, z, scale, shift, mean, invstd}),
+                    "norm_bwd_reduce_bf16_peer: C %% 8, C <= 2048, pitches %% 8, 16-byte aligned tensors");
+  PeerBf16 pr;
+  int rc = peer_bf16_of(peer, c, pr, "norm_bwd_reduce_bf16_peer");
+  if (rc) return rc;
+  const int R = 256 / (c / 8);
+  const size_t smem = (size_t)R * 2 * c * sizeof(float);
+  if (g_f32)
+    hipLaunchKernelGGL(norm_bwd_reduce_bf16_peer_kernel<float>, dim3(nb), dim3(256), smem, (hipStream_t)stream,
+                       static_cast<const float*>(g), ldg, static_cast<const __bf16*>(z), ldz, scale, shift, mean, invstd,
+                       pr, slope, (long)rows, c, partials);
+  else
+    hipLaunchKernelGGL(norm_bwd_reduce_bf16_peer_kernel<__bf16>, dim3(nb), dim3(256), smem, (hipStream_t)stream,
+                       static_cast<const __bf16*>(g), ldg, static_cast<const __bf16*>(z), ldz, scale, shift, mean,
+                       invstd, pr, slope, (long)rows, c, partials);
+  return check_launch("norm_bwd_reduce_bf16_peer");
+}
+
+extern "C" int mpgan_norm_bwd_apply_bf16_peer(const void* g, int32_t g_f32, int32_t ldg, const void* z, int32_t ldz,
+                                              const float* scale, const float* shift, const float* mean,
+                                              const float* invstd, const float* c1, const float* c2,
+                                              const mpgan_peer_taps_bf16* peer, float slope, int64_t rows, int32_t c,
+                                              void* dz, int32_t lddz, float* bias_partials, void* stream) {
+  MPGAN_CHECK_ARG(g && z && scale && shift && mean && invstd && c1 && c2 && dz && rows > 0 && ldg >= c && ldz >= c &&
+                      lddz >= c,
+                  "norm_bwd_apply_bf16_peer: bad argument");
+  const int nb = mpgan_norm_bwd_rows_bf16(rows, c);
+  MPGAN_UNSUPPORTED(nb < 0 || ldg % 8 || ldz % 8 || lddz % 8 || any_misaligned16({g, z, dz, scale, shift, mean, invstd, c1, c2}),
+                    "norm_bwd_apply_bf16_peer: C %% 8, C <= 2048, pitches %% 8, 16-byte aligned tensors");
+  PeerBf16 pr;
+  int rc = peer_bf16_of(peer, c, pr, "norm_bwd_apply_bf16_peer");
+  if (rc) return rc;
+  const int R = 256 / (c / 8);
+  const size_t smem = bias_partials ? (size_t)R * c * sizeof(float) : 0;
+  if (g_f32)
+    hipLaunchKernelGGL(norm_bwd_apply_bf16_peer_kernel<float>, dim3(nb), dim3(256), smem, (hipStream_t)stream,
+                       static_cast<const float*>(g), ldg, static_cast<const __bf16*>(z), ldz, scale, shift, mean, invstd,
+                       c1, c2, pr, slope, (long)rows, c, static_cast<__bf16*>(dz), lddz, bias_partials);
+  else
+    hipLaunchKernelGGL(norm_bwd_apply_bf16_peer_kernel<__bf16>, dim3(nb), dim3(256), smem, (hipStream_t)stream,
+                       static_cast<const __bf16*>(g), ldg, static_cast<const __bf16*>(z), ldz, scale, shift, mean,
+                       invstd, c1, c2, pr, slope, (long)rows, c, static_cast<__bf16*>(dz), lddz, bias_partials);
+  return check_launch("norm_bwd_apply_bf16_peer");
+}
+
+extern "C" int mpgan_tap_l1_bf16(const void* za, int32_t lda, const float* scale_a, const float* shift_a, const void* zb,
+                                 int32_t ldb, const float* scale_b, const float* shift_b, float slope, int64_t rows,
+                                 int32_t c, float* partials, float* out3, void* stream) {
+  MPGAN_CHECK_ARG(za && zb && scale_a && shift_a && scale_b && shift_b && partials && out3 && rows > 0 && c > 0 &&
+                      lda >= c && ldb >= c,
+                  "tap_l1_bf16: bad argument");
+  MPGAN_UNSUPPORTED(c % 8 || lda % 8 || ldb % 8 || any_misaligned16({za, zb, scale_a, shift_a, scale_b, shift_b}),
+                    "tap_l1_bf16: channels / pitches %% 8, 16-byte aligned tensors");
+  long blocks = (rows * (c / 8) + 255) / 256;
+  const long cap = mpgan_tap_l1_partials() / 3;          // the partials size query of mpgan_tap_l1
+  if (blocks > cap) blocks = cap;
+  hipLaunchKernelGGL(tap_l1_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+                     static_cast<const __bf16*>(za), lda, scale_a, shift_a, static_cast<const __bf16*>(zb), ldb, scale_b,
+                     shift_b, slope, (long)rows, c, partials);
+  hipLaunchKernelGGL(tap_l1_bf16_final_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, partials, (int)blocks,
+                     (double)rows * c, out3);
+  return check_launch("tap_l1_bf16");
 }

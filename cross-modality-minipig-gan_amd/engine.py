@@ -1686,7 +1686,6 @@ class PatchDiscPlan:
         self.n, self.dhw, self.dims, self.store, self.disc = n, dhw, dims, store, disc
         self.want_input_grad, self.want_param_grads = want_input_grad, want_param_grads
         E = lambda *shape: torch.empty(*shape, device=dev)
-        Z = lambda *shape: torch.zeros(*shape, device=dev)
         convs = [disc.model_conv[i] for i in (0, 3, 6, 9)]
         bns = [disc.model_conv[i] for i in (1, 4, 7, 10)]
         lin1, lin2 = disc.model_linear[1], disc.model_linear[2]
@@ -1747,18 +1746,27 @@ class PatchDiscPlan:
         self._bwd_cache = {}
         if not want_backward:
             return
+        self.gas = [E(*z.shape) for z in self.zs]
+        self._tap_buffers(dev)
+        if want_input_grad:
+            self.g_x = E(n, *dhw, 1)
+
+    def _tap_buffers(self, dev):
+        """Head gradients and the perceptual loss's per-plan state (both storage modes)."""
+        E = lambda *shape: torch.empty(*shape, device=dev)
+        Z = lambda *shape: torch.zeros(*shape, device=dev)
+        n = self.n
         self.g_prob = E(n)
         self.dlogit = E(n, 1, 1, 1, 1)
-        self.dh = E(n, 1, 1, 1, lin1.out_features)
-        self.gas = [E(*z.shape) for z in self.zs]
+        self.dh = E(n, 1, 1, 1, self.lin1.out_features)
         # gradients arriving through the perceptual taps of the three head tensors (zero unless a
         # perceptual loss deposited them) and the per-layer (z, y, a) coefficients
         self.tap_g_h, self.tap_g_logit, self.tap_g_prob = Z(*self.h.shape), Z(n), Z(n)
-        self.coef_all = Z(4 * len(convs))                      # one buffer: the perceptual loss fills it in one launch
-        self.coef = [self.coef_all[4 * i:4 * i + 4] for i in range(len(convs))]
+        self.coef_all = Z(4 * len(self.convs))                 # one buffer: the perceptual loss fills it in one launch
+        self.coef = [self.coef_all[4 * i:4 * i + 4] for i in range(len(self.convs))]
         # constant weights of the perceptual loss (test_runs/GAN.py:288-298: every tap's L1 mean / its numel; Flatten
         # repeats the last activation, key 12): forward terms in the order [layer0 z, y, a, layer1 ..., h, logit, prob]
-        nl = len(convs)
+        nl = len(self.convs)
         wf, wb = [], []
         for i, z in enumerate(self.zs):
             nel = float(z.numel())
@@ -1768,8 +1776,6 @@ class PatchDiscPlan:
         wf += [1.0 / self.h.numel(), 1.0 / self.logit.numel(), 1.0 / self.prob.numel()]
         self.perc_w_fwd = torch.tensor(wf, device=dev)
         self.perc_w_bwd = torch.tensor(wb, device=dev)
-        if want_input_grad:
-            self.g_x = E(n, *dhw, 1)
 
     def backward_program(self, peer: Optional["PatchDiscPlan"]) -> Program:
         key = id(peer) if peer is not None else 0
@@ -1911,3 +1917,224 @@ class PatchDiscPlan:
                 emit_conv_dgrad(b, self.geoms[0], self.gas[0], store.wp_bwd(self.recs[0]), self.g_x)
         self._bwd_cache[key] = b
         return b
+
+
+class PatchDiscPlanBF16(PatchDiscPlan):
+    """PatchDiscPlan with DiscPlanBF16's storage contract: bf16 raw conv outputs z_i, activations
+    a_0..a_2, activation gradients and packed weights of the three dense convs in HBM; fp32 accumulation, statistics,
+    parameters, weight gradients and Adam.  a_3 and its gradient stay fp32 for the fp32 split-K head, which reads a_3
+    with no prologue.  The perceptual taps are defined on the STORED z_i (y = z_i*scale + shift, a = LeakyReLU(y) in
+    fp32): their values come from mpgan_tap_l1_bf16, their gradients from the peer entries of the bf16 norm backward.
+    Gradients deposited into materialised taps are not offered (deposit_tap_grad raises)."""
+
+    def __init__(self, disc, store: ParamStore, n: int, spatial: Sequence[int], *, want_backward: bool,
+                 want_input_grad: bool, want_param_grads: bool):
+        dims = disc.dimensions
+        dev = store.flat.device
+        dhw = _t3(spatial, dims, 1)
+        self.n, self.dhw, self.dims, self.store, self.disc = n, dhw, dims, store, disc
+        self.want_input_grad, self.want_param_grads = want_input_grad, want_param_grads
+        bf = torch.bfloat16
+        E = lambda *shape: torch.empty(*shape, device=dev)
+        H = lambda *shape: torch.empty(*shape, device=dev, dtype=bf)
+        convs = [disc.model_conv[i] for i in (0, 3, 6, 9)]
+        bns = [disc.model_conv[i] for i in (1, 4, 7, 10)]
+        lin1, lin2 = disc.model_linear[1], disc.model_linear[2]
+        self.convs, self.bns, self.lin1, self.lin2 = convs, bns, lin1, lin2
+        self.x_in = E(n, *dhw, 1)
+        self.geoms, self.zs, self.acts, self.nbs, self.recs = [], [], [], [], []
+        size = dhw
+        scratch = Scratch(dev)
+        for i, cv in enumerate(convs):
+            g = conv_geom_of(cv, n, size, dims)
+            self.geoms.append(g)
+            size = g.out_dhw
+            if min(size) < 1:
+                raise ValueError(f"patch discriminator input {spatial} too small")
+            c = cv.out_channels
+            self.zs.append(H(n, *size, c))
+            self.acts.append(E(n, *size, c) if i == 3 else H(n, *size, c))
+            self.nbs.append(NormBuf(n, c, False, dev))
+            self.recs.append(store.register_conv(cv, cout=c, cin=cv.in_channels,
+                                                 taps=int(torch.tensor(cv.kernel_size).prod())))
+            rows_total = n * size[0] * size[1] * size[2]
+            fwd_rows = (rows_total + 255) // 256 if i == 0 else ops.conv_stats_rows_bf16(g)
+            bwd_rows = ops.norm_bwd_rows_bf16(rows_total, c)
+            scratch.partials_need = max(scratch.partials_need, (fwd_rows + 32) * 2 * c, bwd_rows * 4 * c + c)
+            ws = ops.conv_wgrad_workspace_bf16dy(g) if i == 0 else ops.conv_wgrad_workspace_bf16(g)
+            scratch.ws_need = max(scratch.ws_need, ws // 4)
+        c_last = convs[-1].out_channels
+        P_last = size[0] * size[1] * size[2]
+        if lin1.in_features != P_last * c_last:
+            raise ValueError(f"Linear.in_features {lin1.in_features} != {c_last}*{P_last} for patches {spatial}")
+        # the fp32 head of PatchDiscPlan, reading the fp32 a_3 instead of z_3 through a prologue
+        self.g_l1 = ConvGeom(n, tuple(size), c_last, lin1.out_features, tuple(size), (1, 1, 1), (0, 0, 0))
+        self.g_l2 = ConvGeom(n, (1, 1, 1), lin1.out_features, 1, (1, 1, 1), (1, 1, 1), (0, 0, 0))
+        self.r_l1 = store.register_conv(lin1, cout=lin1.out_features, cin=c_last, taps=P_last, tco=True)
+        self.g_l1_bwd = ConvGeom(n, (1, 1, 1), lin1.out_features, P_last * c_last, (1, 1, 1), (1, 1, 1), (0, 0, 0))
+        self.r_l2 = store.register_conv(lin2, cout=1, cin=lin1.out_features, taps=1)
+        scratch.want_ws(self.g_l1)
+        scratch.want_ws(self.g_l2)
+        scratch.alloc()
+        self.scratch = scratch
+        part = scratch.partials
+        # bf16 packs of the three dense layers: [Cout][tap][Cin] (forward) and [Cin][tap][Cout] (backward-data)
+        rows16, off = [], 0
+        self._w16 = {}
+        for i in (1, 2, 3):
+            r = self.recs[i]
+            nel = r.cout * r.cin * r.taps
+            self._w16[i] = (off, off + (nel + 7) // 8 * 8, nel)
+            rows16.append([r.w_off, off, r.cout, r.cin, r.taps, 0, 0, 0])
+            rows16.append([r.w_off, off + (nel + 7) // 8 * 8, r.cout, r.cin, r.taps, 0, 1, 0])
+            off += 2 * ((nel + 7) // 8 * 8)
+        self.packed16 = torch.empty(off, device=dev, dtype=bf)
+        table16 = torch.tensor(rows16, dtype=torch.int64, device=dev)
+        self.h = E(n, 1, 1, 1, lin1.out_features)
+        self.logit, self.prob = E(n, 1, 1, 1, 1), E(n)
+        self.splitk_ws = E(max(ops.conv_splitk_workspace(self.g_l1) // 4, 4))
+        L = lib()
+        f = self.fwd = Program()
+        store.emit_pack(f)                                   # fp32 packs: first layer, the two Linear layers
+        f.add("pack_weights_bf16", L.mpgan_pack_weights_bf16, store.flat.data_ptr(), self.packed16.data_ptr(),
+              table16.data_ptr(), table16.shape[0], max(r.cout * r.cin * r.taps for r in self.recs[1:]),
+              keep=(self.packed16, table16))
+        src = self.x_in
+        for i, cv in enumerate(convs):
+            g, z, nb, bn, a = self.geoms[i], self.zs[i], self.nbs[i], bns[i], self.acts[i]
+            gc = g.c()
+            rows_total = n * g.out_dhw[0] * g.out_dhw[1] * g.out_dhw[2]
+            if i == 0:
+                rows = (rows_total + 255) // 256
+                f.add("conv_forward_f32_to_bf16", L.mpgan_conv_forward_f32_to_bf16, C.byref(gc), src.data_ptr(), 1,
+                      store.wp(self.recs[0]).data_ptr(), cv.bias.data_ptr(), part.data_ptr(), z.data_ptr(), g.cout,
+                      keep=(gc, src, z, part), desc=_gdesc(g), tag=("thin_cin1_full_kernel<16, true>",
+                                                                     2.0 * conv_macs(g), conv_bytes(g, 2) + 2 * src.numel()))
+            else:
+                rows = ops.conv_stats_rows_bf16(g)
+                f.add("conv_forward_bf16", L.mpgan_conv_forward_bf16, C.byref(gc), src.data_ptr(), g.cin,
+                      self._wf16(i).data_ptr(), cv.bias.data_ptr(), part.data_ptr(), z.data_ptr(), g.cout,
+                      keep=(gc, src, z, part), desc=_gdesc(g),
+                      tag=(_bf16_kernel_name(g, False), 2.0 * conv_macs(g), conv_bytes(g, 2)))
+            f.add("norm_finalize", L.mpgan_norm_finalize, part.data_ptr(), 1, rows, g.cout, rows_total, 0,
+                  _p(bn.weight), _p(bn.bias), float(bn.eps), float(bn.momentum), _p(bn.running_mean),
+                  _p(bn.running_var), _p(bn.num_batches_tracked), nb.scale.data_ptr(), nb.shift.data_ptr(),
+                  nb.mean.data_ptr(), nb.invstd.data_ptr(), keep=(bn, nb))
+            f.add("norm_act_bf16", L.mpgan_norm_act_bf16, z.data_ptr(), g.cout, nb.scale.data_ptr(), nb.shift.data_ptr(),
+                  0.2, rows_total, g.cout, a.data_ptr(), g.cout, int(a.dtype == torch.float32), keep=(a,))
+            src = a
+        gc1 = self.g_l1.c()
+        a3 = self.acts[3]
+        f.add("conv_forward_splitk", L.mpgan_conv_forward_splitk, C.byref(gc1), a3.data_ptr(), _ld(a3),
+              store.wp(self.r_l1).data_ptr(), lin1.bias.data_ptr(), None, self.splitk_ws.data_ptr(),
+              self.splitk_ws.numel() * 4, self.h.data_ptr(), _ld(self.h), keep=(gc1, a3),
+              tag=("gather_conv_pipe_kernel<splitK>", 2.0 * conv_macs(self.g_l1)))
+        emit_conv_fwd(f, self.g_l2, self.h, store.wp(self.r_l2), lin2.bias, self.logit)
+        f.add("sigmoid_forward", L.mpgan_sigmoid_forward, self.logit.data_ptr(), n, self.prob.data_ptr())
+        self.busy = False
+        self.g_x = None
+        self._bwd_cache = {}
+        if not want_backward:
+            return
+        # gradients w.r.t. the activations (bf16; fp32 for a_3, written by the head's GEMM); the BatchNorm backward
+        # overwrites them in place with dz (disc.debug_keep_intermediates: separate dz buffers, for the tests)
+        self.gas = [H(*z.shape) for z in self.zs[:3]] + [E(*self.zs[3].shape)]
+        dz3 = H(*self.zs[3].shape)
+        keep_all = bool(getattr(disc, "debug_keep_intermediates", False))
+        self.dzs = [H(*z.shape) for z in self.zs[:3]] + [dz3] if keep_all else self.gas[:3] + [dz3]
+        self._tap_buffers(dev)
+        if want_input_grad:
+            self.g_x = E(n, *dhw, 1)
+
+    def _wf16(self, i):
+        o, _, nel = self._w16[i]
+        return self.packed16[o:o + nel]
+
+    def _wb16(self, i):
+        _, o, nel = self._w16[i]
+        return self.packed16[o:o + nel]
+
+    def backward_program(self, peer: Optional["PatchDiscPlanBF16"]) -> Program:
+        key = id(peer) if peer is not None else 0
+        if key in self._bwd_cache:
+            return self._bwd_cache[key]
+        store, L = self.store, lib()
+        part, ws = self.scratch.partials, self.scratch.ws
+        gv = store.grad_view if self.want_param_grads else (lambda p: None)
+        b = Program()
+        n = self.n
+        # the head, as PatchDiscPlan's (sigmoid: dlogit = (g_prob + tap_prob) * p(1-p) + tap_logit)
+        b.add("axpby", L.mpgan_axpby, self.g_prob.data_ptr(), 1.0, self.tap_g_prob.data_ptr(), 1.0, n,
+              self.g_prob.data_ptr())
+        b.add("sigmoid_backward", L.mpgan_sigmoid_backward, self.g_prob.data_ptr(), self.prob.data_ptr(), n,
+              self.dlogit.data_ptr())
+        b.add("axpby", L.mpgan_axpby, self.dlogit.data_ptr(), 1.0, self.tap_g_logit.data_ptr(), 1.0, n,
+              self.dlogit.data_ptr())
+        if self.want_param_grads:
+            emit_conv_wgrad(b, self.g_l2, self.h, self.dlogit, gv(self.lin2.weight), ws, dbias=gv(self.lin2.bias))
+        emit_conv_dgrad(b, self.g_l2, self.dlogit, store.wp_bwd(self.r_l2), self.dh, resid=self.tap_g_h)
+        if self.want_param_grads:
+            emit_conv_wgrad(b, self.g_l1, self.acts[3], self.dh, gv(self.lin1.weight), ws, dbias=gv(self.lin1.bias))
+        emit_conv_fwd(b, self.g_l1_bwd, self.dh, store.wp_tco(self.r_l1), None, self.gas[3].view(n, 1, 1, 1, -1))
+        for i in range(len(self.convs) - 1, -1, -1):
+            g, z, nb, bn, cv = self.geoms[i], self.zs[i], self.nbs[i], self.bns[i], self.convs[i]
+            gc = g.c()
+            c = g.cout
+            rows_total = n * g.out_dhw[0] * g.out_dhw[1] * g.out_dhw[2]
+            brow = ops.norm_bwd_rows_bf16(rows_total, c)
+            gin, dz = self.gas[i], self.dzs[i]
+            g32 = int(gin.dtype == torch.float32)
+            base = brow * 3 * c + c                   # the apply pass's bias partials sit behind the rows finalize reads
+            bias_part = part[base:base + brow * c] if (self.want_param_grads and i > 0) else None
+            norm = (nb.scale.data_ptr(), nb.shift.data_ptr(), nb.mean.data_ptr(), nb.invstd.data_ptr())
+            if peer is None:
+                b.add("norm_bwd_reduce_bf16", L.mpgan_norm_bwd_reduce_bf16, gin.data_ptr(), g32, c, z.data_ptr(), c,
+                      *norm, 0.2, rows_total, c, part.data_ptr(), keep=(gin, z, nb, part))
+            else:
+                pt = ops.PeerTapsBF16(peer.zs[i], peer.nbs[i].scale, peer.nbs[i].shift, self.coef[i])
+                pc = pt.c()
+                b.add("norm_bwd_reduce_bf16_peer", L.mpgan_norm_bwd_reduce_bf16_peer, gin.data_ptr(), g32, c,
+                      z.data_ptr(), c, *norm, C.byref(pc), 0.2, rows_total, c, part.data_ptr(),
+                      keep=(gin, z, nb, part, pt, pc))
+            b.add("norm_bwd_finalize", L.mpgan_norm_bwd_finalize, part.data_ptr(), 1, brow, c, rows_total, 0,
+                  _p(gv(bn.weight)), _p(gv(bn.bias)), None, nb.c1.data_ptr(), nb.c2.data_ptr(), keep=(bn,))
+            if peer is None:
+                b.add("norm_bwd_apply_bf16", L.mpgan_norm_bwd_apply_bf16, gin.data_ptr(), g32, c, z.data_ptr(), c,
+                      *norm, nb.c1.data_ptr(), nb.c2.data_ptr(), 0.2, rows_total, c, dz.data_ptr(), c, _p(bias_part),
+                      keep=(dz,))
+            else:
+                b.add("norm_bwd_apply_bf16_peer", L.mpgan_norm_bwd_apply_bf16_peer, gin.data_ptr(), g32, c,
+                      z.data_ptr(), c, *norm, nb.c1.data_ptr(), nb.c2.data_ptr(), C.byref(pc), 0.2, rows_total, c,
+                      dz.data_ptr(), c, _p(bias_part), keep=(dz, pt, pc))
+            if self.want_param_grads:
+                if i > 0:
+                    b.add("reduce_partials", L.mpgan_reduce_partials, bias_part.data_ptr(), brow, c, c,
+                          gv(cv.bias).data_ptr(), 1.0, keep=(bias_part,))
+                    b.add("conv_backward_weight_bf16", L.mpgan_conv_backward_weight_bf16, C.byref(gc),
+                          self.acts[i - 1].data_ptr(), g.cin, dz.data_ptr(), c, gv(cv.weight).data_ptr(), 1.0,
+                          ws.data_ptr(), ws.numel() * 4, keep=(gc, ws), desc=_gdesc(g),
+                          tag=(_bf16_wgrad_kernel_name(g), 2.0 * conv_macs(g), conv_bytes(g, 2)))
+                else:
+                    b.add("conv_backward_weight_bf16dy", L.mpgan_conv_backward_weight_bf16dy, C.byref(gc),
+                          self.x_in.data_ptr(), 1, dz.data_ptr(), c, gv(cv.weight).data_ptr(), gv(cv.bias).data_ptr(),
+                          1.0, ws.data_ptr(), ws.numel() * 4, keep=(gc, ws), desc=_gdesc(g),
+                          tag=(wgrad_kernel_name(g, bf16_dy=True), 2.0 * conv_macs(g),
+                               conv_bytes(g, 2) + 2 * self.x_in.numel()))
+            if i > 0:
+                b.add("conv_backward_data_bf16", L.mpgan_conv_backward_data_bf16, C.byref(gc), dz.data_ptr(), c,
+                      self._wb16(i).data_ptr(), self.gas[i - 1].data_ptr(), g.cin, keep=(gc,), desc=_gdesc(g),
+                      tag=("dgrad:" + _bf16_kernel_name(g, True), 2.0 * conv_macs(g), conv_bytes(g, 2)))
+            elif self.want_input_grad:
+                b.add("conv_backward_data_bf16_to_f32", L.mpgan_conv_backward_data_bf16_to_f32, C.byref(gc),
+                      dz.data_ptr(), c, store.wp_bwd(self.recs[0]).data_ptr(), self.g_x.data_ptr(), 1,
+                      keep=(gc, self.g_x), desc=_gdesc(g))
+        self._bwd_cache[key] = b
+        return b
+
+    def deposit_tap_grad(self, key: int, g: torch.Tensor):
+        raise NotImplementedError(
+            "gradients through materialised perceptual taps are not offered in bf16 storage mode: use the fused "
+            "mpgan_amd.gan_patch.perceptual_loss on the two TapDicts (or storage_dtype='f32')")
+
+    def backward_program_ext(self, peer):
+        raise NotImplementedError("backward_program_ext: fp32 storage only (see deposit_tap_grad)")

@@ -75,11 +75,18 @@ class _PerceptualFn(torch.autograd.Function):
     def forward(ctx, h_fake, h_real, taps_fake, taps_real):
         pf, pr = taps_fake.plan, taps_real.plan
         dev = h_fake.device
+        bf16 = pf.zs[0].dtype == torch.bfloat16
+        if bf16 != (pr.zs[0].dtype == torch.bfloat16):
+            raise ValueError("perceptual_loss: the two passes were run in different storage modes")
         part = torch.empty(ops.tap_l1_partials(), device=dev)
         nl = len(pf.zs)
         vals = torch.empty(3 * nl + 3, device=dev)     # the 16 L1 means ([z, y, a] per layer; a of the last layer
         for i in range(nl):                            # stands for keys 11 and 12), weighted by pf.perc_w_fwd
-            ops.tap_l1(pf.zs[i], pf.lrelu(pf.nbs[i]), pr.zs[i], pr.lrelu(pr.nbs[i]), part, vals[3 * i:3 * i + 3])
+            if bf16:                                   # (bf16 storage: the taps of the stored z)
+                ops.tap_l1_bf16(pf.zs[i], pf.nbs[i].scale, pf.nbs[i].shift, pr.zs[i], pr.nbs[i].scale, pr.nbs[i].shift,
+                                0.2, part, vals[3 * i:3 * i + 3])
+            else:
+                ops.tap_l1(pf.zs[i], pf.lrelu(pf.nbs[i]), pr.zs[i], pr.lrelu(pr.nbs[i]), part, vals[3 * i:3 * i + 3])
         l1part = torch.empty(ops.l1_partials(), device=dev)
         for k, (a, b) in enumerate(((pf.h, pr.h), (pf.logit, pr.logit), (pf.prob, pr.prob))):
             ops.l1_loss(a.reshape(-1), b.reshape(-1), l1part, vals[3 * nl + k])
@@ -132,14 +139,23 @@ def perceptual_loss(y_hat_activations, y_activations):
 
 
 class GAN(nn.Module):
-    """test_runs/GAN.py:236-464 without Lightning."""
+    """test_runs/GAN.py:236-464 without Lightning.
+    storage_dtype: the patch discriminator's storage mode ("f32" or "bf16", see PatchDiscriminator); matmul_dtype: the
+    generator's ("f32" or "bf16", see CasNetGenerator), None = follow storage_dtype (as variant A's GAN does)."""
 
     def __init__(self, channels, width, height, depth=None, latent_dim: int = 100, lr: float = 0.0002,
                  b1: float = 0.5, b2: float = 0.999, batch_size: int = 64, example_data=None,
                  one_sided_label_value=0.9, *, dimensions: Optional[int] = None, n_unet_blocks: int = 4,
                  unet_channels=(32, 64, 128, 256), unet_strides=(2, 2, 2, 2), roi_size=None, num_samples: int = 128,
-                 crop_seed: Optional[int] = None, use_perceptual: bool = True, device="cuda", **kwargs):
+                 crop_seed: Optional[int] = None, use_perceptual: bool = True, device="cuda", storage_dtype: str = "f32",
+                 matmul_dtype: Optional[str] = None, **kwargs):
         super().__init__()
+        if storage_dtype not in ("f32", "bf16"):
+            raise ValueError(f"storage_dtype must be 'f32' or 'bf16', got {storage_dtype!r}")
+        if matmul_dtype is None:
+            matmul_dtype = storage_dtype
+        if matmul_dtype not in ("f32", "bf16"):
+            raise ValueError(f"matmul_dtype must be 'f32', 'bf16' or None, got {matmul_dtype!r}")
         if dimensions is None:
             dimensions = 3 if depth is not None else 2
         self.hparams = types.SimpleNamespace(latent_dim=latent_dim, lr=lr, b1=b1, b2=b2, batch_size=batch_size,
@@ -147,9 +163,9 @@ class GAN(nn.Module):
         data_shape = (channels, width, height) + ((depth,) if dimensions == 3 else ())
         roi_size = tuple(roi_size) if roi_size is not None else (16,) * dimensions
         self.generator = CasNetGenerator(data_shape, n_unet_blocks, dimensions=dimensions, channels=unet_channels,
-                                         strides=unet_strides, device=device)
+                                         strides=unet_strides, device=device, matmul_dtype=matmul_dtype)
         self.discriminator = PatchDiscriminator(data_shape, use_perceptual=use_perceptual, dimensions=dimensions,
-                                                patch=roi_size[0], device=device)
+                                                patch=roi_size[0], device=device, storage_dtype=storage_dtype)
         self.patch_transform = PatchSampler(roi_size, num_samples, crop_seed)
         self.logged: Dict[str, torch.Tensor] = {}
         self.ddp = None

@@ -403,6 +403,17 @@ class TapSet:
         """The tap as the reference would hold it (NC(D)HW, detached) -- for inspection / tests."""
         plan, dims = self.plan, self.plan.dims
         n = plan.n
+        if key < 12 and plan.zs[0].dtype == torch.bfloat16:
+            # bf16 storage: the taps of the stored z (DESIGN.md 3a), in fp32: z exactly, y = z*scale + shift, a = act(y)
+            i, kind = divmod(key, 3)
+            z, nb = plan.zs[i], plan.nbs[i]
+            t = torch.empty(z.shape, device=z.device)
+            if kind == 0:
+                ops.norm_act_bf16(z, torch.ones_like(nb.scale), torch.zeros_like(nb.shift), 1.0, t)
+            else:
+                ops.norm_act_bf16(z, nb.scale, nb.shift, 0.2 if kind == 2 else 1.0, t)
+            t = t.permute(0, 4, 1, 2, 3)
+            return (t.squeeze(2) if dims == 2 else t).contiguous()
         if key < 12:
             i, kind = divmod(key, 3)
             z = plan.zs[i]
@@ -477,10 +488,11 @@ class _PatchDiscFn(torch.autograd.Function):
         spatial = _spatial(x, disc.dimensions)
         n = x.shape[0]
         store = disc.store
-        from .engine import PatchDiscPlan
-        key = ("patch", n, spatial, need_bwd, want_in, want_par)
-        plan = disc._acquire(key, lambda: PatchDiscPlan(disc, store, n, spatial, want_backward=need_bwd,
-                                                        want_input_grad=want_in, want_param_grads=want_par))
+        from .engine import PatchDiscPlan, PatchDiscPlanBF16
+        key = ("patch", n, spatial, need_bwd, want_in, want_par, disc.storage_dtype)
+        plan_cls = PatchDiscPlanBF16 if disc.storage_dtype == "bf16" else PatchDiscPlan
+        plan = disc._acquire(key, lambda: plan_cls(disc, store, n, spatial, want_backward=need_bwd,
+                                                   want_input_grad=want_in, want_param_grads=want_par))
         lease = _Lease(plan)
         plan.clear_taps()
         plan.x_in.view(-1).copy_(x.reshape(-1))
@@ -515,13 +527,19 @@ class _PatchDiscFn(torch.autograd.Function):
 
 
 class PatchDiscriminator(_EngineModule):
-    """test_runs/GAN.py:136-198: returns (validity, perceptual_dict)."""
+    """test_runs/GAN.py:136-198: returns (validity, perceptual_dict).
+    storage_dtype="bf16": activations, activation gradients and packed weights of the three dense convs in bf16 in
+    HBM, with the perceptual taps defined on the stored raw conv outputs; parameters, statistics,
+    weight gradients and Adam stay fp32.  Gradients through materialised taps need storage_dtype="f32"."""
 
-    def __init__(self, img_shape, use_perceptual=True, *, dimensions=3, patch=16, device=None):
+    def __init__(self, img_shape, use_perceptual=True, *, dimensions=3, patch=16, device=None, storage_dtype="f32"):
         super().__init__()
+        if storage_dtype not in ("f32", "bf16"):
+            raise ValueError(f"storage_dtype must be 'f32' or 'bf16', got {storage_dtype!r}")
         self.use_perceptual = use_perceptual
         self.img_shape = img_shape
         self.dimensions = dimensions
+        self.storage_dtype = storage_dtype
         Cv, Bn = _CONV[dimensions], _BN[dimensions]
         self.model_conv = nn.Sequential(
             Cv(1, 64, 3, 1), Bn(64), nn.LeakyReLU(0.2, inplace=True),

@@ -14,7 +14,7 @@ from typing import Optional, Sequence, Tuple
 
 import torch
 
-from ._lib import ConvGeomC, NormFoldC, PeerTapsC, PrologueC, check, lib
+from ._lib import ConvGeomC, NormFoldC, PeerTapsBF16C, PeerTapsC, PrologueC, check, lib
 
 ACT_NONE = 0
 ACT_LEAKY = 1
@@ -713,6 +713,70 @@ def norm_bwd_apply_bf16(g, z, scale, shift, mean, invstd, c1, c2, slope: float, 
                                           c1.data_ptr(), c2.data_ptr(), float(slope), n * P, c, dz.data_ptr(), lddz,
                                           _ptr(bias_partials), _stream()), "norm_bwd_apply_bf16")
     return dz
+
+
+@dataclass
+class PeerTapsBF16:
+    """The other pass of a perceptual-loss pair in bf16 storage (see mpgan_peer_taps_bf16): its stored bf16 z."""
+    z: torch.Tensor
+    scale: torch.Tensor
+    shift: torch.Tensor
+    coef: torch.Tensor  # device float[3]
+
+    def c(self) -> PeerTapsBF16C:
+        t = PeerTapsBF16C()
+        t.z_peer = self.z.data_ptr()
+        t.ld_peer = _clx(self.z, BF16, "peer z")[2]
+        t.scale_peer = self.scale.data_ptr()
+        t.shift_peer = self.shift.data_ptr()
+        t.coef = self.coef.data_ptr()
+        return t
+
+
+def norm_bwd_reduce_bf16_peer(g, z, scale, shift, mean, invstd, peer: PeerTapsBF16, slope: float, partials):
+    n, P, ldz = _clx(z, BF16, "norm_bwd_reduce_bf16_peer z")
+    _, _, ldg = _clx(g, g.dtype, "norm_bwd_reduce_bf16_peer g")
+    if peer.z.shape != z.shape:
+        raise ValueError("norm_bwd_reduce_bf16_peer: peer z must match z")
+    c = z.shape[-1]
+    if partials.numel() < norm_bwd_rows_bf16(n * P, c) * 3 * c + c:
+        raise ValueError("norm_bwd_reduce_bf16_peer: partials too small")
+    pc = peer.c()
+    check(lib().mpgan_norm_bwd_reduce_bf16_peer(g.data_ptr(), int(g.dtype == torch.float32), ldg, z.data_ptr(), ldz,
+                                                scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
+                                                C.byref(pc), float(slope), n * P, c, partials.data_ptr(), _stream()),
+          "norm_bwd_reduce_bf16_peer")
+
+
+def norm_bwd_apply_bf16_peer(g, z, scale, shift, mean, invstd, c1, c2, peer: PeerTapsBF16, slope: float, dz,
+                             bias_partials=None):
+    n, P, ldz = _clx(z, BF16, "norm_bwd_apply_bf16_peer z")
+    _, _, ldg = _clx(g, g.dtype, "norm_bwd_apply_bf16_peer g")
+    _, _, lddz = _clx(dz, BF16, "norm_bwd_apply_bf16_peer dz")
+    if peer.z.shape != z.shape:
+        raise ValueError("norm_bwd_apply_bf16_peer: peer z must match z")
+    c = z.shape[-1]
+    pc = peer.c()
+    check(lib().mpgan_norm_bwd_apply_bf16_peer(g.data_ptr(), int(g.dtype == torch.float32), ldg, z.data_ptr(), ldz,
+                                               scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
+                                               c1.data_ptr(), c2.data_ptr(), C.byref(pc), float(slope), n * P, c,
+                                               dz.data_ptr(), lddz, _ptr(bias_partials), _stream()),
+          "norm_bwd_apply_bf16_peer")
+    return dz
+
+
+def tap_l1_bf16(za, scale_a, shift_a, zb, scale_b, shift_b, slope: float, partials, out3):
+    """out3 = (mean|z_a-z_b|, mean|y_a-y_b|, mean|a_a-a_b|) over two passes' stored bf16 z (mpgan_tap_l1_bf16)."""
+    n, P, lda = _clx(za, BF16, "tap_l1_bf16 a")
+    _, _, ldb = _clx(zb, BF16, "tap_l1_bf16 b")
+    if za.shape != zb.shape:
+        raise ValueError("tap_l1_bf16: shape mismatch")
+    if partials.numel() < tap_l1_partials():
+        raise ValueError("tap_l1_bf16: partials too small")
+    check(lib().mpgan_tap_l1_bf16(za.data_ptr(), lda, scale_a.data_ptr(), shift_a.data_ptr(), zb.data_ptr(), ldb,
+                                  scale_b.data_ptr(), shift_b.data_ptr(), float(slope), n * P, za.shape[-1],
+                                  partials.data_ptr(), out3.data_ptr(), _stream()), "tap_l1_bf16")
+    return out3
 
 
 # --------------------------------------------------------------------------

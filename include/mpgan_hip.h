@@ -529,6 +529,34 @@ int mpgan_norm_bwd_apply_bf16(const void* g, int32_t g_f32, int32_t ldg, const v
                               const float* c2, float slope, int64_t rows, int32_t c, void* dz, int32_t lddz,
                               float* bias_partials, void* stream);
 
+/* Variant B (the patch discriminator, test_runs/GAN.py:136-198,288-298) in bf16 storage: the perceptual taps of a
+ * layer are defined on the STORED bf16 raw conv output z: y = z*scale + shift and a = LeakyReLU(y) in fp32. */
+typedef struct {
+  const void* z_peer;       /* the other pass's stored bf16 raw conv output, same shape */
+  int32_t ld_peer;
+  const float* scale_peer;  /* its norm scale / shift (per channel) */
+  const float* shift_peer;
+  const float* coef;        /* device float[3]: (z, y, a) gradient coefficients; required */
+} mpgan_peer_taps_bf16;
+
+/* mpgan_norm_bwd_reduce_bf16 / _apply_bf16 with the peer-tap terms of mpgan_norm_bwd_reduce / _apply:
+ *   g_a = g - c_a*sign(a_peer - a);  gy = g_a*act'(y) - c_y*sign(y_peer - y);  dz += -c_z*sign(z_peer - z).
+ * Same partial rows, bias partials and g_f32 switch as the entries without peer. */
+int mpgan_norm_bwd_reduce_bf16_peer(const void* g, int32_t g_f32, int32_t ldg, const void* z, int32_t ldz,
+                                    const float* scale, const float* shift, const float* mean, const float* invstd,
+                                    const mpgan_peer_taps_bf16* peer, float slope, int64_t rows, int32_t c,
+                                    float* partials, void* stream);
+int mpgan_norm_bwd_apply_bf16_peer(const void* g, int32_t g_f32, int32_t ldg, const void* z, int32_t ldz,
+                                   const float* scale, const float* shift, const float* mean, const float* invstd,
+                                   const float* c1, const float* c2, const mpgan_peer_taps_bf16* peer, float slope,
+                                   int64_t rows, int32_t c, void* dz, int32_t lddz, float* bias_partials, void* stream);
+/* mpgan_tap_l1 over two passes' bf16 z (C % 8, pitches % 8, 16-byte aligned), each with its fp32 scale / shift:
+ * out3 = (mean|z_a-z_b|, mean|y_a-y_b|, mean|a_a-a_b|), a = LeakyReLU_slope(y); partials >= mpgan_tap_l1_partials()
+ * floats.  A fixed-order two-stage reduction without atomics: the result is reproducible. */
+int mpgan_tap_l1_bf16(const void* za, int32_t lda, const float* scale_a, const float* shift_a, const void* zb,
+                      int32_t ldb, const float* scale_b, const float* shift_b, float slope, int64_t rows, int32_t c,
+                      float* partials, float* out3, void* stream);
+
 /* ---- sliding-window inference (MONAI 0.4.0 sliding_window_inference; code/GAN/minipig_inference.py:110-114) --
  * An image batch (B, C, D, H, W) contiguous fp32 (2-D: D = 1) is padded per dim by pad_lo before / the rest after
  * up to `padded` (never materialised: out-of-range reads give cval), covered by the windows start_z x start_y x
