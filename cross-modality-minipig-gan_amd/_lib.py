@@ -135,6 +135,9 @@ SIGNATURES = {
     "mpgan_conv_backward_weight_bf16": (_I, [_G, _P, _I, _P, _I, _P, _F, _P, _L, _P]),
     "mpgan_conv_forward_f32_to_bf16": (_I, [_G, _P, _I, _P, _P, _P, _P, _I, _P]),
     "mpgan_conv_backward_data_bf16_to_f32": (_I, [_G, _P, _I, _P, _P, _I, _P]),
+    # eval-mode discriminators in bf16 storage: BatchNorm (running statistics) + LeakyReLU in the conv's epilogue
+    "mpgan_conv_forward_act_bf16": (_I, [_G, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
+    "mpgan_conv_forward_act_f32_to_bf16": (_I, [_G, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
     "mpgan_conv_wgrad_workspace_bf16dy": (_L, [_G]),
     "mpgan_conv_backward_weight_bf16dy": (_I, [_G, _P, _I, _P, _I, _P, _P, _F, _P, _L, _P]),
     "mpgan_pack_weights_bf16": (_I, [_P, _P, _P, _I, _L, _P]),

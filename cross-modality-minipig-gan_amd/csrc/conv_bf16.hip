@@ -67,14 +67,22 @@ template <int TM, int TN, int WMW, int BNT>
 __device__ __forceinline__ void hb_epilogue(const f32x16 (&acc)[TM][TN], float* slab, const int* rowpix, float* part,
                                             int rowbase, int colw, int cbase, int wmw, const float* bias, float* stats_row,
                                             int n0, int Cout, char* goutb, int ldo, int tid, int lane,
-                                            const BwdStats* bw = nullptr, float* bwd_row = nullptr, bool pair_cols = false) {
+                                            const BwdStats* bw = nullptr, float* bwd_row = nullptr, bool pair_cols = false,
+                                            const EpiAct* epi = nullptr, bool out_f32 = false) {
   constexpr int PITCH = HbSlab<TN>::PITCH;
   const int li = lane & 31, lh = lane >> 5;
-  float bv[TN];
+  // epilogue activation (eval mode, EpiAct): the slab receives lrelu(acc * scale[c] + shift[c], slope[c]) instead of
+  // acc + bias, so the activated tensor is the only one stored
+  const bool act = epi != nullptr && epi->scale != nullptr;
+  float bv[TN], esc[TN], esh[TN], esl[TN];
 #pragma unroll
   for (int tn = 0; tn < TN; ++tn) {
     const int col = cbase + tn * 32 + li;
     bv[tn] = (bias && col < Cout) ? bias[col] : 0.f;
+    const bool okc = act && col < Cout;
+    esc[tn] = okc ? epi->scale[col] : 1.f;
+    esh[tn] = okc ? epi->shift[col] : 0.f;
+    esl[tn] = okc ? epi->slope[col] : 1.f;
   }
   if (stats_row) {
     float sm[TN], sq[TN];
@@ -136,11 +144,19 @@ __device__ __forceinline__ void hb_epilogue(const f32x16 (&acc)[TM][TN], float* 
 #pragma unroll
   for (int tm = 0; tm < TM; ++tm) {
     __builtin_amdgcn_wave_barrier();
+    if (act) {                                            // (wave-uniform; the plain path keeps its own instructions)
 #pragma unroll
-    for (int tn = 0; tn < TN; ++tn)
+      for (int tn = 0; tn < TN; ++tn)
 #pragma unroll
-      for (int r = 0; r < 16; ++r)
-        slab[((r & 3) + 8 * (r >> 2) + 4 * lh) * PITCH + tn * 32 + li] = acc[tm][tn][r] + bv[tn];
+        for (int r = 0; r < 16; ++r)
+          slab[((r & 3) + 8 * (r >> 2) + 4 * lh) * PITCH + tn * 32 + li] = epi_act1(acc[tm][tn][r], esc[tn], esh[tn], esl[tn]);
+    } else {
+#pragma unroll
+      for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          slab[((r & 3) + 8 * (r >> 2) + 4 * lh) * PITCH + tn * 32 + li] = acc[tm][tn][r] + bv[tn];
+    }
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int j = 0; j < 32 * CH / 64; ++j) {
@@ -149,6 +165,12 @@ __device__ __forceinline__ void hb_epilogue(const f32x16 (&acc)[TM][TN], float* 
       const float4 v0 = *reinterpret_cast<const float4*>(slab + row * PITCH + ch * 8);
       const float4 v1 = *reinterpret_cast<const float4*>(slab + row * PITCH + ch * 8 + 4);
       if (pix < 0 || cbase + ch * 8 >= Cout) continue;
+      if (out_f32) {                                      // the activated tensor the fp32 Linear head reads: not rounded
+        float4* o32 = reinterpret_cast<float4*>(goutb + ((long)pix * ldo + cbase + ch * 8) * 4);
+        o32[0] = v0;
+        o32[1] = v1;
+        continue;
+      }
       bf16x8 o;
       o[0] = (__bf16)v0.x; o[1] = (__bf16)v0.y; o[2] = (__bf16)v0.z; o[3] = (__bf16)v0.w;
       o[4] = (__bf16)v1.x; o[5] = (__bf16)v1.y; o[6] = (__bf16)v1.z; o[7] = (__bf16)v1.w;
@@ -203,6 +225,10 @@ __device__ __forceinline__ void hb_epilogue(const f32x16 (&acc)[TM][TN], float* 
     }
   }
 }
+
+// The activated tensor of an epilogue-activation launch leaves as bf16 (out_bf16) or, for the fp32 Linear head, as fp32;
+// without the activation the bf16 family always writes bf16.
+__device__ __forceinline__ bool hb_out_f32(const GatherConv& p) { return p.epi.scale != nullptr && !p.out_bf16; }
 
 constexpr int HB_BM = 256;          // pixels per tile
 constexpr int HB_BK = 64;           // K elements per step (one 128-byte LDS row)
@@ -428,6 +454,19 @@ __global__ __launch_bounds__(NW * 64, 1) void gather_conv_bf16_kernel(const Gath
   for (int tn = 0; tn < TN; ++tn) {
     const int col = (wn * TN + tn) * 32 + li;
     const float bv = (p.bias && n0 + col < Cout) ? p.bias[n0 + col] : 0.f;
+    if (p.epi.scale) {                                // epilogue activation (EpiAct; block-uniform): see hb_epilogue
+      const bool okc = n0 + col < Cout;
+      const float esc = okc ? p.epi.scale[n0 + col] : 1.f, esh = okc ? p.epi.shift[n0 + col] : 0.f,
+                  esl = okc ? p.epi.slope[n0 + col] : 1.f;
+#pragma unroll
+      for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int row = wm * (HB_BM / T::WM) + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+          img[row * T::IMG_PITCH + col] = epi_act1(acc[tm][tn][r], esc, esh, esl);
+        }
+      continue;
+    }
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
@@ -466,12 +505,19 @@ __global__ __launch_bounds__(NW * 64, 1) void gather_conv_bf16_kernel(const Gath
   }
   char* goutb = reinterpret_cast<char*>(p.out);
   constexpr int CHUNKS = BN / 8;                      // 16-byte chunks per row
+  const bool out_f32 = hb_out_f32(p);
   for (int q = tid; q < HB_BM * CHUNKS; q += NT) {
     const int row = q / CHUNKS, ch = q % CHUNKS;
     const int pix = rowpix[row];
     if (pix < 0 || n0 + ch * 8 >= Cout) continue;
     const float4 v0 = *reinterpret_cast<const float4*>(img + row * T::IMG_PITCH + ch * 8);
     const float4 v1 = *reinterpret_cast<const float4*>(img + row * T::IMG_PITCH + ch * 8 + 4);
+    if (out_f32) {
+      float4* o32 = reinterpret_cast<float4*>(goutb + ((long)pix * p.ldo + n0 + ch * 8) * 4);
+      o32[0] = v0;
+      o32[1] = v1;
+      continue;
+    }
     bf16x8 o;
     o[0] = (__bf16)v0.x; o[1] = (__bf16)v0.y; o[2] = (__bf16)v0.z; o[3] = (__bf16)v0.w;
     o[4] = (__bf16)v1.x; o[5] = (__bf16)v1.y; o[6] = (__bf16)v1.z; o[7] = (__bf16)v1.w;
@@ -896,12 +942,13 @@ __global__ __launch_bounds__(512, 1) void gather_conv_bf16_wide_kernel(const Gat
   }
   const int cbase = PAIR ? (wn & 1) * 64 : n0 + wn * 64;             // first produced channel of this wave's columns
   const BwdStats bwl = p.bwd;                                        // (a local copy: no pointer into the kernel arguments)
+  const EpiAct epl = p.epi;
   __syncthreads();
   hb_epilogue<TM, TN, WM, BN>(acc, reinterpret_cast<float*>(lds + wid * T::EP_WAVE),
                               rowpix + (PAIR ? (wn >> 1) * BM : 0), reinterpret_cast<float*>(lds + T::EP_PART), wm * 128,
                               wn * 64, cbase, wm, p.bias, (!PAIR && p.stats) ? p.stats + (long)stats_row * 2 * Cout : nullptr,
                               n0, Cout, reinterpret_cast<char*>(p.out), p.ldo, tid, lane, &bwl,
-                              bwl.part ? bwl.part + (long)stats_row * 3 * Cout : nullptr, PAIR);
+                              bwl.part ? bwl.part + (long)stats_row * 3 * Cout : nullptr, PAIR, &epl, hb_out_f32(p));
 }
 
 // Which K-stepped form serves a gather: 0 = 256 x 128/64 tile (gather_conv_bf16_kernel), 1 = 256 x 256, 2 = 512 x 128,
@@ -1231,12 +1278,13 @@ __global__ __launch_bounds__(512, 1) void gather_patch_bf16_kernel(const GatherC
     rowpix[tid] = (oz < ph.Mz && oy < ph.My && ox < ph.Mx) ? ((n * p.Do + oz) * p.Ho + oy) * p.Wo + ox : -1;
   }
   const BwdStats bwl = p.bwd;                          // (a local copy: no pointer into the kernel arguments)
+  const EpiAct epl = p.epi;
   __syncthreads();
   hb_epilogue<TM, TN, T::WM, BN>(acc, reinterpret_cast<float*>(lds + wid * HbSlab<TN>::WAVE), rowpix,
                                  reinterpret_cast<float*>(lds + T::EP_PART), wm * TM * 32, wn * (BN / WN), n0 + wn * (BN / WN), wm,
                                  p.bias, p.stats ? p.stats + (long)stats_row * 2 * Cout : nullptr, n0, Cout,
                                  reinterpret_cast<char*>(p.out), p.ldo, tid, lane, &bwl,
-                                 bwl.part ? bwl.part + (long)stats_row * 3 * Cout : nullptr, false);
+                                 bwl.part ? bwl.part + (long)stats_row * 3 * Cout : nullptr, false, &epl, hb_out_f32(p));
 }
 
 static bool hp_ok(const GatherConv& p) {
@@ -1519,12 +1567,13 @@ __global__ __launch_bounds__(512, 1) void gather_patch8_bf16_kernel(const Gather
     rowpix[tid] = (oz < ph.Mz && oy < ph.My && ox < ph.Mx) ? ((n * p.Do + oz) * p.Ho + oy) * p.Wo + ox : -1;
   }
   const BwdStats bwl = p.bwd;                          // (a local copy: no pointer into the kernel arguments)
+  const EpiAct epl = p.epi;
   __syncthreads();
   hb_epilogue<TM, TN, T::WM, BN>(acc, reinterpret_cast<float*>(lds + wid * HbSlab<TN>::WAVE), rowpix,
                                  reinterpret_cast<float*>(lds + T::EP_PART), wm * TM * 32, wn * (BN / WN), n0 + wn * (BN / WN), wm,
                                  p.bias, p.stats ? p.stats + (long)stats_row * 2 * Cout : nullptr, n0, Cout,
                                  reinterpret_cast<char*>(p.out), p.ldo, tid, lane, &bwl,
-                                 bwl.part ? bwl.part + (long)stats_row * 3 * Cout : nullptr, false);
+                                 bwl.part ? bwl.part + (long)stats_row * 3 * Cout : nullptr, false, &epl, hb_out_f32(p));
 }
 
 // 8 x 8 x 8 tiles pay on maps of at least 16 pixels per dimension whose extent wastes little in the last tile
@@ -1728,6 +1777,8 @@ static int hb_dispatch(const GatherConv& p, hipStream_t st, const char* what) {
   if (rc) return rc;
   const long maxM = max_phase_pixels(p);
   if (maxM == 0) return MPGAN_OK;
+  MPGAN_UNSUPPORTED(p.epi.scale && (p.stats || p.bwd.part), "%s: the epilogue activation goes with a plain forward (no fused "
+                    "statistics or norm-backward sums)", what);
   const Bf16Choice c = choose_bf16(p);
   if (p.stats || p.bwd.part) {
     rc = hb_pitch_rule(p, c, what);
@@ -2777,6 +2828,33 @@ extern "C" int mpgan_conv_forward_bf16(const mpgan_conv_geom* g, const void* x, 
   set_geom_flags(p, g);
   build_gather_bf16(p, g, false);
   return hb_dispatch(p, (hipStream_t)stream, "conv_forward_bf16");
+}
+
+// Forward conv of the eval-mode bf16 discriminators: y = lrelu(acc * scale[c] + shift[c], slope[c]), acc the fp32 MFMA
+// accumulator of bf16 x and bf16 w -- running-statistics BatchNorm, LeakyReLU and the conv's bias (folded into `shift`)
+// in the epilogue of whichever form choose_bf16 picks, so the activated tensor is stored ONCE: rounded to bf16 (to nearest
+// even), or as fp32 (y_f32) for the layer the fp32 Linear head reads.  No raw z, no norm_act_bf16 pass; stats_partials must be null.
+extern "C" int mpgan_conv_forward_act_bf16(const mpgan_conv_geom* g, const void* x, int32_t ldx, const void* w_packed,
+                                           const float* scale, const float* shift, const float* slope,
+                                           float* stats_partials, void* y, int32_t ldy, int32_t y_f32, void* stream) {
+  int rc = check_geom(g);
+  if (rc) return rc;
+  MPGAN_CHECK_ARG(x && w_packed && y && scale && shift && slope, "conv_forward_act_bf16: null pointer");
+  MPGAN_CHECK_ARG(ldx >= g->cin && ldy >= g->cout, "conv_forward_act_bf16: bad pitch");
+  MPGAN_CHECK_ARG(((reinterpret_cast<uintptr_t>(scale) | reinterpret_cast<uintptr_t>(shift) | reinterpret_cast<uintptr_t>(slope)) & 15) == 0,
+                  "conv_forward_act_bf16: scale / shift / slope must be 16-byte aligned");
+  MPGAN_CHECK_ARG(stats_partials == nullptr, "conv_forward_act_bf16: the epilogue activation goes without fused statistics "
+                                               "(they describe the raw conv output)");
+  MPGAN_UNSUPPORTED(y_f32 && ldy % 4 != 0, "conv_forward_act_bf16: fp32 output pitch %% 4");
+  GatherConv p{};
+  p.in = static_cast<const float*>(x); p.wp = static_cast<const float*>(w_packed); p.out = static_cast<float*>(y);
+  p.pro = make_pro(nullptr);
+  p.epi.scale = scale; p.epi.shift = shift; p.epi.slope = slope;
+  p.out_bf16 = y_f32 ? 0 : 1;
+  p.ldi = ldx; p.ldo = ldy;
+  set_geom_flags(p, g);
+  build_gather_bf16(p, g, false);
+  return hb_dispatch(p, (hipStream_t)stream, "conv_forward_act_bf16");
 }
 
 extern "C" int mpgan_conv_backward_data_bf16(const mpgan_conv_geom* g, const void* dy, int32_t lddy,

@@ -41,6 +41,8 @@ struct BwdStats {
 //   y = prelu(acc * scale[c] + shift[c], slope[c]) (+ resid) (tanh)
 // (the conv's own bias is folded into shift; slope[c] = 1 leaves a channel linear -- the residual half of a fused
 // unit0 || residual conv).  scale == nullptr: off.  Never combined with fused statistics or norm-backward sums.
+// The bf16 family (conv_bf16.hip: eval-mode discriminators) applies it to the fp32 accumulator in the same place and stores
+// the activated tensor once, as bf16 when out_bf16 is set and as fp32 otherwise (no resid / tanh there).
 struct EpiAct {
   const float* scale;
   const float* shift;
@@ -72,7 +74,8 @@ struct GatherConv {
   int acc_rep;
   NormFold fold;         // consumer side: fold the producer's accumulators into the prologue's scale / shift
   BwdStats bwd;          // see above (part == null: off)
-  int in_bf16, out_bf16; // thin (VALU) kernels of the bf16 path: `in` / `out` point at bf16 data (weights stay fp32)
+  int in_bf16, out_bf16; // thin (VALU) kernels of the bf16 path: `in` / `out` point at bf16 data (weights stay fp32);
+                         // bf16 MFMA kernels with `epi`: out_bf16 = 0 stores the activated tensor as fp32 (hb_out_f32)
   int mm16;              // MPGAN_CONV_MM_BF16: matrix operands rounded to bf16 into LDS, bf16 MFMA, fp32 accumulation
   int min_blocks;        // the geometry's big-tile threshold (0: default), see mpgan_conv_geom
   EpiAct epi;            // epilogue activation (eval-mode inference); epi.scale == nullptr: off

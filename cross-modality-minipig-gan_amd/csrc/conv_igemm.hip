@@ -681,6 +681,12 @@ __global__ __launch_bounds__(256) void thin_cin1_full_kernel(const GatherConv p)
       __bf16* o = reinterpret_cast<__bf16*>(p.out) + (long)d.opix * p.ldo;
 #pragma unroll
       for (int q = 0; q < CQ; ++q) {
+        if (p.epi.scale) {                   // eval mode: the ACTIVATED value is the one rounded and stored (scalar loads)
+          const float4 sc = *reinterpret_cast<const float4*>(p.epi.scale + 4 * q), sh = *reinterpret_cast<const float4*>(p.epi.shift + 4 * q),
+                       sl = *reinterpret_cast<const float4*>(p.epi.slope + 4 * q);
+          acc[q].x = epi_act1(acc[q].x, sc.x, sh.x, sl.x); acc[q].y = epi_act1(acc[q].y, sc.y, sh.y, sl.y);
+          acc[q].z = epi_act1(acc[q].z, sc.z, sh.z, sl.z); acc[q].w = epi_act1(acc[q].w, sc.w, sh.w, sl.w);
+        }
         bf16x4 t;
         t[0] = (__bf16)acc[q].x; t[1] = (__bf16)acc[q].y; t[2] = (__bf16)acc[q].z; t[3] = (__bf16)acc[q].w;
         *reinterpret_cast<bf16x4*>(o + 4 * q) = t;
@@ -1141,6 +1147,8 @@ __global__ __launch_bounds__(256) void thin_cin1_rows_kernel(const GatherConv p)
 #pragma unroll
   for (int t = 0; t < T; ++t) w[t] = p.wp[(long)lane * T + t];               // packed [Cout][tap][Cin = 1]
   const float bv = p.bias ? p.bias[lane] : 0.f;
+  const bool act = OUT_BF16 && p.epi.scale != nullptr;   // eval mode (bf16 out only, see thin_cin1_rows_ok): lane = channel
+  const float esc = act ? p.epi.scale[lane] : 1.f, esh = act ? p.epi.shift[lane] : 0.f, esl = act ? p.epi.slope[lane] : 1.f;
   float s1 = 0.f, s2 = 0.f;
   for (int r = (int)blockIdx.x * 4 + wave; r < rows; r += nwaves) {
     const int my = r % ph.My, q = r / ph.My;
@@ -1167,7 +1175,7 @@ __global__ __launch_bounds__(256) void thin_cin1_rows_kernel(const GatherConv p)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const long e = (orow + x0 + j) * p.ldo + lane;
-        if constexpr (OUT_BF16) reinterpret_cast<__bf16*>(p.out)[e] = (__bf16)o[j];
+        if constexpr (OUT_BF16) reinterpret_cast<__bf16*>(p.out)[e] = (__bf16)(act ? epi_act1(o[j], esc, esh, esl) : o[j]);
         else p.out[e] = o[j];
         const float v = j >= first ? o[j] : 0.f;
         s1 += v;
@@ -2741,8 +2749,11 @@ static GatherChoice choose_thin(const GatherConv& p, long maxM, GatherChoice c) 
                     (!p.bias || (reinterpret_cast<uintptr_t>(p.bias) & 15) == 0)),
                   "thin conv (bf16 out): needs Cin == 1, Cout in {16, 32, 64}, no resid/tanh, aligned output");
     CHOICE_REFUSE(p.stats && p.Cout > 64, "thin conv (bf16 out): fused statistics up to 64 channels");
+    CHOICE_REFUSE(p.epi.scale && (p.stats || p.stats_acc), "thin conv (bf16 out): the epilogue activation goes without fused statistics");
     c.rows = (int)block_rows;
-    if (thin_cin1_rows_ok(p)) { c.form = GForm::ThinBf16OutRows; c.arg = T; return c; }
+    GatherConv plain = p;                  // (the row walker's bf16 instances carry the epilogue activation; the fp32 ones do not)
+    plain.epi.scale = nullptr;
+    if (thin_cin1_rows_ok(plain)) { c.form = GForm::ThinBf16OutRows; c.arg = T; return c; }
     c.form = GForm::ThinBf16OutFull;
     c.arg = p.Cout / 4;
     return c;
@@ -3400,6 +3411,33 @@ extern "C" int mpgan_conv_forward_f32_to_bf16(const mpgan_conv_geom* g, const fl
   build_forward(p, g->n, g->in_dhw, g->cin, g->out_dhw, g->cout, g->k, g->stride, g->pad);
   const long maxM = max_phase_pixels(p);
   MPGAN_CHECK_ARG(maxM < (1L << 31) - 256, "conv_forward_f32_to_bf16: more than 2^31 pixels");
+  return launch_chosen(p, choose_gather(p, maxM), maxM, (hipStream_t)stream);
+}
+
+// The same layer in eval mode: y (bf16) = lrelu(conv(x) * scale[c] + shift[c], slope[c]), the activated value rounded once
+// (mpgan_conv_forward_act_bf16's contract on the HBM-bound VALU kernels).  stats_partials must be null.
+extern "C" int mpgan_conv_forward_act_f32_to_bf16(const mpgan_conv_geom* g, const float* x, int32_t ldx,
+                                                  const float* w_packed, const float* scale, const float* shift,
+                                                  const float* slope, float* stats_partials, void* y, int32_t ldy,
+                                                  void* stream) {
+  int rc = check_geom(g);
+  if (rc) return rc;
+  MPGAN_CHECK_ARG(x && w_packed && y && scale && shift && slope, "conv_forward_act_f32_to_bf16: null pointer");
+  MPGAN_CHECK_ARG(ldx >= g->cin && ldy >= g->cout, "conv_forward_act_f32_to_bf16: bad pitch");
+  MPGAN_CHECK_ARG(((reinterpret_cast<uintptr_t>(scale) | reinterpret_cast<uintptr_t>(shift) | reinterpret_cast<uintptr_t>(slope)) & 15) == 0,
+                  "conv_forward_act_f32_to_bf16: scale / shift / slope must be 16-byte aligned");
+  MPGAN_CHECK_ARG(stats_partials == nullptr, "conv_forward_act_f32_to_bf16: the epilogue activation goes without fused "
+                                               "statistics (they describe the raw conv output)");
+  MPGAN_UNSUPPORTED(g->cin != 1 || g->transposed, "conv_forward_act_f32_to_bf16: ConvNd with one input channel only");
+  GatherConv p{};
+  p.in = x; p.wp = w_packed; p.out = static_cast<float*>(y);
+  p.pro = make_pro(nullptr);
+  p.epi.scale = scale; p.epi.shift = shift; p.epi.slope = slope;
+  p.ldi = ldx; p.ldo = ldy;
+  p.out_bf16 = 1;
+  build_forward(p, g->n, g->in_dhw, g->cin, g->out_dhw, g->cout, g->k, g->stride, g->pad);
+  const long maxM = max_phase_pixels(p);
+  MPGAN_CHECK_ARG(maxM < (1L << 31) - 256, "conv_forward_act_f32_to_bf16: more than 2^31 pixels");
   return launch_chosen(p, choose_gather(p, maxM), maxM, (hipStream_t)stream);
 }
 

@@ -767,6 +767,46 @@ def emit_epi_vectors(prog, rows, dev):
     prog.add("epi_vectors_multi", lib().mpgan_epi_vectors_multi, table.data_ptr(), len(rows), keep=(table,))
 
 
+class _ConstSlope:
+    """A LeakyReLU's slope as emit_conv_fwd_act / mpgan_epi_vectors_multi take an activation: a one-element device
+    tensor in the PReLU column of the table."""
+
+    def __init__(self, slope: float, dev):
+        self.weight = torch.full((1,), float(slope), device=dev)
+
+
+def epi_row(rows, cout, bias, norm_mod, act_mod, dev):
+    """Table row of mpgan_epi_vectors_multi for one eval-mode BatchNorm + activation layer; returns the (3, cpad)
+    tensor whose rows the launch fills with scale / shift / slope (each 16-byte aligned)."""
+    import struct
+    assert norm_mod.running_mean is not None, "eval plan: BatchNorm layers with running statistics only"
+    cpad = (cout + 3) // 4 * 4
+    vec = torch.empty(3, cpad, device=dev)
+    eps_bits = struct.unpack("<I", struct.pack("<f", float(norm_mod.eps)))[0]
+    rows.append([_p(norm_mod.weight) or 0, _p(norm_mod.bias) or 0, norm_mod.running_mean.data_ptr(),
+                 norm_mod.running_var.data_ptr(), _p(bias) or 0, _p(act_mod.weight), vec[0].data_ptr(),
+                 vec[1].data_ptr(), vec[2].data_ptr(), cout, cout, eps_bits])
+    return vec
+
+
+def emit_conv_fwd_act_bf16(prog, rows, g: ConvGeom, x, wp, bias, y, norm_mod, act_mod):
+    """Eval-mode conv of the bf16-storage discriminators: running-statistics BatchNorm + LeakyReLU in the epilogue of the
+    bf16 forward (mpgan_conv_forward_act_bf16; mpgan_conv_forward_act_f32_to_bf16 for the 1-input-channel layer), the
+    activated tensor stored once -- bf16, or fp32 when `y` is (the layer the fp32 head reads)."""
+    vec = epi_row(rows, g.cout, bias, norm_mod, act_mod, x.device)
+    gc = g.c()
+    if g.cin == 1:
+        prog.add("conv_forward_act_f32_to_bf16", lib().mpgan_conv_forward_act_f32_to_bf16, C.byref(gc), x.data_ptr(), 1,
+                 wp.data_ptr(), vec[0].data_ptr(), vec[1].data_ptr(), vec[2].data_ptr(), None, y.data_ptr(), g.cout,
+                 keep=(gc, x, wp, y, vec, norm_mod, act_mod, bias), desc=_gdesc(g),
+                 tag=("thin_cin1_full_kernel<16, true>", 2.0 * conv_macs(g), conv_bytes(g, 2) + 2 * x.numel()))
+        return
+    prog.add("conv_forward_act_bf16", lib().mpgan_conv_forward_act_bf16, C.byref(gc), x.data_ptr(), g.cin, wp.data_ptr(),
+             vec[0].data_ptr(), vec[1].data_ptr(), vec[2].data_ptr(), None, y.data_ptr(), g.cout,
+             int(y.dtype == torch.float32), keep=(gc, x, wp, y, vec, norm_mod, act_mod, bias), desc=_gdesc(g),
+             tag=(_bf16_kernel_name(g, False), 2.0 * conv_macs(g), conv_bytes(g, 2)))
+
+
 def emit_norm_act_add(prog, z, pz, r, pr, out, tanh=False, fold=None):
     """fold: mpgan_norm_fold of z's producer (this launch finalises its statistics)."""
     n, P, ldz = ops._cl(z, "norm_act_add z")
@@ -1385,11 +1425,17 @@ class DiscPlan:
     (code/GAN/GAN_final.py:159-209)."""
 
     def __init__(self, disc, store: ParamStore, n: int, spatial: Sequence[int], *, want_backward: bool,
-                 want_input_grad: bool, want_param_grads: bool):
+                 want_input_grad: bool, want_param_grads: bool, training: bool = True):
+        """training=False: the eval-mode program (running-statistics BatchNorm, forward only): every layer's BatchNorm
+        + LeakyReLU rides in its conv's epilogue (mpgan_conv_forward_act), the activated tensors are the only ones
+        stored, and the head reads the last one without a prologue.  The affine vectors are recomputed on the device
+        at every run from the live parameters and running statistics; nothing else of the module is touched."""
         dims = disc.dimensions
         dev = store.flat.device
         dhw = _t3(spatial, dims, 1)
         self.n, self.dhw, self.dims, self.store = n, dhw, dims, store
+        self.training = training
+        assert training or not want_backward, "eval plans are forward-only"
         E = lambda *shape: torch.empty(*shape, device=dev)
         convs = [disc.model_conv[i] for i in (0, 3, 6, 9)]
         bns = [disc.model_conv[i] for i in (1, 4, 7, 10)]
@@ -1410,6 +1456,8 @@ class DiscPlan:
             for k in cv.kernel_size:
                 taps *= k
             recs.append(store.register_conv(cv, cout=cv.out_channels, cin=cv.in_channels, taps=taps))
+            if not training:       # no statistics partials, no weight-gradient workspace
+                continue
             scratch.want_partials(n, size[0] * size[1] * size[2], cv.out_channels)
             scratch.want_ws(g)
             if g.cin > 1:          # rows of the backward-data launch that also reduces the previous layer's norm backward
@@ -1419,13 +1467,30 @@ class DiscPlan:
         if lin.in_features != P_last * c_last:
             raise ValueError(f"Linear.in_features {lin.in_features} != {c_last}*{P_last} for input {spatial}")
         rlin = store.register_conv(lin, cout=1, cin=c_last, taps=P_last)
-        scratch.alloc()
-        part, ws = scratch.partials, scratch.ws
         self.logit, self.prob = E(n), E(n)
         lin_part = E(ops.linear1_partials(n))
         L = lib()
         f = self.fwd = Program()
         store.emit_pack(f)
+        if not training:
+            leaky, rows, body = _ConstSlope(0.2, dev), [], Program()
+            src = self.x_in
+            for i, cv in enumerate(convs):           # zs[i] holds the ACTIVATED tensor here
+                emit_conv_fwd_act(body, rows, geoms[i], src, store.wp(recs[i]), cv.bias, zs[i], norm_mod=bns[i],
+                                  act_mod=leaky)
+                src = zs[i]
+            emit_epi_vectors(f, rows, dev)
+            f.extend(body)
+            f.add("linear1_forward", L.mpgan_linear1_forward, zs[-1].data_ptr(), None, n, P_last, c_last,
+                  store.wp(rlin).data_ptr(), lin.bias.data_ptr(), lin_part.data_ptr(), self.logit.data_ptr(),
+                  self.prob.data_ptr(), keep=(lin_part, zs))
+            self.acts = zs
+            self.busy = False
+            self.bwd = Program()
+            self.g_x = None
+            return
+        scratch.alloc()
+        part, ws = scratch.partials, scratch.ws
         lrelu = lambda nb: nb.prologue(ACT_LEAKY, 0.2, None)
         src, pro = self.x_in, None
         for i, cv in enumerate(convs):
@@ -1496,11 +1561,16 @@ class DiscPlanBF16:
     The first layer (1 input channel) runs on the HBM-bound VALU kernels with fp32 weights."""
 
     def __init__(self, disc, store: ParamStore, n: int, spatial: Sequence[int], *, want_backward: bool,
-                 want_input_grad: bool, want_param_grads: bool):
+                 want_input_grad: bool, want_param_grads: bool, training: bool = True):
+        """training=False: the eval-mode program (forward only): a_i = LeakyReLU(BN_running(conv_i)) comes out of each
+        conv's epilogue from the fp32 accumulator and is stored once (bf16; fp32 for the last layer) -- no raw z, no
+        statistics, no norm_act_bf16 pass (mpgan_conv_forward_act_bf16)."""
         dims = disc.dimensions
         dev = store.flat.device
         dhw = _t3(spatial, dims, 1)
         self.n, self.dhw, self.dims, self.store = n, dhw, dims, store
+        self.training = training
+        assert training or not want_backward, "eval plans are forward-only"
         bf = torch.bfloat16
         E = lambda *shape: torch.empty(*shape, device=dev)
         H = lambda *shape: torch.empty(*shape, device=dev, dtype=bf)
@@ -1519,13 +1589,16 @@ class DiscPlanBF16:
             size = g.out_dhw
             if min(size) < 1:
                 raise ValueError(f"discriminator input {spatial} too small")
-            zs.append(H(n, *size, cv.out_channels))
+            if training:
+                zs.append(H(n, *size, cv.out_channels))
             acts.append(E(n, *size, cv.out_channels) if i == 3 else H(n, *size, cv.out_channels))
             nbs.append(NormBuf(n, cv.out_channels, False, dev))
             taps = 1
             for k in cv.kernel_size:
                 taps *= k
             recs.append(store.register_conv(cv, cout=cv.out_channels, cin=cv.in_channels, taps=taps))
+            if not training:       # no raw outputs, statistics partials or weight-gradient workspace
+                continue
             rows_total = n * size[0] * size[1] * size[2]
             fwd_rows = (rows_total + 255) // 256 if i == 0 else ops.conv_stats_rows_bf16(g)
             bwd_rows = ops.norm_bwd_rows_bf16(rows_total, cv.out_channels)
@@ -1566,6 +1639,22 @@ class DiscPlanBF16:
               table16.data_ptr(), table16.shape[0], max(r.cout * r.cin * r.taps for r in recs[1:]),
               keep=(packed16, table16))
         src = self.x_in
+        if not training:
+            leaky, rows, body = _ConstSlope(0.2, dev), [], Program()
+            for i, cv in enumerate(convs):
+                emit_conv_fwd_act_bf16(body, rows, geoms[i], src, store.wp(recs[0]) if i == 0 else w16(i), cv.bias,
+                                       acts[i], bns[i], leaky)
+                src = acts[i]
+            emit_epi_vectors(f, rows, dev)
+            f.extend(body)
+            f.add("linear1_forward", L.mpgan_linear1_forward, acts[3].data_ptr(), None, n, P_last, c_last,
+                  store.wp(rlin).data_ptr(), lin.bias.data_ptr(), lin_part.data_ptr(), self.logit.data_ptr(),
+                  self.prob.data_ptr(), keep=(lin_part, acts))
+            self.zs, self.acts, self.nbs = zs, acts, nbs
+            self.busy = False
+            self.bwd = Program()
+            self.g_x = None
+            return
         for i, cv in enumerate(convs):
             g, z, nb, bn = geoms[i], zs[i], nbs[i], bns[i]
             gc = g.c()
@@ -1679,12 +1768,20 @@ class PatchDiscPlan:
     passes (`peer`), see mpgan_peer_taps."""
 
     def __init__(self, disc, store: ParamStore, n: int, spatial: Sequence[int], *, want_backward: bool,
-                 want_input_grad: bool, want_param_grads: bool):
+                 want_input_grad: bool, want_param_grads: bool, training: bool = True, keep_taps: bool = True):
+        """training=False: one of the two eval-mode programs (running-statistics BatchNorm, forward only).
+        keep_taps: the raw z_i are stored as in training and every BatchNorm's scale / shift come from ONE
+        mpgan_norm_from_running_multi launch instead of statistics + finalize -- consumers normalise on load, and
+        TapSet.materialize / the fused perceptual loss read the plan exactly as they read a training one (values only).
+        not keep_taps: the fused program of DiscPlan (BatchNorm + LeakyReLU in each conv's epilogue, activated tensors
+        only), the head reading the last one without a prologue."""
         dims = disc.dimensions
         dev = store.flat.device
         dhw = _t3(spatial, dims, 1)
         self.n, self.dhw, self.dims, self.store, self.disc = n, dhw, dims, store, disc
         self.want_input_grad, self.want_param_grads = want_input_grad, want_param_grads
+        self.training, self.keep_taps = training, keep_taps
+        assert training or not want_backward, "eval plans are forward-only"
         E = lambda *shape: torch.empty(*shape, device=dev)
         convs = [disc.model_conv[i] for i in (0, 3, 6, 9)]
         bns = [disc.model_conv[i] for i in (1, 4, 7, 10)]
@@ -1704,8 +1801,9 @@ class PatchDiscPlan:
             self.nbs.append(NormBuf(n, cv.out_channels, False, dev))
             self.recs.append(store.register_conv(cv, cout=cv.out_channels, cin=cv.in_channels,
                                                  taps=int(torch.tensor(cv.kernel_size).prod())))
-            scratch.want_partials(n, size[0] * size[1] * size[2], cv.out_channels)
-            scratch.want_ws(g)
+            if training:
+                scratch.want_partials(n, size[0] * size[1] * size[2], cv.out_channels)
+                scratch.want_ws(g)
         c_last = convs[-1].out_channels
         P_last = size[0] * size[1] * size[2]
         if lin1.in_features != P_last * c_last:
@@ -1717,8 +1815,9 @@ class PatchDiscPlan:
         # its data gradient as ONE GEMM: (P x 64) * (64 x taps*C) -> the channels-last gradient of the last map
         self.g_l1_bwd = ConvGeom(n, (1, 1, 1), lin1.out_features, P_last * c_last, (1, 1, 1), (1, 1, 1), (0, 0, 0))
         self.r_l2 = store.register_conv(lin2, cout=1, cin=lin1.out_features, taps=1)
-        scratch.want_ws(self.g_l1)
-        scratch.want_ws(self.g_l2)
+        if training:
+            scratch.want_ws(self.g_l1)
+            scratch.want_ws(self.g_l2)
         scratch.alloc()
         self.scratch = scratch
         part, ws = scratch.partials, scratch.ws
@@ -1730,20 +1829,39 @@ class PatchDiscPlan:
         f = self.fwd = Program()
         store.emit_pack(f)
         src, pro = self.x_in, None
-        for i, cv in enumerate(convs):
-            emit_conv_fwd_norm(f, self.geoms[i], src, store.wp(self.recs[i]), cv.bias, self.zs[i], self.nbs[i], bns[i],
-                               part, pro=pro)
-            src, pro = self.zs[i], self.lrelu(self.nbs[i])
-        gc1, pc = self.g_l1.c(), pro.c()
+        if not training and not keep_taps:
+            leaky, rows, body = _ConstSlope(0.2, dev), [], Program()
+            for i, cv in enumerate(convs):            # zs[i] holds the ACTIVATED tensor here
+                emit_conv_fwd_act(body, rows, self.geoms[i], src, store.wp(self.recs[i]), cv.bias, self.zs[i],
+                                  norm_mod=bns[i], act_mod=leaky)
+                src = self.zs[i]
+            emit_epi_vectors(f, rows, dev)
+            f.extend(body)
+        elif not training:
+            eval_norms, body = [], Program()
+            for i, cv in enumerate(convs):
+                emit_conv_fwd_norm(body, self.geoms[i], src, store.wp(self.recs[i]), cv.bias, self.zs[i], self.nbs[i],
+                                   bns[i], part, pro=pro, training=False, eval_norms=eval_norms)
+                src, pro = self.zs[i], self.lrelu(self.nbs[i])
+            emit_eval_norms(f, eval_norms, dev)
+            f.extend(body)
+        else:
+            for i, cv in enumerate(convs):
+                emit_conv_fwd_norm(f, self.geoms[i], src, store.wp(self.recs[i]), cv.bias, self.zs[i], self.nbs[i],
+                                   bns[i], part, pro=pro)
+                src, pro = self.zs[i], self.lrelu(self.nbs[i])
+        gc1, pc = self.g_l1.c(), (pro.c() if pro is not None else None)
         f.add("conv_forward_splitk", L.mpgan_conv_forward_splitk, C.byref(gc1), self.zs[-1].data_ptr(), _ld(self.zs[-1]),
-              store.wp(self.r_l1).data_ptr(), lin1.bias.data_ptr(), C.byref(pc), self.splitk_ws.data_ptr(),
-              self.splitk_ws.numel() * 4, self.h.data_ptr(), _ld(self.h), keep=(gc1, pc, pro),
-              tag=("gather_conv_pipe_kernel<splitK>", 2.0 * conv_macs(self.g_l1)))
+              store.wp(self.r_l1).data_ptr(), lin1.bias.data_ptr(), C.byref(pc) if pc is not None else None,
+              self.splitk_ws.data_ptr(), self.splitk_ws.numel() * 4, self.h.data_ptr(), _ld(self.h),
+              keep=(gc1, pc, pro), tag=("gather_conv_pipe_kernel<splitK>", 2.0 * conv_macs(self.g_l1)))
         emit_conv_fwd(f, self.g_l2, self.h, store.wp(self.r_l2), lin2.bias, self.logit)
         f.add("sigmoid_forward", L.mpgan_sigmoid_forward, self.logit.data_ptr(), n, self.prob.data_ptr())
         self.busy = False
         self.g_x = None
         self._bwd_cache = {}
+        if not training and keep_taps:
+            self._perc_weights(dev)
         if not want_backward:
             return
         self.gas = [E(*z.shape) for z in self.zs]
@@ -1764,6 +1882,10 @@ class PatchDiscPlan:
         self.tap_g_h, self.tap_g_logit, self.tap_g_prob = Z(*self.h.shape), Z(n), Z(n)
         self.coef_all = Z(4 * len(self.convs))                 # one buffer: the perceptual loss fills it in one launch
         self.coef = [self.coef_all[4 * i:4 * i + 4] for i in range(len(self.convs))]
+        self._perc_weights(dev)
+
+    def _perc_weights(self, dev):
+        """The perceptual loss's constant weights (all a tap-keeping eval plan needs of _tap_buffers: value only)."""
         # constant weights of the perceptual loss (test_runs/GAN.py:288-298: every tap's L1 mean / its numel; Flatten
         # repeats the last activation, key 12): forward terms in the order [layer0 z, y, a, layer1 ..., h, logit, prob]
         nl = len(self.convs)
@@ -1928,12 +2050,18 @@ class PatchDiscPlanBF16(PatchDiscPlan):
     Gradients deposited into materialised taps are not offered (deposit_tap_grad raises)."""
 
     def __init__(self, disc, store: ParamStore, n: int, spatial: Sequence[int], *, want_backward: bool,
-                 want_input_grad: bool, want_param_grads: bool):
+                 want_input_grad: bool, want_param_grads: bool, training: bool = True, keep_taps: bool = True):
+        """training=False: the eval-mode programs (see PatchDiscPlan).  keep_taps: raw bf16 z_i stored, scale / shift from
+        the running statistics (one mpgan_norm_from_running_multi launch), norm_act_bf16 as in training; not keep_taps:
+        each a_i straight from its conv's epilogue (mpgan_conv_forward_act_bf16), no z_i and no norm_act_bf16 pass."""
         dims = disc.dimensions
         dev = store.flat.device
         dhw = _t3(spatial, dims, 1)
         self.n, self.dhw, self.dims, self.store, self.disc = n, dhw, dims, store, disc
         self.want_input_grad, self.want_param_grads = want_input_grad, want_param_grads
+        self.training, self.keep_taps = training, keep_taps
+        assert training or not want_backward, "eval plans are forward-only"
+        fused_eval = not training and not keep_taps
         bf = torch.bfloat16
         E = lambda *shape: torch.empty(*shape, device=dev)
         H = lambda *shape: torch.empty(*shape, device=dev, dtype=bf)
@@ -1952,11 +2080,14 @@ class PatchDiscPlanBF16(PatchDiscPlan):
             if min(size) < 1:
                 raise ValueError(f"patch discriminator input {spatial} too small")
             c = cv.out_channels
-            self.zs.append(H(n, *size, c))
+            if not fused_eval:
+                self.zs.append(H(n, *size, c))
             self.acts.append(E(n, *size, c) if i == 3 else H(n, *size, c))
             self.nbs.append(NormBuf(n, c, False, dev))
             self.recs.append(store.register_conv(cv, cout=c, cin=cv.in_channels,
                                                  taps=int(torch.tensor(cv.kernel_size).prod())))
+            if not training:       # no statistics partials, no weight-gradient workspace
+                continue
             rows_total = n * size[0] * size[1] * size[2]
             fwd_rows = (rows_total + 255) // 256 if i == 0 else ops.conv_stats_rows_bf16(g)
             bwd_rows = ops.norm_bwd_rows_bf16(rows_total, c)
@@ -1973,8 +2104,9 @@ class PatchDiscPlanBF16(PatchDiscPlan):
         self.r_l1 = store.register_conv(lin1, cout=lin1.out_features, cin=c_last, taps=P_last, tco=True)
         self.g_l1_bwd = ConvGeom(n, (1, 1, 1), lin1.out_features, P_last * c_last, (1, 1, 1), (1, 1, 1), (0, 0, 0))
         self.r_l2 = store.register_conv(lin2, cout=1, cin=lin1.out_features, taps=1)
-        scratch.want_ws(self.g_l1)
-        scratch.want_ws(self.g_l2)
+        if training:
+            scratch.want_ws(self.g_l1)
+            scratch.want_ws(self.g_l2)
         scratch.alloc()
         self.scratch = scratch
         part = scratch.partials
@@ -2000,26 +2132,39 @@ class PatchDiscPlanBF16(PatchDiscPlan):
               table16.data_ptr(), table16.shape[0], max(r.cout * r.cin * r.taps for r in self.recs[1:]),
               keep=(self.packed16, table16))
         src = self.x_in
-        for i, cv in enumerate(convs):
+        if fused_eval:
+            leaky, erows, body = _ConstSlope(0.2, dev), [], Program()
+            for i, cv in enumerate(convs):
+                emit_conv_fwd_act_bf16(body, erows, self.geoms[i], src, store.wp(self.recs[0]) if i == 0 else self._wf16(i),
+                                       cv.bias, self.acts[i], bns[i], leaky)
+                src = self.acts[i]
+            emit_epi_vectors(f, erows, dev)
+            f.extend(body)
+        elif not training:
+            # every layer's scale / shift depend on parameters and running statistics only: one launch up front
+            emit_eval_norms(f, [(bns[i], self.nbs[i], self.geoms[i].cout) for i in range(len(convs))], dev)
+        for i, cv in enumerate(convs if not fused_eval else ()):
             g, z, nb, bn, a = self.geoms[i], self.zs[i], self.nbs[i], bns[i], self.acts[i]
             gc = g.c()
             rows_total = n * g.out_dhw[0] * g.out_dhw[1] * g.out_dhw[2]
+            stats = part.data_ptr() if training else None
             if i == 0:
                 rows = (rows_total + 255) // 256
                 f.add("conv_forward_f32_to_bf16", L.mpgan_conv_forward_f32_to_bf16, C.byref(gc), src.data_ptr(), 1,
-                      store.wp(self.recs[0]).data_ptr(), cv.bias.data_ptr(), part.data_ptr(), z.data_ptr(), g.cout,
+                      store.wp(self.recs[0]).data_ptr(), cv.bias.data_ptr(), stats, z.data_ptr(), g.cout,
                       keep=(gc, src, z, part), desc=_gdesc(g), tag=("thin_cin1_full_kernel<16, true>",
                                                                      2.0 * conv_macs(g), conv_bytes(g, 2) + 2 * src.numel()))
             else:
                 rows = ops.conv_stats_rows_bf16(g)
                 f.add("conv_forward_bf16", L.mpgan_conv_forward_bf16, C.byref(gc), src.data_ptr(), g.cin,
-                      self._wf16(i).data_ptr(), cv.bias.data_ptr(), part.data_ptr(), z.data_ptr(), g.cout,
+                      self._wf16(i).data_ptr(), cv.bias.data_ptr(), stats, z.data_ptr(), g.cout,
                       keep=(gc, src, z, part), desc=_gdesc(g),
                       tag=(_bf16_kernel_name(g, False), 2.0 * conv_macs(g), conv_bytes(g, 2)))
-            f.add("norm_finalize", L.mpgan_norm_finalize, part.data_ptr(), 1, rows, g.cout, rows_total, 0,
-                  _p(bn.weight), _p(bn.bias), float(bn.eps), float(bn.momentum), _p(bn.running_mean),
-                  _p(bn.running_var), _p(bn.num_batches_tracked), nb.scale.data_ptr(), nb.shift.data_ptr(),
-                  nb.mean.data_ptr(), nb.invstd.data_ptr(), keep=(bn, nb))
+            if training:
+                f.add("norm_finalize", L.mpgan_norm_finalize, part.data_ptr(), 1, rows, g.cout, rows_total, 0,
+                      _p(bn.weight), _p(bn.bias), float(bn.eps), float(bn.momentum), _p(bn.running_mean),
+                      _p(bn.running_var), _p(bn.num_batches_tracked), nb.scale.data_ptr(), nb.shift.data_ptr(),
+                      nb.mean.data_ptr(), nb.invstd.data_ptr(), keep=(bn, nb))
             f.add("norm_act_bf16", L.mpgan_norm_act_bf16, z.data_ptr(), g.cout, nb.scale.data_ptr(), nb.shift.data_ptr(),
                   0.2, rows_total, g.cout, a.data_ptr(), g.cout, int(a.dtype == torch.float32), keep=(a,))
             src = a
@@ -2034,6 +2179,8 @@ class PatchDiscPlanBF16(PatchDiscPlan):
         self.busy = False
         self.g_x = None
         self._bwd_cache = {}
+        if not training and keep_taps:
+            self._perc_weights(dev)
         if not want_backward:
             return
         # gradients w.r.t. the activations (bf16; fp32 for a_3, written by the head's GEMM); the BatchNorm backward

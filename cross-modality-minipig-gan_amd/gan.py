@@ -4,6 +4,7 @@ in SURVEY.md Appendix B), every FLOP in HIP kernels.
 """
 from __future__ import annotations
 
+import contextlib
 import re
 import types
 from typing import Dict, List, Optional
@@ -90,6 +91,20 @@ def adversarial_loss(y_hat, y):
 def reconstruction_loss(y_hat, y):
     """code/GAN/GAN_final.py:247-248."""
     return _L1Fn.apply(y_hat, y)
+
+
+@contextlib.contextmanager
+def eval_modes(*modules):
+    """Every sub-module of `modules` in eval mode inside the block (what Lightning does around validation_step /
+    test_step), each one's own previous mode restored afterwards."""
+    was = [(m, m.training) for top in modules for m in top.modules()]
+    try:
+        for top in modules:
+            top.eval()
+        yield
+    finally:
+        for m, flag in was:
+            m.training = flag
 
 
 # --------------------------------------------------------------------------
@@ -260,6 +275,29 @@ class GAN(nn.Module):
             d_loss = scalar_axpby(real_loss, 0.5, fake_loss, 0.5)
             self.log("d_loss", d_loss)
             return d_loss
+
+    def validation_step(self, batch, batch_idx):
+        """Lightning's validation hook (the reference builds a val_dataloader, GAN_final.py:427-431, and defines no
+        step for it): the losses of training_step (:250-296) on a held-out batch from ONE generator pass, with generator
+        and discriminator in eval mode (running-statistics BatchNorm) under no_grad -- no parameter, buffer, gradient or
+        optimizer state is touched.  Logs and returns val_g_adv_loss, val_g_recon_loss, val_g_loss, val_d_loss as
+        device scalars (no host sync)."""
+        t1w_images, t2w_images = batch["t1w"], batch["t2w"]
+        dev, dt, n = t1w_images.device, t1w_images.dtype, t1w_images.shape[0]
+        with torch.no_grad(), eval_modes(self.generator, self.discriminator):
+            generated_imgs = self(t1w_images)
+            d_fake = self.discriminator(generated_imgs)
+            g_adv_loss = self.adversarial_loss(d_fake, torch.ones(n, 1, device=dev, dtype=dt))
+            g_recon_loss = self.reconstruction_loss(generated_imgs, t2w_images)
+            g_loss = scalar_axpby(g_adv_loss, 1.0, g_recon_loss, 1.0)
+            valid = torch.full((n, 1), float(self.hparams.one_sided_label_value), device=dev, dtype=dt)
+            real_loss = self.adversarial_loss(self.discriminator(t2w_images), valid)
+            fake_loss = self.adversarial_loss(d_fake, torch.zeros(n, 1, device=dev, dtype=dt))
+            d_loss = scalar_axpby(real_loss, 0.5, fake_loss, 0.5)
+        out = {"val_g_adv_loss": g_adv_loss, "val_g_recon_loss": g_recon_loss, "val_g_loss": g_loss, "val_d_loss": d_loss}
+        for name, value in out.items():
+            self.log(name, value)
+        return out
 
     def configure_optimizers(self):                 # GAN_final.py:298-308
         h = self.hparams

@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .gan import FusedAdam, adversarial_loss, reconstruction_loss, scalar_axpby
+from .gan import FusedAdam, adversarial_loss, eval_modes, reconstruction_loss, scalar_axpby
 from .networks import CasNetGenerator, PatchDiscriminator, TapDict, _EngineModule
 
 
@@ -167,6 +167,7 @@ class GAN(nn.Module):
         self.discriminator = PatchDiscriminator(data_shape, use_perceptual=use_perceptual, dimensions=dimensions,
                                                 patch=roi_size[0], device=device, storage_dtype=storage_dtype)
         self.patch_transform = PatchSampler(roi_size, num_samples, crop_seed)
+        self.crop_seed = crop_seed
         self.logged: Dict[str, torch.Tensor] = {}
         self.ddp = None
 
@@ -218,6 +219,40 @@ class GAN(nn.Module):
             d_loss = (real_loss + fake_loss) / 2
             self.log("d_loss", d_loss)
             return d_loss
+
+    def validation_step(self, batch, batch_idx):
+        """Lightning's validation hook (the reference defines none; the body follows its training_step, :300-438, with
+        one generator pass): generator and discriminator in eval mode under no_grad, nothing of either written.  The
+        crops come from a sampler of their own seeded by (crop_seed, batch_idx): validation neither consumes nor depends
+        on the training crop stream, and the same batch_idx gives the same crops.  Logs and returns val_g_adv_loss,
+        val_g_recon_loss, val_g_loss, val_d_loss (and val_g_perceptual_loss with use_perceptual) as device scalars."""
+        t1w_images, t2w_images = batch["t1w"], batch["t2w"]
+        dev, dt = t1w_images.device, t1w_images.dtype
+        sampler = PatchSampler(self.patch_transform.roi, self.patch_transform.num_samples,
+                               [int(self.crop_seed or 0) % (1 << 32), int(batch_idx) % (1 << 32)])
+        out = {}
+        with torch.no_grad(), eval_modes(self.generator, self.discriminator):
+            generated_imgs = self(t1w_images)
+            fake_crops, real_crops = sampler(generated_imgs, t2w_images)
+            n = real_crops.shape[0]
+            d_fake, taps_fake = self.discriminator(fake_crops)
+            d_real, taps_real = self.discriminator(real_crops)
+            g_adv_loss = self.adversarial_loss(d_fake, torch.ones(n, 1, device=dev, dtype=dt))
+            g_recon_loss = self.reconstruction_loss(fake_crops, real_crops)
+            g_loss = scalar_axpby(g_adv_loss, 1.0, g_recon_loss, 1.0)
+            if self.discriminator.use_perceptual:
+                g_perceptual_loss = self.perceptual_loss(taps_fake, taps_real).reshape(())
+                out["val_g_perceptual_loss"] = g_perceptual_loss
+                g_loss = scalar_axpby(g_loss, 1.0, g_perceptual_loss, 1.0)
+            valid = torch.full((n, 1), float(self.hparams.one_sided_label_value), device=dev, dtype=dt)
+            real_loss = self.adversarial_loss(d_real, valid)
+            fake_loss = self.adversarial_loss(d_fake, torch.zeros(n, 1, device=dev, dtype=dt))
+            d_loss = scalar_axpby(real_loss, 0.5, fake_loss, 0.5)
+        out.update({"val_g_adv_loss": g_adv_loss, "val_g_recon_loss": g_recon_loss, "val_g_loss": g_loss,
+                    "val_d_loss": d_loss})
+        for name, value in out.items():
+            self.log(name, value)
+        return out
 
     def configure_optimizers(self):                                         # :440-447
         h = self.hparams

@@ -334,6 +334,29 @@ class _DiscFn(torch.autograd.Function):
         return gx, None, None
 
 
+def _disc_eval(disc, x):
+    """Eval-mode pass of variant A's discriminator: the forward-only plan keyed by the mode (engine.DiscPlan /
+    DiscPlanBF16 with training=False), outside autograd."""
+    with torch.no_grad():
+        spatial = _spatial(x, disc.dimensions)
+        n = x.shape[0]
+        store = disc.store
+        key = ("eval", n, spatial, disc.storage_dtype)
+        plan_cls = DiscPlanBF16 if disc.storage_dtype == "bf16" else DiscPlan
+        plan = disc._acquire(key, lambda: plan_cls(disc, store, n, spatial, want_backward=False, want_input_grad=False,
+                                                   want_param_grads=False, training=False))
+        lease = _Lease(plan)
+        io = plan_io(plan)
+        if not io.bind("x", x):
+            plan.x_in.view(-1).copy_(x.reshape(-1))
+        try:
+            plan.fwd.run()
+            return plan.prob.view(n, 1).clone()
+        finally:
+            io.reset()
+            lease.release()
+
+
 def disc_feature_sizes(spatial: Sequence[int]):
     sizes = [tuple(spatial)]
     for k, s in ((3, 1), (3, 1), (4, 2), (4, 2)):
@@ -374,9 +397,12 @@ class Discriminator(_EngineModule):
         store.register_conv(lin, cout=1, cin=256, taps=lin.in_features // 256)
 
     def forward(self, img):
-        if not self.training:
-            raise NotImplementedError("eval-mode discriminator is not built (the reference never evaluates D)")
+        """Train mode: batch statistics + running-stat updates.  Eval mode (code/GAN/inferrence.py:109-110 puts the
+        whole GAN into it): BatchNorm uses its running statistics, nothing of the module is written, and -- the
+        generator's eval rule -- no gradients are offered: the validity comes back detached."""
         store = self.store
+        if not self.training:
+            return _disc_eval(self, img.detach().contiguous())
         self._anchor.requires_grad_(torch.is_grad_enabled() and self._params_require_grad())
         return _DiscFn.apply(img.contiguous(), self._anchor, self)
 
@@ -526,6 +552,29 @@ class _PatchDiscFn(torch.autograd.Function):
         return gx, None, None
 
 
+def _patch_disc_eval(disc, x):
+    """Eval-mode pass of the patch discriminator: the tap-keeping plan when the caller gets a TapDict, else the fused
+    one (engine.PatchDiscPlan / PatchDiscPlanBF16 with training=False), outside autograd."""
+    from .engine import PatchDiscPlan, PatchDiscPlanBF16
+    with torch.no_grad():
+        spatial = _spatial(x, disc.dimensions)
+        n = x.shape[0]
+        store = disc.store
+        keep = bool(disc.use_perceptual)
+        key = ("patch-eval", n, spatial, keep, disc.storage_dtype)
+        plan_cls = PatchDiscPlanBF16 if disc.storage_dtype == "bf16" else PatchDiscPlan
+        plan = disc._acquire(key, lambda: plan_cls(disc, store, n, spatial, want_backward=False, want_input_grad=False,
+                                                   want_param_grads=False, training=False, keep_taps=keep))
+        lease = _Lease(plan)
+        plan.x_in.view(-1).copy_(x.reshape(-1))
+        plan.fwd.run()
+        prob = plan.prob.view(n, 1).clone()
+        if not keep:
+            lease.release()
+            return prob, {}
+        return prob, TapDict(TapSet(torch.zeros(1, device=x.device), lease))
+
+
 class PatchDiscriminator(_EngineModule):
     """test_runs/GAN.py:136-198: returns (validity, perceptual_dict).
     storage_dtype="bf16": activations, activation gradients and packed weights of the three dense convs in bf16 in
@@ -561,9 +610,12 @@ class PatchDiscriminator(_EngineModule):
         store.register_conv(lin2, cout=1, cin=lin1.out_features, taps=1)
 
     def forward(self, x):
-        if not self.training:
-            raise NotImplementedError("eval-mode discriminator is not built (the reference never evaluates D)")
+        """Eval mode: running-statistics BatchNorm, nothing of the module written, no gradients offered (validity and
+        materialised taps come back detached).  With use_perceptual the raw conv outputs are kept for the TapDict
+        (tap k as in training, BatchNorm taps from the running statistics); without it only activated tensors exist."""
         store = self.store
+        if not self.training:
+            return _patch_disc_eval(self, x.detach().contiguous())
         self._anchor.requires_grad_(torch.is_grad_enabled() and self._params_require_grad())
         prob, handle = _PatchDiscFn.apply(x.contiguous(), self._anchor, self)
         taps = TapDict(TapSet(handle, self._last_lease)) if self.use_perceptual else {}

@@ -637,6 +637,45 @@ def conv_forward_f32_to_bf16(g: ConvGeom, x, w_packed, bias, y, *, stats_partial
     return y
 
 
+def _check_epi(g: ConvGeom, scale, shift, slope, what):
+    for v in (scale, shift, slope):
+        if v.dtype != torch.float32 or not v.is_cuda or v.numel() < g.cout or not v.is_contiguous():
+            raise ValueError(f"{what}: scale / shift / slope must be contiguous CUDA fp32 vectors of >= cout elements")
+
+
+def conv_forward_act_bf16(g: ConvGeom, x, w_packed, scale, shift, slope, y):
+    """Eval-mode bf16 forward: y = lrelu(acc * scale[c] + shift[c], slope[c]) from the fp32 accumulator, stored once --
+    as bf16, or as fp32 when `y` is an fp32 tensor (the layer the Linear head reads)."""
+    what = "conv_forward_act_bf16"
+    _check_shapes(g, x, y, what)
+    _, _, ldx = _clx(x, BF16, what + " x")
+    if y.dtype not in (BF16, torch.float32):
+        raise ValueError(f"{what}: y must be bf16 or fp32")
+    _, _, ldy = _clx(y, y.dtype, what + " y")
+    if w_packed.dtype != BF16 or w_packed.numel() < g.cout * g.cin * g.taps:
+        raise ValueError(f"{what}: packed weight must be bf16 and complete")
+    _check_epi(g, scale, shift, slope, what)
+    gc = g.c()
+    check(lib().mpgan_conv_forward_act_bf16(C.byref(gc), x.data_ptr(), ldx, w_packed.data_ptr(), scale.data_ptr(),
+                                            shift.data_ptr(), slope.data_ptr(), None, y.data_ptr(), ldy,
+                                            int(y.dtype == torch.float32), _stream()), what)
+    return y
+
+
+def conv_forward_act_f32_to_bf16(g: ConvGeom, x, w_packed, scale, shift, slope, y):
+    """The 1-input-channel first layer in eval mode: fp32 image in, activated bf16 out."""
+    what = "conv_forward_act_f32_to_bf16"
+    _check_shapes(g, x, y, what)
+    _, _, ldx = _cl(x, what + " x")
+    _, _, ldy = _clx(y, BF16, what + " y")
+    _check_epi(g, scale, shift, slope, what)
+    gc = g.c()
+    check(lib().mpgan_conv_forward_act_f32_to_bf16(C.byref(gc), x.data_ptr(), ldx, w_packed.data_ptr(), scale.data_ptr(),
+                                                   shift.data_ptr(), slope.data_ptr(), None, y.data_ptr(), ldy,
+                                                   _stream()), what)
+    return y
+
+
 def conv_backward_data_bf16_to_f32(g: ConvGeom, dy, w_packed_bwd, dx):
     _check_shapes(g, dx, dy, "conv_backward_data_bf16_to_f32")
     _, _, lddy = _clx(dy, BF16, "conv_backward_data_bf16_to_f32 dy")

@@ -482,6 +482,25 @@ int mpgan_conv_kernel_name_bf16(const mpgan_conv_geom* g, int32_t backward_data,
 /* dx (bf16) = conv_backward_data(dy (bf16)); w_packed_bwd: bf16, layout 1 of mpgan_pack_weights_bf16. */
 int mpgan_conv_backward_data_bf16(const mpgan_conv_geom* g, const void* dy, int32_t lddy, const void* w_packed_bwd,
                                   void* dx, int32_t lddx, void* stream);
+/* Eval-mode forward in bf16 storage (Discriminator / PatchDiscriminator after .eval()): with running-statistics
+ * BatchNorm the layer's affine is known before its conv runs, so the epilogue of the bf16 forward applies it and the
+ * LeakyReLU to the fp32 MFMA accumulator of bf16 x and bf16 w,
+ *     y = lrelu(acc * scale[c] + shift[c], slope[c]),
+ * and the ACTIVATED tensor is stored once: rounded to bf16 (to nearest even), or unrounded as fp32 when y_f32 != 0
+ * (the layer the fp32 Linear head reads; ldy % 4 == 0 then).  No raw z reaches memory and no mpgan_norm_act_bf16 pass
+ * follows.  The conv's bias is folded into `shift` by the caller (mpgan_epi_vectors_multi does it; a LeakyReLU's constant
+ * slope is passed to it as a one-element device tensor in the PReLU column).  scale / shift / slope: [cout] floats,
+ * 16-byte aligned.  Runs on whichever form serves mpgan_conv_forward_bf16 for this geometry (mpgan_conv_variant_bf16,
+ * mpgan_conv_kernel_name_bf16).  Fused statistics describe the raw conv output, which this launch never forms:
+ * stats_partials must be NULL (MPGAN_ERR_INVALID otherwise). */
+int mpgan_conv_forward_act_bf16(const mpgan_conv_geom* g, const void* x, int32_t ldx, const void* w_packed,
+                                const float* scale, const float* shift, const float* slope, float* stats_partials,
+                                void* y, int32_t ldy, int32_t y_f32, void* stream);
+/* The same for the 1-input-channel first layer: fp32 image in, activated bf16 out (mpgan_conv_forward_f32_to_bf16's
+ * kernels with the epilogue activation). */
+int mpgan_conv_forward_act_f32_to_bf16(const mpgan_conv_geom* g, const float* x, int32_t ldx, const float* w_packed,
+                                       const float* scale, const float* shift, const float* slope,
+                                       float* stats_partials, void* y, int32_t ldy, void* stream);
 /* kernel label of the bf16 weight gradient of this layer: 0 = 128 x 256 tiles, 1 = 256 x 256 (profiling only) */
 int32_t mpgan_conv_wgrad_variant_bf16(const mpgan_conv_geom* g);
 /* dW (fp32, torch layout) = beta*dW + sum over pixels of dy (bf16) x gathered x (bf16): pad-free ConvNd. */
