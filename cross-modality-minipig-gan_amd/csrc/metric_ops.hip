@@ -520,3 +520,290 @@ extern "C" int mpgan_resample_to_identity_grid(const float* vol, const int32_t* 
   hipLaunchKernelGGL(resample_linear_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, vol, g, out);
   return check_launch("resample_to_identity_grid");
 }
+
+// ---------------------------------------------------------------------------------------------------
+// Joint histogram and mutual information (the reference's third stored quality figure).
+//   hist[item][ia][ib] = number of admitted voxels whose a-value falls into bin ia and b-value into bin ib, with
+//   idx = min((int)floorf((v - lo) * s), bins - 1), s = (float)bins / (hi - lo), all in fp32 as written (s is
+//   formed on the host; the device subtracts and multiplies with explicit round-to-nearest operations, so no
+//   contraction can change a bin).  A voxel outside either range, NaN, or refused by the mask is dropped.
+// A block privatises a band of a-rows in LDS as uint32 counters (LDS integer atomics), walks its chunk of the
+// voxels, and flushes its non-zero counters once with 64-bit integer atomics: consecutive lanes flush consecutive
+// counters, so the global atomics are contiguous 512-byte wave-instructions instead of one scattered atomic per
+// voxel.  Integer sums only: the histogram does not depend on execution order.
+// ---------------------------------------------------------------------------------------------------
+namespace mpgan {
+
+constexpr int JH_THREADS = 1024;
+constexpr int JH_LDS_COUNTERS = 16384;          // 64 KB of uint32: two blocks share a CU's 160 KB
+constexpr long JH_CHUNK_MIN = 16384;            // voxels a block walks at least (its zero + flush pass is 16 K counters)
+constexpr long JH_CHUNK_MAX = 1L << 30;         // ... and at most: a uint32 counter cannot overflow
+constexpr int JH_TARGET_BLOCKS = 512;           // two 16-wave blocks per CU
+constexpr int JH_PEEL_ROUNDS = 4;
+
+enum { JH_MASK_NONE = 0, JH_MASK_BOTH_NONZERO = 1, JH_MASK_EITHER_NONZERO = 2, JH_MASK_EXPLICIT = 3 };
+
+// The ONE place the form of a joint-histogram launch is decided: how many a-rows a block keeps in LDS (all of them
+// up to 128 bins; above that a band of floor(16384 / bins) rows, and every band re-reads the voxels and skips those
+// outside it), and how many blocks share one (item, band).
+struct JhChoice {
+  int band_rows, bands;
+  long chunks, per_chunk;                       // per_chunk is a multiple of 4: every chunk starts float4-aligned
+};
+
+static bool jh_finite(float v) { return v - v == 0.f; }   // false for NaN and the infinities
+
+static JhChoice choose_joint_hist(int bins, long n, int batch) {
+  JhChoice c;
+  c.band_rows = bins * bins <= JH_LDS_COUNTERS ? bins : JH_LDS_COUNTERS / bins;
+  c.bands = (bins + c.band_rows - 1) / c.band_rows;
+  long cap = JH_TARGET_BLOCKS / ((long)batch * c.bands);
+  if (cap < 1) cap = 1;
+  long chunks = (n + JH_CHUNK_MIN - 1) / JH_CHUNK_MIN;
+  if (chunks > cap) chunks = cap;
+  const long floor_chunks = (n + JH_CHUNK_MAX - 1) / JH_CHUNK_MAX;
+  if (chunks < floor_chunks) chunks = floor_chunks;
+  if (chunks < 1) chunks = 1;
+  c.chunks = chunks;
+  c.per_chunk = (((n + chunks - 1) / chunks) + 3) & ~3L;
+  return c;
+}
+
+struct JhParams {
+  const float* a;
+  const float* b;
+  const uint8_t* mask;
+  long n;                                       // voxels per item
+  float lo_a, hi_a, s_a, lo_b, hi_b, s_b;
+  int bins, mask_mode, band_rows, bands;
+  long chunks, per_chunk;
+  unsigned long long* hist;
+};
+
+__device__ __forceinline__ int jh_bin(float v, float lo, float s, int bins) {
+  const int i = (int)floorf(__fmul_rn(__fsub_rn(v, lo), s));
+  return i < bins - 1 ? i : bins - 1;
+}
+
+// One voxel per lane, called by every lane of the wave (pend = this lane has a counter to bump).  A wave whose lanes
+// crowd one counter (the background bin of an MRI pair, a constant image) would serialise on an LDS atomic: up to
+// JH_PEEL_ROUNDS times, the leading pending lane adds the number of lanes that share its counter in ONE atomic and
+// all of them retire; lanes still pending after that issue their own.
+__device__ __forceinline__ void jh_submit(unsigned* lh, bool pend, unsigned key) {
+#pragma unroll
+  for (int r = 0; r < JH_PEEL_ROUNDS; ++r) {
+    const unsigned long long act = __ballot(pend);
+    if (act == 0ull) return;
+    const int leader = __ffsll((long long)act) - 1;
+    const unsigned lk = (unsigned)__shfl((int)key, leader, 64);
+    const bool same = pend && key == lk;
+    const unsigned long long m = __ballot(same);
+    if ((int)(threadIdx.x & 63) == leader) atomicAdd(&lh[lk], (unsigned)__popcll(m));
+    pend = pend && !same;
+  }
+  if (pend) atomicAdd(&lh[key], 1u);
+}
+
+__device__ __forceinline__ void jh_voxel(unsigned* lh, const JhParams& p, int r0, int r1, bool valid, float va, float vb,
+                                         unsigned mk) {
+  bool ok = valid && va >= p.lo_a && va <= p.hi_a && vb >= p.lo_b && vb <= p.hi_b;   // NaN fails every comparison
+  if (p.mask_mode == JH_MASK_BOTH_NONZERO) ok = ok && va != 0.f && vb != 0.f;
+  else if (p.mask_mode == JH_MASK_EITHER_NONZERO) ok = ok && (va != 0.f || vb != 0.f);
+  else if (p.mask_mode == JH_MASK_EXPLICIT) ok = ok && mk != 0u;
+  unsigned key = 0;
+  if (ok) {
+    const int ia = jh_bin(va, p.lo_a, p.s_a, p.bins), ib = jh_bin(vb, p.lo_b, p.s_b, p.bins);
+    ok = ia >= r0 && ia < r1;
+    key = (unsigned)((ia - r0) * p.bins + ib);
+  }
+  jh_submit(lh, ok, ok ? key : 0u);
+}
+
+__global__ __launch_bounds__(JH_THREADS) void joint_hist_kernel(JhParams p) {
+  extern __shared__ unsigned jh_lds[];          // [band rows][bins]
+  const int tid = threadIdx.x;
+  long blk = blockIdx.x;
+  const long chunk = blk % p.chunks;
+  blk /= p.chunks;
+  const int band = (int)(blk % p.bands);
+  const long item = blk / p.bands;
+  const int r0 = band * p.band_rows;
+  const int r1 = r0 + p.band_rows < p.bins ? r0 + p.band_rows : p.bins;
+  const int counters = (r1 - r0) * p.bins;
+  for (int i = tid; i < counters; i += JH_THREADS) jh_lds[i] = 0u;
+  __syncthreads();
+  const long c0 = chunk * p.per_chunk;
+  long c1 = c0 + p.per_chunk;
+  if (c1 > p.n) c1 = p.n;
+  if (c0 < c1) {
+    const float* a = p.a + item * p.n;
+    const float* b = p.b + item * p.n;
+    const uint8_t* mk = p.mask_mode == JH_MASK_EXPLICIT ? p.mask + item * p.n : nullptr;
+    const long len = c1 - c0;
+    // 16-byte loads when both item bases are 16-byte aligned (c0 is a multiple of 4); the scalar loop takes every
+    // other alignment and the tail.  Trip counts are block-uniform: jh_submit needs every lane of a wave.
+    const bool vec = ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15u) == 0;
+    const long nvec = vec ? len >> 2 : 0;
+    for (long j0 = 0; j0 < nvec; j0 += JH_THREADS) {
+      const long j = j0 + tid;
+      const bool valid = j < nvec;
+      float4 va = make_float4(0.f, 0.f, 0.f, 0.f), vb = va;
+      unsigned m0 = 1, m1 = 1, m2 = 1, m3 = 1;
+      if (valid) {
+        const long e = c0 + 4 * j;
+        va = *reinterpret_cast<const float4*>(a + e);
+        vb = *reinterpret_cast<const float4*>(b + e);
+        if (mk) { m0 = mk[e]; m1 = mk[e + 1]; m2 = mk[e + 2]; m3 = mk[e + 3]; }
+      }
+      jh_voxel(jh_lds, p, r0, r1, valid, va.x, vb.x, m0);
+      jh_voxel(jh_lds, p, r0, r1, valid, va.y, vb.y, m1);
+      jh_voxel(jh_lds, p, r0, r1, valid, va.z, vb.z, m2);
+      jh_voxel(jh_lds, p, r0, r1, valid, va.w, vb.w, m3);
+    }
+    for (long j0 = 4 * nvec; j0 < len; j0 += JH_THREADS) {
+      const long j = j0 + tid;
+      const bool valid = j < len;
+      float va = 0.f, vb = 0.f;
+      unsigned m0 = 1;
+      if (valid) {
+        va = a[c0 + j];
+        vb = b[c0 + j];
+        if (mk) m0 = mk[c0 + j];
+      }
+      jh_voxel(jh_lds, p, r0, r1, valid, va, vb, m0);
+    }
+  }
+  __syncthreads();
+  unsigned long long* out = p.hist + (item * p.bins + r0) * (long)p.bins;
+  for (int i = tid; i < counters; i += JH_THREADS) {
+    const unsigned c = jh_lds[i];
+    if (c) atomicAdd(&out[i], (unsigned long long)c);
+  }
+}
+
+// Mutual information of one item's histogram, one block per item.  Row and column sums are exact integers (LDS
+// 64-bit integer atomics: order-free).  The three sums of c*log(c) are doubles: every thread adds its terms in a
+// fixed order and the block folds the per-thread sums by a fixed tree, so the six outputs are bitwise reproducible.
+//   H = log N - (sum c log c) / N   (nats);   out6 = (mi, h_a, h_b, h_ab, nmi, count)
+constexpr int MI_THREADS = 1024;
+
+__device__ __forceinline__ double mi_block_sum(double v, double* red) {
+  const int tid = threadIdx.x;
+  __syncthreads();
+  red[tid] = v;
+  __syncthreads();
+  for (int s = MI_THREADS / 2; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+__global__ __launch_bounds__(MI_THREADS) void mutual_info_kernel(const unsigned long long* __restrict__ hist, int bins,
+                                                                  double* __restrict__ out6) {
+  __shared__ unsigned long long rows[256], cols[256];
+  __shared__ double red[MI_THREADS];
+  __shared__ unsigned long long tot_s, nnz_s;
+  const int tid = threadIdx.x;
+  const unsigned long long* h = hist + (long)blockIdx.x * bins * bins;
+  if (tid < 256) { rows[tid] = 0ull; cols[tid] = 0ull; }
+  if (tid == 0) { tot_s = 0ull; nnz_s = 0ull; }
+  __syncthreads();
+  // a wave walks whole rows: lanes over the columns (coalesced), the row sum folded in the wave
+  const int lane = tid & 63, wave = tid >> 6;
+  double s_ab = 0.0;
+  unsigned nnz = 0;
+  for (int r = wave; r < bins; r += MI_THREADS / 64) {
+    unsigned long long rs = 0ull;
+    for (int c = lane; c < bins; c += 64) {
+      const unsigned long long v = h[(long)r * bins + c];
+      if (v) {
+        rs += v;
+        ++nnz;
+        s_ab += (double)v * log((double)v);
+        atomicAdd(&cols[c], v);
+      }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) rs += __shfl_xor(rs, off, 64);
+    if (lane == 0) rows[r] = rs;
+  }
+  if (nnz) atomicAdd(&nnz_s, (unsigned long long)nnz);
+  __syncthreads();
+  double s_a = 0.0, s_b = 0.0;
+  if (tid < bins) {
+    const unsigned long long ra = rows[tid], cb = cols[tid];
+    if (ra) { s_a = (double)ra * log((double)ra); atomicAdd(&tot_s, ra); }
+    if (cb) s_b = (double)cb * log((double)cb);
+  }
+  s_ab = mi_block_sum(s_ab, red);
+  s_a = mi_block_sum(s_a, red);
+  s_b = mi_block_sum(s_b, red);
+  if (tid == 0) {
+    double* o = out6 + 6 * (long)blockIdx.x;
+    const unsigned long long total = tot_s;
+    if (total == 0ull) {
+      const double qnan = __longlong_as_double(0x7ff8000000000000LL);
+      o[0] = o[1] = o[2] = o[3] = o[4] = qnan;
+      o[5] = 0.0;
+    } else if (nnz_s == 1ull) {                  // every voxel in one bin: H_ab == 0
+      o[0] = 0.0; o[1] = 0.0; o[2] = 0.0; o[3] = 0.0; o[4] = 1.0;
+      o[5] = (double)total;
+    } else {
+      const double n = (double)total, ln = log(n);
+      const double ha = ln - s_a / n, hb = ln - s_b / n, hab = ln - s_ab / n;
+      o[0] = ha + hb - hab;
+      o[1] = ha; o[2] = hb; o[3] = hab;
+      o[4] = (ha + hb) / hab;
+      o[5] = n;
+    }
+  }
+}
+
+}  // namespace mpgan
+
+extern "C" int mpgan_joint_histogram(const float* a, const float* b, const uint8_t* mask, int32_t mask_mode,
+                                     int64_t numel_per_item, int32_t batch, float lo_a, float hi_a, float lo_b,
+                                     float hi_b, int32_t bins, int64_t* hist, void* stream) {
+  MPGAN_CHECK_ARG(bins >= 2 && bins <= 256, "joint_histogram: bins %d outside [2, 256]", bins);
+  MPGAN_CHECK_ARG(batch >= 1, "joint_histogram: batch %d < 1", batch);
+  MPGAN_CHECK_ARG(numel_per_item >= 0, "joint_histogram: negative numel_per_item");
+  MPGAN_CHECK_ARG(mask_mode >= JH_MASK_NONE && mask_mode <= JH_MASK_EXPLICIT, "joint_histogram: unknown mask_mode %d",
+                  mask_mode);
+  MPGAN_CHECK_ARG(hist != nullptr, "joint_histogram: null hist");
+  MPGAN_CHECK_ARG((a && b) || numel_per_item == 0, "joint_histogram: null input");
+  MPGAN_CHECK_ARG(mask || mask_mode != JH_MASK_EXPLICIT || numel_per_item == 0,
+                  "joint_histogram: mask_mode 3 needs a mask array");
+  const float span_a = hi_a - lo_a, span_b = hi_b - lo_b;
+  MPGAN_CHECK_ARG(jh_finite(lo_a) && jh_finite(hi_a) && jh_finite(lo_b) && jh_finite(hi_b) && jh_finite(span_a) &&
+                      jh_finite(span_b),
+                  "joint_histogram: non-finite value range");
+  MPGAN_CHECK_ARG(hi_a > lo_a && hi_b > lo_b, "joint_histogram: value range needs hi > lo");
+  const float s_a = (float)bins / span_a, s_b = (float)bins / span_b;
+  MPGAN_CHECK_ARG(jh_finite(s_a) && jh_finite(s_b), "joint_histogram: value range too narrow for fp32 binning");
+  hipStream_t st = (hipStream_t)stream;
+  const JhChoice c = choose_joint_hist(bins, numel_per_item, batch);
+  const int64_t blocks = c.chunks * c.bands * (int64_t)batch;
+  MPGAN_CHECK_ARG(blocks < (1LL << 31), "joint_histogram: too many blocks");
+  hipError_t e = hipMemsetAsync(hist, 0, (size_t)batch * bins * bins * sizeof(int64_t), st);
+  if (e != hipSuccess) { set_error("joint_histogram: hipMemsetAsync: %s", hipGetErrorString(e)); return MPGAN_ERR_HIP; }
+  if (numel_per_item == 0) return MPGAN_OK;
+  JhParams p;
+  p.a = a; p.b = b; p.mask = mask; p.n = numel_per_item;
+  p.lo_a = lo_a; p.hi_a = hi_a; p.s_a = s_a; p.lo_b = lo_b; p.hi_b = hi_b; p.s_b = s_b;
+  p.bins = bins; p.mask_mode = mask_mode; p.band_rows = c.band_rows; p.bands = c.bands;
+  p.chunks = c.chunks; p.per_chunk = c.per_chunk;
+  p.hist = reinterpret_cast<unsigned long long*>(hist);
+  const size_t smem = (size_t)c.band_rows * bins * sizeof(unsigned);
+  hipLaunchKernelGGL(joint_hist_kernel, dim3((unsigned)blocks), dim3(JH_THREADS), smem, st, p);
+  return check_launch("joint_histogram");
+}
+
+extern "C" int mpgan_mutual_information(const int64_t* hist, int32_t batch, int32_t bins, double* out6, void* stream) {
+  MPGAN_CHECK_ARG(bins >= 2 && bins <= 256, "mutual_information: bins %d outside [2, 256]", bins);
+  MPGAN_CHECK_ARG(batch >= 1, "mutual_information: batch %d < 1", batch);
+  MPGAN_CHECK_ARG(hist && out6, "mutual_information: null pointer");
+  hipLaunchKernelGGL(mutual_info_kernel, dim3((unsigned)batch), dim3(MI_THREADS), 0, (hipStream_t)stream,
+                     reinterpret_cast<const unsigned long long*>(hist), (int)bins, out6);
+  return check_launch("mutual_information");
+}

@@ -2,11 +2,13 @@
 row N2): 0..255 rescale + round as code/GAN/inferrence.py:188-204 applies it, then MAE / MSE /
 PSNR and SSIM (data_range 256, code/GAN/psnr_ssim_metric.py:88-106; code/GAN/metrics.py:213-223).
 SSIM restates skimage.metrics.structural_similarity's published algorithm (skimage itself is not in
-this image: parity is pinned on a scipy.ndimage restatement in oracle/metrics_ref.py only)."""
+this image: parity is pinned on a scipy.ndimage restatement in oracle/metrics_ref.py only).
+joint_histogram / mutual_information add the third stored figure of SURVEY.md section 6 (the estimator behind the
+reference's stored MUTINF numbers is unknown: the definition here is pinned against numpy, not against them)."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict
+from typing import Dict, Optional, Tuple, Union
 
 import torch
 
@@ -40,13 +42,18 @@ def image_errors(a: torch.Tensor, b: torch.Tensor, data_range: float = 256.0) ->
     return {"mae": out[0], "mse": out[1], "psnr": out[2]}
 
 
-def score_volume(generated: torch.Tensor, ground_truth: torch.Tensor) -> Dict[str, torch.Tensor]:
+def score_volume(generated: torch.Tensor, ground_truth: torch.Tensor,
+                 mutual_information: bool = False) -> Dict[str, torch.Tensor]:
     """The inference script's scoring: both volumes rescaled to 0..255 and rounded, then compared
-    (MAE / MSE / PSNR; plus SSIM when the tensors are (H, W) or (D, H, W))."""
+    (MAE / MSE / PSNR; plus SSIM when the tensors are (H, W) or (D, H, W)).  mutual_information=True
+    adds "mi" and "nmi" of the two rescaled volumes (256 bins over [0, 256], nats)."""
     g, t = rescale_0_255(generated), rescale_0_255(ground_truth)
     out = image_errors(g, t, 256.0)
     if g.dim() in (2, 3) and min(g.shape[-2:]) >= 7 and (g.dim() == 2 or g.shape[0] >= 7):
         out["ssim"] = ssim(g, t, 256.0)
+    if mutual_information:
+        m = _mutual_information(g, t, bins=256, value_range=(0.0, 256.0))
+        out["mi"], out["nmi"] = m["mi"], m["nmi"]
     return out
 
 
@@ -66,3 +73,83 @@ def ssim(a: torch.Tensor, b: torch.Tensor, data_range: float = 256.0) -> torch.T
     check(lib().mpgan_ssim(a.data_ptr(), b.data_ptr(), dhw, float(data_range), ws.data_ptr(), ws.numel() * 8,
                            out.data_ptr(), _stream()), "ssim")
     return out[0]
+
+
+_MASK_MODES = {None: 0, "both_nonzero": 1, "either_nonzero": 2}
+_MI_KEYS = ("mi", "h_a", "h_b", "h_ab", "nmi", "count")
+ValueRange = Union[Tuple[float, float], Tuple[Tuple[float, float], Tuple[float, float]]]
+
+
+def _ranges(value_range: ValueRange) -> Tuple[float, float, float, float]:
+    if len(value_range) != 2:
+        raise ValueError("value_range: (lo, hi) or ((lo_a, hi_a), (lo_b, hi_b))")
+    if isinstance(value_range[0], (tuple, list)):
+        (lo_a, hi_a), (lo_b, hi_b) = value_range
+    else:
+        lo_a, hi_a = value_range
+        lo_b, hi_b = value_range
+    return float(lo_a), float(hi_a), float(lo_b), float(hi_b)
+
+
+def joint_histogram(a: torch.Tensor, b: torch.Tensor, bins: int = 256, value_range: ValueRange = (0.0, 256.0),
+                    mask: Union[None, str, torch.Tensor] = None, batched: bool = False) -> torch.Tensor:
+    """Joint histogram of two same-shape fp32 device tensors: int64 (bins, bins), rows indexed by a's bin and
+    columns by b's, or (B, bins, bins) with batched=True (dim 0 is the batch).  The bin of a value v over
+    [lo, hi] is min(floor((v - lo) * (bins / (hi - lo))), bins - 1) in fp32, so v == hi falls into the last
+    bin; voxels with a value outside its range or NaN are dropped.  value_range is (lo, hi) for both images or
+    ((lo_a, hi_a), (lo_b, hi_b)).  mask: None, "both_nonzero", "either_nonzero", or a same-shape bool / uint8
+    tensor (non-zero keeps the voxel).  Counts are exact; the result stays on the device."""
+    if a.shape != b.shape:
+        raise ValueError("joint_histogram: shape mismatch")
+    if a.dtype != torch.float32 or b.dtype != torch.float32 or not (a.is_cuda and b.is_cuda):
+        raise ValueError("joint_histogram: expects two fp32 device tensors")
+    if batched and a.dim() < 1:
+        raise ValueError("joint_histogram: batched=True needs a batch dimension")
+    lo_a, hi_a, lo_b, hi_b = _ranges(value_range)
+    a, b = a.contiguous(), b.contiguous()          # a contiguous view keeps its (possibly unaligned) offset
+    mask_ptr = None
+    if isinstance(mask, torch.Tensor):
+        if mask.shape != a.shape or mask.dtype not in (torch.bool, torch.uint8) or mask.device != a.device:
+            raise ValueError("joint_histogram: mask must be a same-shape bool / uint8 tensor on the inputs' device")
+        mask = mask.contiguous()
+        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+        mode, mask_ptr = 3, mask.data_ptr()
+    elif mask in _MASK_MODES:
+        mode = _MASK_MODES[mask]
+    else:
+        raise ValueError(f"joint_histogram: unknown mask {mask!r}")
+    batch = a.shape[0] if batched else 1
+    if batch < 1:
+        raise ValueError("joint_histogram: empty batch")
+    per_item = a.numel() // batch
+    hist = torch.empty((batch, int(bins), int(bins)), dtype=torch.int64, device=a.device)
+    check(lib().mpgan_joint_histogram(a.data_ptr() if per_item else None, b.data_ptr() if per_item else None, mask_ptr,
+                                      mode, per_item, batch, lo_a, hi_a, lo_b, hi_b, int(bins), hist.data_ptr(),
+                                      _stream()), "joint_histogram")
+    return hist if batched else hist[0]
+
+
+def mutual_information_from_histogram(hist: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """The figures of mutual_information() from an int64 (bins, bins) or (B, bins, bins) joint histogram."""
+    if hist.dtype != torch.int64 or hist.dim() not in (2, 3) or hist.shape[-1] != hist.shape[-2] or not hist.is_cuda:
+        raise ValueError("mutual_information_from_histogram: expects an int64 (bins, bins) or (B, bins, bins) device tensor")
+    batched = hist.dim() == 3
+    hist = hist.contiguous()
+    batch = hist.shape[0] if batched else 1
+    out = torch.empty((batch, 6), dtype=torch.float64, device=hist.device)
+    check(lib().mpgan_mutual_information(hist.data_ptr(), batch, hist.shape[-1], out.data_ptr(), _stream()),
+          "mutual_information")
+    return {k: (out[:, i] if batched else out[0, i]) for i, k in enumerate(_MI_KEYS)}
+
+
+def mutual_information(a: torch.Tensor, b: torch.Tensor, bins: int = 256, value_range: ValueRange = (0.0, 256.0),
+                       mask: Union[None, str, torch.Tensor] = None, batched: bool = False) -> Dict[str, torch.Tensor]:
+    """Mutual information of two same-shape fp32 device tensors from their joint_histogram (same arguments):
+    {"mi", "h_a", "h_b", "h_ab", "nmi", "count"} as float64 device scalars, or (B,) tensors with batched=True.
+    Entropies H = log N - (sum c log c) / N over the exact integer counts; mi = h_a + h_b - h_ab;
+    nmi = (h_a + h_b) / h_ab (Studholme); count = N, the number of admitted voxels.  Values are in nats: divide
+    by ln 2 for bits.  No admitted voxel gives NaN (count 0); all voxels in one bin give mi = 0 and nmi = 1."""
+    return mutual_information_from_histogram(joint_histogram(a, b, bins, value_range, mask, batched))
+
+
+_mutual_information = mutual_information        # score_volume's keyword argument shadows the name there

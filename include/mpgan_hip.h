@@ -395,6 +395,28 @@ int64_t mpgan_ssim_workspace(const int32_t* dhw);
 int mpgan_ssim(const float* a, const float* b, const int32_t* dhw, float data_range,
                void* workspace, int64_t workspace_bytes, float* out1, void* stream);
 
+/* ---- joint histogram and mutual information (the MUTINF figure stored in code/eval) ---- */
+#define MPGAN_JH_MASK_NONE 0           /* every voxel inside both ranges */
+#define MPGAN_JH_MASK_BOTH_NONZERO 1   /* ... whose two values are both non-zero */
+#define MPGAN_JH_MASK_EITHER_NONZERO 2 /* ... of which at least one value is non-zero */
+#define MPGAN_JH_MASK_EXPLICIT 3       /* ... whose byte in `mask` is non-zero */
+/* hist[item][ia][ib] (int64, zeroed by the call) counts the voxels of item `item` of two contiguous fp32 arrays of
+ * batch x numel_per_item elements whose a-value falls into bin ia and b-value into bin ib.  The bin of a value v over
+ * [lo, hi] is min((int)floorf((v - lo) * s), bins - 1) with s = (float)bins / (hi - lo), evaluated in fp32 exactly as
+ * written, so v == hi falls into the last bin; a voxel with a value below lo, above hi or NaN, or one the mask mode
+ * refuses, is dropped.  Counts are exact and do not depend on execution order.  2 <= bins <= 256; `mask` (uint8,
+ * same length) is read in mode 3 only and may be null otherwise; a and b may be null when numel_per_item == 0
+ * (a zero histogram).  No workspace. */
+int mpgan_joint_histogram(const float* a, const float* b, const uint8_t* mask, int32_t mask_mode,
+                          int64_t numel_per_item, int32_t batch,
+                          float lo_a, float hi_a, float lo_b, float hi_b, int32_t bins,
+                          int64_t* hist, void* stream);
+/* out6[item] = (mi, h_a, h_b, h_ab, nmi, count) in double from hist[item][bins][bins]: entropies in nats from the
+ * integer counts, H = log N - (sum c log c) / N over the exact int64 marginals and the joint counts;
+ * mi = h_a + h_b - h_ab; nmi = (h_a + h_b) / h_ab (Studholme); count = N.  N == 0: NaN for the five values and
+ * count 0; every voxel in one bin (h_ab == 0): mi = 0, nmi = 1.  Fixed summation order: bitwise reproducible. */
+int mpgan_mutual_information(const int64_t* hist, int32_t batch, int32_t bins, double* out6, void* stream);
+
 /* ---- optimiser ------------------------------------------------------------ */
 /* torch.optim.Adam.step over one flat buffer (GAN_final.py:306-307):
  * m = b1*m+(1-b1)*g; v = b2*v+(1-b2)*g^2; p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t)+eps).
