@@ -1,0 +1,117 @@
+"""Differentiable losses beyond the reference trainer's own two (gan.py holds BCE and L1).
+
+GlobalMutualInformationLoss restates MONAI 0.4.0's loss of that name, which the reference's scoring script imports
+(code/GAN/metrics.py:19): mutual information from Parzen-window (Gaussian) soft bins, the differentiable form of
+metrics.mutual_information.  MONAI is not installed here: the definition in include/mpgan_hip.h is what is pinned,
+against a float64 torch restatement (tests/mi_loss_ref.py).  Forward and backward are fused HIP kernels
+(csrc/mi_loss.hip): no (B, N, bins) weight tensor exists, and the result is bitwise reproducible."""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+
+from . import ops
+from .metrics import ValueRange, _ranges
+
+_REDUCTIONS = ("mean", "sum", "none")
+MAX_BINS = 32
+
+
+def _config(num_bins, sigma_ratio, reduction, value_range, who):
+    if int(num_bins) != num_bins or not 2 <= int(num_bins) <= MAX_BINS:
+        raise ValueError(f"{who}: num_bins must be an integer in [2, {MAX_BINS}], got {num_bins!r}")
+    if not sigma_ratio > 0:
+        raise ValueError(f"{who}: sigma_ratio must be positive, got {sigma_ratio!r}")
+    if reduction not in _REDUCTIONS:
+        raise ValueError(f"{who}: unknown reduction {reduction!r} (expected one of {_REDUCTIONS})")
+    ranges = _ranges(value_range)
+    if not (ranges[1] > ranges[0] and ranges[3] > ranges[2]):
+        raise ValueError(f"{who}: value_range needs hi > lo, got {value_range!r}")
+    return int(num_bins), float(sigma_ratio), ranges
+
+
+def _inputs(pred, target, who):
+    if pred.shape != target.shape:
+        raise ValueError(f"{who}: shape mismatch, pred {tuple(pred.shape)} and target {tuple(target.shape)}")
+    if pred.dim() < 2 or pred.shape[0] < 1 or pred.numel() == 0:
+        raise ValueError(f"{who}: expects non-empty (B, C, *spatial) tensors, got {tuple(pred.shape)}")
+    if pred.dtype != torch.float32 or target.dtype != torch.float32 or not (pred.is_cuda and target.is_cuda):
+        raise ValueError(f"{who}: expects two fp32 device tensors")
+
+
+class _ParzenMIFn(torch.autograd.Function):
+    """The reduced loss -mi; saves the two inputs and the K x K gradient coefficients of every item, so that a second
+    backward (retain_graph) reads unscaled state."""
+
+    @staticmethod
+    def forward(ctx, pred, target, bins, sigma_ratio, nr, dr, ranges, reduction):
+        a, b = pred.contiguous(), target.contiguous()     # a contiguous view keeps its (possibly unaligned) offset
+        batch = a.shape[0]
+        dev = a.device
+        need_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        ws = torch.empty(ops.parzen_mi_workspace(batch, a.numel() // batch, bins) // 8, dtype=torch.float64, device=dev)
+        mi = torch.empty(batch, dtype=torch.float64, device=dev)
+        coef = torch.empty((batch, 2, 32, 32), device=dev) if need_grad else None
+        loss = torch.empty((batch,) if reduction == "none" else (), device=dev)
+        ops.parzen_mi_forward(a, b, batch, ranges, bins, sigma_ratio, nr, dr, ws, mi, None, coef, reduction, loss)
+        ctx.cfg = (batch, ranges, bins, sigma_ratio, -1.0 / batch if reduction == "mean" else -1.0)
+        ctx.save_for_backward(a, b, coef)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        a, b, coef = ctx.saved_tensors
+        batch, ranges, bins, sigma_ratio, scale = ctx.cfg
+        gout = gout.contiguous()
+        grads = [None, None]
+        for wrt in (0, 1):
+            if ctx.needs_input_grad[wrt]:
+                grads[wrt] = ops.parzen_mi_backward(a, b, batch, ranges, bins, sigma_ratio, coef, gout, scale, wrt,
+                                                    torch.empty_like(a))
+        return grads[0], grads[1], None, None, None, None, None, None
+
+
+def global_mutual_information_loss(pred: torch.Tensor, target: torch.Tensor, num_bins: int = 23,
+                                   sigma_ratio: float = 0.5, reduction: str = "mean", smooth_nr: float = 1e-7,
+                                   smooth_dr: float = 1e-7, value_range: ValueRange = (0.0, 1.0)) -> torch.Tensor:
+    """-MI of two (B, C, *spatial) fp32 device tensors from Gaussian soft bins; channels fold into samples.
+    Values are mapped by clamp((x - lo) / (hi - lo), 0, 1) with value_range = (lo, hi) for both tensors or
+    ((lo_pred, hi_pred), (lo_target, hi_target)); the default (0, 1) is MONAI's behaviour, (-1, 1) suits a tanh
+    output.  reduction: "mean" (a scalar), "sum", or "none" ((B,)).  A NaN sample makes its item's loss NaN."""
+    who = "global_mutual_information_loss"
+    bins, sigma_ratio, ranges = _config(num_bins, sigma_ratio, reduction, value_range, who)
+    _inputs(pred, target, who)
+    return _ParzenMIFn.apply(pred, target, bins, sigma_ratio, float(smooth_nr), float(smooth_dr), ranges, reduction)
+
+
+class GlobalMutualInformationLoss(nn.Module):
+    """monai.losses.GlobalMutualInformationLoss(num_bins, sigma_ratio, reduction, smooth_nr, smooth_dr) with a
+    value_range in addition (see global_mutual_information_loss)."""
+
+    def __init__(self, num_bins: int = 23, sigma_ratio: float = 0.5, reduction: str = "mean", smooth_nr: float = 1e-7,
+                 smooth_dr: float = 1e-7, value_range: ValueRange = (0.0, 1.0)):
+        super().__init__()
+        _config(num_bins, sigma_ratio, reduction, value_range, "GlobalMutualInformationLoss")
+        self.num_bins, self.sigma_ratio, self.reduction = int(num_bins), float(sigma_ratio), reduction
+        self.smooth_nr, self.smooth_dr, self.value_range = float(smooth_nr), float(smooth_dr), value_range
+
+    def forward(self, pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        return global_mutual_information_loss(pred, target, self.num_bins, self.sigma_ratio, self.reduction,
+                                              self.smooth_nr, self.smooth_dr, self.value_range)
+
+
+def parzen_joint_histogram(a: torch.Tensor, b: torch.Tensor, num_bins: int = 23, sigma_ratio: float = 0.5,
+                           value_range: ValueRange = (0.0, 1.0)) -> torch.Tensor:
+    """The float64 (B, num_bins, num_bins) Parzen-window joint distribution of two (B, C, *spatial) fp32 device
+    tensors: rows indexed by a's bin, columns by b's; every item's entries sum to 1."""
+    who = "parzen_joint_histogram"
+    bins, sigma_ratio, ranges = _config(num_bins, sigma_ratio, "none", value_range, who)
+    _inputs(a, b, who)
+    a, b = a.contiguous(), b.contiguous()
+    batch = a.shape[0]
+    ws = torch.empty(ops.parzen_mi_workspace(batch, a.numel() // batch, bins) // 8, dtype=torch.float64,
+                     device=a.device)
+    mi = torch.empty(batch, dtype=torch.float64, device=a.device)
+    joint = torch.empty((batch, bins, bins), dtype=torch.float64, device=a.device)
+    ops.parzen_mi_forward(a, b, batch, ranges, bins, sigma_ratio, 1e-7, 1e-7, ws, mi, joint)
+    return joint

@@ -849,3 +849,37 @@ def norm_act_add_fold(z, pz: Prologue, fold: NormFoldC, r, pr: Optional[Prologue
     check(lib().mpgan_norm_act_add_fold(z.data_ptr(), ldz, _pro(pz), C.byref(fold), _ptr(r), ldr, _pro(pr), n, P,
                                         z.shape[-1], int(tanh_out), out.data_ptr(), ldo, _stream()), "norm_act_add_fold")
     return out
+
+
+# ---- Parzen-window mutual information (csrc/mi_loss.hip; losses.py holds the autograd node) ----
+_PMI_REDUCTIONS = {"mean": 0, "sum": 1, "none": 2}
+
+
+def parzen_mi_workspace(batch: int, numel_per_item: int, bins: int) -> int:
+    need = int(lib().mpgan_parzen_mi_workspace(int(batch), int(numel_per_item), int(bins)))
+    if need < 0:
+        raise ValueError(f"parzen_mi_workspace: bad geometry (batch {batch}, {numel_per_item} per item, {bins} bins)")
+    return need
+
+
+def parzen_mi_forward(a, b, batch, ranges, bins, sigma_ratio, smooth_nr, smooth_dr, workspace, mi, joint=None,
+                      coef=None, reduction="none", loss=None):
+    """mi[batch] (float64) of two contiguous fp32 tensors; optionally the joint, the backward's coefficients and
+    the reduced loss (see include/mpgan_hip.h)."""
+    lo_a, hi_a, lo_b, hi_b = ranges
+    check(lib().mpgan_parzen_mi_forward(a.data_ptr(), b.data_ptr(), a.numel() // batch, batch, lo_a, hi_a, lo_b, hi_b,
+                                        int(bins), float(sigma_ratio), float(smooth_nr), float(smooth_dr),
+                                        workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+                                        _ptr(joint), mi.data_ptr(), _ptr(coef), _PMI_REDUCTIONS[reduction],
+                                        _ptr(loss), _stream()), "parzen_mi_forward")
+    return mi
+
+
+def parzen_mi_backward(a, b, batch, ranges, bins, sigma_ratio, coef, upstream, scale, wrt, grad):
+    """grad = upstream[item or 0] * scale * d mi[item] / d (a if wrt == 0 else b)."""
+    lo_a, hi_a, lo_b, hi_b = ranges
+    check(lib().mpgan_parzen_mi_backward(a.data_ptr(), b.data_ptr(), a.numel() // batch, batch, lo_a, hi_a, lo_b, hi_b,
+                                         int(bins), float(sigma_ratio), coef.data_ptr(), upstream.data_ptr(),
+                                         0 if upstream.numel() == 1 else 1, float(scale), int(wrt), grad.data_ptr(),
+                                         _stream()), "parzen_mi_backward")
+    return grad

@@ -417,6 +417,44 @@ int mpgan_joint_histogram(const float* a, const float* b, const uint8_t* mask, i
  * count 0; every voxel in one bin (h_ab == 0): mi = 0, nmi = 1.  Fixed summation order: bitwise reproducible. */
 int mpgan_mutual_information(const int64_t* hist, int32_t batch, int32_t bins, double* out6, void* stream);
 
+/* ---- Parzen-window mutual information: a differentiable loss (MONAI 0.4.0 GlobalMutualInformationLoss, which
+ * code/GAN/metrics.py:19 imports; MONAI is not in this image, the definition below is what is pinned) ----
+ * a, b: contiguous fp32 arrays of batch x numel_per_item elements (channels fold into samples), N = numel_per_item.
+ *   x'      = clamp((x - lo) / (hi - lo), 0, 1)            per image, NaN stays NaN
+ *   c_i     = i / (K - 1), i = 0..K-1;  sigma = sigma_ratio / (K - 1);  p = 1 / (2 sigma^2)
+ *   w_i(x)  = e_i / sum_k e_k,  e_i = exp(-p (x' - c_i)^2)
+ *   pab_ij  = (1/N) sum_n wa_i(n) wb_j(n);  pa_i = sum_j pab_ij;  pb_j = sum_i pab_ij
+ *   mi      = sum_ij pab_ij log((pab_ij + nr) / (pa_i pb_j + dr) + dr)
+ * Gradient: R = (pab + nr) / (pa pb + dr);  A = log(R + dr) + pab / ((R + dr)(pa pb + dr));
+ *   Dp = -pab (pab + nr) / ((R + dr)(pa pb + dr)^2);  G_ij = A_ij + sum_j Dp_ij pb_j;  G'_ij = A_ij + sum_i Dp_ij pa_i;
+ *   h_i(n) = sum_j G_ij wb_j(n);  hbar(n) = sum_i wa_i(n) h_i(n);
+ *   d mi / d a_n = (1/N) (1/(hi_a - lo_a)) m(n) sum_i wa_i(n) (h_i(n) - hbar(n)) (-2 p (a'_n - c_i)),
+ *   m(n) = 1 when the mapped value lies in the CLOSED interval [0, 1] (torch.clamp's rule), else 0; for b the same
+ *   with the roles swapped and G'.
+ * 2 <= bins <= 32 (MPGAN_ERR_INVALID above, before any launch).  The weights and the joint accumulate in fp32 (each
+ * wave an fmaf chain over at most 512 voxels), a block adds its 16 waves' tiles in wave order in fp64 into its own
+ * workspace slot, the slots are summed in slot order and everything after the joint is fp64: results are bitwise
+ * reproducible from call to call.  The calls allocate nothing, are asynchronous on `stream` and can be captured
+ * into a graph. */
+/* Bytes of workspace the forward needs (8-byte aligned): a function of (batch, numel_per_item) only; -1 on a bad
+ * argument. */
+int64_t mpgan_parzen_mi_workspace(int32_t batch, int64_t numel_per_item, int32_t bins);
+/* mi[batch] (double).  Optional outputs, each may be null: joint[batch][bins][bins] (double, pab);
+ * coef[batch][2][32][32] (float, 16-byte aligned: G and G' transposed, each less its pab-weighted mean -- a
+ * constant that cancels in h_i - hbar --, what the backward reads);
+ * loss (float): reduction 0: loss[0] = -mean_b mi; 1: loss[0] = -sum_b mi; 2: loss[b] = -mi[b]. */
+int mpgan_parzen_mi_forward(const float* a, const float* b, int64_t numel_per_item, int32_t batch,
+                            float lo_a, float hi_a, float lo_b, float hi_b, int32_t bins, double sigma_ratio,
+                            double smooth_nr, double smooth_dr, void* workspace, int64_t workspace_bytes,
+                            double* joint, double* mi, float* coef, int32_t reduction, float* loss, void* stream);
+/* grad[batch][numel_per_item] = upstream[item * upstream_stride] * scale * d mi[item] / d (wrt == 0 ? a : b), with
+ * the geometry and coef of the forward call.  upstream is a device array (stride 1) or one device scalar for every
+ * item (stride 0); scale is the host factor of the reduction (-1, or -1/batch for the mean). */
+int mpgan_parzen_mi_backward(const float* a, const float* b, int64_t numel_per_item, int32_t batch,
+                             float lo_a, float hi_a, float lo_b, float hi_b, int32_t bins, double sigma_ratio,
+                             const float* coef, const float* upstream, int32_t upstream_stride, float scale,
+                             int32_t wrt, float* grad, void* stream);
+
 /* ---- optimiser ------------------------------------------------------------ */
 /* torch.optim.Adam.step over one flat buffer (GAN_final.py:306-307):
  * m = b1*m+(1-b1)*g; v = b2*v+(1-b2)*g^2; p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t)+eps).
