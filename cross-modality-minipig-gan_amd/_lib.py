@@ -162,6 +162,7 @@ SIGNATURES = {
     "mpgan_sw_count": (_I, [_SW, _P, _P, _P]),
     "mpgan_sw_blend": (_I, [_SW, _P, _I, _I, _I, _P, _P, _P]),
     "mpgan_sw_finalize": (_I, [_SW, _P, _I, _P, _P, _P]),
+    "mpgan_sw_kernel_name": (_I, [_I, _SW, _P, _P, _P, C.c_char_p, _I]),
 }
 
 

@@ -255,6 +255,43 @@ int check_channels_calls(int32_t ch, int32_t first, int32_t n, const SwGeom& g, 
   return MPGAN_OK;
 }
 
+// ---- the form of each launch: decided in ONE function per launch, which the launch and the label both read ------
+// Gather: VEC when the roi's x extent is a multiple of 4 (the window batch must then be 16-byte aligned: refused
+// otherwise), ALIGNED_IN from the input base.
+struct SwGatherChoice { bool vec, aligned_in; };
+int choose_sw_gather(const SwGeom& g, const void* in, const void* win, SwGatherChoice& c) {
+  MPGAN_CHECK_ARG(in && win, "sw_gather: null pointer");
+  c.vec = g.rx % 4 == 0;
+  c.aligned_in = al16(in);
+  MPGAN_UNSUPPORTED(c.vec && !al16(win), "sw_gather: the window batch must be 16-byte aligned");
+  return MPGAN_OK;
+}
+
+// Count: quads when no window boundary splits one and count (and imp, when given) are 16-byte aligned.
+struct SwWeightedChoice { bool vec, const_imp; };
+int choose_sw_count(const mpgan_sw_geom* h, const void* imp, const void* count, SwWeightedChoice& c) {
+  MPGAN_CHECK_ARG(count, "sw_count: null pointer");
+  c.const_imp = imp == nullptr;
+  c.vec = sw_quads(h) && al16(count) && (imp == nullptr || al16(imp));
+  return MPGAN_OK;
+}
+
+// Blend: as the count, with pred and acc in place of count.
+int choose_sw_blend(const mpgan_sw_geom* h, const void* pred, const void* imp, const void* acc, SwWeightedChoice& c) {
+  MPGAN_CHECK_ARG(pred && acc, "sw_blend: null pointer");
+  c.const_imp = imp == nullptr;
+  c.vec = sw_quads(h) && al16(pred) && al16(acc) && (imp == nullptr || al16(imp));
+  return MPGAN_OK;
+}
+
+// Finalize: quads when W, the padded W and the x padding are multiples of 4 and all three buffers are aligned.
+struct SwFinalizeChoice { bool vec; };
+int choose_sw_finalize(const SwGeom& g, const void* acc, const void* count, const void* out, SwFinalizeChoice& c) {
+  MPGAN_CHECK_ARG(acc && count && out, "sw_finalize: null pointer");
+  c.vec = g.W % 4 == 0 && g.Wp % 4 == 0 && g.px % 4 == 0 && al16(acc) && al16(count) && al16(out);
+  return MPGAN_OK;
+}
+
 }  // namespace
 
 extern "C" int mpgan_sw_gather(const mpgan_sw_geom* h, const float* in, int32_t cin, int32_t first, int32_t n,
@@ -264,27 +301,23 @@ extern "C" int mpgan_sw_gather(const mpgan_sw_geom* h, const float* in, int32_t 
   if (rc) return rc;
   rc = check_channels_calls(cin, first, n, g, h->batch, "sw_gather");
   if (rc) return rc;
-  MPGAN_CHECK_ARG(in && win, "sw_gather: null pointer");
-  const bool vec = g.rx % 4 == 0;
-  MPGAN_UNSUPPORTED(vec && !al16(win), "sw_gather: the window batch must be 16-byte aligned");
+  SwGatherChoice c;
+  rc = choose_sw_gather(g, in, win, c);
+  if (rc) return rc;
   const unsigned rx4 = (unsigned)(g.rx + 3) / 4;
   const long long quads = (long long)g.rz * g.ry * rx4;
   MPGAN_UNSUPPORTED(quads >= (1ll << 31), "sw_gather: roi too large");
   const dim3 grid(blocks_for(quads), cin, n);
   const FastDiv fq = make_fastdiv(rx4), fy = make_fastdiv(g.ry);
   hipStream_t s = (hipStream_t)stream;
-  if (vec && al16(in))
-    hipLaunchKernelGGL((sw_gather_kernel<true, true>), grid, dim3(256), 0, s, in, g, cin, first, cval, fq, fy,
-                       (unsigned)quads, win);
-  else if (vec)
-    hipLaunchKernelGGL((sw_gather_kernel<true, false>), grid, dim3(256), 0, s, in, g, cin, first, cval, fq, fy,
-                       (unsigned)quads, win);
-  else if (al16(in))
-    hipLaunchKernelGGL((sw_gather_kernel<false, true>), grid, dim3(256), 0, s, in, g, cin, first, cval, fq, fy,
-                       (unsigned)quads, win);
-  else
-    hipLaunchKernelGGL((sw_gather_kernel<false, false>), grid, dim3(256), 0, s, in, g, cin, first, cval, fq, fy,
-                       (unsigned)quads, win);
+#define MPGAN_SW_GATHER_(V, A)                                                                                       \
+  hipLaunchKernelGGL((sw_gather_kernel<V, A>), grid, dim3(256), 0, s, in, g, cin, first, cval, fq, fy, (unsigned)quads, \
+                     win)
+  if (c.vec && c.aligned_in) MPGAN_SW_GATHER_(true, true);
+  else if (c.vec) MPGAN_SW_GATHER_(true, false);
+  else if (c.aligned_in) MPGAN_SW_GATHER_(false, true);
+  else MPGAN_SW_GATHER_(false, false);
+#undef MPGAN_SW_GATHER_
   return check_launch("sw_gather");
 }
 
@@ -292,21 +325,21 @@ extern "C" int mpgan_sw_count(const mpgan_sw_geom* h, const float* imp, float* c
   SwGeom g;
   int rc = sw_check(h, g, "sw_count");
   if (rc) return rc;
-  MPGAN_CHECK_ARG(count, "sw_count: null pointer");
-  const bool vec = sw_quads(h) && al16(count) && (imp == nullptr || al16(imp));
-  const unsigned xu = vec ? (unsigned)g.Wp / 4 : (unsigned)g.Wp;
+  SwWeightedChoice c;
+  rc = choose_sw_count(h, imp, count, c);
+  if (rc) return rc;
+  const unsigned xu = c.vec ? (unsigned)g.Wp / 4 : (unsigned)g.Wp;
   const long long units = (long long)g.Dp * g.Hp * xu;
   const dim3 grid(blocks_for(units));
   const FastDiv fq = make_fastdiv(xu), fy = make_fastdiv(g.Hp);
   hipStream_t s = (hipStream_t)stream;
-  if (vec && imp)
-    hipLaunchKernelGGL((sw_count_kernel<true, false>), grid, dim3(256), 0, s, g, imp, fq, fy, (unsigned)units, count);
-  else if (vec)
-    hipLaunchKernelGGL((sw_count_kernel<true, true>), grid, dim3(256), 0, s, g, imp, fq, fy, (unsigned)units, count);
-  else if (imp)
-    hipLaunchKernelGGL((sw_count_kernel<false, false>), grid, dim3(256), 0, s, g, imp, fq, fy, (unsigned)units, count);
-  else
-    hipLaunchKernelGGL((sw_count_kernel<false, true>), grid, dim3(256), 0, s, g, imp, fq, fy, (unsigned)units, count);
+#define MPGAN_SW_COUNT_(V, CI) \
+  hipLaunchKernelGGL((sw_count_kernel<V, CI>), grid, dim3(256), 0, s, g, imp, fq, fy, (unsigned)units, count)
+  if (c.vec && !c.const_imp) MPGAN_SW_COUNT_(true, false);
+  else if (c.vec) MPGAN_SW_COUNT_(true, true);
+  else if (!c.const_imp) MPGAN_SW_COUNT_(false, false);
+  else MPGAN_SW_COUNT_(false, true);
+#undef MPGAN_SW_COUNT_
   return check_launch("sw_count");
 }
 
@@ -317,7 +350,9 @@ extern "C" int mpgan_sw_blend(const mpgan_sw_geom* h, const float* pred, int32_t
   if (rc) return rc;
   rc = check_channels_calls(cout, first, n, g, h->batch, "sw_blend");
   if (rc) return rc;
-  MPGAN_CHECK_ARG(pred && acc, "sw_blend: null pointer");
+  SwWeightedChoice c;
+  rc = choose_sw_blend(h, pred, imp, acc, c);
+  if (rc) return rc;
   // bounding box of the call's windows (padded coordinates) and the images they belong to
   int lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {0, 0, 0};
   const int* sz = h->starts_host;
@@ -332,20 +367,19 @@ extern "C" int mpgan_sw_blend(const mpgan_sw_geom* h, const float* pred, int32_t
     }
   }
   const int b0 = first / g.nwin, b1 = (first + n - 1) / g.nwin;
-  const bool vec = sw_quads(h) && al16(pred) && al16(acc) && (imp == nullptr || al16(imp));
-  const unsigned xu = vec ? (unsigned)(hi[2] - lo[2]) / 4 : (unsigned)(hi[2] - lo[2]);
+  const unsigned xu = c.vec ? (unsigned)(hi[2] - lo[2]) / 4 : (unsigned)(hi[2] - lo[2]);
   const long long units = (long long)(hi[0] - lo[0]) * (hi[1] - lo[1]) * xu;
   const dim3 grid(blocks_for(units), cout, b1 - b0 + 1);
   const FastDiv fq = make_fastdiv(xu), fy = make_fastdiv(hi[1] - lo[1]);
   hipStream_t s = (hipStream_t)stream;
-#define MPGAN_SW_BLEND(V, CI)                                                                                         \
+#define MPGAN_SW_BLEND_(V, CI)                                                                                        \
   hipLaunchKernelGGL((sw_blend_kernel<V, CI>), grid, dim3(256), 0, s, g, pred, cout, first, n, imp, b0, lo[0], lo[1], \
                      lo[2], fq, fy, (unsigned)units, acc)
-  if (vec && imp) MPGAN_SW_BLEND(true, false);
-  else if (vec) MPGAN_SW_BLEND(true, true);
-  else if (imp) MPGAN_SW_BLEND(false, false);
-  else MPGAN_SW_BLEND(false, true);
-#undef MPGAN_SW_BLEND
+  if (c.vec && !c.const_imp) MPGAN_SW_BLEND_(true, false);
+  else if (c.vec) MPGAN_SW_BLEND_(true, true);
+  else if (!c.const_imp) MPGAN_SW_BLEND_(false, false);
+  else MPGAN_SW_BLEND_(false, true);
+#undef MPGAN_SW_BLEND_
   return check_launch("sw_blend");
 }
 
@@ -354,19 +388,52 @@ extern "C" int mpgan_sw_finalize(const mpgan_sw_geom* h, const float* acc, int32
   SwGeom g;
   int rc = sw_check(h, g, "sw_finalize");
   if (rc) return rc;
-  MPGAN_CHECK_ARG(acc && count && out, "sw_finalize: null pointer");
+  SwFinalizeChoice c;
+  rc = choose_sw_finalize(g, acc, count, out, c);
+  if (rc) return rc;
   MPGAN_CHECK_ARG(cout > 0 && cout <= 65535 && h->batch <= 65535, "sw_finalize: channels / batch outside [1, 65535]");
-  const bool vec = g.W % 4 == 0 && g.Wp % 4 == 0 && g.px % 4 == 0 && al16(acc) && al16(count) && al16(out);
-  const unsigned xu = vec ? (unsigned)g.W / 4 : (unsigned)g.W;
+  const unsigned xu = c.vec ? (unsigned)g.W / 4 : (unsigned)g.W;
   const long long units = (long long)g.D * g.H * xu;
   const dim3 grid(blocks_for(units), cout, h->batch);
   const FastDiv fq = make_fastdiv(xu), fy = make_fastdiv(g.H);
   hipStream_t s = (hipStream_t)stream;
-  if (vec)
+  if (c.vec)
     hipLaunchKernelGGL((sw_finalize_kernel<true>), grid, dim3(256), 0, s, g, acc, cout, count, fq, fy,
                        (unsigned)units, out);
   else
     hipLaunchKernelGGL((sw_finalize_kernel<false>), grid, dim3(256), 0, s, g, acc, cout, count, fq, fy,
                        (unsigned)units, out);
   return check_launch("sw_finalize");
+}
+
+// The label of the instance a launch runs, formatted from the launch's own choice.
+extern "C" int mpgan_sw_kernel_name(int32_t launch, const mpgan_sw_geom* h, const void* p0, const void* p1,
+                                    const void* p2, char* buf, int32_t len) {
+  MPGAN_CHECK_ARG(buf && len > 0, "sw_kernel_name: no buffer");
+  MPGAN_CHECK_ARG(launch >= MPGAN_SW_GATHER && launch <= MPGAN_SW_FINALIZE, "sw_kernel_name: unknown launch %d", launch);
+  static const char* const what[4] = {"sw_gather", "sw_count", "sw_blend", "sw_finalize"};
+  static const char* const b[2] = {"false", "true"};
+  SwGeom g;
+  int rc = sw_check(h, g, what[launch]);
+  if (rc) return rc;
+  int n = 0;
+  if (launch == MPGAN_SW_GATHER) {
+    SwGatherChoice c;
+    if ((rc = choose_sw_gather(g, p0, p1, c))) return rc;
+    n = snprintf(buf, len, "sw_gather_kernel<%s, %s>", b[c.vec], b[c.aligned_in]);
+  } else if (launch == MPGAN_SW_COUNT) {
+    SwWeightedChoice c;
+    if ((rc = choose_sw_count(h, p0, p1, c))) return rc;
+    n = snprintf(buf, len, "sw_count_kernel<%s, %s>", b[c.vec], b[c.const_imp]);
+  } else if (launch == MPGAN_SW_BLEND) {
+    SwWeightedChoice c;
+    if ((rc = choose_sw_blend(h, p0, p1, p2, c))) return rc;
+    n = snprintf(buf, len, "sw_blend_kernel<%s, %s>", b[c.vec], b[c.const_imp]);
+  } else {
+    SwFinalizeChoice c;
+    if ((rc = choose_sw_finalize(g, p0, p1, p2, c))) return rc;
+    n = snprintf(buf, len, "sw_finalize_kernel<%s>", b[c.vec]);
+  }
+  MPGAN_CHECK_ARG(n < len, "sw_kernel_name: the name needs %d bytes", n + 1);
+  return MPGAN_OK;
 }

@@ -173,6 +173,21 @@ def _geometry(plan: WindowPlan, batch: int, device):
     return g, (starts_host, starts_dev)
 
 
+SW_LAUNCHES = {"gather": 0, "count": 1, "blend": 2, "finalize": 3}      # MPGAN_SW_* of include/mpgan_hip.h
+
+
+def sw_kernel_name(launch: str, geom, *pointers) -> str:
+    """The profiler's name of the kernel instance the `launch` ("gather", "count", "blend" or "finalize") runs for
+    the geometry `geom` (a SwGeomC) and that launch's data pointers in its own argument order (integers or None;
+    only their alignment is read), from the choice the launch itself makes (mpgan_sw_kernel_name).  Launches
+    nothing; raises RuntimeError where the launch would refuse."""
+    p = tuple(pointers) + (None,) * (3 - len(pointers))
+    buf = C.create_string_buffer(64)
+    check(lib().mpgan_sw_kernel_name(SW_LAUNCHES[launch], C.byref(geom), p[0], p[1], p[2], buf, len(buf)),
+          "sw_kernel_name")
+    return buf.value.decode()
+
+
 def _same_device(dev, want: torch.device, what: str) -> None:
     if dev is None:
         return

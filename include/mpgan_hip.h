@@ -667,6 +667,20 @@ int mpgan_sw_blend(const mpgan_sw_geom* g, const float* pred, int32_t cout, int3
 /* out (B, cout, dhw) = acc / count over the unpadded region (IEEE division). */
 int mpgan_sw_finalize(const mpgan_sw_geom* g, const float* acc, int32_t cout, const float* count, float* out,
                       void* stream);
+/* The profiler's name (without `void mpgan::` and the argument list, e.g. "sw_gather_kernel<true, false>") of the
+ * kernel instance one of the four launches above runs, written to buf[len] from the same choice the launch makes.
+ * Each launch has several forms (16-byte quads or scalars, constant or given importance map) and picks one from
+ * the geometry (roi, padded extent, x starts, image width and x padding modulo 4) and from the 16-byte alignment of
+ * its buffers; a buffer that is not 16-byte aligned sends its launch to the scalar form, except the gather's window
+ * batch, which must be aligned when roi[2] % 4 == 0 (MPGAN_ERR_UNSUPPORTED otherwise, as from the launch).
+ * p0..p2 are that launch's data pointers in its own argument order:
+ *   MPGAN_SW_GATHER: in, win, (ignored)    MPGAN_SW_COUNT: imp (null => constant 1), count, (ignored)
+ *   MPGAN_SW_BLEND: pred, imp, acc         MPGAN_SW_FINALIZE: acc, count, out
+ * Nothing is launched and no data pointer is dereferenced (only starts_host is read); works without a GPU.  The
+ * geometry and the required pointers are validated as by the launch, with the launch's status codes. */
+enum { MPGAN_SW_GATHER = 0, MPGAN_SW_COUNT = 1, MPGAN_SW_BLEND = 2, MPGAN_SW_FINALIZE = 3 };
+int mpgan_sw_kernel_name(int32_t launch, const mpgan_sw_geom* g, const void* p0, const void* p1, const void* p2,
+                         char* buf, int32_t len);
 
 /* ---- development aids (no counterpart in the reference) ----------------------------------------------------
  * In-kernel phase stamps: a library built with `make STAMPS=1` records, for each of the next `launches`

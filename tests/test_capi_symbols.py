@@ -19,7 +19,7 @@ def test_header_declares_the_path():
     names = _declared()
     for must in ("mpgan_conv_forward", "mpgan_conv_backward_data", "mpgan_conv_backward_weight", "mpgan_norm_finalize",
                  "mpgan_norm_bwd_apply", "mpgan_adam_step", "mpgan_l1_loss", "mpgan_bce_forward",
-                 "mpgan_patch_gather", "mpgan_pack_weights"):
+                 "mpgan_patch_gather", "mpgan_pack_weights", "mpgan_sw_gather", "mpgan_sw_kernel_name"):
         assert must in names
 
 

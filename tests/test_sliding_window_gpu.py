@@ -6,36 +6,9 @@ import torch
 
 import sliding_window_ref as ref
 from mpgan_amd import inference as inf
+from sw_helpers import Recorder, noisy as _noisy
 
 pytestmark = pytest.mark.gpu
-
-
-class Recorder:
-    """Wraps a predictor; keeps a CPU copy of every window batch it was given and every output it returned."""
-
-    def __init__(self, fn):
-        self.fn, self.inputs, self.outputs = fn, [], []
-
-    def __call__(self, x):
-        self.inputs.append(x.detach().cpu().clone())
-        y = self.fn(x)
-        self.outputs.append(y.detach().cpu().clone())
-        return y
-
-    def replay(self):
-        it = iter(self.outputs)
-        return lambda x: next(it)
-
-
-def _noisy(cout, seed):
-    """A predictor whose outputs depend on the window content and differ from call to call."""
-    g = torch.Generator(device="cuda").manual_seed(seed)
-
-    def fn(x):
-        base = torch.tanh(x.sum(1, keepdim=True) * 1.7 + 0.3)
-        return (base.repeat(1, cout, *([1] * (x.dim() - 2)))
-                + 0.1 * torch.randn((x.shape[0], cout) + tuple(x.shape[2:]), device=x.device, generator=g))
-    return fn
 
 
 def _check(x, roi, sw, overlap, mode, cout=1, cval=0.0, seed=0):
