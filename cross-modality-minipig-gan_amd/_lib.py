@@ -124,6 +124,9 @@ SIGNATURES = {
     "mpgan_parzen_mi_forward": (_I, [_P, _P, _L, _I, _F, _F, _F, _F, _I, C.c_double, C.c_double, C.c_double, _P, _L, _P,
                                      _P, _P, _I, _P, _P]),
     "mpgan_parzen_mi_backward": (_I, [_P, _P, _L, _I, _F, _F, _F, _F, _I, C.c_double, _P, _P, _I, _F, _I, _P, _P]),
+    "mpgan_ssim_loss_workspace": (_L, [_I3, _I, _I, C.POINTER(C.c_int64)]),
+    "mpgan_ssim_loss_forward": (_I, [_P, _P, _I3, _I, _I, C.c_double, C.c_double, _I, _P, _L, _P, _L, _I, _P, _P]),
+    "mpgan_ssim_loss_backward": (_I, [_P, _P, _I3, _I, _I, C.c_double, _I, _P, _L, _P, _I, C.c_double, _I, _P, _P]),
     "mpgan_adam_step": (_I, [_P, _P, _P, _P, _L, C.c_double, C.c_double, C.c_double, C.c_double, _I, _F, _P]),
     "mpgan_patch_gather": (_I, [_P, _I, _I3, _P, _I, _I3, _P, _P]),
     "mpgan_patch_scatter_add": (_I, [_P, _I, _I3, _P, _I, _I3, _P, _P]),

@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .losses import GlobalMutualInformationLoss
+from .losses import GlobalMutualInformationLoss, SSIMLoss
 from .networks import CasNetGenerator, Discriminator, _EngineModule
 
 
@@ -218,10 +218,13 @@ class GAN(nn.Module):
                  g_lr: float = 0.0005, b1: float = 0.5, b2: float = 0.999, batch_size: int = 64, example_data=None,
                  one_sided_label_value=0.9, *, dimensions: Optional[int] = None, norm: str = "batch",
                  n_unet_blocks: int = 6, unet_channels=(16, 32, 64, 128), unet_strides=(2, 2, 2), device="cuda",
-                 storage_dtype: str = "f32", mi_weight: float = 0.0, mi_bins: int = 23, **kwargs):
+                 storage_dtype: str = "f32", mi_weight: float = 0.0, mi_bins: int = 23,
+                 ssim_weight: float = 0.0, **kwargs):
         super().__init__()
         if mi_weight < 0:
             raise ValueError(f"mi_weight must be >= 0, got {mi_weight!r}")
+        if ssim_weight < 0:
+            raise ValueError(f"ssim_weight must be >= 0, got {ssim_weight!r}")
         if dimensions is None:
             dimensions = 3 if depth is not None else 2
         self.hparams = types.SimpleNamespace(latent_dim=latent_dim, g_lr=g_lr, d_lr=d_lr, b1=b1, b2=b2,
@@ -238,6 +241,9 @@ class GAN(nn.Module):
         # windows over the tanh output's range; with the default 0 no launch and no logged name is added
         self.mi_weight = float(mi_weight)
         self.mi_loss = (GlobalMutualInformationLoss(mi_bins, value_range=(-1.0, 1.0)) if self.mi_weight > 0 else None)
+        # likewise ssim_weight * (1 - SSIM(G(t1w), t2w)), the loss form of the figure metrics.ssim scores a volume with
+        self.ssim_weight = float(ssim_weight)
+        self.ssim_loss = SSIMLoss(value_range=(-1.0, 1.0)) if self.ssim_weight > 0 else None
         self.logged: Dict[str, torch.Tensor] = {}
         self.ddp = None  # set by parallel.DataParallelGAN
 
@@ -269,6 +275,10 @@ class GAN(nn.Module):
                 g_mi_loss = self.mi_loss(generated_imgs, t2w_images)
                 self.log("g_mi_loss", g_mi_loss)
                 g_loss = scalar_axpby(g_loss, 1.0, g_mi_loss, self.mi_weight)
+            if self.ssim_loss is not None:
+                g_ssim_loss = self.ssim_loss(generated_imgs, t2w_images)
+                self.log("g_ssim_loss", g_ssim_loss)
+                g_loss = scalar_axpby(g_loss, 1.0, g_ssim_loss, self.ssim_weight)
             self.log("g_loss", g_loss)
             return g_loss
         if optimizer_idx == 1:                      # GAN_final.py:276-296
@@ -292,7 +302,8 @@ class GAN(nn.Module):
         step for it): the losses of training_step (:250-296) on a held-out batch from ONE generator pass, with generator
         and discriminator in eval mode (running-statistics BatchNorm) under no_grad -- no parameter, buffer, gradient or
         optimizer state is touched.  Logs and returns val_g_adv_loss, val_g_recon_loss, val_g_loss, val_d_loss as
-        device scalars (no host sync); with mi_weight > 0 also val_g_mi_loss, which val_g_loss then includes."""
+        device scalars (no host sync); with mi_weight > 0 also val_g_mi_loss and with ssim_weight > 0 also
+        val_g_ssim_loss, which val_g_loss then includes."""
         t1w_images, t2w_images = batch["t1w"], batch["t2w"]
         dev, dt, n = t1w_images.device, t1w_images.dtype, t1w_images.shape[0]
         with torch.no_grad(), eval_modes(self.generator, self.discriminator):
@@ -304,6 +315,9 @@ class GAN(nn.Module):
             if self.mi_loss is not None:
                 g_mi_loss = self.mi_loss(generated_imgs, t2w_images)
                 g_loss = scalar_axpby(g_loss, 1.0, g_mi_loss, self.mi_weight)
+            if self.ssim_loss is not None:
+                g_ssim_loss = self.ssim_loss(generated_imgs, t2w_images)
+                g_loss = scalar_axpby(g_loss, 1.0, g_ssim_loss, self.ssim_weight)
             valid = torch.full((n, 1), float(self.hparams.one_sided_label_value), device=dev, dtype=dt)
             real_loss = self.adversarial_loss(self.discriminator(t2w_images), valid)
             fake_loss = self.adversarial_loss(d_fake, torch.zeros(n, 1, device=dev, dtype=dt))
@@ -311,6 +325,8 @@ class GAN(nn.Module):
         out = {"val_g_adv_loss": g_adv_loss, "val_g_recon_loss": g_recon_loss, "val_g_loss": g_loss, "val_d_loss": d_loss}
         if self.mi_loss is not None:
             out["val_g_mi_loss"] = g_mi_loss
+        if self.ssim_loss is not None:
+            out["val_g_ssim_loss"] = g_ssim_loss
         for name, value in out.items():
             self.log(name, value)
         return out

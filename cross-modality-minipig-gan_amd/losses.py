@@ -4,7 +4,12 @@ GlobalMutualInformationLoss restates MONAI 0.4.0's loss of that name, which the 
 (code/GAN/metrics.py:19): mutual information from Parzen-window (Gaussian) soft bins, the differentiable form of
 metrics.mutual_information.  MONAI is not installed here: the definition in include/mpgan_hip.h is what is pinned,
 against a float64 torch restatement (tests/mi_loss_ref.py).  Forward and backward are fused HIP kernels
-(csrc/mi_loss.hip): no (B, N, bins) weight tensor exists, and the result is bitwise reproducible."""
+(csrc/mi_loss.hip): no (B, N, bins) weight tensor exists, and the result is bitwise reproducible.
+
+SSIMLoss is 1 - the structural similarity that metrics.ssim scores a volume with (code/GAN/psnr_ssim_metric.py:88-106),
+as a loss: the forward kernel of csrc/ssim_loss.hip also leaves the per-window coefficient maps of the closed-form
+gradient, the backward kernel box-sums them.  Its definition is pinned in include/mpgan_hip.h against the float64
+torch restatement tests/ssim_loss_ref.py."""
 from __future__ import annotations
 
 import torch
@@ -115,3 +120,89 @@ def parzen_joint_histogram(a: torch.Tensor, b: torch.Tensor, num_bins: int = 23,
     joint = torch.empty((batch, bins, bins), dtype=torch.float64, device=a.device)
     ops.parzen_mi_forward(a, b, batch, ranges, bins, sigma_ratio, 1e-7, 1e-7, ws, mi, joint)
     return joint
+
+
+SSIM_WINDOW = 7
+
+
+def _ssim_config(value_range, reduction, who):
+    if reduction not in _REDUCTIONS:
+        raise ValueError(f"{who}: unknown reduction {reduction!r} (expected one of {_REDUCTIONS})")
+    try:
+        lo, hi = (float(v) for v in value_range)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: value_range must be one (lo, hi) pair, got {value_range!r}") from None
+    if not hi > lo or hi - lo == float("inf"):
+        raise ValueError(f"{who}: value_range needs finite hi > lo, got {value_range!r}")
+    return lo, hi
+
+
+def _ssim_inputs(pred, target, who):
+    if pred.shape != target.shape:
+        raise ValueError(f"{who}: shape mismatch, pred {tuple(pred.shape)} and target {tuple(target.shape)}")
+    if pred.dim() not in (4, 5) or pred.shape[0] < 1 or pred.shape[1] < 1:
+        raise ValueError(f"{who}: expects (B, C, H, W) or (B, C, D, H, W) tensors, got {tuple(pred.shape)}")
+    spatial = tuple(pred.shape[2:])
+    windowed = spatial[1:] if len(spatial) == 3 and spatial[0] == 1 else spatial      # a depth of 1 is a slice
+    if min(windowed) < SSIM_WINDOW:
+        raise ValueError(f"{who}: spatial extents {spatial} are below the {SSIM_WINDOW}-wide window")
+    if pred.dtype != torch.float32 or target.dtype != torch.float32 or not (pred.is_cuda and target.is_cuda):
+        raise ValueError(f"{who}: expects two fp32 device tensors")
+    return spatial
+
+
+class _SSIMLossFn(torch.autograd.Function):
+    """The reduced loss 1 - ssim; saves the two inputs and the float64 coefficient maps of the gradients that
+    needs_input_grad asks for.  backward only reads them, so a second backward (retain_graph) gives the same bits."""
+
+    @staticmethod
+    def forward(ctx, pred, target, lo, hi, reduction):
+        a, b = pred.contiguous(), target.contiguous()     # a contiguous view keeps its (possibly unaligned) offset
+        batch, channels, spatial = a.shape[0], a.shape[1], tuple(a.shape[2:])
+        items, dev = batch * channels, a.device
+        mask = int(ctx.needs_input_grad[0]) | (int(ctx.needs_input_grad[1]) << 1)
+        ws_bytes, coef_bytes = ops.ssim_loss_workspace(spatial, items, mask)
+        ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+        coef = torch.empty(coef_bytes // 8, dtype=torch.float64, device=dev) if mask else None
+        loss = torch.empty((batch,) if reduction == "none" else (), device=dev)
+        ops.ssim_loss_forward(a, b, spatial, items, channels, lo, hi, mask, ws, coef, reduction, loss)
+        scale = {"mean": -1.0 / items, "sum": -1.0, "none": -1.0 / channels}[reduction]
+        ctx.cfg = (spatial, items, channels, lo, mask, scale)
+        ctx.save_for_backward(a, b, coef)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        a, b, coef = ctx.saved_tensors
+        spatial, items, channels, lo, mask, scale = ctx.cfg
+        gout = gout.contiguous()
+        grads = [None, None]
+        for wrt in (0, 1):
+            if ctx.needs_input_grad[wrt]:
+                grads[wrt] = ops.ssim_loss_backward(a, b, spatial, items, channels, lo, mask, coef, gout, scale, wrt,
+                                                    torch.empty_like(a))
+        return grads[0], grads[1], None, None, None
+
+
+def ssim_loss(pred: torch.Tensor, target: torch.Tensor, value_range=(0.0, 1.0), reduction: str = "mean") -> torch.Tensor:
+    """1 - SSIM of two (B, C, H, W) or (B, C, D, H, W) fp32 device tensors: every (b, c) image is one item, scored as
+    metrics.ssim scores it (7-wide uniform window on every spatial axis, K1 = 0.01, K2 = 0.03, sample covariance,
+    mean over the windows inside the image) with data range hi - lo of value_range = (lo, hi); lo is subtracted from
+    both tensors, nothing is clamped.  reduction: "mean" (a scalar over the B * C items), "sum", or "none" ((B,), each
+    entry the mean over its channels).  Differentiable in both arguments; bitwise reproducible."""
+    who = "ssim_loss"
+    lo, hi = _ssim_config(value_range, reduction, who)
+    _ssim_inputs(pred, target, who)
+    return _SSIMLossFn.apply(pred, target, lo, hi, reduction)
+
+
+class SSIMLoss(nn.Module):
+    """ssim_loss as a module: SSIMLoss(value_range=(-1.0, 1.0)) suits a tanh output."""
+
+    def __init__(self, value_range=(0.0, 1.0), reduction: str = "mean"):
+        super().__init__()
+        _ssim_config(value_range, reduction, "SSIMLoss")
+        self.value_range, self.reduction = tuple(value_range), reduction
+
+    def forward(self, pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        return ssim_loss(pred, target, self.value_range, self.reduction)

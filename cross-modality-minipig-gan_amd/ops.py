@@ -883,3 +883,38 @@ def parzen_mi_backward(a, b, batch, ranges, bins, sigma_ratio, coef, upstream, s
                                          0 if upstream.numel() == 1 else 1, float(scale), int(wrt), grad.data_ptr(),
                                          _stream()), "parzen_mi_backward")
     return grad
+
+
+# ---- SSIM loss (csrc/ssim_loss.hip; losses.py holds the autograd node) ----
+def _dhw(spatial):
+    return (C.c_int32 * 3)(*((1,) * (3 - len(spatial)) + tuple(int(s) for s in spatial)))
+
+
+def ssim_loss_workspace(spatial, items: int, grad_mask: int):
+    """(workspace bytes, coefficient-buffer bytes) for `items` images of extent `spatial` ((H, W) or (D, H, W))."""
+    coef = C.c_int64(0)
+    need = int(lib().mpgan_ssim_loss_workspace(_dhw(spatial), int(items), int(grad_mask), C.byref(coef)))
+    if need < 0:
+        raise ValueError(f"ssim_loss_workspace: bad geometry ({items} items of extent {tuple(spatial)}): extents below "
+                         "the 7-wide window, or a depth that is neither 1 nor >= 7")
+    return need, int(coef.value)
+
+
+def ssim_loss_forward(a, b, spatial, items, channels, lo, hi, grad_mask, workspace, coef, reduction, loss):
+    """loss (fp32, reduced on the device) of two contiguous fp32 tensors; with grad_mask != 0 also the backward's
+    coefficient maps (see include/mpgan_hip.h)."""
+    check(lib().mpgan_ssim_loss_forward(a.data_ptr(), b.data_ptr(), _dhw(spatial), int(items), int(channels), float(lo),
+                                        float(hi), int(grad_mask), workspace.data_ptr(),
+                                        workspace.numel() * workspace.element_size(), _ptr(coef),
+                                        coef.numel() * coef.element_size() if coef is not None else 0,
+                                        _PMI_REDUCTIONS[reduction], loss.data_ptr(), _stream()), "ssim_loss_forward")
+    return loss
+
+
+def ssim_loss_backward(a, b, spatial, items, channels, lo, grad_mask, coef, upstream, scale, wrt, grad):
+    """grad = upstream[batch entry or 0] * scale * d ssim_item / d (a if wrt == 0 else b)."""
+    check(lib().mpgan_ssim_loss_backward(a.data_ptr(), b.data_ptr(), _dhw(spatial), int(items), int(channels), float(lo),
+                                         int(grad_mask), coef.data_ptr(), coef.numel() * coef.element_size(),
+                                         upstream.data_ptr(), 0 if upstream.numel() == 1 else 1, float(scale), int(wrt),
+                                         grad.data_ptr(), _stream()), "ssim_loss_backward")
+    return grad

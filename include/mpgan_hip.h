@@ -455,6 +455,46 @@ int mpgan_parzen_mi_backward(const float* a, const float* b, int64_t numel_per_i
                              const float* coef, const float* upstream, int32_t upstream_stride, float scale,
                              int32_t wrt, float* grad, void* stream);
 
+/* ---- SSIM loss: the structural similarity of mpgan_ssim as a differentiable loss (the figure
+ * code/GAN/psnr_ssim_metric.py:88-106 reports; the reference's trainer has no such term, the definition below is what
+ * is pinned) ----
+ * a, b: contiguous fp32 arrays of `items` images of dhw = (D, H, W) samples each; an item is one (batch, channel)
+ * image, items = batch * channels.  D == 1: slices, 7x7 windows (d = 2); D >= 7: volumes, 7x7x7 windows (d = 3).
+ * The samples enter shifted, a = x - lo (no clamp: the gradient passes through unchanged); L = hi - lo.
+ *   n = 7^d;  cn = n / (n - 1);  C1 = (0.01 L)^2;  C2 = (0.03 L)^2
+ *   per window lying wholly inside the image (M = prod(S_i - 6) of them):
+ *     ux, uy = window means;  vx = cn (sum a^2 / n - ux^2), vy likewise;  vxy = cn (sum a b / n - ux uy)
+ *     A1 = 2 ux uy + C1;  A2 = 2 vxy + C2;  B1 = ux^2 + uy^2 + C1;  B2 = vx + vy + C2;  S = A1 A2 / (B1 B2)
+ *   ssim_item = mean of S over the M windows (what mpgan_ssim computes for one image);  loss_item = 1 - ssim_item
+ *   reduction 0: loss[0] = mean over the items; 1: loss[0] = their sum; 2: loss[batch], entry b = mean over b's channels.
+ * Gradient: per window  Q = -2 cn S / B2;  R = 2 cn A1 / (B1 B2);
+ *     P = 2 uy A2 / (B1 B2) - 2 ux S / B1 - ux Q - uy R
+ *   d ssim_item / d a_p = (1 / (n M)) (sum P + a_p sum Q + b_p sum R), the sums over the (up to 7^d) valid windows that
+ *   contain sample p; for b the same with the roles swapped: P with ux <-> uy, Q and R shared.
+ * Window sums, the maps and the box sums of the backward are fp64 and every sum has a fixed order (no atomics): the
+ * loss and both gradients are bitwise reproducible from call to call.  The maps are stored as doubles because P holds
+ * -ux Q: sum P + a_p sum Q cancels in flat regions, and an fp32 P would leave its rounding as the gradient's error.
+ * The calls allocate nothing, are asynchronous on `stream` and can be captured into a graph.  Extents below the
+ * window are MPGAN_ERR_INVALID, a depth in 2..6 is MPGAN_ERR_UNSUPPORTED, both before any launch. */
+/* Bytes of workspace the forward needs (8-byte aligned); *coef_bytes (nullable) receives the bytes of the coefficient
+ * buffer for grad_mask (bit 0: a gradient for a will be asked for, bit 1: for b; 0: none, no buffer).  -1 on a bad
+ * argument. */
+int64_t mpgan_ssim_loss_workspace(const int32_t* dhw, int32_t items, int32_t grad_mask, int64_t* coef_bytes);
+/* loss as `reduction` says (fp32, written on the device: no host sync).  With grad_mask != 0 the same pass writes
+ * coef = [Q][R][P of a, if bit 0][P of b, if bit 1], each [items][M] doubles over the window corners; coef may be
+ * null when grad_mask == 0. */
+int mpgan_ssim_loss_forward(const float* a, const float* b, const int32_t* dhw, int32_t items, int32_t channels,
+                            double lo, double hi, int32_t grad_mask, void* workspace, int64_t workspace_bytes,
+                            void* coef, int64_t coef_bytes, int32_t reduction, float* loss, void* stream);
+/* grad[items][D][H][W] = upstream[(item / channels) * upstream_stride] * scale * d ssim_item / d (wrt == 0 ? a : b),
+ * with the geometry, lo, grad_mask and coef of the forward call (coef is read, never written: a second call gives the
+ * same bits).  upstream is a device array over the batch (stride 1) or one device scalar (stride 0); scale is the
+ * host factor of the reduction (-1 for the sum, -1 / items for the mean, -1 / channels for reduction 2). */
+int mpgan_ssim_loss_backward(const float* a, const float* b, const int32_t* dhw, int32_t items, int32_t channels,
+                             double lo, int32_t grad_mask, const void* coef, int64_t coef_bytes,
+                             const float* upstream, int32_t upstream_stride, double scale, int32_t wrt, float* grad,
+                             void* stream);
+
 /* ---- optimiser ------------------------------------------------------------ */
 /* torch.optim.Adam.step over one flat buffer (GAN_final.py:306-307):
  * m = b1*m+(1-b1)*g; v = b2*v+(1-b2)*g^2; p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t)+eps).
