@@ -275,7 +275,9 @@ __global__ void pct_init_kernel(PctState* stt, unsigned* hist, int nt, unsigned 
   for (int i = threadIdx.x; i < PCT_MAXT * PCT_BINS; i += blockDim.x) hist[i] = 0;
 }
 
-// out[j] = s[lo_j] + frac_j * (s[lo_j + 1] - s[lo_j])   (numpy's linear interpolation, in double)
+// out[j] = s[lo_j] + frac_j * (s[lo_j + 1] - s[lo_j])   (numpy's linear interpolation, in double).  With frac_j == 0
+// or two equal order statistics the result is s[lo_j] itself, without arithmetic: an infinite minimum / maximum
+// stays infinite (the interpolation would form inf - inf).
 __global__ void pct_final_kernel(const PctState* __restrict__ stt, int nq, double f0, double f1,
                                  float* __restrict__ out) {
   const double fr[2] = {f0, f1};
@@ -283,7 +285,8 @@ __global__ void pct_final_kernel(const PctState* __restrict__ stt, int nq, doubl
     const double a = (double)pct_unkey(stt->prefix[2 * threadIdx.x]);
     const double b = (double)pct_unkey(stt->prefix[2 * threadIdx.x + 1]);
     const double t = fr[threadIdx.x];
-    out[threadIdx.x] = (float)(t >= 0.5 ? b - (b - a) * (1.0 - t) : a + (b - a) * t);
+    const double v = (t == 0.0 || a == b) ? a : (t >= 0.5 ? b - (b - a) * (1.0 - t) : a + (b - a) * t);
+    out[threadIdx.x] = (float)v;
   }
 }
 
@@ -385,6 +388,7 @@ extern "C" int mpgan_percentiles(const float* x, int64_t numel, const double* q_
                                  int64_t workspace_bytes, float* out, void* stream) {
   MPGAN_CHECK_ARG(x && q_host && workspace && out && numel > 0, "percentiles: bad argument");
   MPGAN_UNSUPPORTED(nq < 1 || nq > 2, "percentiles: 1 or 2 percentiles per call (got %d)", nq);
+  MPGAN_UNSUPPORTED(numel >= (1LL << 32), "percentiles: numel >= 2^32 would overflow the uint32 histogram counters");
   MPGAN_CHECK_ARG(workspace_bytes >= mpgan_percentile_workspace(), "percentiles: workspace too small");
   MPGAN_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "percentiles: workspace must be 8-byte aligned");
   unsigned long long ks[4] = {0, 0, 0, 0};

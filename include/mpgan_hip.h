@@ -367,7 +367,11 @@ int mpgan_image_errors(const float* a, const float* b, int64_t numel, float data
 /* ---- pre-processing, array half of next-row N3 (GAN_final.py:386-394:
  *      ScaleIntensityRangePercentilesd(lower=1, upper=99, b_min=-1, b_max=1, clip=True)) ---------- */
 /* out[j] = np.percentile(x, q[j]) (linear interpolation) for nq in {1, 2} percentiles: exact order
- * statistics by a 3-pass radix select; q_host is read on the host at call time.
+ * statistics by a 3-pass radix select; q_host is read on the host at call time.  Where q lands on an order
+ * statistic (q = 0 and 100 among them) or between two equal ones the result is that statistic itself, so an
+ * infinite minimum / maximum comes back infinite (numpy's interpolation forms inf - inf = NaN there); between an
+ * infinity and another value the result is NaN or infinite as numpy's is.  NaN inputs are not supported.
+ * numel < 2^32: the histogram counters are uint32 (a larger input is refused as unsupported).
  * workspace >= mpgan_percentile_workspace() bytes, 8-byte aligned. */
 int64_t mpgan_percentile_workspace(void);
 int mpgan_percentiles(const float* x, int64_t numel, const double* q_host, int32_t nq,

@@ -34,12 +34,15 @@ def structural_similarity(im1, im2, data_range=256.0, win_size=7, K1=0.01, K2=0.
     return float(S[crop].mean(dtype=np.float64))
 
 
-def scale_intensity_range_percentiles(img, lower=1.0, upper=99.0, b_min=-1.0, b_max=1.0, clip=True):
+def scale_intensity_range_percentiles(img, lower=1.0, upper=99.0, b_min=-1.0, b_max=1.0, clip=True, a_min=None,
+                                      a_max=None):
     """MONAI 0.4.0 `ScaleIntensityRangePercentiles.__call__` with relative=False followed by
-    `ScaleIntensityRange.__call__` (3rd-party source restated; call site code/GAN/GAN_final.py:386-394)."""
+    `ScaleIntensityRange.__call__` (3rd-party source restated; call site code/GAN/GAN_final.py:386-394).
+    a_min / a_max, when given, replace the two percentiles (a test passes the device's own, to hold the scaling
+    kernel alone to this restatement)."""
     img = np.asarray(img)
-    a_min = np.percentile(img, lower)
-    a_max = np.percentile(img, upper)
+    a_min = np.percentile(img, lower) if a_min is None else a_min
+    a_max = np.percentile(img, upper) if a_max is None else a_max
     if a_max - a_min == 0.0:
         return img - a_min
     out = (img - a_min) / (a_max - a_min)

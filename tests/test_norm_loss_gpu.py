@@ -207,7 +207,8 @@ def test_patch_gather_is_bit_exact_and_scatter_is_its_adjoint():
 
 def test_eval_metrics_match_numpy_restatement():
     """inferrence.py:188-204 / psnr_ssim_metric.py:88-106 restated in numpy: min/max rescale to
-    0..255, round, MAE; MSE and PSNR with data_range 256."""
+    0..255, round, MAE; MSE and PSNR with data_range 256.  Bounds from the kernels' arithmetic (DESIGN.md section 8.2,
+    tests/metric_small_ref.py), as in tests/test_metrics_small_gpu.py."""
     from mpgan_amd import metrics
     gen = torch.Generator().manual_seed(2)
     a = torch.rand(1, 1, 40, 48, 44, generator=gen) * 2 - 1
@@ -218,14 +219,35 @@ def test_eval_metrics_match_numpy_restatement():
         lo, hi = np.percentile(x, 0), np.percentile(x, 100)
         return np.round(np.clip((x - lo) / (hi - lo) * 255.0, 0, 255))
 
+    import metric_small_ref as MR
     ra, rb = rescale(a), rescale(b)
     got = metrics.rescale_0_255(a.cuda()).cpu().numpy()
     assert (np.abs(got - ra) > 0).mean() < 1e-4          # .5 ties may round differently in fp32
+    # ... and only those: an element that differs lies within four fp32 roundings of a tie and differs by exactly 1
+    ga = got.astype(np.float64)
+    gb = metrics.rescale_0_255(b.cuda()).cpu().numpy().astype(np.float64)
+    flips = 0
+    for g, r, x in ((ga, ra, a), (gb, rb, b)):
+        off = g != r
+        tie = MR.near_tie_mask(MR.rescale_ref(x.numpy()))
+        assert tie.mean() <= MR.NEAR_TIE_CAP and not (off & ~tie).any() and (np.abs(g - r)[off] == 1).all()
+        flips += int(off.sum())
     s = metrics.score_volume(a.cuda(), b.cuda())
-    mse = ((ra - rb) ** 2).mean()
-    np.testing.assert_allclose(s["mae"].item(), np.abs(ra - rb).mean(), rtol=1e-3)
-    np.testing.assert_allclose(s["mse"].item(), mse, rtol=1e-3)
-    np.testing.assert_allclose(s["psnr"].item(), 10 * np.log10(256.0 ** 2 / mse), rtol=1e-4)
+    # the error kernel against float64 on the device's own rescaled volumes: (m + 11) 2^-24 relative, m = terms per thread
+    n = a.numel()
+    rel = MR.error_rel_bound(n)
+    mae_d, mse_d, psnr_d = MR.errors_ref(ga, gb, 256.0)
+    assert abs(s["mae"].item() - mae_d) <= rel * mae_d and abs(s["mse"].item() - mse_d) <= rel * mse_d
+    assert abs(s["psnr"].item() - psnr_d) <= 10 / np.log(10) * rel + float(MR.f32_ulp(psnr_d))
+    # ... and against the numpy restatement: each flipped tie moves one |d| by 1 and one d^2 by at most 2 max|d| + 1
+    mae, mse = np.abs(ra - rb).mean(), ((ra - rb) ** 2).mean()
+    mae_lim, mse_lim = rel * mae + flips / n, rel * mse + flips * (2 * np.abs(ra - rb).max() + 1) / n
+    assert mae_lim <= 1e-3 * mae and mse_lim <= 1e-3 * mse       # never wider than the bounds these replaced
+    assert abs(s["mae"].item() - mae) <= mae_lim and abs(s["mse"].item() - mse) <= mse_lim
+    psnr = 10 * np.log10(256.0 ** 2 / mse)
+    psnr_lim = 10 / np.log(10) * mse_lim / mse * (1 + 1e-3) + float(MR.f32_ulp(psnr))
+    assert psnr_lim <= 1e-4 * psnr
+    assert abs(s["psnr"].item() - psnr) <= psnr_lim
 
 
 @pytest.mark.parametrize("shape", [(40, 48, 44), (9, 35, 71), (64, 50), (7, 7, 7), (128, 128, 128)])
