@@ -2458,14 +2458,38 @@ __global__ __launch_bounds__(256) void norm_act_bf16_kernel(const __bf16* __rest
 // BatchNorm + LeakyReLU backward on bf16 z:  gy = g*act'(y);  partial rows [chunks*n][3][C] of
 // (sum gy, sum gy*zhat, 0) in the layout mpgan_norm_bwd_finalize consumes; apply: dz = scale*(gy - c1 - zhat*c2).
 // block = R rows x C/8 column groups; chunk = blockIdx.x of gridDim.x over the rows.
-template <typename TG>
+// PEER: with the perceptual taps of a peer pass (variant B): the fp32 path's formula (norm_ops.hip, Peer) on the stored
+// bf16 z of both passes,
+//   g_a = g - ca*sign(a_peer - a),  gy = g_a*act'(y) - cy*sign(y_peer - y),  dz += -cz*sign(z_peer - z),
+// with y = z*scale + shift and a = LeakyReLU_slope(y) in fp32 on each side.  Same grid, rows and partial layout; the
+// instantiations without a peer take an empty descriptor and load and compute nothing for it.
+struct PeerBf16 {
+  const __bf16* z;     // the peer pass's stored raw conv output, [rows][ld]
+  int ld;
+  const float* scale;  // its norm scale / shift
+  const float* shift;
+  const float* coef;   // device float[3]: (cz, cy, ca)
+};
+struct NoPeerBf16 {};
+template <bool PEER>
+using peer_bf16_t = std::conditional_t<PEER, PeerBf16, NoPeerBf16>;
+
+__device__ __forceinline__ float peer_gy_bf16(float g, float y, float yp, float slope, float cy, float ca) {
+  const float ap = yp < 0.f ? yp * slope : yp;
+  const float a = y < 0.f ? y * slope : y;
+  const float ga = g - ca * sgn(ap - a);
+  return (y < 0.f ? ga * slope : ga) - cy * sgn(yp - y);
+}
+
+template <typename TG, bool PEER>
 __global__ __launch_bounds__(256) void norm_bwd_reduce_bf16_kernel(const TG* __restrict__ g, int ldg,
                                                                    const __bf16* __restrict__ z, int ldz,
                                                                    const float* __restrict__ scale,
                                                                    const float* __restrict__ shift,
                                                                    const float* __restrict__ mean,
-                                                                   const float* __restrict__ invstd, float slope,
-                                                                   long rows, int C, float* __restrict__ partials) {
+                                                                   const float* __restrict__ invstd,
+                                                                   peer_bf16_t<PEER> pr, float slope, long rows, int C,
+                                                                   float* __restrict__ partials) {
   extern __shared__ float red[];   // [R][2][C]
   const int CG = C / 8, R = 256 / CG;
   const int q = threadIdx.x % CG, r = threadIdx.x / CG, c = q * 8;
@@ -2475,16 +2499,23 @@ __global__ __launch_bounds__(256) void norm_bwd_reduce_bf16_kernel(const TG* __r
 #pragma unroll
   for (int e = 0; e < 8; ++e) a0[e] = a1[e] = 0.f;
   if (r < R) {
-    float sc[8], sh[8], mu[8], is[8];
+    float sc[8], sh[8], mu[8], is[8], psc[8], psh[8], cy, ca;
     ld8(scale + c, sc); ld8(shift + c, sh); ld8(mean + c, mu); ld8(invstd + c, is);
+    if constexpr (PEER) {
+      ld8(pr.scale + c, psc); ld8(pr.shift + c, psh);
+      cy = pr.coef[1], ca = pr.coef[2];
+    }
     for (long row = beg + r; row < end; row += R) {
-      float zv[8], gv[8];
+      float zv[8], gv[8], zp[8];
       ld8(z + row * ldz + c, zv);
       ld8(g + row * ldg + c, gv);
+      if constexpr (PEER) ld8(pr.z + row * pr.ld + c, zp);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const float y = zv[e] * sc[e] + sh[e];
-        const float gy = y < 0.f ? gv[e] * slope : gv[e];
+        float gy;
+        if constexpr (PEER) gy = peer_gy_bf16(gv[e], y, zp[e] * psc[e] + psh[e], slope, cy, ca);
+        else gy = y < 0.f ? gv[e] * slope : gv[e];
         a0[e] += gy;
         a1[e] = fmaf(gy, (zv[e] - mu[e]) * is[e], a1[e]);
       }
@@ -2507,7 +2538,7 @@ __global__ __launch_bounds__(256) void norm_bwd_reduce_bf16_kernel(const TG* __r
 
 // dz (bf16) = scale*(gy - c1 - zhat*c2); optionally per-block column sums of the ROUNDED dz (the conv's bias
 // gradient: dbias = colsum(dy)) as partial rows [gridDim.x][C].
-template <typename TG>
+template <typename TG, bool PEER>
 __global__ __launch_bounds__(256) void norm_bwd_apply_bf16_kernel(const TG* __restrict__ g, int ldg,
                                                                   const __bf16* __restrict__ z, int ldz,
                                                                   const float* __restrict__ scale,
@@ -2515,8 +2546,9 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_bf16_kernel(const TG* __re
                                                                   const float* __restrict__ mean,
                                                                   const float* __restrict__ invstd,
                                                                   const float* __restrict__ c1,
-                                                                  const float* __restrict__ c2, float slope, long rows,
-                                                                  int C, __bf16* __restrict__ dz, int lddz,
+                                                                  const float* __restrict__ c2, peer_bf16_t<PEER> pr,
+                                                                  float slope, long rows, int C,
+                                                                  __bf16* __restrict__ dz, int lddz,
                                                                   float* __restrict__ bias_partials) {
   extern __shared__ float red[];   // [R][C]
   const int CG = C / 8, R = 256 / CG;
@@ -2525,139 +2557,27 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_bf16_kernel(const TG* __re
 #pragma unroll
   for (int e = 0; e < 8; ++e) bs[e] = 0.f;
   if (r < R) {
-    float sc[8], sh[8], mu[8], is[8], k1[8], k2[8];
+    float sc[8], sh[8], mu[8], is[8], k1[8], k2[8], psc[8], psh[8], cz, cy, ca;
     ld8(scale + c, sc); ld8(shift + c, sh); ld8(mean + c, mu); ld8(invstd + c, is); ld8(c1 + c, k1); ld8(c2 + c, k2);
-    for (long row = (long)blockIdx.x * R + r; row < rows; row += (long)gridDim.x * R) {
-      float zv[8], gv[8], o[8];
-      ld8(z + row * ldz + c, zv);
-      ld8(g + row * ldg + c, gv);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float y = zv[e] * sc[e] + sh[e];
-        const float gy = y < 0.f ? gv[e] * slope : gv[e];
-        o[e] = sc[e] * (gy - k1[e] - (zv[e] - mu[e]) * is[e] * k2[e]);
-        bs[e] += (float)(__bf16)o[e];
-      }
-      st8(dz + row * lddz + c, o);
+    if constexpr (PEER) {
+      ld8(pr.scale + c, psc); ld8(pr.shift + c, psh);
+      cz = pr.coef[0], cy = pr.coef[1], ca = pr.coef[2];
     }
-  }
-  if (bias_partials) {
-    if (r < R) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) red[r * C + c + e] = bs[e];
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < C; i += 256) {
-      float s = 0.f;
-      for (int rr = 0; rr < R; ++rr) s += red[rr * C + i];
-      bias_partials[(long)blockIdx.x * C + i] = s;
-    }
-  }
-}
-
-// The two kernels above with the perceptual taps of a peer pass (variant B): the fp32 path's formula (norm_ops.hip,
-// Peer) on the stored bf16 z of both passes,
-//   g_a = g - ca*sign(a_peer - a),  gy = g_a*act'(y) - cy*sign(y_peer - y),  dz += -cz*sign(z_peer - z),
-// with y = z*scale + shift and a = LeakyReLU_slope(y) in fp32 on each side.  Same grid, rows and partial layout.
-struct PeerBf16 {
-  const __bf16* z;     // the peer pass's stored raw conv output, [rows][ld]
-  int ld;
-  const float* scale;  // its norm scale / shift
-  const float* shift;
-  const float* coef;   // device float[3]: (cz, cy, ca)
-};
-
-__device__ __forceinline__ float peer_gy_bf16(float g, float y, float yp, float slope, float cy, float ca) {
-  const float ap = yp < 0.f ? yp * slope : yp;
-  const float a = y < 0.f ? y * slope : y;
-  const float ga = g - ca * sgn(ap - a);
-  return (y < 0.f ? ga * slope : ga) - cy * sgn(yp - y);
-}
-
-template <typename TG>
-__global__ __launch_bounds__(256) void norm_bwd_reduce_bf16_peer_kernel(const TG* __restrict__ g, int ldg,
-                                                                        const __bf16* __restrict__ z, int ldz,
-                                                                        const float* __restrict__ scale,
-                                                                        const float* __restrict__ shift,
-                                                                        const float* __restrict__ mean,
-                                                                        const float* __restrict__ invstd, PeerBf16 pr,
-                                                                        float slope, long rows, int C,
-                                                                        float* __restrict__ partials) {
-  extern __shared__ float red[];   // [R][2][C]
-  const int CG = C / 8, R = 256 / CG;
-  const int q = threadIdx.x % CG, r = threadIdx.x / CG, c = q * 8;
-  const long per = (rows + gridDim.x - 1) / gridDim.x;
-  const long beg = (long)blockIdx.x * per, end = beg + per < rows ? beg + per : rows;
-  float a0[8], a1[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) a0[e] = a1[e] = 0.f;
-  if (r < R) {
-    float sc[8], sh[8], mu[8], is[8], psc[8], psh[8];
-    ld8(scale + c, sc); ld8(shift + c, sh); ld8(mean + c, mu); ld8(invstd + c, is);
-    ld8(pr.scale + c, psc); ld8(pr.shift + c, psh);
-    const float cy = pr.coef[1], ca = pr.coef[2];
-    for (long row = beg + r; row < end; row += R) {
-      float zv[8], gv[8], zp[8];
-      ld8(z + row * ldz + c, zv);
-      ld8(g + row * ldg + c, gv);
-      ld8(pr.z + row * pr.ld + c, zp);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float y = zv[e] * sc[e] + sh[e];
-        const float gy = peer_gy_bf16(gv[e], y, zp[e] * psc[e] + psh[e], slope, cy, ca);
-        a0[e] += gy;
-        a1[e] = fmaf(gy, (zv[e] - mu[e]) * is[e], a1[e]);
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      red[(r * 2 + 0) * C + c + e] = a0[e];
-      red[(r * 2 + 1) * C + c + e] = a1[e];
-    }
-  }
-  __syncthreads();
-  float* out = partials + (long)blockIdx.x * 3 * C;
-  for (int i = threadIdx.x; i < 3 * C; i += 256) {
-    float s = 0.f;
-    if (i < 2 * C)
-      for (int rr = 0; rr < R; ++rr) s += red[rr * 2 * C + i];
-    out[i] = s;
-  }
-}
-
-template <typename TG>
-__global__ __launch_bounds__(256) void norm_bwd_apply_bf16_peer_kernel(const TG* __restrict__ g, int ldg,
-                                                                       const __bf16* __restrict__ z, int ldz,
-                                                                       const float* __restrict__ scale,
-                                                                       const float* __restrict__ shift,
-                                                                       const float* __restrict__ mean,
-                                                                       const float* __restrict__ invstd,
-                                                                       const float* __restrict__ c1,
-                                                                       const float* __restrict__ c2, PeerBf16 pr,
-                                                                       float slope, long rows, int C,
-                                                                       __bf16* __restrict__ dz, int lddz,
-                                                                       float* __restrict__ bias_partials) {
-  extern __shared__ float red[];   // [R][C]
-  const int CG = C / 8, R = 256 / CG;
-  const int q = threadIdx.x % CG, r = threadIdx.x / CG, c = q * 8;
-  float bs[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) bs[e] = 0.f;
-  if (r < R) {
-    float sc[8], sh[8], mu[8], is[8], k1[8], k2[8], psc[8], psh[8];
-    ld8(scale + c, sc); ld8(shift + c, sh); ld8(mean + c, mu); ld8(invstd + c, is); ld8(c1 + c, k1); ld8(c2 + c, k2);
-    ld8(pr.scale + c, psc); ld8(pr.shift + c, psh);
-    const float cz = pr.coef[0], cy = pr.coef[1], ca = pr.coef[2];
     for (long row = (long)blockIdx.x * R + r; row < rows; row += (long)gridDim.x * R) {
       float zv[8], gv[8], zp[8], o[8];
       ld8(z + row * ldz + c, zv);
       ld8(g + row * ldg + c, gv);
-      ld8(pr.z + row * pr.ld + c, zp);
+      if constexpr (PEER) ld8(pr.z + row * pr.ld + c, zp);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const float y = zv[e] * sc[e] + sh[e];
-        const float gy = peer_gy_bf16(gv[e], y, zp[e] * psc[e] + psh[e], slope, cy, ca);
-        o[e] = sc[e] * (gy - k1[e] - (zv[e] - mu[e]) * is[e] * k2[e]) - cz * sgn(zp[e] - zv[e]);
+        if constexpr (PEER) {
+          const float gy = peer_gy_bf16(gv[e], y, zp[e] * psc[e] + psh[e], slope, cy, ca);
+          o[e] = sc[e] * (gy - k1[e] - (zv[e] - mu[e]) * is[e] * k2[e]) - cz * sgn(zp[e] - zv[e]);
+        } else {
+          const float gy = y < 0.f ? gv[e] * slope : gv[e];
+          o[e] = sc[e] * (gy - k1[e] - (zv[e] - mu[e]) * is[e] * k2[e]);
+        }
         bs[e] += (float)(__bf16)o[e];
       }
       st8(dz + row * lddz + c, o);
@@ -3044,25 +2964,63 @@ extern "C" int32_t mpgan_norm_bwd_rows_bf16(int64_t rows, int32_t c) {
   return (int32_t)(b < 1 ? 1 : b);
 }
 
+static inline bool any_misaligned16(std::initializer_list<const void*> ps) {
+  for (const void* p : ps)
+    if (reinterpret_cast<uintptr_t>(p) & 15) return true;
+  return false;
+}
+
+// The launches behind the four norm-backward entries (the entries keep their own argument checks): grid = the partial
+// rows of mpgan_norm_bwd_rows_bf16, the g dtype and the peer descriptor select the instantiation.
+template <bool PEER>
+static int launch_norm_bwd_reduce_bf16(const char* what, const void* g, int32_t g_f32, int32_t ldg, const void* z,
+                                       int32_t ldz, const float* scale, const float* shift, const float* mean,
+                                       const float* invstd, float slope, int64_t rows, int32_t c, float* partials,
+                                       peer_bf16_t<PEER> pr, void* stream) {
+  const int nb = mpgan_norm_bwd_rows_bf16(rows, c);
+  const int R = 256 / (c / 8);
+  const size_t smem = (size_t)R * 2 * c * sizeof(float);
+  if (g_f32)
+    hipLaunchKernelGGL((norm_bwd_reduce_bf16_kernel<float, PEER>), dim3(nb), dim3(256), smem, (hipStream_t)stream,
+                       static_cast<const float*>(g), ldg, static_cast<const __bf16*>(z), ldz, scale, shift, mean, invstd,
+                       pr, slope, (long)rows, c, partials);
+  else
+    hipLaunchKernelGGL((norm_bwd_reduce_bf16_kernel<__bf16, PEER>), dim3(nb), dim3(256), smem, (hipStream_t)stream,
+                       static_cast<const __bf16*>(g), ldg, static_cast<const __bf16*>(z), ldz, scale, shift, mean,
+                       invstd, pr, slope, (long)rows, c, partials);
+  return check_launch(what);
+}
+
+template <bool PEER>
+static int launch_norm_bwd_apply_bf16(const char* what, const void* g, int32_t g_f32, int32_t ldg, const void* z,
+                                      int32_t ldz, const float* scale, const float* shift, const float* mean,
+                                      const float* invstd, const float* c1, const float* c2, float slope, int64_t rows,
+                                      int32_t c, void* dz, int32_t lddz, float* bias_partials, peer_bf16_t<PEER> pr,
+                                      void* stream) {
+  const int nb = mpgan_norm_bwd_rows_bf16(rows, c);
+  const int R = 256 / (c / 8);
+  const size_t smem = bias_partials ? (size_t)R * c * sizeof(float) : 0;
+  if (g_f32)
+    hipLaunchKernelGGL((norm_bwd_apply_bf16_kernel<float, PEER>), dim3(nb), dim3(256), smem, (hipStream_t)stream,
+                       static_cast<const float*>(g), ldg, static_cast<const __bf16*>(z), ldz, scale, shift, mean, invstd,
+                       c1, c2, pr, slope, (long)rows, c, static_cast<__bf16*>(dz), lddz, bias_partials);
+  else
+    hipLaunchKernelGGL((norm_bwd_apply_bf16_kernel<__bf16, PEER>), dim3(nb), dim3(256), smem, (hipStream_t)stream,
+                       static_cast<const __bf16*>(g), ldg, static_cast<const __bf16*>(z), ldz, scale, shift, mean,
+                       invstd, c1, c2, pr, slope, (long)rows, c, static_cast<__bf16*>(dz), lddz, bias_partials);
+  return check_launch(what);
+}
+
 extern "C" int mpgan_norm_bwd_reduce_bf16(const void* g, int32_t g_f32, int32_t ldg, const void* z, int32_t ldz,
                                           const float* scale, const float* shift, const float* mean,
                                           const float* invstd, float slope, int64_t rows, int32_t c, float* partials,
                                           void* stream) {
   MPGAN_CHECK_ARG(g && z && scale && shift && mean && invstd && partials && rows > 0 && ldg >= c && ldz >= c,
                   "norm_bwd_reduce_bf16: bad argument");
-  const int nb = mpgan_norm_bwd_rows_bf16(rows, c);
-  MPGAN_UNSUPPORTED(nb < 0 || ldg % 8 || ldz % 8, "norm_bwd_reduce_bf16: C %% 8, C <= 2048, pitches %% 8");
-  const int R = 256 / (c / 8);
-  const size_t smem = (size_t)R * 2 * c * sizeof(float);
-  if (g_f32)
-    hipLaunchKernelGGL(norm_bwd_reduce_bf16_kernel<float>, dim3(nb), dim3(256), smem, (hipStream_t)stream,
-                       static_cast<const float*>(g), ldg, static_cast<const __bf16*>(z), ldz, scale, shift, mean, invstd,
-                       slope, (long)rows, c, partials);
-  else
-    hipLaunchKernelGGL(norm_bwd_reduce_bf16_kernel<__bf16>, dim3(nb), dim3(256), smem, (hipStream_t)stream,
-                       static_cast<const __bf16*>(g), ldg, static_cast<const __bf16*>(z), ldz, scale, shift, mean,
-                       invstd, slope, (long)rows, c, partials);
-  return check_launch("norm_bwd_reduce_bf16");
+  MPGAN_UNSUPPORTED(mpgan_norm_bwd_rows_bf16(rows, c) < 0 || ldg % 8 || ldz % 8,
+                    "norm_bwd_reduce_bf16: C %% 8, C <= 2048, pitches %% 8");
+  return launch_norm_bwd_reduce_bf16<false>("norm_bwd_reduce_bf16", g, g_f32, ldg, z, ldz, scale, shift, mean, invstd,
+                                            slope, rows, c, partials, NoPeerBf16{}, stream);
 }
 
 extern "C" int mpgan_norm_bwd_apply_bf16(const void* g, int32_t g_f32, int32_t ldg, const void* z, int32_t ldz,
@@ -3072,25 +3030,10 @@ extern "C" int mpgan_norm_bwd_apply_bf16(const void* g, int32_t g_f32, int32_t l
   MPGAN_CHECK_ARG(g && z && scale && shift && mean && invstd && c1 && c2 && dz && rows > 0 && ldg >= c && ldz >= c &&
                       lddz >= c,
                   "norm_bwd_apply_bf16: bad argument");
-  const int nb = mpgan_norm_bwd_rows_bf16(rows, c);
-  MPGAN_UNSUPPORTED(nb < 0 || ldg % 8 || ldz % 8 || lddz % 8, "norm_bwd_apply_bf16: C %% 8, C <= 2048, pitches %% 8");
-  const int R = 256 / (c / 8);
-  const size_t smem = bias_partials ? (size_t)R * c * sizeof(float) : 0;
-  if (g_f32)
-    hipLaunchKernelGGL(norm_bwd_apply_bf16_kernel<float>, dim3(nb), dim3(256), smem, (hipStream_t)stream,
-                       static_cast<const float*>(g), ldg, static_cast<const __bf16*>(z), ldz, scale, shift, mean, invstd,
-                       c1, c2, slope, (long)rows, c, static_cast<__bf16*>(dz), lddz, bias_partials);
-  else
-    hipLaunchKernelGGL(norm_bwd_apply_bf16_kernel<__bf16>, dim3(nb), dim3(256), smem, (hipStream_t)stream,
-                       static_cast<const __bf16*>(g), ldg, static_cast<const __bf16*>(z), ldz, scale, shift, mean,
-                       invstd, c1, c2, slope, (long)rows, c, static_cast<__bf16*>(dz), lddz, bias_partials);
-  return check_launch("norm_bwd_apply_bf16");
-}
-
-static inline bool any_misaligned16(std::initializer_list<const void*> ps) {
-  for (const void* p : ps)
-    if (reinterpret_cast<uintptr_t>(p) & 15) return true;
-  return false;
+  MPGAN_UNSUPPORTED(mpgan_norm_bwd_rows_bf16(rows, c) < 0 || ldg % 8 || ldz % 8 || lddz % 8,
+                    "norm_bwd_apply_bf16: C %% 8, C <= 2048, pitches %% 8");
+  return launch_norm_bwd_apply_bf16<false>("norm_bwd_apply_bf16", g, g_f32, ldg, z, ldz, scale, shift, mean, invstd, c1,
+                                           c2, slope, rows, c, dz, lddz, bias_partials, NoPeerBf16{}, stream);
 }
 
 static int peer_bf16_of(const mpgan_peer_taps_bf16* t, int32_t c, PeerBf16& pr, const char* what) {
@@ -3112,23 +3055,14 @@ extern "C" int mpgan_norm_bwd_reduce_bf16_peer(const void* g, int32_t g_f32, int
                                                int64_t rows, int32_t c, float* partials, void* stream) {
   MPGAN_CHECK_ARG(g && z && scale && shift && mean && invstd && partials && rows > 0 && ldg >= c && ldz >= c,
                   "norm_bwd_reduce_bf16_peer: bad argument");
-  const int nb = mpgan_norm_bwd_rows_bf16(rows, c);
-  MPGAN_UNSUPPORTED(nb < 0 || ldg % 8 || ldz % 8 || any_misaligned16({g, z, scale, shift, mean, invstd}),
+  MPGAN_UNSUPPORTED(mpgan_norm_bwd_rows_bf16(rows, c) < 0 || ldg % 8 || ldz % 8 ||
+                        any_misaligned16({g, z, scale, shift, mean, invstd}),
                     "norm_bwd_reduce_bf16_peer: C %% 8, C <= 2048, pitches %% 8, 16-byte aligned tensors");
   PeerBf16 pr;
   int rc = peer_bf16_of(peer, c, pr, "norm_bwd_reduce_bf16_peer");
   if (rc) return rc;
-  const int R = 256 / (c / 8);
-  const size_t smem = (size_t)R * 2 * c * sizeof(float);
-  if (g_f32)
-    hipLaunchKernelGGL(norm_bwd_reduce_bf16_peer_kernel<float>, dim3(nb), dim3(256), smem, (hipStream_t)stream,
-                       static_cast<const float*>(g), ldg, static_cast<const __bf16*>(z), ldz, scale, shift, mean, invstd,
-                       pr, slope, (long)rows, c, partials);
-  else
-    hipLaunchKernelGGL(norm_bwd_reduce_bf16_peer_kernel<__bf16>, dim3(nb), dim3(256), smem, (hipStream_t)stream,
-                       static_cast<const __bf16*>(g), ldg, static_cast<const __bf16*>(z), ldz, scale, shift, mean,
-                       invstd, pr, slope, (long)rows, c, partials);
-  return check_launch("norm_bwd_reduce_bf16_peer");
+  return launch_norm_bwd_reduce_bf16<true>("norm_bwd_reduce_bf16_peer", g, g_f32, ldg, z, ldz, scale, shift, mean, invstd,
+                                           slope, rows, c, partials, pr, stream);
 }
 
 extern "C" int mpgan_norm_bwd_apply_bf16_peer(const void* g, int32_t g_f32, int32_t ldg, const void* z, int32_t ldz,
@@ -3139,23 +3073,14 @@ extern "C" int mpgan_norm_bwd_apply_bf16_peer(const void* g, int32_t g_f32, int3
   MPGAN_CHECK_ARG(g && z && scale && shift && mean && invstd && c1 && c2 && dz && rows > 0 && ldg >= c && ldz >= c &&
                       lddz >= c,
                   "norm_bwd_apply_bf16_peer: bad argument");
-  const int nb = mpgan_norm_bwd_rows_bf16(rows, c);
-  MPGAN_UNSUPPORTED(nb < 0 || ldg % 8 || ldz % 8 || lddz % 8 || any_misaligned16({g, z, dz, scale, shift, mean, invstd, c1, c2}),
+  MPGAN_UNSUPPORTED(mpgan_norm_bwd_rows_bf16(rows, c) < 0 || ldg % 8 || ldz % 8 || lddz % 8 ||
+                        any_misaligned16({g, z, dz, scale, shift, mean, invstd, c1, c2}),
                     "norm_bwd_apply_bf16_peer: C %% 8, C <= 2048, pitches %% 8, 16-byte aligned tensors");
   PeerBf16 pr;
   int rc = peer_bf16_of(peer, c, pr, "norm_bwd_apply_bf16_peer");
   if (rc) return rc;
-  const int R = 256 / (c / 8);
-  const size_t smem = bias_partials ? (size_t)R * c * sizeof(float) : 0;
-  if (g_f32)
-    hipLaunchKernelGGL(norm_bwd_apply_bf16_peer_kernel<float>, dim3(nb), dim3(256), smem, (hipStream_t)stream,
-                       static_cast<const float*>(g), ldg, static_cast<const __bf16*>(z), ldz, scale, shift, mean, invstd,
-                       c1, c2, pr, slope, (long)rows, c, static_cast<__bf16*>(dz), lddz, bias_partials);
-  else
-    hipLaunchKernelGGL(norm_bwd_apply_bf16_peer_kernel<__bf16>, dim3(nb), dim3(256), smem, (hipStream_t)stream,
-                       static_cast<const __bf16*>(g), ldg, static_cast<const __bf16*>(z), ldz, scale, shift, mean,
-                       invstd, c1, c2, pr, slope, (long)rows, c, static_cast<__bf16*>(dz), lddz, bias_partials);
-  return check_launch("norm_bwd_apply_bf16_peer");
+  return launch_norm_bwd_apply_bf16<true>("norm_bwd_apply_bf16_peer", g, g_f32, ldg, z, ldz, scale, shift, mean, invstd, c1,
+                                          c2, slope, rows, c, dz, lddz, bias_partials, pr, stream);
 }
 
 extern "C" int mpgan_tap_l1_bf16(const void* za, int32_t lda, const float* scale_a, const float* shift_a, const void* zb,

@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
+import math
 import os
 from typing import List, Optional, Sequence, Tuple
 
@@ -325,10 +326,7 @@ class ParamStore:
         for m in module.modules():
             if isinstance(m, (nn.Conv2d, nn.Conv3d, nn.ConvTranspose2d, nn.ConvTranspose3d)):
                 tr = isinstance(m, (nn.ConvTranspose2d, nn.ConvTranspose3d))
-                taps = 1
-                for k in m.kernel_size:
-                    taps *= k
-                self.register_conv(m, cout=m.out_channels, cin=m.in_channels, taps=taps, transposed=tr)
+                self.register_conv(m, cout=m.out_channels, cin=m.in_channels, taps=math.prod(m.kernel_size), transposed=tr)
 
     def flatten(self):
         params = list(self.module.parameters())
@@ -799,7 +797,7 @@ def emit_conv_fwd_act_bf16(prog, rows, g: ConvGeom, x, wp, bias, y, norm_mod, ac
         prog.add("conv_forward_act_f32_to_bf16", lib().mpgan_conv_forward_act_f32_to_bf16, C.byref(gc), x.data_ptr(), 1,
                  wp.data_ptr(), vec[0].data_ptr(), vec[1].data_ptr(), vec[2].data_ptr(), None, y.data_ptr(), g.cout,
                  keep=(gc, x, wp, y, vec, norm_mod, act_mod, bias), desc=_gdesc(g),
-                 tag=("thin_cin1_full_kernel<16, true>", 2.0 * conv_macs(g), conv_bytes(g, 2) + 2 * x.numel()))
+                 tag=_thin_cin1_tag(g, x))
         return
     prog.add("conv_forward_act_bf16", lib().mpgan_conv_forward_act_bf16, C.byref(gc), x.data_ptr(), g.cin, wp.data_ptr(),
              vec[0].data_ptr(), vec[1].data_ptr(), vec[2].data_ptr(), None, y.data_ptr(), g.cout,
@@ -859,6 +857,165 @@ def emit_norm_bwd(prog, g, z, nb: NormBuf, pro: Prologue, dz, partials, dgamma, 
              dz.data_ptr(), _ld(dz), keep=(dz,), desc=f"C{c} n{n} P{P}")
 
 
+# ---- bf16 storage: the single description of a bf16 layer's launches, for both discriminators ----
+def _bf16_kernel_name(g: ConvGeom, backward_data: bool) -> str:
+    """rocprofv3's name of the bf16 kernel that serves this layer (labels of bench.py's probe), from the same choice
+    the launch makes (mpgan_conv_kernel_name_bf16; the forward is the one with statistics)."""
+    gc = g.c()
+    return kernel_label(lib().mpgan_conv_kernel_name_bf16, C.byref(gc), int(backward_data))
+
+
+def _bf16_wgrad_kernel_name(g: ConvGeom) -> str:
+    """rocprofv3's name of the bf16 weight-gradient kernel of this layer, asked of the library that makes the choice."""
+    gc = g.c()
+    return "wgrad_bf16_wide_kernel" if lib().mpgan_conv_wgrad_variant_bf16(C.byref(gc)) == 1 else "wgrad_bf16_kernel<8>"
+
+
+def _thin_cin1_tag(g: ConvGeom, x):
+    """Probe tag of the 1-input-channel layer's forward (fp32 image in, bf16 out)."""
+    return ("thin_cin1_full_kernel<16, true>", 2.0 * conv_macs(g), conv_bytes(g, 2) + 2 * x.numel())
+
+
+def _rows(g: ConvGeom) -> int:
+    """Rows (pixels of all samples) of a conv's channels-last output."""
+    return g.n * math.prod(g.out_dhw)
+
+
+class PacksBF16:
+    """bf16 packs of a plan's dense convs, from their ConvRecs: [Cout][tap][Cin] (forward) and [Cin][tap][Cout]
+    (backward-data) in one buffer, each pack 16-byte aligned, refreshed from the flat fp32 store by one launch."""
+
+    def __init__(self, recs, dev):
+        rows, off, self._at = [], 0, {}
+        for r in recs:
+            nel = r.cout * r.cin * r.taps
+            pad = (nel + 7) // 8 * 8
+            self._at[id(r)] = (off, off + pad, nel)
+            rows.append([r.w_off, off, r.cout, r.cin, r.taps, 0, 0, 0])
+            rows.append([r.w_off, off + pad, r.cout, r.cin, r.taps, 0, 1, 0])
+            off += 2 * pad
+        self.packed = torch.empty(off, device=dev, dtype=torch.bfloat16)
+        self.table = torch.tensor(rows, dtype=torch.int64, device=dev)
+        self.max_elems = max(r.cout * r.cin * r.taps for r in recs)
+
+    def emit(self, prog, store: ParamStore):
+        prog.add("pack_weights_bf16", lib().mpgan_pack_weights_bf16, store.flat.data_ptr(), self.packed.data_ptr(),
+                 self.table.data_ptr(), self.table.shape[0], self.max_elems, keep=(self.packed, self.table))
+
+    def fwd(self, rec: ConvRec) -> torch.Tensor:
+        o, _, nel = self._at[id(rec)]
+        return self.packed[o:o + nel]
+
+    def bwd(self, rec: ConvRec) -> torch.Tensor:
+        _, o, nel = self._at[id(rec)]
+        return self.packed[o:o + nel]
+
+
+def emit_conv_fwd_bf16(prog, g: ConvGeom, x, wp, bias, z, stats=None) -> int:
+    """Raw conv output z (bf16) with the fp32 BatchNorm statistics out of the epilogue (`stats`: the partials, None
+    for none); the 1-input-channel layer reads the fp32 image and fp32 weights.  Returns the statistics rows written."""
+    gc = g.c()
+    thin = g.cin == 1
+    name = "conv_forward_f32_to_bf16" if thin else "conv_forward_bf16"
+    prog.add(name, getattr(lib(), "mpgan_" + name), C.byref(gc), x.data_ptr(), g.cin, wp.data_ptr(), bias.data_ptr(),
+             _p(stats), z.data_ptr(), g.cout, keep=(gc, x, wp, bias, z, stats), desc=_gdesc(g),
+             tag=_thin_cin1_tag(g, x) if thin else (_bf16_kernel_name(g, False), 2.0 * conv_macs(g), conv_bytes(g, 2)))
+    return (_rows(g) + 255) // 256 if thin else ops.conv_stats_rows_bf16(g)
+
+
+def emit_norm_act_bf16(prog, z, nb: NormBuf, slope: float, a, norm_mod=None, partials=None, stat_rows=0):
+    """a = LeakyReLU(z*scale + shift), stored once (bf16, or fp32 when `a` is).  norm_mod: first finalize the
+    `stat_rows` statistics rows the conv left in `partials` (train mode: running statistics updated); None: scale /
+    shift are already there (emit_eval_norms)."""
+    rows, c = z.numel() // z.shape[-1], z.shape[-1]
+    if norm_mod is not None:
+        prog.add("norm_finalize", lib().mpgan_norm_finalize, partials.data_ptr(), 1, stat_rows, c, rows, 0,
+                 _p(norm_mod.weight), _p(norm_mod.bias), float(norm_mod.eps), float(norm_mod.momentum),
+                 _p(norm_mod.running_mean), _p(norm_mod.running_var), _p(norm_mod.num_batches_tracked),
+                 nb.scale.data_ptr(), nb.shift.data_ptr(), nb.mean.data_ptr(), nb.invstd.data_ptr(),
+                 keep=(norm_mod, nb, partials))
+    prog.add("norm_act_bf16", lib().mpgan_norm_act_bf16, z.data_ptr(), c, nb.scale.data_ptr(), nb.shift.data_ptr(),
+             float(slope), rows, c, a.data_ptr(), c, int(a.dtype == torch.float32), keep=(z, nb, a))
+
+
+def emit_norm_bwd_bf16(prog, g, z, nb: NormBuf, slope: float, dz, partials, dgamma, dbeta, peer=None, reduced_rows=0,
+                       bias_part=False):
+    """emit_norm_bwd on bf16 z: reduce -> finalize -> apply, dz stored as bf16 (g: bf16 or fp32).
+    peer: ops.PeerTapsBF16 of the other pass (the `_peer` entries).  reduced_rows > 0: `partials` already holds that
+    many [3][C] rows, left by the backward-data launch that produced g (emit_conv_dgrad_bf16) -- no reduce pass.
+    bias_part: apply also leaves per-block column sums of the stored dz (the conv's bias gradient); they sit behind
+    the rows finalize reads, and their view of `partials` is returned."""
+    rows, c = z.numel() // z.shape[-1], z.shape[-1]
+    brow = ops.norm_bwd_rows_bf16(rows, c)
+    base = max(brow, reduced_rows) * 3 * c + c
+    assert partials.numel() >= base + (brow * c if bias_part else 0)
+    bias_part = partials[base:base + brow * c] if bias_part else None
+    L = lib()
+    g32 = int(g.dtype == torch.float32)
+    norm = (nb.scale.data_ptr(), nb.shift.data_ptr(), nb.mean.data_ptr(), nb.invstd.data_ptr())
+    pc = peer.c() if peer is not None else None
+    pe, sfx = ((C.byref(pc),), "_peer") if peer is not None else ((), "")
+    assert peer is None or not reduced_rows
+    if not reduced_rows:
+        prog.add("norm_bwd_reduce_bf16" + sfx, getattr(L, "mpgan_norm_bwd_reduce_bf16" + sfx), g.data_ptr(), g32, c,
+                 z.data_ptr(), c, *norm, *pe, float(slope), rows, c, partials.data_ptr(),
+                 keep=(g, z, nb, partials, peer, pc))
+    prog.add("norm_bwd_finalize", L.mpgan_norm_bwd_finalize, partials.data_ptr(), 1, reduced_rows or brow, c, rows, 0,
+             _p(dgamma), _p(dbeta), None, nb.c1.data_ptr(), nb.c2.data_ptr(), keep=(dgamma, dbeta))
+    prog.add("norm_bwd_apply_bf16" + sfx, getattr(L, "mpgan_norm_bwd_apply_bf16" + sfx), g.data_ptr(), g32, c,
+             z.data_ptr(), c, *norm, nb.c1.data_ptr(), nb.c2.data_ptr(), *pe, float(slope), rows, c, dz.data_ptr(), c,
+             _p(bias_part), keep=(g, z, nb, dz, bias_part, peer, pc))
+    return bias_part
+
+
+def emit_conv_wgrad_bf16(prog, g: ConvGeom, x, dy, dw, dbias, ws, bias_part=None):
+    """dW += wgrad on bf16 dy.  Dense layers (bf16 x): dbias += the column sums emit_norm_bwd_bf16 left in `bias_part`;
+    the 1-input-channel layer (fp32 x): the bias gradient rides along in the kernel."""
+    gc = g.c()
+    if g.cin == 1:
+        assert ws.numel() * 4 >= ops.conv_wgrad_workspace_bf16dy(g), "wgrad workspace too small"
+        prog.add("conv_backward_weight_bf16dy", lib().mpgan_conv_backward_weight_bf16dy, C.byref(gc), x.data_ptr(), 1,
+                 dy.data_ptr(), g.cout, dw.data_ptr(), dbias.data_ptr(), 1.0, ws.data_ptr(), ws.numel() * 4,
+                 keep=(gc, x, dy, dw, dbias, ws), desc=_gdesc(g),
+                 tag=(wgrad_kernel_name(g, bf16_dy=True), 2.0 * conv_macs(g), conv_bytes(g, 2) + 2 * x.numel()))
+        return
+    assert ws.numel() * 4 >= ops.conv_wgrad_workspace_bf16(g), "wgrad workspace too small"
+    prog.add("reduce_partials", lib().mpgan_reduce_partials, bias_part.data_ptr(), bias_part.numel() // g.cout, g.cout,
+             g.cout, dbias.data_ptr(), 1.0, keep=(bias_part, dbias))
+    prog.add("conv_backward_weight_bf16", lib().mpgan_conv_backward_weight_bf16, C.byref(gc), x.data_ptr(), g.cin,
+             dy.data_ptr(), g.cout, dw.data_ptr(), 1.0, ws.data_ptr(), ws.numel() * 4, keep=(gc, x, dy, dw, ws),
+             desc=_gdesc(g), tag=(_bf16_wgrad_kernel_name(g), 2.0 * conv_macs(g), conv_bytes(g, 2)))
+
+
+def bwd_stats_rows_bf16(g: ConvGeom) -> int:
+    """Rows of norm-backward sums the fused backward-data form leaves for this geometry (0: it has none)."""
+    gc = g.c()
+    return max(0, int(lib().mpgan_conv_bwd_stats_rows_bf16(C.byref(gc))))
+
+
+def emit_conv_dgrad_bf16(prog, g: ConvGeom, dy, wp_bwd, dx, stats=None) -> int:
+    """Backward-data on bf16 dy; dx is bf16, or fp32 for the 1-input-channel layer (fp32 weights).
+    stats = (z, nb, slope, partials) of the layer in front: where this geometry has the fused form, the epilogue also
+    leaves that layer's norm-backward sums of dx against z in `partials` -- returns their number of rows, else 0 (the
+    caller runs the reduce pass)."""
+    gc = g.c()
+    thin = g.cin == 1
+    tag = None if thin else ("dgrad:" + _bf16_kernel_name(g, True), 2.0 * conv_macs(g), conv_bytes(g, 2))
+    rows = bwd_stats_rows_bf16(g) if stats is not None and not thin else 0
+    if not rows:
+        name = "conv_backward_data_bf16_to_f32" if thin else "conv_backward_data_bf16"
+        prog.add(name, getattr(lib(), "mpgan_" + name), C.byref(gc), dy.data_ptr(), g.cout, wp_bwd.data_ptr(),
+                 dx.data_ptr(), g.cin, keep=(gc, dy, wp_bwd, dx), desc=_gdesc(g), tag=tag)
+        return 0
+    z, nb, slope, partials = stats
+    assert partials.numel() >= rows * 3 * g.cin
+    prog.add("conv_backward_data_bf16", lib().mpgan_conv_backward_data_stats_bf16, C.byref(gc), dy.data_ptr(), g.cout,
+             wp_bwd.data_ptr(), dx.data_ptr(), g.cin, z.data_ptr(), g.cin, nb.scale.data_ptr(), nb.shift.data_ptr(),
+             nb.mean.data_ptr(), nb.invstd.data_ptr(), float(slope), partials.data_ptr(),
+             keep=(gc, dy, wp_bwd, dx, z, nb, partials), desc=_gdesc(g), tag=tag)
+    return rows
+
+
 def _t3(v, dims, fill):
     v = (v,) * dims if isinstance(v, int) else tuple(v)
     return (fill,) * (3 - dims) + tuple(v)
@@ -910,6 +1067,17 @@ class Scratch:
         # fused-statistics partial rows of the forward conv (with or without prologue: same count)
         rows = max(ops.conv_stats_rows(g, code) for code in (0, 1, 2))
         self.partials_need = max(self.partials_need, (rows + 32) * 2 * g.cout)   # + finalize's fold scratch
+
+    def want_bf16_layer(self, g: ConvGeom, fused_rows=0):
+        """One conv -> BN layer in bf16 storage: the forward's statistics rows (+ finalize's fold scratch), the norm
+        backward's [3][C] rows (`fused_rows`: those the next layer's backward-data launch leaves instead, if more) +
+        one vector + the bias partials behind them (emit_norm_bwd_bf16), and the weight gradient's workspace."""
+        c, rows = g.cout, _rows(g)
+        fwd_rows = (rows + 255) // 256 if g.cin == 1 else ops.conv_stats_rows_bf16(g)
+        bwd_rows = max(ops.norm_bwd_rows_bf16(rows, c), fused_rows)
+        self.partials_need = max(self.partials_need, (fwd_rows + 32) * 2 * c, (bwd_rows * 4 + 1) * c)
+        ws = ops.conv_wgrad_workspace_bf16dy(g) if g.cin == 1 else ops.conv_wgrad_workspace_bf16(g)
+        self.ws_need = max(self.ws_need, ws // 4)
 
     def alloc(self):
         self.partials = torch.empty(max(self.partials_need, 4), device=self.dev)
@@ -1452,10 +1620,7 @@ class DiscPlan:
                 raise ValueError(f"discriminator input {spatial} too small")
             zs.append(E(n, *size, cv.out_channels))
             nbs.append(NormBuf(n, cv.out_channels, False, dev))
-            taps = 1
-            for k in cv.kernel_size:
-                taps *= k
-            recs.append(store.register_conv(cv, cout=cv.out_channels, cin=cv.in_channels, taps=taps))
+            recs.append(store.register_conv(cv, cout=cv.out_channels, cin=cv.in_channels, taps=math.prod(cv.kernel_size)))
             if not training:       # no statistics partials, no weight-gradient workspace
                 continue
             scratch.want_partials(n, size[0] * size[1] * size[2], cv.out_channels)
@@ -1540,17 +1705,62 @@ class DiscPlan:
 # --------------------------------------------------------------------------
 # discriminator (variant A), bf16 storage (BASELINE config C5)
 # --------------------------------------------------------------------------
-def _bf16_kernel_name(g: ConvGeom, backward_data: bool) -> str:
-    """rocprofv3's name of the bf16 kernel that serves this layer (labels of bench.py's probe), from the same choice
-    the launch makes (mpgan_conv_kernel_name_bf16; the forward is the one with statistics)."""
-    gc = g.c()
-    return kernel_label(lib().mpgan_conv_kernel_name_bf16, C.byref(gc), int(backward_data))
+class ConvStackBF16:
+    """The four conv -> BN -> LeakyReLU(0.2) layers of a discriminator in bf16 storage, as the plans of
+    both variants hold them: geometries, weight records and bf16 packs, norm vectors, the raw conv outputs z_i (bf16;
+    none where `raw_z` is off: the fused eval program) and the activations a_i (bf16; fp32 for the last layer, which
+    the fp32 head reads)."""
 
+    def __init__(self, disc, store: ParamStore, n: int, dhw, dims: int, *, raw_z: bool, what: str):
+        dev = store.flat.device
+        self.convs = [disc.model_conv[i] for i in (0, 3, 6, 9)]
+        self.bns = [disc.model_conv[i] for i in (1, 4, 7, 10)]
+        self.geoms, self.zs, self.acts, self.nbs, self.recs = [], [], [], [], []
+        size = dhw
+        for i, cv in enumerate(self.convs):
+            g = conv_geom_of(cv, n, size, dims)
+            self.geoms.append(g)
+            size, c = g.out_dhw, cv.out_channels
+            if min(size) < 1:
+                raise ValueError(f"{what} too small")
+            if raw_z:
+                self.zs.append(torch.empty(n, *size, c, device=dev, dtype=torch.bfloat16))
+            self.acts.append(torch.empty(n, *size, c, device=dev, dtype=torch.float32 if i == 3 else torch.bfloat16))
+            self.nbs.append(NormBuf(n, c, False, dev))
+            self.recs.append(store.register_conv(cv, cout=c, cin=cv.in_channels, taps=math.prod(cv.kernel_size)))
+        self.packs = PacksBF16(self.recs[1:], dev)
 
-def _bf16_wgrad_kernel_name(g: ConvGeom) -> str:
-    """rocprofv3's name of the bf16 weight-gradient kernel of this layer, asked of the library that makes the choice."""
-    gc = g.c()
-    return "wgrad_bf16_wide_kernel" if lib().mpgan_conv_wgrad_variant_bf16(C.byref(gc)) == 1 else "wgrad_bf16_kernel<8>"
+    def alloc_grads(self, disc):
+        """(gas, dzs): the gradients w.r.t. the activations (bf16; fp32 for a_3, which the fp32 head writes) and the
+        dz the BatchNorm backward makes of them -- in place, but for the last layer's bf16 dz and under
+        disc.debug_keep_intermediates (separate dz buffers, so that tests can check every layer of the backward
+        against the CPU restatement on the SAME inputs)."""
+        gas = [torch.empty_like(z) for z in self.zs[:3]] + [torch.empty_like(self.acts[3])]
+        keep_all = bool(getattr(disc, "debug_keep_intermediates", False))
+        return gas, [torch.empty_like(z) if keep_all or i == 3 else gas[i] for i, z in enumerate(self.zs)]
+
+    def emit_forward(self, prog, store: ParamStore, x, partials, training: bool):
+        """The bf16 weight packs, then x -> a_3.  Training: statistics out of each conv, finalize, norm_act_bf16; eval
+        with raw z: scale / shift of every layer from the running statistics in one launch up front instead; eval
+        without: each a_i straight from its conv's epilogue."""
+        dev = x.device
+        self.packs.emit(prog, store)
+        wp = lambda i: store.wp(self.recs[0]) if i == 0 else self.packs.fwd(self.recs[i])
+        if not self.zs:
+            leaky, rows, body = _ConstSlope(0.2, dev), [], Program()
+            for i, cv in enumerate(self.convs):
+                emit_conv_fwd_act_bf16(body, rows, self.geoms[i], x, wp(i), cv.bias, self.acts[i], self.bns[i], leaky)
+                x = self.acts[i]
+            emit_epi_vectors(prog, rows, dev)
+            prog.extend(body)
+            return
+        if not training:
+            emit_eval_norms(prog, [(bn, nb, g.cout) for bn, nb, g in zip(self.bns, self.nbs, self.geoms)], dev)
+        for i, cv in enumerate(self.convs):
+            rows = emit_conv_fwd_bf16(prog, self.geoms[i], x, wp(i), cv.bias, self.zs[i], partials if training else None)
+            emit_norm_act_bf16(prog, self.zs[i], self.nbs[i], 0.2, self.acts[i], self.bns[i] if training else None,
+                               partials, rows)
+            x = self.acts[i]
 
 
 class DiscPlanBF16:
@@ -1571,118 +1781,31 @@ class DiscPlanBF16:
         self.n, self.dhw, self.dims, self.store = n, dhw, dims, store
         self.training = training
         assert training or not want_backward, "eval plans are forward-only"
-        bf = torch.bfloat16
         E = lambda *shape: torch.empty(*shape, device=dev)
-        H = lambda *shape: torch.empty(*shape, device=dev, dtype=bf)
-        convs = [disc.model_conv[i] for i in (0, 3, 6, 9)]
-        bns = [disc.model_conv[i] for i in (1, 4, 7, 10)]
         lin = disc.model_linear[1]
         self.x_in = E(n, *dhw, 1)
-        geoms, zs, acts, nbs, recs = [], [], [], [], []
-        size = dhw
-        L = lib()
-        part_need, ws_need = 4, 4
-        fused_rows, prev_bwd_rows = [], 0
-        for i, cv in enumerate(convs):
-            g = conv_geom_of(cv, n, size, dims)
-            geoms.append(g)
-            size = g.out_dhw
-            if min(size) < 1:
-                raise ValueError(f"discriminator input {spatial} too small")
-            if training:
-                zs.append(H(n, *size, cv.out_channels))
-            acts.append(E(n, *size, cv.out_channels) if i == 3 else H(n, *size, cv.out_channels))
-            nbs.append(NormBuf(n, cv.out_channels, False, dev))
-            taps = 1
-            for k in cv.kernel_size:
-                taps *= k
-            recs.append(store.register_conv(cv, cout=cv.out_channels, cin=cv.in_channels, taps=taps))
-            if not training:       # no raw outputs, statistics partials or weight-gradient workspace
-                continue
-            rows_total = n * size[0] * size[1] * size[2]
-            fwd_rows = (rows_total + 255) // 256 if i == 0 else ops.conv_stats_rows_bf16(g)
-            bwd_rows = ops.norm_bwd_rows_bf16(rows_total, cv.out_channels)
+        st = ConvStackBF16(disc, store, n, dhw, dims, raw_z=training, what=f"discriminator input {spatial}")
+        convs, bns, geoms, zs, acts, nbs, recs = st.convs, st.bns, st.geoms, st.zs, st.acts, st.nbs, st.recs
+        self.geoms, self.zs, self.acts, self.nbs, self.recs = geoms, zs, acts, nbs, recs
+        scratch = Scratch(dev)
+        for i, g in enumerate(geoms if training else ()):
             # (rows of the fused norm-backward sums the NEXT layer's backward-data launch leaves for this layer's norm)
-            fused_rows.append(0)
-            if i > 0 and _FUSE_BWD_STATS_BF16:
-                fused_rows[i - 1] = max(0, int(lib().mpgan_conv_bwd_stats_rows_bf16(C.byref(g.c()))))
-                part_need = max(part_need, (max(fused_rows[i - 1], prev_bwd_rows) * 4 + 1) * cv.in_channels)
-            prev_bwd_rows = bwd_rows
-            part_need = max(part_need, (fwd_rows + 32) * 2 * cv.out_channels, bwd_rows * 4 * cv.out_channels + cv.out_channels)
-            ws_need = max(ws_need, (ops.conv_wgrad_workspace_bf16dy(g) if i == 0 else ops.conv_wgrad_workspace_bf16(g)) // 4)
-        P_last = size[0] * size[1] * size[2]
-        c_last = convs[-1].out_channels
+            scratch.want_bf16_layer(g, bwd_stats_rows_bf16(geoms[i + 1]) if _FUSE_BWD_STATS_BF16 and i < 3 else 0)
+        scratch.alloc()
+        part, ws = scratch.partials, scratch.ws
+        P_last, c_last = math.prod(geoms[-1].out_dhw), convs[-1].out_channels
         if lin.in_features != P_last * c_last:
             raise ValueError(f"Linear.in_features {lin.in_features} != {c_last}*{P_last} for input {spatial}")
         rlin = store.register_conv(lin, cout=1, cin=c_last, taps=P_last)
-        part = E(part_need)
-        ws = E(ws_need)
-        # bf16 packs of the three dense layers: [Cout][tap][Cin] (forward) and [Cin][tap][Cout] (backward-data)
-        rows16, off = [], 0
-        self._w16 = {}
-        for i in (1, 2, 3):
-            r = recs[i]
-            nel = r.cout * r.cin * r.taps
-            self._w16[i] = (off, off + (nel + 7) // 8 * 8, nel)
-            rows16.append([r.w_off, off, r.cout, r.cin, r.taps, 0, 0, 0])
-            rows16.append([r.w_off, off + (nel + 7) // 8 * 8, r.cout, r.cin, r.taps, 0, 1, 0])
-            off += 2 * ((nel + 7) // 8 * 8)
-        packed16 = torch.empty(off, device=dev, dtype=bf)
-        table16 = torch.tensor(rows16, dtype=torch.int64, device=dev)
-        w16 = lambda i: packed16[self._w16[i][0]:self._w16[i][0] + self._w16[i][2]]
-        w16b = lambda i: packed16[self._w16[i][1]:self._w16[i][1] + self._w16[i][2]]
         self.logit, self.prob = E(n), E(n)
         lin_part = E(ops.linear1_partials(n))
+        L = lib()
         f = self.fwd = Program()
         store.emit_pack(f)                                   # fp32 packs: first layer, Linear head
-        f.add("pack_weights_bf16", L.mpgan_pack_weights_bf16, store.flat.data_ptr(), packed16.data_ptr(),
-              table16.data_ptr(), table16.shape[0], max(r.cout * r.cin * r.taps for r in recs[1:]),
-              keep=(packed16, table16))
-        src = self.x_in
-        if not training:
-            leaky, rows, body = _ConstSlope(0.2, dev), [], Program()
-            for i, cv in enumerate(convs):
-                emit_conv_fwd_act_bf16(body, rows, geoms[i], src, store.wp(recs[0]) if i == 0 else w16(i), cv.bias,
-                                       acts[i], bns[i], leaky)
-                src = acts[i]
-            emit_epi_vectors(f, rows, dev)
-            f.extend(body)
-            f.add("linear1_forward", L.mpgan_linear1_forward, acts[3].data_ptr(), None, n, P_last, c_last,
-                  store.wp(rlin).data_ptr(), lin.bias.data_ptr(), lin_part.data_ptr(), self.logit.data_ptr(),
-                  self.prob.data_ptr(), keep=(lin_part, acts))
-            self.zs, self.acts, self.nbs = zs, acts, nbs
-            self.busy = False
-            self.bwd = Program()
-            self.g_x = None
-            return
-        for i, cv in enumerate(convs):
-            g, z, nb, bn = geoms[i], zs[i], nbs[i], bns[i]
-            gc = g.c()
-            rows_total = n * g.out_dhw[0] * g.out_dhw[1] * g.out_dhw[2]
-            if i == 0:
-                rows = (rows_total + 255) // 256
-                f.add("conv_forward_f32_to_bf16", L.mpgan_conv_forward_f32_to_bf16, C.byref(gc), src.data_ptr(), 1,
-                      store.wp(recs[0]).data_ptr(), cv.bias.data_ptr(), part.data_ptr(), z.data_ptr(), g.cout,
-                      keep=(gc, src, z, part), desc=_gdesc(g), tag=("thin_cin1_full_kernel<16, true>", 2.0 * conv_macs(g),
-                           conv_bytes(g, 2) + 2 * src.numel()))
-            else:
-                rows = ops.conv_stats_rows_bf16(g)
-                f.add("conv_forward_bf16", L.mpgan_conv_forward_bf16, C.byref(gc), src.data_ptr(), g.cin,
-                      w16(i).data_ptr(), cv.bias.data_ptr(), part.data_ptr(), z.data_ptr(), g.cout,
-                      keep=(gc, src, z, part), desc=_gdesc(g),
-                      tag=(_bf16_kernel_name(g, False), 2.0 * conv_macs(g), conv_bytes(g, 2)))
-            f.add("norm_finalize", L.mpgan_norm_finalize, part.data_ptr(), 1, rows, g.cout, rows_total, 0,
-                  _p(bn.weight), _p(bn.bias), float(bn.eps), float(bn.momentum), _p(bn.running_mean),
-                  _p(bn.running_var), _p(bn.num_batches_tracked), nb.scale.data_ptr(), nb.shift.data_ptr(),
-                  nb.mean.data_ptr(), nb.invstd.data_ptr(), keep=(bn, nb))
-            a = acts[i]
-            f.add("norm_act_bf16", L.mpgan_norm_act_bf16, z.data_ptr(), g.cout, nb.scale.data_ptr(), nb.shift.data_ptr(),
-                  0.2, rows_total, g.cout, a.data_ptr(), g.cout, int(a.dtype == torch.float32), keep=(a,))
-            src = a
+        st.emit_forward(f, store, self.x_in, part, training)
         f.add("linear1_forward", L.mpgan_linear1_forward, acts[3].data_ptr(), None, n, P_last, c_last,
               store.wp(rlin).data_ptr(), lin.bias.data_ptr(), lin_part.data_ptr(), self.logit.data_ptr(),
-              self.prob.data_ptr(), keep=(lin_part,))
-        self.zs, self.acts, self.nbs = zs, acts, nbs
+              self.prob.data_ptr(), keep=(lin_part, st))
         self.busy = False
         self.bwd = Program()
         self.g_x = None
@@ -1692,70 +1815,28 @@ class DiscPlanBF16:
         gv = store.grad_view if want_param_grads else (lambda p: None)
         self.g_prob = E(n)
         dlogit = E(n)
-        # gradients w.r.t. the activations; the BatchNorm backward overwrites them in place with dz
-        # (disc.debug_keep_intermediates: separate dz buffers, so that tests can check every layer of the backward
-        #  against the CPU restatement on the SAME inputs)
-        gas = [H(*z.shape) for z in zs[:3]] + [E(*zs[3].shape)]
-        dz4 = H(*zs[3].shape)
-        keep_all = bool(getattr(disc, "debug_keep_intermediates", False))
-        self.dzs = [H(*z.shape) for z in zs[:3]] + [dz4] if keep_all else [gas[0], gas[1], gas[2], dz4]
-        self.gas = gas
+        self.gas, self.dzs = st.alloc_grads(disc)
+        gas = self.gas
         b.add("sigmoid_backward", L.mpgan_sigmoid_backward, self.g_prob.data_ptr(), self.prob.data_ptr(), n,
               dlogit.data_ptr(), keep=(dlogit,))
         b.add("linear1_backward", L.mpgan_linear1_backward, acts[3].data_ptr(), None, n, P_last, c_last,
               store.wp(rlin).data_ptr(), dlogit.data_ptr(), gas[3].data_ptr(), _p(gv(lin.weight)), _p(gv(lin.bias)),
-              1.0, keep=(gas, dz4))
+              1.0, keep=(gas, self.dzs))
+        reduced = 0                                  # rows the previous backward-data launch left in `part`
         for i in range(3, -1, -1):
-            g, z, nb, bn, cv = geoms[i], zs[i], nbs[i], bns[i], convs[i]
-            gc = g.c()
-            c = g.cout
-            rows_total = n * g.out_dhw[0] * g.out_dhw[1] * g.out_dhw[2]
-            brow = ops.norm_bwd_rows_bf16(rows_total, c)
-            gin = gas[i]
             dz = self.dzs[i]
-            g32 = int(gin.dtype == torch.float32)
-            frow = fused_rows[i] if i < 3 else 0          # > 0: the backward-data launch that produced `gin` left the sums
-            base = max(brow, frow) * 3 * c + c            # the apply pass's bias partials sit behind the rows finalize reads
-            bias_part = part[base:base + brow * c] if (want_param_grads and i > 0) else None
-            if not frow:
-                b.add("norm_bwd_reduce_bf16", L.mpgan_norm_bwd_reduce_bf16, gin.data_ptr(), g32, c, z.data_ptr(), c,
-                      nb.scale.data_ptr(), nb.shift.data_ptr(), nb.mean.data_ptr(), nb.invstd.data_ptr(), 0.2, rows_total,
-                      c, part.data_ptr(), keep=(gin, z, nb, part))
-            b.add("norm_bwd_finalize", L.mpgan_norm_bwd_finalize, part.data_ptr(), 1, frow or brow, c, rows_total, 0,
-                  _p(gv(bn.weight)), _p(gv(bn.bias)), None, nb.c1.data_ptr(), nb.c2.data_ptr(), keep=(bn,))
-            b.add("norm_bwd_apply_bf16", L.mpgan_norm_bwd_apply_bf16, gin.data_ptr(), g32, c, z.data_ptr(), c,
-                  nb.scale.data_ptr(), nb.shift.data_ptr(), nb.mean.data_ptr(), nb.invstd.data_ptr(),
-                  nb.c1.data_ptr(), nb.c2.data_ptr(), 0.2, rows_total, c, dz.data_ptr(), c, _p(bias_part), keep=(dz,))
+            bias_part = emit_norm_bwd_bf16(b, gas[i], zs[i], nbs[i], 0.2, dz, part, gv(bns[i].weight), gv(bns[i].bias),
+                                           reduced_rows=reduced, bias_part=want_param_grads and i > 0)
             if want_param_grads:
-                if i > 0:
-                    b.add("reduce_partials", L.mpgan_reduce_partials, bias_part.data_ptr(), brow, c, c,
-                          gv(cv.bias).data_ptr(), 1.0, keep=(bias_part,))
-                    b.add("conv_backward_weight_bf16", L.mpgan_conv_backward_weight_bf16, C.byref(gc),
-                          acts[i - 1].data_ptr(), g.cin, dz.data_ptr(), c, gv(cv.weight).data_ptr(), 1.0,
-                          ws.data_ptr(), ws.numel() * 4, keep=(gc, ws), desc=_gdesc(g),
-                          tag=(_bf16_wgrad_kernel_name(g), 2.0 * conv_macs(g), conv_bytes(g, 2)))
-                else:
-                    b.add("conv_backward_weight_bf16dy", L.mpgan_conv_backward_weight_bf16dy, C.byref(gc),
-                          self.x_in.data_ptr(), 1, dz.data_ptr(), c, gv(cv.weight).data_ptr(), gv(cv.bias).data_ptr(),
-                          1.0, ws.data_ptr(), ws.numel() * 4, keep=(gc, ws), desc=_gdesc(g),
-                          tag=(wgrad_kernel_name(g, bf16_dy=True), 2.0 * conv_macs(g),
-                               conv_bytes(g, 2) + 2 * self.x_in.numel()))
-            if i > 0 and fused_rows[i - 1]:
-                # ... and the reduce pass of the layer in front (its norm-backward sums against z_{i-1}) in the same launch
-                zp, nbp = zs[i - 1], nbs[i - 1]
-                b.add("conv_backward_data_bf16", L.mpgan_conv_backward_data_stats_bf16, C.byref(gc), dz.data_ptr(), c,
-                      w16b(i).data_ptr(), gas[i - 1].data_ptr(), g.cin, zp.data_ptr(), g.cin, nbp.scale.data_ptr(),
-                      nbp.shift.data_ptr(), nbp.mean.data_ptr(), nbp.invstd.data_ptr(), 0.2, part.data_ptr(),
-                      keep=(gc, zp, nbp), desc=_gdesc(g),
-                      tag=("dgrad:" + _bf16_kernel_name(g, True), 2.0 * conv_macs(g), conv_bytes(g, 2)))
-            elif i > 0:
-                b.add("conv_backward_data_bf16", L.mpgan_conv_backward_data_bf16, C.byref(gc), dz.data_ptr(), c,
-                      w16b(i).data_ptr(), gas[i - 1].data_ptr(), g.cin, keep=(gc,), desc=_gdesc(g),
-                      tag=("dgrad:" + _bf16_kernel_name(g, True), 2.0 * conv_macs(g), conv_bytes(g, 2)))
+                emit_conv_wgrad_bf16(b, geoms[i], acts[i - 1] if i > 0 else self.x_in, dz, gv(convs[i].weight),
+                                     gv(convs[i].bias), ws, bias_part)
+            if i > 0:
+                # (MPGAN_FUSE_BWD_STATS_BF16: ... and the reduce pass of the layer in front in the same launch)
+                reduced = emit_conv_dgrad_bf16(b, geoms[i], dz, st.packs.bwd(recs[i]), gas[i - 1],
+                                               stats=(zs[i - 1], nbs[i - 1], 0.2, part) if _FUSE_BWD_STATS_BF16 else None)
             elif want_input_grad:
                 self.g_x = E(n, *dhw, 1)
-                b.add("conv_backward_data_bf16_to_f32", L.mpgan_conv_backward_data_bf16_to_f32, C.byref(gc), dz.data_ptr(),
-                      c, store.wp_bwd(recs[0]).data_ptr(), self.g_x.data_ptr(), 1, keep=(gc, self.g_x), desc=_gdesc(g))
+                emit_conv_dgrad_bf16(b, geoms[0], dz, store.wp_bwd(recs[0]), self.g_x)
 
 
 # --------------------------------------------------------------------------
@@ -1800,7 +1881,7 @@ class PatchDiscPlan:
             self.zs.append(E(n, *size, cv.out_channels))
             self.nbs.append(NormBuf(n, cv.out_channels, False, dev))
             self.recs.append(store.register_conv(cv, cout=cv.out_channels, cin=cv.in_channels,
-                                                 taps=int(torch.tensor(cv.kernel_size).prod())))
+                                                 taps=math.prod(cv.kernel_size)))
             if training:
                 scratch.want_partials(n, size[0] * size[1] * size[2], cv.out_channels)
                 scratch.want_ws(g)
@@ -2061,41 +2142,18 @@ class PatchDiscPlanBF16(PatchDiscPlan):
         self.want_input_grad, self.want_param_grads = want_input_grad, want_param_grads
         self.training, self.keep_taps = training, keep_taps
         assert training or not want_backward, "eval plans are forward-only"
-        fused_eval = not training and not keep_taps
-        bf = torch.bfloat16
         E = lambda *shape: torch.empty(*shape, device=dev)
-        H = lambda *shape: torch.empty(*shape, device=dev, dtype=bf)
-        convs = [disc.model_conv[i] for i in (0, 3, 6, 9)]
-        bns = [disc.model_conv[i] for i in (1, 4, 7, 10)]
         lin1, lin2 = disc.model_linear[1], disc.model_linear[2]
-        self.convs, self.bns, self.lin1, self.lin2 = convs, bns, lin1, lin2
         self.x_in = E(n, *dhw, 1)
-        self.geoms, self.zs, self.acts, self.nbs, self.recs = [], [], [], [], []
-        size = dhw
+        st = self.stack = ConvStackBF16(disc, store, n, dhw, dims, raw_z=training or keep_taps,
+                                        what=f"patch discriminator input {spatial}")
+        self.convs, self.bns, self.lin1, self.lin2 = st.convs, st.bns, lin1, lin2
+        self.geoms, self.zs, self.acts, self.nbs, self.recs = st.geoms, st.zs, st.acts, st.nbs, st.recs
         scratch = Scratch(dev)
-        for i, cv in enumerate(convs):
-            g = conv_geom_of(cv, n, size, dims)
-            self.geoms.append(g)
-            size = g.out_dhw
-            if min(size) < 1:
-                raise ValueError(f"patch discriminator input {spatial} too small")
-            c = cv.out_channels
-            if not fused_eval:
-                self.zs.append(H(n, *size, c))
-            self.acts.append(E(n, *size, c) if i == 3 else H(n, *size, c))
-            self.nbs.append(NormBuf(n, c, False, dev))
-            self.recs.append(store.register_conv(cv, cout=c, cin=cv.in_channels,
-                                                 taps=int(torch.tensor(cv.kernel_size).prod())))
-            if not training:       # no statistics partials, no weight-gradient workspace
-                continue
-            rows_total = n * size[0] * size[1] * size[2]
-            fwd_rows = (rows_total + 255) // 256 if i == 0 else ops.conv_stats_rows_bf16(g)
-            bwd_rows = ops.norm_bwd_rows_bf16(rows_total, c)
-            scratch.partials_need = max(scratch.partials_need, (fwd_rows + 32) * 2 * c, bwd_rows * 4 * c + c)
-            ws = ops.conv_wgrad_workspace_bf16dy(g) if i == 0 else ops.conv_wgrad_workspace_bf16(g)
-            scratch.ws_need = max(scratch.ws_need, ws // 4)
-        c_last = convs[-1].out_channels
-        P_last = size[0] * size[1] * size[2]
+        for g in (self.geoms if training else ()):
+            scratch.want_bf16_layer(g)
+        size, c_last = self.geoms[-1].out_dhw, self.convs[-1].out_channels
+        P_last = math.prod(size)
         if lin1.in_features != P_last * c_last:
             raise ValueError(f"Linear.in_features {lin1.in_features} != {c_last}*{P_last} for patches {spatial}")
         # the fp32 head of PatchDiscPlan, reading the fp32 a_3 instead of z_3 through a prologue
@@ -2109,65 +2167,13 @@ class PatchDiscPlanBF16(PatchDiscPlan):
             scratch.want_ws(self.g_l2)
         scratch.alloc()
         self.scratch = scratch
-        part = scratch.partials
-        # bf16 packs of the three dense layers: [Cout][tap][Cin] (forward) and [Cin][tap][Cout] (backward-data)
-        rows16, off = [], 0
-        self._w16 = {}
-        for i in (1, 2, 3):
-            r = self.recs[i]
-            nel = r.cout * r.cin * r.taps
-            self._w16[i] = (off, off + (nel + 7) // 8 * 8, nel)
-            rows16.append([r.w_off, off, r.cout, r.cin, r.taps, 0, 0, 0])
-            rows16.append([r.w_off, off + (nel + 7) // 8 * 8, r.cout, r.cin, r.taps, 0, 1, 0])
-            off += 2 * ((nel + 7) // 8 * 8)
-        self.packed16 = torch.empty(off, device=dev, dtype=bf)
-        table16 = torch.tensor(rows16, dtype=torch.int64, device=dev)
         self.h = E(n, 1, 1, 1, lin1.out_features)
         self.logit, self.prob = E(n, 1, 1, 1, 1), E(n)
         self.splitk_ws = E(max(ops.conv_splitk_workspace(self.g_l1) // 4, 4))
         L = lib()
         f = self.fwd = Program()
         store.emit_pack(f)                                   # fp32 packs: first layer, the two Linear layers
-        f.add("pack_weights_bf16", L.mpgan_pack_weights_bf16, store.flat.data_ptr(), self.packed16.data_ptr(),
-              table16.data_ptr(), table16.shape[0], max(r.cout * r.cin * r.taps for r in self.recs[1:]),
-              keep=(self.packed16, table16))
-        src = self.x_in
-        if fused_eval:
-            leaky, erows, body = _ConstSlope(0.2, dev), [], Program()
-            for i, cv in enumerate(convs):
-                emit_conv_fwd_act_bf16(body, erows, self.geoms[i], src, store.wp(self.recs[0]) if i == 0 else self._wf16(i),
-                                       cv.bias, self.acts[i], bns[i], leaky)
-                src = self.acts[i]
-            emit_epi_vectors(f, erows, dev)
-            f.extend(body)
-        elif not training:
-            # every layer's scale / shift depend on parameters and running statistics only: one launch up front
-            emit_eval_norms(f, [(bns[i], self.nbs[i], self.geoms[i].cout) for i in range(len(convs))], dev)
-        for i, cv in enumerate(convs if not fused_eval else ()):
-            g, z, nb, bn, a = self.geoms[i], self.zs[i], self.nbs[i], bns[i], self.acts[i]
-            gc = g.c()
-            rows_total = n * g.out_dhw[0] * g.out_dhw[1] * g.out_dhw[2]
-            stats = part.data_ptr() if training else None
-            if i == 0:
-                rows = (rows_total + 255) // 256
-                f.add("conv_forward_f32_to_bf16", L.mpgan_conv_forward_f32_to_bf16, C.byref(gc), src.data_ptr(), 1,
-                      store.wp(self.recs[0]).data_ptr(), cv.bias.data_ptr(), stats, z.data_ptr(), g.cout,
-                      keep=(gc, src, z, part), desc=_gdesc(g), tag=("thin_cin1_full_kernel<16, true>",
-                                                                     2.0 * conv_macs(g), conv_bytes(g, 2) + 2 * src.numel()))
-            else:
-                rows = ops.conv_stats_rows_bf16(g)
-                f.add("conv_forward_bf16", L.mpgan_conv_forward_bf16, C.byref(gc), src.data_ptr(), g.cin,
-                      self._wf16(i).data_ptr(), cv.bias.data_ptr(), stats, z.data_ptr(), g.cout,
-                      keep=(gc, src, z, part), desc=_gdesc(g),
-                      tag=(_bf16_kernel_name(g, False), 2.0 * conv_macs(g), conv_bytes(g, 2)))
-            if training:
-                f.add("norm_finalize", L.mpgan_norm_finalize, part.data_ptr(), 1, rows, g.cout, rows_total, 0,
-                      _p(bn.weight), _p(bn.bias), float(bn.eps), float(bn.momentum), _p(bn.running_mean),
-                      _p(bn.running_var), _p(bn.num_batches_tracked), nb.scale.data_ptr(), nb.shift.data_ptr(),
-                      nb.mean.data_ptr(), nb.invstd.data_ptr(), keep=(bn, nb))
-            f.add("norm_act_bf16", L.mpgan_norm_act_bf16, z.data_ptr(), g.cout, nb.scale.data_ptr(), nb.shift.data_ptr(),
-                  0.2, rows_total, g.cout, a.data_ptr(), g.cout, int(a.dtype == torch.float32), keep=(a,))
-            src = a
+        st.emit_forward(f, store, self.x_in, scratch.partials, training)
         gc1 = self.g_l1.c()
         a3 = self.acts[3]
         f.add("conv_forward_splitk", L.mpgan_conv_forward_splitk, C.byref(gc1), a3.data_ptr(), _ld(a3),
@@ -2183,23 +2189,10 @@ class PatchDiscPlanBF16(PatchDiscPlan):
             self._perc_weights(dev)
         if not want_backward:
             return
-        # gradients w.r.t. the activations (bf16; fp32 for a_3, written by the head's GEMM); the BatchNorm backward
-        # overwrites them in place with dz (disc.debug_keep_intermediates: separate dz buffers, for the tests)
-        self.gas = [H(*z.shape) for z in self.zs[:3]] + [E(*self.zs[3].shape)]
-        dz3 = H(*self.zs[3].shape)
-        keep_all = bool(getattr(disc, "debug_keep_intermediates", False))
-        self.dzs = [H(*z.shape) for z in self.zs[:3]] + [dz3] if keep_all else self.gas[:3] + [dz3]
+        self.gas, self.dzs = st.alloc_grads(disc)
         self._tap_buffers(dev)
         if want_input_grad:
             self.g_x = E(n, *dhw, 1)
-
-    def _wf16(self, i):
-        o, _, nel = self._w16[i]
-        return self.packed16[o:o + nel]
-
-    def _wb16(self, i):
-        _, o, nel = self._w16[i]
-        return self.packed16[o:o + nel]
 
     def backward_program(self, peer: Optional["PatchDiscPlanBF16"]) -> Program:
         key = id(peer) if peer is not None else 0
@@ -2224,57 +2217,18 @@ class PatchDiscPlanBF16(PatchDiscPlan):
             emit_conv_wgrad(b, self.g_l1, self.acts[3], self.dh, gv(self.lin1.weight), ws, dbias=gv(self.lin1.bias))
         emit_conv_fwd(b, self.g_l1_bwd, self.dh, store.wp_tco(self.r_l1), None, self.gas[3].view(n, 1, 1, 1, -1))
         for i in range(len(self.convs) - 1, -1, -1):
-            g, z, nb, bn, cv = self.geoms[i], self.zs[i], self.nbs[i], self.bns[i], self.convs[i]
-            gc = g.c()
-            c = g.cout
-            rows_total = n * g.out_dhw[0] * g.out_dhw[1] * g.out_dhw[2]
-            brow = ops.norm_bwd_rows_bf16(rows_total, c)
-            gin, dz = self.gas[i], self.dzs[i]
-            g32 = int(gin.dtype == torch.float32)
-            base = brow * 3 * c + c                   # the apply pass's bias partials sit behind the rows finalize reads
-            bias_part = part[base:base + brow * c] if (self.want_param_grads and i > 0) else None
-            norm = (nb.scale.data_ptr(), nb.shift.data_ptr(), nb.mean.data_ptr(), nb.invstd.data_ptr())
-            if peer is None:
-                b.add("norm_bwd_reduce_bf16", L.mpgan_norm_bwd_reduce_bf16, gin.data_ptr(), g32, c, z.data_ptr(), c,
-                      *norm, 0.2, rows_total, c, part.data_ptr(), keep=(gin, z, nb, part))
-            else:
-                pt = ops.PeerTapsBF16(peer.zs[i], peer.nbs[i].scale, peer.nbs[i].shift, self.coef[i])
-                pc = pt.c()
-                b.add("norm_bwd_reduce_bf16_peer", L.mpgan_norm_bwd_reduce_bf16_peer, gin.data_ptr(), g32, c,
-                      z.data_ptr(), c, *norm, C.byref(pc), 0.2, rows_total, c, part.data_ptr(),
-                      keep=(gin, z, nb, part, pt, pc))
-            b.add("norm_bwd_finalize", L.mpgan_norm_bwd_finalize, part.data_ptr(), 1, brow, c, rows_total, 0,
-                  _p(gv(bn.weight)), _p(gv(bn.bias)), None, nb.c1.data_ptr(), nb.c2.data_ptr(), keep=(bn,))
-            if peer is None:
-                b.add("norm_bwd_apply_bf16", L.mpgan_norm_bwd_apply_bf16, gin.data_ptr(), g32, c, z.data_ptr(), c,
-                      *norm, nb.c1.data_ptr(), nb.c2.data_ptr(), 0.2, rows_total, c, dz.data_ptr(), c, _p(bias_part),
-                      keep=(dz,))
-            else:
-                b.add("norm_bwd_apply_bf16_peer", L.mpgan_norm_bwd_apply_bf16_peer, gin.data_ptr(), g32, c,
-                      z.data_ptr(), c, *norm, nb.c1.data_ptr(), nb.c2.data_ptr(), C.byref(pc), 0.2, rows_total, c,
-                      dz.data_ptr(), c, _p(bias_part), keep=(dz, pt, pc))
+            dz, pr = self.dzs[i], None
+            if peer is not None:
+                pr = ops.PeerTapsBF16(peer.zs[i], peer.nbs[i].scale, peer.nbs[i].shift, self.coef[i])
+            bias_part = emit_norm_bwd_bf16(b, self.gas[i], self.zs[i], self.nbs[i], 0.2, dz, part, gv(self.bns[i].weight),
+                                           gv(self.bns[i].bias), peer=pr, bias_part=self.want_param_grads and i > 0)
             if self.want_param_grads:
-                if i > 0:
-                    b.add("reduce_partials", L.mpgan_reduce_partials, bias_part.data_ptr(), brow, c, c,
-                          gv(cv.bias).data_ptr(), 1.0, keep=(bias_part,))
-                    b.add("conv_backward_weight_bf16", L.mpgan_conv_backward_weight_bf16, C.byref(gc),
-                          self.acts[i - 1].data_ptr(), g.cin, dz.data_ptr(), c, gv(cv.weight).data_ptr(), 1.0,
-                          ws.data_ptr(), ws.numel() * 4, keep=(gc, ws), desc=_gdesc(g),
-                          tag=(_bf16_wgrad_kernel_name(g), 2.0 * conv_macs(g), conv_bytes(g, 2)))
-                else:
-                    b.add("conv_backward_weight_bf16dy", L.mpgan_conv_backward_weight_bf16dy, C.byref(gc),
-                          self.x_in.data_ptr(), 1, dz.data_ptr(), c, gv(cv.weight).data_ptr(), gv(cv.bias).data_ptr(),
-                          1.0, ws.data_ptr(), ws.numel() * 4, keep=(gc, ws), desc=_gdesc(g),
-                          tag=(wgrad_kernel_name(g, bf16_dy=True), 2.0 * conv_macs(g),
-                               conv_bytes(g, 2) + 2 * self.x_in.numel()))
+                emit_conv_wgrad_bf16(b, self.geoms[i], self.acts[i - 1] if i > 0 else self.x_in, dz,
+                                     gv(self.convs[i].weight), gv(self.convs[i].bias), ws, bias_part)
             if i > 0:
-                b.add("conv_backward_data_bf16", L.mpgan_conv_backward_data_bf16, C.byref(gc), dz.data_ptr(), c,
-                      self._wb16(i).data_ptr(), self.gas[i - 1].data_ptr(), g.cin, keep=(gc,), desc=_gdesc(g),
-                      tag=("dgrad:" + _bf16_kernel_name(g, True), 2.0 * conv_macs(g), conv_bytes(g, 2)))
+                emit_conv_dgrad_bf16(b, self.geoms[i], dz, self.stack.packs.bwd(self.recs[i]), self.gas[i - 1])
             elif self.want_input_grad:
-                b.add("conv_backward_data_bf16_to_f32", L.mpgan_conv_backward_data_bf16_to_f32, C.byref(gc),
-                      dz.data_ptr(), c, store.wp_bwd(self.recs[0]).data_ptr(), self.g_x.data_ptr(), 1,
-                      keep=(gc, self.g_x), desc=_gdesc(g))
+                emit_conv_dgrad_bf16(b, self.geoms[0], dz, store.wp_bwd(self.recs[0]), self.g_x)
         self._bwd_cache[key] = b
         return b
 

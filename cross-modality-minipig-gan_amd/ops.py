@@ -28,28 +28,22 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
-def _cl(t: torch.Tensor, what: str) -> Tuple[int, int, int]:
-    """Validate a channels-last (N,D,H,W,C) view; return (n, pixels/sample, ld)."""
-    if t.dim() != 5 or t.dtype != torch.float32 or not t.is_cuda:
-        raise ValueError(f"{what}: need a CUDA float32 (N,D,H,W,C) tensor, got {tuple(t.shape)} {t.dtype} {t.device}")
+def _clx(t: torch.Tensor, dtype, what: str) -> Tuple[int, int, int]:
+    """Validate a channels-last (N,D,H,W,C) view of the given dtype; return (n, pixels/sample, ld)."""
+    if t.dim() != 5 or t.dtype != dtype or not t.is_cuda:
+        raise ValueError(f"{what}: need a CUDA {dtype} (N,D,H,W,C) tensor, got {tuple(t.shape)} {t.dtype} {t.device}")
     n, d, h, w, c = t.shape
     st = t.stride()
     # pitch from the innermost dimension that actually has extent (size-1 dims carry arbitrary strides)
-    if w > 1:
-        ld = st[3]
-    elif h > 1:
-        ld = st[2]
-    elif d > 1:
-        ld = st[1]
-    elif n > 1:
-        ld = st[0]
-    else:
-        ld = c
+    ld = st[3] if w > 1 else (st[2] if h > 1 else (st[1] if d > 1 else (st[0] if n > 1 else c)))
     want = (d * h * w * ld, h * w * ld, w * ld, ld, 1)
-    ok = ld >= c and all(sz == 1 or a == b for sz, a, b in zip(t.shape, st, want))
-    if not ok:
+    if not (ld >= c and all(sz == 1 or a == b for sz, a, b in zip(t.shape, st, want))):
         raise ValueError(f"{what}: not a pixel-contiguous channels-last view: shape {tuple(t.shape)} strides {st}")
     return n, d * h * w, ld
+
+
+def _cl(t: torch.Tensor, what: str) -> Tuple[int, int, int]:
+    return _clx(t, torch.float32, what)
 
 
 @dataclass(frozen=True)
@@ -555,19 +549,6 @@ def pack_weight(w: torch.Tensor, *, transposed: bool = False, for_dgrad: bool = 
 # --------------------------------------------------------------------------
 # bf16 storage path (BASELINE config C5): activations / packed weights bf16, fp32 accumulate + statistics
 # --------------------------------------------------------------------------
-def _clx(t: torch.Tensor, dtype, what: str) -> Tuple[int, int, int]:
-    """_cl for a channels-last tensor of the given dtype."""
-    if t.dim() != 5 or t.dtype != dtype or not t.is_cuda:
-        raise ValueError(f"{what}: need a CUDA {dtype} (N,D,H,W,C) tensor, got {tuple(t.shape)} {t.dtype} {t.device}")
-    n, d, h, w, c = t.shape
-    st = t.stride()
-    ld = st[3] if w > 1 else (st[2] if h > 1 else (st[1] if d > 1 else (st[0] if n > 1 else c)))
-    want = (d * h * w * ld, h * w * ld, w * ld, ld, 1)
-    if not (ld >= c and all(sz == 1 or a == b for sz, a, b in zip(t.shape, st, want))):
-        raise ValueError(f"{what}: not a pixel-contiguous channels-last view: shape {tuple(t.shape)} strides {st}")
-    return n, d * h * w, ld
-
-
 BF16 = torch.bfloat16
 
 
@@ -730,30 +711,6 @@ def norm_bwd_rows_bf16(rows: int, c: int) -> int:
     return int(lib().mpgan_norm_bwd_rows_bf16(rows, c))
 
 
-def norm_bwd_reduce_bf16(g, z, scale, shift, mean, invstd, slope: float, partials):
-    n, P, ldz = _clx(z, BF16, "norm_bwd_reduce_bf16 z")
-    _, _, ldg = _clx(g, g.dtype, "norm_bwd_reduce_bf16 g")
-    c = z.shape[-1]
-    if partials.numel() < norm_bwd_rows_bf16(n * P, c) * 3 * c + c:
-        raise ValueError("norm_bwd_reduce_bf16: partials too small")
-    check(lib().mpgan_norm_bwd_reduce_bf16(g.data_ptr(), int(g.dtype == torch.float32), ldg, z.data_ptr(), ldz,
-                                           scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
-                                           float(slope), n * P, c, partials.data_ptr(), _stream()),
-          "norm_bwd_reduce_bf16")
-
-
-def norm_bwd_apply_bf16(g, z, scale, shift, mean, invstd, c1, c2, slope: float, dz, bias_partials=None):
-    n, P, ldz = _clx(z, BF16, "norm_bwd_apply_bf16 z")
-    _, _, ldg = _clx(g, g.dtype, "norm_bwd_apply_bf16 g")
-    _, _, lddz = _clx(dz, BF16, "norm_bwd_apply_bf16 dz")
-    c = z.shape[-1]
-    check(lib().mpgan_norm_bwd_apply_bf16(g.data_ptr(), int(g.dtype == torch.float32), ldg, z.data_ptr(), ldz,
-                                          scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
-                                          c1.data_ptr(), c2.data_ptr(), float(slope), n * P, c, dz.data_ptr(), lddz,
-                                          _ptr(bias_partials), _stream()), "norm_bwd_apply_bf16")
-    return dz
-
-
 @dataclass
 class PeerTapsBF16:
     """The other pass of a perceptual-loss pair in bf16 storage (see mpgan_peer_taps_bf16): its stored bf16 z."""
@@ -772,36 +729,48 @@ class PeerTapsBF16:
         return t
 
 
-def norm_bwd_reduce_bf16_peer(g, z, scale, shift, mean, invstd, peer: PeerTapsBF16, slope: float, partials):
-    n, P, ldz = _clx(z, BF16, "norm_bwd_reduce_bf16_peer z")
-    _, _, ldg = _clx(g, g.dtype, "norm_bwd_reduce_bf16_peer g")
+def _peer_arg(peer: Optional[PeerTapsBF16], z, what):
+    """The descriptor argument of a `_peer` entry (none for the plain one) and the entry's name."""
+    if peer is None:
+        return (), what
     if peer.z.shape != z.shape:
-        raise ValueError("norm_bwd_reduce_bf16_peer: peer z must match z")
+        raise ValueError(f"{what}_peer: peer z must match z")
+    return (C.byref(peer.c()),), what + "_peer"
+
+
+def norm_bwd_reduce_bf16(g, z, scale, shift, mean, invstd, slope: float, partials, peer: Optional[PeerTapsBF16] = None):
+    pe, what = _peer_arg(peer, z, "norm_bwd_reduce_bf16")
+    n, P, ldz = _clx(z, BF16, what + " z")
+    _, _, ldg = _clx(g, g.dtype, what + " g")
     c = z.shape[-1]
     if partials.numel() < norm_bwd_rows_bf16(n * P, c) * 3 * c + c:
-        raise ValueError("norm_bwd_reduce_bf16_peer: partials too small")
-    pc = peer.c()
-    check(lib().mpgan_norm_bwd_reduce_bf16_peer(g.data_ptr(), int(g.dtype == torch.float32), ldg, z.data_ptr(), ldz,
-                                                scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
-                                                C.byref(pc), float(slope), n * P, c, partials.data_ptr(), _stream()),
-          "norm_bwd_reduce_bf16_peer")
+        raise ValueError(what + ": partials too small")
+    check(getattr(lib(), "mpgan_" + what)(g.data_ptr(), int(g.dtype == torch.float32), ldg, z.data_ptr(), ldz,
+                                          scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), invstd.data_ptr(), *pe,
+                                          float(slope), n * P, c, partials.data_ptr(), _stream()), what)
+
+
+def norm_bwd_apply_bf16(g, z, scale, shift, mean, invstd, c1, c2, slope: float, dz, bias_partials=None,
+                        peer: Optional[PeerTapsBF16] = None):
+    pe, what = _peer_arg(peer, z, "norm_bwd_apply_bf16")
+    n, P, ldz = _clx(z, BF16, what + " z")
+    _, _, ldg = _clx(g, g.dtype, what + " g")
+    _, _, lddz = _clx(dz, BF16, what + " dz")
+    c = z.shape[-1]
+    check(getattr(lib(), "mpgan_" + what)(g.data_ptr(), int(g.dtype == torch.float32), ldg, z.data_ptr(), ldz,
+                                          scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
+                                          c1.data_ptr(), c2.data_ptr(), *pe, float(slope), n * P, c, dz.data_ptr(), lddz,
+                                          _ptr(bias_partials), _stream()), what)
+    return dz
+
+
+def norm_bwd_reduce_bf16_peer(g, z, scale, shift, mean, invstd, peer: PeerTapsBF16, slope: float, partials):
+    norm_bwd_reduce_bf16(g, z, scale, shift, mean, invstd, slope, partials, peer=peer)
 
 
 def norm_bwd_apply_bf16_peer(g, z, scale, shift, mean, invstd, c1, c2, peer: PeerTapsBF16, slope: float, dz,
                              bias_partials=None):
-    n, P, ldz = _clx(z, BF16, "norm_bwd_apply_bf16_peer z")
-    _, _, ldg = _clx(g, g.dtype, "norm_bwd_apply_bf16_peer g")
-    _, _, lddz = _clx(dz, BF16, "norm_bwd_apply_bf16_peer dz")
-    if peer.z.shape != z.shape:
-        raise ValueError("norm_bwd_apply_bf16_peer: peer z must match z")
-    c = z.shape[-1]
-    pc = peer.c()
-    check(lib().mpgan_norm_bwd_apply_bf16_peer(g.data_ptr(), int(g.dtype == torch.float32), ldg, z.data_ptr(), ldz,
-                                               scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
-                                               c1.data_ptr(), c2.data_ptr(), C.byref(pc), float(slope), n * P, c,
-                                               dz.data_ptr(), lddz, _ptr(bias_partials), _stream()),
-          "norm_bwd_apply_bf16_peer")
-    return dz
+    return norm_bwd_apply_bf16(g, z, scale, shift, mean, invstd, c1, c2, slope, dz, bias_partials, peer=peer)
 
 
 def tap_l1_bf16(za, scale_a, shift_a, zb, scale_b, shift_b, slope: float, partials, out3):

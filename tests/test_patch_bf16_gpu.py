@@ -84,64 +84,106 @@ def _close_bf16(got, ref, what):
     assert (e <= 8e-3 * ref.abs() + 1e-3 * ref.abs().max()).all(), (what, e.max().item(), ref.abs().max().item())
 
 
-def _norm_bwd_gpu(ops, g, z, nbv, peer, slope, g_dtype, coef):
-    """reduce -> finalize -> apply on the GPU (channels-last); peer None: the entries without peer."""
+def _pitched(t_cl, pitch):
+    """The channels-last tensor as the first C channels of a `pitch`-channel one (pitch None: as it is)."""
+    if pitch is None:
+        return t_cl
+    wide = torch.zeros(*t_cl.shape[:-1], pitch, dtype=t_cl.dtype, device=t_cl.device)
+    wide[..., :t_cl.shape[-1]] = t_cl
+    return wide[..., :t_cl.shape[-1]]
+
+
+def _norm_bwd_gpu(ops, g, z, nbv, peer, slope, g_dtype, coef, pitch=None, bias=True):
+    """reduce -> finalize -> apply on the GPU (channels-last); peer None: the entries without peer.  pitch: z, g, the
+    peer's z and dz are the leading channels of `pitch`-channel tensors; bias False: apply without bias partials."""
     scale, shift, mean, invstd = (_dev(t) for t in nbv)
     c = z.shape[1]
     rows = z.numel() // c
     brow = ops.norm_bwd_rows_bf16(rows, c)
     part = torch.zeros(brow * 4 * c + c, device="cuda")
-    gc, zc = to_cl(g).to(g_dtype), to_cl(z).to(BF)
+    gc, zc = _pitched(to_cl(g).to(g_dtype), pitch), _pitched(to_cl(z).to(BF), pitch)
     if peer is not None:
-        pt = ops.PeerTapsBF16(to_cl(peer[0]).to(BF), _dev(peer[1]), _dev(peer[2]), _dev(torch.tensor(coef)))
+        pt = ops.PeerTapsBF16(_pitched(to_cl(peer[0]).to(BF), pitch), _dev(peer[1]), _dev(peer[2]),
+                              _dev(torch.tensor(coef)))
         ops.norm_bwd_reduce_bf16_peer(gc, zc, scale, shift, mean, invstd, pt, slope, part)
     else:
         ops.norm_bwd_reduce_bf16(gc, zc, scale, shift, mean, invstd, slope, part)
     dgamma, dbeta = torch.zeros(c, device="cuda"), torch.zeros(c, device="cuda")
     c1, c2 = torch.empty(c, device="cuda"), torch.empty(c, device="cuda")
     ops.norm_bwd_finalize(part, 1, brow, c, rows, False, dgamma, dbeta, None, c1, c2)
-    dz = torch.empty_like(zc)
-    bias_part = part[brow * 3 * c + c:]
+    dz = _pitched(torch.empty_like(to_cl(z).to(BF)), pitch)
+    bias_part = part[brow * 3 * c + c:] if bias else None
     if peer is not None:
         ops.norm_bwd_apply_bf16_peer(gc, zc, scale, shift, mean, invstd, c1, c2, pt, slope, dz, bias_part)
     else:
         ops.norm_bwd_apply_bf16(gc, zc, scale, shift, mean, invstd, c1, c2, slope, dz, bias_part)
-    colsum = bias_part.view(brow, c).sum(0).cpu()
+    colsum = bias_part.view(brow, c).sum(0).cpu() if bias else None
     return from_cl(dz.float(), 3), dgamma.cpu(), dbeta.cpu(), colsum, dz
 
 
-@pytest.mark.parametrize("g_dtype", [BF, torch.float32], ids=["g_bf16", "g_f32"])
-def test_peer_norm_backward_bf16(g_dtype):
-    """The peer entries on bf16 z against the fp64 formula on the same stored tensors: dz within one bf16 ulp
-    (8e-3*|ref| + 1e-3*max|ref|, the rule of test_discriminator_bf16_backward_layer_by_layer), dgamma / dbeta
-    within 2e-3 relative L2; with all coefficients zero the output is bit-identical to the entry without peer."""
-    from mpgan_amd import ops
+# (n, c, spatial, pitch, bias partials).  A block covers R = 256 / (c/8) rows per pass; mpgan_norm_bwd_rows_bf16 gives
+# ceil(rows / 32R) blocks.
+NORM_BWD_CASES = {
+    "c8_3rows": (1, 8, (1, 1, 3), None, True),             # c/8 = 1, R = 256: fewer rows than R
+    "c24_R85": (2, 24, (3, 5, 10), None, True),            # c/8 = 3 does not divide 256: R = 85, thread 255 idles
+    "c2048_R1": (1, 2048, (1, 5, 7), None, True),          # R = 1, two blocks, the widest the entry admits
+    "c64_2blocks": (2, 64, (8, 9, 10), None, True),        # 1440 rows: two blocks, the second only part full
+    "c128": (3, 128, (7, 9, 5), None, True),
+    "c64_pitch72": (2, 64, (8, 9, 10), 72, True),          # the first 64 channels of 72-channel tensors
+    "c64_no_bias": (2, 64, (8, 9, 10), None, False),       # bias_partials=None
+}
+
+
+def _norm_bwd_inputs(n, c, sp, g_dtype):
+    """z, the peer's z and g as the kernels read them (g on the grid of its storage dtype), batch statistics of z, an
+    affine pair and the peer's scale / shift."""
     gen = torch.Generator().manual_seed(17)
-    n, c, sp = 3, 128, (7, 9, 5)
     z = ((torch.rand(n, c, *sp, generator=gen) - 0.4) * 3).to(BF).float()
     zp = ((torch.rand(n, c, *sp, generator=gen) - 0.5) * 3).to(BF).float()
-    g = (torch.rand(n, c, *sp, generator=gen) - 0.5).to(g_dtype).float() * 1e-2
-    red = [0, 2, 3, 4]
+    g = ((torch.rand(n, c, *sp, generator=gen) - 0.5).to(g_dtype).float() * 1e-2).to(g_dtype).float()
     mean = z.transpose(0, 1).reshape(c, -1).mean(1)
     invstd = 1.0 / torch.sqrt(z.transpose(0, 1).reshape(c, -1).var(1, unbiased=False) + 1e-5)
     gamma, beta = torch.rand(c, generator=gen) + 0.5, torch.rand(c, generator=gen) - 0.5
     scale, shift = gamma * invstd, beta - mean * gamma * invstd
     sp_, hp_ = torch.rand(c, generator=gen) + 0.5, torch.rand(c, generator=gen) - 0.5
+    return z, zp, g, (scale, shift, mean, invstd), (zp, sp_, hp_)
+
+
+@pytest.mark.parametrize("case", list(NORM_BWD_CASES))
+@pytest.mark.parametrize("g_dtype", [BF, torch.float32], ids=["g_bf16", "g_f32"])
+def test_peer_norm_backward_bf16(g_dtype, case):
+    """The peer entries and the plain entries on bf16 z against the fp64 formula on the same stored tensors, at the
+    shapes where their indexing can go wrong (NORM_BWD_CASES): dz within one bf16 ulp (8e-3*|ref| + 1e-3*max|ref|, the
+    rule of test_discriminator_bf16_backward_layer_by_layer), dgamma / dbeta within 2e-3 relative L2, the column sums of
+    the bias partials against the sum of the stored dz; with all coefficients zero the peer entries' output is
+    bit-identical to the entries without peer.  (g is put on the grid of its storage dtype before the reference sees
+    it: the reference and the kernels read the same numbers.)"""
+    from mpgan_amd import ops
+    n, c, sp, pitch, bias = NORM_BWD_CASES[case]
+    z, zp, g, nbv, peer = _norm_bwd_inputs(n, c, sp, g_dtype)
+    red = [0, 2, 3, 4]
     coef = (3e-3, 2e-3, 4e-3)
-    dz, dgamma, dbeta, colsum, _ = _norm_bwd_gpu(ops, g, z, (scale, shift, mean, invstd), (zp, sp_, hp_), 0.2,
-                                                g_dtype, coef)
-    dz_ref, s1, s2 = P.norm_bwd_peer(g.double(), z, scale, shift, mean, invstd, 0.2, (zp, sp_, hp_), coef)
+    kw = dict(pitch=pitch, bias=bias)
+    dz, dgamma, dbeta, colsum, _ = _norm_bwd_gpu(ops, g, z, nbv, peer, 0.2, g_dtype, coef, **kw)
+    dz_ref, s1, s2 = P.norm_bwd_peer(g.double(), z, *nbv, 0.2, peer, coef)
     _close_bf16(dz, dz_ref.float(), "dz (peer)")
     assert _rel(dgamma, s2) <= 2e-3 and _rel(dbeta, s1) <= 2e-3, (_rel(dgamma, s2), _rel(dbeta, s1))
-    np.testing.assert_allclose(colsum.numpy(), dz.sum(red).numpy(), rtol=1e-3, atol=1e-3)
+    if bias:
+        np.testing.assert_allclose(colsum.numpy(), dz.sum(red).numpy(), rtol=1e-3, atol=1e-3)
     # the peer terms are live: the same launch without them is far away
-    dz0_ref, _, _ = P.norm_bwd_peer(g.double(), z, scale, shift, mean, invstd, 0.2)
+    dz0_ref, s10, s20 = P.norm_bwd_peer(g.double(), z, *nbv, 0.2)
     assert _rel(dz_ref, dz0_ref) > 0.1
     # zero coefficients: bit-identical to the entries without peer
-    a = _norm_bwd_gpu(ops, g, z, (scale, shift, mean, invstd), (zp, sp_, hp_), 0.2, g_dtype, (0.0, 0.0, 0.0))
-    b = _norm_bwd_gpu(ops, g, z, (scale, shift, mean, invstd), None, 0.2, g_dtype, None)
+    a = _norm_bwd_gpu(ops, g, z, nbv, peer, 0.2, g_dtype, (0.0, 0.0, 0.0), **kw)
+    b = _norm_bwd_gpu(ops, g, z, nbv, None, 0.2, g_dtype, None, **kw)
     assert torch.equal(a[4], b[4]) and torch.equal(a[1], b[1]) and torch.equal(a[2], b[2])
-    assert torch.equal(a[3], b[3])
+    if bias:
+        assert torch.equal(a[3], b[3])
+    # the entries without peer against the formula without peer terms
+    _close_bf16(b[0], dz0_ref.float(), "dz (plain)")
+    assert _rel(b[1], s20) <= 2e-3 and _rel(b[2], s10) <= 2e-3, (_rel(b[1], s20), _rel(b[2], s10))
+    if bias:
+        np.testing.assert_allclose(b[3].numpy(), b[0].sum(red).numpy(), rtol=1e-3, atol=1e-3)
 
 
 # ---- 3. / 4. / 7. the whole patch discriminator ----------------------------------------------------------------
