@@ -20,6 +20,7 @@ import ctypes as C
 import dataclasses
 import math
 import os
+import struct
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -709,18 +710,21 @@ def emit_conv_fwd_norm(prog, g: ConvGeom, x, wp, bias, y, nb: NormBuf, norm_mod,
              keep=(norm_mod.weight, norm_mod.bias, rm, rv, nbt, nb, partials), desc=f"C{c} rows{rows}")
 
 
+def _f32_bits(v: float) -> int:
+    """The bit pattern of a float32, as the int64 tables of the `_multi` launches carry one."""
+    return struct.unpack("<I", struct.pack("<f", float(v)))[0]
+
+
 def emit_eval_norms(prog, eval_norms, dev):
     """One launch computing scale/shift of every eval-mode BatchNorm layer of a plan (they depend on
     parameters and running statistics only, not on the input)."""
     if not eval_norms:
         return
-    import struct
     rows = []
     for norm_mod, nb, c in eval_norms:
-        eps_bits = struct.unpack("<I", struct.pack("<f", float(norm_mod.eps)))[0]
         rows.append([_p(norm_mod.weight) or 0, _p(norm_mod.bias) or 0, norm_mod.running_mean.data_ptr(),
                      norm_mod.running_var.data_ptr(), nb.scale.data_ptr(), nb.shift.data_ptr(), nb.mean.data_ptr(),
-                     nb.invstd.data_ptr(), c, eps_bits])
+                     nb.invstd.data_ptr(), c, _f32_bits(norm_mod.eps)])
     table = torch.tensor(rows, dtype=torch.int64, device=dev)
     prog.add("norm_from_running_multi", lib().mpgan_norm_from_running_multi, table.data_ptr(), len(rows),
              keep=(table, eval_norms))
@@ -732,23 +736,10 @@ def emit_conv_fwd_act(prog, rows, g: ConvGeom, x, wp, bias, y, norm_mod=None, ac
     bias and the residual add all in the conv's epilogue (mpgan_conv_forward_act); `rows` collects the plan's table rows
     for the one up-front mpgan_epi_vectors_multi launch that fills this conv's scale / shift / slope vectors.
     c_norm: the norm + activation cover only the first c_norm output channels (a conv fused with its unit's residual conv)."""
-    import struct
     ops._check_in_out(g, x, y, "plan conv_forward_act")
-    c = g.cout if c_norm is None else c_norm
-    if norm_mod is None:
-        c = 0
-    else:
-        assert hasattr(norm_mod, "running_mean") and norm_mod.running_mean is not None, "eval plan: BatchNorm layers only"
     if act_mod is not None:
         assert act_mod.weight.numel() == 1, "eval plan: PReLU with one parameter (MONAI 0.4.0's default)"
-    cpad = (g.cout + 3) // 4 * 4
-    vec = torch.empty(3, cpad, device=x.device)              # scale / shift / slope, each row 16-byte aligned
-    eps_bits = struct.unpack("<I", struct.pack("<f", float(norm_mod.eps if norm_mod is not None else 0.0)))[0]
-    nm = norm_mod
-    rows.append([_p(nm.weight) or 0 if nm is not None else 0, _p(nm.bias) or 0 if nm is not None else 0,
-                 nm.running_mean.data_ptr() if nm is not None else 0, nm.running_var.data_ptr() if nm is not None else 0,
-                 _p(bias) or 0, _p(act_mod.weight) if act_mod is not None else 0,
-                 vec[0].data_ptr(), vec[1].data_ptr(), vec[2].data_ptr(), c, g.cout, eps_bits])
+    vec = epi_row(rows, g.cout, bias, norm_mod, act_mod, x.device, c_norm=c_norm)
     gc = g.c()
     tag = (gather_kernel_name(g, False, False), 2.0 * conv_macs(g), conv_bytes(g))
     prog.add("conv_forward", lib().mpgan_conv_forward_act, C.byref(gc), x.data_ptr(), _ld(x), wp.data_ptr(),
@@ -773,17 +764,20 @@ class _ConstSlope:
         self.weight = torch.full((1,), float(slope), device=dev)
 
 
-def epi_row(rows, cout, bias, norm_mod, act_mod, dev):
-    """Table row of mpgan_epi_vectors_multi for one eval-mode BatchNorm + activation layer; returns the (3, cpad)
-    tensor whose rows the launch fills with scale / shift / slope (each 16-byte aligned)."""
-    import struct
-    assert norm_mod.running_mean is not None, "eval plan: BatchNorm layers with running statistics only"
-    cpad = (cout + 3) // 4 * 4
-    vec = torch.empty(3, cpad, device=dev)
-    eps_bits = struct.unpack("<I", struct.pack("<f", float(norm_mod.eps)))[0]
-    rows.append([_p(norm_mod.weight) or 0, _p(norm_mod.bias) or 0, norm_mod.running_mean.data_ptr(),
-                 norm_mod.running_var.data_ptr(), _p(bias) or 0, _p(act_mod.weight), vec[0].data_ptr(),
-                 vec[1].data_ptr(), vec[2].data_ptr(), cout, cout, eps_bits])
+def epi_row(rows, cout, bias, norm_mod, act_mod, dev, c_norm=None):
+    """Table row of mpgan_epi_vectors_multi for one eval-mode conv with `cout` output channels: running-statistics
+    BatchNorm over the first c_norm of them (default: all; none without a norm_mod), then the activation (none without
+    an act_mod).  Returns the (3, cpad) tensor whose rows the launch fills with scale / shift / slope (each 16-byte
+    aligned)."""
+    nm = norm_mod
+    if nm is not None:
+        assert getattr(nm, "running_mean", None) is not None, "eval plan: BatchNorm layers with running statistics only"
+    c = 0 if nm is None else (cout if c_norm is None else c_norm)
+    vec = torch.empty(3, (cout + 3) // 4 * 4, device=dev)
+    rows.append([(_p(nm.weight) or 0) if nm is not None else 0, (_p(nm.bias) or 0) if nm is not None else 0,
+                 nm.running_mean.data_ptr() if nm is not None else 0, nm.running_var.data_ptr() if nm is not None else 0,
+                 _p(bias) or 0, _p(act_mod.weight) if act_mod is not None else 0, vec[0].data_ptr(), vec[1].data_ptr(),
+                 vec[2].data_ptr(), c, cout, _f32_bits(nm.eps if nm is not None else 0.0)])
     return vec
 
 
@@ -1586,136 +1580,26 @@ def plan_io(plan) -> IoSlots:
 
 
 # --------------------------------------------------------------------------
-# discriminator (variant A)
+# discriminators: the conv stack and the two heads, as the plans of both variants and both storage modes hold them
+# (every launch of a layer and of a head is described in one place)
 # --------------------------------------------------------------------------
-class DiscPlan:
-    """4 x (valid conv -> BN -> LeakyReLU 0.2) -> Flatten -> Linear(F,1) -> Sigmoid
-    (code/GAN/GAN_final.py:159-209)."""
-
-    def __init__(self, disc, store: ParamStore, n: int, spatial: Sequence[int], *, want_backward: bool,
-                 want_input_grad: bool, want_param_grads: bool, training: bool = True):
-        """training=False: the eval-mode program (running-statistics BatchNorm, forward only): every layer's BatchNorm
-        + LeakyReLU rides in its conv's epilogue (mpgan_conv_forward_act), the activated tensors are the only ones
-        stored, and the head reads the last one without a prologue.  The affine vectors are recomputed on the device
-        at every run from the live parameters and running statistics; nothing else of the module is touched."""
-        dims = disc.dimensions
-        dev = store.flat.device
-        dhw = _t3(spatial, dims, 1)
-        self.n, self.dhw, self.dims, self.store = n, dhw, dims, store
-        self.training = training
-        assert training or not want_backward, "eval plans are forward-only"
-        E = lambda *shape: torch.empty(*shape, device=dev)
-        convs = [disc.model_conv[i] for i in (0, 3, 6, 9)]
-        bns = [disc.model_conv[i] for i in (1, 4, 7, 10)]
-        lin = disc.model_linear[1]
-        self.x_in = E(n, *dhw, 1)
-        geoms, zs, nbs, recs = [], [], [], []
-        size = dhw
-        scratch = Scratch(dev)
-        for cv in convs:
-            g = conv_geom_of(cv, n, size, dims)
-            geoms.append(g)
-            size = g.out_dhw
-            if min(size) < 1:
-                raise ValueError(f"discriminator input {spatial} too small")
-            zs.append(E(n, *size, cv.out_channels))
-            nbs.append(NormBuf(n, cv.out_channels, False, dev))
-            recs.append(store.register_conv(cv, cout=cv.out_channels, cin=cv.in_channels, taps=math.prod(cv.kernel_size)))
-            if not training:       # no statistics partials, no weight-gradient workspace
-                continue
-            scratch.want_partials(n, size[0] * size[1] * size[2], cv.out_channels)
-            scratch.want_ws(g)
-            if g.cin > 1:          # rows of the backward-data launch that also reduces the previous layer's norm backward
-                scratch.partials_need = max(scratch.partials_need, ops.conv_bwd_stats_rows(g) * 3 * g.cin)
-        P_last = size[0] * size[1] * size[2]
-        c_last = convs[-1].out_channels
-        if lin.in_features != P_last * c_last:
-            raise ValueError(f"Linear.in_features {lin.in_features} != {c_last}*{P_last} for input {spatial}")
-        rlin = store.register_conv(lin, cout=1, cin=c_last, taps=P_last)
-        self.logit, self.prob = E(n), E(n)
-        lin_part = E(ops.linear1_partials(n))
-        L = lib()
-        f = self.fwd = Program()
-        store.emit_pack(f)
-        if not training:
-            leaky, rows, body = _ConstSlope(0.2, dev), [], Program()
-            src = self.x_in
-            for i, cv in enumerate(convs):           # zs[i] holds the ACTIVATED tensor here
-                emit_conv_fwd_act(body, rows, geoms[i], src, store.wp(recs[i]), cv.bias, zs[i], norm_mod=bns[i],
-                                  act_mod=leaky)
-                src = zs[i]
-            emit_epi_vectors(f, rows, dev)
-            f.extend(body)
-            f.add("linear1_forward", L.mpgan_linear1_forward, zs[-1].data_ptr(), None, n, P_last, c_last,
-                  store.wp(rlin).data_ptr(), lin.bias.data_ptr(), lin_part.data_ptr(), self.logit.data_ptr(),
-                  self.prob.data_ptr(), keep=(lin_part, zs))
-            self.acts = zs
-            self.busy = False
-            self.bwd = Program()
-            self.g_x = None
-            return
-        scratch.alloc()
-        part, ws = scratch.partials, scratch.ws
-        lrelu = lambda nb: nb.prologue(ACT_LEAKY, 0.2, None)
-        src, pro = self.x_in, None
-        for i, cv in enumerate(convs):
-            emit_conv_fwd_norm(f, geoms[i], src, store.wp(recs[i]), cv.bias, zs[i], nbs[i], bns[i], part, pro=pro)
-            src, pro = zs[i], lrelu(nbs[i])
-        pc = pro.c()
-        f.add("linear1_forward", L.mpgan_linear1_forward, zs[-1].data_ptr(), C.byref(pc), n, P_last, c_last,
-              store.wp(rlin).data_ptr(), lin.bias.data_ptr(), lin_part.data_ptr(), self.logit.data_ptr(),
-              self.prob.data_ptr(), keep=(pc, pro, lin_part))
-        self.busy = False
-        self.bwd = Program()
-        self.g_x = None
-        if not want_backward:
-            return
-        b = self.bwd
-        gv = store.grad_view if want_param_grads else (lambda p: None)
-        self.g_prob = E(n)
-        dlogit = E(n)
-        gas = [E(*z.shape) for z in zs]
-        self.zs, self.gas, self.nbs = zs, gas, nbs   # raw conv outputs, their gradients, norm vectors (tests, tools)
-        b.add("sigmoid_backward", L.mpgan_sigmoid_backward, self.g_prob.data_ptr(), self.prob.data_ptr(), n,
-              dlogit.data_ptr(), keep=(dlogit,))
-        b.add("linear1_backward", L.mpgan_linear1_backward, zs[-1].data_ptr(), C.byref(pc), n, P_last, c_last,
-              store.wp(rlin).data_ptr(), dlogit.data_ptr(), gas[-1].data_ptr(), _p(gv(lin.weight)), _p(gv(lin.bias)),
-              1.0, keep=(gas,))
-        reduced = 0                                  # rows the previous backward-data launch left in `part`
-        for i in range(3, -1, -1):
-            pro_i = lrelu(nbs[i])
-            emit_norm_bwd(b, gas[i], zs[i], nbs[i], pro_i, gas[i], part, gv(bns[i].weight), gv(bns[i].bias), None,
-                          reduced_rows=reduced)
-            src = zs[i - 1] if i > 0 else self.x_in
-            pro_in = lrelu(nbs[i - 1]) if i > 0 else None
-            if want_param_grads:
-                emit_conv_wgrad(b, geoms[i], src, gas[i], gv(convs[i].weight), ws, pro=pro_in,
-                                dbias=gv(convs[i].bias), lane=_D_WGRAD_LANE)
-            if i > 0:
-                # the gradient w.r.t. a_{i-1} = LeakyReLU(BN(z_{i-1})): the epilogue of this launch also forms the
-                # norm-backward sums of layer i-1, so that layer needs no reduce pass over g and z
-                reduced = emit_conv_dgrad_stats(b, geoms[i], gas[i], store.wp_bwd(recs[i]), gas[i - 1], zs[i - 1],
-                                                nbs[i - 1], 0.2, part)
-            elif want_input_grad:
-                self.g_x = E(n, *dhw, 1)
-                emit_conv_dgrad(b, geoms[0], gas[0], store.wp_bwd(recs[0]), self.g_x)
-        b.join()
+def _lrelu(nb: NormBuf) -> Prologue:
+    return nb.prologue(ACT_LEAKY, 0.2, None)
 
 
-# --------------------------------------------------------------------------
-# discriminator (variant A), bf16 storage (BASELINE config C5)
-# --------------------------------------------------------------------------
-class ConvStackBF16:
-    """The four conv -> BN -> LeakyReLU(0.2) layers of a discriminator in bf16 storage, as the plans of
-    both variants hold them: geometries, weight records and bf16 packs, norm vectors, the raw conv outputs z_i (bf16;
-    none where `raw_z` is off: the fused eval program) and the activations a_i (bf16; fp32 for the last layer, which
-    the fp32 head reads)."""
+class ConvStack:
+    """The four conv -> BN -> LeakyReLU(0.2) layers of a discriminator in fp32 storage: geometries, weight records, norm
+    vectors and the raw conv outputs z_i, which every consumer normalises on load (`raw_z` off, the fused eval program:
+    the activated tensors are stored there instead)."""
+    PEER = ops.PeerTaps                # the other pass's taps of one layer, as emit_backward's `peers` takes them
+    FUSE_BWD_STATS = True              # variant A: backward-data leaves the norm-backward sums of the layer in front
+    SIDE_WGRAD = True                  # emit_backward takes `wgrad_lane`: the backward program then ends in a join
 
     def __init__(self, disc, store: ParamStore, n: int, dhw, dims: int, *, raw_z: bool, what: str):
-        dev = store.flat.device
+        dev, self.raw_z = store.flat.device, raw_z
         self.convs = [disc.model_conv[i] for i in (0, 3, 6, 9)]
         self.bns = [disc.model_conv[i] for i in (1, 4, 7, 10)]
-        self.geoms, self.zs, self.acts, self.nbs, self.recs = [], [], [], [], []
+        self.geoms, self.zs, self.nbs, self.recs = [], [], [], []
         size = dhw
         for i, cv in enumerate(self.convs):
             g = conv_geom_of(cv, n, size, dims)
@@ -1723,12 +1607,113 @@ class ConvStackBF16:
             size, c = g.out_dhw, cv.out_channels
             if min(size) < 1:
                 raise ValueError(f"{what} too small")
-            if raw_z:
-                self.zs.append(torch.empty(n, *size, c, device=dev, dtype=torch.bfloat16))
-            self.acts.append(torch.empty(n, *size, c, device=dev, dtype=torch.float32 if i == 3 else torch.bfloat16))
+            self._alloc_layer(i, (n, *size, c), dev)
             self.nbs.append(NormBuf(n, c, False, dev))
             self.recs.append(store.register_conv(cv, cout=c, cin=cv.in_channels, taps=math.prod(cv.kernel_size)))
-        self.packs = PacksBF16(self.recs[1:], dev)
+
+    def _alloc_layer(self, i, shape, dev):
+        self.zs.append(torch.empty(shape, device=dev))
+
+    def want_scratch(self, scratch: Scratch, fuse_stats: bool):
+        """Statistics partials and weight-gradient workspace of a training plan; fuse_stats: also the rows a
+        backward-data launch leaves for the norm backward of the layer in front (emit_conv_dgrad_stats)."""
+        for g in self.geoms:
+            scratch.want_partials(g.n, math.prod(g.out_dhw), g.cout)
+            scratch.want_ws(g)
+            if fuse_stats and g.cin > 1:
+                scratch.partials_need = max(scratch.partials_need, ops.conv_bwd_stats_rows(g) * 3 * g.cin)
+
+    def alloc_grads(self, disc):
+        """(gas, dzs): the gradients w.r.t. the activations, and the dz the BatchNorm backward makes of them in place."""
+        gas = [torch.empty_like(z) for z in self.zs]
+        return gas, gas
+
+    def _emit_fused_eval(self, prog, emit_layer, x, wp, outs):
+        """Eval without raw z: outs[i] = LeakyReLU(BN_running(conv_i)) straight from each conv's epilogue, the epilogue
+        vectors of all layers from one launch up front."""
+        dev = x.device
+        leaky, rows, body = _ConstSlope(0.2, dev), [], Program()
+        for i, cv in enumerate(self.convs):
+            emit_layer(body, rows, self.geoms[i], x, wp(i), cv.bias, outs[i], self.bns[i], leaky)
+            x = outs[i]
+        emit_epi_vectors(prog, rows, dev)
+        prog.extend(body)
+
+    def emit_forward(self, prog, store: ParamStore, x, partials, training: bool):
+        """x -> the (tensor, prologue or None) the head reads.  Training: statistics out of each conv, finalize; eval with
+        raw z: scale / shift of every layer from the running statistics in one launch up front instead; eval without:
+        zs[i] holds the ACTIVATED tensor."""
+        wp = lambda i: store.wp(self.recs[i])
+        if not self.raw_z:
+            self._emit_fused_eval(prog, emit_conv_fwd_act, x, wp, self.zs)
+            return self.zs[-1], None
+        eval_norms, body, pro = [], Program(), None
+        for i, cv in enumerate(self.convs):
+            emit_conv_fwd_norm(body, self.geoms[i], x, wp(i), cv.bias, self.zs[i], self.nbs[i], self.bns[i], partials,
+                               pro=pro, training=training, eval_norms=eval_norms)
+            x, pro = self.zs[i], _lrelu(self.nbs[i])
+        emit_eval_norms(prog, eval_norms, x.device)
+        prog.extend(body)
+        return x, pro
+
+    def emit_backward(self, prog, store: ParamStore, x, gas, dzs, partials, ws, *, want_param_grads: bool, g_x,
+                      peers=None, fuse_stats: bool = False, ext=None, wgrad_lane: int = 0):
+        """Per layer, last to first: norm backward (in place) -> weight gradient -> backward data.
+        peers: per layer, the other pass's taps (variant B's fused perceptual loss).  fuse_stats: the backward-data
+        launch also leaves the norm-backward sums of the layer in front, which then needs no reduce pass (variant A).
+        ext: per layer, the gradients (gz, gy, ga) deposited into the materialised taps (conv out, norm out, activation):
+            g_a += G_a;  dz = BNbwd_act(g_a) + BNbwd_identity(G_y) + G_z
+        (BatchNorm's backward is linear in the gradient of its output, so the y-tap's gradient goes through a second
+        norm backward with an identity activation; both add into dgamma / dbeta) -- three more element-wise passes."""
+        gv = store.grad_view if want_param_grads else (lambda p: None)
+        add = lambda dst, src: prog.add("axpby", lib().mpgan_axpby, dst.data_ptr(), 1.0, src.data_ptr(), 1.0, dst.numel(),
+                                        dst.data_ptr(), keep=(dst, src))
+        reduced = 0                                  # rows the previous backward-data launch left in `partials`
+        for i in range(len(self.convs) - 1, -1, -1):
+            g, z, nb, bn, cv = gas[i], self.zs[i], self.nbs[i], self.bns[i], self.convs[i]
+            if ext is not None:
+                add(g, ext[i][2])
+            emit_norm_bwd(prog, g, z, nb, _lrelu(nb), g, partials, gv(bn.weight), gv(bn.bias), None,
+                          peer=peers[i] if peers is not None else None, reduced_rows=reduced)
+            if ext is not None:
+                gz, gy, _ = ext[i]
+                emit_norm_bwd(prog, gy, z, nb, nb.prologue(ACT_NONE), gy, partials, gv(bn.weight), gv(bn.bias), None)
+                add(g, gy)
+                add(g, gz)
+            if want_param_grads:
+                emit_conv_wgrad(prog, self.geoms[i], self.zs[i - 1] if i > 0 else x, g, gv(cv.weight), ws,
+                                pro=_lrelu(self.nbs[i - 1]) if i > 0 else None, dbias=gv(cv.bias), lane=wgrad_lane)
+            if i > 0 and fuse_stats:
+                reduced = emit_conv_dgrad_stats(prog, self.geoms[i], g, store.wp_bwd(self.recs[i]), gas[i - 1],
+                                                self.zs[i - 1], self.nbs[i - 1], 0.2, partials)
+            elif i > 0:
+                emit_conv_dgrad(prog, self.geoms[i], g, store.wp_bwd(self.recs[i]), gas[i - 1])
+            elif g_x is not None:
+                emit_conv_dgrad(prog, self.geoms[0], g, store.wp_bwd(self.recs[0]), g_x)
+
+
+class ConvStackBF16(ConvStack):
+    """The same layers in bf16 storage: bf16 packs of the three dense convs, the raw conv outputs z_i
+    (bf16; none where `raw_z` is off: the fused eval program) and the activations a_i (bf16; fp32 for the last layer,
+    which the fp32 head reads)."""
+    PEER = ops.PeerTapsBF16
+    FUSE_BWD_STATS = _FUSE_BWD_STATS_BF16
+    SIDE_WGRAD = False
+
+    def __init__(self, disc, store: ParamStore, n: int, dhw, dims: int, *, raw_z: bool, what: str):
+        self.acts = []
+        super().__init__(disc, store, n, dhw, dims, raw_z=raw_z, what=what)
+        self.packs = PacksBF16(self.recs[1:], store.flat.device)
+
+    def _alloc_layer(self, i, shape, dev):
+        if self.raw_z:
+            self.zs.append(torch.empty(shape, device=dev, dtype=torch.bfloat16))
+        self.acts.append(torch.empty(shape, device=dev, dtype=torch.float32 if i == 3 else torch.bfloat16))
+
+    def want_scratch(self, scratch: Scratch, fuse_stats: bool):
+        for i, g in enumerate(self.geoms):
+            # (rows of the fused norm-backward sums the NEXT layer's backward-data launch leaves for this layer's norm)
+            scratch.want_bf16_layer(g, bwd_stats_rows_bf16(self.geoms[i + 1]) if fuse_stats and i < 3 else 0)
 
     def alloc_grads(self, disc):
         """(gas, dzs): the gradients w.r.t. the activations (bf16; fp32 for a_3, which the fp32 head writes) and the
@@ -1740,109 +1725,223 @@ class ConvStackBF16:
         return gas, [torch.empty_like(z) if keep_all or i == 3 else gas[i] for i, z in enumerate(self.zs)]
 
     def emit_forward(self, prog, store: ParamStore, x, partials, training: bool):
-        """The bf16 weight packs, then x -> a_3.  Training: statistics out of each conv, finalize, norm_act_bf16; eval
-        with raw z: scale / shift of every layer from the running statistics in one launch up front instead; eval
+        """The bf16 weight packs, then x -> (a_3, None).  Training: statistics out of each conv, finalize, norm_act_bf16;
+        eval with raw z: scale / shift of every layer from the running statistics in one launch up front instead; eval
         without: each a_i straight from its conv's epilogue."""
-        dev = x.device
         self.packs.emit(prog, store)
         wp = lambda i: store.wp(self.recs[0]) if i == 0 else self.packs.fwd(self.recs[i])
-        if not self.zs:
-            leaky, rows, body = _ConstSlope(0.2, dev), [], Program()
-            for i, cv in enumerate(self.convs):
-                emit_conv_fwd_act_bf16(body, rows, self.geoms[i], x, wp(i), cv.bias, self.acts[i], self.bns[i], leaky)
-                x = self.acts[i]
-            emit_epi_vectors(prog, rows, dev)
-            prog.extend(body)
-            return
+        if not self.raw_z:
+            self._emit_fused_eval(prog, emit_conv_fwd_act_bf16, x, wp, self.acts)
+            return self.acts[3], None
         if not training:
-            emit_eval_norms(prog, [(bn, nb, g.cout) for bn, nb, g in zip(self.bns, self.nbs, self.geoms)], dev)
+            emit_eval_norms(prog, [(bn, nb, g.cout) for bn, nb, g in zip(self.bns, self.nbs, self.geoms)], x.device)
         for i, cv in enumerate(self.convs):
             rows = emit_conv_fwd_bf16(prog, self.geoms[i], x, wp(i), cv.bias, self.zs[i], partials if training else None)
             emit_norm_act_bf16(prog, self.zs[i], self.nbs[i], 0.2, self.acts[i], self.bns[i] if training else None,
                                partials, rows)
             x = self.acts[i]
+        return x, None
+
+    def emit_backward(self, prog, store: ParamStore, x, gas, dzs, partials, ws, *, want_param_grads: bool, g_x,
+                      peers=None, fuse_stats: bool = False):
+        """As ConvStack.emit_backward, on the stored bf16 tensors: dz_i goes to dzs[i], the weight gradients stay on the
+        caller's stream, and there is no `ext` (gradients through materialised taps are fp32 storage only)."""
+        gv = store.grad_view if want_param_grads else (lambda p: None)
+        reduced = 0                                  # rows the previous backward-data launch left in `partials`
+        for i in range(len(self.convs) - 1, -1, -1):
+            dz, bn, cv = dzs[i], self.bns[i], self.convs[i]
+            bias_part = emit_norm_bwd_bf16(prog, gas[i], self.zs[i], self.nbs[i], 0.2, dz, partials, gv(bn.weight),
+                                           gv(bn.bias), peer=peers[i] if peers is not None else None,
+                                           reduced_rows=reduced, bias_part=want_param_grads and i > 0)
+            if want_param_grads:
+                emit_conv_wgrad_bf16(prog, self.geoms[i], self.acts[i - 1] if i > 0 else x, dz, gv(cv.weight),
+                                     gv(cv.bias), ws, bias_part)
+            if i > 0:
+                # (fuse_stats: ... and the reduce pass of the layer in front in the same launch)
+                reduced = emit_conv_dgrad_bf16(prog, self.geoms[i], dz, self.packs.bwd(self.recs[i]), gas[i - 1],
+                                               stats=(self.zs[i - 1], self.nbs[i - 1], 0.2, partials) if fuse_stats else None)
+            elif g_x is not None:
+                emit_conv_dgrad_bf16(prog, self.geoms[0], dz, store.wp_bwd(self.recs[0]), g_x)
 
 
-class DiscPlanBF16:
+class LinearHead:
+    """Variant A's head, Flatten -> Linear(F,1) -> Sigmoid, on the last layer's tensor `src` read through `pro` (raw z
+    with the BatchNorm + LeakyReLU prologue, or an activated fp32 tensor with none)."""
+
+    def __init__(self, disc, store: ParamStore, n: int, g_last: ConvGeom, spatial):
+        dev = store.flat.device
+        self.lin, self.n = disc.model_linear[1], n
+        self.P, self.c = math.prod(g_last.out_dhw), g_last.cout
+        if self.lin.in_features != self.P * self.c:
+            raise ValueError(f"Linear.in_features {self.lin.in_features} != {self.c}*{self.P} for input {spatial}")
+        self.rlin = store.register_conv(self.lin, cout=1, cin=self.c, taps=self.P)
+        self.logit, self.prob = torch.empty(n, device=dev), torch.empty(n, device=dev)
+        self.lin_part = torch.empty(ops.linear1_partials(n), device=dev)
+
+    def emit_forward(self, prog, store: ParamStore, src, pro):
+        pc = pro.c() if pro is not None else None
+        prog.add("linear1_forward", lib().mpgan_linear1_forward, src.data_ptr(), C.byref(pc) if pc is not None else None,
+                 self.n, self.P, self.c, store.wp(self.rlin).data_ptr(), self.lin.bias.data_ptr(),
+                 self.lin_part.data_ptr(), self.logit.data_ptr(), self.prob.data_ptr(), keep=(pc, pro, src, self))
+
+    def emit_backward(self, prog, store: ParamStore, src, pro, g_src, want_param_grads: bool):
+        """g_prob (allocated here; the caller fills it) -> g_src, the gradient w.r.t. what `src` holds after `pro`."""
+        gv = store.grad_view if want_param_grads else (lambda p: None)
+        L, pc = lib(), (pro.c() if pro is not None else None)
+        self.g_prob, dlogit = torch.empty_like(self.prob), torch.empty_like(self.prob)
+        prog.add("sigmoid_backward", L.mpgan_sigmoid_backward, self.g_prob.data_ptr(), self.prob.data_ptr(), self.n,
+                 dlogit.data_ptr(), keep=(dlogit, self))
+        prog.add("linear1_backward", L.mpgan_linear1_backward, src.data_ptr(), C.byref(pc) if pc is not None else None,
+                 self.n, self.P, self.c, store.wp(self.rlin).data_ptr(), dlogit.data_ptr(), g_src.data_ptr(),
+                 _p(gv(self.lin.weight)), _p(gv(self.lin.bias)), 1.0, keep=(pc, pro, src, g_src))
+
+
+class PatchHead:
+    """Variant B's head, Flatten -> Linear(F,64) -> Linear(64,1) -> Sigmoid, on the last layer's tensor `src` read
+    through `pro` (see LinearHead).  Linear(F,64) is a conv whose kernel spans the last feature map (packing realises
+    the flatten order), split over K; Linear(64,1) a 1x1x1 conv."""
+
+    def __init__(self, disc, store: ParamStore, n: int, g_last: ConvGeom, spatial):
+        dev = store.flat.device
+        E = lambda *shape: torch.empty(*shape, device=dev)
+        lin1, lin2 = disc.model_linear[1], disc.model_linear[2]
+        self.lin1, self.lin2, self.n = lin1, lin2, n
+        size, c_last = tuple(g_last.out_dhw), g_last.cout
+        P_last = math.prod(size)
+        if lin1.in_features != P_last * c_last:
+            raise ValueError(f"Linear.in_features {lin1.in_features} != {c_last}*{P_last} for patches {spatial}")
+        self.g_l1 = ConvGeom(n, size, c_last, lin1.out_features, size, (1, 1, 1), (0, 0, 0))
+        self.g_l2 = ConvGeom(n, (1, 1, 1), lin1.out_features, 1, (1, 1, 1), (1, 1, 1), (0, 0, 0))
+        self.r_l1 = store.register_conv(lin1, cout=lin1.out_features, cin=c_last, taps=P_last, tco=True)
+        # its data gradient as ONE GEMM: (P x 64) * (64 x taps*C) -> the channels-last gradient of the last map
+        self.g_l1_bwd = ConvGeom(n, (1, 1, 1), lin1.out_features, P_last * c_last, (1, 1, 1), (1, 1, 1), (0, 0, 0))
+        self.r_l2 = store.register_conv(lin2, cout=1, cin=lin1.out_features, taps=1)
+        self.h = E(n, 1, 1, 1, lin1.out_features)
+        self.logit, self.prob = E(n, 1, 1, 1, 1), E(n)
+        self.splitk_ws = E(max(ops.conv_splitk_workspace(self.g_l1) // 4, 4))
+
+    def want_scratch(self, scratch: Scratch):
+        scratch.want_ws(self.g_l1)
+        scratch.want_ws(self.g_l2)
+
+    def alloc_grads(self):
+        """Head gradients, and those arriving through the perceptual taps of the three head tensors (zero unless a
+        perceptual loss deposited them)."""
+        dev, n = self.h.device, self.n
+        self.g_prob = torch.empty(n, device=dev)
+        self.dlogit = torch.empty(n, 1, 1, 1, 1, device=dev)
+        self.dh = torch.empty_like(self.h)
+        self.tap_g_h, self.tap_g_logit, self.tap_g_prob = (torch.zeros(*s, device=dev) for s in (self.h.shape, (n,), (n,)))
+
+    def emit_forward(self, prog, store: ParamStore, src, pro):
+        gc1, pc = self.g_l1.c(), (pro.c() if pro is not None else None)
+        prog.add("conv_forward_splitk", lib().mpgan_conv_forward_splitk, C.byref(gc1), src.data_ptr(), _ld(src),
+                 store.wp(self.r_l1).data_ptr(), self.lin1.bias.data_ptr(), C.byref(pc) if pc is not None else None,
+                 self.splitk_ws.data_ptr(), self.splitk_ws.numel() * 4, self.h.data_ptr(), _ld(self.h),
+                 keep=(gc1, pc, pro, src, self), tag=("gather_conv_pipe_kernel<splitK>", 2.0 * conv_macs(self.g_l1)))
+        emit_conv_fwd(prog, self.g_l2, self.h, store.wp(self.r_l2), self.lin2.bias, self.logit)
+        prog.add("sigmoid_forward", lib().mpgan_sigmoid_forward, self.logit.data_ptr(), self.n, self.prob.data_ptr())
+
+    def emit_backward(self, prog, store: ParamStore, src, pro, g_src, ws, want_param_grads: bool):
+        """g_prob and the head taps' gradients -> g_src, the gradient w.r.t. what `src` holds after `pro`."""
+        gv = store.grad_view if want_param_grads else (lambda p: None)
+        L, n = lib(), self.n
+        # sigmoid: dlogit = (g_prob + tap_prob) * p(1-p) + tap_logit
+        prog.add("axpby", L.mpgan_axpby, self.g_prob.data_ptr(), 1.0, self.tap_g_prob.data_ptr(), 1.0, n,
+                 self.g_prob.data_ptr(), keep=(self,))
+        prog.add("sigmoid_backward", L.mpgan_sigmoid_backward, self.g_prob.data_ptr(), self.prob.data_ptr(), n,
+                 self.dlogit.data_ptr())
+        prog.add("axpby", L.mpgan_axpby, self.dlogit.data_ptr(), 1.0, self.tap_g_logit.data_ptr(), 1.0, n,
+                 self.dlogit.data_ptr())
+        if want_param_grads:
+            emit_conv_wgrad(prog, self.g_l2, self.h, self.dlogit, gv(self.lin2.weight), ws, dbias=gv(self.lin2.bias))
+        emit_conv_dgrad(prog, self.g_l2, self.dlogit, store.wp_bwd(self.r_l2), self.dh, resid=self.tap_g_h)
+        if want_param_grads:
+            emit_conv_wgrad(prog, self.g_l1, src, self.dh, gv(self.lin1.weight), ws, pro=pro, dbias=gv(self.lin1.bias))
+        emit_conv_fwd(prog, self.g_l1_bwd, self.dh, store.wp_tco(self.r_l1), None, g_src.view(n, 1, 1, 1, -1))
+
+
+class _DiscPlanBase:
+    """What the plans of both discriminators share: the boundary, the conv stack (fp32 storage here; the bf16 plans
+    mix in _StorageBF16) and its attributes as tests, tools and networks.py read them off the plan."""
+
+    def _make_stack(self, disc, what: str, raw_z: bool):
+        return ConvStack(disc, self.store, self.n, self.dhw, self.dims, raw_z=raw_z, what=what)
+
+    def _setup(self, disc, store: ParamStore, n: int, spatial, what: str, *, training: bool, want_backward: bool,
+               raw_z: bool):
+        assert training or not want_backward, "eval plans are forward-only"
+        self.n, self.dims, self.store, self.training = n, disc.dimensions, store, training
+        self.dhw = _t3(spatial, self.dims, 1)
+        self.x_in = torch.empty(n, *self.dhw, 1, device=store.flat.device)
+        st = self.stack = self._make_stack(disc, f"{what} {spatial}", raw_z)
+        self.convs, self.bns, self.geoms, self.zs, self.nbs, self.recs = st.convs, st.bns, st.geoms, st.zs, st.nbs, st.recs
+        return st
+
+
+class _StorageBF16:
+    def _make_stack(self, disc, what: str, raw_z: bool):
+        st = ConvStackBF16(disc, self.store, self.n, self.dhw, self.dims, raw_z=raw_z, what=what)
+        self.acts = st.acts
+        return st
+
+
+# --------------------------------------------------------------------------
+# discriminator (variant A)
+# --------------------------------------------------------------------------
+class DiscPlan(_DiscPlanBase):
+    """4 x (valid conv -> BN -> LeakyReLU 0.2) -> Flatten -> Linear(F,1) -> Sigmoid
+    (code/GAN/GAN_final.py:159-209)."""
+
+    def __init__(self, disc, store: ParamStore, n: int, spatial: Sequence[int], *, want_backward: bool,
+                 want_input_grad: bool, want_param_grads: bool, training: bool = True):
+        """training=False: the eval-mode program (running-statistics BatchNorm, forward only): every layer's BatchNorm
+        + LeakyReLU rides in its conv's epilogue (mpgan_conv_forward_act; mpgan_conv_forward_act_bf16 in bf16 storage),
+        the activated tensors are the only ones stored -- no raw z, no statistics, no norm_act_bf16 pass -- and the head
+        reads the last one without a prologue.  The affine vectors are recomputed on the device at every run from the
+        live parameters and running statistics; nothing else of the module is touched."""
+        st = self._setup(disc, store, n, spatial, "discriminator input", training=training, want_backward=want_backward,
+                         raw_z=training)
+        head = self.head = LinearHead(disc, store, n, st.geoms[-1], spatial)
+        self.logit, self.prob = head.logit, head.prob
+        scratch = Scratch(store.flat.device)
+        if training:       # eval: no statistics partials, no weight-gradient workspace
+            st.want_scratch(scratch, st.FUSE_BWD_STATS)
+        scratch.alloc()
+        f = self.fwd = Program()
+        store.emit_pack(f)
+        src, pro = st.emit_forward(f, store, self.x_in, scratch.partials, training)
+        head.emit_forward(f, store, src, pro)
+        self.busy = False
+        b = self.bwd = Program()
+        self.g_x = None
+        if not want_backward:
+            return
+        if want_input_grad:
+            self.g_x = torch.empty_like(self.x_in)
+        # raw conv outputs, their gradients (`dzs`: after the norm backward), norm vectors: read by tests and tools
+        self.gas, self.dzs = st.alloc_grads(disc)
+        head.emit_backward(b, store, src, pro, self.gas[-1], want_param_grads)
+        self.g_prob = head.g_prob
+        st.emit_backward(b, store, self.x_in, self.gas, self.dzs, scratch.partials, scratch.ws,
+                         want_param_grads=want_param_grads, g_x=self.g_x, fuse_stats=st.FUSE_BWD_STATS,
+                         **(dict(wgrad_lane=_D_WGRAD_LANE) if st.SIDE_WGRAD else {}))
+        if st.SIDE_WGRAD:
+            b.join()
+
+
+class DiscPlanBF16(_StorageBF16, DiscPlan):
     """The same network as DiscPlan with bf16 activations, activation gradients and packed weights in HBM
     (code/GAN/GAN_final.py:159-209 at the reference's 3-D shape); fp32 accumulation, statistics, parameters,
     weight gradients and Adam.  Per layer: raw conv output z (bf16) + fused fp32 statistics -> finalize ->
     a = LeakyReLU(BN(z)) materialised once (bf16; fp32 for the last layer, which the fp32 Linear head reads).
     The first layer (1 input channel) runs on the HBM-bound VALU kernels with fp32 weights."""
 
-    def __init__(self, disc, store: ParamStore, n: int, spatial: Sequence[int], *, want_backward: bool,
-                 want_input_grad: bool, want_param_grads: bool, training: bool = True):
-        """training=False: the eval-mode program (forward only): a_i = LeakyReLU(BN_running(conv_i)) comes out of each
-        conv's epilogue from the fp32 accumulator and is stored once (bf16; fp32 for the last layer) -- no raw z, no
-        statistics, no norm_act_bf16 pass (mpgan_conv_forward_act_bf16)."""
-        dims = disc.dimensions
-        dev = store.flat.device
-        dhw = _t3(spatial, dims, 1)
-        self.n, self.dhw, self.dims, self.store = n, dhw, dims, store
-        self.training = training
-        assert training or not want_backward, "eval plans are forward-only"
-        E = lambda *shape: torch.empty(*shape, device=dev)
-        lin = disc.model_linear[1]
-        self.x_in = E(n, *dhw, 1)
-        st = ConvStackBF16(disc, store, n, dhw, dims, raw_z=training, what=f"discriminator input {spatial}")
-        convs, bns, geoms, zs, acts, nbs, recs = st.convs, st.bns, st.geoms, st.zs, st.acts, st.nbs, st.recs
-        self.geoms, self.zs, self.acts, self.nbs, self.recs = geoms, zs, acts, nbs, recs
-        scratch = Scratch(dev)
-        for i, g in enumerate(geoms if training else ()):
-            # (rows of the fused norm-backward sums the NEXT layer's backward-data launch leaves for this layer's norm)
-            scratch.want_bf16_layer(g, bwd_stats_rows_bf16(geoms[i + 1]) if _FUSE_BWD_STATS_BF16 and i < 3 else 0)
-        scratch.alloc()
-        part, ws = scratch.partials, scratch.ws
-        P_last, c_last = math.prod(geoms[-1].out_dhw), convs[-1].out_channels
-        if lin.in_features != P_last * c_last:
-            raise ValueError(f"Linear.in_features {lin.in_features} != {c_last}*{P_last} for input {spatial}")
-        rlin = store.register_conv(lin, cout=1, cin=c_last, taps=P_last)
-        self.logit, self.prob = E(n), E(n)
-        lin_part = E(ops.linear1_partials(n))
-        L = lib()
-        f = self.fwd = Program()
-        store.emit_pack(f)                                   # fp32 packs: first layer, Linear head
-        st.emit_forward(f, store, self.x_in, part, training)
-        f.add("linear1_forward", L.mpgan_linear1_forward, acts[3].data_ptr(), None, n, P_last, c_last,
-              store.wp(rlin).data_ptr(), lin.bias.data_ptr(), lin_part.data_ptr(), self.logit.data_ptr(),
-              self.prob.data_ptr(), keep=(lin_part, st))
-        self.busy = False
-        self.bwd = Program()
-        self.g_x = None
-        if not want_backward:
-            return
-        b = self.bwd
-        gv = store.grad_view if want_param_grads else (lambda p: None)
-        self.g_prob = E(n)
-        dlogit = E(n)
-        self.gas, self.dzs = st.alloc_grads(disc)
-        gas = self.gas
-        b.add("sigmoid_backward", L.mpgan_sigmoid_backward, self.g_prob.data_ptr(), self.prob.data_ptr(), n,
-              dlogit.data_ptr(), keep=(dlogit,))
-        b.add("linear1_backward", L.mpgan_linear1_backward, acts[3].data_ptr(), None, n, P_last, c_last,
-              store.wp(rlin).data_ptr(), dlogit.data_ptr(), gas[3].data_ptr(), _p(gv(lin.weight)), _p(gv(lin.bias)),
-              1.0, keep=(gas, self.dzs))
-        reduced = 0                                  # rows the previous backward-data launch left in `part`
-        for i in range(3, -1, -1):
-            dz = self.dzs[i]
-            bias_part = emit_norm_bwd_bf16(b, gas[i], zs[i], nbs[i], 0.2, dz, part, gv(bns[i].weight), gv(bns[i].bias),
-                                           reduced_rows=reduced, bias_part=want_param_grads and i > 0)
-            if want_param_grads:
-                emit_conv_wgrad_bf16(b, geoms[i], acts[i - 1] if i > 0 else self.x_in, dz, gv(convs[i].weight),
-                                     gv(convs[i].bias), ws, bias_part)
-            if i > 0:
-                # (MPGAN_FUSE_BWD_STATS_BF16: ... and the reduce pass of the layer in front in the same launch)
-                reduced = emit_conv_dgrad_bf16(b, geoms[i], dz, st.packs.bwd(recs[i]), gas[i - 1],
-                                               stats=(zs[i - 1], nbs[i - 1], 0.2, part) if _FUSE_BWD_STATS_BF16 else None)
-            elif want_input_grad:
-                self.g_x = E(n, *dhw, 1)
-                emit_conv_dgrad_bf16(b, geoms[0], dz, store.wp_bwd(recs[0]), self.g_x)
-
 
 # --------------------------------------------------------------------------
 # patch discriminator (variant B)
 # --------------------------------------------------------------------------
-class PatchDiscPlan:
+class PatchDiscPlan(_DiscPlanBase):
     """4 x (valid k3 conv -> BN -> LeakyReLU 0.2) -> Flatten -> Linear(F,64) -> Linear(64,1) ->
     Sigmoid on small patches (test_runs/GAN.py:136-198).  The 16 perceptual taps are never
     materialised: their L1 terms and gradients come from the raw conv outputs of the two
@@ -1852,92 +1951,28 @@ class PatchDiscPlan:
                  want_input_grad: bool, want_param_grads: bool, training: bool = True, keep_taps: bool = True):
         """training=False: one of the two eval-mode programs (running-statistics BatchNorm, forward only).
         keep_taps: the raw z_i are stored as in training and every BatchNorm's scale / shift come from ONE
-        mpgan_norm_from_running_multi launch instead of statistics + finalize -- consumers normalise on load, and
-        TapSet.materialize / the fused perceptual loss read the plan exactly as they read a training one (values only).
+        mpgan_norm_from_running_multi launch instead of statistics + finalize -- consumers normalise on load (bf16
+        storage: norm_act_bf16 as in training), and TapSet.materialize / the fused perceptual loss read the plan exactly
+        as they read a training one (values only).
         not keep_taps: the fused program of DiscPlan (BatchNorm + LeakyReLU in each conv's epilogue, activated tensors
         only), the head reading the last one without a prologue."""
-        dims = disc.dimensions
-        dev = store.flat.device
-        dhw = _t3(spatial, dims, 1)
-        self.n, self.dhw, self.dims, self.store, self.disc = n, dhw, dims, store, disc
+        self.disc, self.keep_taps = disc, keep_taps
         self.want_input_grad, self.want_param_grads = want_input_grad, want_param_grads
-        self.training, self.keep_taps = training, keep_taps
-        assert training or not want_backward, "eval plans are forward-only"
-        E = lambda *shape: torch.empty(*shape, device=dev)
-        convs = [disc.model_conv[i] for i in (0, 3, 6, 9)]
-        bns = [disc.model_conv[i] for i in (1, 4, 7, 10)]
-        lin1, lin2 = disc.model_linear[1], disc.model_linear[2]
-        self.convs, self.bns, self.lin1, self.lin2 = convs, bns, lin1, lin2
-        self.x_in = E(n, *dhw, 1)
-        self.geoms, self.zs, self.nbs, self.recs = [], [], [], []
-        size = dhw
-        scratch = Scratch(dev)
-        for cv in convs:
-            g = conv_geom_of(cv, n, size, dims)
-            self.geoms.append(g)
-            size = g.out_dhw
-            if min(size) < 1:
-                raise ValueError(f"patch discriminator input {spatial} too small")
-            self.zs.append(E(n, *size, cv.out_channels))
-            self.nbs.append(NormBuf(n, cv.out_channels, False, dev))
-            self.recs.append(store.register_conv(cv, cout=cv.out_channels, cin=cv.in_channels,
-                                                 taps=math.prod(cv.kernel_size)))
-            if training:
-                scratch.want_partials(n, size[0] * size[1] * size[2], cv.out_channels)
-                scratch.want_ws(g)
-        c_last = convs[-1].out_channels
-        P_last = size[0] * size[1] * size[2]
-        if lin1.in_features != P_last * c_last:
-            raise ValueError(f"Linear.in_features {lin1.in_features} != {c_last}*{P_last} for patches {spatial}")
-        # Linear(F, 64) as a conv whose kernel spans the last feature map (packing realises the flatten order)
-        self.g_l1 = ConvGeom(n, tuple(size), c_last, lin1.out_features, tuple(size), (1, 1, 1), (0, 0, 0))
-        self.g_l2 = ConvGeom(n, (1, 1, 1), lin1.out_features, 1, (1, 1, 1), (1, 1, 1), (0, 0, 0))
-        self.r_l1 = store.register_conv(lin1, cout=lin1.out_features, cin=c_last, taps=P_last, tco=True)
-        # its data gradient as ONE GEMM: (P x 64) * (64 x taps*C) -> the channels-last gradient of the last map
-        self.g_l1_bwd = ConvGeom(n, (1, 1, 1), lin1.out_features, P_last * c_last, (1, 1, 1), (1, 1, 1), (0, 0, 0))
-        self.r_l2 = store.register_conv(lin2, cout=1, cin=lin1.out_features, taps=1)
+        st = self._setup(disc, store, n, spatial, "patch discriminator input", training=training,
+                         want_backward=want_backward, raw_z=training or keep_taps)
+        head = self.head = PatchHead(disc, store, n, st.geoms[-1], spatial)
+        self.lin1, self.lin2, self.h, self.logit, self.prob = head.lin1, head.lin2, head.h, head.logit, head.prob
+        dev = store.flat.device
+        scratch = self.scratch = Scratch(dev)
         if training:
-            scratch.want_ws(self.g_l1)
-            scratch.want_ws(self.g_l2)
+            st.want_scratch(scratch, False)
+            head.want_scratch(scratch)
         scratch.alloc()
-        self.scratch = scratch
-        part, ws = scratch.partials, scratch.ws
-        self.h = E(n, 1, 1, 1, lin1.out_features)
-        self.logit, self.prob = E(n, 1, 1, 1, 1), E(n)
-        self.splitk_ws = E(max(ops.conv_splitk_workspace(self.g_l1) // 4, 4))
-        L = lib()
-        self.lrelu = lambda nb: nb.prologue(ACT_LEAKY, 0.2, None)
+        self.lrelu = _lrelu
         f = self.fwd = Program()
         store.emit_pack(f)
-        src, pro = self.x_in, None
-        if not training and not keep_taps:
-            leaky, rows, body = _ConstSlope(0.2, dev), [], Program()
-            for i, cv in enumerate(convs):            # zs[i] holds the ACTIVATED tensor here
-                emit_conv_fwd_act(body, rows, self.geoms[i], src, store.wp(self.recs[i]), cv.bias, self.zs[i],
-                                  norm_mod=bns[i], act_mod=leaky)
-                src = self.zs[i]
-            emit_epi_vectors(f, rows, dev)
-            f.extend(body)
-        elif not training:
-            eval_norms, body = [], Program()
-            for i, cv in enumerate(convs):
-                emit_conv_fwd_norm(body, self.geoms[i], src, store.wp(self.recs[i]), cv.bias, self.zs[i], self.nbs[i],
-                                   bns[i], part, pro=pro, training=False, eval_norms=eval_norms)
-                src, pro = self.zs[i], self.lrelu(self.nbs[i])
-            emit_eval_norms(f, eval_norms, dev)
-            f.extend(body)
-        else:
-            for i, cv in enumerate(convs):
-                emit_conv_fwd_norm(f, self.geoms[i], src, store.wp(self.recs[i]), cv.bias, self.zs[i], self.nbs[i],
-                                   bns[i], part, pro=pro)
-                src, pro = self.zs[i], self.lrelu(self.nbs[i])
-        gc1, pc = self.g_l1.c(), (pro.c() if pro is not None else None)
-        f.add("conv_forward_splitk", L.mpgan_conv_forward_splitk, C.byref(gc1), self.zs[-1].data_ptr(), _ld(self.zs[-1]),
-              store.wp(self.r_l1).data_ptr(), lin1.bias.data_ptr(), C.byref(pc) if pc is not None else None,
-              self.splitk_ws.data_ptr(), self.splitk_ws.numel() * 4, self.h.data_ptr(), _ld(self.h),
-              keep=(gc1, pc, pro), tag=("gather_conv_pipe_kernel<splitK>", 2.0 * conv_macs(self.g_l1)))
-        emit_conv_fwd(f, self.g_l2, self.h, store.wp(self.r_l2), lin2.bias, self.logit)
-        f.add("sigmoid_forward", L.mpgan_sigmoid_forward, self.logit.data_ptr(), n, self.prob.data_ptr())
+        self._head_in = st.emit_forward(f, store, self.x_in, scratch.partials, training)
+        head.emit_forward(f, store, *self._head_in)
         self.busy = False
         self.g_x = None
         self._bwd_cache = {}
@@ -1945,23 +1980,19 @@ class PatchDiscPlan:
             self._perc_weights(dev)
         if not want_backward:
             return
-        self.gas = [E(*z.shape) for z in self.zs]
+        self.gas, self.dzs = st.alloc_grads(disc)
         self._tap_buffers(dev)
         if want_input_grad:
-            self.g_x = E(n, *dhw, 1)
+            self.g_x = torch.empty_like(self.x_in)
 
     def _tap_buffers(self, dev):
         """Head gradients and the perceptual loss's per-plan state (both storage modes)."""
-        E = lambda *shape: torch.empty(*shape, device=dev)
-        Z = lambda *shape: torch.zeros(*shape, device=dev)
-        n = self.n
-        self.g_prob = E(n)
-        self.dlogit = E(n, 1, 1, 1, 1)
-        self.dh = E(n, 1, 1, 1, self.lin1.out_features)
-        # gradients arriving through the perceptual taps of the three head tensors (zero unless a
-        # perceptual loss deposited them) and the per-layer (z, y, a) coefficients
-        self.tap_g_h, self.tap_g_logit, self.tap_g_prob = Z(*self.h.shape), Z(n), Z(n)
-        self.coef_all = Z(4 * len(self.convs))                 # one buffer: the perceptual loss fills it in one launch
+        head = self.head
+        head.alloc_grads()
+        self.g_prob, self.dlogit, self.dh = head.g_prob, head.dlogit, head.dh
+        self.tap_g_h, self.tap_g_logit, self.tap_g_prob = head.tap_g_h, head.tap_g_logit, head.tap_g_prob
+        # the per-layer (z, y, a) coefficients of the perceptual taps
+        self.coef_all = torch.zeros(4 * len(self.convs), device=dev)   # one buffer: the perceptual loss fills it in one launch
         self.coef = [self.coef_all[4 * i:4 * i + 4] for i in range(len(self.convs))]
         self._perc_weights(dev)
 
@@ -1980,46 +2011,21 @@ class PatchDiscPlan:
         self.perc_w_fwd = torch.tensor(wf, device=dev)
         self.perc_w_bwd = torch.tensor(wb, device=dev)
 
-    def backward_program(self, peer: Optional["PatchDiscPlan"]) -> Program:
+    def backward_program(self, peer: Optional["PatchDiscPlan"], ext=None) -> Program:
+        """The head, then the conv stack; peer: the other pass of a fused perceptual loss; ext: see backward_program_ext."""
         key = id(peer) if peer is not None else 0
+        if ext is not None:
+            key = ("ext", key)
         if key in self._bwd_cache:
             return self._bwd_cache[key]
-        store, L = self.store, lib()
-        part, ws = self.scratch.partials, self.scratch.ws
-        gv = store.grad_view if self.want_param_grads else (lambda p: None)
-        b = Program()
-        n = self.n
-        # sigmoid: dlogit = (g_prob + tap_prob) * p(1-p) + tap_logit
-        b.add("axpby", L.mpgan_axpby, self.g_prob.data_ptr(), 1.0, self.tap_g_prob.data_ptr(), 1.0, n,
-              self.g_prob.data_ptr())
-        b.add("sigmoid_backward", L.mpgan_sigmoid_backward, self.g_prob.data_ptr(), self.prob.data_ptr(), n,
-              self.dlogit.data_ptr())
-        b.add("axpby", L.mpgan_axpby, self.dlogit.data_ptr(), 1.0, self.tap_g_logit.data_ptr(), 1.0, n,
-              self.dlogit.data_ptr())
-        if self.want_param_grads:
-            emit_conv_wgrad(b, self.g_l2, self.h, self.dlogit, gv(self.lin2.weight), ws, dbias=gv(self.lin2.bias))
-        emit_conv_dgrad(b, self.g_l2, self.dlogit, store.wp_bwd(self.r_l2), self.dh, resid=self.tap_g_h)
-        pro4 = self.lrelu(self.nbs[-1])
-        if self.want_param_grads:
-            emit_conv_wgrad(b, self.g_l1, self.zs[-1], self.dh, gv(self.lin1.weight), ws, pro=pro4,
-                            dbias=gv(self.lin1.bias))
-        emit_conv_fwd(b, self.g_l1_bwd, self.dh, store.wp_tco(self.r_l1), None,
-                      self.gas[-1].view(n, 1, 1, 1, -1))
-        for i in range(len(self.convs) - 1, -1, -1):
-            pr = None
-            if peer is not None:
-                pr = ops.PeerTaps(peer.zs[i], peer.nbs[i].scale, peer.nbs[i].shift, self.coef[i])
-            emit_norm_bwd(b, self.gas[i], self.zs[i], self.nbs[i], self.lrelu(self.nbs[i]), self.gas[i], part,
-                          gv(self.bns[i].weight), gv(self.bns[i].bias), None, peer=pr)
-            src = self.zs[i - 1] if i > 0 else self.x_in
-            pro_in = self.lrelu(self.nbs[i - 1]) if i > 0 else None
-            if self.want_param_grads:
-                emit_conv_wgrad(b, self.geoms[i], src, self.gas[i], gv(self.convs[i].weight), ws, pro=pro_in,
-                                dbias=gv(self.convs[i].bias))
-            if i > 0:
-                emit_conv_dgrad(b, self.geoms[i], self.gas[i], store.wp_bwd(self.recs[i]), self.gas[i - 1])
-            elif self.want_input_grad:
-                emit_conv_dgrad(b, self.geoms[0], self.gas[0], store.wp_bwd(self.recs[0]), self.g_x)
+        st, store, b = self.stack, self.store, Program()
+        self.head.emit_backward(b, store, *self._head_in, self.gas[-1], self.scratch.ws, self.want_param_grads)
+        peers = None
+        if peer is not None:
+            peers = [st.PEER(peer.zs[i], peer.nbs[i].scale, peer.nbs[i].shift, self.coef[i]) for i in range(len(self.convs))]
+        st.emit_backward(b, store, self.x_in, self.gas, self.dzs, self.scratch.partials, self.scratch.ws,
+                         want_param_grads=self.want_param_grads, g_x=self.g_x, peers=peers,
+                         **(dict(ext=ext) if ext is not None else {}))
         self._bwd_cache[key] = b
         return b
 
@@ -2067,170 +2073,18 @@ class PatchDiscPlan:
         self.ext_used = False
 
     def backward_program_ext(self, peer: Optional["PatchDiscPlan"]) -> Program:
-        """backward_program with the external tap gradients folded in, layer by layer:
-            g_a += G_a;  dz = BNbwd_act(g_a) + BNbwd_identity(G_y) + G_z
-        (BatchNorm's backward is linear in the gradient of its output, so the y-tap's gradient goes through a
-        second norm-backward with an identity activation; both add into dgamma / dbeta).  A compatibility path
-        built from the existing kernels: three extra element-wise passes per layer."""
-        key = ("ext", id(peer) if peer is not None else 0)
-        if key in self._bwd_cache:
-            return self._bwd_cache[key]
-        ge = self._ext_buffers()
-        store, L = self.store, lib()
-        part, ws = self.scratch.partials, self.scratch.ws
-        gv = store.grad_view if self.want_param_grads else (lambda p: None)
-        b = Program()
-        n = self.n
-        add = lambda dst, src: b.add("axpby", L.mpgan_axpby, dst.data_ptr(), 1.0, src.data_ptr(), 1.0, dst.numel(),
-                                     dst.data_ptr(), keep=(dst, src))
-        b.add("axpby", L.mpgan_axpby, self.g_prob.data_ptr(), 1.0, self.tap_g_prob.data_ptr(), 1.0, n,
-              self.g_prob.data_ptr())
-        b.add("sigmoid_backward", L.mpgan_sigmoid_backward, self.g_prob.data_ptr(), self.prob.data_ptr(), n,
-              self.dlogit.data_ptr())
-        b.add("axpby", L.mpgan_axpby, self.dlogit.data_ptr(), 1.0, self.tap_g_logit.data_ptr(), 1.0, n,
-              self.dlogit.data_ptr())
-        if self.want_param_grads:
-            emit_conv_wgrad(b, self.g_l2, self.h, self.dlogit, gv(self.lin2.weight), ws, dbias=gv(self.lin2.bias))
-        emit_conv_dgrad(b, self.g_l2, self.dlogit, store.wp_bwd(self.r_l2), self.dh, resid=self.tap_g_h)
-        pro4 = self.lrelu(self.nbs[-1])
-        if self.want_param_grads:
-            emit_conv_wgrad(b, self.g_l1, self.zs[-1], self.dh, gv(self.lin1.weight), ws, pro=pro4,
-                            dbias=gv(self.lin1.bias))
-        emit_conv_fwd(b, self.g_l1_bwd, self.dh, store.wp_tco(self.r_l1), None, self.gas[-1].view(n, 1, 1, 1, -1))
-        for i in range(len(self.convs) - 1, -1, -1):
-            pr = None
-            if peer is not None:
-                pr = ops.PeerTaps(peer.zs[i], peer.nbs[i].scale, peer.nbs[i].shift, self.coef[i])
-            gz, gy, ga = ge[i]
-            add(self.gas[i], ga)
-            emit_norm_bwd(b, self.gas[i], self.zs[i], self.nbs[i], self.lrelu(self.nbs[i]), self.gas[i], part,
-                          gv(self.bns[i].weight), gv(self.bns[i].bias), None, peer=pr)
-            emit_norm_bwd(b, gy, self.zs[i], self.nbs[i], self.nbs[i].prologue(ACT_NONE), gy, part,
-                          gv(self.bns[i].weight), gv(self.bns[i].bias), None)
-            add(self.gas[i], gy)
-            add(self.gas[i], gz)
-            src = self.zs[i - 1] if i > 0 else self.x_in
-            pro_in = self.lrelu(self.nbs[i - 1]) if i > 0 else None
-            if self.want_param_grads:
-                emit_conv_wgrad(b, self.geoms[i], src, self.gas[i], gv(self.convs[i].weight), ws, pro=pro_in,
-                                dbias=gv(self.convs[i].bias))
-            if i > 0:
-                emit_conv_dgrad(b, self.geoms[i], self.gas[i], store.wp_bwd(self.recs[i]), self.gas[i - 1])
-            elif self.want_input_grad:
-                emit_conv_dgrad(b, self.geoms[0], self.gas[0], store.wp_bwd(self.recs[0]), self.g_x)
-        self._bwd_cache[key] = b
-        return b
+        """backward_program with the external tap gradients folded in, layer by layer (ConvStack.emit_backward's `ext`).
+        A compatibility path built from the existing kernels."""
+        return self.backward_program(peer, ext=self._ext_buffers())
 
 
-class PatchDiscPlanBF16(PatchDiscPlan):
+class PatchDiscPlanBF16(_StorageBF16, PatchDiscPlan):
     """PatchDiscPlan with DiscPlanBF16's storage contract: bf16 raw conv outputs z_i, activations
     a_0..a_2, activation gradients and packed weights of the three dense convs in HBM; fp32 accumulation, statistics,
     parameters, weight gradients and Adam.  a_3 and its gradient stay fp32 for the fp32 split-K head, which reads a_3
     with no prologue.  The perceptual taps are defined on the STORED z_i (y = z_i*scale + shift, a = LeakyReLU(y) in
     fp32): their values come from mpgan_tap_l1_bf16, their gradients from the peer entries of the bf16 norm backward.
     Gradients deposited into materialised taps are not offered (deposit_tap_grad raises)."""
-
-    def __init__(self, disc, store: ParamStore, n: int, spatial: Sequence[int], *, want_backward: bool,
-                 want_input_grad: bool, want_param_grads: bool, training: bool = True, keep_taps: bool = True):
-        """training=False: the eval-mode programs (see PatchDiscPlan).  keep_taps: raw bf16 z_i stored, scale / shift from
-        the running statistics (one mpgan_norm_from_running_multi launch), norm_act_bf16 as in training; not keep_taps:
-        each a_i straight from its conv's epilogue (mpgan_conv_forward_act_bf16), no z_i and no norm_act_bf16 pass."""
-        dims = disc.dimensions
-        dev = store.flat.device
-        dhw = _t3(spatial, dims, 1)
-        self.n, self.dhw, self.dims, self.store, self.disc = n, dhw, dims, store, disc
-        self.want_input_grad, self.want_param_grads = want_input_grad, want_param_grads
-        self.training, self.keep_taps = training, keep_taps
-        assert training or not want_backward, "eval plans are forward-only"
-        E = lambda *shape: torch.empty(*shape, device=dev)
-        lin1, lin2 = disc.model_linear[1], disc.model_linear[2]
-        self.x_in = E(n, *dhw, 1)
-        st = self.stack = ConvStackBF16(disc, store, n, dhw, dims, raw_z=training or keep_taps,
-                                        what=f"patch discriminator input {spatial}")
-        self.convs, self.bns, self.lin1, self.lin2 = st.convs, st.bns, lin1, lin2
-        self.geoms, self.zs, self.acts, self.nbs, self.recs = st.geoms, st.zs, st.acts, st.nbs, st.recs
-        scratch = Scratch(dev)
-        for g in (self.geoms if training else ()):
-            scratch.want_bf16_layer(g)
-        size, c_last = self.geoms[-1].out_dhw, self.convs[-1].out_channels
-        P_last = math.prod(size)
-        if lin1.in_features != P_last * c_last:
-            raise ValueError(f"Linear.in_features {lin1.in_features} != {c_last}*{P_last} for patches {spatial}")
-        # the fp32 head of PatchDiscPlan, reading the fp32 a_3 instead of z_3 through a prologue
-        self.g_l1 = ConvGeom(n, tuple(size), c_last, lin1.out_features, tuple(size), (1, 1, 1), (0, 0, 0))
-        self.g_l2 = ConvGeom(n, (1, 1, 1), lin1.out_features, 1, (1, 1, 1), (1, 1, 1), (0, 0, 0))
-        self.r_l1 = store.register_conv(lin1, cout=lin1.out_features, cin=c_last, taps=P_last, tco=True)
-        self.g_l1_bwd = ConvGeom(n, (1, 1, 1), lin1.out_features, P_last * c_last, (1, 1, 1), (1, 1, 1), (0, 0, 0))
-        self.r_l2 = store.register_conv(lin2, cout=1, cin=lin1.out_features, taps=1)
-        if training:
-            scratch.want_ws(self.g_l1)
-            scratch.want_ws(self.g_l2)
-        scratch.alloc()
-        self.scratch = scratch
-        self.h = E(n, 1, 1, 1, lin1.out_features)
-        self.logit, self.prob = E(n, 1, 1, 1, 1), E(n)
-        self.splitk_ws = E(max(ops.conv_splitk_workspace(self.g_l1) // 4, 4))
-        L = lib()
-        f = self.fwd = Program()
-        store.emit_pack(f)                                   # fp32 packs: first layer, the two Linear layers
-        st.emit_forward(f, store, self.x_in, scratch.partials, training)
-        gc1 = self.g_l1.c()
-        a3 = self.acts[3]
-        f.add("conv_forward_splitk", L.mpgan_conv_forward_splitk, C.byref(gc1), a3.data_ptr(), _ld(a3),
-              store.wp(self.r_l1).data_ptr(), lin1.bias.data_ptr(), None, self.splitk_ws.data_ptr(),
-              self.splitk_ws.numel() * 4, self.h.data_ptr(), _ld(self.h), keep=(gc1, a3),
-              tag=("gather_conv_pipe_kernel<splitK>", 2.0 * conv_macs(self.g_l1)))
-        emit_conv_fwd(f, self.g_l2, self.h, store.wp(self.r_l2), lin2.bias, self.logit)
-        f.add("sigmoid_forward", L.mpgan_sigmoid_forward, self.logit.data_ptr(), n, self.prob.data_ptr())
-        self.busy = False
-        self.g_x = None
-        self._bwd_cache = {}
-        if not training and keep_taps:
-            self._perc_weights(dev)
-        if not want_backward:
-            return
-        self.gas, self.dzs = st.alloc_grads(disc)
-        self._tap_buffers(dev)
-        if want_input_grad:
-            self.g_x = E(n, *dhw, 1)
-
-    def backward_program(self, peer: Optional["PatchDiscPlanBF16"]) -> Program:
-        key = id(peer) if peer is not None else 0
-        if key in self._bwd_cache:
-            return self._bwd_cache[key]
-        store, L = self.store, lib()
-        part, ws = self.scratch.partials, self.scratch.ws
-        gv = store.grad_view if self.want_param_grads else (lambda p: None)
-        b = Program()
-        n = self.n
-        # the head, as PatchDiscPlan's (sigmoid: dlogit = (g_prob + tap_prob) * p(1-p) + tap_logit)
-        b.add("axpby", L.mpgan_axpby, self.g_prob.data_ptr(), 1.0, self.tap_g_prob.data_ptr(), 1.0, n,
-              self.g_prob.data_ptr())
-        b.add("sigmoid_backward", L.mpgan_sigmoid_backward, self.g_prob.data_ptr(), self.prob.data_ptr(), n,
-              self.dlogit.data_ptr())
-        b.add("axpby", L.mpgan_axpby, self.dlogit.data_ptr(), 1.0, self.tap_g_logit.data_ptr(), 1.0, n,
-              self.dlogit.data_ptr())
-        if self.want_param_grads:
-            emit_conv_wgrad(b, self.g_l2, self.h, self.dlogit, gv(self.lin2.weight), ws, dbias=gv(self.lin2.bias))
-        emit_conv_dgrad(b, self.g_l2, self.dlogit, store.wp_bwd(self.r_l2), self.dh, resid=self.tap_g_h)
-        if self.want_param_grads:
-            emit_conv_wgrad(b, self.g_l1, self.acts[3], self.dh, gv(self.lin1.weight), ws, dbias=gv(self.lin1.bias))
-        emit_conv_fwd(b, self.g_l1_bwd, self.dh, store.wp_tco(self.r_l1), None, self.gas[3].view(n, 1, 1, 1, -1))
-        for i in range(len(self.convs) - 1, -1, -1):
-            dz, pr = self.dzs[i], None
-            if peer is not None:
-                pr = ops.PeerTapsBF16(peer.zs[i], peer.nbs[i].scale, peer.nbs[i].shift, self.coef[i])
-            bias_part = emit_norm_bwd_bf16(b, self.gas[i], self.zs[i], self.nbs[i], 0.2, dz, part, gv(self.bns[i].weight),
-                                           gv(self.bns[i].bias), peer=pr, bias_part=self.want_param_grads and i > 0)
-            if self.want_param_grads:
-                emit_conv_wgrad_bf16(b, self.geoms[i], self.acts[i - 1] if i > 0 else self.x_in, dz,
-                                     gv(self.convs[i].weight), gv(self.convs[i].bias), ws, bias_part)
-            if i > 0:
-                emit_conv_dgrad_bf16(b, self.geoms[i], dz, self.stack.packs.bwd(self.recs[i]), self.gas[i - 1])
-            elif self.want_input_grad:
-                emit_conv_dgrad_bf16(b, self.geoms[0], dz, store.wp_bwd(self.recs[0]), self.g_x)
-        self._bwd_cache[key] = b
-        return b
 
     def deposit_tap_grad(self, key: int, g: torch.Tensor):
         raise NotImplementedError(

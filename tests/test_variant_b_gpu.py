@@ -244,6 +244,45 @@ def test_reference_perceptual_loss_body_runs_on_the_returned_dict():
     assert torch.isfinite(x3.grad).all()
 
 
+def test_reference_perceptual_loss_body_with_trainable_discriminator():
+    """The same loss body on the materialised taps with the discriminator TRAINABLE: the gradients of all 16 taps of
+    both passes travel back through PatchDiscPlan.backward_program_ext, whose weight-gradient and dgamma / dbeta
+    launches then run.  Every discriminator parameter gradient against the oracle's and against the fused path's
+    (a second pass on the same inputs), by the file's rule: L2-relative below 2e-3 with no kink flip, below 5e-2 with
+    at most 3."""
+    from mpgan_amd.gan import adversarial_loss
+    from mpgan_amd.gan_patch import perceptual_loss
+    ours, ref, R = _pair()
+    gen = torch.Generator().manual_seed(22)
+    xf = torch.rand(2, 1, 16, 16, 16, generator=gen) * 2 - 1
+    xr = torch.rand(2, 1, 16, 16, 16, generator=gen) * 2 - 1
+    # oracle
+    vf, af = ref(xf)
+    _, ar = ref(xr)
+    (1e6 * R.perceptual_loss(af, ar).sum() + R.adversarial_loss(vf, torch.ones_like(vf))).backward()
+    # fused path
+    v1, t1 = ours(xf.cuda())
+    _, t1r = ours(xr.cuda())
+    (1e6 * perceptual_loss(t1, t1r).sum() + adversarial_loss(v1, torch.ones_like(v1))).backward()
+    fused = {name: p.grad.detach().clone() for name, p in ours.named_parameters()}
+    ours.zero_grad()
+    # the reference's body on the returned dicts
+    v2, t2 = ours(xf.cuda())
+    _, t2r = ours(xr.cuda())
+    body = _reference_perceptual_loss(t2, t2r)
+    flips = _kink_flips(t2.tapset, ref, xf) + _kink_flips(t2r.tapset, ref, xr)  # (before backward releases the passes)
+    (1e6 * body.sum() + adversarial_loss(v2, torch.ones_like(v2))).backward()
+    assert flips <= 3, flips
+    tol = 2e-3 if flips == 0 else 5e-2
+    rp = dict(ref.named_parameters())
+    for name, p in ours.named_parameters():
+        if name in ("model_conv.0.bias", "model_conv.3.bias", "model_conv.6.bias", "model_conv.9.bias"):
+            continue   # pre-norm conv biases: exactly-zero true gradient, rounding noise on both sides
+        e_ref, e_fused = _l2rel(p.grad, rp[name].grad), _l2rel(p.grad, fused[name])
+        print(f"{name}: vs oracle {e_ref:.3e}, vs fused {e_fused:.3e}, flips {flips}")
+        assert e_ref < tol and e_fused < tol, (name, e_ref, e_fused, flips)
+
+
 def test_perceptual_loss_on_plain_mappings_runs_through_the_library():
     """`perceptual_loss` given anything but two TapDicts (taps a caller materialised, detached or re-keyed) restates the
     reference's body (test_runs/GAN.py:288-298) over the library's own L1 / axpby kernels: same value as torch's

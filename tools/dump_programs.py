@@ -1,20 +1,27 @@
 #!/usr/bin/env python3
-"""The frozen launch lists of the bf16-storage discriminator plans, in a form that can be diffed across commits
+"""The frozen launch lists of the discriminator plans, fp32 and bf16 storage, in a form that can be diffed across commits
 (development aid: builds the plans, launches nothing).
 
-    python tools/dump_programs.py                                    # variant A and B, every program
-    MPGAN_FUSE_BWD_STATS_BF16=1 python tools/dump_programs.py        # variant A train with the fused norm-backward sums
+    python tools/dump_programs.py [--storage {bf16,f32,both}]        # variant A and B, every program
+    python tools/dump_programs.py --tree DIR                         # the same of another built checkout (the parent commit)
+    MPGAN_FUSE_BWD_STATS_BF16=1 python tools/dump_programs.py        # bf16 variant A train with the fused norm-backward sums
+    MPGAN_DBG_NO_FUSE_BWD_STATS=1 python tools/dump_programs.py      # fp32 variant A train without them
 
 One line per call: index, name, desc, tag, lane, the C entry and its arguments.  Every pointer (an argument or a structure
 field the C signature declares as one) is replaced by an ordinal in order of first appearance within its plan (p0, p1,
 ...), so that the aliasing pattern is compared and the addresses are not; byref structures are expanded field by field.
 Needs an MI355X only because the plans allocate their tensors there."""
+import argparse
 import ctypes as C
 import os
 import sys
 
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, HERE)
+_ap = argparse.ArgumentParser()
+_ap.add_argument("--storage", default="both", choices=("bf16", "f32", "both"))
+_ap.add_argument("--tree", default=HERE, help="a built checkout to import the package from")
+ARGS = _ap.parse_args()
+sys.path.insert(0, os.path.abspath(ARGS.tree))
 
 import torch  # noqa: E402
 from mpgan_amd import engine  # noqa: E402
@@ -94,16 +101,65 @@ def variant_b(shape, n):
         dump(f"{name} eval fwd keep_taps={keep}", ev.fwd, Ordinals())
 
 
+def variant_a_f32(shape, n):
+    """Train forward / backward with all gradients and as the G step takes them (input gradient only), and the eval
+    forward; under MPGAN_DBG_NO_FUSE_BWD_STATS the all-gradients train pair alone."""
+    torch.manual_seed(0)
+    d = Discriminator((1,) + shape, dimensions=len(shape), device=DEV)
+    store, name = d.store, f"A f32 {'x'.join(map(str, shape))} n{n}"
+    steps = [("train", dict(want_input_grad=True, want_param_grads=True))]
+    if engine._FUSE_BWD_STATS:
+        steps.append(("G-step train", dict(want_input_grad=True, want_param_grads=False)))
+    for what, kw in steps:
+        plan, ords = engine.DiscPlan(d, store, n, shape, want_backward=True, **kw), Ordinals()
+        dump(f"{name} {what} fwd", plan.fwd, ords)
+        dump(f"{name} {what} bwd", plan.bwd, ords)
+    if engine._FUSE_BWD_STATS:
+        ev = engine.DiscPlan(d, store, n, shape, want_backward=False, want_input_grad=False, want_param_grads=False,
+                             training=False)
+        dump(f"{name} eval fwd", ev.fwd, Ordinals())
+
+
+def variant_b_f32(shape, n):
+    torch.manual_seed(0)
+    d = PatchDiscriminator((1,) + shape, dimensions=len(shape), patch=shape[0], device=DEV)
+    store, ords, name = d.store, Ordinals(), f"B f32 {'x'.join(map(str, shape))} n{n}"
+    kw = dict(want_backward=True, want_input_grad=True, want_param_grads=True)
+    plan, peer = engine.PatchDiscPlan(d, store, n, shape, **kw), engine.PatchDiscPlan(d, store, n, shape, **kw)
+    dump(f"{name} train fwd", plan.fwd, ords)
+    dump(f"{name} backward_program(None)", plan.backward_program(None), ords)
+    dump(f"{name} backward_program(peer)", plan.backward_program(peer), ords)
+    plan._ext_buffers()
+    dump(f"{name} backward_program_ext(None)", plan.backward_program_ext(None), ords)
+    dump(f"{name} backward_program_ext(peer)", plan.backward_program_ext(peer), ords)
+    for keep in (True, False):
+        ev = engine.PatchDiscPlan(d, store, n, shape, want_backward=False, want_input_grad=False, want_param_grads=False,
+                                  training=False, keep_taps=keep)
+        dump(f"{name} eval fwd keep_taps={keep}", ev.fwd, Ordinals())
+
+
 def main():
+    bf16, f32 = ARGS.storage in ("bf16", "both"), ARGS.storage in ("f32", "both")
     if engine._FUSE_BWD_STATS_BF16:                          # the second invocation: the first shape with fused rows
         print("# MPGAN_FUSE_BWD_STATS_BF16=1")
-        if not (variant_a((40, 40), 3) or variant_a((24, 24, 24), 2)):
+        if bf16 and not (variant_a((40, 40), 3) or variant_a((24, 24, 24), 2)):
             print("# neither small shape has fused rows: 3-D size 48, n 1")
             variant_a((48, 48, 48), 1)
         return
-    variant_a((40, 40), 3)
-    variant_a((24, 24, 24), 2)
-    variant_b((16, 16, 16), 2)
+    if not engine._FUSE_BWD_STATS:                           # the third: fp32 variant A with the separate reduce passes
+        print("# MPGAN_DBG_NO_FUSE_BWD_STATS=1")
+        if f32:
+            variant_a_f32((40, 40), 3)
+            variant_a_f32((24, 24, 24), 2)
+        return
+    if bf16:
+        variant_a((40, 40), 3)
+        variant_a((24, 24, 24), 2)
+        variant_b((16, 16, 16), 2)
+    if f32:
+        variant_a_f32((40, 40), 3)
+        variant_a_f32((24, 24, 24), 2)
+        variant_b_f32((16, 16, 16), 2)
 
 
 if __name__ == "__main__":
