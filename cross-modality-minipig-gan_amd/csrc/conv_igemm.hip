@@ -543,7 +543,8 @@ __global__ __launch_bounds__(256) void gather_conv_dma_kernel(const GatherConv p
   asm volatile("s_barrier" ::: "memory");                // every fragment read done: the LDS becomes the epilogue's
   MPGAN_STAMP(p, 2);
   MPGAN_STAMP(p, 3);
-  conv_epilogue<BN, TM, TN, WN>(p, ph, acc, lds_all, m0, n0, Mtot, stats_row, false, tid, true, bias_pre);
+  // (output path C for the 64- and 128-wide tiles: the discriminator's backward-data launches with fused norm-backward sums)
+  conv_epilogue<BN, TM, TN, WN, (BN >= 64)>(p, ph, acc, lds_all, m0, n0, Mtot, stats_row, false, tid, true, bias_pre);
 }
 
 // ---------------------------------------------------------------------------

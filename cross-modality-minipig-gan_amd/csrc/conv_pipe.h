@@ -3,6 +3,7 @@
 // bf16 on their way into LDS (fp32 storage in HBM, fp32 accumulation; config C5's generator) -- two translation
 // units so that they compile side by side.
 #pragma once
+#include <type_traits>
 #include "mpgan_common.h"
 #include "conv_geom.h"
 #include "lds_dma.h"
@@ -13,9 +14,37 @@ constexpr int BM = 128;
 constexpr int BK = 32;
 constexpr int PITCH = BK + 4;
 
+// `make DEV=1 WALK=1` (libmpgan_hip_walk.so): the BwdStats epilogue as the element-wise walk only, for A/B timing of
+// output path C on one box.  The product build has the switch compiled out.
+#ifndef MPGAN_BWD_EPILOGUE_WALK
+#define MPGAN_BWD_EPILOGUE_WALK 0
+#endif
+
+// One element of the fused norm-backward sums (BwdStats), as norm_bwd_reduce_kernel (norm_ops.hip) forms them.  In the
+// instances of conv_epilogue that have output path C, both paths that leave these sums add through here.  The roundings
+// are spelled out (two fused multiply-adds, everything else rounded on its own: what the compiler made of the walk in
+// those instances before path C existed) instead of left to its contraction, which differs with the surrounding code,
+// so that a channel's sums are the same bits whichever path a launch takes.
+__device__ __forceinline__ void bwd_sums_add(float v, float zz, float sc, float sh, float mu, float is, bool leaky, float slope,
+                                             float& b1, float& b2, float& b3) {
+#pragma clang fp contract(off)
+  const float y = __builtin_fmaf(zz, sc, sh);
+  const float zh = (zz - mu) * is;
+  const bool neg = leaky && y < 0.f;
+  const float gy = neg ? v * slope : v;
+  const float t3 = neg ? v * y : 0.f;
+  b1 += gy;
+  b2 = __builtin_fmaf(gy, zh, b2);
+  b3 += t3;
+}
+
 // Shared epilogue: row -> output pixel map through LDS, bias / residual / tanh,
 // optional fused BatchNorm statistics.  Called after the K-loop's final barrier.
-template <int BN, int TM, int TN, int WN>
+//   BWC: compile output path C (the 16-byte store form of the fused norm-backward sums) into this instance.  Only the
+//        64- and 128-wide LDS-DMA kernels ask for it -- they run the discriminator's backward-data launches, the only
+//        large ones that carry `bwd.part`; every other instance keeps the element-wise walk for that case, with its sums
+//        written as before, and is compiled without path C's registers and code.
+template <int BN, int TM, int TN, int WN, bool BWC = false>
 __device__ __forceinline__ void conv_epilogue(const GatherConv& p, const Phase& ph, f32x16 (&acc)[TM][TN], float* lds,
                                               long m0, int n0, long Mtot, int stats_row, bool zero_rows = false,
                                               int tid = threadIdx.x, bool active = true, const float* bias_pre = nullptr) {
@@ -29,6 +58,19 @@ __device__ __forceinline__ void conv_epilogue(const GatherConv& p, const Phase& 
   const int ksplit_id = p.ksplit > 1 ? (int)(xcd_remap(blockIdx.x, gridDim.x) / (unsigned)(p.ntiles * p.mtiles * (p.packed ? 1 : p.nphase))) : 0;
   // ---- epilogue: row -> output pixel map through LDS, then bias/resid/tanh ----
   int* rowpix = reinterpret_cast<int*>(lds);
+  // fused norm-backward sums of the produced gradient (BwdStats)
+  const bool bw = p.bwd.part != nullptr;
+  // Output path C (below) addresses `out` and `z` as "uniform base + unsigned 32-bit BYTE offset", as the K loops do
+  // for their operands; rows' byte offsets travel through LDS beside the row -> pixel map (ints 128..383).
+  int* rowoo = rowpix + BM;
+  int* rowoz = rowpix + 2 * BM;
+  bool bw_vec = false;
+  if constexpr (BWC) if (bw) {
+    const unsigned long long npix = (unsigned long long)p.N * p.Do * p.Ho * p.Wo;
+    bw_vec = !MPGAN_BWD_EPILOGUE_WALK && !p.epi.scale && !p.resid && !p.tanh_out && (Cout % 4 == 0) && (p.ldo % 4 == 0) &&
+             ((reinterpret_cast<uintptr_t>(p.out) & 15) == 0) && Cout <= p.ldo && Cout <= p.bwd.ldz &&
+             npix * (unsigned)p.ldo * 4ull <= 0xFFFFFFFFull && npix * (unsigned)p.bwd.ldz * 4ull <= 0xFFFFFFFFull;
+  }
   if (active && tid < BM) {
     const unsigned m = (unsigned)m0 + tid;
     int pix = -1;
@@ -43,6 +85,11 @@ __device__ __forceinline__ void conv_epilogue(const GatherConv& p, const Phase& 
       if (oz < p.Do && oy < p.Ho && ox < p.Wo) pix = ((n * p.Do + oz) * p.Ho + oy) * p.Wo + ox;
     }
     rowpix[tid] = pix;
+    if (bw_vec) {
+      const unsigned upix = pix < 0 ? 0u : (unsigned)pix;
+      rowoo[tid] = (int)(upix * (unsigned)p.ldo * 4u);
+      rowoz[tid] = (int)(upix * (unsigned)p.bwd.ldz * 4u);
+    }
   }
   __syncthreads();
   MPGAN_STAMP(p, 4);    // epilogue: row -> pixel map ready
@@ -84,18 +131,17 @@ __device__ __forceinline__ void conv_epilogue(const GatherConv& p, const Phase& 
     esh[tn] = okc ? p.epi.shift[cov[tn]] : 0.f;
     esl[tn] = okc ? p.epi.slope[cov[tn]] : 1.f;
   }
-  // fused norm-backward sums of the produced gradient (BwdStats): per-column vectors and running sums
-  const bool bw = p.bwd.part != nullptr;
   // Output path A (the usual one): every 32 x 32 accumulator tile goes through a wave-private LDS transpose and leaves
   // as 16-byte stores -- a lane holds ONE channel of 16 rows, so direct stores are 4 bytes per lane and 16 store
   // instructions per tile; the phase stamps show 3-6.5 us of every K-stepped launch in issuing them (all blocks end
-  // their K loops together and the scalar stores queue up).  Path B (below): the element-wise walk, kept for the
-  // BwdStats form (its sums need each element beside its z) and for unaligned / odd-width outputs.
+  // their K loops together and the scalar stores queue up).  Path C (below) is its BwdStats form: the lane keeps its
+  // channel's sums (they need each element beside its z) and the stored values take the same transpose.  Path B: the
+  // element-wise walk, for unaligned / odd-width outputs and operands of 4 GiB or more.
   const bool vec_out = !bw && (Cout % 4 == 0) && (ldo % 4 == 0) && ((reinterpret_cast<uintptr_t>(gout) & 15) == 0) &&
                        (!gres || ((ldr % 4 == 0) && (reinterpret_cast<uintptr_t>(gres) & 15) == 0));
   if (vec_out) {
     constexpr int TP = 36;                                 // pitch of the transpose tile: conflict-free both ways
-    float* wt = lds + 2048 + wid * 32 * TP;                // clear of rowpix (ints 0..511) and the statistics area (1024..)
+    float* wt = lds + 2048 + wid * 32 * TP;                // clear of the row maps (ints 0..383), nvp (int 512) and the statistics area (1024..)
     if (active) {
 #pragma unroll
       for (int tm = 0; tm < TM; ++tm)
@@ -137,8 +183,83 @@ __device__ __forceinline__ void conv_epilogue(const GatherConv& p, const Phase& 
   }
   const bool bleaky = p.bwd.leaky != 0;
   const float bslope = p.bwd.slope;
+  // Output path C.  The sums are formed as path B forms them -- a lane is one channel and adds its elements in the
+  // order tm, then r, with the same expressions -- so the partial rows are the same bits.  What changes is how the
+  // elements travel: the tile's z values come in ONE batch of 32-bit-offset loads in front of all stores, the stored
+  // values leave through the wave-private transpose as 16-byte stores, and a tile whose rows all have a pixel and whose
+  // columns all have a channel (block-uniform: most tiles of a launch) runs without per-element tests.
+  if constexpr (BWC) if (active && bw_vec) {
+    constexpr int TP = 36;
+    // the transpose tiles (floats 2048..) must stay clear of the [WMB][3][BN] sums area at lds + 1024, which other waves
+    // may be writing while this one still transposes
+    static_assert((4 / WN) * 3 * BN <= 1024, "the norm-backward sums area would reach into the transpose tiles");
+    float* wt = lds + 2048 + wid * 32 * TP;               // clear of the row maps (ints 0..383), nvp (int 512) and the sums area
+    const char* __restrict__ zb = reinterpret_cast<const char*>(p.bwd.z);
+    char* ob = reinterpret_cast<char*>(gout);
+    const int c4 = lane & 7, rq = lane >> 3;
+    const bool interior = n0 + BN <= Cout && __ballot((rowpix[lane] | rowpix[lane + 64]) < 0) == 0ull;
+    auto walk = [&](auto full) {
+      constexpr bool FULL = decltype(full)::value;
+      float zv[TM][16][TN];
+      unsigned live[TM];                                  // bit r: the lane's row r has a pixel
+#pragma unroll
+      for (int tm = 0; tm < TM; ++tm) {
+        const int rb = (wm * TM + tm) * 32 + 4 * lh;      // the lane's rows: rb + 8 j + i, r = 4 j + i
+        live[tm] = 0u;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int4 oz = *reinterpret_cast<const int4*>(rowoz + rb + 8 * j);
+          int4 px = make_int4(0, 0, 0, 0);
+          if constexpr (!FULL) px = *reinterpret_cast<const int4*>(rowpix + rb + 8 * j);
+          const int ozi[4] = {oz.x, oz.y, oz.z, oz.w}, pxi[4] = {px.x, px.y, px.z, px.w};
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            if constexpr (!FULL) live[tm] |= (pxi[i] >= 0 ? 1u : 0u) << (4 * j + i);
+#pragma unroll
+            for (int tn = 0; tn < TN; ++tn) {
+              const unsigned off = (unsigned)ozi[i] + (unsigned)cov[tn] * 4u;
+              if constexpr (FULL) zv[tm][4 * j + i][tn] = *reinterpret_cast<const float*>(zb + off);
+              else zv[tm][4 * j + i][tn] = (pxi[i] >= 0 && cov[tn] < Cout) ? *reinterpret_cast<const float*>(zb + off) : 0.f;
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int tm = 0; tm < TM; ++tm) {
+        unsigned so[4];                                   // the rows this lane stores: rq + 8 k, columns 4 c4 .. + 3
+        int sp[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          so[k] = (unsigned)rowoo[(wm * TM + tm) * 32 + rq + 8 * k];
+          sp[k] = FULL ? 0 : rowpix[(wm * TM + tm) * 32 + rq + 8 * k];
+        }
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const float v = acc[tm][tn][r] + bv[tn];
+            wt[((r & 3) + 8 * (r >> 2) + 4 * lh) * TP + li] = v;
+            if (FULL || ((live[tm] >> r) & 1u))
+              bwd_sums_add(v, zv[tm][r][tn], bsc[tn], bsh[tn], bmu[tn], bis[tn], bleaky, bslope, b1[tn], b2[tn], b3[tn]);
+            // (keeps each column's chain scalar and in program order: left alone, the compiler pairs the two columns'
+            // arithmetic into packed operations across the whole unrolled walk and needs 70 more registers for it --
+            // past 256, the second resident block is gone)
+            asm volatile("" : "+v"(b1[tn]), "+v"(b2[tn]), "+v"(b3[tn]));
+          }
+          const unsigned cob = (unsigned)(n0 + (wn * TN + tn) * 32 + 4 * c4) * 4u;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const float4 v = *reinterpret_cast<const float4*>(wt + (rq + 8 * k) * TP + 4 * c4);
+            if (FULL || (sp[k] >= 0 && cob < (unsigned)Cout * 4u)) *reinterpret_cast<float4*>(ob + (so[k] + cob)) = v;
+          }
+        }
+      }
+    };
+    if (interior) walk(std::true_type{});
+    else walk(std::false_type{});
+  }
   // row-major walk: the 64-bit pixel offset is formed once per row, not once per element
-  if (active && !vec_out)
+  if (active && !vec_out && !bw_vec)
 #pragma unroll
   for (int tm = 0; tm < TM; ++tm) {
     // BwdStats: the tile's z values are fetched in ONE batch in front of the stores (loads between the stores could
@@ -170,7 +291,9 @@ __device__ __forceinline__ void conv_epilogue(const GatherConv& p, const Phase& 
         if (rrow) v += rrow[cov[tn]];
         if (tanh_out) v = tanhf(v);
         orow[cov[tn]] = v;
-        if (bw) {                            // as norm_bwd_reduce_kernel (norm_ops.hip), element by element
+        if constexpr (BWC) {                 // (the instances with path C: both paths through one helper, same bits)
+          if (bw) bwd_sums_add(v, zv[r][tn], bsc[tn], bsh[tn], bmu[tn], bis[tn], bleaky, bslope, b1[tn], b2[tn], b3[tn]);
+        } else if (bw) {                     // as norm_bwd_reduce_kernel (norm_ops.hip), element by element
           const float zz = zv[r][tn];
           const float y = zz * bsc[tn] + bsh[tn];
           const float zh = (zz - bmu[tn]) * bis[tn];
