@@ -106,6 +106,10 @@ SIGNATURES = {
     "mpgan_debug_clock_khz": (_I, []),
     "mpgan_linear1_backward": (_I, [_P, _PR, _I, _L, _I, _P, _P, _P, _P, _P, _F, _P]),
     "mpgan_sigmoid_bce": (_I, [_P, _I, _F, _F, _P, _P, _P, _P]),
+    # Markovian (PatchGAN) head
+    "mpgan_maphead_forward": (_I, [_P, _PR, _I, _I3, _I, _I3, _P, _P, _P, _P, _P]),
+    "mpgan_maphead_workspace": (_L, [_I, _I3, _I, _I3]),
+    "mpgan_maphead_backward": (_I, [_P, _PR, _I, _I3, _I, _I3, _P, _P, _P, _P, _P, _F, _P, _L, _P]),
     "mpgan_l1_partials": (_I, []),
     "mpgan_l1_loss": (_I, [_P, _P, _L, _F, _P, _P, _P, _P]),
     "mpgan_metric_partials": (_I, []),

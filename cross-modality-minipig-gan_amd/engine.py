@@ -1796,6 +1796,46 @@ class LinearHead:
                  _p(gv(self.lin.weight)), _p(gv(self.lin.bias)), 1.0, keep=(pc, pro, src, g_src))
 
 
+class MapHead:
+    """Variant A's Markovian (PatchGAN) head, a last valid Conv(256, 1, k) -> Sigmoid on the last layer's tensor `src`
+    read through `pro` (see LinearHead): a map of per-receptive-field verdicts, out = last - k + 1 per dimension.  One
+    fp32 class for all four plans: the bf16 and the eval stacks hand it an fp32 activated tensor and no prologue."""
+
+    def __init__(self, disc, store: ParamStore, n: int, g_last: ConvGeom, spatial):
+        dev = store.flat.device
+        self.conv, self.n, self.c = disc.model_head[0], n, g_last.cout
+        self.in_dhw = tuple(g_last.out_dhw)
+        self.k = _t3(self.conv.kernel_size, disc.dimensions, 1)
+        if min(i - k for i, k in zip(self.in_dhw, self.k)) < 0:
+            raise ValueError(f"last feature map {self.in_dhw} smaller than the head's kernel {self.k} for input {spatial}")
+        self.map_dhw = tuple(i - k + 1 for i, k in zip(self.in_dhw, self.k))
+        self.P = math.prod(self.map_dhw)
+        self.rconv = store.register_conv(self.conv, cout=1, cin=self.c, taps=math.prod(self.k))
+        self.logit, self.prob = torch.empty(n * self.P, device=dev), torch.empty(n * self.P, device=dev)
+        self._in3, self._k3 = (C.c_int32 * 3)(*self.in_dhw), (C.c_int32 * 3)(*self.k)
+
+    def emit_forward(self, prog, store: ParamStore, src, pro):
+        pc = pro.c() if pro is not None else None
+        prog.add("maphead_forward", lib().mpgan_maphead_forward, src.data_ptr(), C.byref(pc) if pc is not None else None,
+                 self.n, self._in3, self.c, self._k3, store.wp(self.rconv).data_ptr(), self.conv.bias.data_ptr(),
+                 self.logit.data_ptr(), self.prob.data_ptr(), keep=(pc, pro, src, self))
+
+    def emit_backward(self, prog, store: ParamStore, src, pro, g_src, want_param_grads: bool):
+        """g_prob (allocated here; the caller fills it) -> g_src, the gradient w.r.t. what `src` holds after `pro`."""
+        gv = store.grad_view if want_param_grads else (lambda p: None)
+        L, pc = lib(), (pro.c() if pro is not None else None)
+        self.g_prob, dlogit = torch.empty_like(self.prob), torch.empty_like(self.prob)
+        self.dlogit = dlogit                        # read by tests: what maphead_backward was given
+        ws_bytes = ops.maphead_workspace(self.n, self.in_dhw, self.c, self.k) if want_param_grads else 0
+        ws = torch.empty(max(ws_bytes // 4, 4), device=self.prob.device) if want_param_grads else None
+        prog.add("sigmoid_backward", L.mpgan_sigmoid_backward, self.g_prob.data_ptr(), self.prob.data_ptr(),
+                 self.n * self.P, dlogit.data_ptr(), keep=(dlogit, self))
+        prog.add("maphead_backward", L.mpgan_maphead_backward, src.data_ptr(), C.byref(pc) if pc is not None else None,
+                 self.n, self._in3, self.c, self._k3, store.wp(self.rconv).data_ptr(), dlogit.data_ptr(),
+                 g_src.data_ptr(), _p(gv(self.conv.weight)), _p(gv(self.conv.bias)), 1.0, _p(ws), ws_bytes,
+                 keep=(pc, pro, src, g_src, ws))
+
+
 class PatchHead:
     """Variant B's head, Flatten -> Linear(F,64) -> Linear(64,1) -> Sigmoid, on the last layer's tensor `src` read
     through `pro` (see LinearHead).  Linear(F,64) is a conv whose kernel spans the last feature map (packing realises
@@ -1891,7 +1931,8 @@ class _StorageBF16:
 # --------------------------------------------------------------------------
 class DiscPlan(_DiscPlanBase):
     """4 x (valid conv -> BN -> LeakyReLU 0.2) -> Flatten -> Linear(F,1) -> Sigmoid
-    (code/GAN/GAN_final.py:159-209)."""
+    (code/GAN/GAN_final.py:159-209); with disc.head == "markovian" the head is Conv(256, 1, 4) -> Sigmoid instead
+    (MapHead: `logit` / `prob` then hold a map per sample)."""
 
     def __init__(self, disc, store: ParamStore, n: int, spatial: Sequence[int], *, want_backward: bool,
                  want_input_grad: bool, want_param_grads: bool, training: bool = True):
@@ -1902,7 +1943,8 @@ class DiscPlan(_DiscPlanBase):
         live parameters and running statistics; nothing else of the module is touched."""
         st = self._setup(disc, store, n, spatial, "discriminator input", training=training, want_backward=want_backward,
                          raw_z=training)
-        head = self.head = LinearHead(disc, store, n, st.geoms[-1], spatial)
+        head_cls = MapHead if getattr(disc, "head", "linear") == "markovian" else LinearHead
+        head = self.head = head_cls(disc, store, n, st.geoms[-1], spatial)
         self.logit, self.prob = head.logit, head.prob
         scratch = Scratch(store.flat.device)
         if training:       # eval: no statistics partials, no weight-gradient workspace

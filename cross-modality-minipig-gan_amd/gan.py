@@ -219,7 +219,7 @@ class GAN(nn.Module):
                  one_sided_label_value=0.9, *, dimensions: Optional[int] = None, norm: str = "batch",
                  n_unet_blocks: int = 6, unet_channels=(16, 32, 64, 128), unet_strides=(2, 2, 2), device="cuda",
                  storage_dtype: str = "f32", mi_weight: float = 0.0, mi_bins: int = 23,
-                 ssim_weight: float = 0.0, **kwargs):
+                 ssim_weight: float = 0.0, d_head: str = "linear", **kwargs):
         super().__init__()
         if mi_weight < 0:
             raise ValueError(f"mi_weight must be >= 0, got {mi_weight!r}")
@@ -228,7 +228,8 @@ class GAN(nn.Module):
         if dimensions is None:
             dimensions = 3 if depth is not None else 2
         self.hparams = types.SimpleNamespace(latent_dim=latent_dim, g_lr=g_lr, d_lr=d_lr, b1=b1, b2=b2,
-                                             batch_size=batch_size, one_sided_label_value=one_sided_label_value)
+                                             batch_size=batch_size, one_sided_label_value=one_sided_label_value,
+                                             d_head=d_head)
         data_shape = (channels, width, height) + ((depth,) if dimensions == 3 else ())
         # storage_dtype="bf16" is config C5: the discriminator stores its activations in bf16 and the generator's
         # matrix products take bf16 operands (fp32 storage: its launches are matrix-bound, not byte-bound)
@@ -236,7 +237,7 @@ class GAN(nn.Module):
                                          channels=unet_channels, strides=unet_strides, device=device,
                                          matmul_dtype="bf16" if storage_dtype == "bf16" else "f32")
         self.discriminator = Discriminator(data_shape, dimensions=dimensions, device=device,
-                                           storage_dtype=storage_dtype)
+                                           storage_dtype=storage_dtype, head=d_head)
         # opt-in auxiliary generator loss (not in the reference's trainer): mi_weight * (-MI(G(t1w), t2w)) from Parzen
         # windows over the tanh output's range; with the default 0 no launch and no logged name is added
         self.mi_weight = float(mi_weight)
@@ -256,6 +257,13 @@ class GAN(nn.Module):
     def reconstruction_loss(self, y_hat, y):
         return reconstruction_loss(y_hat, y)
 
+    def _labels(self, validity, value: float):
+        """The BCE target of one discriminator output: (B, 1) as in the reference; with d_head="markovian" the shape of
+        the validity map, every verdict getting the same label."""
+        if self.hparams.d_head == "markovian":
+            return torch.full_like(validity, float(value))
+        return torch.full((validity.shape[0], 1), float(value), device=validity.device, dtype=validity.dtype)
+
     def log(self, name, value, **kw):
         """Lightning's self.log: scalars stay on the device (no per-step sync)."""
         self.logged[name] = value.detach()
@@ -265,8 +273,8 @@ class GAN(nn.Module):
         if optimizer_idx == 0:                      # GAN_final.py:254-273
             generated_imgs = self(t1w_images)
             self.generated_imgs = generated_imgs
-            valid = torch.ones(t1w_images.shape[0], 1, device=t1w_images.device, dtype=t1w_images.dtype)
-            g_adv_loss = self.adversarial_loss(self.discriminator(generated_imgs), valid)
+            d_fake = self.discriminator(generated_imgs)
+            g_adv_loss = self.adversarial_loss(d_fake, self._labels(d_fake, 1.0))
             self.log("g_adv_loss", g_adv_loss)
             g_recon_loss = self.reconstruction_loss(generated_imgs, t2w_images)
             self.log("g_recon_loss", g_recon_loss)
@@ -282,17 +290,16 @@ class GAN(nn.Module):
             self.log("g_loss", g_loss)
             return g_loss
         if optimizer_idx == 1:                      # GAN_final.py:276-296
-            valid = torch.full((t1w_images.shape[0], 1), float(self.hparams.one_sided_label_value),
-                               device=t1w_images.device, dtype=t1w_images.dtype)
             # (D(real) and G(t1w) are independent, and rounds 1-3 carried an opt-in mode that ran the generator's
             #  forward on a high-priority stream underneath D(real).  It measured nothing beyond run-to-run spread
             #  -- 59.1 vs 58.6 ms at C3, 174.3 vs 175.8 ms at C5 -- while stretching D's kernels up to 3x, and its first
             #  use in a process once ended in a host SIGSEGV inside hipStreamWaitEvent on that stream: removed in
             #  round 4)
-            real_loss = self.adversarial_loss(self.discriminator(t2w_images), valid)
+            d_real = self.discriminator(t2w_images)
+            real_loss = self.adversarial_loss(d_real, self._labels(d_real, self.hparams.one_sided_label_value))
             generated = self(t1w_images).detach()
-            fake = torch.zeros(t1w_images.shape[0], 1, device=t1w_images.device, dtype=t1w_images.dtype)
-            fake_loss = self.adversarial_loss(self.discriminator(generated), fake)
+            d_fake = self.discriminator(generated)
+            fake_loss = self.adversarial_loss(d_fake, self._labels(d_fake, 0.0))
             d_loss = scalar_axpby(real_loss, 0.5, fake_loss, 0.5)
             self.log("d_loss", d_loss)
             return d_loss
@@ -305,11 +312,10 @@ class GAN(nn.Module):
         device scalars (no host sync); with mi_weight > 0 also val_g_mi_loss and with ssim_weight > 0 also
         val_g_ssim_loss, which val_g_loss then includes."""
         t1w_images, t2w_images = batch["t1w"], batch["t2w"]
-        dev, dt, n = t1w_images.device, t1w_images.dtype, t1w_images.shape[0]
         with torch.no_grad(), eval_modes(self.generator, self.discriminator):
             generated_imgs = self(t1w_images)
             d_fake = self.discriminator(generated_imgs)
-            g_adv_loss = self.adversarial_loss(d_fake, torch.ones(n, 1, device=dev, dtype=dt))
+            g_adv_loss = self.adversarial_loss(d_fake, self._labels(d_fake, 1.0))
             g_recon_loss = self.reconstruction_loss(generated_imgs, t2w_images)
             g_loss = scalar_axpby(g_adv_loss, 1.0, g_recon_loss, 1.0)
             if self.mi_loss is not None:
@@ -318,9 +324,9 @@ class GAN(nn.Module):
             if self.ssim_loss is not None:
                 g_ssim_loss = self.ssim_loss(generated_imgs, t2w_images)
                 g_loss = scalar_axpby(g_loss, 1.0, g_ssim_loss, self.ssim_weight)
-            valid = torch.full((n, 1), float(self.hparams.one_sided_label_value), device=dev, dtype=dt)
-            real_loss = self.adversarial_loss(self.discriminator(t2w_images), valid)
-            fake_loss = self.adversarial_loss(d_fake, torch.zeros(n, 1, device=dev, dtype=dt))
+            d_real = self.discriminator(t2w_images)
+            real_loss = self.adversarial_loss(d_real, self._labels(d_real, self.hparams.one_sided_label_value))
+            fake_loss = self.adversarial_loss(d_fake, self._labels(d_fake, 0.0))
             d_loss = scalar_axpby(real_loss, 0.5, fake_loss, 0.5)
         out = {"val_g_adv_loss": g_adv_loss, "val_g_recon_loss": g_recon_loss, "val_g_loss": g_loss, "val_d_loss": d_loss}
         if self.mi_loss is not None:

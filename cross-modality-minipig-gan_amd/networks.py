@@ -290,7 +290,7 @@ class _DiscFn(torch.autograd.Function):
         spatial = _spatial(x, disc.dimensions)
         n = x.shape[0]
         store = disc.store
-        key = (n, spatial, need_bwd, want_in, want_par)
+        key = (n, spatial, need_bwd, want_in, want_par, disc.head)
         plan_cls = DiscPlanBF16 if disc.storage_dtype == "bf16" else DiscPlan
         plan = disc._acquire(key, lambda: plan_cls(disc, store, n, spatial, want_backward=need_bwd,
                                                    want_input_grad=want_in, want_param_grads=want_par))
@@ -303,7 +303,7 @@ class _DiscFn(torch.autograd.Function):
         finally:
             if not need_bwd:
                 io.reset()
-        prob = plan.prob.view(n, 1).clone()
+        prob = plan.prob.view(disc.validity_shape(n, spatial)).clone()
         if need_bwd:
             ctx.lease = lease
             ctx.shape = x.shape
@@ -341,7 +341,7 @@ def _disc_eval(disc, x):
         spatial = _spatial(x, disc.dimensions)
         n = x.shape[0]
         store = disc.store
-        key = ("eval", n, spatial, disc.storage_dtype)
+        key = ("eval", n, spatial, disc.storage_dtype, disc.head)
         plan_cls = DiscPlanBF16 if disc.storage_dtype == "bf16" else DiscPlan
         plan = disc._acquire(key, lambda: plan_cls(disc, store, n, spatial, want_backward=False, want_input_grad=False,
                                                    want_param_grads=False, training=False))
@@ -351,7 +351,7 @@ def _disc_eval(disc, x):
             plan.x_in.view(-1).copy_(x.reshape(-1))
         try:
             plan.fwd.run()
-            return plan.prob.view(n, 1).clone()
+            return plan.prob.view(disc.validity_shape(n, spatial)).clone()
         finally:
             io.reset()
             lease.release()
@@ -364,15 +364,32 @@ def disc_feature_sizes(spatial: Sequence[int]):
     return sizes
 
 
+_MAP_HEAD_KERNEL = 4
+
+
+def disc_map_size(spatial: Sequence[int]):
+    """The validity map of the Markovian head for an input of `spatial`: the last feature map less 3 per dimension."""
+    return tuple(n - _MAP_HEAD_KERNEL + 1 for n in disc_feature_sizes(spatial)[-1])
+
+
 class Discriminator(_EngineModule):
     """code/GAN/GAN_final.py:159-209.  The reference hard-codes
     Linear(256*29*29*29, 1) for its 128^3 input (:201); in_features here is
-    computed from img_shape (the same number for 128^3)."""
+    computed from img_shape (the same number for 128^3).
 
-    def __init__(self, img_shape, use_perceptual=True, *, dimensions=3, device=None, storage_dtype="f32"):
+    head="markovian": the PatchGAN head the reference lists as a TODO (GAN_final.py:125) in place of the Linear one:
+    `model_head` = Conv(256, 1, kernel_size=4) -> Sigmoid on the last feature map, and forward returns a map
+    (B, 1, *disc_map_size(spatial)) of per-receptive-field verdicts; there is no `model_linear`, and the network is no
+    longer tied to one input size."""
+
+    def __init__(self, img_shape, use_perceptual=True, *, dimensions=3, device=None, storage_dtype="f32",
+                 head="linear"):
         super().__init__()
         if storage_dtype not in ("f32", "bf16"):
             raise ValueError(f"storage_dtype must be 'f32' or 'bf16', got {storage_dtype!r}")
+        if head not in ("linear", "markovian"):
+            raise ValueError(f"head must be 'linear' or 'markovian', got {head!r}")
+        self.head = head
         self.use_perceptual = use_perceptual
         self.img_shape = img_shape
         self.dimensions = dimensions
@@ -388,13 +405,26 @@ class Discriminator(_EngineModule):
         if min(last) < 1:
             raise ValueError(f"img_shape {img_shape} too small for the discriminator")
         self._last = last
-        self.model_linear = nn.Sequential(nn.Flatten(), nn.Linear(256 * int(np.prod(last)), 1), nn.Sigmoid())
+        if head == "markovian":
+            if min(last) < _MAP_HEAD_KERNEL:
+                raise ValueError(f"img_shape {img_shape} too small for the Markovian head: the last feature map {last} "
+                                 f"must be at least {_MAP_HEAD_KERNEL} per dimension (input side >= 26)")
+            self.model_head = nn.Sequential(Cv(256, 1, kernel_size=_MAP_HEAD_KERNEL, stride=1, bias=True), nn.Sigmoid())
+        else:
+            self.model_linear = nn.Sequential(nn.Flatten(), nn.Linear(256 * int(np.prod(last)), 1), nn.Sigmoid())
         if device is not None:
             self.to(device)
 
     def _register_extra(self, store):
+        if self.head == "markovian":           # a ConvNd: the store has registered it with the stack's convs
+            return
         lin = self.model_linear[1]
         store.register_conv(lin, cout=1, cin=256, taps=lin.in_features // 256)
+
+    def validity_shape(self, n: int, spatial: Sequence[int]):
+        """Shape of forward's result for a batch of n inputs of `spatial`: (n, 1), or (n, 1, *map) for the Markovian head
+        (one channel: NC(D)HW is layout-identical to the plan's channels-last buffer)."""
+        return (n, 1, *disc_map_size(spatial)) if self.head == "markovian" else (n, 1)
 
     def forward(self, img):
         """Train mode: batch statistics + running-stat updates.  Eval mode (code/GAN/inferrence.py:109-110 puts the

@@ -467,6 +467,44 @@ def bce_backward(prob, target, gout, dprob):
                                    dprob.data_ptr(), _stream()), "bce_backward")
 
 
+def _i3(v: Sequence[int]):
+    return (C.c_int32 * 3)(*[int(x) for x in v])
+
+
+def maphead_workspace(n: int, in_dhw: Sequence[int], c: int, k_dhw: Sequence[int]) -> int:
+    """Bytes of scratch maphead_backward needs for dw."""
+    need = int(lib().mpgan_maphead_workspace(n, _i3(in_dhw), c, _i3(k_dhw)))
+    if need < 0:
+        check(-2, "maphead_workspace")
+    return need
+
+
+def maphead_forward(z, p: Optional[Prologue], k_dhw: Sequence[int], w_perm, bias, logit, prob=None):
+    """The Markovian head's valid conv C -> 1 on the channels-last (N,D,H,W,C) z read through `p`: logit and
+    prob = sigmoid(logit), both (N, D-kd+1, H-kh+1, W-kw+1)."""
+    n, P, ld = _cl(z, "maphead_forward z")
+    c = z.shape[-1]
+    if ld != c:
+        raise ValueError("maphead_forward: z must be dense")
+    check(lib().mpgan_maphead_forward(z.data_ptr(), _pro(p), n, _i3(z.shape[1:4]), c, _i3(k_dhw), w_perm.data_ptr(),
+                                      _ptr(bias), logit.data_ptr(), _ptr(prob), _stream()), "maphead_forward")
+    return logit
+
+
+def maphead_backward(z, p: Optional[Prologue], k_dhw: Sequence[int], w_perm, dlogit, g_a, dw, dbias, beta=0.0,
+                     workspace=None):
+    """g_a (w.r.t. the activated tensor), dw (torch order, beta-accumulated) and dbias of maphead_forward; each may be
+    None.  workspace: a tensor of at least maphead_workspace(...) bytes (dw only)."""
+    n, P, ld = _cl(z, "maphead_backward z")
+    c = z.shape[-1]
+    if ld != c or (g_a is not None and (g_a.shape != z.shape or not g_a.is_contiguous())):
+        raise ValueError("maphead_backward: z / g_a must be dense and same shape")
+    ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+    check(lib().mpgan_maphead_backward(z.data_ptr(), _pro(p), n, _i3(z.shape[1:4]), c, _i3(k_dhw), w_perm.data_ptr(),
+                                       dlogit.data_ptr(), _ptr(g_a), _ptr(dw), _ptr(dbias), float(beta),
+                                       _ptr(workspace), ws_bytes, _stream()), "maphead_backward")
+
+
 def sigmoid_backward(dprob, prob, dlogit):
     check(lib().mpgan_sigmoid_backward(dprob.data_ptr(), prob.data_ptr(), prob.numel(), dlogit.data_ptr(), _stream()),
           "sigmoid_backward")

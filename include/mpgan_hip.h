@@ -321,6 +321,29 @@ int mpgan_linear1_backward(const float* z, const mpgan_prologue* p, int32_t n,
                            const float* dlogit, float* g_a, float* dw, float* dbias,
                            float beta, void* stream);
 
+/* ---- discriminator head, Markovian (PatchGAN): a last valid conv C -> 1 + Sigmoid ---- */
+/* z: channels-last (n, in_dhw, c), depth 1 in 2-D; kernel k_dhw, stride 1, no padding: out = in - k + 1 per dimension.
+ *   logit[n][p] = bias + sum_tap sum_c act(z[n][p+tap][c]*scale[c] + shift[c]) * w_perm[tap][c]
+ *   prob = sigmoid(logit) (nullable)
+ * p null: z is already activated; p->n_stride = c: per-sample scale / shift.  w_perm: what mpgan_pack_weights makes of
+ * the (1, c, kd, kh, kw) weight, [tap][c].  fp32; no atomics, every sum in a fixed order (per lane its channel quads
+ * and the taps in index order, then the lanes of the wave), so two runs give the same bits.
+ * Refused before any launch: c % 4 != 0, z / w_perm / g_a / workspace not 16-byte aligned, in < k in any dimension,
+ * taps*c*4 above the 64 KiB of LDS the kernels keep the weights in, a workspace that is too small. */
+int mpgan_maphead_forward(const float* z, const mpgan_prologue* p, int32_t n, const int32_t in_dhw[3], int32_t c,
+                          const int32_t k_dhw[3], const float* w_perm, const float* bias, float* logit,
+                          float* prob /* nullable */, void* stream);
+/* bytes of caller-supplied scratch mpgan_maphead_backward needs for dw (-1: geometry refused, see mpgan_last_error) */
+int64_t mpgan_maphead_workspace(int32_t n, const int32_t in_dhw[3], int32_t c, const int32_t k_dhw[3]);
+/* g_a[n][q][c] = sum_tap dlogit[n][q-tap] * w_perm[tap][c] over the taps that land inside the map (the gradient w.r.t.
+ *   the ACTIVATED tensor, as mpgan_linear1_backward leaves it);
+ * dw (torch order (1, c, kd, kh, kw)) = beta*dw + sum_{n,p} dlogit[n][p] * a[n][p+tap][c]: per-chunk partials in the
+ *   workspace, then a finalize that adds the chunks in index order;
+ * dbias = beta*dbias + sum dlogit.  g_a, dw, dbias: each nullable (workspace is needed for dw only). */
+int mpgan_maphead_backward(const float* z, const mpgan_prologue* p, int32_t n, const int32_t in_dhw[3], int32_t c,
+                           const int32_t k_dhw[3], const float* w_perm, const float* dlogit, float* g_a, float* dw,
+                           float* dbias, float beta, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* prob = sigmoid(logit); loss = mean BCE(prob, target) with log clamped at
  * -100 (F.binary_cross_entropy, GAN_final.py:244-245); dlogit = loss_scale *
  * dL/dlogit computed THROUGH the clamped log and the sigmoid exactly as

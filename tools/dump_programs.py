@@ -4,6 +4,7 @@
 
     python tools/dump_programs.py [--storage {bf16,f32,both}]        # variant A and B, every program
     python tools/dump_programs.py --tree DIR                         # the same of another built checkout (the parent commit)
+    python tools/dump_programs.py --head markovian                   # variant A with the Markovian (PatchGAN) head
     MPGAN_FUSE_BWD_STATS_BF16=1 python tools/dump_programs.py        # bf16 variant A train with the fused norm-backward sums
     MPGAN_DBG_NO_FUSE_BWD_STATS=1 python tools/dump_programs.py      # fp32 variant A train without them
 
@@ -19,6 +20,8 @@ import sys
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _ap = argparse.ArgumentParser()
 _ap.add_argument("--storage", default="both", choices=("bf16", "f32", "both"))
+_ap.add_argument("--head", default="linear", choices=("linear", "markovian"),
+                 help="variant A's head; markovian lists variant A alone, at shapes whose last feature map is >= 4")
 _ap.add_argument("--tree", default=HERE, help="a built checkout to import the package from")
 ARGS = _ap.parse_args()
 sys.path.insert(0, os.path.abspath(ARGS.tree))
@@ -28,6 +31,9 @@ from mpgan_amd import engine  # noqa: E402
 from mpgan_amd.networks import Discriminator, PatchDiscriminator  # noqa: E402
 
 DEV = "cuda"
+# the default keeps the constructor call and the titles of the commits before the option existed (--tree)
+HEAD_KW = {} if ARGS.head == "linear" else {"head": ARGS.head}
+HEAD_TAG = "" if ARGS.head == "linear" else f" {ARGS.head}"
 
 
 class Ordinals(dict):
@@ -67,8 +73,8 @@ def variant_a(shape, n):
     """Train forward / backward and the eval forward; under MPGAN_FUSE_BWD_STATS_BF16 the train pair alone, and only if a
     backward-data launch of this shape leaves fused norm-backward rows (returns whether it does)."""
     torch.manual_seed(0)
-    d = Discriminator((1,) + shape, dimensions=len(shape), device=DEV, storage_dtype="bf16")
-    store, ords, name = d.store, Ordinals(), f"A bf16 {'x'.join(map(str, shape))} n{n}"
+    d = Discriminator((1,) + shape, dimensions=len(shape), device=DEV, storage_dtype="bf16", **HEAD_KW)
+    store, ords, name = d.store, Ordinals(), f"A bf16{HEAD_TAG} {'x'.join(map(str, shape))} n{n}"
     train = engine.DiscPlanBF16(d, store, n, shape, want_backward=True, want_input_grad=True, want_param_grads=True)
     if engine._FUSE_BWD_STATS_BF16:
         L = engine.lib()
@@ -105,8 +111,8 @@ def variant_a_f32(shape, n):
     """Train forward / backward with all gradients and as the G step takes them (input gradient only), and the eval
     forward; under MPGAN_DBG_NO_FUSE_BWD_STATS the all-gradients train pair alone."""
     torch.manual_seed(0)
-    d = Discriminator((1,) + shape, dimensions=len(shape), device=DEV)
-    store, name = d.store, f"A f32 {'x'.join(map(str, shape))} n{n}"
+    d = Discriminator((1,) + shape, dimensions=len(shape), device=DEV, **HEAD_KW)
+    store, name = d.store, f"A f32{HEAD_TAG} {'x'.join(map(str, shape))} n{n}"
     steps = [("train", dict(want_input_grad=True, want_param_grads=True))]
     if engine._FUSE_BWD_STATS:
         steps.append(("G-step train", dict(want_input_grad=True, want_param_grads=False)))
@@ -140,6 +146,11 @@ def variant_b_f32(shape, n):
 
 def main():
     bf16, f32 = ARGS.storage in ("bf16", "both"), ARGS.storage in ("f32", "both")
+    if ARGS.head == "markovian":                             # (24^3 ends in a 3^3 feature map: 32^3 here)
+        for fn in ([variant_a] if bf16 else []) + ([variant_a_f32] if f32 else []):
+            fn((40, 40), 3)
+            fn((32, 32, 32), 2)
+        return
     if engine._FUSE_BWD_STATS_BF16:                          # the second invocation: the first shape with fused rows
         print("# MPGAN_FUSE_BWD_STATS_BF16=1")
         if bf16 and not (variant_a((40, 40), 3) or variant_a((24, 24, 24), 2)):
