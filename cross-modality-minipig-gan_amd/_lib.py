@@ -112,6 +112,9 @@ SIGNATURES = {
     "mpgan_maphead_backward": (_I, [_P, _PR, _I, _I3, _I, _I3, _P, _P, _P, _P, _P, _F, _P, _L, _P]),
     "mpgan_l1_partials": (_I, []),
     "mpgan_l1_loss": (_I, [_P, _P, _L, _F, _P, _P, _P, _P]),
+    # objectives on the logits (adv_loss.hip)
+    "mpgan_adv_loss_partials": (_I, [_I]),
+    "mpgan_adv_loss": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
     "mpgan_metric_partials": (_I, []),
     "mpgan_rescale_minmax": (_I, [_P, _L, _F, _F, _I, _P, _P, _P, _P]),
     "mpgan_image_errors": (_I, [_P, _P, _L, _F, _P, _P, _P]),

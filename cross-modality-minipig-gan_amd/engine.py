@@ -1766,43 +1766,52 @@ class ConvStackBF16(ConvStack):
 
 class LinearHead:
     """Variant A's head, Flatten -> Linear(F,1) -> Sigmoid, on the last layer's tensor `src` read through `pro` (raw z
-    with the BatchNorm + LeakyReLU prologue, or an activated fp32 tensor with none)."""
+    with the BatchNorm + LeakyReLU prologue, or an activated fp32 tensor with none).  With disc.output == "logit" the
+    Sigmoid is not applied: no `prob`, and the backward starts from `dlogit`, which the caller fills."""
 
     def __init__(self, disc, store: ParamStore, n: int, g_last: ConvGeom, spatial):
         dev = store.flat.device
         self.lin, self.n = disc.model_linear[1], n
+        self.logits_out = getattr(disc, "output", "prob") == "logit"
         self.P, self.c = math.prod(g_last.out_dhw), g_last.cout
         if self.lin.in_features != self.P * self.c:
             raise ValueError(f"Linear.in_features {self.lin.in_features} != {self.c}*{self.P} for input {spatial}")
         self.rlin = store.register_conv(self.lin, cout=1, cin=self.c, taps=self.P)
-        self.logit, self.prob = torch.empty(n, device=dev), torch.empty(n, device=dev)
+        self.logit, self.prob = torch.empty(n, device=dev), (None if self.logits_out else torch.empty(n, device=dev))
         self.lin_part = torch.empty(ops.linear1_partials(n), device=dev)
 
     def emit_forward(self, prog, store: ParamStore, src, pro):
         pc = pro.c() if pro is not None else None
         prog.add("linear1_forward", lib().mpgan_linear1_forward, src.data_ptr(), C.byref(pc) if pc is not None else None,
                  self.n, self.P, self.c, store.wp(self.rlin).data_ptr(), self.lin.bias.data_ptr(),
-                 self.lin_part.data_ptr(), self.logit.data_ptr(), self.prob.data_ptr(), keep=(pc, pro, src, self))
+                 self.lin_part.data_ptr(), self.logit.data_ptr(), _p(self.prob), keep=(pc, pro, src, self))
 
     def emit_backward(self, prog, store: ParamStore, src, pro, g_src, want_param_grads: bool):
-        """g_prob (allocated here; the caller fills it) -> g_src, the gradient w.r.t. what `src` holds after `pro`."""
+        """g_prob (allocated here; the caller fills it; `dlogit` with disc.output == "logit") -> g_src, the gradient
+        w.r.t. what `src` holds after `pro`."""
         gv = store.grad_view if want_param_grads else (lambda p: None)
         L, pc = lib(), (pro.c() if pro is not None else None)
-        self.g_prob, dlogit = torch.empty_like(self.prob), torch.empty_like(self.prob)
-        prog.add("sigmoid_backward", L.mpgan_sigmoid_backward, self.g_prob.data_ptr(), self.prob.data_ptr(), self.n,
-                 dlogit.data_ptr(), keep=(dlogit, self))
+        if self.logits_out:
+            self.g_prob, dlogit = None, torch.empty_like(self.logit)
+            self.dlogit = dlogit
+        else:
+            self.g_prob, dlogit = torch.empty_like(self.prob), torch.empty_like(self.prob)
+            prog.add("sigmoid_backward", L.mpgan_sigmoid_backward, self.g_prob.data_ptr(), self.prob.data_ptr(), self.n,
+                     dlogit.data_ptr(), keep=(dlogit, self))
         prog.add("linear1_backward", L.mpgan_linear1_backward, src.data_ptr(), C.byref(pc) if pc is not None else None,
                  self.n, self.P, self.c, store.wp(self.rlin).data_ptr(), dlogit.data_ptr(), g_src.data_ptr(),
-                 _p(gv(self.lin.weight)), _p(gv(self.lin.bias)), 1.0, keep=(pc, pro, src, g_src))
+                 _p(gv(self.lin.weight)), _p(gv(self.lin.bias)), 1.0, keep=(pc, pro, src, g_src, dlogit))
 
 
 class MapHead:
     """Variant A's Markovian (PatchGAN) head, a last valid Conv(256, 1, k) -> Sigmoid on the last layer's tensor `src`
     read through `pro` (see LinearHead): a map of per-receptive-field verdicts, out = last - k + 1 per dimension.  One
-    fp32 class for all four plans: the bf16 and the eval stacks hand it an fp32 activated tensor and no prologue."""
+    fp32 class for all four plans: the bf16 and the eval stacks hand it an fp32 activated tensor and no prologue.
+    disc.output == "logit": as in LinearHead."""
 
     def __init__(self, disc, store: ParamStore, n: int, g_last: ConvGeom, spatial):
         dev = store.flat.device
+        self.logits_out = getattr(disc, "output", "prob") == "logit"
         self.conv, self.n, self.c = disc.model_head[0], n, g_last.cout
         self.in_dhw = tuple(g_last.out_dhw)
         self.k = _t3(self.conv.kernel_size, disc.dimensions, 1)
@@ -1811,29 +1820,33 @@ class MapHead:
         self.map_dhw = tuple(i - k + 1 for i, k in zip(self.in_dhw, self.k))
         self.P = math.prod(self.map_dhw)
         self.rconv = store.register_conv(self.conv, cout=1, cin=self.c, taps=math.prod(self.k))
-        self.logit, self.prob = torch.empty(n * self.P, device=dev), torch.empty(n * self.P, device=dev)
+        self.logit = torch.empty(n * self.P, device=dev)
+        self.prob = None if self.logits_out else torch.empty(n * self.P, device=dev)
         self._in3, self._k3 = (C.c_int32 * 3)(*self.in_dhw), (C.c_int32 * 3)(*self.k)
 
     def emit_forward(self, prog, store: ParamStore, src, pro):
         pc = pro.c() if pro is not None else None
         prog.add("maphead_forward", lib().mpgan_maphead_forward, src.data_ptr(), C.byref(pc) if pc is not None else None,
                  self.n, self._in3, self.c, self._k3, store.wp(self.rconv).data_ptr(), self.conv.bias.data_ptr(),
-                 self.logit.data_ptr(), self.prob.data_ptr(), keep=(pc, pro, src, self))
+                 self.logit.data_ptr(), _p(self.prob), keep=(pc, pro, src, self))
 
     def emit_backward(self, prog, store: ParamStore, src, pro, g_src, want_param_grads: bool):
-        """g_prob (allocated here; the caller fills it) -> g_src, the gradient w.r.t. what `src` holds after `pro`."""
+        """g_prob (allocated here; the caller fills it; `dlogit` with disc.output == "logit") -> g_src, the gradient
+        w.r.t. what `src` holds after `pro`."""
         gv = store.grad_view if want_param_grads else (lambda p: None)
         L, pc = lib(), (pro.c() if pro is not None else None)
-        self.g_prob, dlogit = torch.empty_like(self.prob), torch.empty_like(self.prob)
+        self.g_prob = None if self.logits_out else torch.empty_like(self.logit)
+        dlogit = torch.empty_like(self.logit)
         self.dlogit = dlogit                        # read by tests: what maphead_backward was given
         ws_bytes = ops.maphead_workspace(self.n, self.in_dhw, self.c, self.k) if want_param_grads else 0
-        ws = torch.empty(max(ws_bytes // 4, 4), device=self.prob.device) if want_param_grads else None
-        prog.add("sigmoid_backward", L.mpgan_sigmoid_backward, self.g_prob.data_ptr(), self.prob.data_ptr(),
-                 self.n * self.P, dlogit.data_ptr(), keep=(dlogit, self))
+        ws = torch.empty(max(ws_bytes // 4, 4), device=self.logit.device) if want_param_grads else None
+        if not self.logits_out:
+            prog.add("sigmoid_backward", L.mpgan_sigmoid_backward, self.g_prob.data_ptr(), self.prob.data_ptr(),
+                     self.n * self.P, dlogit.data_ptr(), keep=(dlogit, self))
         prog.add("maphead_backward", L.mpgan_maphead_backward, src.data_ptr(), C.byref(pc) if pc is not None else None,
                  self.n, self._in3, self.c, self._k3, store.wp(self.rconv).data_ptr(), dlogit.data_ptr(),
                  g_src.data_ptr(), _p(gv(self.conv.weight)), _p(gv(self.conv.bias)), 1.0, _p(ws), ws_bytes,
-                 keep=(pc, pro, src, g_src, ws))
+                 keep=(pc, pro, src, g_src, ws, dlogit))
 
 
 class PatchHead:
@@ -1964,7 +1977,8 @@ class DiscPlan(_DiscPlanBase):
         # raw conv outputs, their gradients (`dzs`: after the norm backward), norm vectors: read by tests and tools
         self.gas, self.dzs = st.alloc_grads(disc)
         head.emit_backward(b, store, src, pro, self.gas[-1], want_param_grads)
-        self.g_prob = head.g_prob
+        # what the caller fills before running `bwd`: g_prob, or with disc.output == "logit" g_logit (the other is None)
+        self.g_prob, self.g_logit = head.g_prob, (head.dlogit if head.logits_out else None)
         st.emit_backward(b, store, self.x_in, self.gas, self.dzs, scratch.partials, scratch.ws,
                          want_param_grads=want_param_grads, g_x=self.g_x, fuse_stats=st.FUSE_BWD_STATS,
                          **(dict(wgrad_lane=_D_WGRAD_LANE) if st.SIDE_WGRAD else {}))

@@ -61,6 +61,29 @@ class _L1Fn(torch.autograd.Function):
         return (g if ctx.needs_input_grad[0] else None), gb
 
 
+class _AdvLogitFn(torch.autograd.Function):
+    """An objective on the discriminator's logits (ops.adv_loss: "bce_logits" = F.binary_cross_entropy_with_logits,
+    "lsgan" = F.mse_loss), mean; dL/dlogit is written by the forward launch and the backward scales it by gout."""
+
+    @staticmethod
+    def forward(ctx, y_hat, y, kind):
+        if ctx.needs_input_grad[1]:
+            raise NotImplementedError("adversarial_loss: the target is a label, no gradient is offered for it")
+        z, t = y_hat.contiguous(), y.contiguous()
+        loss = torch.empty((), device=z.device)
+        part = torch.empty(ops.adv_loss_partials(z.numel()), device=z.device, dtype=torch.float64)
+        grad = torch.empty_like(z) if ctx.needs_input_grad[0] else None
+        ops.adv_loss(z, t, kind, part, loss, grad)
+        ctx.grad = grad
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        g = torch.empty_like(ctx.grad)          # a fresh tensor, as in _L1Fn
+        ops.scale_by_device_scalar(ctx.grad, gout.contiguous(), g)
+        return g, None, None
+
+
 class _AxpbyFn(torch.autograd.Function):
     """alpha*a + beta*b on device scalars (the loss sums of training_step) through the library's own
     pointwise kernel, so that no torch elementwise kernel sits on the step path."""
@@ -84,9 +107,17 @@ def scalar_axpby(a, alpha, b, beta):
     return _AxpbyFn.apply(a, float(alpha), b, float(beta))
 
 
-def adversarial_loss(y_hat, y):
-    """code/GAN/GAN_final.py:244-245."""
-    return _BCEFn.apply(y_hat, y)
+ADV_LOSSES = ("bce", "bce_logits", "lsgan")
+
+
+def adversarial_loss(y_hat, y, kind="bce"):
+    """code/GAN/GAN_final.py:244-245 (kind="bce": y_hat holds probabilities).  kind="bce_logits" | "lsgan": y_hat holds
+    the logits of a Discriminator(output="logit"), see _AdvLogitFn and DESIGN.md 7d."""
+    if kind == "bce":
+        return _BCEFn.apply(y_hat, y)
+    if kind not in ADV_LOSSES:
+        raise ValueError(f"adversarial_loss: kind must be one of {ADV_LOSSES}, got {kind!r}")
+    return _AdvLogitFn.apply(y_hat, y, kind)
 
 
 def reconstruction_loss(y_hat, y):
@@ -208,6 +239,12 @@ class FusedAdam(torch.optim.Optimizer):
 # --------------------------------------------------------------------------
 # the GAN module
 # --------------------------------------------------------------------------
+class _HParams(types.SimpleNamespace):
+    """GAN.hparams.  `adv_loss` reads "bce" unless the constructor was given another objective, and only then is it an
+    entry of vars(hparams): a default GAN lists exactly the hyper-parameters it listed before the option existed."""
+    adv_loss = "bce"
+
+
 class GAN(nn.Module):
     """code/GAN/GAN_final.py:212-317.  `training_step(batch, batch_idx,
     optimizer_idx)` has the reference's body; `fit_batch` is Lightning's
@@ -219,25 +256,31 @@ class GAN(nn.Module):
                  one_sided_label_value=0.9, *, dimensions: Optional[int] = None, norm: str = "batch",
                  n_unet_blocks: int = 6, unet_channels=(16, 32, 64, 128), unet_strides=(2, 2, 2), device="cuda",
                  storage_dtype: str = "f32", mi_weight: float = 0.0, mi_bins: int = 23,
-                 ssim_weight: float = 0.0, d_head: str = "linear", **kwargs):
+                 ssim_weight: float = 0.0, d_head: str = "linear", adv_loss: str = "bce", **kwargs):
         super().__init__()
+        if adv_loss not in ADV_LOSSES:
+            raise ValueError(f"adv_loss must be one of {ADV_LOSSES}, got {adv_loss!r}")
         if mi_weight < 0:
             raise ValueError(f"mi_weight must be >= 0, got {mi_weight!r}")
         if ssim_weight < 0:
             raise ValueError(f"ssim_weight must be >= 0, got {ssim_weight!r}")
         if dimensions is None:
             dimensions = 3 if depth is not None else 2
-        self.hparams = types.SimpleNamespace(latent_dim=latent_dim, g_lr=g_lr, d_lr=d_lr, b1=b1, b2=b2,
-                                             batch_size=batch_size, one_sided_label_value=one_sided_label_value,
-                                             d_head=d_head)
+        self.hparams = _HParams(latent_dim=latent_dim, g_lr=g_lr, d_lr=d_lr, b1=b1, b2=b2,
+                                batch_size=batch_size, one_sided_label_value=one_sided_label_value, d_head=d_head)
+        if adv_loss != _HParams.adv_loss:
+            self.hparams.adv_loss = adv_loss
         data_shape = (channels, width, height) + ((depth,) if dimensions == 3 else ())
         # storage_dtype="bf16" is config C5: the discriminator stores its activations in bf16 and the generator's
         # matrix products take bf16 operands (fp32 storage: its launches are matrix-bound, not byte-bound)
         self.generator = CasNetGenerator(data_shape, n_unet_blocks, dimensions=dimensions, norm=norm,
                                          channels=unet_channels, strides=unet_strides, device=device,
                                          matmul_dtype="bf16" if storage_dtype == "bf16" else "f32")
+        # adv_loss="bce" is the reference's objective on the Sigmoid's output; the other two are computed on the logits
+        # (their gradient does not vanish when the discriminator wins), which the discriminator then returns
         self.discriminator = Discriminator(data_shape, dimensions=dimensions, device=device,
-                                           storage_dtype=storage_dtype, head=d_head)
+                                           storage_dtype=storage_dtype, head=d_head,
+                                           output="prob" if adv_loss == "bce" else "logit")
         # opt-in auxiliary generator loss (not in the reference's trainer): mi_weight * (-MI(G(t1w), t2w)) from Parzen
         # windows over the tanh output's range; with the default 0 no launch and no logged name is added
         self.mi_weight = float(mi_weight)
@@ -252,13 +295,13 @@ class GAN(nn.Module):
         return self.generator(x)
 
     def adversarial_loss(self, y_hat, y):
-        return adversarial_loss(y_hat, y)
+        return adversarial_loss(y_hat, y, kind=self.hparams.adv_loss)
 
     def reconstruction_loss(self, y_hat, y):
         return reconstruction_loss(y_hat, y)
 
     def _labels(self, validity, value: float):
-        """The BCE target of one discriminator output: (B, 1) as in the reference; with d_head="markovian" the shape of
+        """The target of one discriminator output: (B, 1) as in the reference; with d_head="markovian" the shape of
         the validity map, every verdict getting the same label."""
         if self.hparams.d_head == "markovian":
             return torch.full_like(validity, float(value))

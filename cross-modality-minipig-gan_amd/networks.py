@@ -290,7 +290,7 @@ class _DiscFn(torch.autograd.Function):
         spatial = _spatial(x, disc.dimensions)
         n = x.shape[0]
         store = disc.store
-        key = (n, spatial, need_bwd, want_in, want_par, disc.head)
+        key = (n, spatial, need_bwd, want_in, want_par, disc.head, disc.output)
         plan_cls = DiscPlanBF16 if disc.storage_dtype == "bf16" else DiscPlan
         plan = disc._acquire(key, lambda: plan_cls(disc, store, n, spatial, want_backward=need_bwd,
                                                    want_input_grad=want_in, want_param_grads=want_par))
@@ -303,7 +303,7 @@ class _DiscFn(torch.autograd.Function):
         finally:
             if not need_bwd:
                 io.reset()
-        prob = plan.prob.view(disc.validity_shape(n, spatial)).clone()
+        prob = _validity(disc, plan).view(disc.validity_shape(n, spatial)).clone()
         if need_bwd:
             ctx.lease = lease
             ctx.shape = x.shape
@@ -319,7 +319,7 @@ class _DiscFn(torch.autograd.Function):
         plan = ctx.lease.plan
         _ = ctx.saved_tensors
         io = plan_io(plan)
-        plan.g_prob.copy_(gprob.reshape(-1))
+        (plan.g_prob if plan.g_logit is None else plan.g_logit).copy_(gprob.reshape(-1))
         gx = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty(ctx.shape, device=gprob.device, dtype=torch.float32)
@@ -334,6 +334,11 @@ class _DiscFn(torch.autograd.Function):
         return gx, None, None
 
 
+def _validity(disc, plan):
+    """What forward returns of a plan: the probabilities, or with output="logit" the logits (such a plan has no prob)."""
+    return plan.logit if disc.output == "logit" else plan.prob
+
+
 def _disc_eval(disc, x):
     """Eval-mode pass of variant A's discriminator: the forward-only plan keyed by the mode (engine.DiscPlan /
     DiscPlanBF16 with training=False), outside autograd."""
@@ -341,7 +346,7 @@ def _disc_eval(disc, x):
         spatial = _spatial(x, disc.dimensions)
         n = x.shape[0]
         store = disc.store
-        key = ("eval", n, spatial, disc.storage_dtype, disc.head)
+        key = ("eval", n, spatial, disc.storage_dtype, disc.head, disc.output)
         plan_cls = DiscPlanBF16 if disc.storage_dtype == "bf16" else DiscPlan
         plan = disc._acquire(key, lambda: plan_cls(disc, store, n, spatial, want_backward=False, want_input_grad=False,
                                                    want_param_grads=False, training=False))
@@ -351,7 +356,7 @@ def _disc_eval(disc, x):
             plan.x_in.view(-1).copy_(x.reshape(-1))
         try:
             plan.fwd.run()
-            return plan.prob.view(disc.validity_shape(n, spatial)).clone()
+            return _validity(disc, plan).view(disc.validity_shape(n, spatial)).clone()
         finally:
             io.reset()
             lease.release()
@@ -380,16 +385,23 @@ class Discriminator(_EngineModule):
     head="markovian": the PatchGAN head the reference lists as a TODO (GAN_final.py:125) in place of the Linear one:
     `model_head` = Conv(256, 1, kernel_size=4) -> Sigmoid on the last feature map, and forward returns a map
     (B, 1, *disc_map_size(spatial)) of per-receptive-field verdicts; there is no `model_linear`, and the network is no
-    longer tied to one input size."""
+    longer tied to one input size.
+
+    output="logit": forward returns the logits, for an objective computed on them (gan.GAN(adv_loss="bce_logits" |
+    "lsgan")).  The module tree and the state_dict keys are those of output="prob" -- the nn.Sigmoid stays where it is
+    and is not applied -- so the same checkpoints load; the plans launch no sigmoid and no sigmoid backward."""
 
     def __init__(self, img_shape, use_perceptual=True, *, dimensions=3, device=None, storage_dtype="f32",
-                 head="linear"):
+                 head="linear", output="prob"):
         super().__init__()
         if storage_dtype not in ("f32", "bf16"):
             raise ValueError(f"storage_dtype must be 'f32' or 'bf16', got {storage_dtype!r}")
         if head not in ("linear", "markovian"):
             raise ValueError(f"head must be 'linear' or 'markovian', got {head!r}")
+        if output not in ("prob", "logit"):
+            raise ValueError(f"output must be 'prob' or 'logit', got {output!r}")
         self.head = head
+        self.output = output
         self.use_perceptual = use_perceptual
         self.img_shape = img_shape
         self.dimensions = dimensions

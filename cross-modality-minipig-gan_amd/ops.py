@@ -535,6 +535,40 @@ def l1_loss(a, b, partials, loss, grad_a=None, grad_scale: float = 1.0):
                               loss.data_ptr(), _ptr(grad_a), _stream()), "l1_loss")
 
 
+ADV_KINDS = {"bce_logits": 0, "lsgan": 1}      # MPGAN_ADV_BCE_LOGITS, MPGAN_ADV_LSGAN
+
+
+def adv_loss_partials(n: int) -> int:
+    """Doubles of scratch adv_loss needs for n logits."""
+    need = int(lib().mpgan_adv_loss_partials(int(n)))
+    if need < 0:
+        check(-1, "adv_loss_partials")
+    return need
+
+
+def adv_loss(logit, target, kind: str, partials, loss, grad=None):
+    """loss = the mean objective `kind` ("bce_logits" | "lsgan") of fp32 logits against targets of the same shape;
+    grad (optional) = dL/dlogit for an upstream gradient of 1.  partials: float64, >= adv_loss_partials(n)."""
+    if kind not in ADV_KINDS:
+        raise ValueError(f"adv_loss: kind must be one of {sorted(ADV_KINDS)}, got {kind!r}")
+    if logit.shape != target.shape or not logit.is_contiguous() or not target.is_contiguous():
+        raise ValueError("adv_loss: logit and target must be contiguous and same shape")
+    if logit.dtype != torch.float32 or target.dtype != torch.float32 or partials.dtype != torch.float64:
+        raise ValueError("adv_loss: logit / target must be float32 and partials float64")
+    if grad is not None and (grad.shape != logit.shape or not grad.is_contiguous() or grad.dtype != torch.float32):
+        raise ValueError("adv_loss: grad must be a contiguous float32 tensor of logit's shape")
+    if not all(t.is_cuda for t in (logit, target, partials, loss) + ((grad,) if grad is not None else ())):
+        raise ValueError("adv_loss: every tensor must be on the GPU (there is no CPU path)")
+    n = logit.numel()
+    if n >= 2 ** 31:
+        raise ValueError(f"adv_loss: {n} elements exceed the 32-bit count of mpgan_adv_loss")
+    if n > 0 and partials.numel() < adv_loss_partials(n):
+        raise ValueError(f"adv_loss: partials holds {partials.numel()} doubles, needs {adv_loss_partials(n)}")
+    check(lib().mpgan_adv_loss(logit.data_ptr(), target.data_ptr(), n, ADV_KINDS[kind], partials.data_ptr(),
+                               loss.data_ptr(), _ptr(grad), _stream()), "adv_loss")
+    return loss
+
+
 def adam_step(p, g, m, v, lr, b1, b2, eps, step: int, grad_scale: float = 1.0):
     if not (p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()):
         raise ValueError("adam_step: flat buffers must be contiguous")

@@ -375,6 +375,25 @@ int32_t mpgan_l1_partials(void);
 int mpgan_l1_loss(const float* a, const float* b, int64_t numel, float grad_scale,
                   float* partials, float* loss, float* grad_a, void* stream);
 
+/* ---- adversarial objectives on the LOGITS (no Sigmoid in front) ----
+ * MPGAN_ADV_BCE_LOGITS (F.binary_cross_entropy_with_logits; no log clamp, no 1e-12 guard; soft targets such as 0.9
+ * are ordinary inputs):
+ *   term_i = max(z_i,0) - z_i*t_i + log1p(exp(-|z_i|));  loss = mean_i term_i
+ *   grad_i = (sigma(z_i) - t_i)/n,  sigma(z) = (z >= 0 ? 1 : e)/(1 + e) with e = exp(-|z|): neither branch overflows
+ * MPGAN_ADV_LSGAN (F.mse_loss on the logits, CycleGAN's convention: no factor 1/2):
+ *   term_i = (z_i - t_i)^2;  loss = mean_i term_i;  grad_i = 2*(z_i - t_i)/n
+ * grad (nullable) is dL/dlogit for an upstream gradient of 1, written by the forward launch as mpgan_l1_loss writes its
+ * own; an autograd backward is mpgan_scale_by_device_scalar on it.  Element terms in fp32, sums in fp64: per lane its
+ * elements in index order, then the lanes of the wave, then the waves of the block, one plain store per block into
+ * `partials`, the block partials added in index order (a second small launch; one block finishes alone).  No atomics
+ * and a grid that depends on n alone: two runs give the same bits.  16-byte accesses when logit, target and grad are
+ * 16-byte aligned (scalar tail), element-wise otherwise.  partials: >= mpgan_adv_loss_partials(n) doubles, 8-byte
+ * aligned.  MPGAN_ERR_INVALID before any launch: n <= 0, an unknown kind, a null logit / target / partials / loss. */
+enum { MPGAN_ADV_BCE_LOGITS = 0, MPGAN_ADV_LSGAN = 1 };
+int32_t mpgan_adv_loss_partials(int32_t n); /* doubles of caller-supplied scratch (-1: n <= 0) */
+int mpgan_adv_loss(const float* logit, const float* target, int32_t n, int32_t kind, double* partials, float* loss,
+                   float* grad /* nullable */, void* stream);
+
 /* ---- evaluation metrics (next-row N2: inferrence.py:188-204, metrics.py:213-223,
  *      psnr_ssim_metric.py:88-106) ---------------------------------------------------- */
 /* y = clip(round((x-min)/(max-min)*(b_max-b_min)+b_min)): ScaleIntensityRangePercentiles(0,100,0,255)
