@@ -537,15 +537,7 @@ static void hb_copy_dbg() {
 }
 template <auto KERN>
 static int hb_prepare(int smem, const char* name) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (e != hipSuccess) {
-      set_error("%s: hipFuncSetAttribute(%d): %s", name, smem, hipGetErrorString(e));
-      return MPGAN_ERR_HIP;
-    }
-    attr_set = true;
-  }
+  if (const int rc = raise_lds_limit<KERN>(smem, name)) return rc;
   hb_copy_dbg();
   return MPGAN_OK;
 }
@@ -2392,16 +2384,8 @@ int launch_thin_cout1_mfma_bf16(const GatherConv& p, hipStream_t st) {
   tg.tiles_x = (ph.Mx + tg.tx - 1) / tg.tx;
   const int T = ph.nz * ph.ny * ph.nx;
   const int smem = T * TC_MAXQ * (int)sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(thin_cout1_mfma_bf16_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 27 * TC_MAXQ * (int)sizeof(float));
-    if (e != hipSuccess) {
-      set_error("thin_cout1_mfma_bf16: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return MPGAN_ERR_HIP;
-    }
-    attr_set = true;
-  }
+  if (const int rc = raise_lds_limit<thin_cout1_mfma_bf16_kernel>(27 * TC_MAXQ * (int)sizeof(float), "thin_cout1_mfma_bf16"))
+    return rc;
   const long blocks = (long)p.N * tg.tiles_z * tg.tiles_y * tg.tiles_x;
   MPGAN_CHECK_ARG(blocks < (1L << 31), "thin_cout1_mfma_bf16: too many tiles");
   hipLaunchKernelGGL(thin_cout1_mfma_bf16_kernel, dim3((unsigned)blocks), dim3(256), smem, st, p, tg);
@@ -2679,16 +2663,8 @@ using namespace mpgan;
 // forms' geometry does not hold is it rebuilt with them (conv_geom.h) for the K-stepped kernels -- even where
 // choose_bf16 then prefers a wide K-stepped form to the patch forms.
 static void build_gather_bf16(GatherConv& p, const mpgan_conv_geom* g, bool backward_data) {
-  const bool fwd_type = backward_data ? g->transposed != 0 : g->transposed == 0;
-  const int32_t *gd = backward_data ? g->out_dhw : g->in_dhw, *pd = backward_data ? g->in_dhw : g->out_dhw;
-  const int cg = backward_data ? g->cout : g->cin, cp = backward_data ? g->cin : g->cout;
-  if (fwd_type) {
-    build_forward(p, g->n, gd, cg, pd, cp, g->k, g->stride, g->pad);
-    return;
-  }
-  build_transposed(p, g->n, gd, cg, pd, cp, g->k, g->stride, g->pad, false);
-  if (hb_patch_geometry(p)) return;
-  build_transposed(p, g->n, gd, cg, pd, cp, g->k, g->stride, g->pad, true);
+  if (!build_gather(p, g, backward_data, false) || hb_patch_geometry(p)) return;
+  build_gather(p, g, backward_data, true);
 }
 
 // What a geometry query decides from: the GatherConv the entry point builds for this geometry and direction, with
@@ -2698,7 +2674,6 @@ static GatherConv standin_bf16(const mpgan_conv_geom* g, bool backward_data) {
   GatherConv p{};
   p.in = g_standin; p.wp = g_standin; p.out = g_standin;
   p.pro = make_pro(nullptr);
-  set_geom_flags(p, g);
   build_gather_bf16(p, g, backward_data);
   p.ldi = p.Cin; p.ldo = p.Cout;
   return p;
@@ -2745,7 +2720,6 @@ extern "C" int mpgan_conv_forward_bf16(const mpgan_conv_geom* g, const void* x, 
   p.bias = bias; p.stats = stats_partials;
   p.pro = make_pro(nullptr);
   p.ldi = ldx; p.ldo = ldy;
-  set_geom_flags(p, g);
   build_gather_bf16(p, g, false);
   return hb_dispatch(p, (hipStream_t)stream, "conv_forward_bf16");
 }
@@ -2772,7 +2746,6 @@ extern "C" int mpgan_conv_forward_act_bf16(const mpgan_conv_geom* g, const void*
   p.epi.scale = scale; p.epi.shift = shift; p.epi.slope = slope;
   p.out_bf16 = y_f32 ? 0 : 1;
   p.ldi = ldx; p.ldo = ldy;
-  set_geom_flags(p, g);
   build_gather_bf16(p, g, false);
   return hb_dispatch(p, (hipStream_t)stream, "conv_forward_act_bf16");
 }
@@ -2787,7 +2760,6 @@ extern "C" int mpgan_conv_backward_data_bf16(const mpgan_conv_geom* g, const voi
   p.in = static_cast<const float*>(dy); p.wp = static_cast<const float*>(w_packed_bwd); p.out = static_cast<float*>(dx);
   p.pro = make_pro(nullptr);
   p.ldi = lddy; p.ldo = lddx;
-  set_geom_flags(p, g);
   build_gather_bf16(p, g, true);
   return hb_dispatch(p, (hipStream_t)stream, "conv_backward_data_bf16");
 }
@@ -2826,7 +2798,6 @@ extern "C" int mpgan_conv_backward_data_stats_bf16(const mpgan_conv_geom* g, con
   p.bwd.z = static_cast<const float*>(z); p.bwd.ldz = ldz;
   p.bwd.scale = scale; p.bwd.shift = shift; p.bwd.mean = mean; p.bwd.invstd = invstd;
   p.bwd.part = partials; p.bwd.leaky = 1; p.bwd.slope = slope;
-  set_geom_flags(p, g);
   build_gather_bf16(p, g, true);
   // the pitch rule ahead of the operand checks too: a dy beyond the 4 GiB offset range reports its pitch
   rc = hb_pitch_rule(p, choose_bf16(p), "conv_backward_data_stats_bf16");

@@ -350,4 +350,17 @@ inline void build_transposed(GatherConv& p, int n, const int32_t* gath_dhw, int 
   p.nphase = np;
 }
 
+// The gather an entry point runs for a geometry and a direction, with the geometry's dispatch knobs.  Backward-data
+// swaps the gathered and the produced side; a conv's backward-data and a transposed conv's forward are the
+// transposed-type gather.  Returns whether it built that one.
+inline bool build_gather(GatherConv& p, const mpgan_conv_geom* g, bool backward_data, bool classes_ok = true) {
+  set_geom_flags(p, g);
+  const int32_t *gd = backward_data ? g->out_dhw : g->in_dhw, *pd = backward_data ? g->in_dhw : g->out_dhw;
+  const int cg = backward_data ? g->cout : g->cin, cp = backward_data ? g->cin : g->cout;
+  const bool transposed = backward_data == !g->transposed;
+  if (transposed) build_transposed(p, g->n, gd, cg, pd, cp, g->k, g->stride, g->pad, classes_ok);
+  else build_forward(p, g->n, gd, cg, pd, cp, g->k, g->stride, g->pad);
+  return transposed;
+}
+
 }  // namespace mpgan

@@ -1246,9 +1246,10 @@ static_assert(sizeof(GatherConv) + sizeof(PatchLaunch) <= 4096, "gather_patch ke
 
 // ---------------------------------------------------------------------------
 // Which kernel serves a gather conv.  choose_gather() (below, after the last predicate) is the ONE place the form is
-// decided: launch_gather runs its choice, and every geometry query (mpgan_conv_variant, the statistics-row counts,
-// accumulator / fold support) reads the choice made for the stand-in GatherConv the entry point would build
-// (standin_conv), so a query cannot disagree with its launch.
+// decided: every launch runs its choice (launch_gather_tail), and every geometry query (mpgan_conv_variant, the
+// statistics-row counts, accumulator / fold support, the label) reads the choice made for the stand-in GatherConv of the
+// entry point (standin_conv: the same build_gather, compact pitches, aligned operands), so a query cannot disagree with
+// its launch.
 // ---------------------------------------------------------------------------
 enum class GForm {
   ThinBf16OutRows,   // thin_cin1_rows_kernel<T, true>             (fp32 -> bf16, mpgan_conv_forward_f32_to_bf16)
@@ -1278,12 +1279,21 @@ struct GatherChoice {
   int code;          // mpgan_conv_variant's number (include/mpgan_hip.h); an Mm16 form keeps the code of the fp32 form
                      //   it stands in for (same tiles, same rows)
   int rows;          // partial rows of fused statistics / norm-backward sums the launch writes (0: the form has none)
-  int arg;           // template argument of a thin form (T, CQ, V, LANES or REVX) / of Patch3d (MM16) / of Kstep (SCALAR)
-  int bn, wraps, pro, ks;   // K-stepped forms: channel tile (select_variant), WRAPS, PRO, in-block split-K
-  bool fast;         // Pipe: the FAST instance
+  // The template arguments of the instance, final: the launchers and gather_kernel_name read these and decide nothing.
+  int arg;           // a thin form's one argument (T, CQ, V, LANES or REVX, a value that has an instance) / Patch3d: MM16
+  int pro;           // PRO of the K-stepped and patch forms, HAS_PRO of Patch3d
+  int bn, wraps, ks; // K-stepped forms: channel tile BN (it fixes TM, TN, WN: bn_tile), WRAPS, in-block split-K KS
+  bool fast, scalar; // Pipe: FAST; Kstep: SCALAR
+  int cin;           // Patch / PatchPersist: CIN, NARROW, MERGE
+  bool narrow, merge;
   PatchLaunch pl;    // Patch / PatchPersist: the plan, its LDS bytes; PatchPersist: tiles and grid
   int smem, ntiles, grid;
 };
+// <BN, TM, TN, WN> of the K-stepped kernels' three channel tiles
+struct BnTile { int bn, tm, tn, wn; };
+static BnTile bn_tile(int bn) { return bn == 128 ? BnTile{128, 2, 2, 2} : (bn == 64 ? BnTile{64, 1, 2, 1} : BnTile{32, 1, 1, 1}); }
+// The forms that fuse the norm-backward sums of a backward-data launch (BwdStats): the K-stepped ones.
+static bool fuses_bwd_sums(GForm f) { return f == GForm::Mm16 || f == GForm::Pipe || f == GForm::Dma || f == GForm::Kstep; }
 
 //   MERGE : one block walks ALL phases of its tile (strided backward-data / transposed convs): the
 //           phases read the same input pixels, so the patch (union of their tap offsets) and the
@@ -2046,6 +2056,21 @@ __global__ __launch_bounds__(256) void gather_patch_persist_kernel(const GatherC
   }
 }
 
+// Host view of the input window a tile of the patch kernels stages (the kernels compute the same from their arguments):
+// PH x PW pixels and `taps` weight taps -- of one phase, or (ph == nullptr) of the merged form, whose patch spans the
+// union of the phases' tap offsets (yspan x xspan) and whose weights are every tap of the kernel.
+struct PatchWindow { int PH, PW, taps; };
+static PatchWindow patch_window(const GatherConv& p, const Phase* ph, int yspan = 0, int xspan = 0) {
+  int taps = p.Ky * p.Kx;
+  if (ph) {
+    const int ny = ph->nz > 0 ? ph->ny : 0, nx = ph->nx;
+    yspan = (ny > 0 ? ny - 1 : 0) * abs(p.dstep[1]);
+    xspan = (nx > 0 ? nx - 1 : 0) * abs(p.dstep[2]);
+    taps = ny * nx;
+  }
+  return {(PT_H - 1) * p.istride[1] + yspan + 1, (PT_W - 1) * p.istride[2] + xspan + 1, taps};
+}
+
 // Geometry test for the patch kernel (pointer alignment is checked at launch).
 static bool patch_plan(const GatherConv& p, PatchLaunch* out, int* smem_bytes) {
   static const bool off = dev_env("MPGAN_DBG_NO_PATCH") != nullptr;
@@ -2060,15 +2085,13 @@ static bool patch_plan(const GatherConv& p, PatchLaunch* out, int* smem_bytes) {
   for (int i = 0; i < p.nphase; ++i) {
     const Phase& ph = p.ph[i];
     if (ph.nz > 1) return false;
-    const int ny = ph.nz > 0 ? ph.ny : 0, nx = ph.nx;
-    if (ny * nx > 9) return false;
-    const int ys = (ny > 0 ? ny - 1 : 0) * abs(p.dstep[1]), xs = (nx > 0 ? nx - 1 : 0) * abs(p.dstep[2]);
-    const int PH = (PT_H - 1) * p.istride[1] + ys + 1, PW = (PT_W - 1) * p.istride[2] + xs + 1;
-    if (PH * PW > maxpix) maxpix = PH * PW;
-    if (ny * nx > maxtaps) maxtaps = ny * nx;
+    const PatchWindow w = patch_window(p, &ph);
+    if (w.taps > 9) return false;
+    if (w.PH * w.PW > maxpix) maxpix = w.PH * w.PW;
+    if (w.taps > maxtaps) maxtaps = w.taps;
     if (out) {
-      out->fPW[i] = make_fastdiv((unsigned)PW);
-      out->fNx[i] = make_fastdiv((unsigned)(nx > 0 ? nx : 1));
+      out->fPW[i] = make_fastdiv((unsigned)w.PW);
+      out->fNx[i] = make_fastdiv((unsigned)(ph.nx > 0 ? ph.nx : 1));
     }
     if (ph.Mz > 0 && ph.My > maxMy) maxMy = ph.My;
     if (ph.Mx > maxMx) maxMx = ph.Mx;
@@ -2096,12 +2119,12 @@ static bool patch_plan(const GatherConv& p, PatchLaunch* out, int* smem_bytes) {
     if (ylo > yhi) merged = false;
   }
   if (merged) {
-    const int PHu = (PT_H - 1) * p.istride[1] + (yhi - ylo) + 1, PWu = (PT_W - 1) * p.istride[2] + (xhi - xlo) + 1;
-    mpatch = PHu * PWu * PC;
-    mbytes = ((long)mpatch + (long)p.Ky * p.Kx * p.Cout * PC + 256) * 4;
+    const PatchWindow u = patch_window(p, nullptr, yhi - ylo, xhi - xlo);
+    mpatch = u.PH * u.PW * PC;
+    mbytes = ((long)mpatch + (long)u.taps * p.Cout * PC + 256) * 4;
     if (mbytes > 96 * 1024) merged = false;
     else if (out) {
-      out->fPWm = make_fastdiv((unsigned)PWu);
+      out->fPWm = make_fastdiv((unsigned)u.PW);
       out->fKx = make_fastdiv((unsigned)p.Kx);
     }
   }
@@ -2118,70 +2141,42 @@ static bool patch_plan(const GatherConv& p, PatchLaunch* out, int* smem_bytes) {
   return true;
 }
 
-template <int CIN, int PRO, bool NARROW, bool MERGE>
-static int launch_patch_variant(const GatherConv& p, const PatchLaunch& pl, int smem, hipStream_t st) {
-  auto kern = gather_patch_kernel<CIN, PRO, NARROW, MERGE>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    if (e != hipSuccess) {
-      set_error("gather_patch: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return MPGAN_ERR_HIP;
-    }
-    attr_set = true;
+// Runs the instance <CIN, PRO, NARROW, MERGE> of a Patch (one tile per block) or PatchPersist choice.
+template <bool PERSIST, int CIN, int PRO, bool NARROW, bool MERGE>
+static int launch_patch_instance(const GatherConv& p, const GatherChoice& c, const PatchLaunch& pl, hipStream_t st) {
+  if constexpr (PERSIST) {
+    if (const int rc = raise_lds_limit<gather_patch_persist_kernel<CIN, PRO, NARROW, MERGE>>(150 * 1024, "gather_patch_persist"))
+      return rc;
+    hipLaunchKernelGGL((gather_patch_persist_kernel<CIN, PRO, NARROW, MERGE>), dim3((unsigned)c.grid), dim3(256), c.smem, st,
+                       p, pl, c.ntiles);
+    return check_launch("gather_patch_persist");
+  } else {
+    if (const int rc = raise_lds_limit<gather_patch_kernel<CIN, PRO, NARROW, MERGE>>(96 * 1024, "gather_patch")) return rc;
+    dim3 grid((unsigned)(pl.tiles_x * pl.tiles_y * p.N * (MERGE ? 1 : p.nphase)));
+    hipLaunchKernelGGL((gather_patch_kernel<CIN, PRO, NARROW, MERGE>), grid, dim3(256), c.smem, st, p, pl);
+    return check_launch("gather_patch");
   }
-  dim3 grid((unsigned)(pl.tiles_x * pl.tiles_y * p.N * (MERGE ? 1 : p.nphase)));
-  hipLaunchKernelGGL(kern, grid, dim3(256), smem, st, p, pl);
-  return check_launch("gather_patch");
 }
 
-template <int CIN>
-static int launch_patch_cin(const GatherConv& p, const PatchLaunch& pl, int smem, hipStream_t st) {
-  const bool pro = p.pro.scale != nullptr;
-  if (pl.merged) {       // never with a prologue (patch_plan)
-    if (p.Cout <= 16) return launch_patch_variant<CIN, 0, true, true>(p, pl, smem, st);
-    return launch_patch_variant<CIN, 0, false, true>(p, pl, smem, st);
-  }
-  if (p.Cout <= 16)
-    return pro ? launch_patch_variant<CIN, 1, true, false>(p, pl, smem, st)
-               : launch_patch_variant<CIN, 0, true, false>(p, pl, smem, st);
-  return pro ? launch_patch_variant<CIN, 1, false, false>(p, pl, smem, st)
-             : launch_patch_variant<CIN, 0, false, false>(p, pl, smem, st);
+// The one map from a patch choice's (cin, pro, narrow, merge) to the instances that exist (the merged form has no prologue).
+template <bool PERSIST, int CIN>
+static int launch_patch_cin(const GatherConv& p, const GatherChoice& c, const PatchLaunch& pl, hipStream_t st) {
+  if (c.merge)
+    return c.narrow ? launch_patch_instance<PERSIST, CIN, 0, true, true>(p, c, pl, st)
+                    : launch_patch_instance<PERSIST, CIN, 0, false, true>(p, c, pl, st);
+  if (c.narrow)
+    return c.pro ? launch_patch_instance<PERSIST, CIN, 1, true, false>(p, c, pl, st)
+                 : launch_patch_instance<PERSIST, CIN, 0, true, false>(p, c, pl, st);
+  return c.pro ? launch_patch_instance<PERSIST, CIN, 1, false, false>(p, c, pl, st)
+               : launch_patch_instance<PERSIST, CIN, 0, false, false>(p, c, pl, st);
 }
-
-// ---- persistent form -------------------------------------------------------------------------
-template <int CIN, int PRO, bool NARROW, bool MERGE>
-static int launch_patch_persist_variant(const GatherConv& p, const PatchLaunch& pl, int smem, int ntiles, int grid,
-                                        hipStream_t st) {
-  auto kern = gather_patch_persist_kernel<CIN, PRO, NARROW, MERGE>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    if (e != hipSuccess) {
-      set_error("gather_patch_persist: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return MPGAN_ERR_HIP;
-    }
-    attr_set = true;
+template <bool PERSIST>
+static int launch_patch(const GatherConv& p, const GatherChoice& c, const PatchLaunch& pl, hipStream_t st) {
+  switch (c.cin) {
+    case 16: return launch_patch_cin<PERSIST, 16>(p, c, pl, st);
+    case 32: return launch_patch_cin<PERSIST, 32>(p, c, pl, st);
+    default: return launch_patch_cin<PERSIST, 64>(p, c, pl, st);
   }
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), smem, st, p, pl, ntiles);
-  return check_launch("gather_patch_persist");
-}
-
-template <int CIN>
-static int launch_patch_persist_cin(const GatherConv& p, const PatchLaunch& pl, int smem, int ntiles, int grid,
-                                    hipStream_t st) {
-  const bool pro = p.pro.scale != nullptr;
-  if (pl.merged) {
-    if (p.Cout <= 16) return launch_patch_persist_variant<CIN, 0, true, true>(p, pl, smem, ntiles, grid, st);
-    return launch_patch_persist_variant<CIN, 0, false, true>(p, pl, smem, ntiles, grid, st);
-  }
-  if (p.Cout <= 16)
-    return pro ? launch_patch_persist_variant<CIN, 1, true, false>(p, pl, smem, ntiles, grid, st)
-               : launch_patch_persist_variant<CIN, 0, true, false>(p, pl, smem, ntiles, grid, st);
-  return pro ? launch_patch_persist_variant<CIN, 1, false, false>(p, pl, smem, ntiles, grid, st)
-             : launch_patch_persist_variant<CIN, 0, false, false>(p, pl, smem, ntiles, grid, st);
 }
 
 // Plan of the persistent form; false: keep the one-tile-per-block kernel (several unmerged phases, a patch
@@ -2192,18 +2187,8 @@ static bool patch_persist_plan(const GatherConv& p, const PatchLaunch& pl, Patch
   if (off) return false;
   if (p.nphase != 1 && !pl.merged) return false;
   const int PC = p.Cin + 4, CQ = p.Cin / 4;
-  int PH, PW, wtaps;
-  if (pl.merged) {
-    PH = (PT_H - 1) * p.istride[1] + (pl.yhi - pl.ylo) + 1;
-    PW = (PT_W - 1) * p.istride[2] + (pl.xhi - pl.xlo) + 1;
-    wtaps = p.Ky * p.Kx;
-  } else {
-    const Phase& ph = p.ph[0];
-    const int ny = ph.nz > 0 ? ph.ny : 0, nx = ph.nx;
-    PH = (PT_H - 1) * p.istride[1] + (ny > 0 ? ny - 1 : 0) * abs(p.dstep[1]) + 1;
-    PW = (PT_W - 1) * p.istride[2] + (nx > 0 ? nx - 1 : 0) * abs(p.dstep[2]) + 1;
-    wtaps = ny * nx;
-  }
+  const PatchWindow w = pl.merged ? patch_window(p, nullptr, pl.yhi - pl.ylo, pl.xhi - pl.xlo) : patch_window(p, &p.ph[0]);
+  const int PH = w.PH, PW = w.PW, wtaps = w.taps;
   const int LU = p.Cin == 16 ? 9 : 12;
   if (PH * PW * CQ > LU * 256) return false;
   if (PH > 0xffff || PW > 0xffff) return false;
@@ -2255,16 +2240,7 @@ static int launch_variant(const GatherConv& p, long maxM, hipStream_t st) {
   auto kern = gather_conv_kernel<BN, TM, TN, WN, SCALAR>;
   static const int lds_pad = dev_env("MPGAN_DBG_LDS_PAD") ? atoi(dev_env("MPGAN_DBG_LDS_PAD")) : 0;
   const int smem = 2 * (BM + BN) * PITCH * (int)sizeof(float) + lds_pad;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (e != hipSuccess) {
-      set_error("gather_conv: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return MPGAN_ERR_HIP;
-    }
-    attr_set = true;
-  }
+  if (const int rc = raise_lds_limit<gather_conv_kernel<BN, TM, TN, WN, SCALAR>>(smem, "gather_conv")) return rc;
   GatherConv q = p;
   const long pairs = set_tile_grid(q, BM);
   q.ntiles = (p.Cout + BN - 1) / BN;
@@ -2301,16 +2277,8 @@ static int launch_pipe_variant(const GatherConv& p, long maxM, hipStream_t st) {
   auto kern = gather_conv_pipe_kernel<BN, TM, TN, WN, WRAPS, PRO, FAST, KS>;
   static const int lds_pad = dev_env("MPGAN_DBG_LDS_PAD") ? atoi(dev_env("MPGAN_DBG_LDS_PAD")) : 0;
   const int smem = KS * 2 * (BM + BN) * PITCH * (int)sizeof(float) + lds_pad;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (e != hipSuccess) {
-      set_error("gather_conv_pipe: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return MPGAN_ERR_HIP;
-    }
-    attr_set = true;
-  }
+  if (const int rc = raise_lds_limit<gather_conv_pipe_kernel<BN, TM, TN, WN, WRAPS, PRO, FAST, KS>>(smem, "gather_conv_pipe"))
+    return rc;
   GatherConv q = p;
   const long pairs = set_tile_grid(q, BM);
   q.ntiles = (p.Cout + BN - 1) / BN;
@@ -2374,15 +2342,7 @@ static int launch_dma_variant(const GatherConv& p, long maxM, hipStream_t st) {
   auto kern = gather_conv_dma_kernel<BN, TM, TN, WN, NST>;
   constexpr int smem_loop = NST * (BM + BN) * 128, smem_epi = (2048 + 4 * 32 * 36 + 1024) * 4;   // (conv_epilogue's scratch)
   constexpr int smem = smem_loop > smem_epi ? smem_loop : smem_epi;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (e != hipSuccess) {
-      set_error("gather_conv_dma: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return MPGAN_ERR_HIP;
-    }
-    attr_set = true;
-  }
+  if (const int rc = raise_lds_limit<gather_conv_dma_kernel<BN, TM, TN, WN, NST>>(smem, "gather_conv_dma")) return rc;
   GatherConv q = p;
   const long pairs = set_tile_grid(q, BM);
   q.ntiles = (p.Cout + BN - 1) / BN;
@@ -2702,32 +2662,14 @@ static P3Grid patch3d_grid(const GatherConv& p) {
   return P3Grid{(ph.Mz + P3_TZ - 1) / P3_TZ, (ph.My + P3_TY - 1) / P3_TY, (ph.Mx + P3_TX - 1) / P3_TX};
 }
 
-static int launch_patch3d(const GatherConv& p, const GatherChoice& c, hipStream_t st) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(gather_patch3d_c16_kernel<true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, P3_SMEM);
-    hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(gather_patch3d_c16_kernel<false>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, P3_SMEM);
-    hipError_t e3 = hipFuncSetAttribute(reinterpret_cast<const void*>(gather_patch3d_c16_kernel<true, true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, P3M_SMEM);
-    hipError_t e4 = hipFuncSetAttribute(reinterpret_cast<const void*>(gather_patch3d_c16_kernel<false, true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, P3M_SMEM);
-    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess) {
-      set_error("gather_patch3d: hipFuncSetAttribute: %s",
-                hipGetErrorString(e1 != hipSuccess ? e1 : (e2 != hipSuccess ? e2 : (e3 != hipSuccess ? e3 : e4))));
-      return MPGAN_ERR_HIP;
-    }
-    attr_set = true;
-  }
+template <bool HAS_PRO, bool MM16>
+static int launch_patch3d_instance(const GatherConv& p, hipStream_t st) {
+  constexpr int smem = MM16 ? P3M_SMEM : P3_SMEM;
+  if (const int rc = raise_lds_limit<gather_patch3d_c16_kernel<HAS_PRO, MM16>>(smem, "gather_patch3d")) return rc;
   const P3Grid tg = patch3d_grid(p);
   const long ntiles = (long)p.N * tg.tiles_z * tg.tiles_y * tg.tiles_x;
   dim3 grid((unsigned)(ntiles < 512 ? ntiles : 512));          // two resident blocks per CU, each walking its range of tiles
-  if (c.arg) {
-    if (c.pro) hipLaunchKernelGGL((gather_patch3d_c16_kernel<true, true>), grid, dim3(256), P3M_SMEM, st, p, tg);
-    else hipLaunchKernelGGL((gather_patch3d_c16_kernel<false, true>), grid, dim3(256), P3M_SMEM, st, p, tg);
-  } else if (c.pro) hipLaunchKernelGGL(gather_patch3d_c16_kernel<true>, grid, dim3(256), P3_SMEM, st, p, tg);
-  else hipLaunchKernelGGL(gather_patch3d_c16_kernel<false>, grid, dim3(256), P3_SMEM, st, p, tg);
+  hipLaunchKernelGGL((gather_patch3d_c16_kernel<HAS_PRO, MM16>), grid, dim3(256), smem, st, p, tg);
   return check_launch("gather_patch3d_c16");
 }
 
@@ -2850,7 +2792,10 @@ static GatherChoice choose_gather(const GatherConv& p, long maxM) {
                     "(mpgan_conv_acc_supported / mpgan_conv_fold_supported said otherwise?)");
       c.code = c.pl.merged ? 17 : 16;
       c.rows = c.pl.tiles_x * c.pl.tiles_y * p.N * p.nphase;
+      c.cin = p.Cin;                    // 16, 32 or 64 (patch_plan)
       c.pro = p.pro.scale != nullptr;   // (never with the merged form: patch_plan)
+      c.narrow = p.Cout <= 16;
+      c.merge = c.pl.merged != 0;
       c.form = persist ? GForm::PatchPersist : GForm::Patch;
       if (persist) {
         c.pl = pp;
@@ -2882,7 +2827,9 @@ static GatherChoice choose_gather(const GatherConv& p, long maxM) {
     else if (p.pro.n_stride == 0 && p.pro.act == MPGAN_ACT_LEAKY && !p.pro.slope_ptr && p.pro.slope >= 0.f && p.pro.slope <= 1.f)
       c.pro = 3;
     else c.pro = p.pro.n_stride == 0 ? 1 : 2;
-    const bool ks2 = variant != 128 && pipe_wants_ksplit2(p, variant, maxM);   // (Cin % 32 == 0 only)
+    // The instance rules, applied here and nowhere else: FAST exists for the 128 tile with one wrap and PRO 3, in-block
+    // split-K (KS = 2) for one wrap and the 64 / 32 tiles -- of the fp32 kernel without PRO 3.
+    const bool ks2 = c.wraps == 1 && variant != 128 && pipe_wants_ksplit2(p, variant, maxM);
     if (c.wraps == 1 && c.pro == 3 && variant == 128 && fast_geometry(p, 128)) {
       c.fast = true;
       c.code = 1128;
@@ -2902,7 +2849,7 @@ static GatherChoice choose_gather(const GatherConv& p, long maxM) {
     return c;
   }
   c.form = GForm::Kstep;
-  c.arg = !vec;
+  c.scalar = !vec;
   return c;
 }
 #undef CHOICE_REFUSE
@@ -2919,9 +2866,9 @@ static int launch_chosen(const GatherConv& p, const GatherChoice& c, long maxM, 
     case GForm::ThinBf16OutRows:
     case GForm::Cin1Rows: {
       const bool bf = c.form == GForm::ThinBf16OutRows;
-      if (bf && T == 9) hipLaunchKernelGGL((thin_cin1_rows_kernel<9, true>), block_grid, dim3(256), 0, st, p);
+      if (bf && c.arg == 9) hipLaunchKernelGGL((thin_cin1_rows_kernel<9, true>), block_grid, dim3(256), 0, st, p);
       else if (bf) hipLaunchKernelGGL((thin_cin1_rows_kernel<27, true>), block_grid, dim3(256), 0, st, p);
-      else if (T == 9) hipLaunchKernelGGL((thin_cin1_rows_kernel<9, false>), block_grid, dim3(256), 0, st, p);
+      else if (c.arg == 9) hipLaunchKernelGGL((thin_cin1_rows_kernel<9, false>), block_grid, dim3(256), 0, st, p);
       else hipLaunchKernelGGL((thin_cin1_rows_kernel<27, false>), block_grid, dim3(256), 0, st, p);
       return check_launch(bf ? "thin_cin1_rows_bf16" : "thin_cin1_rows");
     }
@@ -2930,13 +2877,7 @@ static int launch_chosen(const GatherConv& p, const GatherChoice& c, long maxM, 
       if (c.arg == 4) hipLaunchKernelGGL((thin_cin1_full_kernel<4, true>), block_grid, dim3(256), smem, st, p);
       else if (c.arg == 8) hipLaunchKernelGGL((thin_cin1_full_kernel<8, true>), block_grid, dim3(256), smem, st, p);
       else {
-        static bool attr_set = false;
-        if (!attr_set) {
-          hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(thin_cin1_full_kernel<16, true>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-          if (e != hipSuccess) { set_error("thin_cin1_full: hipFuncSetAttribute: %s", hipGetErrorString(e)); return MPGAN_ERR_HIP; }
-          attr_set = true;
-        }
+        if (const int rc = raise_lds_limit<thin_cin1_full_kernel<16, true>>(96 * 1024, "thin_cin1_full")) return rc;
         hipLaunchKernelGGL((thin_cin1_full_kernel<16, true>), block_grid, dim3(256), smem, st, p);
       }
       return check_launch("thin_cin1_full_bf16");
@@ -3002,13 +2943,10 @@ static int launch_chosen(const GatherConv& p, const GatherChoice& c, long maxM, 
       }
       return check_launch("thin_cout1");
     }
-    case GForm::Patch3d: return launch_patch3d(p, c, st);
-    case GForm::Patch:
-      switch (p.Cin) {
-        case 16: return launch_patch_cin<16>(p, c.pl, c.smem, st);
-        case 32: return launch_patch_cin<32>(p, c.pl, c.smem, st);
-        default: return launch_patch_cin<64>(p, c.pl, c.smem, st);
-      }
+    case GForm::Patch3d:
+      if (c.arg) return c.pro ? launch_patch3d_instance<true, true>(p, st) : launch_patch3d_instance<false, true>(p, st);
+      return c.pro ? launch_patch3d_instance<true, false>(p, st) : launch_patch3d_instance<false, false>(p, st);
+    case GForm::Patch: return launch_patch<false>(p, c, c.pl, st);
     case GForm::PatchPersist: {
       static void* zp = nullptr;          // address of the device-side zero page, looked up once
       if (!zp && hipGetSymbolAddress(&zp, HIP_SYMBOL(g_patch_zero_page)) != hipSuccess) {
@@ -3018,11 +2956,7 @@ static int launch_chosen(const GatherConv& p, const GatherChoice& c, long maxM, 
       }
       PatchLaunch pl = c.pl;
       pl.zero_page = zp;
-      switch (p.Cin) {
-        case 16: return launch_patch_persist_cin<16>(p, pl, c.smem, c.ntiles, c.grid, st);
-        case 32: return launch_patch_persist_cin<32>(p, pl, c.smem, c.ntiles, c.grid, st);
-        default: return launch_patch_persist_cin<64>(p, pl, c.smem, c.ntiles, c.grid, st);
-      }
+      return launch_patch<true>(p, c, pl, st);
     }
     case GForm::Mm16: return launch_gather_mm16(p, c.bn, c.wraps, c.pro, c.ks, maxM, st);
     case GForm::Pipe: return c.wraps == 1 ? launch_pipe_pro<1>(p, c, maxM, st) : launch_pipe_pro<2>(p, c, maxM, st);
@@ -3031,7 +2965,7 @@ static int launch_chosen(const GatherConv& p, const GatherChoice& c, long maxM, 
       if (c.bn == 64) return launch_dma_variant<64, 1, 2, 1>(p, maxM, st);
       return launch_dma_variant<32, 1, 1, 1, 2>(p, maxM, st);
     case GForm::Kstep:
-      if (c.arg) {
+      if (c.scalar) {
         if (c.bn == 128) return launch_variant<128, 2, 2, 2, true>(p, maxM, st);
         if (c.bn == 64) return launch_variant<64, 1, 2, 1, true>(p, maxM, st);
         return launch_variant<32, 1, 1, 1, true>(p, maxM, st);
@@ -3043,54 +2977,55 @@ static int launch_chosen(const GatherConv& p, const GatherChoice& c, long maxM, 
   return MPGAN_ERR_UNSUPPORTED;
 }
 
-// rocprofv3's name of the instance launch_chosen runs for a choice (without `void mpgan::` and the argument list).
-static int gather_kernel_name(const GatherConv& p, const GatherChoice& c, char* buf, int len) {
+// rocprofv3's name of the instance launch_chosen runs for a choice (without `void mpgan::` and the argument list): the
+// choice's fields, printed.
+static int gather_kernel_name(const GatherChoice& c, char* buf, int len) {
   const char* b[2] = {"false", "true"};
-  const int a = c.arg, lanes16 = a == 4 || a == 8 ? a : 16;   // (the instances of the thin forms' switches)
-  const int T = p.Kz * p.Ky * p.Kx == 9 ? 9 : 27;
-  // K-stepped forms: BN, TM, TN, WN of the channel tile
-  const int tm = c.bn == 128 ? 2 : 1, tn = c.bn == 32 ? 1 : 2, wn = c.bn == 128 ? 2 : 1;
-  const int cin = p.Cin == 16 || p.Cin == 32 ? p.Cin : 64;
-  const int ppro = c.pl.merged ? 0 : c.pro;
+  const BnTile t = bn_tile(c.bn);
   switch (c.form) {
-    case GForm::ThinBf16OutRows: return snprintf(buf, len, "thin_cin1_rows_kernel<%d, true>", T);
-    case GForm::Cin1Rows: return snprintf(buf, len, "thin_cin1_rows_kernel<%d, false>", T);
-    case GForm::ThinBf16OutFull: return snprintf(buf, len, "thin_cin1_full_kernel<%d, true>", lanes16);
-    case GForm::Cin1Full: return snprintf(buf, len, "thin_cin1_full_kernel<%d, false>", lanes16);
+    case GForm::ThinBf16OutRows: return snprintf(buf, len, "thin_cin1_rows_kernel<%d, true>", c.arg);
+    case GForm::Cin1Rows: return snprintf(buf, len, "thin_cin1_rows_kernel<%d, false>", c.arg);
+    case GForm::ThinBf16OutFull: return snprintf(buf, len, "thin_cin1_full_kernel<%d, true>", c.arg);
+    case GForm::Cin1Full: return snprintf(buf, len, "thin_cin1_full_kernel<%d, false>", c.arg);
     case GForm::ThinBf16InMfma: return snprintf(buf, len, "thin_cout1_mfma_bf16_kernel");
-    case GForm::ThinBf16In: return snprintf(buf, len, "thin_cout1_kernel<%d, true>", lanes16);
-    case GForm::C1C1Rows4: return snprintf(buf, len, "thin_c1c1_rows4_kernel<%s>", b[a != 0]);
-    case GForm::Cin1: return snprintf(buf, len, "thin_cin1_kernel<%d>", a == 4 ? 4 : 1);
-    case GForm::ConvtQuad: return snprintf(buf, len, "convt_quad_cout1_kernel<%d>", lanes16);
-    case GForm::ConvtOct: return snprintf(buf, len, "convt_oct_cout1_kernel<%d>", lanes16);
-    case GForm::Cout1:
-      return snprintf(buf, len, "thin_cout1_kernel<%d, false>", a > 0 && a <= 32 && (a & (a - 1)) == 0 ? a : 64);
-    case GForm::Patch3d: return snprintf(buf, len, "gather_patch3d_c16_kernel<%s, %s>", b[c.pro != 0], b[a != 0]);
+    case GForm::ThinBf16In: return snprintf(buf, len, "thin_cout1_kernel<%d, true>", c.arg);
+    case GForm::C1C1Rows4: return snprintf(buf, len, "thin_c1c1_rows4_kernel<%s>", b[c.arg]);
+    case GForm::Cin1: return snprintf(buf, len, "thin_cin1_kernel<%d>", c.arg);
+    case GForm::ConvtQuad: return snprintf(buf, len, "convt_quad_cout1_kernel<%d>", c.arg);
+    case GForm::ConvtOct: return snprintf(buf, len, "convt_oct_cout1_kernel<%d>", c.arg);
+    case GForm::Cout1: return snprintf(buf, len, "thin_cout1_kernel<%d, false>", c.arg);
+    case GForm::Patch3d: return snprintf(buf, len, "gather_patch3d_c16_kernel<%s, %s>", b[c.pro], b[c.arg]);
     case GForm::Patch:
+      return snprintf(buf, len, "gather_patch_kernel<%d, %d, %s, %s>", c.cin, c.pro, b[c.narrow], b[c.merge]);
     case GForm::PatchPersist:
-      return snprintf(buf, len, "%s<%d, %d, %s, %s>",
-                      c.form == GForm::Patch ? "gather_patch_kernel" : "gather_patch_persist_kernel", cin, ppro,
-                      b[p.Cout <= 16], b[c.pl.merged != 0]);
-    case GForm::Mm16: {   // (launch_gather_mm16: in-block split-K for one wrap and the 64 / 32 channel tiles only)
-      const int ks = c.wraps == 1 && c.ks == 2 && c.bn != 128 ? 2 : 1;
-      return snprintf(buf, len, "gather_conv_pipe_kernel<%d, %d, %d, %d, %d, %d, false, %d, true>", c.bn, tm, tn, wn,
-                      c.wraps, c.pro, ks);
-    }
-    case GForm::Pipe: {   // (launch_pipe_bn: FAST is the 128 tile, in-block split-K the 64 / 32 tiles)
-      const bool fast = c.wraps == 1 && c.pro == 3 && c.fast;
-      const int ks = !fast && c.wraps == 1 && c.pro != 3 && c.ks == 2 ? 2 : 1;
-      const int bn = fast ? 128 : (ks == 2 && c.bn != 64 ? 32 : c.bn);
-      return snprintf(buf, len, "gather_conv_pipe_kernel<%d, %d, %d, %d, %d, %d, %s, %d, false>", bn,
-                      bn == 128 ? 2 : 1, bn == 32 ? 1 : 2, bn == 128 ? 2 : 1, c.wraps, c.pro, b[fast], ks);
-    }
-    case GForm::Dma: return snprintf(buf, len, "gather_conv_dma_kernel<%d, %d, %d, %d, 2>", c.bn, tm, tn, wn);
-    case GForm::Kstep: return snprintf(buf, len, "gather_conv_kernel<%d, %d, %d, %d, %s>", c.bn, tm, tn, wn, b[a != 0]);
+      return snprintf(buf, len, "gather_patch_persist_kernel<%d, %d, %s, %s>", c.cin, c.pro, b[c.narrow], b[c.merge]);
+    case GForm::Mm16:
+      return snprintf(buf, len, "gather_conv_pipe_kernel<%d, %d, %d, %d, %d, %d, false, %d, true>", t.bn, t.tm, t.tn, t.wn,
+                      c.wraps, c.pro, c.ks);
+    case GForm::Pipe:
+      return snprintf(buf, len, "gather_conv_pipe_kernel<%d, %d, %d, %d, %d, %d, %s, %d, false>", t.bn, t.tm, t.tn, t.wn,
+                      c.wraps, c.pro, b[c.fast], c.ks);
+    case GForm::Dma: return snprintf(buf, len, "gather_conv_dma_kernel<%d, %d, %d, %d, 2>", t.bn, t.tm, t.tn, t.wn);
+    case GForm::Kstep:
+      return snprintf(buf, len, "gather_conv_kernel<%d, %d, %d, %d, %s>", t.bn, t.tm, t.tn, t.wn, b[c.scalar]);
   }
   return snprintf(buf, len, "?");
 }
 
+// The tail of every gather launch: size checks, the choice, its launch.
+static int launch_gather_tail(const GatherConv& p, hipStream_t st) {
+  const long maxM = max_phase_pixels(p);
+  if (maxM == 0) return MPGAN_OK;
+  MPGAN_CHECK_ARG((long)p.N * p.Do * p.Ho * p.Wo < (1L << 31) && (long)p.N * p.Di * p.Hi * p.Wi < (1L << 31) &&
+                      maxM < (1L << 31) - 256,
+                  "gather_conv: more than 2^31 pixels");
+  MPGAN_CHECK_ARG((long)p.Cout * p.Cin * p.Kz * p.Ky * p.Kx < (1L << 31), "gather_conv: weight larger than 2^31");
+  return launch_chosen(p, choose_gather(p, maxM), maxM, st);
+}
+
+// The launch of the fp32 entries.  The STAMPS build hands each of them the next slice of the stamp buffer (the bf16-thin
+// entries call the tail and take none).
 #ifdef MPGAN_STAMPS
-static int launch_gather_impl(const GatherConv& p, hipStream_t st);
 static int launch_gather(const GatherConv& p0, hipStream_t st) {
   GatherConv p = p0;
   StampCtx& c = stamp_ctx();
@@ -3101,32 +3036,15 @@ static int launch_gather(const GatherConv& p0, hipStream_t st) {
     p.stamp_blocks = (int)c.blocks;
     c.next += 1;
   }
-  return launch_gather_impl(p, st);
+  return launch_gather_tail(p, st);
 }
-static int launch_gather_impl(const GatherConv& p, hipStream_t st) {
 #else
-static int launch_gather(const GatherConv& p, hipStream_t st) {
+static int launch_gather(const GatherConv& p, hipStream_t st) { return launch_gather_tail(p, st); }
 #endif
-  const long maxM = max_phase_pixels(p);
-  if (maxM == 0) return MPGAN_OK;
-  MPGAN_CHECK_ARG((long)p.N * p.Do * p.Ho * p.Wo < (1L << 31) && (long)p.N * p.Di * p.Hi * p.Wi < (1L << 31) &&
-                      maxM < (1L << 31) - 256,
-                  "gather_conv: more than 2^31 pixels");
-  MPGAN_CHECK_ARG((long)p.Cout * p.Cin * p.Kz * p.Ky * p.Kx < (1L << 31), "gather_conv: weight larger than 2^31");
-  return launch_chosen(p, choose_gather(p, maxM), maxM, st);
-}
 
 }  // namespace mpgan
 
 using namespace mpgan;
-
-static void build_for_forward(GatherConv& p, const mpgan_conv_geom* g) {
-  set_geom_flags(p, g);
-  if (!g->transposed)
-    build_forward(p, g->n, g->in_dhw, g->cin, g->out_dhw, g->cout, g->k, g->stride, g->pad);
-  else
-    build_transposed(p, g->n, g->in_dhw, g->cin, g->out_dhw, g->cout, g->k, g->stride, g->pad);
-}
 
 // out[pix][co] = bias[co] + sum_s partial[s][pix][co]   (fixed order)
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ part, int ksplit, long rows,
@@ -3162,7 +3080,7 @@ static int plan_ksplit(const GatherConv& p) {
 extern "C" int64_t mpgan_conv_splitk_workspace(const mpgan_conv_geom* g) {
   if (check_geom(g)) return -1;
   GatherConv p{};
-  build_for_forward(p, g);
+  build_gather(p, g, false);
   const int ks = plan_ksplit(p);
   if (ks <= 1) return 0;
   return (int64_t)ks * g->n * g->out_dhw[0] * g->out_dhw[1] * g->out_dhw[2] * g->cout * (int64_t)sizeof(float);
@@ -3180,14 +3098,9 @@ static GatherConv standin_conv(const mpgan_conv_geom* g, bool backward_data, int
   p.fold = make_fold(nullptr);
   if (pro_code) p.pro.scale = p.pro.shift = g_standin;
   if (pro_code == 3) { p.pro.act = MPGAN_ACT_LEAKY; p.pro.slope = 0.2f; }
-  set_geom_flags(p, g);
-  const int cg = backward_data ? g->cout : g->cin, cp = backward_data ? g->cin : g->cout;
-  const int32_t* gd = backward_data ? g->out_dhw : g->in_dhw;
-  const int32_t* pd = backward_data ? g->in_dhw : g->out_dhw;
-  if (backward_data == !g->transposed) build_transposed(p, g->n, gd, cg, pd, cp, g->k, g->stride, g->pad);
-  else build_forward(p, g->n, gd, cg, pd, cp, g->k, g->stride, g->pad);
-  p.ldi = cg; p.ldo = cp; p.ldr = cp;
-  if (pro_code == 2) p.pro.n_stride = cg;
+  build_gather(p, g, backward_data);
+  p.ldi = p.Cin; p.ldo = p.Cout; p.ldr = p.Cout;
+  if (pro_code == 2) p.pro.n_stride = p.Cin;
   return p;
 }
 
@@ -3203,8 +3116,7 @@ extern "C" int mpgan_conv_kernel_name(const mpgan_conv_geom* g, int32_t backward
   int rc = check_geom(g);
   if (rc) return rc;
   MPGAN_CHECK_ARG(buf && len > 0 && pro_code >= 0 && pro_code <= 3, "conv_kernel_name: no buffer / bad prologue code");
-  const GatherConv p = standin_conv(g, backward_data, pro_code);
-  const int n = gather_kernel_name(p, choose_standin(p), buf, len);
+  const int n = gather_kernel_name(choose_standin(standin_conv(g, backward_data, pro_code)), buf, len);
   MPGAN_CHECK_ARG(n < len, "conv_kernel_name: the name needs %d bytes", n + 1);
   return MPGAN_OK;
 }
@@ -3239,7 +3151,7 @@ extern "C" int32_t mpgan_conv_fold_supported(const mpgan_conv_geom* g) {
 extern "C" int32_t mpgan_conv_bwd_stats_rows(const mpgan_conv_geom* g) {
   if (check_geom(g)) return 0;
   const GatherChoice c = choose_standin(standin_conv(g, true, 0));
-  return c.rc == MPGAN_OK && c.form >= GForm::Mm16 ? c.rows : 0;
+  return c.rc == MPGAN_OK && fuses_bwd_sums(c.form) ? c.rows : 0;
 }
 
 extern "C" int mpgan_conv_forward_fold(const mpgan_conv_geom* g, const float* x, int32_t ldx, const float* w_packed,
@@ -3264,7 +3176,7 @@ extern "C" int mpgan_conv_forward_fold(const mpgan_conv_geom* g, const float* x,
     p.pro.n_stride = 0;
   }
   p.ldi = ldx; p.ldo = ldy; p.ldr = ldr; p.tanh_out = tanh_out;
-  build_for_forward(p, g);
+  build_gather(p, g, false);
   if (stats_partials || stats_acc) {
     MPGAN_CHECK_ARG(!resid && !tanh_out, "conv_forward: fused statistics describe the raw conv output (no resid/tanh)");
     const int code = p.pro.scale ? (p.pro.n_stride ? 2 : 1) : 0;
@@ -3300,7 +3212,7 @@ extern "C" int mpgan_conv_forward_act(const mpgan_conv_geom* g, const float* x, 
   p.fold = make_fold(nullptr);
   p.epi.scale = scale; p.epi.shift = shift; p.epi.slope = slope;
   p.ldi = ldx; p.ldo = ldy; p.ldr = ldr; p.tanh_out = tanh_out;
-  build_for_forward(p, g);
+  build_gather(p, g, false);
   return launch_gather(p, (hipStream_t)stream);
 }
 
@@ -3323,7 +3235,7 @@ extern "C" int mpgan_conv_forward_splitk(const mpgan_conv_geom* g, const float* 
   p.in = x; p.wp = w_packed; p.out = y; p.bias = bias;
   p.pro = make_pro(pro);
   p.ldi = ldx; p.ldo = ldy;
-  build_for_forward(p, g);
+  build_gather(p, g, false);
   const int ks = plan_ksplit(p);
   if (ks <= 1) return launch_gather(p, (hipStream_t)stream);
   const long rows = (long)g->n * g->out_dhw[0] * g->out_dhw[1] * g->out_dhw[2];
@@ -3355,11 +3267,7 @@ extern "C" int mpgan_conv_backward_data(const mpgan_conv_geom* g, const float* d
   p.in = dy; p.wp = w_packed_bwd; p.out = dx; p.bias = nullptr; p.resid = resid;
   p.pro = make_pro(nullptr);
   p.ldi = lddy; p.ldo = lddx; p.ldr = ldr; p.tanh_out = 0;
-  set_geom_flags(p, g);
-  if (!g->transposed)
-    build_transposed(p, g->n, g->out_dhw, g->cout, g->in_dhw, g->cin, g->k, g->stride, g->pad);
-  else
-    build_forward(p, g->n, g->out_dhw, g->cout, g->in_dhw, g->cin, g->k, g->stride, g->pad);
+  build_gather(p, g, true);
   return launch_gather(p, (hipStream_t)stream);
 }
 
@@ -3385,11 +3293,7 @@ extern "C" int mpgan_conv_backward_data_stats(const mpgan_conv_geom* g, const fl
   p.ldi = lddy; p.ldo = lddx; p.ldr = 0; p.tanh_out = 0;
   p.bwd.z = z; p.bwd.ldz = ldz; p.bwd.scale = scale; p.bwd.shift = shift; p.bwd.mean = mean; p.bwd.invstd = invstd;
   p.bwd.leaky = act == MPGAN_ACT_LEAKY; p.bwd.slope = slope; p.bwd.part = partials;
-  set_geom_flags(p, g);
-  if (!g->transposed)
-    build_transposed(p, g->n, g->out_dhw, g->cout, g->in_dhw, g->cin, g->k, g->stride, g->pad);
-  else
-    build_forward(p, g->n, g->out_dhw, g->cout, g->in_dhw, g->cin, g->k, g->stride, g->pad);
+  build_gather(p, g, true);
   return launch_gather(p, (hipStream_t)stream);
 }
 
@@ -3409,10 +3313,8 @@ extern "C" int mpgan_conv_forward_f32_to_bf16(const mpgan_conv_geom* g, const fl
   p.ldi = ldx; p.ldo = ldy;
   p.out_bf16 = 1;
   p.stats = stats_partials;
-  build_forward(p, g->n, g->in_dhw, g->cin, g->out_dhw, g->cout, g->k, g->stride, g->pad);
-  const long maxM = max_phase_pixels(p);
-  MPGAN_CHECK_ARG(maxM < (1L << 31) - 256, "conv_forward_f32_to_bf16: more than 2^31 pixels");
-  return launch_chosen(p, choose_gather(p, maxM), maxM, (hipStream_t)stream);
+  build_gather(p, g, false);
+  return launch_gather_tail(p, (hipStream_t)stream);
 }
 
 // The same layer in eval mode: y (bf16) = lrelu(conv(x) * scale[c] + shift[c], slope[c]), the activated value rounded once
@@ -3436,10 +3338,8 @@ extern "C" int mpgan_conv_forward_act_f32_to_bf16(const mpgan_conv_geom* g, cons
   p.epi.scale = scale; p.epi.shift = shift; p.epi.slope = slope;
   p.ldi = ldx; p.ldo = ldy;
   p.out_bf16 = 1;
-  build_forward(p, g->n, g->in_dhw, g->cin, g->out_dhw, g->cout, g->k, g->stride, g->pad);
-  const long maxM = max_phase_pixels(p);
-  MPGAN_CHECK_ARG(maxM < (1L << 31) - 256, "conv_forward_act_f32_to_bf16: more than 2^31 pixels");
-  return launch_chosen(p, choose_gather(p, maxM), maxM, (hipStream_t)stream);
+  build_gather(p, g, false);
+  return launch_gather_tail(p, (hipStream_t)stream);
 }
 
 extern "C" int mpgan_conv_backward_data_bf16_to_f32(const mpgan_conv_geom* g, const void* dy, int32_t lddy,
@@ -3454,8 +3354,6 @@ extern "C" int mpgan_conv_backward_data_bf16_to_f32(const mpgan_conv_geom* g, co
   p.pro = make_pro(nullptr);
   p.ldi = lddy; p.ldo = lddx;
   p.in_bf16 = 1;
-  build_transposed(p, g->n, g->out_dhw, g->cout, g->in_dhw, g->cin, g->k, g->stride, g->pad);
-  const long maxM = max_phase_pixels(p);
-  MPGAN_CHECK_ARG(maxM < (1L << 31) - 256, "conv_backward_data_bf16_to_f32: more than 2^31 pixels");
-  return launch_chosen(p, choose_gather(p, maxM), maxM, (hipStream_t)stream);
+  build_gather(p, g, true);
+  return launch_gather_tail(p, (hipStream_t)stream);
 }

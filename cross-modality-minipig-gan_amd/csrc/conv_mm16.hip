@@ -22,15 +22,9 @@ static int launch_mm16_variant(const GatherConv& p, long maxM, hipStream_t st) {
   constexpr int fold_b = KS > 1 ? TM * TN * 16 * 256 * 4 : 0;          // in-block split-K: the groups' sums through LDS
   constexpr int epi_b = CONV_EPI_FLOATS * 4;
   constexpr int smem = loop_b > fold_b ? (loop_b > epi_b ? loop_b : epi_b) : (fold_b > epi_b ? fold_b : epi_b);
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (e != hipSuccess) {
-      set_error("gather_conv_pipe (bf16 operands): hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return MPGAN_ERR_HIP;
-    }
-    attr_set = true;
-  }
+  if (const int rc = raise_lds_limit<gather_conv_pipe_kernel<BN, TM, TN, WN, WRAPS, PRO, false, KS, true>>(
+          smem, "gather_conv_pipe (bf16 operands)"))
+    return rc;
   GatherConv q = p;
   const long pairs = set_tile_grid(q, BM);
   q.ntiles = (p.Cout + BN - 1) / BN;
@@ -42,13 +36,14 @@ static int launch_mm16_variant(const GatherConv& p, long maxM, hipStream_t st) {
 }
 
 template <int WRAPS, int PRO>
-static int launch_mm16_bn(const GatherConv& p, int variant, bool ksplit2, long maxM, hipStream_t st) {
-  if constexpr (WRAPS == 1) {
-    if (ksplit2 && variant == 64) return launch_mm16_variant<64, 1, 2, 1, 1, PRO, 2>(p, maxM, st);
-    if (ksplit2 && variant == 32) return launch_mm16_variant<32, 1, 1, 1, 1, PRO, 2>(p, maxM, st);
+static int launch_mm16_bn(const GatherConv& p, int bn, int ks, long maxM, hipStream_t st) {
+  if constexpr (WRAPS == 1) {   // (KS = 2 exists for one wrap and the 64 / 32 tiles: choose_gather asks for no other)
+    if (ks == 2)
+      return bn == 64 ? launch_mm16_variant<64, 1, 2, 1, 1, PRO, 2>(p, maxM, st)
+                      : launch_mm16_variant<32, 1, 1, 1, 1, PRO, 2>(p, maxM, st);
   }
-  if (variant == 128) return launch_mm16_variant<128, 2, 2, 2, WRAPS, PRO, 1>(p, maxM, st);
-  if (variant == 64) return launch_mm16_variant<64, 1, 2, 1, WRAPS, PRO, 1>(p, maxM, st);
+  if (bn == 128) return launch_mm16_variant<128, 2, 2, 2, WRAPS, PRO, 1>(p, maxM, st);
+  if (bn == 64) return launch_mm16_variant<64, 1, 2, 1, WRAPS, PRO, 1>(p, maxM, st);
   return launch_mm16_variant<32, 1, 1, 1, WRAPS, PRO, 1>(p, maxM, st);
 }
 
@@ -60,11 +55,10 @@ bool mm16_gather_ok(const GatherConv& p) {
          !p.stats_acc && p.ksplit <= 1 && !p.in_bf16 && !p.out_bf16;
 }
 
-// The instance of an Mm16 choice (choose_gather, conv_igemm.hip): channel tile bn, WRAPS, PRO 0 / 1, in-block split-K ks.
+// The instance an Mm16 choice names (choose_gather, conv_igemm.hip): BN, WRAPS, PRO 0 / 1 and KS as given.
 int launch_gather_mm16(const GatherConv& p, int bn, int wraps, int pro, int ks, long maxM, hipStream_t st) {
-  if (wraps == 1)
-    return pro ? launch_mm16_bn<1, 1>(p, bn, ks == 2, maxM, st) : launch_mm16_bn<1, 0>(p, bn, ks == 2, maxM, st);
-  return pro ? launch_mm16_bn<2, 1>(p, bn, false, maxM, st) : launch_mm16_bn<2, 0>(p, bn, false, maxM, st);
+  if (wraps == 1) return pro ? launch_mm16_bn<1, 1>(p, bn, ks, maxM, st) : launch_mm16_bn<1, 0>(p, bn, ks, maxM, st);
+  return pro ? launch_mm16_bn<2, 1>(p, bn, ks, maxM, st) : launch_mm16_bn<2, 0>(p, bn, ks, maxM, st);
 }
 
 // ---- weight gradient -----------------------------------------------------------------------------------------------
@@ -72,15 +66,8 @@ template <int BD, int BG, int TM, int TN, int WN, int PRO, bool PAD>
 static int launch_wgrad_mm16_variant(const WgradParams& p, hipStream_t st) {
   auto kern = wgrad_pipe_kernel<BD, BG, TM, TN, WN, PRO, PAD, true>;
   constexpr int smem = 2 * WBK * (BD + BG) * (int)sizeof(float) + 2 * 32 * 16;   // + the row tables
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (e != hipSuccess) {
-      set_error("wgrad_pipe (bf16 operands): hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return MPGAN_ERR_HIP;
-    }
-    attr_set = true;
-  }
+  if (const int rc = raise_lds_limit<wgrad_pipe_kernel<BD, BG, TM, TN, WN, PRO, PAD, true>>(smem, "wgrad_pipe (bf16 operands)"))
+    return rc;
   dim3 grid((unsigned)p.tiles_c * p.tiles_d * p.nsplit);
   hipLaunchKernelGGL(kern, grid, dim3(256), smem, st, p);
   return check_launch("wgrad_pipe (bf16 operands)");

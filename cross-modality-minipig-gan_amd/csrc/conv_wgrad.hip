@@ -1016,18 +1016,13 @@ static int launch_wgrad_p2(const WgradParams& p, const WP2Plan& pl, hipStream_t 
   const WP2Grid tg{pl.tiles_y, pl.tiles_x, pl.ntiles};
   auto k1 = wgrad_patch2d_kernel<CD, CG, S, TX, true>;
   auto k0 = wgrad_patch2d_kernel<CD, CG, S, TX, false>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(k1), hipFuncAttributeMaxDynamicSharedMemorySize, K::SMEM);
-    hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(k0), hipFuncAttributeMaxDynamicSharedMemorySize, K::SMEM);
-    if (e1 != hipSuccess || e0 != hipSuccess) {
-      set_error("wgrad_patch2d: hipFuncSetAttribute: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e0));
-      return MPGAN_ERR_HIP;
-    }
-    attr_set = true;
+  if (p.pro.scale) {
+    if (const int rc = raise_lds_limit<wgrad_patch2d_kernel<CD, CG, S, TX, true>>(K::SMEM, "wgrad_patch2d")) return rc;
+    hipLaunchKernelGGL(k1, dim3(pl.blocks), dim3(256), K::SMEM, st, p, tg);
+  } else {
+    if (const int rc = raise_lds_limit<wgrad_patch2d_kernel<CD, CG, S, TX, false>>(K::SMEM, "wgrad_patch2d")) return rc;
+    hipLaunchKernelGGL(k0, dim3(pl.blocks), dim3(256), K::SMEM, st, p, tg);
   }
-  if (p.pro.scale) hipLaunchKernelGGL(k1, dim3(pl.blocks), dim3(256), K::SMEM, st, p, tg);
-  else hipLaunchKernelGGL(k0, dim3(pl.blocks), dim3(256), K::SMEM, st, p, tg);
   return check_launch("wgrad_patch2d");
 }
 
@@ -1254,15 +1249,7 @@ static WgradChoice choose_wgrad(const mpgan_conv_geom* g, const WgradParams& p, 
 template <int BD, int BG, int TM, int TN, int WN, int KW, bool SD, bool SG>
 static int launch_wgrad_variant(const WgradParams& p, const WgradChoice& c, hipStream_t st) {
   auto kern = wgrad_kernel<BD, BG, TM, TN, WN, KW, SD, SG>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, c.smem);
-    if (e != hipSuccess) {
-      set_error("wgrad: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return MPGAN_ERR_HIP;
-    }
-    attr_set = true;
-  }
+  if (const int rc = raise_lds_limit<wgrad_kernel<BD, BG, TM, TN, WN, KW, SD, SG>>(c.smem, "wgrad")) return rc;
   hipLaunchKernelGGL(kern, dim3(c.grid), dim3(256), c.smem, st, p);
   return check_launch("wgrad");
 }
@@ -1270,15 +1257,7 @@ static int launch_wgrad_variant(const WgradParams& p, const WgradChoice& c, hipS
 template <int BD, int BG, int TM, int TN, int WN, int PRO, bool PAD>
 static int launch_wgrad_pipe_variant(const WgradParams& p, const WgradChoice& c, hipStream_t st) {
   auto kern = wgrad_pipe_kernel<BD, BG, TM, TN, WN, PRO, PAD>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, c.smem);
-    if (e != hipSuccess) {
-      set_error("wgrad_pipe: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return MPGAN_ERR_HIP;
-    }
-    attr_set = true;
-  }
+  if (const int rc = raise_lds_limit<wgrad_pipe_kernel<BD, BG, TM, TN, WN, PRO, PAD>>(c.smem, "wgrad_pipe")) return rc;
   hipLaunchKernelGGL(kern, dim3(c.grid), dim3(256), c.smem, st, p);
   return check_launch("wgrad_pipe");
 }
@@ -1348,13 +1327,7 @@ static int launch_chosen(const WgradChoice& c, WgradParams p, float* dw, float* 
       break;
     case WForm::Thin:
       if (c.smem > 64 * 1024) {   // (the bf16-dy 3x3x3 instance only, see choose_wgrad)
-        static bool attr_set = false;
-        if (!attr_set) {
-          hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_thin_kernel<4, 27, true>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-          if (e != hipSuccess) { set_error("wgrad_thin: hipFuncSetAttribute: %s", hipGetErrorString(e)); return MPGAN_ERR_HIP; }
-          attr_set = true;
-        }
+        if (const int r = raise_lds_limit<wgrad_thin_kernel<4, 27, true>>(150 * 1024, "wgrad_thin")) return r;
       }
       if (c.bf16) launch_wgrad_thin<4, true>(p, c, st);
       else if (c.v == 4) launch_wgrad_thin<4, false>(p, c, st);

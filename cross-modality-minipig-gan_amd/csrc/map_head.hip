@@ -337,15 +337,6 @@ static void mh_chunks(const MapGeom& g, int* chunks, int* rows_per_chunk) {
   *chunks = (rows + *rows_per_chunk - 1) / *rows_per_chunk;
 }
 
-static int mh_lds_attr(const void* kern, const char* what) {
-  hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, MH_LDS_BYTES);
-  if (e != hipSuccess) {
-    set_error("%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e));
-    return MPGAN_ERR_HIP;
-  }
-  return MPGAN_OK;
-}
-
 static int mh_strip_grid(int items, int smem) {
   const int per_cu = smem > 40960 ? 2 : (smem > 20480 ? 4 : 8);   // 160 KiB of LDS per CU, at most 32 waves
   const int blocks = (items + 3) / 4, cap = 256 * per_cu;
@@ -359,11 +350,7 @@ extern "C" int mpgan_maphead_forward(const float* z, const mpgan_prologue* p, in
   MapGeom g;
   if (int rc = mh_geom("maphead_forward", n, in_dhw, c, k_dhw, &g)) return rc;
   MPGAN_UNSUPPORTED(!al16(z) || !al16(w_perm), "maphead_forward: needs 16-B aligned z and w_perm");
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (int rc = mh_lds_attr(reinterpret_cast<const void*>(maphead_forward_kernel), "maphead_forward")) return rc;
-    attr_set = true;
-  }
+  if (const int rc = raise_lds_limit<maphead_forward_kernel>(MH_LDS_BYTES, "maphead_forward")) return rc;
   const int xstrips = (g.OW + MH_STRIP - 1) / MH_STRIP;
   const int items = g.n * g.OD * g.OH * xstrips;
   const int smem = g.taps * g.C * 4;
@@ -399,11 +386,7 @@ extern "C" int mpgan_maphead_backward(const float* z, const mpgan_prologue* p, i
   }
   hipStream_t s = (hipStream_t)stream;
   if (g_a) {
-    static bool attr_set = false;
-    if (!attr_set) {
-      if (int rc = mh_lds_attr(reinterpret_cast<const void*>(maphead_bwd_data_kernel), "maphead_backward")) return rc;
-      attr_set = true;
-    }
+    if (const int rc = raise_lds_limit<maphead_bwd_data_kernel>(MH_LDS_BYTES, "maphead_backward")) return rc;
     const int xstrips = (g.W + MH_STRIP - 1) / MH_STRIP;
     const int items = g.n * g.D * g.H * xstrips;
     const int smem = g.taps * g.C * 4;

@@ -84,6 +84,22 @@ inline int check_launch(const char* what) {
   return MPGAN_OK;
 }
 
+// The one-time preamble of a launcher whose instance KERN may need more dynamic LDS than the default limit: raised
+// once per instantiation.
+template <auto KERN>
+inline int raise_lds_limit(int smem, const char* name) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    if (e != hipSuccess) {
+      set_error("%s: hipFuncSetAttribute(%d): %s", name, smem, hipGetErrorString(e));
+      return MPGAN_ERR_HIP;
+    }
+    attr_set = true;
+  }
+  return MPGAN_OK;
+}
+
 // Device view of the optional normalise+activate prologue.
 struct Pro {
   const float* scale;

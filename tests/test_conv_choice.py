@@ -176,3 +176,35 @@ def test_wgrad_labels_name_library_kernels():
                 assert name.startswith("wgrad") and name in kernels and name.endswith(", true>"), (g, name)
     assert seen == {"wgrad_patch3d_c16_kernel", "wgrad_patch2d_kernel", "wgrad_thin_rows_kernel", "wgrad_thin_kernel",
                     "wgrad_pipe_kernel", "wgrad_kernel"}, seen
+
+
+def _fp32_sweep():
+    for sp in [(40, 36), (130, 126), (13, 21), (18, 17, 19), (34, 33, 32)]:
+        for cin, cout, (k, s, p), tr, mm, mb in itertools.product(
+                (1, 16, 32, 64, 128, 192), (1, 8, 16, 24, 32, 64, 128),
+                [(1, 1, 0), (3, 1, 1), (3, 1, 0), (3, 2, 1), (4, 2, 1), (2, 1, 0)], (False, True), (False, True), (0, 1)):
+            # a transposed k3 s2 layer doubles its extent: output padding 1 in every dimension it strides
+            op = ((1, 1, 1) if len(sp) == 3 else (0, 1, 1)) if tr and (k, s) == (3, 2) else (0, 0, 0)
+            g = _g(2, sp, cin, cout, k, s, p, transposed=tr, out_pad=op, mm_bf16=mm, min_blocks=mb)
+            if min(g.out_dhw) >= 1:
+                yield g
+
+
+def test_fp32_labels_name_library_kernels():
+    # every label the fp32 gather choice prints is an instance the library holds, whatever the form
+    from mpgan_amd import _lib
+    nm = shutil.which("nm") or shutil.which("llvm-nm")
+    assert nm, "no nm on PATH"
+    out = subprocess.run([nm, "-C", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    kernels = set(re.findall(r"void mpgan::(\w+(?:<[^()]*>)?)\(mpgan::GatherConv", out))
+    seen, labels = set(), set()
+    for g in _fp32_sweep():
+        gc = g.c()
+        for pro_code, bwd in itertools.product((0, 1, 2, 3), (0, 1)):
+            labels.add(engine.kernel_label(lib().mpgan_conv_kernel_name, C.byref(gc), bwd, pro_code))
+    for name in labels:
+        assert name in kernels, name
+        seen.add(name.split("_kernel")[0])
+    assert seen == {"thin_cin1", "thin_cin1_full", "thin_cin1_rows", "thin_cout1", "thin_c1c1_rows4", "convt_quad_cout1",
+                    "convt_oct_cout1", "gather_patch", "gather_patch_persist", "gather_patch3d_c16", "gather_conv_pipe",
+                    "gather_conv_dma", "gather_conv"}, seen

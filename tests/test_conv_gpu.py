@@ -271,7 +271,15 @@ PATCH_CASES = [
     (32, 24, 1, 1, 0, (9, 17), False),      # 1x1, Cout not a power of two
     (64, 16, 3, 2, 1, (13, 9), True),       # transposed: 4 phases, odd extents
     (32, 8, 3, 2, 1, (8, 16), True),
+    (32, 8, 3, 2, 1, (13, 21), False),      # 17 x 33-pixel patch: too large for the persistent form's register round
+    (16, 24, 3, 2, 1, (7, 11), True),       # wide body of the one-tile kernel (prologue), persistent merged form (none)
 ]
+# the instances the last two rows are there for: (with prologue, without, mirrored backward-data)
+PATCH_LABELS = {
+    PATCH_CASES[-2]: ("gather_patch_kernel<32, 1, true, false>", "gather_patch_kernel<32, 0, true, false>", None),
+    PATCH_CASES[-1]: ("gather_patch_kernel<16, 1, false, false>", "gather_patch_persist_kernel<16, 0, false, true>",
+                      "gather_patch_persist_kernel<16, 0, false, true>"),
+}
 
 
 @pytest.mark.parametrize("case", PATCH_CASES, ids=lambda c: "{}to{}_k{}s{}p{}_{}".format(c[0], c[1], c[2], c[3], c[4], "T" if c[6] else "F"))
@@ -302,6 +310,10 @@ def test_patch_kernel_forward_stats_prologue_and_dgrad(case):
     assert lib().mpgan_conv_variant(ctypes.byref(gc), 0, 1) == 16, "expected the patch kernel for this geometry"
     assert lib().mpgan_conv_variant(ctypes.byref(gc), 0, 0) == (17 if tr else 16)     # merged phases without a prologue
     wp = ops.pack_weight(w.cuda(), transposed=tr)
+    if case in PATCH_LABELS:
+        from mpgan_amd import engine
+        assert engine.gather_kernel_name(g, False, True) == PATCH_LABELS[case][0]         # (1)
+        assert engine.gather_kernel_name(g, False, False) == PATCH_LABELS[case][1]        # (2), (2b)
 
     # (1) prologue + fused statistics
     y_ref = conv(a)
@@ -349,6 +361,8 @@ def test_patch_kernel_forward_stats_prologue_and_dgrad(case):
         F.conv2d(xf, wf, None, stride=s, padding=p).backward(gy)
         gfc = gf.c()
         assert lib().mpgan_conv_variant(ctypes.byref(gfc), 1, 0) == 17      # all phases in one block
+        if case in PATCH_LABELS:
+            assert engine.gather_kernel_name(gf, True, False) == PATCH_LABELS[case][2]
         dx = torch.full((n, *gf.in_dhw, cout), float("nan"), device="cuda")
         ops.conv_backward_data(gf, to_cl(gy), ops.pack_weight(wf.cuda(), for_dgrad=True), dx)
         assert_close(from_cl(dx, 2), xf.grad, what="patch dgrad (strided conv)")
