@@ -167,6 +167,16 @@ SIGNATURES = {
     "mpgan_norm_bwd_apply_bf16_peer": (_I, [_P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, C.POINTER(PeerTapsBF16C), _F,
                                             _L, _I, _P, _I, _P, _P]),
     "mpgan_tap_l1_bf16": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _F, _L, _I, _P, _P, _P]),
+    # conditional discriminator: the first conv over two 1-channel input planes
+    "mpgan_conv2p_stats_rows": (_I, [_G, _I]),
+    "mpgan_conv2p_kernel_name": (_I, [_G, _I, C.c_char_p, _I]),
+    "mpgan_conv2p_forward": (_I, [_G, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "mpgan_conv2p_forward_act": (_I, [_G, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "mpgan_conv2p_forward_f32_to_bf16": (_I, [_G, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "mpgan_conv2p_forward_act_f32_to_bf16": (_I, [_G, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "mpgan_conv2p_wgrad_workspace": (_L, [_G]),
+    "mpgan_conv2p_wgrad_kernel_name": (_I, [_G, _I, C.c_char_p, _I]),
+    "mpgan_conv2p_backward_weight": (_I, [_G, _P, _P, _P, _I, _I, _P, _P, _F, _P, _L, _P]),
     # sliding-window inference (inference.py)
     "mpgan_sw_gather": (_I, [_SW, _P, _I, _I, _I, _F, _P, _P]),
     "mpgan_sw_count": (_I, [_SW, _P, _P, _P]),

@@ -85,6 +85,8 @@ struct GatherConv {
   Phase ph[MAX_PHASES];
   int tile_start[MAX_PHASES + 1];   // packed: first (phase, m-tile) pair = statistics row of phase i; past nphase = INT_MAX
   int group_start[9];               // packed: first tile of work group k (one eighth of EVERY phase), see decode_block
+  const float* in2;                 // two-plane form (mpgan_conv2p_*, Cin == 2): the second input channel as a 1-channel tensor of
+                                    // its own, `in` being the first; null everywhere else (last: no other field moves)
 };
 
 // `row`: index of the block's (phase, m-tile) pair = its row of fused statistics / norm-backward partial sums.

@@ -1208,6 +1208,112 @@ static bool thin_cin1_rows_ok(const GatherConv& p) {
          p.Ho == ph.My && p.Do == ph.Mz;
 }
 
+// Two-plane form of the row walker: 2 -> 64 channels (the conditional discriminator's conv1, D(cat(image, condition))),
+// the two input channels being two SEPARATE 1-channel tensors, p.in (plane 0, the image) and p.in2 (plane 1, the
+// condition): no concatenated tensor exists.  Same walk, grid, re-anchored last group and statistics rows as
+// thin_cin1_rows_kernel; a lane holds the 2 T weights of its channel as T (plane 0, plane 1) pairs -- the generic
+// [Cout][tap][Cin = 2] pack read as 8-byte pairs -- both planes' 6-wide windows are wave-uniform loads, and a product
+// pair accumulates into a pair (two FMAs per instruction where the compiler packs them), the halves added once per
+// pixel, whose 64 channels are stored once.  The epilogue activation exists in both instances.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+// (The walk is a function of its own for its __restrict__ arguments: with them the planes' loads stay wave-uniform scalar
+// loads across the fp32 instance's stores, which the same pointers read out of the argument struct do not.)
+template <int T, bool OUT_BF16>
+__device__ __forceinline__ void thin_cin2_rows_walk(const GatherConv& p, const float* __restrict__ in0,
+                                                    const float* __restrict__ in1, float* __restrict__ outf) {
+  __shared__ float red[4][128];
+  constexpr int KZ = T == 27 ? 3 : 1;
+  const Phase& ph = p.ph[0];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  const int rows = p.N * ph.Mz * ph.My, Mx = ph.Mx;
+  const int nwaves = (int)gridDim.x * 4, ngroups = (Mx + 3) >> 2;
+  f32x2 w[T];
+#pragma unroll
+  for (int t = 0; t < T; ++t) w[t] = *reinterpret_cast<const f32x2*>(p.wp + ((long)lane * T + t) * 2);
+  const float bv = p.bias ? p.bias[lane] : 0.f;
+  const bool act = p.epi.scale != nullptr;               // eval mode: lane = channel
+  const float esc = act ? p.epi.scale[lane] : 1.f, esh = act ? p.epi.shift[lane] : 0.f, esl = act ? p.epi.slope[lane] : 1.f;
+  float s1 = 0.f, s2 = 0.f;
+  for (int r = (int)blockIdx.x * 4 + wave; r < rows; r += nwaves) {
+    const int my = r % ph.My, q = r / ph.My;
+    const int mz = q % ph.Mz, n = q / ph.Mz;
+    const long ioff = (((long)n * p.Di + mz) * p.Hi + my) * p.Wi;
+    const float* __restrict__ g0 = in0 + ioff;
+    const float* __restrict__ g1 = in1 + ioff;
+    const long orow = (long)r * Mx;
+    for (int gi = 0; gi < ngroups; ++gi) {
+      const int x0 = gi + 1 < ngroups ? 4 * gi : Mx - 4;
+      const int first = 4 * gi - x0;
+      f32x2 o[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[j] = f32x2{bv, 0.f};
+#pragma unroll
+      for (int kz = 0; kz < KZ; ++kz)
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky) {
+          const long so = ((long)kz * p.Hi + ky) * p.Wi + x0;                       // wave-uniform: scalar loads
+          const float* __restrict__ src0 = g0 + so;
+          const float* __restrict__ src1 = g1 + so;
+          f32x2 win[6];
+#pragma unroll
+          for (int i = 0; i < 6; ++i) win[i] = f32x2{src0[i], src1[i]};
+#pragma unroll
+          for (int kx = 0; kx < 3; ++kx)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = __builtin_elementwise_fma(w[(kz * 3 + ky) * 3 + kx], win[j + kx], o[j]);
+        }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float oj = o[j].x + o[j].y;
+        const long e = (orow + x0 + j) * p.ldo + lane;
+        const float st = act ? epi_act1(oj, esc, esh, esl) : oj;
+        if constexpr (OUT_BF16) reinterpret_cast<__bf16*>(outf)[e] = (__bf16)st;
+        else outf[e] = st;
+        const float v = j >= first ? oj : 0.f;
+        s1 += v;
+        s2 = fmaf(v, v, s2);
+      }
+    }
+  }
+  if (p.stats) {
+    red[wave][lane] = s1;
+    red[wave][64 + lane] = s2;
+    __syncthreads();
+    if (threadIdx.x < 128)
+      p.stats[(long)blockIdx.x * 128 + threadIdx.x] =
+          (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+  }
+}
+
+template <int T, bool OUT_BF16>
+__global__ __launch_bounds__(256) void thin_cin2_rows_kernel(const GatherConv p) {
+  thin_cin2_rows_walk<T, OUT_BF16>(p, p.in, p.in2, p.out);
+}
+
+// What the two-plane row walker needs of the geometry and the operands (the first unmet condition's message, or null).
+static const char* thin_cin2_rows_refusal(const GatherConv& p) {
+  const int T = p.Kz * p.Ky * p.Kx;
+  const Phase& ph = p.ph[0];
+  if (!(p.Cin == 2 && p.Cout == 64 && p.nphase == 1 && (T == 9 || T == 27) && p.Kx == 3 && p.Ky == 3 && p.Kz == (T == 27 ? 3 : 1)))
+    return "two-plane conv: a ConvNd 2 -> 64 with a 3x3 or 3x3x3 kernel only";
+  if (!(ph.nx == 3 && ph.ny == 3 && ph.nz == p.Kz && ph.dx0 == 0 && ph.dy0 == 0 && ph.dz0 == 0 && ph.kx0 == 0 && ph.ky0 == 0 &&
+        ph.kz0 == 0 && p.dstep[0] == 1 && p.dstep[1] == 1 && p.dstep[2] == 1 && p.kstep[0] == 1 && p.kstep[1] == 1 &&
+        p.kstep[2] == 1 && p.istride[0] == 1 && p.istride[1] == 1 && p.istride[2] == 1 && p.ostride[0] == 1 &&
+        p.ostride[1] == 1 && p.ostride[2] == 1 && ph.oz == 0 && ph.oy == 0 && ph.ox == 0 && p.Wi == ph.Mx + 2 &&
+        p.Hi == ph.My + 2 && p.Di == ph.Mz + (T == 27 ? 2 : 0) && p.Wo == ph.Mx && p.Ho == ph.My && p.Do == ph.Mz))
+    return "two-plane conv: stride 1 and no padding only";
+  if (ph.Mx < 4) return "two-plane conv: at least 4 output columns (input width >= 6)";
+  if (p.pro.scale || p.resid || p.tanh_out || p.stats_acc || p.in_bf16 || p.fold.acc || p.bwd.part || p.ksplit > 1)
+    return "two-plane conv: a plain forward (no prologue, residual, tanh, accumulator statistics or split-K)";
+  if (reinterpret_cast<uintptr_t>(p.wp) & 7) return "two-plane conv: the packed weight must be 8-byte aligned";
+  if (p.stats && !p.out_bf16)
+    return "two-plane conv (fp32 out): no fused statistics, as the one-plane 1 -> 64 layer (mpgan_conv2p_stats_rows() == 0): "
+           "use mpgan_channel_stats";
+  if (p.epi.scale && p.stats) return "two-plane conv: the epilogue activation goes without fused statistics";
+  return nullptr;
+}
+
 // ---------------------------------------------------------------------------
 // Patch kernel: 2-D layers with <= 32 output channels and 16/32/64 gathered channels
 // (the U-Net's stride-1 units, its stride-2 down convs up to 32 channels, the transposed
@@ -1258,6 +1364,7 @@ enum class GForm {
   ThinBf16In,        // thin_cout1_kernel<LANES, true>
   C1C1Rows4,         // thin_c1c1_rows4_kernel<REVX>
   Cin1Rows,          // thin_cin1_rows_kernel<T, false>
+  Cin2Rows,          // thin_cin2_rows_kernel<T, OUT_BF16>         (two input planes: mpgan_conv2p_forward*)
   Cin1Full,          // thin_cin1_full_kernel<CQ>
   Cin1,              // thin_cin1_kernel<V>
   ConvtQuad,         // convt_quad_cout1_kernel<LANES>
@@ -1284,6 +1391,7 @@ struct GatherChoice {
   int pro;           // PRO of the K-stepped and patch forms, HAS_PRO of Patch3d
   int bn, wraps, ks; // K-stepped forms: channel tile BN (it fixes TM, TN, WN: bn_tile), WRAPS, in-block split-K KS
   bool fast, scalar; // Pipe: FAST; Kstep: SCALAR
+  bool out_bf16;     // Cin2Rows: OUT_BF16
   int cin;           // Patch / PatchPersist: CIN, NARROW, MERGE
   bool narrow, merge;
   PatchLaunch pl;    // Patch / PatchPersist: the plan, its LDS bytes; PatchPersist: tiles and grid
@@ -2749,6 +2857,16 @@ static GatherChoice choose_thin(const GatherConv& p, long maxM, GatherChoice c) 
 static GatherChoice choose_gather(const GatherConv& p, long maxM) {
   GatherChoice c{};
   c.rc = MPGAN_OK;
+  if (p.in2) {          // two input planes (the conditional D.conv1): the row walker's two-plane form or nothing
+    const char* why = thin_cin2_rows_refusal(p);
+    CHOICE_REFUSE(why != nullptr, why);
+    c.form = GForm::Cin2Rows;
+    c.code = 1;
+    c.arg = p.Kz * p.Ky * p.Kx;
+    c.out_bf16 = p.out_bf16 != 0;
+    c.rows = p.out_bf16 ? (int)((maxM + 255) / 256) : 0;   // one statistics row per block, where today's conv1 leaves them
+    return c;
+  }
   if (p.out_bf16 || p.in_bf16) return choose_thin(p, maxM, c);
   const int variant = select_variant(p, maxM, thin_cin1_ok(p), thin_cout1_ok(p));
   c.code = c.bn = variant;
@@ -2872,6 +2990,12 @@ static int launch_chosen(const GatherConv& p, const GatherChoice& c, long maxM, 
       else hipLaunchKernelGGL((thin_cin1_rows_kernel<27, false>), block_grid, dim3(256), 0, st, p);
       return check_launch(bf ? "thin_cin1_rows_bf16" : "thin_cin1_rows");
     }
+    case GForm::Cin2Rows:
+      if (c.out_bf16 && c.arg == 9) hipLaunchKernelGGL((thin_cin2_rows_kernel<9, true>), block_grid, dim3(256), 0, st, p);
+      else if (c.out_bf16) hipLaunchKernelGGL((thin_cin2_rows_kernel<27, true>), block_grid, dim3(256), 0, st, p);
+      else if (c.arg == 9) hipLaunchKernelGGL((thin_cin2_rows_kernel<9, false>), block_grid, dim3(256), 0, st, p);
+      else hipLaunchKernelGGL((thin_cin2_rows_kernel<27, false>), block_grid, dim3(256), 0, st, p);
+      return check_launch("thin_cin2_rows");
     case GForm::ThinBf16OutFull: {
       const size_t smem = ((size_t)((T * p.Cout + 3) & ~3) + (p.stats ? 256 * (size_t)(p.Cout + 1) : 0)) * sizeof(float);
       if (c.arg == 4) hipLaunchKernelGGL((thin_cin1_full_kernel<4, true>), block_grid, dim3(256), smem, st, p);
@@ -2985,6 +3109,7 @@ static int gather_kernel_name(const GatherChoice& c, char* buf, int len) {
   switch (c.form) {
     case GForm::ThinBf16OutRows: return snprintf(buf, len, "thin_cin1_rows_kernel<%d, true>", c.arg);
     case GForm::Cin1Rows: return snprintf(buf, len, "thin_cin1_rows_kernel<%d, false>", c.arg);
+    case GForm::Cin2Rows: return snprintf(buf, len, "thin_cin2_rows_kernel<%d, %s>", c.arg, b[c.out_bf16]);
     case GForm::ThinBf16OutFull: return snprintf(buf, len, "thin_cin1_full_kernel<%d, true>", c.arg);
     case GForm::Cin1Full: return snprintf(buf, len, "thin_cin1_full_kernel<%d, false>", c.arg);
     case GForm::ThinBf16InMfma: return snprintf(buf, len, "thin_cout1_mfma_bf16_kernel");
@@ -3356,4 +3481,92 @@ extern "C" int mpgan_conv_backward_data_bf16_to_f32(const mpgan_conv_geom* g, co
   p.in_bf16 = 1;
   build_gather(p, g, true);
   return launch_gather_tail(p, (hipStream_t)stream);
+}
+
+
+// ---- two input planes (the conditional discriminator's conv1: D(cat(image, condition)), Conv(2 -> 64, 3, stride 1)) ----
+// x_img and x_cond are the two input channels as two dense 1-channel tensors (N, D, H, W); w_packed is the generic
+// [Cout][tap][Cin = 2] pack, plane 0 the image.  One body for the four entries: scale == null is the raw forward.
+static int conv2p_forward(const char* who, const mpgan_conv_geom* g, const float* x_img, const float* x_cond,
+                          const float* w_packed, const float* bias, const float* scale, const float* shift,
+                          const float* slope, bool act, float* stats_partials, void* y, int32_t ldy, bool out_bf16,
+                          void* stream) {
+  int rc = check_geom(g);
+  if (rc) return rc;
+  MPGAN_CHECK_ARG(x_img && x_cond && w_packed && y && (!act || (scale && shift && slope)), "%s: null pointer", who);
+  MPGAN_CHECK_ARG(ldy >= g->cout, "%s: bad pitch", who);
+  MPGAN_CHECK_ARG(!(act && stats_partials), "%s: the epilogue activation goes without fused statistics (they describe the "
+                                            "raw conv output)", who);
+  MPGAN_UNSUPPORTED(g->cin != 2 || g->transposed, "%s: ConvNd with two input channels only", who);
+  GatherConv p{};
+  p.in = x_img; p.in2 = x_cond; p.wp = w_packed; p.out = static_cast<float*>(y); p.bias = act ? nullptr : bias;
+  p.pro = make_pro(nullptr);
+  p.fold = make_fold(nullptr);
+  if (act) { p.epi.scale = scale; p.epi.shift = shift; p.epi.slope = slope; }
+  p.ldi = 1; p.ldo = ldy;
+  p.out_bf16 = out_bf16;
+  p.stats = stats_partials;
+  build_gather(p, g, false);
+  return launch_gather_tail(p, (hipStream_t)stream);
+}
+
+extern "C" int mpgan_conv2p_forward(const mpgan_conv_geom* g, const float* x_img, const float* x_cond,
+                                    const float* w_packed, const float* bias, float* stats_partials, float* y,
+                                    int32_t ldy, void* stream) {
+  return conv2p_forward("conv2p_forward", g, x_img, x_cond, w_packed, bias, nullptr, nullptr, nullptr, false,
+                        stats_partials, y, ldy, false, stream);
+}
+
+extern "C" int mpgan_conv2p_forward_act(const mpgan_conv_geom* g, const float* x_img, const float* x_cond,
+                                        const float* w_packed, const float* scale, const float* shift,
+                                        const float* slope, float* y, int32_t ldy, void* stream) {
+  return conv2p_forward("conv2p_forward_act", g, x_img, x_cond, w_packed, nullptr, scale, shift, slope, true, nullptr, y,
+                        ldy, false, stream);
+}
+
+extern "C" int mpgan_conv2p_forward_f32_to_bf16(const mpgan_conv_geom* g, const float* x_img, const float* x_cond,
+                                                const float* w_packed, const float* bias, float* stats_partials,
+                                                void* y, int32_t ldy, void* stream) {
+  return conv2p_forward("conv2p_forward_f32_to_bf16", g, x_img, x_cond, w_packed, bias, nullptr, nullptr, nullptr, false,
+                        stats_partials, y, ldy, true, stream);
+}
+
+extern "C" int mpgan_conv2p_forward_act_f32_to_bf16(const mpgan_conv_geom* g, const float* x_img, const float* x_cond,
+                                                    const float* w_packed, const float* scale, const float* shift,
+                                                    const float* slope, float* stats_partials, void* y, int32_t ldy,
+                                                    void* stream) {
+  return conv2p_forward("conv2p_forward_act_f32_to_bf16", g, x_img, x_cond, w_packed, nullptr, scale, shift, slope, true,
+                        stats_partials, y, ldy, true, stream);
+}
+
+// The stand-in of those launches for the geometry queries (standin_conv with a second plane).
+static GatherConv standin_conv2p(const mpgan_conv_geom* g, bool out_bf16) {
+  GatherConv p = standin_conv(g, false, 0);
+  p.in2 = g_standin;
+  p.ldi = 1;
+  p.out_bf16 = out_bf16;
+  return p;
+}
+
+extern "C" int32_t mpgan_conv2p_stats_rows(const mpgan_conv_geom* g, int32_t out_bf16) {
+  if (check_geom(g) || g->cin != 2 || g->transposed) return 0;
+  GatherConv p = standin_conv2p(g, out_bf16 != 0);
+  p.stats = g_standin;
+  const GatherChoice c = choose_standin(p);
+  return c.rc == MPGAN_OK ? c.rows : 0;
+}
+
+extern "C" int mpgan_conv2p_kernel_name(const mpgan_conv_geom* g, int32_t out_bf16, char* buf, int32_t len) {
+  int rc = check_geom(g);
+  if (rc) return rc;
+  MPGAN_CHECK_ARG(buf && len > 0, "conv2p_kernel_name: no buffer");
+  MPGAN_UNSUPPORTED(g->cin != 2 || g->transposed, "conv2p_kernel_name: ConvNd with two input channels only");
+  const GatherChoice c = choose_standin(standin_conv2p(g, out_bf16 != 0));
+  if (c.rc != MPGAN_OK) {
+    set_error("%s", c.msg);
+    return c.rc;
+  }
+  const int n = gather_kernel_name(c, buf, len);
+  MPGAN_CHECK_ARG(n < len, "conv2p_kernel_name: the name needs %d bytes", n + 1);
+  return MPGAN_OK;
 }

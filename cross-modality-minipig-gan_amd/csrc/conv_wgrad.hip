@@ -585,6 +585,89 @@ static bool thin_rows_ok(const WgradParams& p, int T) {
          p.Gx == p.Mx + 2 && p.Gy == p.My + 2 && p.Gz == p.Mz + (T == 27 ? 2 : 0);
 }
 
+// Two-plane form of the row walker, for the 2 -> 64 conv whose input channels are two separate 1-channel tensors
+// (p.gath: plane 0, p.gath2: plane 1; the conditional discriminator's conv1).  ONE pass over dy, the large operand:
+// a lane keeps the 2 T sums of its channel as T (plane 0, plane 1) pairs -- 54 accumulator registers at T = 27, one
+// channel per thread, so the kernel stays below 128 VGPRs (four waves per SIMD) -- and a product pair takes both
+// planes' wave-uniform samples.  The slab is [64][T][2], which the slab reducer turns into torch layout (64, 2, k...);
+// the four waves' sums leave through LDS one plane at a time (the rows' 28 KiB at T = 27 instead of 56).
+// ---------------------------------------------------------------------------
+typedef float wf32x2 __attribute__((ext_vector_type(2)));
+template <int T, bool DENSE_BF16>
+__global__ __launch_bounds__(256) void wgrad_thin2_rows_kernel(const WgradParams p) {
+  __shared__ float red[4][64 * T + 64];
+  constexpr int KZ = T == 27 ? 3 : 1;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  const int rows = p.N * p.Mz * p.My;
+  const int nwaves = (int)gridDim.x * 4;
+  const int Mx = p.Mx, ngroups = (Mx + 3) >> 2;
+  wf32x2 acc[T];
+  float bsum = 0.f;
+#pragma unroll
+  for (int t = 0; t < T; ++t) acc[t] = wf32x2{0.f, 0.f};
+  for (int r = (int)blockIdx.x * 4 + wave; r < rows; r += nwaves) {
+    const int my = r % p.My, q = r / p.My;
+    const int mz = q % p.Mz, n = q / p.Mz;
+    const long drow = (long)r * Mx;                                        // first pixel of the dense row
+    const long goff = (((long)n * p.Gz + mz) * p.Gy + my) * p.Gx;
+    const float* __restrict__ g0 = p.gath + goff;
+    const float* __restrict__ g1 = p.gath2 + goff;
+    for (int gi = 0; gi < ngroups; ++gi) {
+      const int x0 = gi + 1 < ngroups ? 4 * gi : Mx - 4;
+      const int first = 4 * gi - x0;                                       // pixels j < first were counted by the previous group
+      wf32x2 d[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const long e = (drow + x0 + j) * p.ldd + lane;
+        float v;
+        if constexpr (DENSE_BF16) v = (float)reinterpret_cast<const __bf16*>(p.dense)[e];
+        else v = p.dense[e];
+        v = j >= first ? v : 0.f;
+        d[j] = wf32x2{v, v};
+        bsum += v;
+      }
+#pragma unroll
+      for (int kz = 0; kz < KZ; ++kz)
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky) {
+          const long wo = ((long)kz * p.Gy + ky) * p.Gx + x0;                        // wave-uniform: scalar loads
+          const float* __restrict__ w0 = g0 + wo;
+          const float* __restrict__ w1 = g1 + wo;
+          wf32x2 win[6];
+#pragma unroll
+          for (int i = 0; i < 6; ++i) win[i] = wf32x2{w0[i], w1[i]};
+#pragma unroll
+          for (int kx = 0; kx < 3; ++kx)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              acc[(kz * 3 + ky) * 3 + kx] = __builtin_elementwise_fma(d[j], win[j + kx], acc[(kz * 3 + ky) * 3 + kx]);
+        }
+    }
+  }
+  float* out = p.partial + (long)blockIdx.x * 64 * T * 2;
+#pragma unroll
+  for (int pl = 0; pl < 2; ++pl) {
+    if (pl) __syncthreads();                                               // plane 0's rows have been read
+#pragma unroll
+    for (int t = 0; t < T; ++t) red[wave][lane * T + t] = acc[t][pl];
+    if (pl == 0) red[wave][64 * T + lane] = bsum;
+    __syncthreads();
+    for (int i = threadIdx.x; i < 64 * T + (pl == 0 ? 64 : 0); i += 256) {
+      const float s = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
+      if (i < 64 * T) out[2 * i + pl] = s;                                 // [c][t][plane]
+      else if (p.bias_partial) p.bias_partial[(long)blockIdx.x * 64 + (i - 64 * T)] = s;
+    }
+  }
+}
+
+// The geometry wgrad_thin2_rows_kernel walks (a 2 -> 64 pad-free stride-1 3x3 / 3x3x3 conv over two 1-channel planes).
+static bool thin2_rows_ok(const WgradParams& p, int T) {
+  return p.Cd == 64 && p.Cg == 2 && p.ldg == 1 && !p.pro.scale && (T == 9 || T == 27) && p.Kx == 3 && p.Ky == 3 &&
+         p.Kz == (T == 27 ? 3 : 1) && p.sz == 1 && p.sy == 1 && p.sx == 1 && p.pz == 0 && p.py == 0 && p.px == 0 && p.Mx >= 4 &&
+         p.Gx == p.Mx + 2 && p.Gy == p.My + 2 && p.Gz == p.Mz + (T == 27 ? 2 : 0);
+}
+
 // ---------------------------------------------------------------------------
 // Weight gradient of the 16 -> 16 3x3x3 stride-1 conv (the 3-D U-Net's 64^3 level; conv_igemm.hip's
 // gather_patch3d_c16_kernel serves its forward and backward-data): dW[co][tap][ci] = sum_px dy[px][co] * a[px + tap][ci].
@@ -1123,7 +1206,8 @@ enum class WForm {
   Patch2d,    // wgrad_patch2d_kernel<CD, CG, S, TX, HAS_PRO>
   ThinRows,   // wgrad_thin_rows_kernel<T, DENSE_BF16>
   Thin,       // wgrad_thin_kernel<V, T, DENSE_BF16>
-  Mm16,       // wgrad_pipe_kernel<BD, BG, TM, TN, WN, PRO, PAD, true>   (conv_mm16.hip)
+  Thin2Rows,  // wgrad_thin2_rows_kernel<T, DENSE_BF16>                     (two gathered planes: mpgan_conv2p_backward_weight)
+  Mm16,      // wgrad_pipe_kernel<BD, BG, TM, TN, WN, PRO, PAD, true>   (conv_mm16.hip)
   Pipe,       // wgrad_pipe_kernel<BD, BG, TM, TN, WN, PRO, PAD>
   Generic,    // wgrad_kernel<BD, BG, TM, TN, WN, KW, SCALAR_D, SCALAR_G>
 };
@@ -1171,6 +1255,21 @@ static WgradChoice choose_wgrad(const mpgan_conv_geom* g, const WgradParams& p, 
   const int Cd = p.Cd, Cg = p.Cg, T = p.Kz * p.Ky * p.Kx;
   const long M = (long)p.N * p.Mz * p.My * p.Mx;
   const bool pro = p.pro.scale != nullptr;
+  if (p.gath2) {   // two gathered planes (the conditional D.conv1): the row walker's two-plane form or nothing
+    CHOICE_REFUSE(!thin2_rows_ok(p, T), "conv2p_backward_weight: a pad-free stride-1 ConvNd 2 -> 64 with a 3x3 or 3x3x3 kernel "
+                                        "and at least 4 output columns only");
+    CHOICE_REFUSE(bf16_dy && (reinterpret_cast<uintptr_t>(p.dense) & 1), "conv2p_backward_weight: misaligned bf16 dy");
+    c.form = WForm::Thin2Rows;
+    c.t = T;
+    c.bf16 = bf16_dy;
+    // the row walk of plan_thin_wgrad's blocks: about 1024 pixels each, at most 1024 slabs for the reducer
+    long blocks = (M + 1023) / 1024;
+    blocks = blocks > 1024 ? 1024 : (blocks < 1 ? 1 : blocks);
+    c.grid = c.slabs = c.bias_slabs = (int)blocks;
+    c.ws = slab_bytes(c.slabs, c.bias_slabs, Cd, T * Cg);
+    c.narrow = !bf16_dy && (long)Cd * Cg * T <= 32L * 512 && c.slabs >= 64;
+    return c;
+  }
   // the thin kernels unroll 1, 3x3 and 3x3x3 taps only; a bf16 dy has the thin form alone (3-D 1 -> 64: 112 KiB of
   // lane rows, one block per CU)
   const bool kshape = T == 1 || (T == 9 && p.Kz == 1 && p.Ky == 3 && p.Kx == 3) || (T == 27 && p.Kz == 3 && p.Ky == 3 && p.Kx == 3);
@@ -1325,8 +1424,15 @@ static int launch_chosen(const WgradChoice& c, WgradParams p, float* dw, float* 
       else hipLaunchKernelGGL((wgrad_thin_rows_kernel<27, false>), dim3(c.grid), dim3(256), 0, st, p);
       rc = check_launch("wgrad_thin_rows");
       break;
+    case WForm::Thin2Rows:
+      if (c.bf16 && c.t == 9) hipLaunchKernelGGL((wgrad_thin2_rows_kernel<9, true>), dim3(c.grid), dim3(256), 0, st, p);
+      else if (c.bf16) hipLaunchKernelGGL((wgrad_thin2_rows_kernel<27, true>), dim3(c.grid), dim3(256), 0, st, p);
+      else if (c.t == 9) hipLaunchKernelGGL((wgrad_thin2_rows_kernel<9, false>), dim3(c.grid), dim3(256), 0, st, p);
+      else hipLaunchKernelGGL((wgrad_thin2_rows_kernel<27, false>), dim3(c.grid), dim3(256), 0, st, p);
+      rc = check_launch("wgrad_thin2_rows");
+      break;
     case WForm::Thin:
-      if (c.smem > 64 * 1024) {   // (the bf16-dy 3x3x3 instance only, see choose_wgrad)
+      if (c.smem > 64 * 1024) {  // (the bf16-dy 3x3x3 instance only, see choose_wgrad)
         if (const int r = raise_lds_limit<wgrad_thin_kernel<4, 27, true>>(150 * 1024, "wgrad_thin")) return r;
       }
       if (c.bf16) launch_wgrad_thin<4, true>(p, c, st);
@@ -1372,6 +1478,7 @@ static int wgrad_kernel_name(const WgradChoice& c, char* buf, int len) {
       return snprintf(buf, len, "wgrad_patch2d_kernel<%d, %d, %d, %d, %s>", c.p2.Cd, c.p2.Cg, c.p2.S, c.p2.tx, b[c.pro != 0]);
     case WForm::ThinRows: return snprintf(buf, len, "wgrad_thin_rows_kernel<%d, %s>", c.t, b[c.bf16]);
     case WForm::Thin: return snprintf(buf, len, "wgrad_thin_kernel<%d, %d, %s>", c.v, c.t, b[c.bf16]);
+    case WForm::Thin2Rows: return snprintf(buf, len, "wgrad_thin2_rows_kernel<%d, %s>", c.t, b[c.bf16]);
     case WForm::Mm16:
     case WForm::Pipe:
       return snprintf(buf, len, "wgrad_pipe_kernel<%d, %d, %d, %d, %d, %d, %s, %s>", c.bd, c.bg, w.tm, w.tn, w.wn, c.pro,
@@ -1530,5 +1637,58 @@ extern "C" int mpgan_conv_backward_weight_bf16dy(const mpgan_conv_geom* g, const
     return c.rc;
   }
   MPGAN_CHECK_ARG(workspace_bytes >= c.ws, "conv_backward_weight_bf16dy: workspace too small");
+  return launch_chosen(c, p, dw, dbias, beta, (hipStream_t)stream);
+}
+
+// ---- two input planes (the conditional discriminator's conv1, Conv(2 -> 64, 3, stride 1) on two 1-channel tensors) ----
+static WgradParams wgrad_params_2p(const mpgan_conv_geom* g, const float* x_img, const float* x_cond, const void* dy,
+                                   int32_t lddy, void* workspace, bool bf16_dy) {
+  WgradParams p = wgrad_params(g, x_img, 1, nullptr, dy, lddy, workspace, bf16_dy);
+  p.gath2 = x_cond;
+  return p;
+}
+
+static WgradChoice choose_standin_2p(const mpgan_conv_geom* g, bool bf16_dy) {
+  return choose_wgrad(g, wgrad_params_2p(g, w_standin, w_standin, w_standin, g->cout, w_standin, bf16_dy), bf16_dy);
+}
+
+extern "C" int64_t mpgan_conv2p_wgrad_workspace(const mpgan_conv_geom* g) {
+  if (!g || g->transposed || g->cin != 2) return -1;
+  const WgradChoice c = choose_standin_2p(g, false);   // (the slabs do not depend on dy's type)
+  return c.rc == MPGAN_OK ? c.ws : -1;
+}
+
+extern "C" int mpgan_conv2p_wgrad_kernel_name(const mpgan_conv_geom* g, int32_t bf16_dy, char* buf, int32_t len) {
+  MPGAN_CHECK_ARG(g && buf && len > 0, "conv2p_wgrad_kernel_name: no geometry / buffer");
+  MPGAN_UNSUPPORTED(g->transposed || g->cin != 2, "conv2p_wgrad_kernel_name: ConvNd with two input channels only");
+  const WgradChoice c = choose_standin_2p(g, bf16_dy != 0);
+  if (c.rc != MPGAN_OK) {
+    set_error("%s", c.msg);
+    return c.rc;
+  }
+  const int n = wgrad_kernel_name(c, buf, len);
+  MPGAN_CHECK_ARG(n < len, "conv2p_wgrad_kernel_name: the name needs %d bytes", n + 1);
+  return MPGAN_OK;
+}
+
+extern "C" int mpgan_conv2p_backward_weight(const mpgan_conv_geom* g, const float* x_img, const float* x_cond,
+                                            const void* dy, int32_t lddy, int32_t dy_bf16, float* dw, float* dbias,
+                                            float beta, void* workspace, int64_t workspace_bytes, void* stream) {
+  MPGAN_CHECK_ARG(g && x_img && x_cond && dy && dw && workspace, "conv2p_backward_weight: null pointer");
+  MPGAN_UNSUPPORTED(g->transposed || g->cin != 2, "conv2p_backward_weight: ConvNd with two input channels only");
+  MPGAN_CHECK_ARG(lddy >= g->cout, "conv2p_backward_weight: bad pitch");
+  int Cd, Cg, T;
+  long M;
+  wgrad_dims(g, Cd, Cg, T, M);
+  MPGAN_CHECK_ARG(M < (1L << 31) - 64 && (long)g->n * g->in_dhw[0] * g->in_dhw[1] * g->in_dhw[2] < (1L << 31),
+                  "conv2p_backward_weight: more than 2^31 pixels");
+  const WgradParams p = wgrad_params_2p(g, x_img, x_cond, dy, lddy, workspace, dy_bf16 != 0);
+  const WgradChoice c = choose_wgrad(g, p, dy_bf16 != 0);
+  if (c.rc != MPGAN_OK) {
+    set_error("%s", c.msg);
+    return c.rc;
+  }
+  MPGAN_CHECK_ARG(workspace_bytes >= c.ws, "conv2p_backward_weight: workspace %lld < %lld bytes",
+                  (long long)workspace_bytes, (long long)c.ws);
   return launch_chosen(c, p, dw, dbias, beta, (hipStream_t)stream);
 }

@@ -243,11 +243,15 @@ __global__ __launch_bounds__(256) void pack_weights_kernel(const float* __restri
   const long so = e[0], dof = e[1];
   const int Cout = (int)e[2], Cin = (int)e[3], T = (int)e[4];
   const int transposed = (int)e[5], dgrad = (int)e[6];
-  const long total = (long)Cout * Cin * T;
+  const long total = dgrad == 3 ? (long)Cout * T : (long)Cout * Cin * T;
   const long stride = (long)gridDim.x * blockDim.x;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
     int co, ci, t;
-    if (dgrad == 0) {  // dst [co][t][ci]
+    if (dgrad == 3) {  // dst [t][co] of input channel 0 ALONE: the backward-data pack of a conv's first input plane
+      co = (int)(i % Cout);
+      t = (int)(i / Cout);
+      ci = 0;
+    } else if (dgrad == 0) {  // dst [co][t][ci]
       ci = (int)(i % Cin);
       long q = i / Cin;
       t = (int)(q % T);

@@ -26,6 +26,8 @@ struct WgradParams {
   int fold_rounds; // thin kernel only: rounds of its lane-row fold (0 / 1: one)
   int tiles_c, tiles_d;  // 1-D launch of tiles_c*tiles_d*nsplit blocks, XCD-remapped, column tile fastest
   FastDiv fMx, fMy, fMz;
+  const float* gath2;  // two-plane thin kernel only (mpgan_conv2p_backward_weight): the second gathered channel as a 1-channel
+                       // tensor of its own, `gath` being the first; null everywhere else (last: no other field moves)
 };
 
 struct WBlockId { int tc, td, split; };

@@ -295,7 +295,7 @@ def _p(t):
 # --------------------------------------------------------------------------
 class ConvRec:
     """One conv / transposed conv / linear-as-conv weight in the flat store."""
-    __slots__ = ("mod", "transposed", "cout", "cin", "taps", "w_off", "fwd_off", "bwd_off", "tco", "tco_off")
+    __slots__ = ("mod", "transposed", "cout", "cin", "taps", "w_off", "fwd_off", "bwd_off", "tco", "tco_off", "plane0_bwd")
 
 
 class FusedRec:
@@ -394,11 +394,24 @@ class ParamStore:
             raise RuntimeError("ParamStore: conv registered after plans were built")
         r = ConvRec()
         r.mod, r.transposed, r.cout, r.cin, r.taps = mod, transposed, cout, cin, taps
-        r.tco, r.tco_off = tco, -1
+        r.tco, r.tco_off, r.plane0_bwd = tco, -1, False
         self.convs.append(r)
         self._by_mod[id(mod)] = r
         if self.flat is not None:
             self._build_pack_table()
+        return r
+
+    def pack_plane0_bwd(self, mod):
+        """The backward-data pack of this registered ConvNd holds input channel 0 alone, [tap][cout] (layout 3 of
+        mpgan_pack_weights): the conditional discriminator's first conv, whose second input plane is data."""
+        r = self._by_mod[id(mod)]
+        if r.plane0_bwd:
+            return r
+        if self.frozen:
+            raise RuntimeError("ParamStore: pack layout changed after plans were built")
+        assert not r.transposed
+        r.plane0_bwd = True
+        self._build_pack_table()
         return r
 
     def register_fused(self, conv_a, conv_b) -> FusedRec:
@@ -436,7 +449,7 @@ class ParamStore:
             r.bwd_off = off
             off += (n + 3) // 4 * 4
             rows.append([r.w_off, r.fwd_off, r.cout, r.cin, r.taps, int(r.transposed), 0, 0])
-            rows.append([r.w_off, r.bwd_off, r.cout, r.cin, r.taps, int(r.transposed), 1, 0])
+            rows.append([r.w_off, r.bwd_off, r.cout, r.cin, r.taps, int(r.transposed), 3 if r.plane0_bwd else 1, 0])
             if r.tco:
                 r.tco_off = off
                 off += (n + 3) // 4 * 4
@@ -1010,6 +1023,68 @@ def emit_conv_dgrad_bf16(prog, g: ConvGeom, dy, wp_bwd, dx, stats=None) -> int:
     return rows
 
 
+# ---- the conditional discriminator's first conv: two 1-channel input planes (image, condition), mpgan_conv2p_* ----
+def _conv2p_tag(name: str, g: ConvGeom, dense):
+    """Probe tag of a two-plane launch: both fp32 planes read once, the 64-channel tensor read or written once."""
+    return (name, 2.0 * conv_macs(g), 4 * g.n * math.prod(g.in_dhw) * 2 + dense.numel() * dense.element_size())
+
+
+def _check_conv2p(g: ConvGeom, x, cond, dense, what: str):
+    if cond is None or tuple(cond.shape) != tuple(x.shape) or tuple(x.shape) != (g.n, *g.in_dhw, 1):
+        raise ValueError(f"{what}: the image and the condition must both be {(g.n, *g.in_dhw, 1)}")
+    if tuple(dense.shape) != (g.n, *g.out_dhw, g.cout):
+        raise ValueError(f"{what}: output shape {tuple(dense.shape)} != {(g.n, *g.out_dhw, g.cout)}")
+
+
+def emit_conv2p_fwd(prog, g: ConvGeom, x, cond, wp, bias, z, stats=None) -> int:
+    """Raw output z (fp32 or bf16, as `z` is) of the two-plane conv; `stats`: the partials that receive the fused
+    statistics rows (bf16 z only).  Returns the rows written (0: none, run a statistics pass)."""
+    _check_conv2p(g, x, cond, z, "plan conv2p_forward")
+    bf = z.dtype == torch.bfloat16
+    rows = ops.conv2p_stats_rows(g, bf) if stats is not None else 0
+    name = "conv2p_forward_f32_to_bf16" if bf else "conv2p_forward"
+    gc = g.c()
+    prog.add(name, getattr(lib(), "mpgan_" + name), C.byref(gc), x.data_ptr(), cond.data_ptr(), wp.data_ptr(),
+             bias.data_ptr(), _p(stats) if rows else None, z.data_ptr(), g.cout, keep=(gc, x, cond, wp, bias, z, stats),
+             desc=_gdesc(g), tag=_conv2p_tag(ops.conv2p_kernel_name(g, bf), g, z))
+    return rows
+
+
+def emit_conv2p_fwd_act(prog, rows, g: ConvGeom, x, cond, wp, bias, y, norm_mod, act_mod):
+    """Eval mode: running-statistics BatchNorm + LeakyReLU in the two-plane conv's epilogue, the activated tensor stored
+    once as fp32 or bf16 (as `y` is); `rows`: see emit_conv_fwd_act."""
+    _check_conv2p(g, x, cond, y, "plan conv2p_forward_act")
+    vec = epi_row(rows, g.cout, bias, norm_mod, act_mod, x.device)
+    bf = y.dtype == torch.bfloat16
+    gc = g.c()
+    head = (C.byref(gc), x.data_ptr(), cond.data_ptr(), wp.data_ptr(), vec[0].data_ptr(), vec[1].data_ptr(), vec[2].data_ptr())
+    kw = dict(keep=(gc, x, cond, wp, bias, y, vec, norm_mod, act_mod), desc=_gdesc(g),
+              tag=_conv2p_tag(ops.conv2p_kernel_name(g, bf), g, y))
+    if bf:
+        prog.add("conv2p_forward_act_f32_to_bf16", lib().mpgan_conv2p_forward_act_f32_to_bf16, *head, None, y.data_ptr(),
+                 g.cout, **kw)
+    else:
+        prog.add("conv2p_forward_act", lib().mpgan_conv2p_forward_act, *head, y.data_ptr(), g.cout, **kw)
+
+
+def emit_conv2p_wgrad(prog, g: ConvGeom, x, cond, dy, dw, dbias, ws, lane=0):
+    """dW (64, 2, k...) += the weight gradient over both planes from one pass over dy (fp32 or bf16); dbias rides along."""
+    _check_conv2p(g, x, cond, dy, "plan conv2p_backward_weight")
+    bf = dy.dtype == torch.bfloat16
+    assert ws.numel() * 4 >= ops.conv2p_wgrad_workspace(g), "wgrad workspace too small"
+    gc = g.c()
+    prog.add("conv2p_backward_weight", lib().mpgan_conv2p_backward_weight, C.byref(gc), x.data_ptr(), cond.data_ptr(),
+             dy.data_ptr(), g.cout, int(bf), dw.data_ptr(), _p(dbias), 1.0, ws.data_ptr(), ws.numel() * 4,
+             keep=(gc, x, cond, dy, dw, dbias, ws), desc=_gdesc(g),
+             tag=_conv2p_tag(ops.conv2p_wgrad_kernel_name(g, bf), g, dy), lane=lane)
+
+
+def image_plane_geom(g: ConvGeom) -> ConvGeom:
+    """The two-plane conv seen from its image plane alone: what its backward-data runs as (a C -> 1 gather over the
+    layout-3 pack); the condition is data and gets no gradient."""
+    return dataclasses.replace(g, cin=1)
+
+
 def _t3(v, dims, fill):
     v = (v,) * dims if isinstance(v, int) else tuple(v)
     return (fill,) * (3 - dims) + tuple(v)
@@ -1062,15 +1137,18 @@ class Scratch:
         rows = max(ops.conv_stats_rows(g, code) for code in (0, 1, 2))
         self.partials_need = max(self.partials_need, (rows + 32) * 2 * g.cout)   # + finalize's fold scratch
 
-    def want_bf16_layer(self, g: ConvGeom, fused_rows=0):
+    def want_bf16_layer(self, g: ConvGeom, fused_rows=0, two_plane=False):
         """One conv -> BN layer in bf16 storage: the forward's statistics rows (+ finalize's fold scratch), the norm
         backward's [3][C] rows (`fused_rows`: those the next layer's backward-data launch leaves instead, if more) +
         one vector + the bias partials behind them (emit_norm_bwd_bf16), and the weight gradient's workspace."""
         c, rows = g.cout, _rows(g)
-        fwd_rows = (rows + 255) // 256 if g.cin == 1 else ops.conv_stats_rows_bf16(g)
+        if two_plane:                      # the two-plane first layer: fp32 planes in, its own rows and slabs
+            fwd_rows, ws = ops.conv2p_stats_rows(g, True), ops.conv2p_wgrad_workspace(g)
+        else:
+            fwd_rows = (rows + 255) // 256 if g.cin == 1 else ops.conv_stats_rows_bf16(g)
+            ws = ops.conv_wgrad_workspace_bf16dy(g) if g.cin == 1 else ops.conv_wgrad_workspace_bf16(g)
         bwd_rows = max(ops.norm_bwd_rows_bf16(rows, c), fused_rows)
         self.partials_need = max(self.partials_need, (fwd_rows + 32) * 2 * c, (bwd_rows * 4 + 1) * c)
-        ws = ops.conv_wgrad_workspace_bf16dy(g) if g.cin == 1 else ops.conv_wgrad_workspace_bf16(g)
         self.ws_need = max(self.ws_need, ws // 4)
 
     def alloc(self):
@@ -1575,7 +1653,8 @@ def plan_io(plan) -> IoSlots:
     io = getattr(plan, "io", None)
     if io is None:
         io = plan.io = IoSlots((plan.fwd, plan.bwd), x=plan.x_in, y=getattr(plan, "y", None),
-                               g_y=getattr(plan, "g_y", None), g_x=getattr(plan, "g_x", None))
+                               g_y=getattr(plan, "g_y", None), g_x=getattr(plan, "g_x", None),
+                               c=getattr(plan, "c_in", None))
     return io
 
 
@@ -1597,6 +1676,7 @@ class ConvStack:
 
     def __init__(self, disc, store: ParamStore, n: int, dhw, dims: int, *, raw_z: bool, what: str):
         dev, self.raw_z = store.flat.device, raw_z
+        self.cond = None                   # the plan's condition plane, set before emitting when geoms[0].cin == 2
         self.convs = [disc.model_conv[i] for i in (0, 3, 6, 9)]
         self.bns = [disc.model_conv[i] for i in (1, 4, 7, 10)]
         self.geoms, self.zs, self.nbs, self.recs = [], [], [], []
@@ -1610,6 +1690,13 @@ class ConvStack:
             self._alloc_layer(i, (n, *size, c), dev)
             self.nbs.append(NormBuf(n, c, False, dev))
             self.recs.append(store.register_conv(cv, cout=c, cin=cv.in_channels, taps=math.prod(cv.kernel_size)))
+        if self.two_plane:                 # backward-data of layer 0 reaches the image plane alone
+            store.pack_plane0_bwd(self.convs[0])
+
+    @property
+    def two_plane(self) -> bool:
+        """Layer 0 reads two 1-channel planes, the image and `cond` (the conditional discriminator)."""
+        return self.geoms[0].cin == 2
 
     def _alloc_layer(self, i, shape, dev):
         self.zs.append(torch.empty(shape, device=dev))
@@ -1617,8 +1704,11 @@ class ConvStack:
     def want_scratch(self, scratch: Scratch, fuse_stats: bool):
         """Statistics partials and weight-gradient workspace of a training plan; fuse_stats: also the rows a
         backward-data launch leaves for the norm backward of the layer in front (emit_conv_dgrad_stats)."""
-        for g in self.geoms:
+        for i, g in enumerate(self.geoms):
             scratch.want_partials(g.n, math.prod(g.out_dhw), g.cout)
+            if i == 0 and self.two_plane:      # its own weight-gradient slabs; statistics by the separate pass
+                scratch.ws_need = max(scratch.ws_need, ops.conv2p_wgrad_workspace(g) // 4)
+                continue
             scratch.want_ws(g)
             if fuse_stats and g.cin > 1:
                 scratch.partials_need = max(scratch.partials_need, ops.conv_bwd_stats_rows(g) * 3 * g.cin)
@@ -1634,7 +1724,10 @@ class ConvStack:
         dev = x.device
         leaky, rows, body = _ConstSlope(0.2, dev), [], Program()
         for i, cv in enumerate(self.convs):
-            emit_layer(body, rows, self.geoms[i], x, wp(i), cv.bias, outs[i], self.bns[i], leaky)
+            if i == 0 and self.two_plane:
+                emit_conv2p_fwd_act(body, rows, self.geoms[0], x, self.cond, wp(0), cv.bias, outs[0], self.bns[0], leaky)
+            else:
+                emit_layer(body, rows, self.geoms[i], x, wp(i), cv.bias, outs[i], self.bns[i], leaky)
             x = outs[i]
         emit_epi_vectors(prog, rows, dev)
         prog.extend(body)
@@ -1649,8 +1742,15 @@ class ConvStack:
             return self.zs[-1], None
         eval_norms, body, pro = [], Program(), None
         for i, cv in enumerate(self.convs):
-            emit_conv_fwd_norm(body, self.geoms[i], x, wp(i), cv.bias, self.zs[i], self.nbs[i], self.bns[i], partials,
-                               pro=pro, training=training, eval_norms=eval_norms)
+            if i == 0 and self.two_plane:      # as the one-plane conv1: no fused statistics in fp32, a statistics pass
+                emit_conv2p_fwd(body, self.geoms[0], x, self.cond, wp(0), cv.bias, self.zs[0])
+                if training:
+                    emit_norm_stats(body, self.zs[0], self.nbs[0], self.bns[0], partials)
+                else:
+                    eval_norms.append((self.bns[0], self.nbs[0], self.geoms[0].cout))
+            else:
+                emit_conv_fwd_norm(body, self.geoms[i], x, wp(i), cv.bias, self.zs[i], self.nbs[i], self.bns[i], partials,
+                                   pro=pro, training=training, eval_norms=eval_norms)
             x, pro = self.zs[i], _lrelu(self.nbs[i])
         emit_eval_norms(prog, eval_norms, x.device)
         prog.extend(body)
@@ -1680,7 +1780,9 @@ class ConvStack:
                 emit_norm_bwd(prog, gy, z, nb, nb.prologue(ACT_NONE), gy, partials, gv(bn.weight), gv(bn.bias), None)
                 add(g, gy)
                 add(g, gz)
-            if want_param_grads:
+            if want_param_grads and i == 0 and self.two_plane:
+                emit_conv2p_wgrad(prog, self.geoms[0], x, self.cond, g, gv(cv.weight), gv(cv.bias), ws, lane=wgrad_lane)
+            elif want_param_grads:
                 emit_conv_wgrad(prog, self.geoms[i], self.zs[i - 1] if i > 0 else x, g, gv(cv.weight), ws,
                                 pro=_lrelu(self.nbs[i - 1]) if i > 0 else None, dbias=gv(cv.bias), lane=wgrad_lane)
             if i > 0 and fuse_stats:
@@ -1688,8 +1790,8 @@ class ConvStack:
                                                 self.zs[i - 1], self.nbs[i - 1], 0.2, partials)
             elif i > 0:
                 emit_conv_dgrad(prog, self.geoms[i], g, store.wp_bwd(self.recs[i]), gas[i - 1])
-            elif g_x is not None:
-                emit_conv_dgrad(prog, self.geoms[0], g, store.wp_bwd(self.recs[0]), g_x)
+            elif g_x is not None:    # (two planes: the image plane's gradient alone, over the layout-3 pack)
+                emit_conv_dgrad(prog, image_plane_geom(self.geoms[0]), g, store.wp_bwd(self.recs[0]), g_x)
 
 
 class ConvStackBF16(ConvStack):
@@ -1713,7 +1815,8 @@ class ConvStackBF16(ConvStack):
     def want_scratch(self, scratch: Scratch, fuse_stats: bool):
         for i, g in enumerate(self.geoms):
             # (rows of the fused norm-backward sums the NEXT layer's backward-data launch leaves for this layer's norm)
-            scratch.want_bf16_layer(g, bwd_stats_rows_bf16(self.geoms[i + 1]) if fuse_stats and i < 3 else 0)
+            scratch.want_bf16_layer(g, bwd_stats_rows_bf16(self.geoms[i + 1]) if fuse_stats and i < 3 else 0,
+                                    two_plane=i == 0 and self.two_plane)
 
     def alloc_grads(self, disc):
         """(gas, dzs): the gradients w.r.t. the activations (bf16; fp32 for a_3, which the fp32 head writes) and the
@@ -1736,7 +1839,11 @@ class ConvStackBF16(ConvStack):
         if not training:
             emit_eval_norms(prog, [(bn, nb, g.cout) for bn, nb, g in zip(self.bns, self.nbs, self.geoms)], x.device)
         for i, cv in enumerate(self.convs):
-            rows = emit_conv_fwd_bf16(prog, self.geoms[i], x, wp(i), cv.bias, self.zs[i], partials if training else None)
+            if i == 0 and self.two_plane:
+                rows = emit_conv2p_fwd(prog, self.geoms[0], x, self.cond, wp(0), cv.bias, self.zs[0],
+                                       partials if training else None)
+            else:
+                rows = emit_conv_fwd_bf16(prog, self.geoms[i], x, wp(i), cv.bias, self.zs[i], partials if training else None)
             emit_norm_act_bf16(prog, self.zs[i], self.nbs[i], 0.2, self.acts[i], self.bns[i] if training else None,
                                partials, rows)
             x = self.acts[i]
@@ -1753,7 +1860,9 @@ class ConvStackBF16(ConvStack):
             bias_part = emit_norm_bwd_bf16(prog, gas[i], self.zs[i], self.nbs[i], 0.2, dz, partials, gv(bn.weight),
                                            gv(bn.bias), peer=peers[i] if peers is not None else None,
                                            reduced_rows=reduced, bias_part=want_param_grads and i > 0)
-            if want_param_grads:
+            if want_param_grads and i == 0 and self.two_plane:
+                emit_conv2p_wgrad(prog, self.geoms[0], x, self.cond, dz, gv(cv.weight), gv(cv.bias), ws)
+            elif want_param_grads:
                 emit_conv_wgrad_bf16(prog, self.geoms[i], self.acts[i - 1] if i > 0 else x, dz, gv(cv.weight),
                                      gv(cv.bias), ws, bias_part)
             if i > 0:
@@ -1761,7 +1870,7 @@ class ConvStackBF16(ConvStack):
                 reduced = emit_conv_dgrad_bf16(prog, self.geoms[i], dz, self.packs.bwd(self.recs[i]), gas[i - 1],
                                                stats=(self.zs[i - 1], self.nbs[i - 1], 0.2, partials) if fuse_stats else None)
             elif g_x is not None:
-                emit_conv_dgrad_bf16(prog, self.geoms[0], dz, store.wp_bwd(self.recs[0]), g_x)
+                emit_conv_dgrad_bf16(prog, image_plane_geom(self.geoms[0]), dz, store.wp_bwd(self.recs[0]), g_x)
 
 
 class LinearHead:
@@ -1928,6 +2037,8 @@ class _DiscPlanBase:
         self.dhw = _t3(spatial, self.dims, 1)
         self.x_in = torch.empty(n, *self.dhw, 1, device=store.flat.device)
         st = self.stack = self._make_stack(disc, f"{what} {spatial}", raw_z)
+        # the conditional discriminator: the condition plane, bound like x_in (IoSlots "c")
+        self.c_in = st.cond = torch.empty_like(self.x_in) if st.two_plane else None
         self.convs, self.bns, self.geoms, self.zs, self.nbs, self.recs = st.convs, st.bns, st.geoms, st.zs, st.nbs, st.recs
         return st
 

@@ -241,8 +241,10 @@ class FusedAdam(torch.optim.Optimizer):
 # --------------------------------------------------------------------------
 class _HParams(types.SimpleNamespace):
     """GAN.hparams.  `adv_loss` reads "bce" unless the constructor was given another objective, and only then is it an
-    entry of vars(hparams): a default GAN lists exactly the hyper-parameters it listed before the option existed."""
+    entry of vars(hparams): a default GAN lists exactly the hyper-parameters it listed before the option existed.
+    `conditional` likewise reads False unless the constructor was given True."""
     adv_loss = "bce"
+    conditional = False
 
 
 class GAN(nn.Module):
@@ -256,7 +258,8 @@ class GAN(nn.Module):
                  one_sided_label_value=0.9, *, dimensions: Optional[int] = None, norm: str = "batch",
                  n_unet_blocks: int = 6, unet_channels=(16, 32, 64, 128), unet_strides=(2, 2, 2), device="cuda",
                  storage_dtype: str = "f32", mi_weight: float = 0.0, mi_bins: int = 23,
-                 ssim_weight: float = 0.0, d_head: str = "linear", adv_loss: str = "bce", **kwargs):
+                 ssim_weight: float = 0.0, d_head: str = "linear", adv_loss: str = "bce", conditional: bool = False,
+                 **kwargs):
         super().__init__()
         if adv_loss not in ADV_LOSSES:
             raise ValueError(f"adv_loss must be one of {ADV_LOSSES}, got {adv_loss!r}")
@@ -270,6 +273,8 @@ class GAN(nn.Module):
                                 batch_size=batch_size, one_sided_label_value=one_sided_label_value, d_head=d_head)
         if adv_loss != _HParams.adv_loss:
             self.hparams.adv_loss = adv_loss
+        if conditional:
+            self.hparams.conditional = True
         data_shape = (channels, width, height) + ((depth,) if dimensions == 3 else ())
         # storage_dtype="bf16" is config C5: the discriminator stores its activations in bf16 and the generator's
         # matrix products take bf16 operands (fp32 storage: its launches are matrix-bound, not byte-bound)
@@ -277,10 +282,11 @@ class GAN(nn.Module):
                                          channels=unet_channels, strides=unet_strides, device=device,
                                          matmul_dtype="bf16" if storage_dtype == "bf16" else "f32")
         # adv_loss="bce" is the reference's objective on the Sigmoid's output; the other two are computed on the logits
-        # (their gradient does not vanish when the discriminator wins), which the discriminator then returns
+        # (their gradient does not vanish when the discriminator wins), which the discriminator then returns.
+        # conditional=True is pix2pix's discriminator: it judges the (T1, T2) PAIR, D(cat(t2w, t1w))
         self.discriminator = Discriminator(data_shape, dimensions=dimensions, device=device,
                                            storage_dtype=storage_dtype, head=d_head,
-                                           output="prob" if adv_loss == "bce" else "logit")
+                                           output="prob" if adv_loss == "bce" else "logit", conditional=conditional)
         # opt-in auxiliary generator loss (not in the reference's trainer): mi_weight * (-MI(G(t1w), t2w)) from Parzen
         # windows over the tanh output's range; with the default 0 no launch and no logged name is added
         self.mi_weight = float(mi_weight)
@@ -307,6 +313,12 @@ class GAN(nn.Module):
             return torch.full_like(validity, float(value))
         return torch.full((validity.shape[0], 1), float(value), device=validity.device, dtype=validity.dtype)
 
+    def _judge(self, images, t1w_images):
+        """The discriminator's verdict on `images`; a conditional one sees the T1 input they belong to beside them."""
+        if self.hparams.conditional:
+            return self.discriminator(images, t1w_images.detach())
+        return self.discriminator(images)
+
     def log(self, name, value, **kw):
         """Lightning's self.log: scalars stay on the device (no per-step sync)."""
         self.logged[name] = value.detach()
@@ -316,7 +328,7 @@ class GAN(nn.Module):
         if optimizer_idx == 0:                      # GAN_final.py:254-273
             generated_imgs = self(t1w_images)
             self.generated_imgs = generated_imgs
-            d_fake = self.discriminator(generated_imgs)
+            d_fake = self._judge(generated_imgs, t1w_images)
             g_adv_loss = self.adversarial_loss(d_fake, self._labels(d_fake, 1.0))
             self.log("g_adv_loss", g_adv_loss)
             g_recon_loss = self.reconstruction_loss(generated_imgs, t2w_images)
@@ -338,10 +350,10 @@ class GAN(nn.Module):
             #  -- 59.1 vs 58.6 ms at C3, 174.3 vs 175.8 ms at C5 -- while stretching D's kernels up to 3x, and its first
             #  use in a process once ended in a host SIGSEGV inside hipStreamWaitEvent on that stream: removed in
             #  round 4)
-            d_real = self.discriminator(t2w_images)
+            d_real = self._judge(t2w_images, t1w_images)
             real_loss = self.adversarial_loss(d_real, self._labels(d_real, self.hparams.one_sided_label_value))
             generated = self(t1w_images).detach()
-            d_fake = self.discriminator(generated)
+            d_fake = self._judge(generated, t1w_images)
             fake_loss = self.adversarial_loss(d_fake, self._labels(d_fake, 0.0))
             d_loss = scalar_axpby(real_loss, 0.5, fake_loss, 0.5)
             self.log("d_loss", d_loss)
@@ -357,7 +369,7 @@ class GAN(nn.Module):
         t1w_images, t2w_images = batch["t1w"], batch["t2w"]
         with torch.no_grad(), eval_modes(self.generator, self.discriminator):
             generated_imgs = self(t1w_images)
-            d_fake = self.discriminator(generated_imgs)
+            d_fake = self._judge(generated_imgs, t1w_images)
             g_adv_loss = self.adversarial_loss(d_fake, self._labels(d_fake, 1.0))
             g_recon_loss = self.reconstruction_loss(generated_imgs, t2w_images)
             g_loss = scalar_axpby(g_adv_loss, 1.0, g_recon_loss, 1.0)
@@ -367,7 +379,7 @@ class GAN(nn.Module):
             if self.ssim_loss is not None:
                 g_ssim_loss = self.ssim_loss(generated_imgs, t2w_images)
                 g_loss = scalar_axpby(g_loss, 1.0, g_ssim_loss, self.ssim_weight)
-            d_real = self.discriminator(t2w_images)
+            d_real = self._judge(t2w_images, t1w_images)
             real_loss = self.adversarial_loss(d_real, self._labels(d_real, self.hparams.one_sided_label_value))
             fake_loss = self.adversarial_loss(d_fake, self._labels(d_fake, 0.0))
             d_loss = scalar_axpby(real_loss, 0.5, fake_loss, 0.5)

@@ -282,15 +282,21 @@ class CasNetGenerator(_EngineModule):
         return _GenFn.apply(x.contiguous(), self._anchor, self)
 
 
+def _bind_cond(plan, io, cond):
+    """The condition plane of a conditional discriminator's pass, bound in place like the image (or staged)."""
+    if cond is not None and not io.bind("c", cond):
+        plan.c_in.view(-1).copy_(cond.reshape(-1))
+
+
 class _DiscFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, anchor, disc):
+    def forward(ctx, x, anchor, disc, cond=None):
         want_in, want_par = bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1])
         need_bwd = want_in or want_par
         spatial = _spatial(x, disc.dimensions)
         n = x.shape[0]
         store = disc.store
-        key = (n, spatial, need_bwd, want_in, want_par, disc.head, disc.output)
+        key = (n, spatial, need_bwd, want_in, want_par, disc.head, disc.output, disc.conditional)
         plan_cls = DiscPlanBF16 if disc.storage_dtype == "bf16" else DiscPlan
         plan = disc._acquire(key, lambda: plan_cls(disc, store, n, spatial, want_backward=need_bwd,
                                                    want_input_grad=want_in, want_param_grads=want_par))
@@ -298,6 +304,7 @@ class _DiscFn(torch.autograd.Function):
         io = plan_io(plan)
         if not io.bind("x", x):                  # (see _GenFn: the first conv reads the caller's tensor in place)
             plan.x_in.view(-1).copy_(x.reshape(-1))
+        _bind_cond(plan, io, cond)
         try:
             plan.fwd.run()
         finally:
@@ -307,7 +314,7 @@ class _DiscFn(torch.autograd.Function):
         if need_bwd:
             ctx.lease = lease
             ctx.shape = x.shape
-            ctx.save_for_backward(x)
+            ctx.save_for_backward(*((x,) if cond is None else (x, cond)))   # (the weight gradient reads both again)
             if want_par:
                 store.attach_grads()
         else:
@@ -331,7 +338,7 @@ class _DiscFn(torch.autograd.Function):
         if gx is not None and not direct:
             gx.view(-1).copy_(plan.g_x.view(-1))
         ctx.lease.release()
-        return gx, None, None
+        return gx, None, None, None
 
 
 def _validity(disc, plan):
@@ -339,14 +346,14 @@ def _validity(disc, plan):
     return plan.logit if disc.output == "logit" else plan.prob
 
 
-def _disc_eval(disc, x):
+def _disc_eval(disc, x, cond=None):
     """Eval-mode pass of variant A's discriminator: the forward-only plan keyed by the mode (engine.DiscPlan /
     DiscPlanBF16 with training=False), outside autograd."""
     with torch.no_grad():
         spatial = _spatial(x, disc.dimensions)
         n = x.shape[0]
         store = disc.store
-        key = ("eval", n, spatial, disc.storage_dtype, disc.head, disc.output)
+        key = ("eval", n, spatial, disc.storage_dtype, disc.head, disc.output, disc.conditional)
         plan_cls = DiscPlanBF16 if disc.storage_dtype == "bf16" else DiscPlan
         plan = disc._acquire(key, lambda: plan_cls(disc, store, n, spatial, want_backward=False, want_input_grad=False,
                                                    want_param_grads=False, training=False))
@@ -354,6 +361,7 @@ def _disc_eval(disc, x):
         io = plan_io(plan)
         if not io.bind("x", x):
             plan.x_in.view(-1).copy_(x.reshape(-1))
+        _bind_cond(plan, io, cond)
         try:
             plan.fwd.run()
             return _validity(disc, plan).view(disc.validity_shape(n, spatial)).clone()
@@ -389,10 +397,16 @@ class Discriminator(_EngineModule):
 
     output="logit": forward returns the logits, for an objective computed on them (gan.GAN(adv_loss="bce_logits" |
     "lsgan")).  The module tree and the state_dict keys are those of output="prob" -- the nn.Sigmoid stays where it is
-    and is not applied -- so the same checkpoints load; the plans launch no sigmoid and no sigmoid backward."""
+    and is not applied -- so the same checkpoints load; the plans launch no sigmoid and no sigmoid backward.
+
+    conditional=True: the pix2pix discriminator D(cat(img, cond)): `model_conv[0]` is Conv(2, 64, 3) and forward takes
+    the condition (the T1 volume the image belongs to) as a second tensor of img's shape.  The two are never
+    concatenated: the first conv reads them as two planes.  Input channel 0 is the image, so
+    weight[:, 0] is what an unconditional conv1 holds; the state_dict keys are unchanged.  The condition is data: it
+    gets no gradient and must not require one."""
 
     def __init__(self, img_shape, use_perceptual=True, *, dimensions=3, device=None, storage_dtype="f32",
-                 head="linear", output="prob"):
+                 head="linear", output="prob", conditional=False):
         super().__init__()
         if storage_dtype not in ("f32", "bf16"):
             raise ValueError(f"storage_dtype must be 'f32' or 'bf16', got {storage_dtype!r}")
@@ -402,13 +416,14 @@ class Discriminator(_EngineModule):
             raise ValueError(f"output must be 'prob' or 'logit', got {output!r}")
         self.head = head
         self.output = output
+        self.conditional = bool(conditional)
         self.use_perceptual = use_perceptual
         self.img_shape = img_shape
         self.dimensions = dimensions
         self.storage_dtype = storage_dtype      # activations / packed weights in HBM; parameters, statistics, Adam: fp32
         Cv, Bn = _CONV[dimensions], _BN[dimensions]
         self.model_conv = nn.Sequential(
-            Cv(1, 64, 3, 1), Bn(64), nn.LeakyReLU(0.2, inplace=True),
+            Cv(2 if conditional else 1, 64, 3, 1), Bn(64), nn.LeakyReLU(0.2, inplace=True),
             Cv(64, 128, 3, 1), Bn(128), nn.LeakyReLU(0.2, inplace=True),
             Cv(128, 256, 4, 2), Bn(256), nn.LeakyReLU(0.2, inplace=True),
             Cv(256, 256, 4, 2), Bn(256), nn.LeakyReLU(0.2, inplace=True))
@@ -438,15 +453,33 @@ class Discriminator(_EngineModule):
         (one channel: NC(D)HW is layout-identical to the plan's channels-last buffer)."""
         return (n, 1, *disc_map_size(spatial)) if self.head == "markovian" else (n, 1)
 
-    def forward(self, img):
+    def _check_cond(self, img, cond):
+        """forward's rules for the condition, checked before anything touches the device."""
+        if not self.conditional:
+            if cond is not None:
+                raise ValueError("this Discriminator is unconditional (conditional=False): forward takes the image alone")
+            return
+        if cond is None:
+            raise ValueError("a conditional Discriminator needs the condition: forward(img, cond)")
+        if tuple(cond.shape) != tuple(img.shape) or cond.dtype != img.dtype or cond.device != img.device:
+            raise ValueError(f"cond must match img: {tuple(img.shape)} {img.dtype} on {img.device}, got "
+                             f"{tuple(cond.shape)} {cond.dtype} on {cond.device}")
+        if cond.requires_grad:
+            raise ValueError("the condition is data: it gets no gradient here (pass cond.detach())")
+
+    def forward(self, img, cond=None):
         """Train mode: batch statistics + running-stat updates.  Eval mode (code/GAN/inferrence.py:109-110 puts the
         whole GAN into it): BatchNorm uses its running statistics, nothing of the module is written, and -- the
-        generator's eval rule -- no gradients are offered: the validity comes back detached."""
+        generator's eval rule -- no gradients are offered: the validity comes back detached.
+        cond: the condition of a conditional discriminator (required there, refused otherwise), of img's shape."""
+        self._check_cond(img, cond)
         store = self.store
+        if cond is not None:
+            cond = cond.contiguous()
         if not self.training:
-            return _disc_eval(self, img.detach().contiguous())
+            return _disc_eval(self, img.detach().contiguous(), cond)
         self._anchor.requires_grad_(torch.is_grad_enabled() and self._params_require_grad())
-        return _DiscFn.apply(img.contiguous(), self._anchor, self)
+        return _DiscFn.apply(img.contiguous(), self._anchor, self, cond)
 
 
 # --------------------------------------------------------------------------

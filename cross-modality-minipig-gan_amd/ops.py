@@ -959,3 +959,103 @@ def ssim_loss_backward(a, b, spatial, items, channels, lo, grad_mask, coef, upst
                                          upstream.data_ptr(), 0 if upstream.numel() == 1 else 1, float(scale), int(wrt),
                                          grad.data_ptr(), _stream()), "ssim_loss_backward")
     return grad
+
+
+# --------------------------------------------------------------------------
+# conditional discriminator: the first conv over two 1-channel input planes (include/mpgan_hip.h: mpgan_conv2p_*)
+# --------------------------------------------------------------------------
+def _check_planes(g: ConvGeom, x_img, x_cond, y, ydtype, what):
+    """The two input planes (dense fp32, n * prod(in_dhw) elements each, any shape) and the channels-last output."""
+    want = g.n * g.in_dhw[0] * g.in_dhw[1] * g.in_dhw[2]
+    for name, t in (("x_img", x_img), ("x_cond", x_cond)):
+        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() != want:
+            raise ValueError(f"{what}: {name} must be a contiguous CUDA fp32 plane of {want} elements, got "
+                             f"{tuple(t.shape)} {t.dtype} {t.device}")
+    if g.cin != 2:
+        raise ValueError(f"{what}: a geometry with two input channels, got cin = {g.cin}")
+    if tuple(y.shape) != (g.n, *g.out_dhw, g.cout):
+        raise ValueError(f"{what}: output shape {tuple(y.shape)} != {(g.n, *g.out_dhw, g.cout)}")
+    return _clx(y, ydtype, what + " y")[2]
+
+
+def conv2p_stats_rows(g: ConvGeom, out_bf16: bool) -> int:
+    gc = g.c()
+    return int(lib().mpgan_conv2p_stats_rows(C.byref(gc), int(out_bf16)))
+
+
+def conv2p_kernel_name(g: ConvGeom, out_bf16: bool) -> str:
+    gc = g.c()
+    buf = C.create_string_buffer(160)
+    check(lib().mpgan_conv2p_kernel_name(C.byref(gc), int(out_bf16), buf, len(buf)), "conv2p_kernel_name")
+    return buf.value.decode()
+
+
+def conv2p_forward(g: ConvGeom, x_img, x_cond, w_packed, bias, y, *, stats_partials=None):
+    """y = conv(cat(x_img, x_cond)) + bias; y fp32, or bf16 (then stats_partials may receive the fused statistics rows)."""
+    bf = y.dtype == BF16
+    what = "conv2p_forward_f32_to_bf16" if bf else "conv2p_forward"
+    ldy = _check_planes(g, x_img, x_cond, y, y.dtype, what)
+    if w_packed.numel() < g.cout * 2 * g.taps:
+        raise ValueError(f"{what}: packed weight too small")
+    if stats_partials is not None and stats_partials.numel() < conv2p_stats_rows(g, bf) * 2 * g.cout:
+        raise ValueError(f"{what}: stats_partials too small")
+    gc = g.c()
+    check(getattr(lib(), "mpgan_" + what)(C.byref(gc), x_img.data_ptr(), x_cond.data_ptr(), w_packed.data_ptr(), _ptr(bias),
+                                          _ptr(stats_partials), y.data_ptr(), ldy, _stream()), what)
+    return y
+
+
+def conv2p_forward_act(g: ConvGeom, x_img, x_cond, w_packed, scale, shift, slope, y):
+    """Eval mode: y = lrelu(conv(cat(x_img, x_cond)) * scale + shift, slope), stored once as fp32 or bf16 (y's dtype)."""
+    bf = y.dtype == BF16
+    what = "conv2p_forward_act_f32_to_bf16" if bf else "conv2p_forward_act"
+    ldy = _check_planes(g, x_img, x_cond, y, y.dtype, what)
+    _check_epi(g, scale, shift, slope, what)
+    gc = g.c()
+    args = (C.byref(gc), x_img.data_ptr(), x_cond.data_ptr(), w_packed.data_ptr(), scale.data_ptr(), shift.data_ptr(),
+            slope.data_ptr())
+    if bf:
+        check(lib().mpgan_conv2p_forward_act_f32_to_bf16(*args, None, y.data_ptr(), ldy, _stream()), what)
+    else:
+        check(lib().mpgan_conv2p_forward_act(*args, y.data_ptr(), ldy, _stream()), what)
+    return y
+
+
+def conv2p_wgrad_workspace(g: ConvGeom) -> int:
+    gc = g.c()
+    return int(lib().mpgan_conv2p_wgrad_workspace(C.byref(gc)))
+
+
+def conv2p_wgrad_kernel_name(g: ConvGeom, bf16_dy: bool) -> str:
+    gc = g.c()
+    buf = C.create_string_buffer(160)
+    check(lib().mpgan_conv2p_wgrad_kernel_name(C.byref(gc), int(bf16_dy), buf, len(buf)), "conv2p_wgrad_kernel_name")
+    return buf.value.decode()
+
+
+def conv2p_backward_weight(g: ConvGeom, x_img, x_cond, dy, dw, workspace, *, beta: float = 0.0, dbias=None):
+    """dw (64, 2, k...) = beta*dw + the weight gradient over both planes, dy fp32 or bf16; dbias rides along."""
+    what = "conv2p_backward_weight"
+    lddy = _check_planes(g, x_img, x_cond, dy, dy.dtype, what)
+    if dy.dtype not in (torch.float32, BF16):
+        raise ValueError(f"{what}: dy must be fp32 or bf16")
+    if dw.dtype != torch.float32 or dw.numel() != g.cout * 2 * g.taps or not dw.is_contiguous():
+        raise ValueError(f"{what}: dw must be the contiguous fp32 torch-layout weight gradient")
+    gc = g.c()
+    check(lib().mpgan_conv2p_backward_weight(C.byref(gc), x_img.data_ptr(), x_cond.data_ptr(), dy.data_ptr(), lddy,
+                                             int(dy.dtype == BF16), dw.data_ptr(), _ptr(dbias), float(beta),
+                                             workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+                                             _stream()), what)
+    return dw
+
+
+def pack_weight_plane0_bwd(w: torch.Tensor) -> torch.Tensor:
+    """Layout 3 of mpgan_pack_weights for ONE ConvNd weight: [tap][cout] of input channel 0 -- what backward-data of the
+    image plane of a two-plane conv consumes (with the geometry's cin set to 1)."""
+    w = w.contiguous()
+    cout, cin = w.shape[0], w.shape[1]
+    taps = w.numel() // (cin * cout)
+    table = torch.tensor([[0, 0, cout, cin, taps, 0, 3, 0]], dtype=torch.int64, device=w.device)
+    packed = torch.empty(cout * taps, dtype=torch.float32, device=w.device)
+    pack_weights(w, packed, table, 1, w.numel())
+    return packed

@@ -173,7 +173,9 @@ int mpgan_conv_wgrad_kernel_name(const mpgan_conv_geom* g, int32_t pro_code, int
  * table: device int64 [n_entries][8] = {src_off, dst_off, cout, cin, taps,
  * transposed, layout, 0}; offsets in floats into `flat_params` / `packed`;
  * layout 0 = [cout][tap][cin] (forward), 1 = [cin][tap][cout] (backward-data),
- * 2 = [tap][cin][cout] (backward-data of a Linear expressed as a whole-grid conv). */
+ * 2 = [tap][cin][cout] (backward-data of a Linear expressed as a whole-grid conv),
+ * 3 = [tap][cout] of input channel 0 alone, cout*taps floats (ConvNd only; fp32 pack only): the backward-data pack of
+ * the image plane of a two-plane conv, see mpgan_conv2p_forward. */
 int mpgan_pack_weights(const float* flat_params, float* packed, const int64_t* table,
                        int32_t n_entries, int64_t max_elems, void* stream);
 
@@ -721,6 +723,55 @@ int mpgan_norm_bwd_apply_bf16_peer(const void* g, int32_t g_f32, int32_t ldg, co
 int mpgan_tap_l1_bf16(const void* za, int32_t lda, const float* scale_a, const float* shift_a, const void* zb,
                       int32_t ldb, const float* scale_b, const float* shift_b, float slope, int64_t rows, int32_t c,
                       float* partials, float* out3, void* stream);
+
+/* ---- conditional (pix2pix) discriminator: the first conv over two input planes ----------------------------------
+ * D(cat(image, condition)): model_conv[0] is Conv(2, 64, 3, stride 1, no padding), and its two input channels are two
+ * SEPARATE dense 1-channel fp32 tensors (N, D, H, W), x_img (plane 0: the generated or real T2) and x_cond (plane 1:
+ * the T1 it belongs to); no concatenated or interleaved tensor is materialised.  g describes the ConvNd itself
+ * (cin == 2, cout == 64, 3x3 with depth 1 or 3x3x3, stride 1, pad 0, at least 4 output columns); every other geometry
+ * is MPGAN_ERR_UNSUPPORTED with a message, before any launch.  w_packed: layout 0 of mpgan_pack_weights,
+ * [64][tap][2], 8-byte aligned, so that weight[:, 0] of a conditional checkpoint is what an unconditional conv1 holds.
+ * One row-walking VALU kernel, lane = output channel (thin_cin2_rows_kernel, conv_igemm.hip): each output pixel's 64
+ * channels are stored once.
+ * Replaces: Discriminator.model_conv[0] (GAN_final.py:167-169) applied to torch.cat([img, cond], 1), the conditional
+ * discriminator of pix2pix (the paper GAN_final.py:125 cites); the reference itself has no such call.
+ *
+ * mpgan_conv2p_forward:  y (fp32) = conv + bias.  stats_partials must be NULL: as for the one-plane 1 -> 64 layer the
+ *   fp32 launch leaves no fused statistics (mpgan_conv2p_stats_rows(g, 0) == 0; use mpgan_channel_stats).
+ * mpgan_conv2p_forward_f32_to_bf16:  y (bf16) = conv + bias, rounded once; stats_partials (nullable) receives
+ *   mpgan_conv2p_stats_rows(g, 1) rows [2][64] of (sum y, sum y^2) taken in fp32 before rounding, one per block of the
+ *   launch, each pixel counted once; feed them to mpgan_norm_finalize(n = 1, chunks = rows).
+ * mpgan_conv2p_forward_act / _act_f32_to_bf16:  eval mode, y = lrelu(conv * scale[c] + shift[c], slope[c]) stored once
+ *   as fp32 / bf16 (mpgan_conv_forward_act's contract: the bias is folded into shift); stats_partials must be NULL.
+ * mpgan_conv2p_kernel_name: the profiling label of those launches (out_bf16: of the _f32_to_bf16 ones), written like
+ *   mpgan_conv_kernel_name's; rows, label and launch read one choice (choose_gather, conv_igemm.hip). */
+int32_t mpgan_conv2p_stats_rows(const mpgan_conv_geom* g, int32_t out_bf16);
+int mpgan_conv2p_kernel_name(const mpgan_conv_geom* g, int32_t out_bf16, char* buf, int32_t len);
+int mpgan_conv2p_forward(const mpgan_conv_geom* g, const float* x_img, const float* x_cond, const float* w_packed,
+                         const float* bias, float* stats_partials, float* y, int32_t ldy, void* stream);
+int mpgan_conv2p_forward_act(const mpgan_conv_geom* g, const float* x_img, const float* x_cond, const float* w_packed,
+                             const float* scale, const float* shift, const float* slope, float* y, int32_t ldy,
+                             void* stream);
+int mpgan_conv2p_forward_f32_to_bf16(const mpgan_conv_geom* g, const float* x_img, const float* x_cond,
+                                     const float* w_packed, const float* bias, float* stats_partials, void* y,
+                                     int32_t ldy, void* stream);
+int mpgan_conv2p_forward_act_f32_to_bf16(const mpgan_conv_geom* g, const float* x_img, const float* x_cond,
+                                         const float* w_packed, const float* scale, const float* shift,
+                                         const float* slope, float* stats_partials, void* y, int32_t ldy, void* stream);
+/* dW (fp32, torch layout (64, 2, k...)) = beta*dW + sum over pixels, both planes from ONE pass over dy; dbias
+ * (nullable) = beta*dbias + colsum(dy), fused.  dy: fp32, or bf16 when dy_bf16 != 0 (converted on load).  Per-block
+ * partial slabs in `workspace` (>= mpgan_conv2p_wgrad_workspace(g) bytes; -1: geometry refused), then the fixed-order
+ * slab reducer of mpgan_conv_backward_weight: two runs give the same bits.  mpgan_conv2p_wgrad_kernel_name: the label,
+ * from the same choice (choose_wgrad, conv_wgrad.hip).
+ * Replaces: the autograd weight / bias gradient of that conv under loss.backward() (GAN_final.py:296).
+ * There is no gradient for the condition (it is data), and the image plane's input gradient needs no entry of its
+ * own: mpgan_conv_backward_data / mpgan_conv_backward_data_bf16_to_f32 with the geometry's cin set to 1 and the
+ * layout-3 pack of mpgan_pack_weights ([tap][cout] of weight[:, 0]). */
+int64_t mpgan_conv2p_wgrad_workspace(const mpgan_conv_geom* g);
+int mpgan_conv2p_wgrad_kernel_name(const mpgan_conv_geom* g, int32_t bf16_dy, char* buf, int32_t len);
+int mpgan_conv2p_backward_weight(const mpgan_conv_geom* g, const float* x_img, const float* x_cond, const void* dy,
+                                 int32_t lddy, int32_t dy_bf16, float* dw, float* dbias, float beta, void* workspace,
+                                 int64_t workspace_bytes, void* stream);
 
 /* ---- sliding-window inference (MONAI 0.4.0 sliding_window_inference; code/GAN/minipig_inference.py:110-114) --
  * An image batch (B, C, D, H, W) contiguous fp32 (2-D: D = 1) is padded per dim by pad_lo before / the rest after

@@ -5,6 +5,7 @@
     python tools/dump_programs.py [--storage {bf16,f32,both}]        # variant A and B, every program
     python tools/dump_programs.py --tree DIR                         # the same of another built checkout (the parent commit)
     python tools/dump_programs.py --head markovian                   # variant A with the Markovian (PatchGAN) head
+    python tools/dump_programs.py --conditional [--head markovian]   # variant A conditional: D(cat(img, cond)), DESIGN.md 7e
     MPGAN_FUSE_BWD_STATS_BF16=1 python tools/dump_programs.py        # bf16 variant A train with the fused norm-backward sums
     MPGAN_DBG_NO_FUSE_BWD_STATS=1 python tools/dump_programs.py      # fp32 variant A train without them
 
@@ -22,6 +23,8 @@ _ap = argparse.ArgumentParser()
 _ap.add_argument("--storage", default="both", choices=("bf16", "f32", "both"))
 _ap.add_argument("--head", default="linear", choices=("linear", "markovian"),
                  help="variant A's head; markovian lists variant A alone, at shapes whose last feature map is >= 4")
+_ap.add_argument("--conditional", action="store_true",
+                 help="variant A as the conditional (pix2pix) discriminator, listed alone: conv1 over two input planes")
 _ap.add_argument("--tree", default=HERE, help="a built checkout to import the package from")
 ARGS = _ap.parse_args()
 sys.path.insert(0, os.path.abspath(ARGS.tree))
@@ -34,6 +37,9 @@ DEV = "cuda"
 # the default keeps the constructor call and the titles of the commits before the option existed (--tree)
 HEAD_KW = {} if ARGS.head == "linear" else {"head": ARGS.head}
 HEAD_TAG = "" if ARGS.head == "linear" else f" {ARGS.head}"
+if ARGS.conditional:
+    HEAD_KW["conditional"] = True
+    HEAD_TAG += " conditional"
 
 
 class Ordinals(dict):
@@ -146,7 +152,7 @@ def variant_b_f32(shape, n):
 
 def main():
     bf16, f32 = ARGS.storage in ("bf16", "both"), ARGS.storage in ("f32", "both")
-    if ARGS.head == "markovian":                             # (24^3 ends in a 3^3 feature map: 32^3 here)
+    if ARGS.head == "markovian" or ARGS.conditional:         # (24^3 ends in a 3^3 feature map: 32^3 here)
         for fn in ([variant_a] if bf16 else []) + ([variant_a_f32] if f32 else []):
             fn((40, 40), 3)
             fn((32, 32, 32), 2)
