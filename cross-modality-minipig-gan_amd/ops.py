@@ -961,6 +961,76 @@ def ssim_loss_backward(a, b, spatial, items, channels, lo, grad_mask, coef, upst
     return grad
 
 
+# ---- differentiable augmentation (csrc/diffaug.hip; augment.py holds the sampler and the autograd node) ----
+DIFFAUG_BRIGHTNESS, DIFFAUG_CONTRAST, DIFFAUG_TRANSLATION, DIFFAUG_CUTOUT = 1, 2, 4, 8      # MPGAN_DIFFAUG_*
+
+
+def _diffaug_geometry(x, what: str):
+    """(n, spatial) of a contiguous fp32 (B, 1, *S) device tensor, S = (H, W) or (D, H, W)."""
+    if x.dim() not in (4, 5) or x.shape[1] != 1:
+        raise ValueError(f"{what}: need a (B, 1, H, W) or (B, 1, D, H, W) tensor, got {tuple(x.shape)}")
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError(f"{what}: the image must be contiguous float32, got {x.dtype} with strides {x.stride()}")
+    if not x.is_cuda:
+        raise ValueError(f"{what}: every tensor must be on the GPU (there is no CPU path)")
+    if x.numel() >= 2 ** 31:
+        raise ValueError(f"{what}: {x.numel()} elements exceed the 32-bit count of mpgan_diffaug_*")
+    return int(x.shape[0]), tuple(int(s) for s in x.shape[2:])
+
+
+def _diffaug_tables(x, n, ops_mask, color, geom, workspace, spatial, what):
+    if ops_mask & ~15:
+        raise ValueError(f"{what}: unknown ops bits {ops_mask:#x}")
+    for t, dtype, cols, name, used in ((color, torch.float32, 2, "color", ops_mask & 3), (geom, torch.int32, 9, "geom", ops_mask & 12)):
+        if t is None:
+            if used:
+                raise ValueError(f"{what}: ops {ops_mask:#x} need the {name} table")
+            continue
+        if tuple(t.shape) != (n, cols) or t.dtype != dtype or not t.is_contiguous() or t.device != x.device:
+            raise ValueError(f"{what}: {name} must be a contiguous {dtype} ({n}, {cols}) tensor on {x.device}, got "
+                             f"{tuple(t.shape)} {t.dtype} on {t.device}")
+    if ops_mask & DIFFAUG_CONTRAST:
+        need = diffaug_workspace(n, spatial)
+        if (workspace is None or workspace.dtype != torch.float64 or not workspace.is_contiguous()
+                or workspace.device != x.device or workspace.numel() * 8 < need):
+            raise ValueError(f"{what}: contrast needs a contiguous float64 workspace of >= {need} bytes on {x.device}")
+
+
+def diffaug_workspace(n: int, spatial) -> int:
+    """Bytes of fp64 block partials diffaug_forward / diffaug_backward need with DIFFAUG_CONTRAST."""
+    need = int(lib().mpgan_diffaug_workspace(int(n), _dhw(spatial)))
+    if need < 0:
+        check(-1, "diffaug_workspace")
+    return need
+
+
+def diffaug_forward(x, ops_mask: int, color, geom, fill: float, workspace, y):
+    """y = the augmentation `ops_mask` (DIFFAUG_* bits) of x under the per-sample tables color (B, 2) float32 and
+    geom (B, 9) int32 (include/mpgan_hip.h); workspace: float64, only with DIFFAUG_CONTRAST."""
+    n, spatial = _diffaug_geometry(x, "diffaug_forward")
+    if y.shape != x.shape:
+        raise ValueError(f"diffaug_forward: y has shape {tuple(y.shape)}, x {tuple(x.shape)}")
+    _diffaug_geometry(y, "diffaug_forward")
+    _diffaug_tables(x, n, int(ops_mask), color, geom, workspace, spatial, "diffaug_forward")
+    check(lib().mpgan_diffaug_forward(x.data_ptr(), n, _dhw(spatial), int(ops_mask), _ptr(color), _ptr(geom), float(fill),
+                                      _ptr(workspace), workspace.numel() * 8 if workspace is not None else 0,
+                                      y.data_ptr(), _stream()), "diffaug_forward")
+    return y
+
+
+def diffaug_backward(gy, ops_mask: int, color, geom, workspace, gx):
+    """gx = the gradient of diffaug_forward's input for the output gradient gy, same tables (neither x nor y is needed)."""
+    n, spatial = _diffaug_geometry(gy, "diffaug_backward")
+    if gx.shape != gy.shape:
+        raise ValueError(f"diffaug_backward: gx has shape {tuple(gx.shape)}, gy {tuple(gy.shape)}")
+    _diffaug_geometry(gx, "diffaug_backward")
+    _diffaug_tables(gy, n, int(ops_mask), color, geom, workspace, spatial, "diffaug_backward")
+    check(lib().mpgan_diffaug_backward(gy.data_ptr(), n, _dhw(spatial), int(ops_mask), _ptr(color), _ptr(geom),
+                                       _ptr(workspace), workspace.numel() * 8 if workspace is not None else 0,
+                                       gx.data_ptr(), _stream()), "diffaug_backward")
+    return gx
+
+
 # --------------------------------------------------------------------------
 # conditional discriminator: the first conv over two 1-channel input planes (include/mpgan_hip.h: mpgan_conv2p_*)
 # --------------------------------------------------------------------------

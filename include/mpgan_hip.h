@@ -543,6 +543,35 @@ int mpgan_ssim_loss_backward(const float* a, const float* b, const int32_t* dhw,
                              const float* upstream, int32_t upstream_stride, double scale, int32_t wrt, float* grad,
                              void* stream);
 
+/* ---- differentiable augmentation in front of the discriminator (DiffAugment, Zhao et al. 2020) ----
+ * x: contiguous fp32 [n][D][H][W] (one channel; 2-D images have D = 1); N = D H W.  Per sample s, from two device tables
+ * (nothing is read on the host):
+ *   color: float [n][2] = (b, c), brightness offset and contrast factor
+ *   geom:  int32 [n][9] = (t_d, t_h, t_w, lo_d, lo_h, lo_w, size_d, size_h, size_w)
+ * `ops` selects what is applied; a disabled op ignores its table entries (and a table no enabled op reads may be null).
+ * With m = the mean of x over the sample:
+ *   u[q]    = c (x[q] - m) + m + b                 (b = 0 without BRIGHTNESS; c = 1 and no mean without CONTRAST)
+ *   keep(p) = inside(p + t) and not (lo_k <= p_k < lo_k + size_k for every axis k)
+ *   y[p]    = keep(p) ? u[p + t] : fill
+ *   g_u[q]  = inside(q - t) and keep(q - t) ? g_y[q - t] : 0
+ *   g_x[q]  = c g_u[q] + (1 - c) / N * sum_q' g_u[q']        (the sum only with CONTRAST)
+ * Any t is legal (|t_k| >= S_k: all fill) and any box (negative lo, past the edge, size <= 0: nothing cut).  Without a
+ * colour op y and g_x are copies, zeros and `fill`: exact.  m and (1 - c) / N * sum g_u are fp64 sums rounded to fp32
+ * once; the element arithmetic is fp32.
+ * Launches: one each way, two with CONTRAST (the block partials of the sample sums into `ws`, then the apply kernel, which
+ * adds a sample's partials itself).  No atomics; the grid and every sum's order depend on (n, dhw) alone: two runs give
+ * the same bits.  16-byte accesses when both pointers are 16-byte aligned and W % 4 == 0, element-wise otherwise.
+ * ws: >= mpgan_diffaug_workspace(n, dhw) bytes, 8-byte aligned; read and written only with CONTRAST (may be null
+ * otherwise).  The backward needs neither x nor y.  MPGAN_ERR_INVALID before any launch: a null x / y / dhw (or a table
+ * an enabled op reads), n <= 0, an extent < 1, unknown ops bits, n * N >= 2^31, with CONTRAST a null, short or
+ * misaligned ws. */
+enum { MPGAN_DIFFAUG_BRIGHTNESS = 1, MPGAN_DIFFAUG_CONTRAST = 2, MPGAN_DIFFAUG_TRANSLATION = 4, MPGAN_DIFFAUG_CUTOUT = 8 };
+int64_t mpgan_diffaug_workspace(int32_t n, const int32_t* dhw); /* bytes of fp64 block partials (-1: bad geometry) */
+int mpgan_diffaug_forward(const float* x, int32_t n, const int32_t* dhw, int32_t ops, const float* color,
+                          const int32_t* geom, float fill, void* ws, int64_t ws_bytes, float* y, void* stream);
+int mpgan_diffaug_backward(const float* gy, int32_t n, const int32_t* dhw, int32_t ops, const float* color,
+                           const int32_t* geom, void* ws, int64_t ws_bytes, float* gx, void* stream);
+
 /* ---- optimiser ------------------------------------------------------------ */
 /* torch.optim.Adam.step over one flat buffer (GAN_final.py:306-307):
  * m = b1*m+(1-b1)*g; v = b2*v+(1-b2)*g^2; p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t)+eps).
