@@ -71,6 +71,7 @@ SIGNATURES = {
     "mpgan_conv_wgrad_workspace": (_L, [_G]),
     "mpgan_conv_backward_weight": (_I, [_G, _P, _I, _PR, _P, _I, _P, _P, _F, _P, _L, _P]),
     "mpgan_conv_wgrad_kernel_name": (_I, [_G, _I, _I, C.c_char_p, _I]),
+    "mpgan_conv_wgrad_kernel_name_at": (_I, [_G, _P, _I, _PR, _P, _I, _I, C.c_char_p, _I]),
     "mpgan_pack_weights": (_I, [_P, _P, _P, _I, _L, _P]),
     "mpgan_stats_chunks": (_I, [_L, _I]),
     "mpgan_channel_stats": (_I, [_P, _I, _I, _L, _I, _P, _P]),

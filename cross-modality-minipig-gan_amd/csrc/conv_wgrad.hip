@@ -1588,11 +1588,11 @@ extern "C" int mpgan_conv_wgrad_kernel_name(const mpgan_conv_geom* g, int32_t pr
   return MPGAN_OK;
 }
 
-extern "C" int mpgan_conv_backward_weight(const mpgan_conv_geom* g, const float* x, int32_t ldx,
-                                          const mpgan_prologue* pro, const float* dy, int32_t lddy, float* dw,
-                                          float* dbias, float beta, void* workspace, int64_t workspace_bytes,
-                                          void* stream) {
-  MPGAN_CHECK_ARG(g && x && dy && dw && workspace, "conv_backward_weight: null pointer");
+// The operand checks of mpgan_conv_backward_weight, shared with its label query (the launch adds dw, dbias and the
+// workspace).
+static int check_wgrad_operands(const mpgan_conv_geom* g, const float* x, int32_t ldx, const mpgan_prologue* pro,
+                                const float* dy, int32_t lddy) {
+  MPGAN_CHECK_ARG(g && x && dy, "conv_backward_weight: null pointer");
   MPGAN_CHECK_ARG(ldx >= g->cin && lddy >= g->cout, "conv_backward_weight: bad pitch");
   int Cd, Cg, T;
   long M;
@@ -1601,13 +1601,51 @@ extern "C" int mpgan_conv_backward_weight(const mpgan_conv_geom* g, const float*
                       (long)g->n * g->in_dhw[0] * g->in_dhw[1] * g->in_dhw[2] < (1L << 31) &&
                       (long)g->n * g->out_dhw[0] * g->out_dhw[1] * g->out_dhw[2] < (1L << 31),
                   "conv_backward_weight: more than 2^31 pixels");
+  MPGAN_UNSUPPORTED(g->transposed && pro && pro->scale, "conv_backward_weight: prologue on a transposed conv input");
+  return MPGAN_OK;
+}
+
+// ... and of mpgan_conv_backward_weight_bf16dy.
+static int check_wgrad_operands_bf16dy(const mpgan_conv_geom* g, const float* x, const void* dy) {
+  MPGAN_CHECK_ARG(g && x && dy, "conv_backward_weight_bf16dy: null pointer");
+  MPGAN_UNSUPPORTED(g->transposed || g->cin != 1, "conv_backward_weight_bf16dy: ConvNd with one input channel only");
+  int Cd, Cg, T;
+  long M;
+  wgrad_dims(g, Cd, Cg, T, M);
+  MPGAN_CHECK_ARG(M < (1L << 31) - 64, "conv_backward_weight_bf16dy: more than 2^31 pixels");
+  return MPGAN_OK;
+}
+
+extern "C" int mpgan_conv_wgrad_kernel_name_at(const mpgan_conv_geom* g, const float* x, int32_t ldx,
+                                               const mpgan_prologue* pro, const void* dy, int32_t lddy, int32_t bf16_dy,
+                                               char* buf, int32_t len) {
+  MPGAN_CHECK_ARG(buf && len > 0, "conv_wgrad_kernel_name_at: no buffer");
+  if (const int rc = bf16_dy ? check_wgrad_operands_bf16dy(g, x, dy)
+                             : check_wgrad_operands(g, x, ldx, pro, static_cast<const float*>(dy), lddy))
+    return rc;
+  const WgradParams p = wgrad_params(g, x, ldx, bf16_dy ? nullptr : pro, dy, lddy, nullptr, bf16_dy != 0);
+  const WgradChoice c = choose_wgrad(g, p, bf16_dy != 0);
+  if (c.rc != MPGAN_OK) {
+    set_error("%s", c.msg);
+    return c.rc;
+  }
+  const int n = wgrad_kernel_name(c, buf, len);
+  MPGAN_CHECK_ARG(n < len, "conv_wgrad_kernel_name_at: the name needs %d bytes", n + 1);
+  return MPGAN_OK;
+}
+
+extern "C" int mpgan_conv_backward_weight(const mpgan_conv_geom* g, const float* x, int32_t ldx,
+                                          const mpgan_prologue* pro, const float* dy, int32_t lddy, float* dw,
+                                          float* dbias, float beta, void* workspace, int64_t workspace_bytes,
+                                          void* stream) {
+  if (const int rc = check_wgrad_operands(g, x, ldx, pro, dy, lddy)) return rc;
+  MPGAN_CHECK_ARG(dw && workspace, "conv_backward_weight: null pointer");
   const int64_t need = generic_wgrad_bytes(g);
   MPGAN_CHECK_ARG(workspace_bytes >= need, "conv_backward_weight: workspace %lld < %lld bytes",
                   (long long)workspace_bytes, (long long)need);
   MPGAN_UNSUPPORTED(dbias && g->transposed,
                     "conv_backward_weight: fused bias gradient is for ConvNd only (dy is the gathered operand of a "
                     "transposed conv)");
-  MPGAN_UNSUPPORTED(g->transposed && pro && pro->scale, "conv_backward_weight: prologue on a transposed conv input");
   const WgradParams p = wgrad_params(g, x, ldx, pro, dy, lddy, workspace, false);
   const WgradChoice c = choose_wgrad(g, p, false);
   if (c.rc != MPGAN_OK) {
@@ -1624,12 +1662,8 @@ extern "C" int mpgan_conv_backward_weight(const mpgan_conv_geom* g, const float*
 extern "C" int mpgan_conv_backward_weight_bf16dy(const mpgan_conv_geom* g, const float* x, int32_t ldx, const void* dy,
                                                  int32_t lddy, float* dw, float* dbias, float beta, void* workspace,
                                                  int64_t workspace_bytes, void* stream) {
-  MPGAN_CHECK_ARG(g && x && dy && dw && workspace, "conv_backward_weight_bf16dy: null pointer");
-  MPGAN_UNSUPPORTED(g->transposed || g->cin != 1, "conv_backward_weight_bf16dy: ConvNd with one input channel only");
-  int Cd, Cg, T;
-  long M;
-  wgrad_dims(g, Cd, Cg, T, M);
-  MPGAN_CHECK_ARG(M < (1L << 31) - 64, "conv_backward_weight_bf16dy: more than 2^31 pixels");
+  if (const int rc = check_wgrad_operands_bf16dy(g, x, dy)) return rc;
+  MPGAN_CHECK_ARG(dw && workspace, "conv_backward_weight_bf16dy: null pointer");
   const WgradParams p = wgrad_params(g, x, ldx, nullptr, dy, lddy, workspace, true);
   const WgradChoice c = choose_wgrad(g, p, true);
   if (c.rc != MPGAN_OK) {

@@ -274,6 +274,16 @@ def wgrad_kernel_name(g: ConvGeom, pro=None, bf16_dy: bool = False) -> str:
     return kernel_label(lib().mpgan_conv_wgrad_kernel_name, C.byref(gc), code, int(bf16_dy))
 
 
+def wgrad_kernel_name_at(g: ConvGeom, x, dy, pro=None) -> str:
+    """The same label for these very operands (mpgan_conv_wgrad_kernel_name_at): the pitches, base alignment and
+    prologue of x and dy decide as they do in the launch; a bf16 dy names the bf16-dy entry's instance."""
+    gc = g.c()
+    bf16_dy = dy.dtype == torch.bfloat16
+    lddy = ops._clx(dy, dy.dtype, "wgrad_kernel_name_at dy")[2]
+    return kernel_label(lib().mpgan_conv_wgrad_kernel_name_at, C.byref(gc), x.data_ptr(), _ld(x), ops._pro(pro),
+                        dy.data_ptr(), lddy, int(bf16_dy))
+
+
 def kernel_label(entry, *args) -> str:
     """The label a mpgan_conv_kernel_name* entry writes for these arguments."""
     buf = C.create_string_buffer(160)

@@ -168,6 +168,12 @@ int mpgan_conv_backward_weight(const mpgan_conv_geom* g, const float* x, int32_t
  * mpgan_conv_kernel_name's; pro_code as there.  The launch, mpgan_conv_wgrad_workspace(_bf16dy) and this label read
  * one choice (choose_wgrad, conv_wgrad.hip). */
 int mpgan_conv_wgrad_kernel_name(const mpgan_conv_geom* g, int32_t pro_code, int32_t bf16_dy, char* buf, int32_t len);
+/* The same label for the operands actually passed: pitches, base alignment and prologue enter the choice as they do in
+ * mpgan_conv_backward_weight (bf16_dy: mpgan_conv_backward_weight_bf16dy, which takes no prologue), after that entry's
+ * own operand checks; a refusal returns the launch's status and message.  The pointers are read for alignment only:
+ * nothing is dereferenced or launched. */
+int mpgan_conv_wgrad_kernel_name_at(const mpgan_conv_geom* g, const float* x, int32_t ldx, const mpgan_prologue* pro,
+                                    const void* dy, int32_t lddy, int32_t bf16_dy, char* buf, int32_t len);
 
 /* Repack every conv / linear weight of a network in ONE launch.
  * table: device int64 [n_entries][8] = {src_off, dst_off, cout, cin, taps,
