@@ -21,7 +21,7 @@ import dataclasses
 import math
 import os
 import struct
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
@@ -1169,290 +1169,287 @@ class Scratch:
 # --------------------------------------------------------------------------
 # residual U-Net
 # --------------------------------------------------------------------------
-class _RU:
-    """Handles into one ResidualUnit's parameter modules."""
+class ConvUnit:
+    """One `conv [+ norm + PReLU]` of a U-Net plan: the modules, the conv's pack record and geometry, its raw output `z`
+    and the norm layer's device vectors, and the launches that touch them (the emit_* helpers with this unit's operands
+    filled in).  `p` is the UNetPlan that carries the programs, the store, the scratch and the mode."""
 
-    def __init__(self, ru):
-        self.units = []
-        for unit in ru.conv:
-            adn = getattr(unit, "adn", None)
-            self.units.append((unit.conv, adn.N if adn is not None else None, adn.A if adn is not None else None))
-        self.res = ru.residual if not isinstance(ru.residual, nn.Identity) else None
+    def __init__(self, p: "UNetPlan", conv, adn, in_dhw, z=None):
+        self.p, self.conv = p, conv
+        self.N, self.A = (adn.N, adn.A) if adn is not None else (None, None)
+        self.g = g = conv_geom_of(conv, p.n, in_dhw, p.dims)
+        self.rec = p.store.register_conv(conv, cout=g.cout, cin=g.cin, taps=math.prod(conv.kernel_size),
+                                         transposed=g.transposed)
+        self.z = z                         # None: alloc() gives it a buffer of its own, unless fuse() has by then
+        self.fused = self.gf = self.zf = None
+        self.nb = None
+        if self.N is not None:
+            self.nb = NormBuf(p.n, g.cout, p.instance, p.dev)
+            p.scratch.want_partials(p.n, math.prod(g.out_dhw), g.cout)
+        p.scratch.want_ws(g)
+
+    def alloc(self) -> "ConvUnit":
+        if self.z is None:
+            self.z = self.p.E(self.p.n, *self.g.out_dhw, self.g.cout)
+        return self
+
+    def fuse(self, other: "ConvUnit"):
+        """This conv and `other` read the same input with the same geometry: ONE forward conv over their concatenated
+        output channels writes [z | other.z] (one launch, the input read once)."""
+        p, c = self.p, self.g.cout
+        self.fused = p.store.register_fused(self.conv, other.conv)       # before any packed offset is taken (emit)
+        self.gf = dataclasses.replace(self.g, cout=c + other.g.cout)
+        self.zf = p.E(p.n, *self.g.out_dhw, self.gf.cout)
+        self.z, other.z = self.zf[..., :c], self.zf[..., c:]
+        p.scratch.want_ws(self.gf)
+
+    def acc_want(self, code, consumer_ok):
+        """[(NormBuf, accumulator row width)] when the producing kernel (prologue `code`) can leave accumulator
+        statistics and the first consumer can fold them, else []."""
+        g = self.g if self.fused is None else self.gf
+        return [(self.nb, g.cout)] if consumer_ok and ops.conv_acc_supported(g, code) else []
+
+    def prologue(self) -> Prologue:
+        return self.nb.prologue(ACT_LEAKY, 1.0, self.A.weight)
+
+    def _fwd_operands(self):
+        """Geometry, packed weights, bias, output and normed channel count of the forward launch: the fused pair's,
+        whose first `cout` channels alone are normed, when there is one."""
+        st = self.p.store
+        if self.fused is not None:
+            return self.gf, st.wp_fused(self.fused), st.bias_fused(self.fused), self.zf, self.g.cout
+        return self.g, st.wp(self.rec), self.conv.bias, self.z, None
+
+    def fwd_norm(self, x, pre: Optional["ConvUnit"] = None):
+        """Raw output and the norm's statistics (train, and eval outside the fused path); `pre`: the unit in front,
+        whose norm + PReLU is applied to x on load."""
+        p = self.p
+        g, w, bias, y, c_norm = self._fwd_operands()
+        emit_conv_fwd_norm(p.fwd, g, x, w, bias, y, self.nb, self.N, p.scratch.partials,
+                           pro=pre.prologue() if pre is not None else None, training=p.training,
+                           eval_norms=p.eval_norms, c_norm=c_norm, fold=pre.nb.fold() if pre is not None else None)
+
+    def fwd_act(self, x, y=None, resid=None, tanh=False):
+        """Fused eval forward: the ACTIVATED output (running-statistics norm, PReLU, bias, `resid`) into y (default z)."""
+        p = self.p
+        g, w, bias, z, c_norm = self._fwd_operands()
+        emit_conv_fwd_act(p.fwd, p.epi_rows, g, x, w, bias, z if y is None else y, self.N, self.A, c_norm=c_norm,
+                          resid=resid, tanh=tanh)
+
+    def fwd(self, x, resid=None, tanh=False):
+        """Plain conv into z (a residual branch, the top level's conv-only unit)."""
+        emit_conv_fwd(self.p.fwd, self.g, x, self.p.store.wp(self.rec), self.conv.bias, self.z, resid=resid, tanh=tanh)
+
+    def norm_bwd(self, g, dz):
+        p, gv = self.p, self.p.store.grad_view
+        emit_norm_bwd(p.bwd, g, self.z, self.nb, self.prologue(), dz, p.scratch.partials, gv(self.N.weight),
+                      gv(self.N.bias), gv(self.A.weight))
+
+    def wgrad(self, x, dy, pre: Optional["ConvUnit"] = None):
+        """Weight (and, for a ConvNd, bias) gradient, onto the side program."""
+        p, gv = self.p, self.p.store.grad_view
+        emit_conv_wgrad(p.side, self.g, x, dy, gv(self.conv.weight), p.scratch.ws,
+                        pro=pre.prologue() if pre is not None else None,
+                        dbias=None if self.g.transposed else gv(self.conv.bias), lane=1)
+
+    def dgrad(self, dy, dx, resid=None):
+        emit_conv_dgrad(self.p.bwd, self.g, dy, self.p.store.wp_bwd(self.rec), dx, resid=resid)
+
+
+class ResidualUnit:
+    """MONAI's two-subunit ResidualUnit, every down level and the bottom of the U:
+    out = act(norm(conv1(act(norm(conv0(x)))))) + residual(x).  `out` is set by the plan once the unit's geometry has
+    sized the buffer it is a slice of."""
+
+    def __init__(self, p: "UNetPlan", ru, x, out=None):
+        self.p, self.x, self.out = p, x, out
+        m0, m1 = ru.conv
+        in_dhw = tuple(x.shape[1:4])
+        # MONAI's ResidualUnit has a residual conv only when the stride or the channel count changes: a bottom
+        # layer with chans[-2] == chans[-1] (generator_test.py's (…, 512, 512)) adds its input unchanged.
+        identity = isinstance(ru.residual, nn.Identity)
+        self.u0 = ConvUnit(p, m0.conv, m0.adn, in_dhw)
+        self.res = None if identity else ConvUnit(p, ru.residual, None, in_dhw)
+        if not identity and _FUSE_DOWN and same_geom(self.u0.g, self.res.g):    # (never the bottom: its residual is 1x1)
+            self.u0.fuse(self.res)
+        self.u0.alloc()
+        self.u1 = ConvUnit(p, m1.conv, m1.adn, self.u0.g.out_dhw).alloc()
+        self.r = x if identity else self.res.alloc().z
+
+    def acc_wants(self):
+        # (the consumer of conv1's statistics is the residual-sum pass)
+        return self.u0.acc_want(0, ops.conv_fold_supported(self.u1.g)) + self.u1.acc_want(1, True)
+
+    def emit_forward(self):
+        u0, u1 = self.u0, self.u1
+        u0.fwd_norm(self.x)
+        if self.res is not None and u0.fused is None:
+            # (the residual conv could run on the side stream; measured: the event hand-offs cost more
+            #  than the ~20 us kernels they would overlap -- G forward 4.42 -> 4.56 ms)
+            self.res.fwd(self.x)
+        u1.fwd_norm(u0.z, pre=u0)
+        emit_norm_act_add(self.p.fwd, u1.z, u1.prologue(), self.r, None, self.out, fold=u1.nb.fold())
+
+    def emit_forward_eval(self):
+        """The fused eval path: conv1's epilogue adds the residual and writes `out`."""
+        self.u0.fwd_act(self.x)                    # fused with the residual conv: its own channels alone are normed + activated
+        if self.res is not None and self.u0.fused is None:
+            self.res.fwd(self.x)
+        self.u1.fwd_act(self.u0.z, y=self.out, resid=self.r)
+
+    def emit_backward(self, g_out, dz1, ga0, dx, accumulate_first=True):
+        """g_out = dL/d(out); dz1, ga0: scratch of conv1's output shape.  dL/dx goes to `dx`: both backward-data launches
+        accumulate into it, or the first writes it (accumulate_first=False: nothing is there yet), or, with dx None,
+        neither runs."""
+        u0, u1, res = self.u0, self.u1, self.res
+        u1.norm_bwd(g_out, dz1)
+        u1.wgrad(u0.z, dz1, pre=u0)
+        u1.dgrad(dz1, ga0)
+        u0.norm_bwd(ga0, ga0)
+        u0.wgrad(self.x, ga0)
+        if res is not None:
+            res.wgrad(self.x, g_out)
+        if dx is None:
+            return
+        u0.dgrad(ga0, dx, resid=dx if accumulate_first else None)
+        if res is not None:
+            res.dgrad(g_out, dx, resid=dx)
+        else:
+            emit_norm_act_add(self.p.bwd, g_out, None, dx, None, dx)           # identity residual: dx += g_out
+
+
+class UpLevel:
+    """One up level: transposed conv + norm + PReLU on the concatenation `cat`, then the one-subunit ResidualUnit on its
+    output -- normed, its residual act(norm(zt)) applied through the prologue pair, or, at the top of the U, conv-only
+    on the materialised activation `ua`."""
+
+    def __init__(self, p: "UNetPlan", up, cat, out, tanh):
+        self.p, self.cat, self.out, self.tanh = p, cat, out, tanh
+        unit = up[1].conv[0]
+        adn = getattr(unit, "adn", None)
+        self.top = adn is None
+        self.t = t = ConvUnit(p, up[0].conv, up[0].adn, tuple(cat.shape[1:4])).alloc()
+        assert t.g.out_dhw == tuple(out.shape[1:4]), (t.g.out_dhw, out.shape)
+        self.u = ConvUnit(p, unit.conv, adn, t.g.out_dhw, z=out if self.top else None).alloc()
+        self.ua = torch.empty_like(t.z) if self.top else None
+
+    def acc_wants(self):
+        if self.top:                               # materialised by the residual-sum pass
+            return self.t.acc_want(0, True)
+        return self.t.acc_want(0, ops.conv_fold_supported(self.u.g)) + self.u.acc_want(1, True)
+
+    def emit_forward(self):
+        t, u, f = self.t, self.u, self.p.fwd
+        t.fwd_norm(self.cat)
+        if self.top:
+            emit_norm_act_add(f, t.z, t.prologue(), None, None, self.ua, fold=t.nb.fold())
+            u.fwd(self.ua, resid=self.ua, tanh=self.tanh)
+        else:
+            u.fwd_norm(t.z, pre=t)
+            emit_norm_act_add(f, u.z, u.prologue(), t.z, t.prologue(), self.out, tanh=self.tanh, fold=u.nb.fold())
+
+    def emit_forward_eval(self):
+        """The fused eval path: the transposed conv leaves act(norm(.)) itself (in `ua` at the top, else in zt)."""
+        t, u = self.t, self.u
+        t.fwd_act(self.cat, y=self.ua)
+        if self.top:
+            u.fwd(self.ua, resid=self.ua, tanh=self.tanh)
+        else:
+            u.fwd_act(t.z, y=self.out, resid=t.z, tanh=self.tanh)
+
+    def emit_backward(self, g_out, dzu, gta, gcat):
+        """g_out = dL/d(out); dzu, gta: scratch of zt's shape; dL/d(cat) is written to gcat."""
+        t, u, p = self.t, self.u, self.p
+        if self.top:
+            u.wgrad(self.ua, g_out)
+            u.dgrad(g_out, gta, resid=g_out)
+        else:
+            u.norm_bwd(g_out, dzu)
+            u.wgrad(t.z, dzu, pre=t)
+            u.dgrad(dzu, gta, resid=g_out)
+        t.norm_bwd(gta, gta)
+        emit_bias_grad(p.bwd, gta, p.store.grad_view(t.conv.bias), p.scratch.partials)
+        t.wgrad(self.cat, gta)
+        t.dgrad(gta, gcat)
+
+
+class GradScratch(NamedTuple):
+    """The gradient buffers one U-Net's backward works in."""
+    gcat: list          # per level: dL/d(cat_l)
+    up: list            # per up level: (dzu, gta)
+    ru: list            # per down level, then the bottom: (dz1, ga0)
 
 
 class UNetPlan:
-    """Forward/backward programs of one residual U-Net for a fixed input shape."""
+    """Forward/backward programs of one residual U-Net for a fixed input shape: [down units] + bottom + [up levels]."""
 
     def __init__(self, unet, store: ParamStore, n: int, spatial: Sequence[int], x_in, y_out, *, tanh_out: bool,
-                 instance: bool, want_backward: bool, gbufs: Optional[dict], scratch: Scratch, training: bool = True,
+                 instance: bool, want_backward: bool, scratch: Scratch, training: bool = True,
                  own_mark: Optional[Mark] = None, wait_mark: Optional[Mark] = None):
-        self.unet, self.store, self.n = unet, store, n
-        self.training = training
-        dims = unet.dimensions
-        self.dims = dims
-        dev = x_in.device
-        chans = list(unet.channels)
+        self.unet, self.store, self.n, self.scratch = unet, store, n, scratch
+        self.training, self.instance, self.want_backward = training, instance, want_backward
+        self.dims, self.dev = unet.dimensions, x_in.device
+        self.chans = chans = list(unet.channels)
         L = len(chans)                      # levels incl. bottom
-        strides = list(unet.strides)[:L - 1]
-        dhw0 = _t3(spatial, dims, 1)
-        for d in range(3 - dims, 3):
+        dhw0 = _t3(spatial, self.dims, 1)
+        for d in range(3 - self.dims, 3):
             if dhw0[d] % (2 ** (L - 1)) != 0:
                 raise ValueError(f"U-Net input extent {dhw0[d]} is not divisible by {2 ** (L - 1)}")
-        # walk the module tree: level l = (down RU, up Sequential); last = bottom RU
-        downs, ups = [], []
-        blk = unet.model
-        while True:
-            downs.append(_RU(blk[0]))
-            ups.append(blk[2])
-            sub = blk[1].submodule
-            if isinstance(sub, nn.Sequential):
-                blk = sub
-            else:
-                bottom = _RU(sub)
-                break
-        assert len(downs) == L - 1
-        self.fwd, self.bwd = Program(), Program()
-        f = self.fwd
-        E = lambda *shape: torch.empty(*shape, device=dev)
-
-        def reg(conv):
-            tr = isinstance(conv, (nn.ConvTranspose2d, nn.ConvTranspose3d))
-            taps = 1
-            for k in conv.kernel_size:
-                taps *= k
-            return store.register_conv(conv, cout=conv.out_channels, cin=conv.in_channels, taps=taps, transposed=tr)
-
-        def prelu_pro(nb, A):
-            return nb.prologue(ACT_LEAKY, 1.0, A.weight)
-
-        # ---- shapes ----
-        sizes = [dhw0]
-        in_ch = [1] + chans[:L - 2]          # input channels of down level l
-        geoms_down = []
-        for l in range(L - 1):
-            g0 = conv_geom_of(downs[l].units[0][0], n, sizes[l], dims)
-            geoms_down.append(g0)
-            sizes.append(g0.out_dhw)
-        sub_out = [chans[l] for l in range(L - 2)] + [chans[L - 1]]  # channels appended to cat_l
-        self.saved = []
-        cats = [E(n, *sizes[l + 1], chans[l] + sub_out[l]) for l in range(L - 1)]
-        self.cats = cats
-        recs = {}
-
-        def R(conv):
-            if id(conv) not in recs:
-                recs[id(conv)] = reg(conv)
-            return recs[id(conv)]
-
-        # ================= forward =================
-        down_state = []
-        for l in range(L - 1):
-            ru = downs[l]
-            xin = x_in if l == 0 else cats[l - 1][..., :chans[l - 1]]
-            c = chans[l]
-            (cv0, N0, A0), (cv1, N1, A1) = ru.units
-            g0 = geoms_down[l]
-            g1 = conv_geom_of(cv1, n, sizes[l + 1], dims)
-            gr = conv_geom_of(ru.res, n, sizes[l], dims)
-            # unit0 and the strided residual conv read the same input with the same geometry: ONE conv over
-            # their concatenated output channels writes [z0 | r] (one launch, the input read once)
-            fuse = _FUSE_DOWN and same_geom(g0, gr)
-            fr = None
-            if fuse:
-                zr = E(n, *sizes[l + 1], 2 * c)
-                z0, r = zr[..., :c], zr[..., c:]
-                gf = dataclasses.replace(g0, cout=2 * c)
-                reg(cv0), reg(ru.res)
-                fr = store.register_fused(cv0, ru.res)       # before any packed offset is taken (emit)
-            else:
-                zr, gf = None, None
-                z0, r = E(n, *sizes[l + 1], c), E(n, *sizes[l + 1], c)
-            z1 = E(n, *sizes[l + 1], c)
-            nb0, nb1 = NormBuf(n, c, instance, dev), NormBuf(n, c, instance, dev)
-            P = sizes[l + 1][0] * sizes[l + 1][1] * sizes[l + 1][2]
-            scratch.want_partials(n, P, c)
-            for g in (g0, g1, gr) + ((gf,) if fuse else ()):
-                scratch.want_ws(g)
-            down_state.append(dict(xin=xin, z0=z0, z1=z1, r=r, nb0=nb0, nb1=nb1, g0=g0, g1=g1, gr=gr, ru=ru, c=c,
-                                   zr=zr, gf=gf, fr=fr))
-        # bottom
-        cb_in, cb = chans[L - 2], chans[L - 1]
-        (bc0, BN0, BA0), (bc1, BN1, BA1) = bottom.units
-        sb = sizes[L - 1]
-        gb0 = conv_geom_of(bc0, n, sb, dims)
-        gb1 = conv_geom_of(bc1, n, sb, dims)
-        # MONAI's ResidualUnit has a residual conv only when the stride or the channel count changes: a bottom
-        # layer with chans[-2] == chans[-1] (generator_test.py's (…, 512, 512)) adds its input unchanged.
-        gbr = conv_geom_of(bottom.res, n, sb, dims) if bottom.res is not None else None
-        zb0, zb1 = E(n, *sb, cb), E(n, *sb, cb)
-        rb = E(n, *sb, cb) if gbr is not None else None
-        nbb0, nbb1 = NormBuf(n, cb, instance, dev), NormBuf(n, cb, instance, dev)
-        scratch.want_partials(n, sb[0] * sb[1] * sb[2], cb)
-        for g in (gb0, gb1, gbr):
-            if g is not None:
-                scratch.want_ws(g)
-        # up
-        up_state = []
-        out_ch = in_ch                        # output channels of up level l == input channels of down level l
-        for l in range(L - 1):
-            convT_blk, ru_mod = ups[l][0], _RU(ups[l][1])
-            ct, NT, AT = convT_blk.conv, convT_blk.adn.N, convT_blk.adn.A
-            co = out_ch[l]
-            gt = conv_geom_of(ct, n, sizes[l + 1], dims)
-            assert gt.out_dhw == tuple(sizes[l]), (gt.out_dhw, sizes[l])
-            cu, NU, AU = ru_mod.units[0]
-            gu = conv_geom_of(cu, n, sizes[l], dims)
-            zt = E(n, *sizes[l], co)
-            nbt = NormBuf(n, co, instance, dev)
-            P = sizes[l][0] * sizes[l][1] * sizes[l][2]
-            scratch.want_partials(n, P, co)
-            scratch.want_ws(gt)
-            scratch.want_ws(gu)
-            st = dict(ct=ct, NT=NT, AT=AT, cu=cu, NU=NU, AU=AU, gt=gt, gu=gu, zt=zt, nbt=nbt, co=co)
-            if NU is not None:
-                st["zu"] = E(n, *sizes[l], co)
-                st["nbu"] = NormBuf(n, co, instance, dev)
-            else:
-                st["ua"] = E(n, *sizes[l], co)
-            up_state.append(st)
-        self._late = (down_state, up_state)
-        # Accumulator statistics (csrc/norm_fold.h) for the norm layers whose producing kernel can leave them and
-        # whose first consumer can fold them: no finalize launch for those.  (nb, accumulator row width)
-        self.acc_wants = []
-        if training and not instance and _ACC_STATS:
-            def want(nb, g_prod, code, consumer_ok):
-                if consumer_ok and ops.conv_acc_supported(g_prod, code):
-                    self.acc_wants.append((nb, g_prod.cout))
-            for l in range(L - 1):
-                sdn = down_state[l]
-                want(sdn["nb0"], sdn["gf"] if sdn["gf"] is not None else sdn["g0"], 0, ops.conv_fold_supported(sdn["g1"]))
-                want(sdn["nb1"], sdn["g1"], 1, True)                     # consumer: the residual-sum pass
-            want(nbb0, gb0, 0, ops.conv_fold_supported(gb1))
-            want(nbb1, gb1, 1, True)
-            for l in range(L - 1):
-                u = up_state[l]
-                if "zu" in u:
-                    want(u["nbt"], u["gt"], 0, ops.conv_fold_supported(u["gu"]))
-                    want(u["nbu"], u["gu"], 1, True)
-                else:
-                    want(u["nbt"], u["gt"], 0, True)                     # top level: materialised by the residual-sum pass
-        self.scratch = scratch
+        self.fwd, self.bwd, self.side = Program(), Program(), Program()      # side: the weight gradients (lane 1)
         self._marks = (own_mark, wait_mark)
         self.eval_norms = [] if not training else None   # eval mode: (norm module, NormBuf, C) of every layer
         self.epi_rows = []                                # eval mode, BatchNorm: table rows of emit_conv_fwd_act
         self.eval_fused = (not training) and (not instance) and (not want_backward)
-        self._build_args = dict(x_in=x_in, y_out=y_out, tanh_out=tanh_out, want_backward=want_backward, gbufs=gbufs,
-                                chans=chans, L=L, sizes=sizes, in_ch=in_ch, sub_out=sub_out, cats=cats, R=R,
-                                bottom=dict(bc0=bc0, BN0=BN0, BA0=BA0, bc1=bc1, BN1=BN1, BA1=BA1, res=bottom.res,
-                                            gb0=gb0, gb1=gb1, gbr=gbr, zb0=zb0, zb1=zb1, rb=rb, nbb0=nbb0, nbb1=nbb1,
-                                            cb=cb, cb_in=cb_in),
-                                prelu_pro=prelu_pro, instance=instance)
-
-    def _emit_eval(self, a, down_state, up_state):
-        """Eval-mode inference program of one U-Net (code/GAN/inferrence.py:97-110): every
-        conv emits its ACTIVATED output -- running-statistics BatchNorm, PReLU, bias and the unit's residual add in its
-        epilogue -- so no norm_act_add launch and no normalise-on-load prologue remain: 15 launches per U-Net instead of
-        22, all of them convs.  Same buffers as the training plan (a raw-output buffer now holds the activation)."""
-        f, store, rows = self.fwd, self.store, self.epi_rows
-        R = a["R"]
-        chans, L, cats = a["chans"], a["L"], a["cats"]
-        y_out = a["y_out"]
-        bt = a["bottom"]
-        wp = store.wp
+        # walk the module tree: level l = (down ResidualUnit, SkipConnection, up Sequential), the innermost submodule
+        # the bottom unit.  cat_l = [down l's output | what the submodule appends] is the up level's input.
+        self.downs, self.cats, up_mods = [], [], []
+        x, blk = x_in, unet.model
         for l in range(L - 1):
-            s = down_state[l]
-            (cv0, N0, A0), (cv1, N1, A1) = s["ru"].units
-            if s["gf"] is not None:       # unit0 || residual in one conv: the first c channels are normed + activated
-                fr = s["fr"]
-                emit_conv_fwd_act(f, rows, s["gf"], s["xin"], store.wp_fused(fr), store.bias_fused(fr), s["zr"], N0, A0,
-                                  c_norm=s["c"])
-            else:
-                emit_conv_fwd_act(f, rows, s["g0"], s["xin"], wp(R(cv0)), cv0.bias, s["z0"], N0, A0)
-                emit_conv_fwd(f, s["gr"], s["xin"], wp(R(s["ru"].res)), s["ru"].res.bias, s["r"])
-            emit_conv_fwd_act(f, rows, s["g1"], s["z0"], wp(R(cv1)), cv1.bias, cats[l][..., :s["c"]], N1, A1, resid=s["r"])
-        d_last = cats[L - 2][..., :bt["cb_in"]]
-        emit_conv_fwd_act(f, rows, bt["gb0"], d_last, wp(R(bt["bc0"])), bt["bc0"].bias, bt["zb0"], bt["BN0"], bt["BA0"])
-        if bt["res"] is not None:
-            emit_conv_fwd(f, bt["gbr"], d_last, wp(R(bt["res"])), bt["res"].bias, bt["rb"])
-        emit_conv_fwd_act(f, rows, bt["gb1"], bt["zb0"], wp(R(bt["bc1"])), bt["bc1"].bias, cats[L - 2][..., bt["cb_in"]:],
-                          bt["BN1"], bt["BA1"], resid=bt["rb"] if bt["res"] is not None else d_last)
-        for l in range(L - 2, -1, -1):
-            u = up_state[l]
-            if "zu" in u:
-                emit_conv_fwd_act(f, rows, u["gt"], cats[l], wp(R(u["ct"])), u["ct"].bias, u["zt"], u["NT"], u["AT"])
-                dst = cats[l - 1][..., chans[l - 1]:] if l > 0 else y_out
-                emit_conv_fwd_act(f, rows, u["gu"], u["zt"], wp(R(u["cu"])), u["cu"].bias, dst, u["NU"], u["AU"],
-                                  resid=u["zt"], tanh=(a["tanh_out"] and l == 0))
-            else:                          # top level: the transposed conv leaves act(bn(.)) itself, then the conv-only unit
-                emit_conv_fwd_act(f, rows, u["gt"], cats[l], wp(R(u["ct"])), u["ct"].bias, u["ua"], u["NT"], u["AT"])
-                emit_conv_fwd(f, u["gu"], u["ua"], wp(R(u["cu"])), u["cu"].bias, y_out, resid=u["ua"], tanh=a["tanh_out"])
+            ru, skip, up = blk
+            down = ResidualUnit(self, ru, x)
+            cat = self.E(n, *down.u1.g.out_dhw, up[0].conv.in_channels)
+            x = down.out = cat[..., :chans[l]]
+            self.downs.append(down)
+            self.cats.append(cat)
+            up_mods.append(up)
+            blk = skip.submodule
+        assert not isinstance(blk, nn.Sequential), "U-Net depth and its channel list disagree"
+        self.bottom = ResidualUnit(self, blk, x, self.cats[-1][..., chans[L - 2]:])
+        self.ups = [UpLevel(self, up_mods[l], self.cats[l], self.cats[l - 1][..., chans[l - 1]:] if l > 0 else y_out,
+                            tanh=tanh_out and l == 0) for l in range(L - 1)]
+        # Accumulator statistics (csrc/norm_fold.h) for the norm layers whose producing kernel can leave them and
+        # whose first consumer can fold them: no finalize launch for those.  (nb, accumulator row width)
+        self.acc_wants = []
+        if training and not instance and _ACC_STATS:
+            self.acc_wants = [w for unit in self.downs + [self.bottom] + self.ups for w in unit.acc_wants()]
+
+    def E(self, *shape):
+        return torch.empty(*shape, device=self.dev)
+
+    def grad_scratch(self) -> GradScratch:
+        """One set of gradient buffers for emit(): their shapes follow from the architecture and the input shape alone,
+        so the U-Nets of a generator share sets (GeneratorPlan)."""
+        like = torch.empty_like
+        return GradScratch(gcat=[like(c) for c in self.cats], up=[(like(u.t.z), like(u.t.z)) for u in self.ups],
+                           ru=[(like(r.u1.z), like(r.u1.z)) for r in self.downs + [self.bottom]])
 
     # programs are emitted after the shared scratch has been sized and allocated
-    def emit(self):
-        a = self._build_args
-        down_state, up_state = self._late
-        store, scratch = self.store, self.scratch
-        part, ws = scratch.partials, scratch.ws
-        f, b = self.fwd, self.bwd
-        R, prelu_pro = a["R"], a["prelu_pro"]
-        chans, L, sizes, cats = a["chans"], a["L"], a["sizes"], a["cats"]
-        x_in, y_out = a["x_in"], a["y_out"]
-        tr = self.training
-        bt = a["bottom"]
-        wp, wpb = store.wp, store.wp_bwd
+    def emit(self, gs: Optional[GradScratch] = None, g_out=None, g_x=None):
+        """gs: the gradient scratch set of this backward; g_out = dL/dy; g_x: where dL/dx goes, None if unwanted."""
+        units, chans = self.downs + [self.bottom], self.chans
         if self.eval_fused:
-            self._emit_eval(a, down_state, up_state)
+            # Eval-mode inference program (SURVEY.md section 8(f) row N1; code/GAN/inferrence.py:97-110): every conv emits
+            # its ACTIVATED output -- running-statistics BatchNorm, PReLU, bias and the unit's residual add in its
+            # epilogue -- so no norm_act_add launch and no normalise-on-load prologue remain: 15 launches per U-Net
+            # instead of 22, all of them convs.  Same buffers as the training plan (a raw-output buffer now holds the
+            # activation).
+            for unit in units + self.ups[::-1]:
+                unit.emit_forward_eval()
             return
-
-        # ================= forward =================
-        for l in range(L - 1):
-            s = down_state[l]
-            (cv0, N0, A0), (cv1, N1, A1) = s["ru"].units
-            if s["gf"] is not None:
-                fr = s["fr"]
-                emit_conv_fwd_norm(f, s["gf"], s["xin"], store.wp_fused(fr), store.bias_fused(fr), s["zr"], s["nb0"], N0,
-                                   part, training=tr, eval_norms=self.eval_norms, c_norm=s["c"])
-            else:
-                emit_conv_fwd_norm(f, s["g0"], s["xin"], wp(R(cv0)), cv0.bias, s["z0"], s["nb0"], N0, part, training=tr,
-                                   eval_norms=self.eval_norms)
-                # (the residual conv could run on the side stream; measured: the event hand-offs cost more
-                #  than the ~20 us kernels they would overlap -- G forward 4.42 -> 4.56 ms)
-                emit_conv_fwd(f, s["gr"], s["xin"], wp(R(s["ru"].res)), s["ru"].res.bias, s["r"])
-            emit_conv_fwd_norm(f, s["g1"], s["z0"], wp(R(cv1)), cv1.bias, s["z1"], s["nb1"], N1, part,
-                               pro=prelu_pro(s["nb0"], A0), training=tr, eval_norms=self.eval_norms,
-                               fold=s["nb0"].fold())
-            emit_norm_act_add(f, s["z1"], prelu_pro(s["nb1"], A1), s["r"], None, cats[l][..., :s["c"]],
-                              fold=s["nb1"].fold())
-        d_last = cats[L - 2][..., :bt["cb_in"]]
-        emit_conv_fwd_norm(f, bt["gb0"], d_last, wp(R(bt["bc0"])), bt["bc0"].bias, bt["zb0"], bt["nbb0"], bt["BN0"],
-                           part, training=tr, eval_norms=self.eval_norms)
-        if bt["res"] is not None:
-            emit_conv_fwd(f, bt["gbr"], d_last, wp(R(bt["res"])), bt["res"].bias, bt["rb"])
-        emit_conv_fwd_norm(f, bt["gb1"], bt["zb0"], wp(R(bt["bc1"])), bt["bc1"].bias, bt["zb1"], bt["nbb1"],
-                           bt["BN1"], part, pro=prelu_pro(bt["nbb0"], bt["BA0"]), training=tr, eval_norms=self.eval_norms,
-                           fold=bt["nbb0"].fold())
-        emit_norm_act_add(f, bt["zb1"], prelu_pro(bt["nbb1"], bt["BA1"]), bt["rb"] if bt["res"] is not None else d_last,
-                          None, cats[L - 2][..., bt["cb_in"]:], fold=bt["nbb1"].fold())
-        for l in range(L - 2, -1, -1):
-            u = up_state[l]
-            emit_conv_fwd_norm(f, u["gt"], cats[l], wp(R(u["ct"])), u["ct"].bias, u["zt"], u["nbt"], u["NT"], part,
-                               training=tr, eval_norms=self.eval_norms)
-            pt = prelu_pro(u["nbt"], u["AT"])
-            if "zu" in u:
-                emit_conv_fwd_norm(f, u["gu"], u["zt"], wp(R(u["cu"])), u["cu"].bias, u["zu"], u["nbu"], u["NU"], part,
-                                   pro=pt, training=tr, eval_norms=self.eval_norms, fold=u["nbt"].fold())
-                dst = cats[l - 1][..., chans[l - 1]:] if l > 0 else y_out
-                emit_norm_act_add(f, u["zu"], prelu_pro(u["nbu"], u["AU"]), u["zt"], pt, dst,
-                                  tanh=(a["tanh_out"] and l == 0), fold=u["nbu"].fold())
-            else:
-                # top level: conv-only residual unit on the materialised act(bn(zt))
-                emit_norm_act_add(f, u["zt"], pt, None, None, u["ua"], fold=u["nbt"].fold())
-                emit_conv_fwd(f, u["gu"], u["ua"], wp(R(u["cu"])), u["cu"].bias, y_out, resid=u["ua"],
-                              tanh=a["tanh_out"])
-        if not a["want_backward"]:
+        for unit in units + self.ups[::-1]:
+            unit.emit_forward()
+        if not self.want_backward:
             return
-
-        # ================= backward =================
         # Weight gradients run on the side stream (lane 1), all of them AFTER this U-Net's norm-backward /
         # backward-data chain has been enqueued: they only read (activation, dz) pairs that nothing
         # rewrites inside this U-Net's backward, and write parameter gradients / the split-K workspace
@@ -1461,75 +1458,17 @@ class UNetPlan:
         # and rotates).  `wait_mark` orders this U-Net after the side-stream work of the U-Net that
         # used the same set last.
         own_mark, wait_mark = self._marks
-        bw = Program()
+        b = self.bwd
         if wait_mark is not None:
             b.wait(wait_mark)
-        G = a["gbufs"]                       # shared gradient scratch (see GeneratorPlan)
-        gv = store.grad_view
-        g_out, g_x = G["g_out"], G["g_x"]
-        # ---- up path, top to bottom of the U ----
-        for l in range(0, L - 1):
-            u = up_state[l]
-            pt = prelu_pro(u["nbt"], u["AT"])
-            g_u = g_out if l == 0 else G["gcat"][l - 1][..., chans[l - 1]:]
-            if "zu" in u:
-                dzu, gta = G["dzu"][l], G["gta"][l]
-                emit_norm_bwd(b, g_u, u["zu"], u["nbu"], prelu_pro(u["nbu"], u["AU"]), dzu, part,
-                              gv(u["NU"].weight), gv(u["NU"].bias), gv(u["AU"].weight))
-                emit_conv_wgrad(bw, u["gu"], u["zt"], dzu, gv(u["cu"].weight), ws, pro=pt, dbias=gv(u["cu"].bias), lane=1)
-                emit_conv_dgrad(b, u["gu"], dzu, wpb(R(u["cu"])), gta, resid=g_u)
-            else:
-                gta = G["gta"][l]
-                emit_conv_wgrad(bw, u["gu"], u["ua"], g_u, gv(u["cu"].weight), ws, dbias=gv(u["cu"].bias), lane=1)
-                emit_conv_dgrad(b, u["gu"], g_u, wpb(R(u["cu"])), gta, resid=g_u)
-            emit_norm_bwd(b, gta, u["zt"], u["nbt"], pt, gta, part, gv(u["NT"].weight), gv(u["NT"].bias),
-                          gv(u["AT"].weight))
-            emit_bias_grad(b, gta, gv(u["ct"].bias), part)
-            emit_conv_wgrad(bw, u["gt"], cats[l], gta, gv(u["ct"].weight), ws, lane=1)
-            emit_conv_dgrad(b, u["gt"], gta, wpb(R(u["ct"])), G["gcat"][l])
-        # ---- bottom ----
-        gcat_last = G["gcat"][L - 2]
-        g_b = gcat_last[..., bt["cb_in"]:]
-        gd_last = gcat_last[..., :bt["cb_in"]]
-        d_last = cats[L - 2][..., :bt["cb_in"]]
-        dzb1, gab0 = G["dzb1"], G["gab0"]
-        emit_norm_bwd(b, g_b, bt["zb1"], bt["nbb1"], prelu_pro(bt["nbb1"], bt["BA1"]), dzb1, part,
-                      gv(bt["BN1"].weight), gv(bt["BN1"].bias), gv(bt["BA1"].weight))
-        emit_conv_wgrad(bw, bt["gb1"], bt["zb0"], dzb1, gv(bt["bc1"].weight), ws, pro=prelu_pro(bt["nbb0"], bt["BA0"]),
-                        dbias=gv(bt["bc1"].bias), lane=1)
-        emit_conv_dgrad(b, bt["gb1"], dzb1, wpb(R(bt["bc1"])), gab0)
-        emit_norm_bwd(b, gab0, bt["zb0"], bt["nbb0"], prelu_pro(bt["nbb0"], bt["BA0"]), gab0, part,
-                      gv(bt["BN0"].weight), gv(bt["BN0"].bias), gv(bt["BA0"].weight))
-        emit_conv_wgrad(bw, bt["gb0"], d_last, gab0, gv(bt["bc0"].weight), ws, dbias=gv(bt["bc0"].bias), lane=1)
-        emit_conv_dgrad(b, bt["gb0"], gab0, wpb(R(bt["bc0"])), gd_last, resid=gd_last)
-        if bt["res"] is not None:
-            emit_conv_wgrad(bw, bt["gbr"], d_last, g_b, gv(bt["res"].weight), ws, dbias=gv(bt["res"].bias), lane=1)
-            emit_conv_dgrad(b, bt["gbr"], g_b, wpb(R(bt["res"])), gd_last, resid=gd_last)
-        else:
-            emit_norm_act_add(b, g_b, None, gd_last, None, gd_last)           # identity residual: gd_last += g_b
-        # ---- down path, bottom to top ----
-        for l in range(L - 2, -1, -1):
-            s = down_state[l]
-            (cv0, N0, A0), (cv1, N1, A1) = s["ru"].units
-            g_d = G["gcat"][l][..., :s["c"]]
-            dz1, ga0 = G["dz1"][l], G["ga0"][l]
-            emit_norm_bwd(b, g_d, s["z1"], s["nb1"], prelu_pro(s["nb1"], A1), dz1, part, gv(N1.weight), gv(N1.bias),
-                          gv(A1.weight))
-            emit_conv_wgrad(bw, s["g1"], s["z0"], dz1, gv(cv1.weight), ws, pro=prelu_pro(s["nb0"], A0),
-                            dbias=gv(cv1.bias), lane=1)
-            emit_conv_dgrad(b, s["g1"], dz1, wpb(R(cv1)), ga0)
-            emit_norm_bwd(b, ga0, s["z0"], s["nb0"], prelu_pro(s["nb0"], A0), ga0, part, gv(N0.weight), gv(N0.bias),
-                          gv(A0.weight))
-            emit_conv_wgrad(bw, s["g0"], s["xin"], ga0, gv(cv0.weight), ws, dbias=gv(cv0.bias), lane=1)
-            emit_conv_wgrad(bw, s["gr"], s["xin"], g_d, gv(s["ru"].res.weight), ws, dbias=gv(s["ru"].res.bias), lane=1)
-            if l > 0:
-                tgt = G["gcat"][l - 1][..., :chans[l - 1]]
-                emit_conv_dgrad(b, s["g0"], ga0, wpb(R(cv0)), tgt, resid=tgt)
-                emit_conv_dgrad(b, s["gr"], g_d, wpb(R(s["ru"].res)), tgt, resid=tgt)
-            elif g_x is not None:
-                emit_conv_dgrad(b, s["g0"], ga0, wpb(R(cv0)), g_x)
-                emit_conv_dgrad(b, s["gr"], g_d, wpb(R(s["ru"].res)), g_x, resid=g_x)
-        b.extend(bw)
+        gskip = [g[..., :c] for g, c in zip(gs.gcat, chans)]      # dL/d(down level l's output), cat_l's first half
+        gsub = [g[..., c:] for g, c in zip(gs.gcat, chans)]       # dL/d(what the submodule appended to cat_l)
+        for l, up in enumerate(self.ups):                         # up path, top to bottom of the U
+            up.emit_backward(g_out if l == 0 else gsub[l - 1], *gs.up[l], gs.gcat[l])
+        self.bottom.emit_backward(gsub[-1], *gs.ru[-1], gskip[-1])
+        for l in range(len(self.downs) - 1, -1, -1):              # down path, bottom to top
+            self.downs[l].emit_backward(gskip[l], *gs.ru[l], gskip[l - 1] if l > 0 else g_x, accumulate_first=l > 0)
+        b.extend(self.side)
         if own_mark is not None:
             b.mark(own_mark)
         else:
@@ -1551,47 +1490,18 @@ class GeneratorPlan:
         self.n, self.dhw, self.dims = n, dhw, dims
         self.store = store
         E = lambda *shape: torch.empty(*shape, device=dev)
-        self.acts = [E(n, *dhw, 1) for _ in range(len(unets) + 1)]   # x0 .. y
+        nU = len(unets)
+        self.acts = [E(n, *dhw, 1) for _ in range(nU + 1)]   # x0 .. y
         self.x_in, self.y = self.acts[0], self.acts[-1]
         self.scratch = Scratch(dev)
         self.want_backward = want_backward
-        chans = list(unets[0].channels)
-        L = len(chans)
-        gb = None
-        if want_backward:
-            # gradient scratch shared by all U-Nets (their backwards run one after another)
-            sizes = [dhw]
-            for l in range(L - 1):
-                sizes.append(tuple((s + 1) // 2 if i >= 3 - dims else s for i, s in enumerate(sizes[-1])))
-            in_ch = [1] + chans[:L - 2]
-            sub_out = [chans[l] for l in range(L - 2)] + [chans[L - 1]]
-            def grad_scratch():
-                return dict(
-                    gcat=[E(n, *sizes[l + 1], chans[l] + sub_out[l]) for l in range(L - 1)],
-                    dzu=[E(n, *sizes[l], in_ch[l]) for l in range(L - 1)],
-                    gta=[E(n, *sizes[l], in_ch[l]) for l in range(L - 1)],
-                    dz1=[E(n, *sizes[l + 1], chans[l]) for l in range(L - 1)],
-                    ga0=[E(n, *sizes[l + 1], chans[l]) for l in range(L - 1)],
-                    dzb1=E(n, *sizes[L - 1], chans[L - 1]), gab0=E(n, *sizes[L - 1], chans[L - 1]))
-            # two sets, rotated: U-Net u's weight gradients (side stream) still read set u % 2 while
-            # U-Net u-1's chain fills the other one
-            gb = [grad_scratch(), grad_scratch()]
-            self.g_acts = [E(n, *dhw, 1) for _ in range(len(unets) + 1)]   # dL/d(acts[u]); never shared
-            self.g_y = E(n, *dhw, 1)          # upstream gradient dL/dy is copied here
-        self.unet_plans: List[UNetPlan] = []
-        nU = len(unets)
         marks = [Mark() for _ in range(nU)]
-        for u, unet in enumerate(unets):
-            g = None
-            if want_backward:
-                g = dict(gb[u % 2])
-                g["g_out"] = self.g_acts[u + 1]
-                g["g_x"] = self.g_acts[u] if (u > 0 or want_input_grad) else None
-            with geom_defaults(mm_bf16=mm_bf16):
-                self.unet_plans.append(UNetPlan(unet, store, n, spatial, self.acts[u], self.acts[u + 1],
-                                                tanh_out=(u == nU - 1), instance=instance, want_backward=want_backward,
-                                                gbufs=g, scratch=self.scratch, training=training,
-                                                own_mark=marks[u], wait_mark=marks[u + 2] if u + 2 < nU else None))
+        with geom_defaults(mm_bf16=mm_bf16):
+            self.unet_plans: List[UNetPlan] = [
+                UNetPlan(unet, store, n, spatial, self.acts[u], self.acts[u + 1], tanh_out=(u == nU - 1),
+                         instance=instance, want_backward=want_backward, scratch=self.scratch, training=training,
+                         own_mark=marks[u], wait_mark=marks[u + 2] if u + 2 < nU else None)
+                for u, unet in enumerate(unets)]
         self.scratch.alloc()
         wants = [w for p in self.unet_plans for w in p.acc_wants]
         self.acc_all = None
@@ -1603,8 +1513,17 @@ class GeneratorPlan:
                 sz = ops.ACC_REPLICAS * ops.ACC_WORDS * cw
                 nb.acc = self.acc_all[off:off + sz]
                 off += sz
-        for p in self.unet_plans:
-            p.emit()
+        if want_backward:
+            # gradient scratch shared by all U-Nets (their backwards run one after another); two sets, rotated:
+            # U-Net u's weight gradients (side stream) still read set u % 2 while U-Net u-1's chain fills the other one
+            gsets = [self.unet_plans[0].grad_scratch(), self.unet_plans[0].grad_scratch()]
+            self.g_acts = [E(n, *dhw, 1) for _ in range(nU + 1)]   # dL/d(acts[u]); never shared
+            self.g_y = E(n, *dhw, 1)          # upstream gradient dL/dy is copied here
+            for u, p in enumerate(self.unet_plans):
+                p.emit(gsets[u % 2], self.g_acts[u + 1], self.g_acts[u] if (u > 0 or want_input_grad) else None)
+        else:
+            for p in self.unet_plans:
+                p.emit()
         self.fwd = Program()
         store.emit_pack(self.fwd)
         if self.acc_all is not None:      # one memset for every norm layer of the forward

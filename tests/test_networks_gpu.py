@@ -55,20 +55,29 @@ def _check_param_grads(ours, ref, rtol=2e-3):
     assert len(flipped) <= max(2, len(ref_p) // 10), flipped       # ... and only a few tensors may need it
 
 
-@pytest.mark.parametrize("dims,spatial,n,norm,nblocks", [
-    (2, (32, 48), 2, "batch", 2),
-    (2, (64, 64), 3, "batch", 6),       # the reference's 6-U-Net cascade
-    (2, (32, 32), 2, "instance", 2),    # north_star's InstanceNorm variant (MONAI Norm.INSTANCE: no gamma / beta)
-    (2, (32, 32), 2, "instance_affine", 2),
-    (3, (16, 16, 24), 2, "batch", 2),   # the reference's real (3-D) graph
-])
-def test_generator_forward_backward_matches_oracle(dims, spatial, n, norm, nblocks):
+_IDENTITY_BOTTOM = dict(channels=(8, 16, 16), strides=(2, 2))   # equal last two channel counts: the bottom unit adds its input
+
+
+@pytest.mark.parametrize("dims,spatial,n,norm,nblocks,arch", [
+    (2, (32, 48), 2, "batch", 2, {}),
+    (2, (64, 64), 3, "batch", 6, {}),       # the reference's 6-U-Net cascade
+    (2, (32, 32), 2, "instance", 2, {}),    # north_star's InstanceNorm variant (MONAI Norm.INSTANCE: no gamma / beta)
+    (2, (32, 32), 2, "instance_affine", 2, {}),
+    (3, (16, 16, 24), 2, "batch", 2, {}),   # the reference's real (3-D) graph
+    (2, (16, 24), 2, "batch", 3, _IDENTITY_BOTTOM),
+    (3, (8, 8, 12), 2, "batch", 3, _IDENTITY_BOTTOM),
+], ids=[  # the first five keep the names they had before `arch` joined the parameters
+    "2-spatial0-2-batch-2", "2-spatial1-3-batch-6", "2-spatial2-2-instance-2", "2-spatial3-2-instance_affine-2",
+    "3-spatial4-2-batch-2", "2d-identity-bottom", "3d-identity-bottom"])
+def test_generator_forward_backward_matches_oracle(dims, spatial, n, norm, nblocks, arch):
     R = _oracle()
     from mpgan_amd.networks import CasNetGenerator
-    ref = R.CasNetGenerator((1, *spatial), nblocks, dimensions=dims, norm=norm)
+    ref = R.CasNetGenerator((1, *spatial), nblocks, dimensions=dims, norm=norm, **arch)
     R.closed_form_fill_(ref)
     ref.train()
-    ours = CasNetGenerator((1, *spatial), nblocks, dimensions=dims, norm=norm)
+    if arch:
+        assert isinstance(ref.model[0].model[1].submodule[1].submodule.residual, torch.nn.Identity)   # the bottom unit
+    ours = CasNetGenerator((1, *spatial), nblocks, dimensions=dims, norm=norm, **arch)
     ours.load_state_dict(ref.state_dict())
     ours.cuda().train()
     gen = torch.Generator().manual_seed(7)

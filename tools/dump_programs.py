@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""The frozen launch lists of the discriminator plans, fp32 and bf16 storage, in a form that can be diffed across commits
-(development aid: builds the plans, launches nothing).
+"""The frozen launch lists of the discriminator plans, fp32 and bf16 storage, and of the generator's plans, in a form that
+can be diffed across commits (development aid: builds the plans, launches nothing).
 
     python tools/dump_programs.py [--storage {bf16,f32,both}]        # variant A and B, every program
     python tools/dump_programs.py --tree DIR                         # the same of another built checkout (the parent commit)
@@ -8,6 +8,10 @@
     python tools/dump_programs.py --conditional [--head markovian]   # variant A conditional: D(cat(img, cond)), DESIGN.md 7e
     MPGAN_FUSE_BWD_STATS_BF16=1 python tools/dump_programs.py        # bf16 variant A train with the fused norm-backward sums
     MPGAN_DBG_NO_FUSE_BWD_STATS=1 python tools/dump_programs.py      # fp32 variant A train without them
+    python tools/dump_programs.py --net generator                    # GeneratorPlan.fwd / .bwd of GENERATOR_CASES, 3 U-Nets each
+    MPGAN_DBG_NO_FUSE_DOWN=1 python tools/dump_programs.py --net generator   # ... first conv and residual conv as two launches
+    MPGAN_ACC_STATS=1 python tools/dump_programs.py --net generator  # ... with accumulator statistics (no finalize launches)
+    python tools/dump_programs.py ... --digest                       # one line per program: call count, sha256 of its lines
 
 One line per call: index, name, desc, tag, lane, the C entry and its arguments.  Every pointer (an argument or a structure
 field the C signature declares as one) is replaced by an ordinal in order of first appearance within its plan (p0, p1,
@@ -15,6 +19,7 @@ field the C signature declares as one) is replaced by an ordinal in order of fir
 Needs an MI355X only because the plans allocate their tensors there."""
 import argparse
 import ctypes as C
+import hashlib
 import os
 import sys
 
@@ -25,13 +30,16 @@ _ap.add_argument("--head", default="linear", choices=("linear", "markovian"),
                  help="variant A's head; markovian lists variant A alone, at shapes whose last feature map is >= 4")
 _ap.add_argument("--conditional", action="store_true",
                  help="variant A as the conditional (pix2pix) discriminator, listed alone: conv1 over two input planes")
+_ap.add_argument("--net", default="discriminator", choices=("discriminator", "generator"),
+                 help="generator lists the CasNet generator's plans alone (the other options do not apply to it)")
+_ap.add_argument("--digest", action="store_true", help="one line per program: its call count and the sha256 of its lines")
 _ap.add_argument("--tree", default=HERE, help="a built checkout to import the package from")
 ARGS = _ap.parse_args()
 sys.path.insert(0, os.path.abspath(ARGS.tree))
 
 import torch  # noqa: E402
 from mpgan_amd import engine  # noqa: E402
-from mpgan_amd.networks import Discriminator, PatchDiscriminator  # noqa: E402
+from mpgan_amd.networks import CasNetGenerator, Discriminator, PatchDiscriminator  # noqa: E402
 
 DEV = "cuda"
 # the default keeps the constructor call and the titles of the commits before the option existed (--tree)
@@ -64,7 +72,7 @@ def _value(v, ctype, ords):
 
 
 def dump(title, prog, ords):
-    print(f"== {title}: {len(prog)} calls")
+    lines = []
     for i, (fn, args) in enumerate(prog.calls):
         if fn is None:                                       # stream bookkeeping (join / mark / wait)
             entry, shown = args[0], []
@@ -72,7 +80,11 @@ def dump(title, prog, ords):
             entry = fn.__name__
             types = getattr(fn, "argtypes", None) or [None] * len(args)
             shown = [_value(a, t, ords) for a, t in zip(args, types)]
-        print(f"{i:3d} {prog.names[i]} | {prog.descs[i]} | {prog.tags[i]} | lane{prog.lanes[i]} | {entry}({', '.join(shown)})")
+        lines.append(f"{i:3d} {prog.names[i]} | {prog.descs[i]} | {prog.tags[i]} | lane{prog.lanes[i]} | {entry}({', '.join(shown)})")
+    if ARGS.digest:
+        print(f"== {title}: {len(prog)} calls, sha256 {hashlib.sha256(chr(10).join(lines).encode()).hexdigest()}")
+    else:
+        print("\n".join([f"== {title}: {len(prog)} calls"] + lines))
 
 
 def variant_a(shape, n):
@@ -150,7 +162,41 @@ def variant_b_f32(shape, n):
         dump(f"{name} eval fwd keep_taps={keep}", ev.fwd, Ordinals())
 
 
+# Three U-Nets each, so that the wait_mark rotation of the two gradient scratch sets (u + 2 < nU) appears.
+# (title, spatial, n, CasNetGenerator keywords, GeneratorPlan keywords)
+_TRAIN = dict(want_backward=True, want_input_grad=True, training=True)
+_EVAL = dict(want_backward=False, want_input_grad=False, training=False)
+GENERATOR_CASES = [
+    ("train", (32, 32), 2, {}, _TRAIN),
+    ("train no input grad", (32, 32), 2, {}, dict(_TRAIN, want_input_grad=False)),
+    ("eval", (32, 32), 2, {}, _EVAL),                                         # BatchNorm: the fused-epilogue path
+    ("train", (16, 16, 16), 2, {}, _TRAIN),
+    ("train instance", (16, 16, 16), 2, dict(norm="instance"), _TRAIN),
+    ("train mm_bf16", (16, 16, 16), 2, dict(matmul_dtype="bf16"), _TRAIN),
+    ("eval instance", (16, 16, 16), 1, dict(norm="instance"), _EVAL),         # the non-fused eval path
+    ("train identity bottom", (16, 24), 2, dict(channels=(8, 16, 16), strides=(2, 2)), _TRAIN),
+    ("train variant B", (16, 16, 16), 1, dict(channels=(32, 64, 128, 256), strides=(2, 2, 2, 2)), _TRAIN),
+]
+
+
+def generator(what, shape, n, gen_kw, plan_kw):
+    """One GeneratorPlan of a fresh 3-U-Net generator, through its constructor and `fwd` / `bwd` alone."""
+    torch.manual_seed(0)
+    gen = CasNetGenerator((1,) + shape, 3, dimensions=len(shape), device=DEV, **gen_kw)
+    plan = engine.GeneratorPlan(gen, gen.store, n, shape, instance=gen.norm.startswith("instance"),
+                                mm_bf16=gen.matmul_dtype == "bf16", **plan_kw)
+    ords, name = Ordinals(), f"G {'x'.join(map(str, shape))} n{n} {what}"
+    dump(f"{name} fwd", plan.fwd, ords)
+    if plan_kw["want_backward"]:
+        dump(f"{name} bwd", plan.bwd, ords)
+
+
 def main():
+    if ARGS.net == "generator":
+        print(f"# MPGAN_DBG_NO_FUSE_DOWN={int(not engine._FUSE_DOWN)} MPGAN_ACC_STATS={int(engine._ACC_STATS)}")
+        for case in GENERATOR_CASES:
+            generator(*case)
+        return
     bf16, f32 = ARGS.storage in ("bf16", "both"), ARGS.storage in ("f32", "both")
     if ARGS.head == "markovian" or ARGS.conditional:         # (24^3 ends in a 3^3 feature map: 32^3 here)
         for fn in ([variant_a] if bf16 else []) + ([variant_a_f32] if f32 else []):
