@@ -140,6 +140,12 @@ SIGNATURES = {
     "mpgan_diffaug_forward": (_I, [_P, _I, _I3, _I, _P, _P, _F, _P, _L, _P, _P]),
     "mpgan_diffaug_backward": (_I, [_P, _I, _I3, _I, _P, _P, _P, _L, _P, _P]),
     "mpgan_adam_step": (_I, [_P, _P, _P, _P, _L, C.c_double, C.c_double, C.c_double, C.c_double, _I, _F, _P]),
+    # gradient norm / clipping, Adam with a device coefficient and a weight EMA, buffer EMA (optim_ops.hip)
+    "mpgan_grad_norm_workspace": (_L, [_L]),
+    "mpgan_grad_norm": (_I, [_P, _L, _F, _F, _P, _L, _P, _P]),
+    "mpgan_adam_step_ex": (_I, [_P, _P, _P, _P, _L, C.c_double, C.c_double, C.c_double, C.c_double, _I, _F, _P, _P, _F,
+                                _P]),
+    "mpgan_ema_buffers": (_I, [_P, _I, _L, _F, _P]),
     "mpgan_patch_gather": (_I, [_P, _I, _I3, _P, _I, _I3, _P, _P]),
     "mpgan_patch_scatter_add": (_I, [_P, _I, _I3, _P, _I, _I3, _P, _P]),
     "mpgan_zero_bytes": (_I, [_P, _L, _P]),

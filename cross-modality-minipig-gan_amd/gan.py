@@ -146,14 +146,40 @@ def eval_modes(*modules):
 class FusedAdam(torch.optim.Optimizer):
     """torch.optim.Adam(lr, betas, eps=1e-8, weight_decay=0) as ONE kernel over
     the network's flat parameter buffer (code/GAN/GAN_final.py:306-307).
-    `grad_scale` (e.g. 1/world_size after a sum all-reduce) is applied on load."""
+    `grad_scale` (e.g. 1/world_size after a sum all-reduce) is applied on load.
 
-    def __init__(self, net: _EngineModule, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+    Opt-in, on the same pass over the flat buffer; with none of them given step() is the one
+    ops.adam_step launch:
+      max_grad_norm      torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm) in front of the step: the norm of
+                         grad_scale * flat_grad and its coefficient stay on the device (no host sync)
+      measure_grad_norm  the norm alone; either way `opt.grad_norm` is the device scalar of the pre-clip norm
+      ema                a twin of `net` (same class and layout) whose flat parameters become
+                         lerp(ema, p_new, 1 - ema_decay_at(step, ema_decay, ema_warmup)) inside the Adam kernel, and
+                         whose buffers follow net's in one more launch (num_batches_tracked is copied)"""
+
+    def __init__(self, net: _EngineModule, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, *, max_grad_norm=None,
+                 measure_grad_norm: bool = False, ema: Optional[_EngineModule] = None, ema_decay: float = 0.999,
+                 ema_warmup: bool = True):
+        if max_grad_norm is not None and not float(max_grad_norm) > 0:
+            raise ValueError(f"FusedAdam: max_grad_norm must be > 0 or None, got {max_grad_norm!r}")
+        if ema is not None and not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError(f"FusedAdam: ema_decay must be in [0, 1), got {ema_decay!r}")
+        if ema is not None and ema is net:
+            raise ValueError("FusedAdam: ema must be a twin of net, not net itself")
         self.net = net
         super().__init__(list(net.parameters()), dict(lr=lr, betas=betas, eps=eps))
         self._version = -1
         self.step_count = 0
         self.grad_scale = 1.0
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.measure_grad_norm = bool(measure_grad_norm)
+        self.ema, self.ema_decay, self.ema_warmup = ema, float(ema_decay), bool(ema_warmup)
+        self.grad_norm: Optional[torch.Tensor] = None    # device scalar: the last step's pre-clip norm
+        self._norm_out = self._norm_ws = None
+        self._norm_numel = -1
+        self._ema_key = None
+        self._buf_slots = self._buf_key = self._buf_table = None
+        self._buf_max = 0
 
     def _state(self):
         store = self.net.store
@@ -230,11 +256,98 @@ class FusedAdam(torch.optim.Optimizer):
                 loss = closure()
         store = self._state()
         g = self.param_groups[0]
+        ema_flat = self._ema_flat(store) if self.ema is not None else None     # ValueError before anything is stepped
         self.step_count += 1
-        ops.adam_step(store.flat, store.flat_grad, self.exp_avg, self.exp_avg_sq, g["lr"], g["betas"][0],
-                      g["betas"][1], g["eps"], self.step_count, self.grad_scale)
-        store.touch()                               # the packed weights are stale now
+        want_norm = self.max_grad_norm is not None or self.measure_grad_norm
+        if not want_norm and self.ema is None:
+            ops.adam_step(store.flat, store.flat_grad, self.exp_avg, self.exp_avg_sq, g["lr"], g["betas"][0],
+                          g["betas"][1], g["eps"], self.step_count, self.grad_scale)
+            store.touch()                           # the packed weights are stale now
+            return loss
+        coef = None
+        if want_norm:
+            out2 = self._norm_buffers(store)
+            ops.grad_norm(store.flat_grad, out2, self._norm_ws, self.grad_scale, self.max_grad_norm or 0.0)
+            self.grad_norm = out2[0]
+            coef = out2[1:2] if self.max_grad_norm is not None else None
+        w = 1.0 - ema_decay_at(self.step_count, self.ema_decay, self.ema_warmup) if self.ema is not None else 0.0
+        ops.adam_step_ex(store.flat, store.flat_grad, self.exp_avg, self.exp_avg_sq, g["lr"], g["betas"][0],
+                         g["betas"][1], g["eps"], self.step_count, self.grad_scale, coef=coef, ema=ema_flat,
+                         ema_weight=w)
+        store.touch()
+        if self.ema is not None:
+            table, n, max_elems = self._buffer_table()
+            ops.ema_buffers(table, n, max_elems, w)
+            self.ema.store.touch()                  # the twin's packed weights are stale too
         return loss
+
+    def _norm_buffers(self, store):
+        dev, numel = store.flat.device, store.flat_grad.numel()
+        if self._norm_out is None or self._norm_out.device != dev or self._norm_numel != numel:
+            self._norm_out = torch.zeros(2, device=dev)
+            self._norm_ws = torch.empty(ops.grad_norm_workspace(numel) // 8, device=dev, dtype=torch.float64)
+            self._norm_numel = numel
+        return self._norm_out
+
+    def _ema_flat(self, store):
+        """The twin's flat buffer, after checking (once per pair of stores) that it has the live layout."""
+        estore = self.ema.store
+        k = self._ema_key
+        if k is None or k[0] is not store or k[1] != store.version or k[2] is not estore or k[3] != estore.version:
+            live, twin = list(self.net.parameters()), list(self.ema.parameters())
+            same = (len(live) == len(twin) and estore.flat.numel() == store.flat.numel()
+                    and estore.flat.device == store.flat.device
+                    and all(p.shape == q.shape and store.offset(p) == estore.offset(q) for p, q in zip(live, twin)))
+            if not same:
+                raise ValueError("FusedAdam: the ema module's flat parameter layout differs from the network's "
+                                 f"({estore.flat.numel()} vs {store.flat.numel()} floats): it must be a twin built "
+                                 "with the same constructor arguments")
+            for q in twin:                          # the twin is never trained: no gradient views on it
+                q.grad = None
+            self._ema_key = (store, store.version, estore, estore.version)
+        return estore.flat
+
+    def _buffer_table(self):
+        """Device table [src_ptr, dst_ptr, numel, kind] of ops.ema_buffers over zip(net.buffers(), ema.buffers()),
+        rebuilt when either store or any buffer's storage changed.  The per-step check is one data_ptr() per buffer
+        through the owning modules' _buffers dicts (found once per pair of stores: walking ~1000 modules twice per
+        step would cost more host time than the step's kernels take)."""
+        if self._buf_slots is None or self._buf_slots[0] is not self._ema_key:
+            slots = [[(m._buffers, k) for m in net.modules() for k, t in m._buffers.items() if t is not None]
+                     for net in (self.net, self.ema)]
+            if len(slots[0]) != len(slots[1]):
+                raise ValueError(f"FusedAdam: the ema module has {len(slots[1])} buffers, the network {len(slots[0])}")
+            self._buf_slots = (self._ema_key, slots[0], slots[1])
+            self._buf_key = None
+        live = [d[k] for d, k in self._buf_slots[1]]
+        twin = [d[k] for d, k in self._buf_slots[2]]
+        key = [t.data_ptr() for t in live] + [t.data_ptr() for t in twin]
+        if key != self._buf_key:
+            rows = []
+            for a, b in zip(live, twin):
+                if a.shape != b.shape or a.dtype != b.dtype or not (a.is_contiguous() and b.is_contiguous()):
+                    raise ValueError(f"FusedAdam: buffer mismatch between the network and its ema twin: "
+                                     f"{tuple(a.shape)} {a.dtype} vs {tuple(b.shape)} {b.dtype}")
+                if a.dtype not in (torch.float32, torch.int64):
+                    raise ValueError(f"FusedAdam: no EMA for a buffer of dtype {a.dtype}")
+                if a.numel() > 0:
+                    rows.append([a.data_ptr(), b.data_ptr(), a.numel(), 0 if a.dtype == torch.float32 else 1])
+            self._buf_table = (torch.tensor(rows, dtype=torch.int64, device=self.net.store.flat.device)
+                               if rows else None)
+            self._buf_max = max((r[2] for r in rows), default=0)
+            self._buf_key = key
+        n = 0 if self._buf_table is None else self._buf_table.shape[0]
+        return self._buf_table, n, self._buf_max
+
+
+def ema_decay_at(step: int, decay: float, warmup: bool = True) -> float:
+    """The EMA decay of optimiser step `step` (1-based): min(decay, (1 + t) / (10 + t)) with t = step - 1 when
+    `warmup` is set (0.1 at the first step, so an average started from the initial weights forgets them quickly),
+    else `decay`."""
+    if not warmup:
+        return float(decay)
+    t = max(int(step) - 1, 0)
+    return min(float(decay), (1.0 + t) / (10.0 + t))
 
 
 # --------------------------------------------------------------------------
@@ -244,11 +357,16 @@ class _HParams(types.SimpleNamespace):
     """GAN.hparams.  `adv_loss` reads "bce" unless the constructor was given another objective, and only then is it an
     entry of vars(hparams): a default GAN lists exactly the hyper-parameters it listed before the option existed.
     `conditional` likewise reads False unless the constructor was given True, and `diff_augment` "" (with
-    `diff_augment_fill` 0.0) unless it was given a policy."""
+    `diff_augment_fill` 0.0) unless it was given a policy, and `ema_decay` 0.0 / `ema_warmup` True / `grad_clip` 0.0 /
+    `log_grad_norm` False unless the constructor was given another value."""
     adv_loss = "bce"
     conditional = False
     diff_augment = ""
     diff_augment_fill = 0.0
+    ema_decay = 0.0
+    ema_warmup = True
+    grad_clip = 0.0
+    log_grad_norm = False
 
 
 class GAN(nn.Module):
@@ -263,7 +381,8 @@ class GAN(nn.Module):
                  n_unet_blocks: int = 6, unet_channels=(16, 32, 64, 128), unet_strides=(2, 2, 2), device="cuda",
                  storage_dtype: str = "f32", mi_weight: float = 0.0, mi_bins: int = 23,
                  ssim_weight: float = 0.0, d_head: str = "linear", adv_loss: str = "bce", conditional: bool = False,
-                 diff_augment: str = "", diff_augment_fill: float = 0.0, **kwargs):
+                 diff_augment: str = "", diff_augment_fill: float = 0.0, ema_decay: float = 0.0,
+                 ema_warmup: bool = True, grad_clip: float = 0.0, log_grad_norm: bool = False, **kwargs):
         super().__init__()
         if adv_loss not in ADV_LOSSES:
             raise ValueError(f"adv_loss must be one of {ADV_LOSSES}, got {adv_loss!r}")
@@ -271,6 +390,10 @@ class GAN(nn.Module):
             raise ValueError(f"mi_weight must be >= 0, got {mi_weight!r}")
         if ssim_weight < 0:
             raise ValueError(f"ssim_weight must be >= 0, got {ssim_weight!r}")
+        if not 0.0 <= ema_decay < 1.0:
+            raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay!r}")
+        if not grad_clip >= 0:
+            raise ValueError(f"grad_clip must be >= 0, got {grad_clip!r}")
         aug_ops = parse_policy(diff_augment)         # ValueError on an unknown policy word, before anything is built
         if dimensions is None:
             dimensions = 3 if depth is not None else 2
@@ -283,6 +406,10 @@ class GAN(nn.Module):
         if aug_ops:
             self.hparams.diff_augment = str(diff_augment)
             self.hparams.diff_augment_fill = float(diff_augment_fill)
+        for name, value in (("ema_decay", float(ema_decay)), ("ema_warmup", bool(ema_warmup)),
+                            ("grad_clip", float(grad_clip)), ("log_grad_norm", bool(log_grad_norm))):
+            if value != getattr(_HParams, name):
+                setattr(self.hparams, name, value)
         data_shape = (channels, width, height) + ((depth,) if dimensions == 3 else ())
         # storage_dtype="bf16" is config C5: the discriminator stores its activations in bf16 and the generator's
         # matrix products take bf16 operands (fp32 storage: its launches are matrix-bound, not byte-bound)
@@ -295,6 +422,18 @@ class GAN(nn.Module):
         self.discriminator = Discriminator(data_shape, dimensions=dimensions, device=device,
                                            storage_dtype=storage_dtype, head=d_head,
                                            output="prob" if adv_loss == "bce" else "logit", conditional=conditional)
+        # ema_decay > 0: the averaged generator (the one to score and ship), a twin that opt_g's step
+        # writes; it stays in eval mode, takes no gradient, and its keys are generator_ema.*.  With the default 0.0
+        # there is no module, no state_dict key and no launch.  (Built last: the live networks draw the same initial
+        # weights from a seed with or without it.)
+        self.generator_ema = None
+        if ema_decay > 0:
+            self.generator_ema = CasNetGenerator(data_shape, n_unet_blocks, dimensions=dimensions, norm=norm,
+                                                 channels=unet_channels, strides=unet_strides, device=device,
+                                                 matmul_dtype="bf16" if storage_dtype == "bf16" else "f32")
+            self.generator_ema.requires_grad_(False)
+            self.generator_ema.eval()
+            self.reset_ema()
         # opt-in auxiliary generator loss (not in the reference's trainer): mi_weight * (-MI(G(t1w), t2w)) from Parzen
         # windows over the tanh output's range; with the default 0 no launch and no logged name is added
         self.mi_weight = float(mi_weight)
@@ -312,6 +451,18 @@ class GAN(nn.Module):
 
     def forward(self, x):
         return self.generator(x)
+
+    def reset_ema(self):
+        """Restart the average from the live generator: its weights and buffers copied into generator_ema."""
+        if self.generator_ema is None:
+            raise RuntimeError("reset_ema: this GAN was built without ema_decay")
+        self.generator_ema.load_state_dict(self.generator.state_dict())
+
+    def train(self, mode: bool = True):
+        super().train(mode)
+        if self.generator_ema is not None:
+            self.generator_ema.eval()               # the averaged generator is only ever evaluated
+        return self
 
     def adversarial_loss(self, y_hat, y):
         return adversarial_loss(y_hat, y, kind=self.hparams.adv_loss)
@@ -387,7 +538,8 @@ class GAN(nn.Module):
         and discriminator in eval mode (running-statistics BatchNorm) under no_grad -- no parameter, buffer, gradient or
         optimizer state is touched.  Logs and returns val_g_adv_loss, val_g_recon_loss, val_g_loss, val_d_loss as
         device scalars (no host sync); with mi_weight > 0 also val_g_mi_loss and with ssim_weight > 0 also
-        val_g_ssim_loss, which val_g_loss then includes."""
+        val_g_ssim_loss, which val_g_loss then includes; with ema_decay > 0 also val_ema_g_recon_loss, the L1 of
+        generator_ema(t1w) against t2w."""
         t1w_images, t2w_images = batch["t1w"], batch["t2w"]
         with torch.no_grad(), eval_modes(self.generator, self.discriminator):
             generated_imgs = self(t1w_images)
@@ -405,19 +557,25 @@ class GAN(nn.Module):
             real_loss = self.adversarial_loss(d_real, self._labels(d_real, self.hparams.one_sided_label_value))
             fake_loss = self.adversarial_loss(d_fake, self._labels(d_fake, 0.0))
             d_loss = scalar_axpby(real_loss, 0.5, fake_loss, 0.5)
+            if self.generator_ema is not None:
+                ema_recon_loss = self.reconstruction_loss(self.generator_ema(t1w_images), t2w_images)
         out = {"val_g_adv_loss": g_adv_loss, "val_g_recon_loss": g_recon_loss, "val_g_loss": g_loss, "val_d_loss": d_loss}
         if self.mi_loss is not None:
             out["val_g_mi_loss"] = g_mi_loss
         if self.ssim_loss is not None:
             out["val_g_ssim_loss"] = g_ssim_loss
+        if self.generator_ema is not None:
+            out["val_ema_g_recon_loss"] = ema_recon_loss
         for name, value in out.items():
             self.log(name, value)
         return out
 
     def configure_optimizers(self):                 # GAN_final.py:298-308
         h = self.hparams
-        opt_g = FusedAdam(self.generator, lr=h.g_lr, betas=(h.b1, h.b2))
-        opt_d = FusedAdam(self.discriminator, lr=h.d_lr, betas=(h.b1, h.b2))
+        norm_opts = dict(max_grad_norm=h.grad_clip if h.grad_clip > 0 else None, measure_grad_norm=h.log_grad_norm)
+        opt_g = FusedAdam(self.generator, lr=h.g_lr, betas=(h.b1, h.b2), ema=self.generator_ema,
+                          ema_decay=h.ema_decay, ema_warmup=h.ema_warmup, **norm_opts)
+        opt_d = FusedAdam(self.discriminator, lr=h.d_lr, betas=(h.b1, h.b2), **norm_opts)
         return [opt_g, opt_d], []
 
     def fit_batch(self, batch, batch_idx, optimizers) -> Dict[str, torch.Tensor]:
@@ -435,6 +593,8 @@ class GAN(nn.Module):
             if self.ddp is not None:
                 self.ddp.reduce_gradients(nets[idx], opt)
             opt.step()
+            if getattr(opt, "grad_norm", None) is not None:     # clipping or measuring is on: a snapshot of the scalar
+                self.log(("g_grad_norm", "d_grad_norm")[idx], opt.grad_norm.clone())
             for p in other.parameters():
                 p.requires_grad_(True)
         return dict(self.logged)
@@ -492,6 +652,9 @@ def load_reference_checkpoint(model: nn.Module, path: str, strict: bool = False,
                 sd = sub
                 break
     res = model.load_state_dict(sd, strict=strict)
+    if (isinstance(model, GAN) and model.generator_ema is not None
+            and not any(k.startswith("generator_ema.") for k in sd)):
+        model.reset_ema()                           # a checkpoint without an average: start it from the loaded weights
     if optimizers is not None and isinstance(blob, dict) and blob.get("optimizer_states"):
         states = blob["optimizer_states"]
         if len(states) != len(optimizers):

@@ -579,6 +579,66 @@ def adam_step(p, g, m, v, lr, b1, b2, eps, step: int, grad_scale: float = 1.0):
           "adam_step")
 
 
+def _flat_f32(t, what: str, name: str):
+    if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+        raise ValueError(f"{what}: {name} must be a contiguous float32 tensor on the GPU (there is no CPU path), "
+                         f"got {t.dtype} on {t.device}")
+
+
+def grad_norm_workspace(numel: int) -> int:
+    """Bytes of scratch grad_norm needs for numel elements."""
+    need = int(lib().mpgan_grad_norm_workspace(int(numel)))
+    if need < 0:
+        check(-1, "grad_norm_workspace")
+    return need
+
+
+def grad_norm(g, out2, workspace, grad_scale: float = 1.0, max_norm: float = 0.0):
+    """out2[0] = ||g * grad_scale||_2 (fp64 sums), out2[1] = clip_grad_norm_'s coefficient for max_norm (1 when
+    max_norm <= 0); both stay on the device.  workspace: >= grad_norm_workspace(g.numel()) bytes."""
+    _flat_f32(g, "grad_norm", "g")
+    _flat_f32(out2, "grad_norm", "out2")
+    if out2.numel() < 2:
+        raise ValueError(f"grad_norm: out2 holds {out2.numel()} floats, needs 2")
+    if not workspace.is_cuda or not workspace.is_contiguous():
+        raise ValueError("grad_norm: workspace must be a contiguous tensor on the GPU")
+    ws_bytes = workspace.numel() * workspace.element_size()
+    if g.numel() > 0 and ws_bytes < grad_norm_workspace(g.numel()):
+        raise ValueError(f"grad_norm: workspace holds {ws_bytes} bytes, needs {grad_norm_workspace(g.numel())}")
+    check(lib().mpgan_grad_norm(g.data_ptr(), g.numel(), float(grad_scale), float(max_norm), workspace.data_ptr(),
+                                ws_bytes, out2.data_ptr(), _stream()), "grad_norm")
+    return out2
+
+
+def adam_step_ex(p, g, m, v, lr, b1, b2, eps, step: int, grad_scale: float = 1.0, coef=None, ema=None,
+                 ema_weight: float = 0.0):
+    """adam_step with the gradient also multiplied by the device scalar `coef` (grad_norm's out2[1:2]) and, with `ema`,
+    ema = lerp(ema, p_new, ema_weight) written in the same pass."""
+    for name, t in (("p", p), ("g", g), ("m", m), ("v", v)) + ((("ema", ema),) if ema is not None else ()):
+        _flat_f32(t, "adam_step_ex", name)
+        if t.numel() != p.numel():
+            raise ValueError(f"adam_step_ex: size mismatch ({name} has {t.numel()} elements, p {p.numel()})")
+    if coef is not None:
+        _flat_f32(coef, "adam_step_ex", "coef")
+        if coef.numel() != 1:
+            raise ValueError(f"adam_step_ex: coef must hold one float, got {coef.numel()}")
+    check(lib().mpgan_adam_step_ex(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), float(lr),
+                                   float(b1), float(b2), float(eps), int(step), float(grad_scale), _ptr(coef),
+                                   _ptr(ema), float(ema_weight), _stream()), "adam_step_ex")
+
+
+def ema_buffers(table, n_entries: int, max_elems: int, ema_weight: float):
+    """One launch over `table` (int64 [n][4] on the device: src_ptr, dst_ptr, numel, kind): fp32 rows (kind 0) are
+    dst = lerp(dst, src, ema_weight), int64 rows (kind 1) are copied."""
+    if n_entries > 0:
+        if table.dtype != torch.int64 or not table.is_cuda or not table.is_contiguous():
+            raise ValueError("ema_buffers: table must be a contiguous int64 tensor on the GPU")
+        if table.numel() < 4 * n_entries:
+            raise ValueError(f"ema_buffers: table holds {table.numel()} values, needs {4 * n_entries}")
+    check(lib().mpgan_ema_buffers(_ptr(table) if n_entries > 0 else None, int(n_entries), int(max_elems),
+                                  float(ema_weight), _stream()), "ema_buffers")
+
+
 def _i3(v: Sequence[int]):
     return (C.c_int32 * 3)(*[int(x) for x in v])
 

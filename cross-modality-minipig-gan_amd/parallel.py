@@ -26,8 +26,12 @@ class DataParallelGAN:
             self.broadcast_parameters()
 
     def broadcast_parameters(self, src: int = 0):
-        """Identical replicas: rank `src`'s flat parameter buffers and norm buffers."""
-        for net in (self.gan.generator, self.gan.discriminator):
+        """Identical replicas: rank `src`'s flat parameter buffers and norm buffers (the averaged generator's too,
+        when the GAN keeps one)."""
+        nets = [self.gan.generator, self.gan.discriminator]
+        if getattr(self.gan, "generator_ema", None) is not None:
+            nets.append(self.gan.generator_ema)
+        for net in nets:
             dist.broadcast(net.store.flat, src, group=self.pg)
             for b in net.buffers():
                 dist.broadcast(b, src, group=self.pg)

@@ -587,6 +587,35 @@ int mpgan_adam_step(float* p, const float* g, float* m, float* v, int64_t numel,
                     double lr, double b1, double b2, double eps, int32_t step, float grad_scale,
                     void* stream);
 
+/* The step's optional extras (optim_ops.hip); mpgan_adam_step above is the default step and unchanged.
+ *
+ * Global gradient norm and torch.nn.utils.clip_grad_norm_'s coefficient, both left on the device:
+ *   out2[0] = (float)sqrt(sum_i (double)(fl32(g_i * grad_scale))^2)    the product in fp32, as Adam loads it; its
+ *                                                                       square and every sum in fp64
+ *   out2[1] = max_norm > 0 ? min(1, max_norm / (out2[0] + 1e-6f)) : 1   in fp32; a non-finite norm propagates as in torch
+ * Two launches (block partials, then one finalising block), no atomics, a partial count that depends on numel alone:
+ * two runs give the same bits.  16-byte loads when g is 16-byte aligned (scalar tail), element-wise otherwise.
+ * ws: >= mpgan_grad_norm_workspace(numel) bytes, 8-byte aligned.  MPGAN_ERR_INVALID before any launch: numel <= 0, a
+ * null g / ws / out2, a short or misaligned workspace. */
+int64_t mpgan_grad_norm_workspace(int64_t numel);
+int mpgan_grad_norm(const float* g, int64_t numel, float grad_scale, float max_norm, void* ws, int64_t ws_bytes,
+                    float* out2, void* stream);
+/* mpgan_adam_step with, when `coef` (one device float, e.g. out2 + 1 above) is given, the gradient also multiplied by
+ * *coef: gi = g[i] * fl32(grad_scale * *coef), clipping without a host sync.  (The two factors are multiplied first:
+ * a coefficient of exactly 1.0f then changes no bit, whatever grad_scale is.)  With coef == NULL and ema == NULL the
+ * results equal mpgan_adam_step's bit for bit.  When `ema` is given, ema[i] = lerp(ema[i], p_new[i], ema_weight) in torch's form (w < 0.5: e + w*(p-e), else
+ * p - (p-e)*(1-w)) while the new parameter is still in a register; ema_weight = 1 - decay, in [0, 1].
+ * Any numel > 0 and any 4-byte alignment: 16-byte accesses when p, g, m, v (and ema) are all 16-byte aligned. */
+int mpgan_adam_step_ex(float* p, const float* g, float* m, float* v, int64_t numel,
+                       double lr, double b1, double b2, double eps, int32_t step, float grad_scale,
+                       const float* coef /* device, may be NULL */, float* ema /* may be NULL */, float ema_weight,
+                       void* stream);
+/* EMA of a network's buffers into its twin's in one launch.  table: device int64 [n_entries][4] =
+ * {src_ptr, dst_ptr, numel, kind}; kind 0: fp32, dst = lerp(dst, src, ema_weight) as above; kind 1: int64, dst = src
+ * (BatchNorm's num_batches_tracked).  max_elems: the largest numel of the table.  n_entries == 0 returns 0 without a
+ * launch. */
+int mpgan_ema_buffers(const int64_t* table, int32_t n_entries, int64_t max_elems, float ema_weight, void* stream);
+
 /* ---- patch gather / scatter (variant B, test_runs/GAN.py:263-272,313-337) -- */
 /* patches[(b*S+s)][roi^dims] = vol[b][corner+...]; bit-exact copy.
  * corners: device int32 [B*S][3] (z,y,x). */
