@@ -146,3 +146,223 @@ class DiffAugment(nn.Module):
         if cond is None:
             return y
         return y, diff_augment(cond, params, color=False, fill=self.fill)
+
+
+# ---- paired affine augmentation of the training pair itself (csrc/pair_augment.hip) --------------------
+# Not in front of D but on the data: the same random rotation, scale, shift and flips on t1w and t2w, Gaussian noise on
+# the input, so that every term of the generator loss sees a new pair.  Runs under no_grad; there is no backward.
+#
+#     p = sample_affine_params(B, S, rotate=0.3, scale=0.1, shift=0.05, flip=(2,), noise_std=0.05, device=x.device)
+#     t1, t2 = affine_warp(t1w, p.theta, t2w, noise=torch.randn_like(t1w), sigma=p.sigma)
+#     batch = PairAugment(rotate=0.3, noise_std=0.05)(batch)        # the module: one draw, one launch, a new dict
+WARP_MODES = {"constant": ops.WARP_CONSTANT, "border": ops.WARP_BORDER}
+PAIR_KEYS = ("t1w", "t2w")                            # plane 0, plane 1
+
+
+class AffineParams(NamedTuple):
+    """One draw: theta (B, 12) float64, per sample the row-major 3 x 4 (A | t) in (d, h, w) voxel-index order (output
+    voxel p samples the input at A p + t); sigma (B, 2) float32, the noise standard deviation of plane 0 and plane 1."""
+    theta: torch.Tensor
+    sigma: torch.Tensor
+
+
+def _triple(value, ndim: int, what: str):
+    """A number (every axis; for `rotate` in 2-D the in-plane angle) or one entry per axis -> a (d, h, w) triple."""
+    if isinstance(value, (int, float)):
+        vals = [float(value)] * ndim
+    else:
+        vals = [float(v) for v in value]
+        if len(vals) != ndim:
+            raise ValueError(f"{what}: one number or {ndim} of them, got {value!r}")
+    if any(not v >= 0 for v in vals):
+        raise ValueError(f"{what} must be >= 0, got {value!r}")
+    return [0.0] * (3 - ndim) + vals
+
+
+def _check_affine_options(rotate, scale, shift, flip, prob, noise_std, noise_prob, noise_planes, ndim: int):
+    if isinstance(rotate, (int, float)) and ndim == 2:
+        rot = [float(rotate), 0.0, 0.0]               # 2-D: the one angle is the in-plane one, about d
+        if not rot[0] >= 0:
+            raise ValueError(f"rotate must be >= 0, got {rotate!r}")
+    elif ndim == 2:
+        raise ValueError(f"rotate: a 2-D image has one angle, got {rotate!r}")
+    else:
+        rot = _triple(rotate, 3, "rotate")
+    if not 0.0 <= float(scale) < 1.0:
+        raise ValueError(f"scale must be in [0, 1), got {scale!r}")
+    sh = _triple(shift, ndim, "shift")
+    axes = sorted({int(a) % ndim if -ndim <= int(a) < ndim else -1 for a in flip})
+    if axes and axes[0] < 0:
+        raise ValueError(f"flip: axes of a {ndim}-D image, got {tuple(flip)!r}")
+    for name, v in (("prob", prob), ("noise_prob", noise_prob)):
+        if not 0.0 <= float(v) <= 1.0:
+            raise ValueError(f"{name} must be in [0, 1], got {v!r}")
+    if not float(noise_std) >= 0:
+        raise ValueError(f"noise_std must be >= 0, got {noise_std!r}")
+    planes = sorted({int(k) for k in noise_planes})
+    if any(k not in (0, 1) for k in planes):
+        raise ValueError(f"noise_planes: a subset of (0, 1), got {tuple(noise_planes)!r}")
+    return rot, float(scale), sh, [a + 3 - ndim for a in axes], planes
+
+
+def sample_affine_params(n: int, spatial: Sequence[int], *, rotate=0.0, scale: float = 0.0, shift=0.0,
+                         flip: Sequence[int] = (), prob: float = 1.0, noise_std: float = 0.0, noise_prob: float = 1.0,
+                         noise_planes: Sequence[int] = (0,), generator: Optional[torch.Generator] = None,
+                         device="cpu") -> AffineParams:
+    """Draw the parameters of `n` samples of extent `spatial` ((H, W) or (D, H, W)), in pure torch ops on `device` (no host
+    sync).  In (d, h, w) index order, with c = (S - 1) / 2 the centre of the extent (input and output alike):
+        R = R_d R_h R_w,  R_d = [[1,0,0],[0,c,-s],[0,s,c]],  R_h = [[c,0,s],[0,1,0],[-s,0,c]],  R_w = [[c,-s,0],[s,c,0],[0,0,1]]
+        A = F R / s,  t = c - A c + shift
+    rotate: the largest |angle| in radians, one number or (about d, about h, about w); each angle is U[-r, r]; a 2-D
+            image has the one in-plane angle (about d).
+    scale:  a in [0, 1): s = 1 + a U[-1, 1]; s > 1 zooms in.
+    shift:  a fraction f of each extent (one number or one per axis): U[-f S, f S] voxels, continuous.
+    flip:   axes of `spatial` (0 = the first), each reversed with probability 0.5: F = diag(+-1).
+    prob:   a sample keeps its spatial draw with this probability, else it gets exactly (I | 0): a bit copy.
+    noise_std, noise_prob, noise_planes: for each listed plane sigma = noise_std U[0, 1) with probability noise_prob,
+            else 0 (MONAI 0.4's RandGaussianNoise: the std is itself drawn); the other plane's sigma is 0.
+    Draw order, one torch.rand each: rotate (n, 3) (2-D: (n, 1)), scale (n,), shift (n, ndim), flip (n, number of
+    axes), the prob gate (n,) when prob < 1, then sigma (n, number of planes) and its gate (n, number of planes) when
+    noise_prob < 1.  A disabled op (rotate 0, scale 0, shift 0, no flip axis, prob 1 or 0, noise_std 0, noise_prob 1 or
+    0) draws nothing and leaves its neutral entry; with prob 0 no spatial op draws.  In 2-D the d row and column of A are (1, 0, 0) and t_d = 0."""
+    spatial = tuple(int(s) for s in spatial)
+    if len(spatial) not in (2, 3) or min(spatial) < 1:
+        raise ValueError(f"sample_affine_params: spatial must be (H, W) or (D, H, W) with extents >= 1, got {spatial}")
+    ndim = len(spatial)
+    rot, a, sh, axes, planes = _check_affine_options(rotate, scale, shift, flip, prob, noise_std, noise_prob,
+                                                     noise_planes, ndim)
+    device = torch.device(device)
+    kw = dict(generator=generator, device=device, dtype=torch.float64)
+    S = (1,) * (3 - ndim) + spatial
+    first = 3 - ndim
+    zero, one = torch.zeros(n, dtype=torch.float64, device=device), torch.ones(n, dtype=torch.float64, device=device)
+    ang = [zero, zero, zero]
+    live = prob > 0.0                                 # prob 0: no spatial op is drawn at all
+    if live and any(r > 0 for r in rot):
+        u = torch.rand((n, 3 if ndim == 3 else 1), **kw)
+        for k in range(u.shape[1]):
+            ang[k] = (2.0 * u[:, k] - 1.0) * rot[k]
+    s = one
+    if live and a > 0:
+        s = 1.0 + a * (2.0 * torch.rand((n,), **kw) - 1.0)
+    t_shift = [zero, zero, zero]
+    if live and any(f > 0 for f in sh):
+        u = torch.rand((n, ndim), **kw)
+        for k in range(ndim):
+            t_shift[first + k] = (2.0 * u[:, k] - 1.0) * (sh[first + k] * S[first + k])
+    F = [one, one, one]
+    if live and axes:
+        u = torch.rand((n, len(axes)), **kw)
+        for j, k in enumerate(axes):
+            F[k] = torch.where(u[:, j] < 0.5, -one, one)
+    (cd, ch, cw), (sd, sh_, sw) = [torch.cos(x) for x in ang], [torch.sin(x) for x in ang]
+    R = [[ch * cw, -ch * sw, sh_],
+         [cd * sw + sd * sh_ * cw, cd * cw - sd * sh_ * sw, -sd * ch],
+         [sd * sw - cd * sh_ * cw, sd * cw + cd * sh_ * sw, cd * ch]]
+    A = [[F[i] * R[i][j] / s for j in range(3)] for i in range(3)]
+    ctr = [(S[k] - 1) / 2.0 for k in range(3)]
+    t = [ctr[i] - (A[i][0] * ctr[0] + A[i][1] * ctr[1] + A[i][2] * ctr[2]) + t_shift[i] for i in range(3)]
+    if ndim == 2:
+        A[0], t[0] = [one, zero, zero], zero
+        A[1][0], A[2][0] = zero, zero
+    theta = torch.stack([A[i][j] if j < 3 else t[i] for i in range(3) for j in range(4)], 1)
+    if 0.0 < prob < 1.0:
+        identity = torch.eye(3, 4, dtype=torch.float64, device=device).reshape(1, 12)
+        theta = torch.where((torch.rand((n,), **kw) < prob)[:, None], theta, identity)
+    sigma = torch.zeros((n, 2), dtype=torch.float32, device=device)
+    if noise_std > 0 and planes and noise_prob > 0.0:
+        draw = torch.rand((n, len(planes)), **kw) * float(noise_std)
+        if noise_prob < 1.0:
+            draw = torch.where(torch.rand((n, len(planes)), **kw) < noise_prob, draw, torch.zeros_like(draw))
+        for j, k in enumerate(planes):
+            sigma[:, k] = draw[:, j].to(torch.float32)
+    return AffineParams(theta.contiguous(), sigma)
+
+
+def affine_warp(x: torch.Tensor, theta: torch.Tensor, x1: Optional[torch.Tensor] = None, *, out_size=None,
+                mode: str = "border", fill=-1.0, noise=None, sigma: Optional[torch.Tensor] = None):
+    """The trilinear resampling of a (B, 1, *S) fp32 GPU tensor (and of `x1`, under the same map, in the same launch) at
+    c = A p + t per sample, theta (B, 12) float64 = (A | t) in (d, h, w) voxel-index order; returns one tensor, or a pair
+    with `x1`.  out_size: the output's spatial extent (default: the input's).  mode "border" clamps c to the image,
+    "constant" gives a corner outside it the value `fill` (one number, or one per plane).  noise: a field of the
+    output's shape for plane 0, or a pair (field or None, field or None); plane k then gets + sigma[:, k] * noise_k
+    (sigma (B, 2) float32).  Not differentiable: an input that requires grad is refused."""
+    planes = [x] if x1 is None else [x, x1]
+    for t in planes:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError("affine_warp: every tensor must be on the GPU (there is no CPU path)")
+        if t.requires_grad and torch.is_grad_enabled():
+            raise ValueError("affine_warp: not differentiable (an input requires grad); call it under torch.no_grad() "
+                             "or on detached tensors")
+    if mode not in WARP_MODES:
+        raise ValueError(f"affine_warp: mode must be one of {sorted(WARP_MODES)}, got {mode!r}")
+    fills = (float(fill),) * 2 if isinstance(fill, (int, float)) else tuple(float(f) for f in fill)
+    if len(fills) != 2:
+        raise ValueError(f"affine_warp: fill is one number or one per plane, got {fill!r}")
+    noises = [noise, None] if noise is None or isinstance(noise, torch.Tensor) else list(noise)
+    if len(noises) != 2:
+        raise ValueError("affine_warp: noise is one field (plane 0) or a pair")
+    planes = [t.detach().contiguous() for t in planes]
+    out_size = tuple(x.shape[2:]) if out_size is None else tuple(int(s) for s in out_size)
+    if len(out_size) != x.dim() - 2:
+        raise ValueError(f"affine_warp: out_size {out_size} for a {x.dim() - 2}-D image")
+    outs = [torch.empty((x.shape[0], 1, *out_size), dtype=torch.float32, device=x.device) for _ in planes]
+    ops.affine_warp(planes[0], planes[1] if x1 is not None else None, theta, WARP_MODES[mode], fills[0], fills[1],
+                    noises[0], noises[1], sigma, outs[0], outs[1] if x1 is not None else None)
+    return outs[0] if x1 is None else (outs[0], outs[1])
+
+
+class PairAugment(nn.Module):
+    """Random geometric augmentation of a training pair with noise on the input (the reference imports MONAI's
+    RandRotated and RandGaussianNoised, GAN_final.py:35-36, and never wires them in): forward(batch) draws once
+    (sample_affine_params; `generator`: a torch.Generator on the batch's device, or None for torch's global one), warps
+    batch["t1w"] and batch["t2w"] under the same draw in one launch, adds sigma * N(0, 1) to `noise_keys` (the field: one
+    torch.randn of shape (number of noise keys, *t1w.shape) from the same generator, after the parameters; none is
+    drawn when noise_std is 0) and returns a new dict; the other entries pass through.  `.last_params` is the last
+    draw, `.last_noise` its field (or None).  No parameters, no buffers, no gradient."""
+
+    def __init__(self, rotate=0.0, scale: float = 0.0, shift=0.0, flip: Sequence[int] = (), prob: float = 1.0,
+                 noise_std: float = 0.0, noise_prob: float = 1.0, noise_keys: Sequence[str] = ("t1w",),
+                 mode: str = "border", fill: float = -1.0, generator: Optional[torch.Generator] = None):
+        super().__init__()
+        noise_keys = (noise_keys,) if isinstance(noise_keys, str) else tuple(noise_keys)
+        if any(k not in PAIR_KEYS for k in noise_keys):
+            raise ValueError(f"PairAugment: noise_keys must be a subset of {PAIR_KEYS}, got {noise_keys!r}")
+        if mode not in WARP_MODES:
+            raise ValueError(f"PairAugment: mode must be one of {sorted(WARP_MODES)}, got {mode!r}")
+        self.noise_planes = sorted({PAIR_KEYS.index(k) for k in noise_keys})
+        for ndim in (2, 3):                           # ValueError on a value no image could take
+            try:
+                _check_affine_options(rotate, scale, shift, flip, prob, noise_std, noise_prob, self.noise_planes, ndim)
+                break
+            except ValueError:
+                if ndim == 3:
+                    raise
+        self.options = dict(rotate=rotate, scale=float(scale), shift=shift, flip=tuple(flip), prob=float(prob),
+                            noise_std=float(noise_std), noise_prob=float(noise_prob))
+        self.mode, self.fill = mode, float(fill)
+        self.generator = generator
+        self.last_params: Optional[AffineParams] = None
+        self.last_noise: Optional[torch.Tensor] = None
+
+    def extra_repr(self):
+        return ", ".join(f"{k}={v!r}" for k, v in self.options.items()) + f", mode={self.mode!r}, fill={self.fill}"
+
+    def forward(self, batch):
+        t1w, t2w = batch["t1w"], batch["t2w"]
+        with torch.no_grad():
+            p = sample_affine_params(t1w.shape[0], tuple(t1w.shape[2:]), noise_planes=self.noise_planes,
+                                     generator=self.generator, device=t1w.device, **self.options)
+            noise = [None, None]
+            field = None
+            if self.options["noise_std"] > 0 and self.noise_planes:
+                field = torch.randn((len(self.noise_planes), *t1w.shape), generator=self.generator, device=t1w.device,
+                                    dtype=torch.float32)
+                for j, k in enumerate(self.noise_planes):
+                    noise[k] = field[j]
+            self.last_params, self.last_noise = p, field
+            y1, y2 = affine_warp(t1w, p.theta, t2w, mode=self.mode, fill=self.fill, noise=noise,
+                                 sigma=p.sigma if field is not None else None)
+        out = dict(batch)
+        out["t1w"], out["t2w"] = y1, y2
+        return out

@@ -5,6 +5,7 @@ in SURVEY.md Appendix B), every FLOP in HIP kernels.
 from __future__ import annotations
 
 import contextlib
+import inspect
 import re
 import types
 from typing import Dict, List, Optional
@@ -13,7 +14,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .augment import DiffAugment, parse_policy
+from .augment import DiffAugment, PairAugment, parse_policy
 from .losses import GlobalMutualInformationLoss, SSIMLoss
 from .networks import CasNetGenerator, Discriminator, _EngineModule
 
@@ -353,12 +354,24 @@ def ema_decay_at(step: int, decay: float, warmup: bool = True) -> float:
 # --------------------------------------------------------------------------
 # the GAN module
 # --------------------------------------------------------------------------
+def _pair_augment_module(options: Optional[dict]) -> Optional[PairAugment]:
+    """GAN(pair_augment=...): None, or the keywords of augment.PairAugment (its generator is the GAN's aug_generator)."""
+    if options is None:
+        return None
+    known = [k for k in inspect.signature(PairAugment.__init__).parameters if k not in ("self", "generator")]
+    unknown = sorted(set(options) - set(known)) if isinstance(options, dict) else None
+    if unknown is None or unknown:
+        raise ValueError(f"pair_augment: a dict of PairAugment keywords {known}, got {options!r}")
+    return PairAugment(**options)
+
+
 class _HParams(types.SimpleNamespace):
     """GAN.hparams.  `adv_loss` reads "bce" unless the constructor was given another objective, and only then is it an
     entry of vars(hparams): a default GAN lists exactly the hyper-parameters it listed before the option existed.
     `conditional` likewise reads False unless the constructor was given True, and `diff_augment` "" (with
     `diff_augment_fill` 0.0) unless it was given a policy, and `ema_decay` 0.0 / `ema_warmup` True / `grad_clip` 0.0 /
-    `log_grad_norm` False unless the constructor was given another value."""
+    `log_grad_norm` False unless the constructor was given another value, and `pair_augment` None unless it was given
+    the keywords of a PairAugment."""
     adv_loss = "bce"
     conditional = False
     diff_augment = ""
@@ -367,6 +380,7 @@ class _HParams(types.SimpleNamespace):
     ema_warmup = True
     grad_clip = 0.0
     log_grad_norm = False
+    pair_augment = None
 
 
 class GAN(nn.Module):
@@ -382,7 +396,8 @@ class GAN(nn.Module):
                  storage_dtype: str = "f32", mi_weight: float = 0.0, mi_bins: int = 23,
                  ssim_weight: float = 0.0, d_head: str = "linear", adv_loss: str = "bce", conditional: bool = False,
                  diff_augment: str = "", diff_augment_fill: float = 0.0, ema_decay: float = 0.0,
-                 ema_warmup: bool = True, grad_clip: float = 0.0, log_grad_norm: bool = False, **kwargs):
+                 ema_warmup: bool = True, grad_clip: float = 0.0, log_grad_norm: bool = False,
+                 pair_augment: Optional[dict] = None, **kwargs):
         super().__init__()
         if adv_loss not in ADV_LOSSES:
             raise ValueError(f"adv_loss must be one of {ADV_LOSSES}, got {adv_loss!r}")
@@ -395,6 +410,7 @@ class GAN(nn.Module):
         if not grad_clip >= 0:
             raise ValueError(f"grad_clip must be >= 0, got {grad_clip!r}")
         aug_ops = parse_policy(diff_augment)         # ValueError on an unknown policy word, before anything is built
+        pair_module = _pair_augment_module(pair_augment)    # likewise on an unknown keyword or a value out of range
         if dimensions is None:
             dimensions = 3 if depth is not None else 2
         self.hparams = _HParams(latent_dim=latent_dim, g_lr=g_lr, d_lr=d_lr, b1=b1, b2=b2,
@@ -410,6 +426,8 @@ class GAN(nn.Module):
                             ("grad_clip", float(grad_clip)), ("log_grad_norm", bool(log_grad_norm))):
             if value != getattr(_HParams, name):
                 setattr(self.hparams, name, value)
+        if pair_module is not None:
+            self.hparams.pair_augment = dict(pair_augment)
         data_shape = (channels, width, height) + ((depth,) if dimensions == 3 else ())
         # storage_dtype="bf16" is config C5: the discriminator stores its activations in bf16 and the generator's
         # matrix products take bf16 operands (fp32 storage: its launches are matrix-bound, not byte-bound)
@@ -446,6 +464,10 @@ class GAN(nn.Module):
         # for torch's global one (data-parallel runs: every rank seeds its own, or all ranks draw the same parameters)
         self.augment = DiffAugment(diff_augment, fill=diff_augment_fill) if aug_ops else None
         self.aug_generator: Optional[torch.Generator] = None
+        # opt-in augmentation of the training pair itself (augment.PairAugment): fit_batch warps t1w and
+        # t2w under one draw, with noise on the input, before the G step; both steps see that pair.  It draws from
+        # aug_generator too, ahead of the step's DiffAugment draws.  With the default None there is no module and no launch.
+        self.pair_augment = pair_module
         self.logged: Dict[str, torch.Tensor] = {}
         self.ddp = None  # set by parallel.DataParallelGAN
 
@@ -583,6 +605,10 @@ class GAN(nn.Module):
         #  underneath the generator's backward gains 0.7 ms of 60 -- matrix-bound kernels and chains
         #  of small launches contend for the same CUs -- and stretches D's forward kernels by 20 %.)
         nets: List[_EngineModule] = [self.generator, self.discriminator]
+        if self.pair_augment is not None:           # once per batch: training_step and validation_step never augment
+            self.pair_augment.generator = self.aug_generator
+            with torch.no_grad():
+                batch = self.pair_augment(batch)
         for idx, opt in enumerate(optimizers):
             other = nets[1 - idx]
             for p in other.parameters():            # toggle_optimizer

@@ -1091,6 +1091,46 @@ def diffaug_backward(gy, ops_mask: int, color, geom, workspace, gx):
     return gx
 
 
+# ---- paired affine augmentation (csrc/pair_augment.hip; augment.py holds the sampler and the module) ----
+WARP_CONSTANT, WARP_BORDER = 0, 1                                                            # MPGAN_WARP_*
+
+
+def affine_warp(x0, x1, theta, mode: int, fill0: float, fill1: float, noise0, noise1, sigma, y0, y1):
+    """y_k = the trilinear resampling of x_k at c = A p + t under the per-sample theta (B, 12) float64, plus
+    sigma[:, k] * noise_k where plane k has a noise field (include/mpgan_hip.h).  x1 / y1 None: one plane.  The
+    outputs may have another spatial extent than the inputs."""
+    n, spatial = _diffaug_geometry(x0, "affine_warp")
+    _, out_spatial = _diffaug_geometry(y0, "affine_warp")
+    if y0.shape[0] != n or len(out_spatial) != len(spatial) or y0.device != x0.device:
+        raise ValueError(f"affine_warp: y0 has shape {tuple(y0.shape)} on {y0.device}, x0 {tuple(x0.shape)} on {x0.device}")
+    if (x1 is None) != (y1 is None):
+        raise ValueError("affine_warp: x1 and y1 go together")
+    if x1 is not None:
+        _diffaug_geometry(x1, "affine_warp")
+        _diffaug_geometry(y1, "affine_warp")
+        if x1.shape != x0.shape or y1.shape != y0.shape or x1.device != x0.device or y1.device != x0.device:
+            raise ValueError(f"affine_warp: the second plane has shapes {tuple(x1.shape)} -> {tuple(y1.shape)}, the first "
+                             f"{tuple(x0.shape)} -> {tuple(y0.shape)}")
+    if mode not in (WARP_CONSTANT, WARP_BORDER):
+        raise ValueError(f"affine_warp: unknown mode {mode!r}")
+    if noise1 is not None and x1 is None:
+        raise ValueError("affine_warp: noise1 without a second plane")
+    if (sigma is None) != (noise0 is None and noise1 is None):
+        raise ValueError("affine_warp: sigma goes with a noise field, and a noise field with sigma")
+    tables = [(theta, torch.float64, (n, 12), "theta"), (sigma, torch.float32, (n, 2), "sigma"),
+              (noise0, torch.float32, tuple(y0.shape), "noise0"), (noise1, torch.float32, tuple(y0.shape), "noise1")]
+    for t, dtype, shape, name in tables:
+        if t is None and name != "theta":
+            continue
+        if t is None or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != x0.device:
+            raise ValueError(f"affine_warp: {name} must be a contiguous {dtype} {shape} tensor on {x0.device}, got "
+                             + (f"{tuple(t.shape)} {t.dtype} on {t.device}" if t is not None else "None"))
+    check(lib().mpgan_affine_warp(x0.data_ptr(), _ptr(x1), n, _dhw(spatial), _dhw(out_spatial), theta.data_ptr(), int(mode),
+                                  float(fill0), float(fill1), _ptr(noise0), _ptr(noise1), _ptr(sigma), y0.data_ptr(),
+                                  _ptr(y1), _stream()), "affine_warp")
+    return y0 if y1 is None else (y0, y1)
+
+
 # --------------------------------------------------------------------------
 # conditional discriminator: the first conv over two 1-channel input planes (include/mpgan_hip.h: mpgan_conv2p_*)
 # --------------------------------------------------------------------------

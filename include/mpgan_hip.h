@@ -578,6 +578,33 @@ int mpgan_diffaug_forward(const float* x, int32_t n, const int32_t* dhw, int32_t
 int mpgan_diffaug_backward(const float* gy, int32_t n, const int32_t* dhw, int32_t ops, const float* color,
                            const int32_t* geom, void* ws, int64_t ws_bytes, float* gx, void* stream);
 
+/* ---- paired affine augmentation of the training pair itself (pair_augment.hip) ----
+ * x0, x1: contiguous fp32 [n][D][H][W] (one channel; 2-D images have D = 1), the two planes of a pair; x1 == y1 == null
+ * warps one plane.  y0, y1: [n][oD][oH][oW]; in_dhw and out_dhw may differ.  Per sample s, from device tables (nothing is
+ * read on the host):
+ *   theta: double [n][12], a row-major 3 x 4 (A | t) in (d, h, w) voxel-index order
+ *   sigma: float [n][2], the noise factor of plane 0 and plane 1
+ * Output voxel p = (d, h, w) samples the input at the continuous index c = A p + t:
+ *   y_k[p] = trilinear(x_k, c) + sigma[s][k] * noise_k[p]          (the second term only with a noise_k pointer)
+ * over the 8 corners floor(c) + {0,1}^3 with the weights prod_axis (1 - f or f), f = c - floor(c):
+ *   MPGAN_WARP_CONSTANT  a corner outside the input has the value fill_k (scipy's mode="grid-constant"; with fill 0
+ *                        grid_sample(padding_mode="zeros", align_corners=True))
+ *   MPGAN_WARP_BORDER    c is first clamped to [0, S - 1] per axis (scipy's mode="nearest"; grid_sample's "border")
+ * Both are continuous in c; a corner whose weight is exactly 0 is not read.  c, the weights, the lerps and the noise
+ * term are fp64, rounded to fp32 once; the coordinates and weights are computed once per voxel and used for both
+ * planes.  An integer-valued (A | t) (identity, flips, quarter turns, integer shifts) copies bits.  A plane whose sigma
+ * is 0, or that has no noise pointer, gets the bits of the call without noise.  Any theta is legal: a c beyond the
+ * input (or NaN) is `fill` / the clamped edge.
+ * Launch: one kernel for both planes, one thread per output voxel, a block per 4 x 8 x 32 (D = 1: 1 x 8 x 32) tile of
+ * the output.  No atomics; the grid depends on (n, out_dhw) alone: two runs give the same bits.
+ * MPGAN_ERR_INVALID before any launch: a null x0 / y0 / theta / in_dhw / out_dhw, x1 without y1 or the reverse, n <= 0,
+ * an extent < 1, an unknown mode, a noise pointer without sigma (or sigma without one, or noise1 without x1),
+ * n * N_in or n * N_out >= 2^31. */
+enum { MPGAN_WARP_CONSTANT = 0, MPGAN_WARP_BORDER = 1 };
+int mpgan_affine_warp(const float* x0, const float* x1, int32_t n, const int32_t* in_dhw, const int32_t* out_dhw,
+                      const double* theta, int32_t mode, float fill0, float fill1, const float* noise0,
+                      const float* noise1, const float* sigma, float* y0, float* y1, void* stream);
+
 /* ---- optimiser ------------------------------------------------------------ */
 /* torch.optim.Adam.step over one flat buffer (GAN_final.py:306-307):
  * m = b1*m+(1-b1)*g; v = b2*v+(1-b2)*g^2; p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t)+eps).
