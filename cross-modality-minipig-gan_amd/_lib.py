@@ -135,6 +135,12 @@ SIGNATURES = {
     "mpgan_ssim_loss_workspace": (_L, [_I3, _I, _I, C.POINTER(C.c_int64)]),
     "mpgan_ssim_loss_forward": (_I, [_P, _P, _I3, _I, _I, C.c_double, C.c_double, _I, _P, _L, _P, _L, _I, _P, _P]),
     "mpgan_ssim_loss_backward": (_I, [_P, _P, _I3, _I, _I, C.c_double, _I, _P, _L, _P, _I, C.c_double, _I, _P, _P]),
+    # Sobel edge loss (edge_loss.hip)
+    "mpgan_sobel_magnitude_forward": (_I, [_P, _I3, _I, C.c_double, _P, _P]),
+    "mpgan_sobel_magnitude_backward": (_I, [_P, _I3, _I, C.c_double, _P, _P, _P]),
+    "mpgan_edge_loss_workspace": (_L, [_I3, _I]),
+    "mpgan_edge_loss_forward": (_I, [_P, _P, _I3, _I, _I, C.c_double, _P, _L, _I, _P, _P]),
+    "mpgan_edge_loss_backward": (_I, [_P, _P, _I3, _I, _I, C.c_double, _P, _I, C.c_double, _I, _P, _P]),
     # differentiable augmentation in front of D (diffaug.hip)
     "mpgan_diffaug_workspace": (_L, [_I, _I3]),
     "mpgan_diffaug_forward": (_I, [_P, _I, _I3, _I, _P, _P, _F, _P, _L, _P, _P]),

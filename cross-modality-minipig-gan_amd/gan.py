@@ -15,7 +15,7 @@ import torch.nn as nn
 
 from . import ops
 from .augment import DiffAugment, PairAugment, parse_policy
-from .losses import GlobalMutualInformationLoss, SSIMLoss
+from .losses import EdgeLoss, GlobalMutualInformationLoss, SSIMLoss
 from .networks import CasNetGenerator, Discriminator, _EngineModule
 
 
@@ -397,7 +397,7 @@ class GAN(nn.Module):
                  ssim_weight: float = 0.0, d_head: str = "linear", adv_loss: str = "bce", conditional: bool = False,
                  diff_augment: str = "", diff_augment_fill: float = 0.0, ema_decay: float = 0.0,
                  ema_warmup: bool = True, grad_clip: float = 0.0, log_grad_norm: bool = False,
-                 pair_augment: Optional[dict] = None, **kwargs):
+                 pair_augment: Optional[dict] = None, edge_weight: float = 0.0, edge_eps: float = 1e-6, **kwargs):
         super().__init__()
         if adv_loss not in ADV_LOSSES:
             raise ValueError(f"adv_loss must be one of {ADV_LOSSES}, got {adv_loss!r}")
@@ -405,6 +405,8 @@ class GAN(nn.Module):
             raise ValueError(f"mi_weight must be >= 0, got {mi_weight!r}")
         if ssim_weight < 0:
             raise ValueError(f"ssim_weight must be >= 0, got {ssim_weight!r}")
+        if edge_weight < 0:
+            raise ValueError(f"edge_weight must be >= 0, got {edge_weight!r}")
         if not 0.0 <= ema_decay < 1.0:
             raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay!r}")
         if not grad_clip >= 0:
@@ -459,6 +461,10 @@ class GAN(nn.Module):
         # likewise ssim_weight * (1 - SSIM(G(t1w), t2w)), the loss form of the figure metrics.ssim scores a volume with
         self.ssim_weight = float(ssim_weight)
         self.ssim_loss = SSIMLoss(value_range=(-1.0, 1.0)) if self.ssim_weight > 0 else None
+        # and edge_weight * mean |m(G(t1w)) - m(t2w)| over the Sobel edge-magnitude maps, Ea-GAN's generator term
+        # (DESIGN.md 7i); like every generator term it sees the pair fit_batch hands over, never DiffAugment's output
+        self.edge_weight = float(edge_weight)
+        self.edge_loss = EdgeLoss(eps=edge_eps) if self.edge_weight > 0 else None
         # opt-in differentiable augmentation of everything D sees in training_step (augment.py); with the
         # default "" there is no module and no launch.  aug_generator: a torch.Generator on the images' device, or None
         # for torch's global one (data-parallel runs: every rank seeds its own, or all ranks draw the same parameters)
@@ -537,6 +543,10 @@ class GAN(nn.Module):
                 g_ssim_loss = self.ssim_loss(generated_imgs, t2w_images)
                 self.log("g_ssim_loss", g_ssim_loss)
                 g_loss = scalar_axpby(g_loss, 1.0, g_ssim_loss, self.ssim_weight)
+            if self.edge_loss is not None:
+                g_edge_loss = self.edge_loss(generated_imgs, t2w_images)
+                self.log("g_edge_loss", g_edge_loss)
+                g_loss = scalar_axpby(g_loss, 1.0, g_edge_loss, self.edge_weight)
             self.log("g_loss", g_loss)
             return g_loss
         if optimizer_idx == 1:                      # GAN_final.py:276-296
@@ -559,9 +569,9 @@ class GAN(nn.Module):
         step for it): the losses of training_step (:250-296) on a held-out batch from ONE generator pass, with generator
         and discriminator in eval mode (running-statistics BatchNorm) under no_grad -- no parameter, buffer, gradient or
         optimizer state is touched.  Logs and returns val_g_adv_loss, val_g_recon_loss, val_g_loss, val_d_loss as
-        device scalars (no host sync); with mi_weight > 0 also val_g_mi_loss and with ssim_weight > 0 also
-        val_g_ssim_loss, which val_g_loss then includes; with ema_decay > 0 also val_ema_g_recon_loss, the L1 of
-        generator_ema(t1w) against t2w."""
+        device scalars (no host sync); with mi_weight > 0 also val_g_mi_loss, with ssim_weight > 0 also
+        val_g_ssim_loss and with edge_weight > 0 also val_g_edge_loss, which val_g_loss then includes; with
+        ema_decay > 0 also val_ema_g_recon_loss, the L1 of generator_ema(t1w) against t2w."""
         t1w_images, t2w_images = batch["t1w"], batch["t2w"]
         with torch.no_grad(), eval_modes(self.generator, self.discriminator):
             generated_imgs = self(t1w_images)
@@ -575,6 +585,9 @@ class GAN(nn.Module):
             if self.ssim_loss is not None:
                 g_ssim_loss = self.ssim_loss(generated_imgs, t2w_images)
                 g_loss = scalar_axpby(g_loss, 1.0, g_ssim_loss, self.ssim_weight)
+            if self.edge_loss is not None:
+                g_edge_loss = self.edge_loss(generated_imgs, t2w_images)
+                g_loss = scalar_axpby(g_loss, 1.0, g_edge_loss, self.edge_weight)
             d_real = self._judge(t2w_images, t1w_images)
             real_loss = self.adversarial_loss(d_real, self._labels(d_real, self.hparams.one_sided_label_value))
             fake_loss = self.adversarial_loss(d_fake, self._labels(d_fake, 0.0))
@@ -586,6 +599,8 @@ class GAN(nn.Module):
             out["val_g_mi_loss"] = g_mi_loss
         if self.ssim_loss is not None:
             out["val_g_ssim_loss"] = g_ssim_loss
+        if self.edge_loss is not None:
+            out["val_g_edge_loss"] = g_edge_loss
         if self.generator_ema is not None:
             out["val_ema_g_recon_loss"] = ema_recon_loss
         for name, value in out.items():

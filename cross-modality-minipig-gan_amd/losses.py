@@ -9,7 +9,12 @@ against a float64 torch restatement (tests/mi_loss_ref.py).  Forward and backwar
 SSIMLoss is 1 - the structural similarity that metrics.ssim scores a volume with (code/GAN/psnr_ssim_metric.py:88-106),
 as a loss: the forward kernel of csrc/ssim_loss.hip also leaves the per-window coefficient maps of the closed-form
 gradient, the backward kernel box-sums them.  Its definition is pinned in include/mpgan_hip.h against the float64
-torch restatement tests/ssim_loss_ref.py."""
+torch restatement tests/ssim_loss_ref.py.
+
+EdgeLoss is the edge-aware generator term of Ea-GAN (Yu et al. 2019): the L1 distance of the 3-D Sobel edge-magnitude
+maps of the two volumes, over a replicate border.  csrc/edge_loss.hip holds the fused stencils (the forward writes no
+map, the backward recomputes from the two inputs) and sobel_magnitude, the map itself as a differentiable op.  Ea-GAN's
+code is not available here: the definition in include/mpgan_hip.h is what is pinned, against tests/edge_loss_ref.py."""
 from __future__ import annotations
 
 import torch
@@ -206,3 +211,111 @@ class SSIMLoss(nn.Module):
 
     def forward(self, pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         return ssim_loss(pred, target, self.value_range, self.reduction)
+
+
+def _edge_config(eps, reduction, who):
+    if reduction not in _REDUCTIONS:
+        raise ValueError(f"{who}: unknown reduction {reduction!r} (expected one of {_REDUCTIONS})")
+    try:
+        eps = float(eps)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: eps must be a positive number, got {eps!r}") from None
+    if not (eps > 0 and eps != float("inf") and torch.tensor(eps, dtype=torch.float32).item() > 0):
+        raise ValueError(f"{who}: eps must be positive and finite in fp32, got {eps!r}")
+    return eps
+
+
+def _edge_input(x, who, name="x"):
+    if x.dim() not in (4, 5) or x.numel() == 0:
+        raise ValueError(f"{who}: expects non-empty (B, C, H, W) or (B, C, D, H, W) tensors, got {name} "
+                         f"{tuple(x.shape)}")
+    if x.dtype != torch.float32 or not x.is_cuda:
+        raise ValueError(f"{who}: expects fp32 device tensors")
+    return tuple(x.shape[2:])
+
+
+def _edge_inputs(pred, target, who):
+    if pred.shape != target.shape:
+        raise ValueError(f"{who}: shape mismatch, pred {tuple(pred.shape)} and target {tuple(target.shape)}")
+    _edge_input(pred, who, "pred")
+    return _edge_input(target, who, "target")
+
+
+class _SobelMagnitudeFn(torch.autograd.Function):
+    """m(x); saves x alone, backward recomputes G and m from it."""
+
+    @staticmethod
+    def forward(ctx, x, eps):
+        x = x.contiguous()                                # a contiguous view keeps its (possibly unaligned) offset
+        ctx.cfg = (tuple(x.shape[2:]), x.shape[0] * x.shape[1], eps)
+        ctx.save_for_backward(x)
+        return ops.sobel_magnitude_forward(x, *ctx.cfg, torch.empty_like(x))
+
+    @staticmethod
+    def backward(ctx, gout):
+        (x,) = ctx.saved_tensors
+        return ops.sobel_magnitude_backward(x, *ctx.cfg, gout.contiguous(), torch.empty_like(x)), None
+
+
+def sobel_magnitude(x: torch.Tensor, eps: float = 1e-6) -> torch.Tensor:
+    """The Sobel edge-magnitude map sqrt(sum_k G_k^2 + eps) of a (B, C, H, W) or (B, C, D, H, W) fp32 device tensor, in
+    the shape of x: G_k is the 3^d Sobel operator along axis k, normalised so that a ramp of slope 1 answers 1, over a
+    replicate border (a constant image has no edges, up to its faces).  Differentiable; the gradient is 0 in flat
+    regions.  The definition is pinned in include/mpgan_hip.h against tests/edge_loss_ref.py."""
+    who = "sobel_magnitude"
+    eps = _edge_config(eps, "none", who)
+    _edge_input(x, who)
+    return _SobelMagnitudeFn.apply(x, eps)
+
+
+class _EdgeLossFn(torch.autograd.Function):
+    """The reduced loss; saves the two inputs and nothing else: backward forms the signs from them again, so a second
+    backward (retain_graph) gives the same bits."""
+
+    @staticmethod
+    def forward(ctx, pred, target, eps, reduction):
+        a, b = pred.contiguous(), target.contiguous()     # a contiguous view keeps its (possibly unaligned) offset
+        batch, channels, spatial = a.shape[0], a.shape[1], tuple(a.shape[2:])
+        items, dev = batch * channels, a.device
+        ws = torch.empty(ops.edge_loss_workspace(spatial, items) // 8, dtype=torch.float64, device=dev)
+        loss = torch.empty((batch,) if reduction == "none" else (), device=dev)
+        ops.edge_loss_forward(a, b, spatial, items, channels, eps, ws, reduction, loss)
+        scale = {"mean": 1.0 / items, "sum": 1.0, "none": 1.0 / channels}[reduction]
+        ctx.cfg = (spatial, items, channels, eps, scale)
+        ctx.save_for_backward(a, b)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        a, b = ctx.saved_tensors
+        spatial, items, channels, eps, scale = ctx.cfg
+        gout = gout.contiguous()
+        grads = [None, None]
+        for wrt in (0, 1):
+            if ctx.needs_input_grad[wrt]:
+                grads[wrt] = ops.edge_loss_backward(a, b, spatial, items, channels, eps, gout, scale, wrt,
+                                                    torch.empty_like(a))
+        return grads[0], grads[1], None, None
+
+
+def edge_loss(pred: torch.Tensor, target: torch.Tensor, eps: float = 1e-6, reduction: str = "mean") -> torch.Tensor:
+    """The edge-aware term of Ea-GAN (Yu et al. 2019): mean |m(pred) - m(target)| of the Sobel edge-magnitude maps
+    (sobel_magnitude) of two (B, C, H, W) or (B, C, D, H, W) fp32 device tensors; every (b, c) image is one item.
+    reduction: "mean" (a scalar over the B * C items), "sum", or "none" ((B,), each entry the mean over its channels).
+    One fused kernel each way (csrc/edge_loss.hip): no gradient or magnitude map is materialised.  Differentiable in
+    both arguments; bitwise reproducible."""
+    who = "edge_loss"
+    eps = _edge_config(eps, reduction, who)
+    _edge_inputs(pred, target, who)
+    return _EdgeLossFn.apply(pred, target, eps, reduction)
+
+
+class EdgeLoss(nn.Module):
+    """edge_loss as a module."""
+
+    def __init__(self, eps: float = 1e-6, reduction: str = "mean"):
+        super().__init__()
+        self.eps, self.reduction = _edge_config(eps, reduction, "EdgeLoss"), reduction
+
+    def forward(self, pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        return edge_loss(pred, target, self.eps, self.reduction)

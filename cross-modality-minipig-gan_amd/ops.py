@@ -1021,6 +1021,45 @@ def ssim_loss_backward(a, b, spatial, items, channels, lo, grad_mask, coef, upst
     return grad
 
 
+# ---- Sobel edge loss (csrc/edge_loss.hip; losses.py holds the autograd nodes) ----
+def sobel_magnitude_forward(x, spatial, items, eps, out):
+    """out = m(x), the Sobel edge magnitude of `items` contiguous fp32 images (see include/mpgan_hip.h)."""
+    check(lib().mpgan_sobel_magnitude_forward(x.data_ptr(), _dhw(spatial), int(items), float(eps), out.data_ptr(),
+                                              _stream()), "sobel_magnitude_forward")
+    return out
+
+
+def sobel_magnitude_backward(x, spatial, items, eps, dy, dx):
+    """dx = the adjoint of m at x for the upstream map dy; recomputed from x."""
+    check(lib().mpgan_sobel_magnitude_backward(x.data_ptr(), _dhw(spatial), int(items), float(eps), dy.data_ptr(),
+                                               dx.data_ptr(), _stream()), "sobel_magnitude_backward")
+    return dx
+
+
+def edge_loss_workspace(spatial, items: int) -> int:
+    """Workspace bytes for `items` images of extent `spatial` ((H, W) or (D, H, W))."""
+    need = int(lib().mpgan_edge_loss_workspace(_dhw(spatial), int(items)))
+    if need < 0:
+        raise ValueError(f"edge_loss_workspace: bad geometry ({items} items of extent {tuple(spatial)})")
+    return need
+
+
+def edge_loss_forward(a, b, spatial, items, channels, eps, workspace, reduction, loss):
+    """loss (fp32, reduced on the device) of two contiguous fp32 tensors; no magnitude map is written."""
+    check(lib().mpgan_edge_loss_forward(a.data_ptr(), b.data_ptr(), _dhw(spatial), int(items), int(channels), float(eps),
+                                        workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+                                        _PMI_REDUCTIONS[reduction], loss.data_ptr(), _stream()), "edge_loss_forward")
+    return loss
+
+
+def edge_loss_backward(a, b, spatial, items, channels, eps, upstream, scale, wrt, grad):
+    """grad = upstream[batch entry or 0] * scale * d loss_item / d (a if wrt == 0 else b)."""
+    check(lib().mpgan_edge_loss_backward(a.data_ptr(), b.data_ptr(), _dhw(spatial), int(items), int(channels),
+                                         float(eps), upstream.data_ptr(), 0 if upstream.numel() == 1 else 1,
+                                         float(scale), int(wrt), grad.data_ptr(), _stream()), "edge_loss_backward")
+    return grad
+
+
 # ---- differentiable augmentation (csrc/diffaug.hip; augment.py holds the sampler and the autograd node) ----
 DIFFAUG_BRIGHTNESS, DIFFAUG_CONTRAST, DIFFAUG_TRANSLATION, DIFFAUG_CUTOUT = 1, 2, 4, 8      # MPGAN_DIFFAUG_*
 

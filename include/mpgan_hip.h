@@ -549,6 +549,53 @@ int mpgan_ssim_loss_backward(const float* a, const float* b, const int32_t* dhw,
                              const float* upstream, int32_t upstream_stride, double scale, int32_t wrt, float* grad,
                              void* stream);
 
+/* ---- Sobel edge loss: the L1 distance of two 3-D Sobel edge-magnitude maps (the generator term of Ea-GAN, Yu et al.
+ * 2019; the definition below is what is pinned; Ea-GAN's own filters are this operator times 8 in 2-D, times 32 in 3-D) ----
+ * x, a, b: contiguous fp32 arrays of `items` images of dhw = (D, H, W) samples each; an item is one (batch, channel)
+ * image, items = batch * channels.  Any extent >= 1 is legal.  d = 3 (a 2-D image has D = 1, see below).
+ *   Dv = (-1, 0, 1);  Sv = (1, 2, 1);  clamp is per axis to [0, n - 1] (a replicate border: a constant image has no
+ *   edges anywhere, where zero padding would plant a frame of them)
+ *   G_k(x)_p = 1 / (2 4^(d-1)) sum over t in {-1,0,1}^d of Dv[t_k] prod_{j != k} Sv[t_j] x[clamp(p + t)]
+ *              (a ramp of slope 1 per voxel along axis k answers 1)
+ *   m(x)_p   = sqrt(sum_k G_k(x)_p^2 + eps),  eps > 0;  d m_p / d G_k = G_k / m, which is 0 in flat regions
+ *   D == 1: the three z taps read one voxel, G_z = 0 and the z smoothing sums to 4 / 4: exactly the 2-D operator
+ *   1 / (2 4) sum Dv Sv x.  Nothing is special-cased.
+ *   loss_item = mean over the N = D H W voxels of |m(a)_p - m(b)_p|
+ *   reduction 0: loss[0] = mean over the items; 1: loss[0] = their sum; 2: loss[batch], entry b = mean over b's channels.
+ * Adjoint of m for an upstream map dy:  dx_p = sum_q dy_q sum_k (G_k / m)_q dG_k(x)_q / dx_p.  A tap of q that falls
+ * outside the image lands on the border voxel it was clamped to, so along each axis the transposed taps of p are
+ * (q = p - 1, p, p + 1) with weights (1, 2 + [p == 0] + [p == n - 1], 1) for Sv and (1, [p == n - 1] - [p == 0], -1)
+ * for Dv, over the q inside the image.
+ * Gradient of the loss: the adjoint with dy_q = s_q / N for a and -s_q / N for b (and b's G, m), where
+ * s_q = sign(m(a)_q - m(b)_q), sign(0) = 0.
+ * The tap sums are formed in fp64 (exact for fp32 samples) and rounded once, so G_k keeps its relative precision where
+ * the image is nearly flat; m and G_k / m are fp32.  All four entry points take m from one device function: the loss
+ * and a composition through the magnitude map see the same bits of m, hence the same signs.  Block partial sums of
+ * the loss are fp64 and every sum has a fixed order (no atomics): results are bitwise reproducible from call to call.
+ * Nothing but the inputs passes from forward to backward.  The calls allocate nothing, are asynchronous on `stream`
+ * and can be captured into a graph.  A null pointer, eps <= 0, an extent < 1, items outside [1, 65535] or an unknown
+ * reduction is MPGAN_ERR_INVALID before any launch. */
+/* out[items][D][H][W] = m(x). */
+int mpgan_sobel_magnitude_forward(const float* x, const int32_t* dhw, int32_t items, double eps, float* out,
+                                  void* stream);
+/* dx[items][D][H][W] = the adjoint above for the upstream map dy[items][D][H][W]; recomputed from x. */
+int mpgan_sobel_magnitude_backward(const float* x, const int32_t* dhw, int32_t items, double eps, const float* dy,
+                                   float* dx, void* stream);
+/* Bytes of workspace mpgan_edge_loss_forward needs (8-byte aligned).  -1 on a bad argument. */
+int64_t mpgan_edge_loss_workspace(const int32_t* dhw, int32_t items);
+/* loss as `reduction` says (fp32, written on the device: no host sync).  No magnitude map is written: a block's
+ * partial sum goes to `workspace`, a second stage adds an item's partials in slot order. */
+int mpgan_edge_loss_forward(const float* a, const float* b, const int32_t* dhw, int32_t items, int32_t channels,
+                            double eps, void* workspace, int64_t workspace_bytes, int32_t reduction, float* loss,
+                            void* stream);
+/* grad[items][D][H][W] = upstream[(item / channels) * upstream_stride] * scale * d loss_item / d (wrt == 0 ? a : b),
+ * the signs formed on the fly from a and b.  upstream is a device array over the batch (stride 1) or one device scalar
+ * (stride 0); scale is the host factor of the reduction (1 for the sum, 1 / items for the mean, 1 / channels for
+ * reduction 2). */
+int mpgan_edge_loss_backward(const float* a, const float* b, const int32_t* dhw, int32_t items, int32_t channels,
+                             double eps, const float* upstream, int32_t upstream_stride, double scale, int32_t wrt,
+                             float* grad, void* stream);
+
 /* ---- differentiable augmentation in front of the discriminator (DiffAugment, Zhao et al. 2020) ----
  * x: contiguous fp32 [n][D][H][W] (one channel; 2-D images have D = 1); N = D H W.  Per sample s, from two device tables
  * (nothing is read on the host):
