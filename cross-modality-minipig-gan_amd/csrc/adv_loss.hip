@@ -3,8 +3,8 @@
 // the mean loss's block partials and dL/dlogit for an upstream gradient of 1; a second, tiny one adds the partials
 // (a single block finishes on its own).
 //   arithmetic   element terms in fp32, every sum in fp64
-//   sum order    per lane its elements in index order, then the lanes of the wave, then the four waves through LDS;
-//                one plain store per block; the block partials in index order.  No atomics, and the grid depends on n
+//   sum order    per lane its elements in index order, then block_sum4 (reduce.h); one plain store per block; the
+//                block partials in index order.  No atomics, and the grid depends on n
 //                alone: two runs give the same bits.
 //   access       16-byte loads and stores when logit / target / grad are 16-byte aligned, the n % 4 last elements
 //                scalar; element by element otherwise.
@@ -33,12 +33,6 @@ __device__ __forceinline__ float adv_elem(float z, float t, float nf, float* g) 
   const float d = z - t;
   *g = (2.f * d) / nf;
   return d * d;
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
 }
 
 template <int KIND, bool VEC>
@@ -75,11 +69,8 @@ __global__ __launch_bounds__(256) void adv_loss_kernel(const float* __restrict__
       if (grad) grad[i] = g;
     }
   }
-  acc = wave_sum_f64(acc);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-  __syncthreads();
+  const double s = block_sum4(acc, sh);
   if (threadIdx.x == 0) {
-    const double s = ((sh[0] + sh[1]) + sh[2]) + sh[3];
     partials[blockIdx.x] = s;
     if (gridDim.x == 1) *loss = (float)(s / (double)n);
   }

@@ -8,9 +8,9 @@
 //           backward: shift = -t, box = the clipped box moved by t,   affine(v) = v,  outside = 0, then c g_u + k with
 //                     k = (1 - c) / N * sum g_u
 //   arithmetic   element terms in fp32, every sum in fp64; m and k are rounded to fp32 once
-//   sum order    per lane its elements in index order, then the lanes of the wave, then the four waves through LDS; one
+//   sum order    per lane its elements in index order, then block_sum4 (reduce.h); one
 //                plain store per block.  The apply kernel adds a sample's partials itself: lane l the partials l, l+64,
-//                ... in index order, then the lanes of the wave (every wave of every block does the same additions).
+//                ... in index order, then wave_sum (every wave of every block does the same additions).
 //                No atomics; the grid depends on (n, dhw) alone and no parameter is read on the host: two runs give the
 //                same bits.
 //   access       16-byte loads and stores when both pointers are 16-byte aligned and W % 4 == 0 (every row of every
@@ -74,12 +74,6 @@ __device__ __forceinline__ DaXform da_xform(const int32_t* __restrict__ geom, in
 
 __device__ __forceinline__ bool da_in(int v, int lo, int hi) { return v >= lo && v < hi; }
 
-__device__ __forceinline__ double wave_sum_f64_da(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // The gathered values of one unit (VEC: the quad at row `row`, columns w0 .. w0+3; else one element) and their keep
 // flags.  src is the sample's base.  Masked lanes of a quad read nothing that lies outside the row.
 template <bool VEC>
@@ -138,10 +132,8 @@ __global__ __launch_bounds__(DA_THREADS) void diffaug_sum_kernel(const float* __
 #pragma unroll
     for (int k = 0; k < (VEC ? 4 : 1); ++k) acc += keep[k] ? (double)v[k] : 0.0;
   }
-  acc = wave_sum_f64_da(acc);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) partials[blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+  acc = block_sum4(acc, sh);
+  if (threadIdx.x == 0) partials[blockIdx.x] = acc;
 }
 
 template <bool VEC>
@@ -161,7 +153,7 @@ __global__ __launch_bounds__(DA_THREADS) void diffaug_apply_kernel(const float* 
   if (contrast) {
     double t = 0.0;
     for (int j = threadIdx.x & 63; j < bps; j += 64) t += partials[s * bps + j];
-    t = wave_sum_f64_da(t);
+    t = wave_sum(t);
     m = backward ? (float)((1.0 - (double)c) * t / (double)N) : (float)(t / (double)N);
   }
   const float outside = backward ? 0.f : fill;

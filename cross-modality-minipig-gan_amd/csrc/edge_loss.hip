@@ -6,7 +6,8 @@
 //                                  source coordinates, and writes the map.
 //   el_forward_kernel<.., true>    the loss: stages both images, a thread forms m(a) and m(b) of its (y, x) column and
 //                                  adds |m(a) - m(b)| in double; block partial -> workspace slot.  No map is written.
-//   el_item_kernel, el_loss_kernel an item's partials in slot order + a fixed tree, then the reduction over the items.
+//   launch_loss_tail (loss_ops.hip) an item's partials in slot order + a fixed tree (loss_item_kernel), then the
+//                                  reduction over the items (loss_reduce_kernel<false>); reduce.h states the orders.
 //   el_backward_kernel             the adjoint as a gather.  Stages x (and, for the loss, the other image) with a halo
 //                                  of 2, writes the three coefficients w_q G_k(q) / m(q) of the tile plus a halo of 1
 //                                  to LDS -- zero for a q outside the image -- and every voxel of the tile then sums its
@@ -157,54 +158,14 @@ __global__ __launch_bounds__(256) void el_forward_kernel(ElFwd p) {
 #pragma unroll
     for (int k = 0; k < NZ; ++k)
       if (col_ok && z0 + k < p.D) local += fabs((double)ma[k] - (double)mb[k]);
-    double* red = reinterpret_cast<double*>(el_sm);
-    red[tid] = local;                           // block sum in a fixed order
-    __syncthreads();
-    for (int s2 = 128; s2 > 0; s2 >>= 1) {
-      if (tid < s2) red[tid] += red[tid + s2];
-      __syncthreads();
-    }
-    if (tid == 0) p.partials[item * p.tiles + blockIdx.x] = red[0];
+    local = block_tree_sum<256>(local, reinterpret_cast<double*>(el_sm));   // block sum in a fixed order
+    if (tid == 0) p.partials[item * p.tiles + blockIdx.x] = local;
   } else {
     __syncthreads();                            // every column has been read: the tile of a becomes the output tile
 #pragma unroll
     for (int k = 0; k < NZ; ++k) sa[(k * EL_TY + ty) * EL_TX + tx] = ma[k];
     __syncthreads();
     el_store<NZ>(sa, p.out + item * vox, p.D, p.H, p.W, z0, y0, x0);
-  }
-}
-
-// loss_item[item] = (sum of the item's tile partials) / N
-__global__ __launch_bounds__(256) void el_item_kernel(const double* __restrict__ partials, long tiles, double inv_n,
-                                                      double* __restrict__ loss_item) {
-  __shared__ double red[256];
-  const double* w = partials + (long)blockIdx.x * tiles;
-  double s = 0.0;
-  for (long i = threadIdx.x; i < tiles; i += 256) s += w[i];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int s2 = 128; s2 > 0; s2 >>= 1) {
-    if (threadIdx.x < s2) red[threadIdx.x] += red[threadIdx.x + s2];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) loss_item[blockIdx.x] = red[0] * inv_n;
-}
-
-// reduction 0: loss[0] = mean over the items; 1: their sum; 2: loss[b] = mean over b's channels
-__global__ void el_loss_kernel(const double* __restrict__ loss_item, int items, int channels, int reduction,
-                               float* __restrict__ loss) {
-  if (reduction == 2) {
-    for (int b = threadIdx.x; b < items / channels; b += blockDim.x) {
-      double s = 0.0;
-      for (int c = 0; c < channels; ++c) s += loss_item[b * channels + c];
-      loss[b] = (float)(s / (double)channels);
-    }
-    return;
-  }
-  if (threadIdx.x == 0) {
-    double s = 0.0;
-    for (int i = 0; i < items; ++i) s += loss_item[i];
-    loss[0] = (float)(reduction == 0 ? s / (double)items : s);
   }
 }
 
@@ -444,10 +405,8 @@ extern "C" int mpgan_edge_loss_forward(const float* a, const float* b, const int
   } else {
     hipLaunchKernelGGL((el_forward_kernel<1, true>), grid, dim3(256), el_fwd_lds(1, true), st, p);
   }
-  hipLaunchKernelGGL(el_item_kernel, dim3((unsigned)items), dim3(256), 0, st, (const double*)p.partials, g.tiles,
-                     1.0 / (double)g.vox, loss_item);
-  hipLaunchKernelGGL(el_loss_kernel, dim3(1), dim3(64), 0, st, (const double*)loss_item, (int)items, (int)channels,
-                     (int)reduction, loss);
+  // loss_item = (sum of the item's tile partials) / N; loss = loss_item over the items
+  launch_loss_tail(p.partials, g.tiles, 1.0 / (double)g.vox, loss_item, items, channels, reduction, false, loss, st);
   return check_launch("edge_loss_forward");
 }
 

@@ -16,16 +16,6 @@ static inline int ew_blocks2(long total) {
   return (int)b;
 }
 
-__device__ __forceinline__ float block_sum_256(float v, float* sh) {
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) sh[w] = v;
-  __syncthreads();
-  float r = sh[0] + sh[1] + sh[2] + sh[3];
-  __syncthreads();
-  return r;
-}
-
 // ---- linear head -----------------------------------------------------------
 __global__ __launch_bounds__(256) void linear1_partial_kernel(const float* __restrict__ z, Pro p, long P, int C,
                                                               const float* __restrict__ w,
@@ -51,7 +41,7 @@ __global__ __launch_bounds__(256) void linear1_partial_kernel(const float* __res
     }
     acc += a[0] * wv.x + a[1] * wv.y + a[2] * wv.z + a[3] * wv.w;
   }
-  acc = block_sum_256(acc, sh);
+  acc = block_sum4<true>(acc, sh);
   if (threadIdx.x == 0) partials[n * LIN_CHUNKS + chunk] = acc;
 }
 
@@ -75,7 +65,7 @@ __global__ __launch_bounds__(256) void bce_forward_kernel(const float* __restric
     const float pr = prob[i], t = target[i];
     acc += -(t * fmaxf(logf(pr), -100.f) + (1.f - t) * fmaxf(logf(1.f - pr), -100.f));
   }
-  acc = block_sum_256(acc, sh);
+  acc = block_sum4<true>(acc, sh);
   if (threadIdx.x == 0) *loss = acc / (float)n;
 }
 
@@ -182,7 +172,7 @@ __global__ __launch_bounds__(256) void sigmoid_bce_kernel(const float* __restric
       dlogit[i] = gp * (1.f - pr) * pr;
     }
   }
-  acc = block_sum_256(acc, sh);
+  acc = block_sum4<true>(acc, sh);
   if (threadIdx.x == 0 && loss) *loss = acc / (float)n;
 }
 
@@ -198,22 +188,54 @@ __global__ __launch_bounds__(256) void l1_partial_kernel(const float* __restrict
     acc += fabsf(d);
     if (grad) grad[i] = d > 0.f ? gscale : (d < 0.f ? -gscale : 0.f);
   }
-  acc = block_sum_256(acc, sh);
+  acc = block_sum4<true>(acc, sh);
   if (threadIdx.x == 0) partials[blockIdx.x] = acc;
 }
 
 __global__ __launch_bounds__(256) void l1_final_kernel(const float* __restrict__ partials, int n, double inv_numel,
                                                        float* __restrict__ loss) {
   __shared__ double sh[256];
+  const double t = strided_serial_sum256(partials, n, sh);
+  if (threadIdx.x == 0) *loss = (float)(t * inv_numel);
+}
+
+// ---- the tail of a tiled pair loss (SSIM loss, edge loss; reduce.h states the order) -------------------------------
+// item[i] = (sum of item i's tile partials) * inv
+__global__ __launch_bounds__(256) void loss_item_kernel(const double* __restrict__ partials, long tiles, double inv,
+                                                        double* __restrict__ item) {
+  __shared__ double red[256];
+  const double* w = partials + (long)blockIdx.x * tiles;
   double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) s += (double)partials[i];
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int i = 0; i < 256; ++i) t += sh[i];
-    *loss = (float)(t * inv_numel);
+  for (long i = threadIdx.x; i < tiles; i += 256) s += w[i];
+  s = block_tree_sum<256>(s, red);
+  if (threadIdx.x == 0) item[blockIdx.x] = s * inv;
+}
+
+// reduction 0: loss[0] = mean over the items of v; 1: their sum; 2: loss[b] = mean over b's channels.  v = item[i], or
+// 1.0 - item[i] with ONE_MINUS (SSIM: the subtraction comes before the sum)
+template <bool ONE_MINUS>
+__global__ void loss_reduce_kernel(const double* __restrict__ item, int items, int channels, int reduction,
+                                   float* __restrict__ loss) {
+  if (reduction == 2) {
+    for (int b = threadIdx.x; b < items / channels; b += blockDim.x) {
+      double s = 0.0;
+      for (int c = 0; c < channels; ++c) s += ONE_MINUS ? 1.0 - item[b * channels + c] : item[b * channels + c];
+      loss[b] = (float)(s / (double)channels);
+    }
+    return;
   }
+  if (threadIdx.x == 0) {
+    double s = 0.0;
+    for (int i = 0; i < items; ++i) s += ONE_MINUS ? 1.0 - item[i] : item[i];
+    loss[0] = (float)(reduction == 0 ? s / (double)items : s);
+  }
+}
+
+void launch_loss_tail(const double* partials, long tiles, double inv, double* item, int items, int channels,
+                      int reduction, bool one_minus, float* loss, hipStream_t stream) {
+  hipLaunchKernelGGL(loss_item_kernel, dim3((unsigned)items), dim3(256), 0, stream, partials, tiles, inv, item);
+  auto kern = one_minus ? loss_reduce_kernel<true> : loss_reduce_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(1), dim3(64), 0, stream, (const double*)item, items, channels, reduction, loss);
 }
 
 // ---- Adam ----------------------------------------------------------------------

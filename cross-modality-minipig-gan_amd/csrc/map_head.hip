@@ -283,17 +283,14 @@ __global__ __launch_bounds__(256) void maphead_wgrad_final_kernel(const float* _
   dw[o] = beta != 0.f ? beta * dw[o] + s : s;
 }
 
-// dbias = beta*dbias + sum dlogit: thread t adds elements t, t+256, ... in order, then the lanes, then the waves.
+// dbias = beta*dbias + sum dlogit: thread t adds elements t, t+256, ... in order, then block_sum4 (reduce.h).
 __global__ __launch_bounds__(256) void maphead_dbias_kernel(const float* __restrict__ dlogit, int total,
                                                             float* __restrict__ dbias, float beta) {
   __shared__ float sh[4];
   float acc = 0.f;
   for (int i = threadIdx.x; i < total; i += 256) acc += dlogit[i];
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-  __syncthreads();
+  const float s = block_sum4(acc, sh);
   if (threadIdx.x == 0) {
-    const float s = sh[0] + sh[1] + sh[2] + sh[3];
     *dbias = beta != 0.f ? beta * (*dbias) + s : s;
   }
 }

@@ -70,14 +70,11 @@ __global__ __launch_bounds__(256) void err_partial_kernel(const float* __restric
     ae += fabsf(d);
     se += d * d;
   }
-  ae = wave_sum(ae);
-  se = wave_sum(se);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) { s1[w] = ae; s2[w] = se; }
-  __syncthreads();
+  ae = block_sum4(ae, s1);
+  se = block_sum4(se, s2);
   if (threadIdx.x == 0) {
-    partials[2 * blockIdx.x] = s1[0] + s1[1] + s1[2] + s1[3];
-    partials[2 * blockIdx.x + 1] = s2[0] + s2[1] + s2[2] + s2[3];
+    partials[2 * blockIdx.x] = ae;
+    partials[2 * blockIdx.x + 1] = se;
   }
 }
 
@@ -89,11 +86,8 @@ __global__ __launch_bounds__(64) void err_final_kernel(const float* __restrict__
     ae += (double)partials[2 * i];
     se += (double)partials[2 * i + 1];
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    ae += __shfl_xor(ae, off, 64);
-    se += __shfl_xor(se, off, 64);
-  }
+  ae = wave_sum(ae);
+  se = wave_sum(se);
   if (threadIdx.x == 0) {
     const double mae = ae * inv_n, mse = se * inv_n;
     out3[0] = (float)mae;
@@ -171,13 +165,8 @@ __global__ __launch_bounds__(256) void ssim_partial_kernel(const float* __restri
   }
   // block sum in a fixed order
   __shared__ double red[256];
-  red[tid] = local;
-  __syncthreads();
-  for (int s2 = 128; s2 > 0; s2 >>= 1) {
-    if (tid < s2) red[tid] += red[tid + s2];
-    __syncthreads();
-  }
-  if (tid == 0) partials[blockIdx.x] = red[0];
+  local = block_tree_sum<256>(local, red);
+  if (tid == 0) partials[blockIdx.x] = local;
 }
 
 __global__ __launch_bounds__(256) void ssim_final_kernel(const double* __restrict__ partials, int nb, double inv_count,
@@ -185,13 +174,8 @@ __global__ __launch_bounds__(256) void ssim_final_kernel(const double* __restric
   __shared__ double red[256];
   double s = 0.0;
   for (int i = threadIdx.x; i < nb; i += 256) s += partials[i];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int s2 = 128; s2 > 0; s2 >>= 1) {
-    if (threadIdx.x < s2) red[threadIdx.x] += red[threadIdx.x + s2];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out1[0] = (float)(red[0] * inv_count);
+  s = block_tree_sum<256>(s, red);
+  if (threadIdx.x == 0) out1[0] = (float)(s * inv_count);
 }
 
 // ---- np.percentile on the device (ScaleIntensityRangePercentilesd, GAN_final.py:386-394) --------
@@ -691,18 +675,6 @@ __global__ __launch_bounds__(JH_THREADS) void joint_hist_kernel(JhParams p) {
 //   H = log N - (sum c log c) / N   (nats);   out6 = (mi, h_a, h_b, h_ab, nmi, count)
 constexpr int MI_THREADS = 1024;
 
-__device__ __forceinline__ double mi_block_sum(double v, double* red) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-  red[tid] = v;
-  __syncthreads();
-  for (int s = MI_THREADS / 2; s > 0; s >>= 1) {
-    if (tid < s) red[tid] += red[tid + s];
-    __syncthreads();
-  }
-  return red[0];
-}
-
 __global__ __launch_bounds__(MI_THREADS) void mutual_info_kernel(const unsigned long long* __restrict__ hist, int bins,
                                                                   double* __restrict__ out6) {
   __shared__ unsigned long long rows[256], cols[256];
@@ -728,8 +700,7 @@ __global__ __launch_bounds__(MI_THREADS) void mutual_info_kernel(const unsigned 
         atomicAdd(&cols[c], v);
       }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) rs += __shfl_xor(rs, off, 64);
+    rs = wave_sum(rs);
     if (lane == 0) rows[r] = rs;
   }
   if (nnz) atomicAdd(&nnz_s, (unsigned long long)nnz);
@@ -740,9 +711,9 @@ __global__ __launch_bounds__(MI_THREADS) void mutual_info_kernel(const unsigned 
     if (ra) { s_a = (double)ra * log((double)ra); atomicAdd(&tot_s, ra); }
     if (cb) s_b = (double)cb * log((double)cb);
   }
-  s_ab = mi_block_sum(s_ab, red);
-  s_a = mi_block_sum(s_a, red);
-  s_b = mi_block_sum(s_b, red);
+  s_ab = block_tree_sum<MI_THREADS, true>(s_ab, red);
+  s_a = block_tree_sum<MI_THREADS, true>(s_a, red);
+  s_b = block_tree_sum<MI_THREADS, true>(s_b, red);
   if (tid == 0) {
     double* o = out6 + 6 * (long)blockIdx.x;
     const unsigned long long total = tot_s;

@@ -116,18 +116,6 @@ __global__ __launch_bounds__(64 * PMI_WAVES) void pmi_joint_kernel(PmiJoint q) {
   q.ws[(item * q.slots + slot) * PMI_TILE + threadIdx.x] = s;
 }
 
-__device__ __forceinline__ double pmi_block_sum(double v, double* red) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-  red[tid] = v;
-  __syncthreads();
-  for (int s = PMI_TILE / 2; s > 0; s >>= 1) {
-    if (tid < s) red[tid] += red[tid + s];
-    __syncthreads();
-  }
-  return red[0];
-}
-
 // coef[item][0][i][j] = G_ij, coef[item][1][j][i] = G'_ij, each minus a constant (below); floats, zero outside K x K
 __global__ __launch_bounds__(PMI_TILE) void pmi_finalize_kernel(const double* __restrict__ ws, long slots, long n,
                                                                 int bins, double nr, double dr,
@@ -182,14 +170,14 @@ __global__ __launch_bounds__(PMI_TILE) void pmi_finalize_kernel(const double* __
   // it is: store G minus its pab-weighted mean (the mean of hbar over the voxels), which keeps the fp32 backward's
   // h small against its spread.  Likewise for G'.
   const double ga = in ? A + ua[i] : 0.0, gb = in ? A + ub[j] : 0.0;
-  const double ma = pmi_block_sum(s * ga, sd), mb = pmi_block_sum(s * gb, sd);
+  const double ma = block_tree_sum<PMI_TILE, true>(s * ga, sd), mb = block_tree_sum<PMI_TILE, true>(s * gb, sd);
   if (coef) {
     float* c = coef + item * 2 * PMI_TILE;
     c[i * PMI_T + j] = in ? (float)(ga - ma) : 0.f;
     c[PMI_TILE + j * PMI_T + i] = in ? (float)(gb - mb) : 0.f;
   }
   if (joint && in) joint[(item * bins + i) * bins + j] = s;
-  const double total = pmi_block_sum(in ? s * lg : 0.0, sd);
+  const double total = block_tree_sum<PMI_TILE, true>(in ? s * lg : 0.0, sd);
   if (tid == 0) mi[item] = total;
 }
 

@@ -218,10 +218,6 @@ StampCtx& stamp_ctx();                      // host side (capi.cpp)
 #define MPGAN_STAMP_NOW() 0ull
 #endif
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 }  // namespace mpgan
+
+#include "reduce.h"   // wave_sum and the block sums

@@ -220,12 +220,6 @@ __global__ __launch_bounds__(256) void norm_bwd_reduce_kernel(const float* __res
   (void)cz;
 }
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // One wave per statistic: lanes stride over the partial rows (fixed assignment),
 // then a fixed butterfly -- deterministic, and no longer a serial 1000-row walk.
 __global__ __launch_bounds__(256) void norm_finalize_kernel(const float* __restrict__ partials, int N, int chunks,
@@ -251,8 +245,8 @@ __global__ __launch_bounds__(256) void norm_finalize_kernel(const float* __restr
     s += (double)row[c];
     ss += (double)row[W + c];
   }
-  s = wave_sum_d(s);
-  ss = wave_sum_d(ss);
+  s = wave_sum(s);
+  ss = wave_sum(ss);
   if (lane != 0) return;
   const double cnt = (double)P * (ne - nb);
   const double m = s / cnt;
@@ -447,8 +441,8 @@ __global__ __launch_bounds__(256) void norm_bwd_finalize_kernel(const float* __r
         s2 += (double)v[u][1];
       }
     }
-    t1 = wave_sum_d(s1);
-    t2 = wave_sum_d(s2);
+    t1 = wave_sum(s1);
+    t2 = wave_sum(s2);
     if (lane == 0) {
       const double cnt = (double)P * N;
       c1[c] = (float)(t1 / cnt);
@@ -462,8 +456,8 @@ __global__ __launch_bounds__(256) void norm_bwd_finalize_kernel(const float* __r
         s1 += (double)row[c];
         s2 += (double)row[C + c];
       }
-      s1 = wave_sum_d(s1);
-      s2 = wave_sum_d(s2);
+      s1 = wave_sum(s1);
+      s2 = wave_sum(s2);
       t1 += s1;
       t2 += s2;
       if (lane == 0) {
@@ -655,7 +649,7 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(const float* __res
   if (c >= C) return;
   double s = 0.0;
   for (int r = lane; r < rows; r += 64) s += (double)partials[(long)r * row_stride + c];
-  s = wave_sum_d(s);
+  s = wave_sum(s);
   if (lane == 0) out[c] = beta != 0.f ? beta * out[c] + (float)s : (float)s;
 }
 

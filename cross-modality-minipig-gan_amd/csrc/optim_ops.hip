@@ -2,9 +2,9 @@
 // gradient's global norm with torch's clip coefficient, an Adam step that reads that coefficient from the device and
 // leaves an exponential moving average of the new parameters, and the table-driven EMA of the norm buffers.
 //   norm         g_i * grad_scale rounded to fp32 (the value Adam loads), its square and every sum in fp64: per lane
-//                its elements in index order, then the lanes of the wave, then the four waves, one plain store per
-//                block; a second, one-block launch adds the block partials in a fixed order.  No atomics and a grid
-//                that depends on numel alone: two runs give the same bits.
+//                its elements in index order, then block_sum4 (reduce.h), one plain store per block; a second,
+//                one-block launch adds the block partials by strided_serial_sum256.  No atomics and a grid that
+//                depends on numel alone: two runs give the same bits.
 //   Adam         adam_kernel's operations (loss_ops.hip) element for element; the coefficient is one scalar
 //                load per thread, so clipping needs no host sync.
 //   access       16-byte loads and stores when every participating pointer is 16-byte aligned (scalar tail),
@@ -25,12 +25,6 @@ static inline int gn_blocks(long numel) {
 static inline int opt_blocks(long work) {
   long b = (work + 255) / 256;
   return (int)(b > OPT_MAX_BLOCKS ? OPT_MAX_BLOCKS : (b < 1 ? 1 : b));
-}
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
 }
 
 __device__ __forceinline__ double gn_sq(float g, float gscale) {
@@ -58,10 +52,8 @@ __global__ __launch_bounds__(256) void grad_norm_partial_kernel(const float* __r
   } else {
     for (long i = gt; i < numel; i += stride) acc += gn_sq(g[i], gscale);
   }
-  acc = wave_sum_d(acc);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) partials[blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+  acc = block_sum4(acc, sh);
+  if (threadIdx.x == 0) partials[blockIdx.x] = acc;
 }
 
 // out2 = (norm, clip coefficient): torch.nn.utils.clip_grad_norm_'s clamp(max_norm / (norm + 1e-6), max=1.0) in fp32;
@@ -69,13 +61,8 @@ __global__ __launch_bounds__(256) void grad_norm_partial_kernel(const float* __r
 __global__ __launch_bounds__(256) void grad_norm_final_kernel(const double* __restrict__ partials, int blocks,
                                                               float max_norm, float* __restrict__ out2) {
   __shared__ double sh[256];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < blocks; i += 256) s += partials[i];
-  sh[threadIdx.x] = s;
-  __syncthreads();
+  const double t = strided_serial_sum256(partials, blocks, sh);
   if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int i = 0; i < 256; ++i) t += sh[i];
     const float norm = (float)sqrt(t);
     out2[0] = norm;
     float coef = 1.f;

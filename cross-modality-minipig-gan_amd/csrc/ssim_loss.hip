@@ -1,5 +1,6 @@
 // Differentiable SSIM loss (include/mpgan_hip.h: "SSIM loss" states the definition and the closed-form gradient).
-// Four kernels, no floating-point atomics, no scatter; every sum is taken in a fixed order in fp64:
+// Two kernels of its own and the shared loss tail, no floating-point atomics, no scatter; every sum is taken in a
+// fixed order in fp64 (reduce.h):
 //
 //   sl_forward_kernel   the pattern of ssim_partial_kernel (metric_ops.hip): a block stages the (TZ+WZ-1) x 14 x 38
 //                       region of both images of ONE item in LDS, a thread owns one (y, x) column of the 8 x 32 tile,
@@ -8,8 +9,9 @@
 //                       window, in double (exactly what a per-sample x - lo in double gives, to 1e-14).  When a
 //                       gradient is wanted the same pass writes the per-window coefficient maps Q, R and P of each
 //                       differentiated image, as doubles (see "storage" below).  Block partial -> workspace slot.
-//   sl_item_kernel      one block per item: its tiles' partials in slot order + a fixed tree -> ssim_item (double).
-//   sl_loss_kernel      loss = 1 - ssim over the items in item order: mean, sum, or per batch entry over its channels.
+//   launch_loss_tail    (loss_ops.hip) loss_item_kernel, one block per item: its tiles' partials in slot order + a fixed
+//                       tree -> ssim_item (double); loss_reduce_kernel<true>: loss = 1 - ssim over the items in item
+//                       order: mean, sum, or per batch entry over its channels.
 //   sl_backward_kernel  a gather: an output voxel box-sums each map over the windows that contain it (the map is zero
 //                       outside the M valid corners).  One map at a time goes through one LDS buffer with a 6-sample
 //                       halo in front of the tile on every windowed axis; per staged z a thread forms the 7x7 plane
@@ -130,47 +132,8 @@ __global__ __launch_bounds__(256) void sl_forward_kernel(SlFwd p) {
     }
     __builtin_amdgcn_sched_barrier(0);          // one window's divisions at a time
   }
-  red[tid] = local;                             // block sum in a fixed order
-  __syncthreads();
-  for (int s2 = 128; s2 > 0; s2 >>= 1) {
-    if (tid < s2) red[tid] += red[tid + s2];
-    __syncthreads();
-  }
-  if (tid == 0) p.partials[item * p.tiles + blockIdx.x] = red[0];
-}
-
-// ssim_item[item] = (sum of the item's tile partials) / M
-__global__ __launch_bounds__(256) void sl_item_kernel(const double* __restrict__ partials, long tiles, double inv_m,
-                                                      double* __restrict__ ssim_item) {
-  __shared__ double red[256];
-  const double* w = partials + (long)blockIdx.x * tiles;
-  double s = 0.0;
-  for (long i = threadIdx.x; i < tiles; i += 256) s += w[i];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int s2 = 128; s2 > 0; s2 >>= 1) {
-    if (threadIdx.x < s2) red[threadIdx.x] += red[threadIdx.x + s2];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) ssim_item[blockIdx.x] = red[0] * inv_m;
-}
-
-// reduction 0: loss[0] = mean over the items of 1 - ssim; 1: their sum; 2: loss[b] = mean over b's channels
-__global__ void sl_loss_kernel(const double* __restrict__ ssim_item, int items, int channels, int reduction,
-                               float* __restrict__ loss) {
-  if (reduction == 2) {
-    for (int b = threadIdx.x; b < items / channels; b += blockDim.x) {
-      double s = 0.0;
-      for (int c = 0; c < channels; ++c) s += 1.0 - ssim_item[b * channels + c];
-      loss[b] = (float)(s / (double)channels);
-    }
-    return;
-  }
-  if (threadIdx.x == 0) {
-    double s = 0.0;
-    for (int i = 0; i < items; ++i) s += 1.0 - ssim_item[i];
-    loss[0] = (float)(reduction == 0 ? s / (double)items : s);
-  }
+  local = block_tree_sum<256>(local, red);      // block sum in a fixed order
+  if (tid == 0) p.partials[item * p.tiles + blockIdx.x] = local;
 }
 
 struct SlBwd {
@@ -333,10 +296,8 @@ extern "C" int mpgan_ssim_loss_forward(const float* a, const float* b, const int
     const size_t smem = 2ul * SL_PLANE * sizeof(float);
     hipLaunchKernelGGL((sl_forward_kernel<1, 1>), grid, dim3(256), smem, st, p);
   }
-  hipLaunchKernelGGL(sl_item_kernel, dim3((unsigned)items), dim3(256), 0, st, (const double*)p.partials, g.fwd_tiles,
-                     1.0 / (double)g.M, ssim_item);
-  hipLaunchKernelGGL(sl_loss_kernel, dim3(1), dim3(64), 0, st, (const double*)ssim_item, (int)items, (int)channels,
-                     (int)reduction, loss);
+  // ssim_item = (sum of the item's tile partials) / M; loss = 1 - ssim over the items
+  launch_loss_tail(p.partials, g.fwd_tiles, 1.0 / (double)g.M, ssim_item, items, channels, reduction, true, loss, st);
   return check_launch("ssim_loss_forward");
 }
 

@@ -465,6 +465,10 @@ class GAN(nn.Module):
         # (DESIGN.md 7i); like every generator term it sees the pair fit_batch hands over, never DiffAugment's output
         self.edge_weight = float(edge_weight)
         self.edge_loss = EdgeLoss(eps=edge_eps) if self.edge_weight > 0 else None
+        # the active terms as (log name, weight, module), in the order _add_generator_terms adds them to g_loss
+        self._generator_terms = [(name, weight, module) for name, weight, module in (
+            ("g_mi_loss", self.mi_weight, self.mi_loss), ("g_ssim_loss", self.ssim_weight, self.ssim_loss),
+            ("g_edge_loss", self.edge_weight, self.edge_loss)) if module is not None]
         # opt-in differentiable augmentation of everything D sees in training_step (augment.py); with the
         # default "" there is no module and no launch.  aug_generator: a torch.Generator on the images' device, or None
         # for torch's global one (data-parallel runs: every rank seeds its own, or all ranks draw the same parameters)
@@ -524,6 +528,14 @@ class GAN(nn.Module):
         """Lightning's self.log: scalars stay on the device (no per-step sync)."""
         self.logged[name] = value.detach()
 
+    def _add_generator_terms(self, g_loss, generated_imgs, t2w_images, terms: dict):
+        """g_loss plus weight * term for every opt-in generator term, one scalar_axpby each in the list's order (that
+        order is the bits of g_loss); the terms' values go into `terms` under their log names."""
+        for name, weight, module in self._generator_terms:
+            terms[name] = module(generated_imgs, t2w_images)
+            g_loss = scalar_axpby(g_loss, 1.0, terms[name], weight)
+        return g_loss
+
     def training_step(self, batch, batch_idx, optimizer_idx):
         t1w_images, t2w_images = batch["t1w"], batch["t2w"]
         if optimizer_idx == 0:                      # GAN_final.py:254-273
@@ -535,18 +547,10 @@ class GAN(nn.Module):
             g_recon_loss = self.reconstruction_loss(generated_imgs, t2w_images)
             self.log("g_recon_loss", g_recon_loss)
             g_loss = scalar_axpby(g_adv_loss, 1.0, g_recon_loss, 1.0)
-            if self.mi_loss is not None:
-                g_mi_loss = self.mi_loss(generated_imgs, t2w_images)
-                self.log("g_mi_loss", g_mi_loss)
-                g_loss = scalar_axpby(g_loss, 1.0, g_mi_loss, self.mi_weight)
-            if self.ssim_loss is not None:
-                g_ssim_loss = self.ssim_loss(generated_imgs, t2w_images)
-                self.log("g_ssim_loss", g_ssim_loss)
-                g_loss = scalar_axpby(g_loss, 1.0, g_ssim_loss, self.ssim_weight)
-            if self.edge_loss is not None:
-                g_edge_loss = self.edge_loss(generated_imgs, t2w_images)
-                self.log("g_edge_loss", g_edge_loss)
-                g_loss = scalar_axpby(g_loss, 1.0, g_edge_loss, self.edge_weight)
+            terms = {}
+            g_loss = self._add_generator_terms(g_loss, generated_imgs, t2w_images, terms)
+            for name, value in terms.items():
+                self.log(name, value)
             self.log("g_loss", g_loss)
             return g_loss
         if optimizer_idx == 1:                      # GAN_final.py:276-296
@@ -579,15 +583,8 @@ class GAN(nn.Module):
             g_adv_loss = self.adversarial_loss(d_fake, self._labels(d_fake, 1.0))
             g_recon_loss = self.reconstruction_loss(generated_imgs, t2w_images)
             g_loss = scalar_axpby(g_adv_loss, 1.0, g_recon_loss, 1.0)
-            if self.mi_loss is not None:
-                g_mi_loss = self.mi_loss(generated_imgs, t2w_images)
-                g_loss = scalar_axpby(g_loss, 1.0, g_mi_loss, self.mi_weight)
-            if self.ssim_loss is not None:
-                g_ssim_loss = self.ssim_loss(generated_imgs, t2w_images)
-                g_loss = scalar_axpby(g_loss, 1.0, g_ssim_loss, self.ssim_weight)
-            if self.edge_loss is not None:
-                g_edge_loss = self.edge_loss(generated_imgs, t2w_images)
-                g_loss = scalar_axpby(g_loss, 1.0, g_edge_loss, self.edge_weight)
+            terms = {}
+            g_loss = self._add_generator_terms(g_loss, generated_imgs, t2w_images, terms)
             d_real = self._judge(t2w_images, t1w_images)
             real_loss = self.adversarial_loss(d_real, self._labels(d_real, self.hparams.one_sided_label_value))
             fake_loss = self.adversarial_loss(d_fake, self._labels(d_fake, 0.0))
@@ -595,12 +592,7 @@ class GAN(nn.Module):
             if self.generator_ema is not None:
                 ema_recon_loss = self.reconstruction_loss(self.generator_ema(t1w_images), t2w_images)
         out = {"val_g_adv_loss": g_adv_loss, "val_g_recon_loss": g_recon_loss, "val_g_loss": g_loss, "val_d_loss": d_loss}
-        if self.mi_loss is not None:
-            out["val_g_mi_loss"] = g_mi_loss
-        if self.ssim_loss is not None:
-            out["val_g_ssim_loss"] = g_ssim_loss
-        if self.edge_loss is not None:
-            out["val_g_edge_loss"] = g_edge_loss
+        out.update(("val_" + name, value) for name, value in terms.items())
         if self.generator_ema is not None:
             out["val_ema_g_recon_loss"] = ema_recon_loss
         for name, value in out.items():

@@ -27,26 +27,56 @@ _REDUCTIONS = ("mean", "sum", "none")
 MAX_BINS = 32
 
 
+def _check_reduction(reduction, who):
+    if reduction not in _REDUCTIONS:
+        raise ValueError(f"{who}: unknown reduction {reduction!r} (expected one of {_REDUCTIONS})")
+
+
+def _pair_inputs(pred, target, who, shape_error):
+    """The checks every pair loss makes, in their order: one shape, the loss's own rule for that shape
+    (shape_error(shape) gives the complaint or None), two fp32 device tensors."""
+    if pred.shape != target.shape:
+        raise ValueError(f"{who}: shape mismatch, pred {tuple(pred.shape)} and target {tuple(target.shape)}")
+    complaint = shape_error(tuple(pred.shape))
+    if complaint:
+        raise ValueError(f"{who}: {complaint}")
+    if pred.dtype != torch.float32 or target.dtype != torch.float32 or not (pred.is_cuda and target.is_cuda):
+        raise ValueError(f"{who}: expects two fp32 device tensors")
+
+
+def _pair_forward(pred, target, reduction, per_channel=True):
+    """What every pair loss's forward starts from: the contiguous inputs, (batch, channels, spatial), the empty loss of
+    the reduction and d loss / d(sum over the items) for an upstream gradient of 1.  Every (b, c) image is an item;
+    without per_channel the channels fold into the batch entry's item."""
+    a, b = pred.contiguous(), target.contiguous()         # a contiguous view keeps its (possibly unaligned) offset
+    batch, channels = a.shape[0], a.shape[1] if per_channel else 1
+    loss = torch.empty((batch,) if reduction == "none" else (), device=a.device)
+    scale = {"mean": 1.0 / (batch * channels), "sum": 1.0, "none": 1.0 / channels}[reduction]
+    return a, b, (batch, channels, tuple(a.shape[2:])), loss, scale
+
+
+def _pair_backward(ctx, gout, launch):
+    """(grad pred, grad target) of a pair loss: launch(gout, wrt, out) for each input that needs_input_grad names."""
+    gout = gout.contiguous()
+    like = ctx.saved_tensors[0]
+    return tuple(launch(gout, wrt, torch.empty_like(like)) if ctx.needs_input_grad[wrt] else None for wrt in (0, 1))
+
+
 def _config(num_bins, sigma_ratio, reduction, value_range, who):
     if int(num_bins) != num_bins or not 2 <= int(num_bins) <= MAX_BINS:
         raise ValueError(f"{who}: num_bins must be an integer in [2, {MAX_BINS}], got {num_bins!r}")
     if not sigma_ratio > 0:
         raise ValueError(f"{who}: sigma_ratio must be positive, got {sigma_ratio!r}")
-    if reduction not in _REDUCTIONS:
-        raise ValueError(f"{who}: unknown reduction {reduction!r} (expected one of {_REDUCTIONS})")
+    _check_reduction(reduction, who)
     ranges = _ranges(value_range)
     if not (ranges[1] > ranges[0] and ranges[3] > ranges[2]):
         raise ValueError(f"{who}: value_range needs hi > lo, got {value_range!r}")
     return int(num_bins), float(sigma_ratio), ranges
 
 
-def _inputs(pred, target, who):
-    if pred.shape != target.shape:
-        raise ValueError(f"{who}: shape mismatch, pred {tuple(pred.shape)} and target {tuple(target.shape)}")
-    if pred.dim() < 2 or pred.shape[0] < 1 or pred.numel() == 0:
-        raise ValueError(f"{who}: expects non-empty (B, C, *spatial) tensors, got {tuple(pred.shape)}")
-    if pred.dtype != torch.float32 or target.dtype != torch.float32 or not (pred.is_cuda and target.is_cuda):
-        raise ValueError(f"{who}: expects two fp32 device tensors")
+def _mi_shape_error(shape):
+    if len(shape) < 2 or 0 in shape:
+        return f"expects non-empty (B, C, *spatial) tensors, got {shape}"
 
 
 class _ParzenMIFn(torch.autograd.Function):
@@ -55,16 +85,14 @@ class _ParzenMIFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, target, bins, sigma_ratio, nr, dr, ranges, reduction):
-        a, b = pred.contiguous(), target.contiguous()     # a contiguous view keeps its (possibly unaligned) offset
-        batch = a.shape[0]
+        a, b, (batch, _, _), loss, scale = _pair_forward(pred, target, reduction, per_channel=False)
         dev = a.device
         need_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         ws = torch.empty(ops.parzen_mi_workspace(batch, a.numel() // batch, bins) // 8, dtype=torch.float64, device=dev)
         mi = torch.empty(batch, dtype=torch.float64, device=dev)
         coef = torch.empty((batch, 2, 32, 32), device=dev) if need_grad else None
-        loss = torch.empty((batch,) if reduction == "none" else (), device=dev)
         ops.parzen_mi_forward(a, b, batch, ranges, bins, sigma_ratio, nr, dr, ws, mi, None, coef, reduction, loss)
-        ctx.cfg = (batch, ranges, bins, sigma_ratio, -1.0 / batch if reduction == "mean" else -1.0)
+        ctx.cfg = (batch, ranges, bins, sigma_ratio, -scale)
         ctx.save_for_backward(a, b, coef)
         return loss
 
@@ -72,13 +100,8 @@ class _ParzenMIFn(torch.autograd.Function):
     def backward(ctx, gout):
         a, b, coef = ctx.saved_tensors
         batch, ranges, bins, sigma_ratio, scale = ctx.cfg
-        gout = gout.contiguous()
-        grads = [None, None]
-        for wrt in (0, 1):
-            if ctx.needs_input_grad[wrt]:
-                grads[wrt] = ops.parzen_mi_backward(a, b, batch, ranges, bins, sigma_ratio, coef, gout, scale, wrt,
-                                                    torch.empty_like(a))
-        return grads[0], grads[1], None, None, None, None, None, None
+        return _pair_backward(ctx, gout, lambda g, wrt, out: ops.parzen_mi_backward(
+            a, b, batch, ranges, bins, sigma_ratio, coef, g, scale, wrt, out)) + (None,) * 6
 
 
 def global_mutual_information_loss(pred: torch.Tensor, target: torch.Tensor, num_bins: int = 23,
@@ -90,7 +113,7 @@ def global_mutual_information_loss(pred: torch.Tensor, target: torch.Tensor, num
     output.  reduction: "mean" (a scalar), "sum", or "none" ((B,)).  A NaN sample makes its item's loss NaN."""
     who = "global_mutual_information_loss"
     bins, sigma_ratio, ranges = _config(num_bins, sigma_ratio, reduction, value_range, who)
-    _inputs(pred, target, who)
+    _pair_inputs(pred, target, who, _mi_shape_error)
     return _ParzenMIFn.apply(pred, target, bins, sigma_ratio, float(smooth_nr), float(smooth_dr), ranges, reduction)
 
 
@@ -116,7 +139,7 @@ def parzen_joint_histogram(a: torch.Tensor, b: torch.Tensor, num_bins: int = 23,
     tensors: rows indexed by a's bin, columns by b's; every item's entries sum to 1."""
     who = "parzen_joint_histogram"
     bins, sigma_ratio, ranges = _config(num_bins, sigma_ratio, "none", value_range, who)
-    _inputs(a, b, who)
+    _pair_inputs(a, b, who, _mi_shape_error)
     a, b = a.contiguous(), b.contiguous()
     batch = a.shape[0]
     ws = torch.empty(ops.parzen_mi_workspace(batch, a.numel() // batch, bins) // 8, dtype=torch.float64,
@@ -131,8 +154,7 @@ SSIM_WINDOW = 7
 
 
 def _ssim_config(value_range, reduction, who):
-    if reduction not in _REDUCTIONS:
-        raise ValueError(f"{who}: unknown reduction {reduction!r} (expected one of {_REDUCTIONS})")
+    _check_reduction(reduction, who)
     try:
         lo, hi = (float(v) for v in value_range)
     except (TypeError, ValueError):
@@ -142,18 +164,13 @@ def _ssim_config(value_range, reduction, who):
     return lo, hi
 
 
-def _ssim_inputs(pred, target, who):
-    if pred.shape != target.shape:
-        raise ValueError(f"{who}: shape mismatch, pred {tuple(pred.shape)} and target {tuple(target.shape)}")
-    if pred.dim() not in (4, 5) or pred.shape[0] < 1 or pred.shape[1] < 1:
-        raise ValueError(f"{who}: expects (B, C, H, W) or (B, C, D, H, W) tensors, got {tuple(pred.shape)}")
-    spatial = tuple(pred.shape[2:])
+def _ssim_shape_error(shape):
+    if len(shape) not in (4, 5) or shape[0] < 1 or shape[1] < 1:
+        return f"expects (B, C, H, W) or (B, C, D, H, W) tensors, got {shape}"
+    spatial = shape[2:]
     windowed = spatial[1:] if len(spatial) == 3 and spatial[0] == 1 else spatial      # a depth of 1 is a slice
     if min(windowed) < SSIM_WINDOW:
-        raise ValueError(f"{who}: spatial extents {spatial} are below the {SSIM_WINDOW}-wide window")
-    if pred.dtype != torch.float32 or target.dtype != torch.float32 or not (pred.is_cuda and target.is_cuda):
-        raise ValueError(f"{who}: expects two fp32 device tensors")
-    return spatial
+        return f"spatial extents {spatial} are below the {SSIM_WINDOW}-wide window"
 
 
 class _SSIMLossFn(torch.autograd.Function):
@@ -162,17 +179,14 @@ class _SSIMLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, target, lo, hi, reduction):
-        a, b = pred.contiguous(), target.contiguous()     # a contiguous view keeps its (possibly unaligned) offset
-        batch, channels, spatial = a.shape[0], a.shape[1], tuple(a.shape[2:])
+        a, b, (batch, channels, spatial), loss, scale = _pair_forward(pred, target, reduction)
         items, dev = batch * channels, a.device
         mask = int(ctx.needs_input_grad[0]) | (int(ctx.needs_input_grad[1]) << 1)
         ws_bytes, coef_bytes = ops.ssim_loss_workspace(spatial, items, mask)
         ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
         coef = torch.empty(coef_bytes // 8, dtype=torch.float64, device=dev) if mask else None
-        loss = torch.empty((batch,) if reduction == "none" else (), device=dev)
         ops.ssim_loss_forward(a, b, spatial, items, channels, lo, hi, mask, ws, coef, reduction, loss)
-        scale = {"mean": -1.0 / items, "sum": -1.0, "none": -1.0 / channels}[reduction]
-        ctx.cfg = (spatial, items, channels, lo, mask, scale)
+        ctx.cfg = (spatial, items, channels, lo, mask, -scale)
         ctx.save_for_backward(a, b, coef)
         return loss
 
@@ -180,13 +194,8 @@ class _SSIMLossFn(torch.autograd.Function):
     def backward(ctx, gout):
         a, b, coef = ctx.saved_tensors
         spatial, items, channels, lo, mask, scale = ctx.cfg
-        gout = gout.contiguous()
-        grads = [None, None]
-        for wrt in (0, 1):
-            if ctx.needs_input_grad[wrt]:
-                grads[wrt] = ops.ssim_loss_backward(a, b, spatial, items, channels, lo, mask, coef, gout, scale, wrt,
-                                                    torch.empty_like(a))
-        return grads[0], grads[1], None, None, None
+        return _pair_backward(ctx, gout, lambda g, wrt, out: ops.ssim_loss_backward(
+            a, b, spatial, items, channels, lo, mask, coef, g, scale, wrt, out)) + (None,) * 3
 
 
 def ssim_loss(pred: torch.Tensor, target: torch.Tensor, value_range=(0.0, 1.0), reduction: str = "mean") -> torch.Tensor:
@@ -197,7 +206,7 @@ def ssim_loss(pred: torch.Tensor, target: torch.Tensor, value_range=(0.0, 1.0), 
     entry the mean over its channels).  Differentiable in both arguments; bitwise reproducible."""
     who = "ssim_loss"
     lo, hi = _ssim_config(value_range, reduction, who)
-    _ssim_inputs(pred, target, who)
+    _pair_inputs(pred, target, who, _ssim_shape_error)
     return _SSIMLossFn.apply(pred, target, lo, hi, reduction)
 
 
@@ -214,8 +223,7 @@ class SSIMLoss(nn.Module):
 
 
 def _edge_config(eps, reduction, who):
-    if reduction not in _REDUCTIONS:
-        raise ValueError(f"{who}: unknown reduction {reduction!r} (expected one of {_REDUCTIONS})")
+    _check_reduction(reduction, who)
     try:
         eps = float(eps)
     except (TypeError, ValueError):
@@ -225,20 +233,17 @@ def _edge_config(eps, reduction, who):
     return eps
 
 
-def _edge_input(x, who, name="x"):
-    if x.dim() not in (4, 5) or x.numel() == 0:
-        raise ValueError(f"{who}: expects non-empty (B, C, H, W) or (B, C, D, H, W) tensors, got {name} "
-                         f"{tuple(x.shape)}")
+def _edge_shape_error(shape):
+    if len(shape) not in (4, 5) or 0 in shape:
+        return f"expects non-empty (B, C, H, W) or (B, C, D, H, W) tensors, got {shape}"
+
+
+def _edge_input(x, who):
+    complaint = _edge_shape_error(tuple(x.shape))
+    if complaint:
+        raise ValueError(f"{who}: {complaint}")
     if x.dtype != torch.float32 or not x.is_cuda:
         raise ValueError(f"{who}: expects fp32 device tensors")
-    return tuple(x.shape[2:])
-
-
-def _edge_inputs(pred, target, who):
-    if pred.shape != target.shape:
-        raise ValueError(f"{who}: shape mismatch, pred {tuple(pred.shape)} and target {tuple(target.shape)}")
-    _edge_input(pred, who, "pred")
-    return _edge_input(target, who, "target")
 
 
 class _SobelMagnitudeFn(torch.autograd.Function):
@@ -274,13 +279,10 @@ class _EdgeLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, target, eps, reduction):
-        a, b = pred.contiguous(), target.contiguous()     # a contiguous view keeps its (possibly unaligned) offset
-        batch, channels, spatial = a.shape[0], a.shape[1], tuple(a.shape[2:])
-        items, dev = batch * channels, a.device
-        ws = torch.empty(ops.edge_loss_workspace(spatial, items) // 8, dtype=torch.float64, device=dev)
-        loss = torch.empty((batch,) if reduction == "none" else (), device=dev)
+        a, b, (batch, channels, spatial), loss, scale = _pair_forward(pred, target, reduction)
+        items = batch * channels
+        ws = torch.empty(ops.edge_loss_workspace(spatial, items) // 8, dtype=torch.float64, device=a.device)
         ops.edge_loss_forward(a, b, spatial, items, channels, eps, ws, reduction, loss)
-        scale = {"mean": 1.0 / items, "sum": 1.0, "none": 1.0 / channels}[reduction]
         ctx.cfg = (spatial, items, channels, eps, scale)
         ctx.save_for_backward(a, b)
         return loss
@@ -289,13 +291,8 @@ class _EdgeLossFn(torch.autograd.Function):
     def backward(ctx, gout):
         a, b = ctx.saved_tensors
         spatial, items, channels, eps, scale = ctx.cfg
-        gout = gout.contiguous()
-        grads = [None, None]
-        for wrt in (0, 1):
-            if ctx.needs_input_grad[wrt]:
-                grads[wrt] = ops.edge_loss_backward(a, b, spatial, items, channels, eps, gout, scale, wrt,
-                                                    torch.empty_like(a))
-        return grads[0], grads[1], None, None
+        return _pair_backward(ctx, gout, lambda g, wrt, out: ops.edge_loss_backward(
+            a, b, spatial, items, channels, eps, g, scale, wrt, out)) + (None,) * 2
 
 
 def edge_loss(pred: torch.Tensor, target: torch.Tensor, eps: float = 1e-6, reduction: str = "mean") -> torch.Tensor:
@@ -306,7 +303,7 @@ def edge_loss(pred: torch.Tensor, target: torch.Tensor, eps: float = 1e-6, reduc
     both arguments; bitwise reproducible."""
     who = "edge_loss"
     eps = _edge_config(eps, reduction, who)
-    _edge_inputs(pred, target, who)
+    _pair_inputs(pred, target, who, _edge_shape_error)
     return _EdgeLossFn.apply(pred, target, eps, reduction)
 
 

@@ -952,8 +952,20 @@ def norm_act_add_fold(z, pz: Prologue, fold: NormFoldC, r, pr: Optional[Prologue
     return out
 
 
-# ---- Parzen-window mutual information (csrc/mi_loss.hip; losses.py holds the autograd node) ----
-_PMI_REDUCTIONS = {"mean": 0, "sum": 1, "none": 2}
+# ---- the pair losses (losses.py holds the autograd nodes) ----
+_REDUCTIONS = {"mean": 0, "sum": 1, "none": 2}
+
+
+def _nbytes(t) -> int:
+    return 0 if t is None else t.numel() * t.element_size()
+
+
+def _up_stride(upstream) -> int:
+    """0: one upstream gradient for every item (a reduced loss); 1: one per batch entry."""
+    return 0 if upstream.numel() == 1 else 1
+
+
+# ---- Parzen-window mutual information (csrc/mi_loss.hip) ----
 
 
 def parzen_mi_workspace(batch: int, numel_per_item: int, bins: int) -> int:
@@ -970,8 +982,8 @@ def parzen_mi_forward(a, b, batch, ranges, bins, sigma_ratio, smooth_nr, smooth_
     lo_a, hi_a, lo_b, hi_b = ranges
     check(lib().mpgan_parzen_mi_forward(a.data_ptr(), b.data_ptr(), a.numel() // batch, batch, lo_a, hi_a, lo_b, hi_b,
                                         int(bins), float(sigma_ratio), float(smooth_nr), float(smooth_dr),
-                                        workspace.data_ptr(), workspace.numel() * workspace.element_size(),
-                                        _ptr(joint), mi.data_ptr(), _ptr(coef), _PMI_REDUCTIONS[reduction],
+                                        workspace.data_ptr(), _nbytes(workspace),
+                                        _ptr(joint), mi.data_ptr(), _ptr(coef), _REDUCTIONS[reduction],
                                         _ptr(loss), _stream()), "parzen_mi_forward")
     return mi
 
@@ -981,7 +993,7 @@ def parzen_mi_backward(a, b, batch, ranges, bins, sigma_ratio, coef, upstream, s
     lo_a, hi_a, lo_b, hi_b = ranges
     check(lib().mpgan_parzen_mi_backward(a.data_ptr(), b.data_ptr(), a.numel() // batch, batch, lo_a, hi_a, lo_b, hi_b,
                                          int(bins), float(sigma_ratio), coef.data_ptr(), upstream.data_ptr(),
-                                         0 if upstream.numel() == 1 else 1, float(scale), int(wrt), grad.data_ptr(),
+                                         _up_stride(upstream), float(scale), int(wrt), grad.data_ptr(),
                                          _stream()), "parzen_mi_backward")
     return grad
 
@@ -1005,19 +1017,18 @@ def ssim_loss_forward(a, b, spatial, items, channels, lo, hi, grad_mask, workspa
     """loss (fp32, reduced on the device) of two contiguous fp32 tensors; with grad_mask != 0 also the backward's
     coefficient maps (see include/mpgan_hip.h)."""
     check(lib().mpgan_ssim_loss_forward(a.data_ptr(), b.data_ptr(), _dhw(spatial), int(items), int(channels), float(lo),
-                                        float(hi), int(grad_mask), workspace.data_ptr(),
-                                        workspace.numel() * workspace.element_size(), _ptr(coef),
-                                        coef.numel() * coef.element_size() if coef is not None else 0,
-                                        _PMI_REDUCTIONS[reduction], loss.data_ptr(), _stream()), "ssim_loss_forward")
+                                        float(hi), int(grad_mask), workspace.data_ptr(), _nbytes(workspace),
+                                        _ptr(coef), _nbytes(coef),
+                                        _REDUCTIONS[reduction], loss.data_ptr(), _stream()), "ssim_loss_forward")
     return loss
 
 
 def ssim_loss_backward(a, b, spatial, items, channels, lo, grad_mask, coef, upstream, scale, wrt, grad):
     """grad = upstream[batch entry or 0] * scale * d ssim_item / d (a if wrt == 0 else b)."""
     check(lib().mpgan_ssim_loss_backward(a.data_ptr(), b.data_ptr(), _dhw(spatial), int(items), int(channels), float(lo),
-                                         int(grad_mask), coef.data_ptr(), coef.numel() * coef.element_size(),
-                                         upstream.data_ptr(), 0 if upstream.numel() == 1 else 1, float(scale), int(wrt),
-                                         grad.data_ptr(), _stream()), "ssim_loss_backward")
+                                         int(grad_mask), coef.data_ptr(), _nbytes(coef), upstream.data_ptr(),
+                                         _up_stride(upstream), float(scale), int(wrt), grad.data_ptr(), _stream()),
+          "ssim_loss_backward")
     return grad
 
 
@@ -1047,15 +1058,15 @@ def edge_loss_workspace(spatial, items: int) -> int:
 def edge_loss_forward(a, b, spatial, items, channels, eps, workspace, reduction, loss):
     """loss (fp32, reduced on the device) of two contiguous fp32 tensors; no magnitude map is written."""
     check(lib().mpgan_edge_loss_forward(a.data_ptr(), b.data_ptr(), _dhw(spatial), int(items), int(channels), float(eps),
-                                        workspace.data_ptr(), workspace.numel() * workspace.element_size(),
-                                        _PMI_REDUCTIONS[reduction], loss.data_ptr(), _stream()), "edge_loss_forward")
+                                        workspace.data_ptr(), _nbytes(workspace), _REDUCTIONS[reduction],
+                                        loss.data_ptr(), _stream()), "edge_loss_forward")
     return loss
 
 
 def edge_loss_backward(a, b, spatial, items, channels, eps, upstream, scale, wrt, grad):
     """grad = upstream[batch entry or 0] * scale * d loss_item / d (a if wrt == 0 else b)."""
     check(lib().mpgan_edge_loss_backward(a.data_ptr(), b.data_ptr(), _dhw(spatial), int(items), int(channels),
-                                         float(eps), upstream.data_ptr(), 0 if upstream.numel() == 1 else 1,
+                                         float(eps), upstream.data_ptr(), _up_stride(upstream),
                                          float(scale), int(wrt), grad.data_ptr(), _stream()), "edge_loss_backward")
     return grad
 

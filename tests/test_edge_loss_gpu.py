@@ -13,6 +13,9 @@ All kernels tile z-y-x as 4 x 8 x 32 (1 x 8 x 32 when the image is one plane).  
     m (1,1,21,37)                      passed at a storage offset of one element: data_ptr % 16 == 4
     n (1,1,12,24,96)                   3 x 3 x 3 tiles: the middle one touches no face of the image and runs the gather
                                        with the constant interior weights
+    o (2,2,136,544)                    17 x 17 = 289 tiles per item, more than the 256 threads of the block that adds an
+                                       item's partials: the loss alone, under every reduction (not in edge_loss_ref.CASES,
+                                       whose every entry also runs the gradient and map tests)
 
 The bound, for the loss, the map and each gradient (max-abs over the tensor), is the one of test_ssim_loss_gpu.py:
 
@@ -35,6 +38,7 @@ from mpgan_amd.gan import reconstruction_loss
 pytestmark = pytest.mark.gpu
 
 CASES = list(R.CASES)
+WIDE, WIDE_SEED = (2, 2, 136, 544), 40 + len(CASES)                # shape o, the loss alone
 
 
 def _dev(x, case=""):
@@ -163,6 +167,24 @@ def test_reductions_upstream_and_second_backward(reduction):
     (3 * out).backward()                                           # the upstream scalar enters as one more factor
     assert float((p.grad - 3 * g1p).abs().max()) <= 4 * 2.0 ** -23 * 3 * float(g1p.abs().max())
     assert float((t.grad - 3 * g1t).abs().max()) <= 4 * 2.0 ** -23 * 3 * float(g1t.abs().max())
+
+
+@functools.lru_cache(maxsize=None)
+def _wide_reference():
+    """(pred, target) of shape o and the loss of every (b, c) image in fp64 and in fp32, once on the CPU."""
+    pred, target = R.structured_pair(WIDE, seed=WIDE_SEED)
+    return pred, target, R.loss_items(pred, target), R.loss_items(pred, target, dtype=torch.float32)
+
+
+@pytest.mark.parametrize("reduction", ["mean", "sum", "none"])
+def test_more_than_256_tiles_per_item(reduction):
+    """Shape o: an item's tile partials outnumber the 256 threads of the block that adds them.  That kernel's own error
+    is one fp32 rounding of an fp64 sum (6e-8 relative), inside the bound's additive term."""
+    pred, target, i64, i32 = _wide_reference()
+    loss = losses.EdgeLoss(reduction=reduction)(pred.cuda(), target.cuda())
+    assert tuple(loss.shape) == ((2,) if reduction == "none" else ())
+    reduce = {"mean": lambda x: x.mean(), "sum": lambda x: x.sum(), "none": lambda x: x.mean(dim=1)}[reduction]
+    _bound(f"shape o {reduction} loss", loss, reduce(i64), reduce(i32))
 
 
 def test_none_is_one_entry_per_batch_item_with_its_own_upstream():

@@ -2,7 +2,8 @@
 
 Both kernels tile y-x as 8 x 32 and z as 4 (the forward over window corners, the backward over samples), so the
 shapes the definition's issue lists cross every tile edge; case "h" adds a volume that spans two tiles with a ragged
-remainder on every axis of both launches (corners 7 x 11 x 35, samples 13 x 17 x 41).
+remainder on every axis of both launches (corners 7 x 11 x 35, samples 13 x 17 x 41); case "i" gives an item more
+forward tiles than the 256 threads of the block that adds them (the loss alone, under every reduction).
 
 The bound, for the loss and for each gradient (max-abs over the tensor):
 
@@ -29,7 +30,9 @@ CASES = {
     "f": (2, 1, 13, 21, 37),       # 3-D
     "g": (1, 1, 21, 37),           # passed at a storage offset of one element: data_ptr % 16 == 4
     "h": (1, 1, 13, 17, 41),       # two tiles and a ragged remainder on every axis, forward and backward
+    "i": (2, 2, 136, 544),         # 17 x 17 = 289 forward tiles per item: the item kernel's 256-stride loop wraps (loss only)
 }
+GRAD_CASES = [case for case in CASES if case != "i"]
 RANGE = (-1.0, 1.0)
 
 
@@ -73,7 +76,7 @@ def _run(case, reduction="mean", grad=(True, True)):
     return p, t, losses.SSIMLoss(RANGE, reduction)(p, t)
 
 
-@pytest.mark.parametrize("case", list(CASES))
+@pytest.mark.parametrize("case", GRAD_CASES)
 def test_loss_and_both_gradients(case):
     p, t, loss = _run(case)
     assert loss.shape == () and loss.dtype == torch.float32
@@ -82,6 +85,24 @@ def test_loss_and_both_gradients(case):
     _bound(f"case {case} loss", loss, l64, l32)
     _bound(f"case {case} grad pred", p.grad, gp64, gp32)
     _bound(f"case {case} grad target", t.grad, gt64, gt32)
+
+
+@functools.lru_cache(maxsize=None)
+def _items_reference(case):
+    """ssim of every (b, c) image in fp64 and in fp32, once on the CPU."""
+    pred, target = _inputs(case)
+    return tuple(R.ssim_items(pred, target, RANGE, dtype) for dtype in (torch.float64, torch.float32))
+
+
+@pytest.mark.parametrize("reduction", ["mean", "sum", "none"])
+def test_more_than_256_tiles_per_item(reduction):
+    """Case i: an item's tile partials outnumber the item kernel's 256 threads.  The kernel's own error is one fp32
+    rounding of an fp64 sum (6e-8 relative), inside the bound's additive term."""
+    _, _, loss = _run("i", reduction, grad=(False, False))
+    assert tuple(loss.shape) == ((2,) if reduction == "none" else ())
+    reduce = {"mean": lambda x: x.mean(), "sum": lambda x: x.sum(), "none": lambda x: x.mean(dim=1)}[reduction]
+    i64, i32 = _items_reference("i")
+    _bound(f"case i {reduction} loss", loss, reduce(1.0 - i64), reduce(1.0 - i32))
 
 
 @pytest.mark.parametrize("shape", [(23, 41), (9, 17, 35)])
