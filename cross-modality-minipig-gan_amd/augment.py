@@ -225,6 +225,12 @@ def sample_affine_params(n: int, spatial: Sequence[int], *, rotate=0.0, scale: f
     axes), the prob gate (n,) when prob < 1, then sigma (n, number of planes) and its gate (n, number of planes) when
     noise_prob < 1.  A disabled op (rotate 0, scale 0, shift 0, no flip axis, prob 1 or 0, noise_std 0, noise_prob 1 or
     0) draws nothing and leaves its neutral entry; with prob 0 no spatial op draws.  In 2-D the d row and column of A are (1, 0, 0) and t_d = 0."""
+    return _sample_affine(n, spatial, rotate, scale, shift, flip, prob, noise_std, noise_prob, noise_planes, generator,
+                          device)[0]
+
+
+def _sample_affine(n, spatial, rotate, scale, shift, flip, prob, noise_std, noise_prob, noise_planes, generator, device):
+    """sample_affine_params and the boolean (n,) gate of its `prob` draw (None when 0 < prob < 1 does not hold)."""
     spatial = tuple(int(s) for s in spatial)
     if len(spatial) not in (2, 3) or min(spatial) < 1:
         raise ValueError(f"sample_affine_params: spatial must be (H, W) or (D, H, W) with extents >= 1, got {spatial}")
@@ -266,9 +272,11 @@ def sample_affine_params(n: int, spatial: Sequence[int], *, rotate=0.0, scale: f
         A[0], t[0] = [one, zero, zero], zero
         A[1][0], A[2][0] = zero, zero
     theta = torch.stack([A[i][j] if j < 3 else t[i] for i in range(3) for j in range(4)], 1)
+    gate = None
     if 0.0 < prob < 1.0:
         identity = torch.eye(3, 4, dtype=torch.float64, device=device).reshape(1, 12)
-        theta = torch.where((torch.rand((n,), **kw) < prob)[:, None], theta, identity)
+        gate = torch.rand((n,), **kw) < prob
+        theta = torch.where(gate[:, None], theta, identity)
     sigma = torch.zeros((n, 2), dtype=torch.float32, device=device)
     if noise_std > 0 and planes and noise_prob > 0.0:
         draw = torch.rand((n, len(planes)), **kw) * float(noise_std)
@@ -276,7 +284,7 @@ def sample_affine_params(n: int, spatial: Sequence[int], *, rotate=0.0, scale: f
             draw = torch.where(torch.rand((n, len(planes)), **kw) < noise_prob, draw, torch.zeros_like(draw))
         for j, k in enumerate(planes):
             sigma[:, k] = draw[:, j].to(torch.float32)
-    return AffineParams(theta.contiguous(), sigma)
+    return AffineParams(theta.contiguous(), sigma), gate
 
 
 def affine_warp(x: torch.Tensor, theta: torch.Tensor, x1: Optional[torch.Tensor] = None, *, out_size=None,
@@ -287,28 +295,171 @@ def affine_warp(x: torch.Tensor, theta: torch.Tensor, x1: Optional[torch.Tensor]
     "constant" gives a corner outside it the value `fill` (one number, or one per plane).  noise: a field of the
     output's shape for plane 0, or a pair (field or None, field or None); plane k then gets + sigma[:, k] * noise_k
     (sigma (B, 2) float32).  Not differentiable: an input that requires grad is refused."""
+    planes, fills, noises, outs = _warp_arguments("affine_warp", x, x1, out_size, mode, fill, noise)
+    ops.affine_warp(planes[0], planes[1] if x1 is not None else None, theta, WARP_MODES[mode], fills[0], fills[1],
+                    noises[0], noises[1], sigma, outs[0], outs[1] if x1 is not None else None)
+    return outs[0] if x1 is None else (outs[0], outs[1])
+
+
+def _warp_arguments(what, x, x1, out_size, mode, fill, noise):
+    """The checks affine_warp and deform_warp share: (detached contiguous planes, fills, noises, new outputs)."""
     planes = [x] if x1 is None else [x, x1]
     for t in planes:
         if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ValueError("affine_warp: every tensor must be on the GPU (there is no CPU path)")
+            raise ValueError(f"{what}: every tensor must be on the GPU (there is no CPU path)")
         if t.requires_grad and torch.is_grad_enabled():
-            raise ValueError("affine_warp: not differentiable (an input requires grad); call it under torch.no_grad() "
+            raise ValueError(f"{what}: not differentiable (an input requires grad); call it under torch.no_grad() "
                              "or on detached tensors")
     if mode not in WARP_MODES:
-        raise ValueError(f"affine_warp: mode must be one of {sorted(WARP_MODES)}, got {mode!r}")
+        raise ValueError(f"{what}: mode must be one of {sorted(WARP_MODES)}, got {mode!r}")
     fills = (float(fill),) * 2 if isinstance(fill, (int, float)) else tuple(float(f) for f in fill)
     if len(fills) != 2:
-        raise ValueError(f"affine_warp: fill is one number or one per plane, got {fill!r}")
+        raise ValueError(f"{what}: fill is one number or one per plane, got {fill!r}")
     noises = [noise, None] if noise is None or isinstance(noise, torch.Tensor) else list(noise)
     if len(noises) != 2:
-        raise ValueError("affine_warp: noise is one field (plane 0) or a pair")
+        raise ValueError(f"{what}: noise is one field (plane 0) or a pair")
     planes = [t.detach().contiguous() for t in planes]
     out_size = tuple(x.shape[2:]) if out_size is None else tuple(int(s) for s in out_size)
     if len(out_size) != x.dim() - 2:
-        raise ValueError(f"affine_warp: out_size {out_size} for a {x.dim() - 2}-D image")
+        raise ValueError(f"{what}: out_size {out_size} for a {x.dim() - 2}-D image")
     outs = [torch.empty((x.shape[0], 1, *out_size), dtype=torch.float32, device=x.device) for _ in planes]
-    ops.affine_warp(planes[0], planes[1] if x1 is not None else None, theta, WARP_MODES[mode], fills[0], fills[1],
-                    noises[0], noises[1], sigma, outs[0], outs[1] if x1 is not None else None)
+    return planes, fills, noises, outs
+
+
+# ---- elastic deformation and MRI intensity augmentation of the same pair (DESIGN.md 7j; the same file's second kernel) ---
+# A smooth non-rigid warp on both images, a smooth multiplicative bias field and a gamma change on the input alone:
+#
+#     q = sample_deform_params(B, S, elastic=0.3, bias_field=0.3, gamma=0.3, device=x.device)
+#     t1, t2 = deform_warp(t1w, p.theta, t2w, ctrl=q.ctrl, gain=q.gain, gamma=q.gamma)
+#     batch = PairAugment(rotate=0.3, elastic=0.3, bias_field=0.3, gamma=0.3)(batch)
+ELASTIC_MAX = 0.4                                     # of the lattice spacing: below it p + u(p) cannot fold
+LATTICE_MIN, LATTICE_MAX = 4, 64
+
+
+class DeformParams(NamedTuple):
+    """One draw, each table None when its option is off: ctrl (B, ndim, *grid) float64, the control displacements of the
+    (d, h, w) coordinate in voxels; gain (B, *grid) float64, the control values of the log-gain; gamma (B, 2) float64,
+    the exponent of plane 0 and plane 1."""
+    ctrl: Optional[torch.Tensor]
+    gain: Optional[torch.Tensor]
+    gamma: Optional[torch.Tensor]
+
+
+def _lattice(grid, spatial, what: str):
+    """One int (every axis of extent > 1; an axis of extent 1 gets 1) or one per axis -> the lattice extents."""
+    if isinstance(grid, int):
+        if not LATTICE_MIN <= grid <= LATTICE_MAX:
+            raise ValueError(f"{what}: a lattice extent is in [{LATTICE_MIN}, {LATTICE_MAX}], got {grid!r}")
+        return (grid,) if spatial is None else tuple(grid if s > 1 else 1 for s in spatial)
+    grid = tuple(int(g) for g in grid)
+    if len(grid) not in ((2, 3) if spatial is None else (len(spatial),)):
+        raise ValueError(f"{what}: one int or one per axis, got {grid!r}")
+    for k, g in enumerate(grid):                      # (spatial None: the extents are not known yet, 1 may be right)
+        if g != 1 if spatial is not None and spatial[k] == 1 else not (LATTICE_MIN <= g <= LATTICE_MAX
+                                                                       or (spatial is None and g == 1)):
+            raise ValueError(f"{what}: a lattice extent is in [{LATTICE_MIN}, {LATTICE_MAX}] (1 on an axis of extent 1), got {grid!r}")
+    return grid
+
+
+def _check_deform_options(elastic, elastic_grid, bias_field, bias_grid, gamma, intensity_prob, intensity_planes,
+                          spatial=None):
+    if not 0.0 <= float(elastic) <= ELASTIC_MAX:
+        raise ValueError(f"elastic must be in [0, {ELASTIC_MAX}] (a fraction of the lattice spacing; beyond it the map can "
+                         f"fold), got {elastic!r}")
+    for name, v in (("bias_field", bias_field), ("gamma", gamma)):
+        if not float(v) >= 0:
+            raise ValueError(f"{name} must be >= 0, got {v!r}")
+    if not 0.0 <= float(intensity_prob) <= 1.0:
+        raise ValueError(f"intensity_prob must be in [0, 1], got {intensity_prob!r}")
+    planes = sorted({int(k) for k in intensity_planes})
+    if any(k not in (0, 1) for k in planes):
+        raise ValueError(f"intensity_planes: a subset of (0, 1), got {tuple(intensity_planes)!r}")
+    return _lattice(elastic_grid, spatial, "elastic_grid"), _lattice(bias_grid, spatial, "bias_grid"), planes
+
+
+def sample_deform_params(n: int, spatial: Sequence[int], *, elastic: float = 0.0, elastic_grid=6, bias_field: float = 0.0,
+                         bias_grid=4, gamma: float = 0.0, intensity_prob: float = 1.0,
+                         intensity_planes: Sequence[int] = (0,), spatial_gate: Optional[torch.Tensor] = None,
+                         generator: Optional[torch.Generator] = None, device="cpu") -> DeformParams:
+    """Draw the lattices of `n` samples of extent `spatial` ((H, W) or (D, H, W)), in pure torch ops on `device`, float64
+    (no host sync).  A lattice of extent g_k over S_k voxels has the spacing delta_k = (S_k - 1) / (g_k - 3)
+    (include/mpgan_hip.h: mpgan_deform_warp).
+    elastic:      in [0, 0.4]: ctrl[:, k] = elastic * delta_k * U[-1, 1].  A B-spline deformation whose control
+                  displacements stay below about 0.4 of the spacing cannot fold, hence the cap.
+    elastic_grid, bias_grid: one int in [4, 64] or one per axis (an axis of extent 1 has the lattice extent 1).
+    bias_field:   >= 0: the control values of the log-gain are bias_field * U[-1, 1] (the gain stays within e^+-bias_field).
+    gamma:        >= 0: gamma[s][k] = exp(gamma * U[-1, 1]) for the planes of intensity_planes, exactly 1.0 for the others.
+    intensity_prob: one gate per sample for gain and gamma together; a gated-off sample gets an all-zero gain lattice and
+                  gamma 1.0, which deform_warp turns into a bit copy of the ungained value.
+    spatial_gate: a boolean (n,) tensor (PairAugment passes on the gate of its `prob` draw): a gated-off sample gets a
+                  zero ctrl.  It draws nothing.
+    Draw order, one torch.rand each: ctrl (n, ndim, *elastic_grid), gain (n, *bias_grid), gamma (n, number of planes),
+    then the intensity gate (n,) when 0 < intensity_prob < 1 and gain or gamma is on.  A disabled option (elastic 0;
+    bias_field 0, gamma 0, no plane or intensity_prob 0) draws nothing and returns None for its table."""
+    spatial = tuple(int(s) for s in spatial)
+    if len(spatial) not in (2, 3) or min(spatial) < 1:
+        raise ValueError(f"sample_deform_params: spatial must be (H, W) or (D, H, W) with extents >= 1, got {spatial}")
+    eg, bg, planes = _check_deform_options(elastic, elastic_grid, bias_field, bias_grid, gamma, intensity_prob,
+                                           intensity_planes, spatial)
+    device = torch.device(device)
+    kw = dict(generator=generator, device=device, dtype=torch.float64)
+    ctrl = gain = gam = None
+    if elastic > 0:
+        delta = torch.tensor([(s - 1) / (g - 3) if g > 1 else 0.0 for s, g in zip(spatial, eg)], dtype=torch.float64)
+        delta = (float(elastic) * delta).to(device).view(1, len(spatial), *[1] * len(spatial))
+        ctrl = (2.0 * torch.rand((n, len(spatial), *eg), **kw) - 1.0) * delta
+        if spatial_gate is not None:
+            ctrl = torch.where(spatial_gate.view(n, *[1] * (ctrl.dim() - 1)), ctrl, torch.zeros_like(ctrl))
+        ctrl = ctrl.contiguous()
+    live = intensity_prob > 0.0 and bool(planes)
+    if live and bias_field > 0:
+        gain = float(bias_field) * (2.0 * torch.rand((n, *bg), **kw) - 1.0)
+    if live and gamma > 0:
+        gam = torch.ones((n, 2), dtype=torch.float64, device=device)
+        draw = torch.exp(float(gamma) * (2.0 * torch.rand((n, len(planes)), **kw) - 1.0))
+        for j, k in enumerate(planes):
+            gam[:, k] = draw[:, j]
+    if intensity_prob < 1.0 and (gain is not None or gam is not None):
+        on = torch.rand((n,), **kw) < intensity_prob
+        if gain is not None:
+            gain = torch.where(on.view(n, *[1] * len(bg)), gain, torch.zeros_like(gain))
+        if gam is not None:
+            gam = torch.where(on[:, None], gam, torch.ones_like(gam))
+    return DeformParams(ctrl, None if gain is None else gain.contiguous(), gam)
+
+
+def deform_warp(x: torch.Tensor, theta: torch.Tensor, x1: Optional[torch.Tensor] = None, *, ctrl=None, gain=None,
+                gain_planes: Sequence[int] = (0,), gamma=None, value_range=(-1.0, 1.0), out_size=None,
+                mode: str = "border", fill=-1.0, noise=None, sigma: Optional[torch.Tensor] = None):
+    """affine_warp with an elastic deformation of the map and an intensity change of the values, in the same one launch
+    (include/mpgan_hip.h: mpgan_deform_warp):  c = (A p + t) + u(p) with u the cubic B-spline of the control
+    displacements ctrl (B, ndim, *grid) float64, in voxels, over the OUTPUT extent; on the planes listed in `gain_planes`
+    v += (v - lo) * expm1(b(p)) with b the B-spline of the log-gain lattice gain (B, *grid) float64; then
+    v = lo + (hi - lo) * ((v - lo) / (hi - lo)) ** gamma[:, k] with gamma (B, 2) float64 and (lo, hi) = value_range; then
+    the noise term.  ctrl, gain and gamma may each be None (that term is absent); zero lattices and gamma 1 give
+    affine_warp's bits, and a value of exactly lo stays lo.  The other arguments are affine_warp's.  Not differentiable."""
+    planes, fills, noises, outs = _warp_arguments("deform_warp", x, x1, out_size, mode, fill, noise)
+    ndim = x.dim() - 2
+    for t, lead, name in ((ctrl, 2, "ctrl"), (gain, 1, "gain")):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dim() != lead + ndim or t.dtype != torch.float64
+                              or (name == "ctrl" and t.shape[1] != ndim)):
+            raise ValueError(f"deform_warp: {name} must be a float64 (B, {'ndim, ' if lead == 2 else ''}*grid) tensor for a "
+                             f"{ndim}-D image, got {tuple(t.shape) if isinstance(t, torch.Tensor) else t!r}")
+    if ndim == 2:                                     # the d channel and the d extent of a 2-D lattice
+        if ctrl is not None:
+            ctrl = torch.cat([torch.zeros_like(ctrl[:, :1]), ctrl], 1).unsqueeze(2)
+        if gain is not None:
+            gain = gain.unsqueeze(1)
+    mask = 0
+    if gain is not None:
+        if any(int(k) not in (0, 1) for k in gain_planes):
+            raise ValueError(f"deform_warp: gain_planes is a subset of (0, 1), got {tuple(gain_planes)!r}")
+        mask = sum(1 << k for k in {int(k) for k in gain_planes})
+    lo, hi = (float(v) for v in value_range)
+    ops.deform_warp(planes[0], planes[1] if x1 is not None else None, theta,
+                    None if ctrl is None else ctrl.contiguous(), None if gain is None else gain.contiguous(), mask, gamma,
+                    lo, hi, WARP_MODES[mode], fills[0], fills[1], noises[0], noises[1], sigma, outs[0],
+                    outs[1] if x1 is not None else None)
     return outs[0] if x1 is None else (outs[0], outs[1])
 
 
@@ -319,12 +470,33 @@ class PairAugment(nn.Module):
     batch["t1w"] and batch["t2w"] under the same draw in one launch, adds sigma * N(0, 1) to `noise_keys` (the field: one
     torch.randn of shape (number of noise keys, *t1w.shape) from the same generator, after the parameters; none is
     drawn when noise_std is 0) and returns a new dict; the other entries pass through.  `.last_params` is the last
-    draw, `.last_noise` its field (or None).  No parameters, no buffers, no gradient."""
+    draw, `.last_noise` its field (or None).  No parameters, no buffers, no gradient.
+
+    elastic, elastic_grid, bias_field, bias_grid, gamma, intensity_prob (sample_deform_params; kept in
+    `.deform_options`), intensity_keys and value_range add an elastic deformation of both images under the same lattice
+    and a bias field and gamma change on `intensity_keys`: with any of elastic, bias_field, gamma above 0 the one launch
+    is deform_warp's, the lattices are drawn after the affine parameters and before the noise field, a sample that the
+    `prob` gate turned off gets no deformation either (with prob 0 none is drawn), and `.last_deform` holds the
+    DeformParams.  With all three 0 nothing changes: affine_warp, the same draws, `.last_deform` None."""
 
     def __init__(self, rotate=0.0, scale: float = 0.0, shift=0.0, flip: Sequence[int] = (), prob: float = 1.0,
                  noise_std: float = 0.0, noise_prob: float = 1.0, noise_keys: Sequence[str] = ("t1w",),
-                 mode: str = "border", fill: float = -1.0, generator: Optional[torch.Generator] = None):
+                 mode: str = "border", fill: float = -1.0, generator: Optional[torch.Generator] = None,
+                 elastic: float = 0.0, elastic_grid=6, bias_field: float = 0.0, bias_grid=4, gamma: float = 0.0,
+                 intensity_prob: float = 1.0, intensity_keys: Sequence[str] = ("t1w",), value_range=(-1.0, 1.0)):
         super().__init__()
+        intensity_keys = (intensity_keys,) if isinstance(intensity_keys, str) else tuple(intensity_keys)
+        if any(k not in PAIR_KEYS for k in intensity_keys):
+            raise ValueError(f"PairAugment: intensity_keys must be a subset of {PAIR_KEYS}, got {intensity_keys!r}")
+        self.intensity_planes = sorted({PAIR_KEYS.index(k) for k in intensity_keys})
+        _check_deform_options(elastic, elastic_grid, bias_field, bias_grid, gamma, intensity_prob, self.intensity_planes)
+        value_range = tuple(float(v) for v in value_range)
+        if len(value_range) != 2 or not value_range[1] > value_range[0]:
+            raise ValueError(f"PairAugment: value_range is (lo, hi) with hi > lo, got {value_range!r}")
+        self.deform_options = dict(elastic=float(elastic), elastic_grid=elastic_grid, bias_field=float(bias_field),
+                                   bias_grid=bias_grid, gamma=float(gamma), intensity_prob=float(intensity_prob))
+        self.value_range = value_range
+        self.last_deform: Optional[DeformParams] = None
         noise_keys = (noise_keys,) if isinstance(noise_keys, str) else tuple(noise_keys)
         if any(k not in PAIR_KEYS for k in noise_keys):
             raise ValueError(f"PairAugment: noise_keys must be a subset of {PAIR_KEYS}, got {noise_keys!r}")
@@ -346,13 +518,33 @@ class PairAugment(nn.Module):
         self.last_noise: Optional[torch.Tensor] = None
 
     def extra_repr(self):
-        return ", ".join(f"{k}={v!r}" for k, v in self.options.items()) + f", mode={self.mode!r}, fill={self.fill}"
+        text = ", ".join(f"{k}={v!r}" for k, v in self.options.items()) + f", mode={self.mode!r}, fill={self.fill}"
+        if self.deforms:
+            text += ", " + ", ".join(f"{k}={v!r}" for k, v in self.deform_options.items())
+        return text
+
+    @property
+    def deforms(self) -> bool:
+        """Whether forward launches deform_warp (any of elastic, bias_field, gamma is on) or affine_warp."""
+        return any(self.deform_options[k] > 0 for k in ("elastic", "bias_field", "gamma"))
 
     def forward(self, batch):
         t1w, t2w = batch["t1w"], batch["t2w"]
         with torch.no_grad():
-            p = sample_affine_params(t1w.shape[0], tuple(t1w.shape[2:]), noise_planes=self.noise_planes,
-                                     generator=self.generator, device=t1w.device, **self.options)
+            n, spatial = t1w.shape[0], tuple(t1w.shape[2:])
+            if not self.deforms:
+                p = sample_affine_params(n, spatial, noise_planes=self.noise_planes, generator=self.generator,
+                                         device=t1w.device, **self.options)
+                q = None
+            else:
+                o = self.options
+                p, gate = _sample_affine(n, spatial, o["rotate"], o["scale"], o["shift"], o["flip"], o["prob"],
+                                         o["noise_std"], o["noise_prob"], self.noise_planes, self.generator, t1w.device)
+                q = dict(self.deform_options)
+                if o["prob"] == 0.0:                  # no spatial op draws at all
+                    q["elastic"] = 0.0
+                q = sample_deform_params(n, spatial, intensity_planes=self.intensity_planes, spatial_gate=gate,
+                                         generator=self.generator, device=t1w.device, **q)
             noise = [None, None]
             field = None
             if self.options["noise_std"] > 0 and self.noise_planes:
@@ -360,9 +552,14 @@ class PairAugment(nn.Module):
                                     dtype=torch.float32)
                 for j, k in enumerate(self.noise_planes):
                     noise[k] = field[j]
-            self.last_params, self.last_noise = p, field
-            y1, y2 = affine_warp(t1w, p.theta, t2w, mode=self.mode, fill=self.fill, noise=noise,
-                                 sigma=p.sigma if field is not None else None)
+            self.last_params, self.last_noise, self.last_deform = p, field, q
+            sigma = p.sigma if field is not None else None
+            if q is None:
+                y1, y2 = affine_warp(t1w, p.theta, t2w, mode=self.mode, fill=self.fill, noise=noise, sigma=sigma)
+            else:
+                y1, y2 = deform_warp(t1w, p.theta, t2w, ctrl=q.ctrl, gain=q.gain, gain_planes=self.intensity_planes,
+                                     gamma=q.gamma, value_range=self.value_range, mode=self.mode, fill=self.fill,
+                                     noise=noise, sigma=sigma)
         out = dict(batch)
         out["t1w"], out["t2w"] = y1, y2
         return out

@@ -13,6 +13,18 @@
 //              for both planes.  No atomics, no grid cap (n * N_out < 2^31 bounds the tile count): two runs give the
 //              same bits.
 //   offsets    n * N_in, n * N_out < 2^31 are required, so every element offset fits 32 bits.
+//
+// Elastic deformation and intensity augmentation of the same pair (mpgan_deform_warp): a second kernel on the
+// same tiles, the same warp_axis / warp_value and the same expression for A p + t.
+//   map        c = (A p + t) + u(p), u a cubic B-spline free-form deformation over the OUTPUT extent from a per-sample
+//              lattice of control displacements; the lattice coordinate of an axis depends on that axis's index alone
+//   value      as above, then on the planes of gain_planes v += (v - lo) * expm1(b(p)) (b: a B-spline of a log-gain
+//              lattice; skipped where expm1(b) == 0), then v = lo + R * pow(max(v - lo, 0) / R, gamma) (skipped where
+//              gamma == 1), then the noise term as above.  Zero lattices and gamma 1 give the affine kernel's bits.
+//   row lattices  a block covers a 1 x 8 x 32 tile whatever the depth (one d, BH rows of h).  It first reduces the d and h
+//              sums of both lattices once per row into LDS: BH rows x (3 + 1) channels x g_w doubles (<= 16 KiB, static).
+//              After one barrier a voxel adds 4 terms per channel with the weights of its w.  Every sum has a fixed
+//              order; no atomics.
 #include "mpgan_common.h"
 
 namespace mpgan {
@@ -132,18 +144,216 @@ __global__ __launch_bounds__(256) void affine_warp_kernel(const float* __restric
   }
 }
 
+// ---- mpgan_deform_warp ---------------------------------------------------------------------------------------------------
+constexpr int kLatticeMax = 64;                    // the largest lattice extent per axis (the LDS rows are sized by it)
+
+struct DeformArgs {
+  const double* ctrl;      // [n][3][cg0][cg1][cg2] control displacements in input voxels, or null
+  const double* gain;      // [n][gg0][gg1][gg2] log-gain control values, or null
+  const double* gamma;     // [n][2], or null
+  int cg[3], gg[3];
+  int gain_planes;
+  double lo, hi;
+};
+
+// One axis of the lattice rule: the four entries min(i0 + a, g - 1), a = 0..3, with the weights B[a].  An axis of
+// output extent 1 has the lattice extent 1 and the single weight 1 (the other three weights are 0 on entry 0).
+struct SplineAxis {
+  int i0;
+  double B[4];
+};
+
+__device__ __forceinline__ SplineAxis spline_axis(int p, int S, int g) {
+  SplineAxis a;
+  if (g < 4) {
+    a.i0 = 0;
+    a.B[0] = 1.0; a.B[1] = 0.0; a.B[2] = 0.0; a.B[3] = 0.0;
+    return a;
+  }
+  const double xi = 1.0 + ((double)p * (double)(g - 3)) / (double)(S - 1);      // g >= 4 implies S > 1 (host check)
+  int i = (int)floor(xi);
+  i = i < 1 ? 1 : (i > g - 3 ? g - 3 : i);         // xi in [1, g - 2]: the clamp keeps every index inside whatever p is
+  const double f = xi - (double)i, f2 = f * f, f3 = f2 * f, m = 1.0 - f;
+  a.i0 = i - 1;
+  a.B[0] = m * m * m / 6.0;
+  a.B[1] = (3.0 * f3 - 6.0 * f2 + 4.0) / 6.0;
+  a.B[2] = (-3.0 * f3 + 3.0 * f2 + 3.0 * f + 1.0) / 6.0;
+  a.B[3] = f3 / 6.0;
+  return a;
+}
+
+// rows[(r * NCH + k) * g[2] + j] = sum over a, b of Bd[a] Bh[b] L[k][id + a][ih + b][j] for the ROWS rows h0 + r of the
+// tile at depth weights `ad` (L: one sample's lattice [NCH][g0][g1][g2]).  A row beyond the output takes the last
+// row's weights; nobody reads it.
+template <int ROWS, int NCH>
+__device__ __forceinline__ void spline_rows(double* __restrict__ rows, const double* __restrict__ L, const int* g,
+                                            const SplineAxis& ad, int h0, int outH) {
+  const int gw = g[2], total = ROWS * NCH * gw;
+  for (int e = threadIdx.x; e < total; e += 256) {
+    const int j = e % gw, q = e / gw, k = q % NCH, r = q / NCH;
+    const int h = h0 + r < outH ? h0 + r : outH - 1;
+    const SplineAxis ah = spline_axis(h, outH, g[1]);
+    double acc = 0.0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      const int id = ad.i0 + a < g[0] ? ad.i0 + a : g[0] - 1;
+      double row = 0.0;
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const int ih = ah.i0 + b < g[1] ? ah.i0 + b : g[1] - 1;
+        row += ah.B[b] * L[((size_t)(k * g[0] + id) * g[1] + ih) * gw + j];
+      }
+      acc += ad.B[a] * row;
+    }
+    rows[e] = acc;
+  }
+}
+
+__device__ __forceinline__ double spline_row_value(const double* __restrict__ row, const SplineAxis& aw, int gw) {
+  double acc = 0.0;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) acc += aw.B[c] * row[aw.i0 + c < gw ? aw.i0 + c : gw - 1];
+  return acc;
+}
+
+#ifdef MPGAN_DEV_SWITCHES
+// what else was measured: the literal 64-term sum per voxel and channel, straight from the lattice
+template <int NCH>
+__device__ __forceinline__ void spline_voxel(double* __restrict__ out, const double* __restrict__ L, const int* g,
+                                             const SplineAxis& ad, const SplineAxis& ah, const SplineAxis& aw) {
+  for (int k = 0; k < NCH; ++k) {
+    double acc = 0.0;
+    for (int a = 0; a < 4; ++a) {
+      const int id = ad.i0 + a < g[0] ? ad.i0 + a : g[0] - 1;
+      for (int b = 0; b < 4; ++b) {
+        const int ih = ah.i0 + b < g[1] ? ah.i0 + b : g[1] - 1;
+        const double* row = L + ((size_t)(k * g[0] + id) * g[1] + ih) * g[2];
+        double t = 0.0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) t += aw.B[c] * row[aw.i0 + c < g[2] ? aw.i0 + c : g[2] - 1];
+        acc += ad.B[a] * ah.B[b] * t;
+      }
+    }
+    out[k] = acc;
+  }
+}
+#endif
+
+// gain (e = expm1 of the log-gain, 0 on a plane without gain) and gamma around lo; a value of exactly lo stays lo
+__device__ __forceinline__ double warp_intensity(double v, double e, double gam, double lo, double R) {
+  if (e != 0.0) v += (v - lo) * e;
+  if (gam != 1.0) v = lo + R * pow(fmax(v - lo, 0.0) / R, gam);
+  return v;
+}
+
+template <class T, bool BORDER, bool ROWS = true>
+__global__ __launch_bounds__(256) void deform_warp_kernel(const float* __restrict__ x0, const float* __restrict__ x1,
+                                                          WarpDims dm, const double* __restrict__ theta, DeformArgs df,
+                                                          float fill0, float fill1, const float* __restrict__ noise0,
+                                                          const float* __restrict__ noise1,
+                                                          const float* __restrict__ sigma, float* __restrict__ y0,
+                                                          float* __restrict__ y1) {
+  static_assert(T::BD == 1, "the row lattices are per d step: every thread of the block has the same d");
+  __shared__ double s_ctrl[ROWS ? T::BH * 3 * kLatticeMax : 1];
+  __shared__ double s_gain[ROWS ? T::BH * kLatticeMax : 1];
+  unsigned q, tw, th, td, s;
+  fdivmod(blockIdx.x, dm.divTW, q, tw);
+  fdivmod(q, dm.divTH, q, th);
+  fdivmod(q, dm.divTD, s, td);
+  const int lw = threadIdx.x % T::BW, lh = threadIdx.x / T::BW;
+  const int w = (int)tw * T::TW + lw, h = (int)th * T::TH + lh;
+  const bool active = w < dm.out[2] && h < dm.out[1];        // (no early return: the block meets at barriers)
+  const double* __restrict__ th12 = theta + (size_t)s * 12;
+  double A[3][4];
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) A[k][j] = th12[k * 4 + j];
+  const int Nin = dm.in[0] * dm.in[1] * dm.in[2], Nout = dm.out[0] * dm.out[1] * dm.out[2];
+  const int sH = dm.in[2], sD = dm.in[1] * dm.in[2];
+  const float* __restrict__ p0 = x0 + (size_t)s * Nin;
+  const float* __restrict__ p1 = x1 ? x1 + (size_t)s * Nin : nullptr;
+  const double sg0 = noise0 ? (double)sigma[s * 2] : 0.0, sg1 = noise1 ? (double)sigma[s * 2 + 1] : 0.0;
+  const double* __restrict__ cl = df.ctrl ? df.ctrl + (size_t)s * 3 * df.cg[0] * df.cg[1] * df.cg[2] : nullptr;
+  const double* __restrict__ gl = df.gain ? df.gain + (size_t)s * df.gg[0] * df.gg[1] * df.gg[2] : nullptr;
+  const double gam0 = df.gamma ? df.gamma[s * 2] : 1.0, gam1 = df.gamma ? df.gamma[s * 2 + 1] : 1.0;
+  const double R = df.hi - df.lo;
+  const int wc = w < dm.out[2] ? w : dm.out[2] - 1;
+  SplineAxis cw, gw;                                // this thread's w weights: the same at every d step
+  if (cl) cw = spline_axis(wc, dm.out[2], df.cg[2]);
+  if (gl) gw = spline_axis(wc, dm.out[2], df.gg[2]);
+  double base[3];                                   // A p + t without the d term
+#pragma unroll
+  for (int k = 0; k < 3; ++k) base[k] = A[k][1] * (double)h + A[k][2] * (double)w + A[k][3];
+#pragma unroll 1
+  for (int i = 0; i < T::ID; ++i) {                 // (ID == 1 in the product: one d step per block)
+    const int d = (int)td * T::TD + i;
+    if (d >= dm.out[0]) break;                      // the same for every thread of the block
+    if (ROWS) {
+      if (i) __syncthreads();                       // the last step's reads are done
+      if (cl) spline_rows<T::BH, 3>(s_ctrl, cl, df.cg, spline_axis(d, dm.out[0], df.cg[0]), (int)th * T::TH, dm.out[1]);
+      if (gl) spline_rows<T::BH, 1>(s_gain, gl, df.gg, spline_axis(d, dm.out[0], df.gg[0]), (int)th * T::TH, dm.out[1]);
+      __syncthreads();
+    }
+    if (!active) continue;
+    double c0 = A[0][0] * (double)d + base[0];
+    double c1 = A[1][0] * (double)d + base[1];
+    double c2 = A[2][0] * (double)d + base[2];
+    double b = 0.0;                                 // the log-gain
+    if (cl) {                                       // an axis of extent 1 has no displacement
+      double u[3];
+      if (ROWS) {
+        const double* row = s_ctrl + lh * 3 * df.cg[2];
+        u[0] = spline_row_value(row, cw, df.cg[2]);
+        u[1] = spline_row_value(row + df.cg[2], cw, df.cg[2]);
+        u[2] = spline_row_value(row + 2 * df.cg[2], cw, df.cg[2]);
+      }
+#ifdef MPGAN_DEV_SWITCHES
+      else
+        spline_voxel<3>(u, cl, df.cg, spline_axis(d, dm.out[0], df.cg[0]), spline_axis(h, dm.out[1], df.cg[1]), cw);
+#endif
+      c0 += dm.out[0] > 1 ? u[0] : 0.0;
+      c1 += dm.out[1] > 1 ? u[1] : 0.0;
+      c2 += dm.out[2] > 1 ? u[2] : 0.0;
+    }
+    if (gl) {
+      if (ROWS) b = spline_row_value(s_gain + lh * df.gg[2], gw, df.gg[2]);
+#ifdef MPGAN_DEV_SWITCHES
+      else
+        spline_voxel<1>(&b, gl, df.gg, spline_axis(d, dm.out[0], df.gg[0]), spline_axis(h, dm.out[1], df.gg[1]), gw);
+#endif
+    }
+    const double e = gl ? expm1(b) : 0.0;
+    const WarpAxis ad = warp_axis<BORDER>(c0, dm.in[0]);
+    const WarpAxis ah = warp_axis<BORDER>(c1, dm.in[1]);
+    const WarpAxis aw = warp_axis<BORDER>(c2, dm.in[2]);
+    const int o = (d * dm.out[1] + h) * dm.out[2] + w;
+    const size_t go = (size_t)s * Nout + o;
+    double v = warp_value<BORDER>(p0, ad, ah, aw, sH, sD, (double)fill0);
+    v = warp_intensity(v, (df.gain_planes & 1) ? e : 0.0, gam0, df.lo, R);
+    if (sg0 != 0.0) v += sg0 * (double)noise0[go];
+    y0[go] = (float)v;
+    if (p1) {
+      double u = warp_value<BORDER>(p1, ad, ah, aw, sH, sD, (double)fill1);
+      u = warp_intensity(u, (df.gain_planes & 2) ? e : 0.0, gam1, df.lo, R);
+      if (sg1 != 0.0) u += sg1 * (double)noise1[go];
+      y1[go] = (float)u;
+    }
+  }
+}
+
 }  // namespace mpgan
 
 using namespace mpgan;
 
-// n * D * H * W of one side: 0 and *N, or -1 with the error set.
-static int warp_count(const char* side, int32_t n, const int32_t* dhw, long* N) {
-  MPGAN_CHECK_ARG(dhw[0] >= 1 && dhw[1] >= 1 && dhw[2] >= 1, "mpgan_affine_warp: bad argument (%s extent %d x %d x %d)",
+// n * D * H * W of one side: 0 and *N, or -1 with the error set (fn: the entry point's name, for the message).
+static int warp_count(const char* fn, const char* side, int32_t n, const int32_t* dhw, long* N) {
+  MPGAN_CHECK_ARG(dhw[0] >= 1 && dhw[1] >= 1 && dhw[2] >= 1, "%s: bad argument (%s extent %d x %d x %d)", fn,
                   side, dhw[0], dhw[1], dhw[2]);
   const long cap = 0x7fffffffL;
   long e = n;
   for (int k = 0; k < 3; ++k) {
-    MPGAN_CHECK_ARG(e <= cap / dhw[k], "mpgan_affine_warp: %s n * D * H * W = %d * %d * %d * %d exceeds the 32-bit element count",
+    MPGAN_CHECK_ARG(e <= cap / dhw[k], "%s: %s n * D * H * W = %d * %d * %d * %d exceeds the 32-bit element count", fn,
                     side, n, dhw[0], dhw[1], dhw[2]);
     e *= dhw[k];
   }
@@ -151,19 +361,41 @@ static int warp_count(const char* side, int32_t n, const int32_t* dhw, long* N) 
   return MPGAN_OK;
 }
 
+// What both entry points refuse.
+static int warp_check(const char* fn, const float* x0, const float* x1, int32_t n, const int32_t* in_dhw,
+                      const int32_t* out_dhw, const double* theta, int32_t mode, const float* noise0, const float* noise1,
+                      const float* sigma, const float* y0, const float* y1) {
+  MPGAN_CHECK_ARG(x0 && y0 && theta && in_dhw && out_dhw, "%s: bad argument (null x0 / y0 / theta / in_dhw / out_dhw)", fn);
+  MPGAN_CHECK_ARG((x1 != nullptr) == (y1 != nullptr), "%s: bad argument (x1 and y1 go together: %s alone)", fn,
+                  x1 ? "x1" : "y1");
+  MPGAN_CHECK_ARG(n > 0, "%s: bad argument (n = %d)", fn, n);
+  MPGAN_CHECK_ARG(mode == MPGAN_WARP_CONSTANT || mode == MPGAN_WARP_BORDER, "%s: unknown mode %d (constant 0, border 1)", fn, mode);
+  MPGAN_CHECK_ARG(!(noise0 || noise1) || sigma, "%s: bad argument (noise without sigma)", fn);
+  MPGAN_CHECK_ARG(!sigma || noise0 || noise1, "%s: bad argument (sigma without noise)", fn);
+  MPGAN_CHECK_ARG(!noise1 || x1, "%s: bad argument (noise1 without the second plane)", fn);
+  long Nin, Nout;
+  if (int rc = warp_count(fn, "input", n, in_dhw, &Nin)) return rc;
+  return warp_count(fn, "output", n, out_dhw, &Nout);
+}
+
+// The tiling of the output: dm and the number of tiles (= blocks).
+template <class T>
+static long warp_dims(int32_t n, const int32_t* in_dhw, const int32_t* out_dhw, WarpDims* dm) {
+  for (int k = 0; k < 3; ++k) { dm->in[k] = in_dhw[k]; dm->out[k] = out_dhw[k]; }
+  const long tW = (out_dhw[2] + T::TW - 1) / T::TW, tH = (out_dhw[1] + T::TH - 1) / T::TH,
+             tD = (out_dhw[0] + T::TD - 1) / T::TD;
+  dm->divTW = make_fastdiv((unsigned)tW);
+  dm->divTH = make_fastdiv((unsigned)tH);
+  dm->divTD = make_fastdiv((unsigned)tD);
+  return (long)n * tD * tH * tW;                    // every tile holds an output voxel of its own: <= n * N_out < 2^31
+}
+
 template <class T>
 static int warp_launch(const float* x0, const float* x1, int32_t n, const int32_t* in_dhw, const int32_t* out_dhw,
                        const double* theta, int32_t mode, float fill0, float fill1, const float* noise0,
                        const float* noise1, const float* sigma, float* y0, float* y1, void* stream) {
   WarpDims dm;
-  for (int k = 0; k < 3; ++k) { dm.in[k] = in_dhw[k]; dm.out[k] = out_dhw[k]; }
-  const long tW = (out_dhw[2] + T::TW - 1) / T::TW, tH = (out_dhw[1] + T::TH - 1) / T::TH,
-             tD = (out_dhw[0] + T::TD - 1) / T::TD;
-  dm.divTW = make_fastdiv((unsigned)tW);
-  dm.divTH = make_fastdiv((unsigned)tH);
-  dm.divTD = make_fastdiv((unsigned)tD);
-  const long tiles = (long)n * tD * tH * tW;        // every tile holds an output voxel of its own: <= n * N_out < 2^31
-  const dim3 grid((unsigned)tiles), block(256);
+  const dim3 grid((unsigned)warp_dims<T>(n, in_dhw, out_dhw, &dm)), block(256);
   if (mode == MPGAN_WARP_BORDER)
     hipLaunchKernelGGL((affine_warp_kernel<T, true>), grid, block, 0, (hipStream_t)stream, x0, x1, dm, theta, fill0, fill1,
                        noise0, noise1, sigma, y0, y1);
@@ -177,17 +409,7 @@ extern "C" int mpgan_affine_warp(const float* x0, const float* x1, int32_t n, co
                                  const int32_t* out_dhw, const double* theta, int32_t mode, float fill0, float fill1,
                                  const float* noise0, const float* noise1, const float* sigma, float* y0, float* y1,
                                  void* stream) {
-  MPGAN_CHECK_ARG(x0 && y0 && theta && in_dhw && out_dhw, "mpgan_affine_warp: bad argument (null x0 / y0 / theta / in_dhw / out_dhw)");
-  MPGAN_CHECK_ARG((x1 != nullptr) == (y1 != nullptr), "mpgan_affine_warp: bad argument (x1 and y1 go together: %s alone)",
-                  x1 ? "x1" : "y1");
-  MPGAN_CHECK_ARG(n > 0, "mpgan_affine_warp: bad argument (n = %d)", n);
-  MPGAN_CHECK_ARG(mode == MPGAN_WARP_CONSTANT || mode == MPGAN_WARP_BORDER, "mpgan_affine_warp: unknown mode %d (constant 0, border 1)", mode);
-  MPGAN_CHECK_ARG(!(noise0 || noise1) || sigma, "mpgan_affine_warp: bad argument (noise without sigma)");
-  MPGAN_CHECK_ARG(!sigma || noise0 || noise1, "mpgan_affine_warp: bad argument (sigma without noise)");
-  MPGAN_CHECK_ARG(!noise1 || x1, "mpgan_affine_warp: bad argument (noise1 without the second plane)");
-  long Nin, Nout;
-  if (int rc = warp_count("input", n, in_dhw, &Nin)) return rc;
-  if (int rc = warp_count("output", n, out_dhw, &Nout)) return rc;
+  if (int rc = warp_check("mpgan_affine_warp", x0, x1, n, in_dhw, out_dhw, theta, mode, noise0, noise1, sigma, y0, y1)) return rc;
   int tile = out_dhw[0] > 1 ? 0 : 1;
   if (const char* e = dev_env("MPGAN_DBG_WARP_TILE")) tile = atoi(e);
 #define MPGAN_WARP_GO(T) return warp_launch<T>(x0, x1, n, in_dhw, out_dhw, theta, mode, fill0, fill1, noise0, noise1, sigma, y0, y1, stream)
@@ -207,4 +429,71 @@ extern "C" int mpgan_affine_warp(const float* x0, const float* x1, int32_t n, co
 #undef MPGAN_WARP_GO
   set_error("mpgan_affine_warp: unknown tile %d", tile);
   return MPGAN_ERR_INVALID;
+}
+
+// The lattice rule of include/mpgan_hip.h over the output extent: extent 1 on an axis of extent 1, else 4 .. 64.
+static int lattice_check(const char* what, const double* lattice, const int32_t* g, const int32_t* out_dhw) {
+  if (!lattice) return MPGAN_OK;
+  MPGAN_CHECK_ARG(g, "mpgan_deform_warp: bad argument (%s without its size triple)", what);
+  for (int k = 0; k < 3; ++k) {
+    if (out_dhw[k] == 1)
+      MPGAN_CHECK_ARG(g[k] == 1, "mpgan_deform_warp: %s lattice %d x %d x %d: axis %d has output extent 1 and must have lattice extent 1",
+                      what, g[0], g[1], g[2], k);
+    else
+      MPGAN_CHECK_ARG(g[k] >= 4 && g[k] <= kLatticeMax, "mpgan_deform_warp: %s lattice %d x %d x %d: axis %d must have an extent in [4, %d]",
+                      what, g[0], g[1], g[2], k, kLatticeMax);
+  }
+  return MPGAN_OK;
+}
+
+template <class T, bool ROWS = true>
+static int deform_launch(const float* x0, const float* x1, int32_t n, const int32_t* in_dhw, const int32_t* out_dhw,
+                         const double* theta, const DeformArgs& df, int32_t mode, float fill0, float fill1,
+                         const float* noise0, const float* noise1, const float* sigma, float* y0, float* y1,
+                         void* stream) {
+  WarpDims dm;
+  const dim3 grid((unsigned)warp_dims<T>(n, in_dhw, out_dhw, &dm)), block(256);
+  if (mode == MPGAN_WARP_BORDER)
+    hipLaunchKernelGGL((deform_warp_kernel<T, true, ROWS>), grid, block, 0, (hipStream_t)stream, x0, x1, dm, theta, df, fill0,
+                       fill1, noise0, noise1, sigma, y0, y1);
+  else
+    hipLaunchKernelGGL((deform_warp_kernel<T, false, ROWS>), grid, block, 0, (hipStream_t)stream, x0, x1, dm, theta, df, fill0,
+                       fill1, noise0, noise1, sigma, y0, y1);
+  return check_launch("mpgan_deform_warp");
+}
+
+extern "C" int mpgan_deform_warp(const float* x0, const float* x1, int32_t n, const int32_t* in_dhw,
+                                 const int32_t* out_dhw, const double* theta, const double* ctrl,
+                                 const int32_t* ctrl_dhw, const double* gain, const int32_t* gain_dhw,
+                                 int32_t gain_planes, const double* gamma, double lo, double hi, int32_t mode,
+                                 float fill0, float fill1, const float* noise0, const float* noise1,
+                                 const float* sigma, float* y0, float* y1, void* stream) {
+  if (int rc = warp_check("mpgan_deform_warp", x0, x1, n, in_dhw, out_dhw, theta, mode, noise0, noise1, sigma, y0, y1)) return rc;
+  if (int rc = lattice_check("ctrl", ctrl, ctrl_dhw, out_dhw)) return rc;
+  if (int rc = lattice_check("gain", gain, gain_dhw, out_dhw)) return rc;
+  MPGAN_CHECK_ARG(!(gain_planes & ~3), "mpgan_deform_warp: unknown gain_planes bits %#x (1 = plane 0, 2 = plane 1)", gain_planes);
+  MPGAN_CHECK_ARG(!gain || gain_planes, "mpgan_deform_warp: bad argument (gain with gain_planes == 0)");
+  MPGAN_CHECK_ARG(!(gain_planes & 2) || x1, "mpgan_deform_warp: bad argument (gain_planes names plane 1 without the second plane)");
+  MPGAN_CHECK_ARG(!(gain || gamma) || hi > lo, "mpgan_deform_warp: bad argument (value range [%g, %g]: hi must exceed lo)", lo, hi);
+  DeformArgs df;
+  df.ctrl = ctrl;
+  df.gain = gain;
+  df.gamma = gamma;
+  for (int k = 0; k < 3; ++k) { df.cg[k] = ctrl ? ctrl_dhw[k] : 1; df.gg[k] = gain ? gain_dhw[k] : 1; }
+  df.gain_planes = gain ? gain_planes : 0;
+  df.lo = lo;
+  df.hi = hi;
+  // a 1 x 8 x 32 tile whatever the depth: one d step per block needs no loop around the row lattices (the loop of the
+  // 4 x 8 x 32 tile keeps the constants of pow and expm1 in registers across its barrier: 181 VGPRs against 70)
+#ifdef MPGAN_DEV_SWITCHES
+  // what else was measured: MPGAN_DBG_DEFORM_TILE=0 the 4 x 8 x 32 tile, MPGAN_DBG_DEFORM_FORM=1 the
+  // 64-term sum per voxel instead of the row lattices
+  if (const char* e = dev_env("MPGAN_DBG_DEFORM_TILE"))
+    if (atoi(e) == 0)
+      return deform_launch<WarpTile3d>(x0, x1, n, in_dhw, out_dhw, theta, df, mode, fill0, fill1, noise0, noise1, sigma, y0, y1, stream);
+  if (const char* e = dev_env("MPGAN_DBG_DEFORM_FORM"))
+    if (atoi(e) == 1)
+      return deform_launch<WarpTile2d, false>(x0, x1, n, in_dhw, out_dhw, theta, df, mode, fill0, fill1, noise0, noise1, sigma, y0, y1, stream);
+#endif
+  return deform_launch<WarpTile2d>(x0, x1, n, in_dhw, out_dhw, theta, df, mode, fill0, fill1, noise0, noise1, sigma, y0, y1, stream);
 }

@@ -1181,6 +1181,70 @@ def affine_warp(x0, x1, theta, mode: int, fill0: float, fill1: float, noise0, no
     return y0 if y1 is None else (y0, y1)
 
 
+def deform_warp(x0, x1, theta, ctrl, gain, gain_planes: int, gamma, lo: float, hi: float, mode: int, fill0: float,
+                fill1: float, noise0, noise1, sigma, y0, y1):
+    """affine_warp with c = (A p + t) + u(p), u the cubic B-spline deformation of the lattice ctrl (B, 3, g_d, g_h, g_w)
+    float64, then on the planes of the bit mask `gain_planes` v += (v - lo) * expm1(b(p)) with b the B-spline of the
+    log-gain lattice gain (B, b_d, b_h, b_w) float64, then v = lo + (hi - lo) * ((v - lo) / (hi - lo)) ** gamma[:, k]
+    (gamma (B, 2) float64), then the noise term (include/mpgan_hip.h).  ctrl, gain and gamma may each be None: that
+    term is absent.  A 2-D image has lattices with g_d = 1."""
+    n, spatial = _diffaug_geometry(x0, "deform_warp")
+    _, out_spatial = _diffaug_geometry(y0, "deform_warp")
+    if y0.shape[0] != n or len(out_spatial) != len(spatial) or y0.device != x0.device:
+        raise ValueError(f"deform_warp: y0 has shape {tuple(y0.shape)} on {y0.device}, x0 {tuple(x0.shape)} on {x0.device}")
+    if (x1 is None) != (y1 is None):
+        raise ValueError("deform_warp: x1 and y1 go together")
+    if x1 is not None:
+        _diffaug_geometry(x1, "deform_warp")
+        _diffaug_geometry(y1, "deform_warp")
+        if x1.shape != x0.shape or y1.shape != y0.shape or x1.device != x0.device or y1.device != x0.device:
+            raise ValueError(f"deform_warp: the second plane has shapes {tuple(x1.shape)} -> {tuple(y1.shape)}, the first "
+                             f"{tuple(x0.shape)} -> {tuple(y0.shape)}")
+    if mode not in (WARP_CONSTANT, WARP_BORDER):
+        raise ValueError(f"deform_warp: unknown mode {mode!r}")
+    if noise1 is not None and x1 is None:
+        raise ValueError("deform_warp: noise1 without a second plane")
+    if (sigma is None) != (noise0 is None and noise1 is None):
+        raise ValueError("deform_warp: sigma goes with a noise field, and a noise field with sigma")
+    gain_planes = int(gain_planes)
+    if gain_planes & ~3 or (gain is not None and not gain_planes) or (gain_planes & 2 and x1 is None):
+        raise ValueError(f"deform_warp: gain_planes {gain_planes:#x} is a mask of the planes given (1 = plane 0, 2 = plane 1), "
+                         "not 0 with a gain lattice")
+    if (gain is not None or gamma is not None) and not float(hi) > float(lo):
+        raise ValueError(f"deform_warp: the value range needs hi > lo, got [{lo}, {hi}]")
+    out3 = (1,) * (3 - len(out_spatial)) + tuple(out_spatial)
+    grids = {}
+    for t, lead, name in ((ctrl, (n, 3), "ctrl"), (gain, (n,), "gain")):
+        if t is None:
+            grids[name] = None
+            continue
+        if (not isinstance(t, torch.Tensor) or t.dim() != len(lead) + 3 or tuple(t.shape[:len(lead)]) != lead
+                or t.dtype != torch.float64 or not t.is_contiguous() or t.device != x0.device):
+            raise ValueError(f"deform_warp: {name} must be a contiguous float64 {lead + ('g_d', 'g_h', 'g_w')} tensor on "
+                             f"{x0.device}, got {tuple(t.shape) if isinstance(t, torch.Tensor) else t!r}")
+        g = tuple(int(v) for v in t.shape[len(lead):])
+        if any(gk != 1 if sk == 1 else not 4 <= gk <= 64 for gk, sk in zip(g, out3)):
+            raise ValueError(f"deform_warp: the {name} lattice {g} over the output extent {out3}: 1 on an axis of extent 1, "
+                             "else 4 .. 64")
+        grids[name] = g
+    tables = [(theta, torch.float64, (n, 12), "theta"), (sigma, torch.float32, (n, 2), "sigma"),
+              (gamma, torch.float64, (n, 2), "gamma"), (noise0, torch.float32, tuple(y0.shape), "noise0"),
+              (noise1, torch.float32, tuple(y0.shape), "noise1")]
+    for t, dtype, shape, name in tables:
+        if t is None and name != "theta":
+            continue
+        if t is None or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != x0.device:
+            raise ValueError(f"deform_warp: {name} must be a contiguous {dtype} {shape} tensor on {x0.device}, got "
+                             + (f"{tuple(t.shape)} {t.dtype} on {t.device}" if t is not None else "None"))
+    check(lib().mpgan_deform_warp(x0.data_ptr(), _ptr(x1), n, _dhw(spatial), _dhw(out_spatial), theta.data_ptr(),
+                                  _ptr(ctrl), _dhw(grids["ctrl"]) if ctrl is not None else None,
+                                  _ptr(gain), _dhw(grids["gain"]) if gain is not None else None,
+                                  gain_planes if gain is not None else 0, _ptr(gamma), float(lo), float(hi), int(mode),
+                                  float(fill0), float(fill1), _ptr(noise0), _ptr(noise1), _ptr(sigma), y0.data_ptr(),
+                                  _ptr(y1), _stream()), "deform_warp")
+    return y0 if y1 is None else (y0, y1)
+
+
 # --------------------------------------------------------------------------
 # conditional discriminator: the first conv over two 1-channel input planes (include/mpgan_hip.h: mpgan_conv2p_*)
 # --------------------------------------------------------------------------

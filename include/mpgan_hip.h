@@ -652,6 +652,46 @@ int mpgan_affine_warp(const float* x0, const float* x1, int32_t n, const int32_t
                       const double* theta, int32_t mode, float fill0, float fill1, const float* noise0,
                       const float* noise1, const float* sigma, float* y0, float* y1, void* stream);
 
+/* ---- elastic deformation and MRI intensity augmentation of the same pair (pair_augment.hip) ----
+ * mpgan_affine_warp with a smooth non-rigid displacement added to the map (both planes alike) and, per plane, a smooth
+ * multiplicative bias field and a gamma change.  Every argument the two share means what it means above.  Per output
+ * voxel p = (d, h, w) of sample s, in fp64 with one rounding to fp32 at the end:
+ *   c      = (A p + t) + u(p)                    A p + t computed as mpgan_affine_warp computes it, u added afterwards;
+ *                                                u: cubic B-spline free-form deformation, in input voxels, (d, h, w) order
+ *   v_k    = trilinear(x_k, c)                   CONSTANT / BORDER and fill_k as above
+ *   v_k   += (v_k - lo) * expm1(b(p))            planes of gain_planes only (bit 1 = plane 0, bit 2 = plane 1);
+ *                                                b: cubic B-spline of a scalar log-gain lattice; skipped where expm1(b) == 0
+ *   v_k    = lo + R * pow(max(v_k - lo, 0) / R, gamma[s][k])      R = hi - lo; skipped when gamma[s][k] == 1.0 exactly
+ *   y_k[p] = v_k + sigma[s][k] * noise_k[p]      as above
+ * Device tables (nothing is read on the host), each lattice with an int32 size triple of its own (read on the host):
+ *   ctrl:  double [n][3][g_d][g_h][g_w], control displacements of the (d, h, w) coordinate; ctrl_dhw = (g_d, g_h, g_w)
+ *   gain:  double [n][b_d][b_h][b_w], control values of the log-gain; gain_dhw = (b_d, b_h, b_w)
+ *   gamma: double [n][2], the exponent of plane 0 and plane 1 (> 0)
+ * Each of the three may be null: its term is then absent, not zero.
+ * Lattice rule, the same for both lattices, over the OUTPUT extent S = out_dhw.  On an axis with S_k == 1 the lattice
+ * extent must be 1: the axis has the single weight 1 and u_k = 0 there (2-D images: g_d = 1).  On every other axis
+ * 4 <= g_k <= 64 and
+ *   xi = 1 + p_k (g_k - 3) / (S_k - 1);   i = min(floor(xi), g_k - 3);   f = xi - i   (in [0, 1])
+ *   value = sum over a = 0..3 (per axis) of B_a(f) * lattice[i + a - 1]
+ *   B_0 = (1 - f)^3 / 6,  B_1 = (3 f^3 - 6 f^2 + 4) / 6,  B_2 = (-3 f^3 + 3 f^2 + 3 f + 1) / 6,  B_3 = f^3 / 6
+ * so one control point lies beyond each face and the spacing is delta_k = (S_k - 1) / (g_k - 3) voxels.  The weights
+ * are >= 0 and sum to 1; control displacements below about 0.4 delta_k cannot fold the map p + u(p).  The order of the
+ * 64 terms is not part of the definition.
+ * Consequences: all-zero ctrl, all-zero gain and gamma == 1 give the bits of mpgan_affine_warp on the same arguments;
+ * a sampled value of exactly lo stays exactly lo under gain and gamma (background stays background; noise may then
+ * move it); one plane and two planes give the same bits per plane; gain_planes leaves the other plane untouched.
+ * Launch: one kernel on mpgan_affine_warp's tiles.  For each d step of its tile a block reduces the d and h sums of
+ * both lattices once per (d, h) row into LDS (<= 16 KiB); a voxel then adds 4 terms per channel.  No atomics; the grid
+ * depends on (n, out_dhw) alone and every sum has a fixed order: two runs give the same bits.
+ * MPGAN_ERR_INVALID before any launch: everything mpgan_affine_warp refuses; a lattice pointer without its size
+ * triple; a lattice extent that breaks the rule; gain with gain_planes == 0; gain_planes naming plane 1 without x1;
+ * unknown gain_planes bits; hi <= lo when gain or gamma is given. */
+int mpgan_deform_warp(const float* x0, const float* x1, int32_t n, const int32_t* in_dhw, const int32_t* out_dhw,
+                      const double* theta, const double* ctrl, const int32_t* ctrl_dhw, const double* gain,
+                      const int32_t* gain_dhw, int32_t gain_planes, const double* gamma, double lo, double hi,
+                      int32_t mode, float fill0, float fill1, const float* noise0, const float* noise1,
+                      const float* sigma, float* y0, float* y1, void* stream);
+
 /* ---- optimiser ------------------------------------------------------------ */
 /* torch.optim.Adam.step over one flat buffer (GAN_final.py:306-307):
  * m = b1*m+(1-b1)*g; v = b2*v+(1-b2)*g^2; p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t)+eps).

@@ -5,6 +5,7 @@ device (needs an MI355X).
     python tools/bench_pair_augment.py [--iters 20] [--repeats 7] [--no-step]
     MPGAN_LIB_PATH=.../libmpgan_hip_dev.so python tools/bench_pair_augment.py --tiles      # every tile of the dev build
     rocprofv3 --kernel-trace --stats ... -- python tools/bench_pair_augment.py --loop 30    # kernel durations
+    python tools/bench_pair_augment.py --deform                                           # the elastic / intensity kernel
 
 Rows: (4, 1, 128, 128, 128) and (16, 1, 256, 256), mode "border", one fixed draw with rotate 0.4 rad on every axis, scale
 0.15, shift 0.05 and noise on t1w.  "kernel" is ops.affine_warp into preallocated outputs (the launch alone),
@@ -15,7 +16,15 @@ the timed size (fp32 grid arithmetic: within 1e-3).  Each figure: HIP events aro
 call; median of `repeats` windows, spread = max - min of the windows; the windows of the paths alternate in one process.
 traffic = the bytes the launch must move (2 reads + 2 writes + 1 noise read per voxel pair = 20 B) and the share of
 6.3 TB/s that the kernel figure amounts to.  The last rows time a fit_batch of variant A at the C3 shape (16 x 256^2,
-fp32) and at the C5 shape (4 x 128^3, bf16 storage) without and with pair_augment."""
+fp32) and at the C5 shape (4 x 128^3, bf16 storage) without and with pair_augment.
+
+--deform: at the same shapes and under the same affine draw, the launch alone of ops.affine_warp, of
+ops.deform_warp with an elastic lattice only (elastic 0.3, grid 6) and with elastic + bias field + gamma (0.3 each, bias
+grid 4; gain and gamma on t1w), alternating in one process, each with its ratio to the affine launch; then a fit_batch at
+the C5 shape without pair_augment, with the affine options and with the affine + deform options.  With the development
+build (MPGAN_LIB_PATH) four more rows per shape time what else was built: the 4 x 8 x 32 tile (MPGAN_DBG_DEFORM_TILE=0)
+beside the product's 1 x 8 x 32, and the 64-term sum per voxel (MPGAN_DBG_DEFORM_FORM=1) beside the product's row
+lattices in LDS (the two forms are first compared at the timed size: within 1e-6)."""
 import argparse
 import os
 import statistics
@@ -122,6 +131,66 @@ def tiles(iters, repeats):
             print(f"{label:10s} tile {name:8s} {med[name]:9.4f} +-{spr[name]:6.4f}")
 
 
+DEFORM = dict(elastic=0.3, bias_field=0.3, gamma=0.3)
+
+
+def deform_call(t1w, t2w, p, noise, q, intensity, switch=None):
+    y1, y2 = torch.empty_like(t1w), torch.empty_like(t2w)
+    pad = lambda t, ctrl: t if t is None or t1w.dim() == 5 else (
+        torch.cat([torch.zeros_like(t[:, :1]), t], 1).unsqueeze(2) if ctrl else t.unsqueeze(1)).contiguous()
+    ctrl, gain = pad(q.ctrl, True), pad(q.gain, False) if intensity else None
+    gamma = q.gamma if intensity else None
+
+    def run():
+        if switch is not None:
+            os.environ[switch[0]] = switch[1]
+        ops.deform_warp(t1w, t2w, p.theta, ctrl, gain, 1, gamma, -1.0, 1.0, ops.WARP_BORDER, -1.0, -1.0, noise, None,
+                        p.sigma, y1, y2)
+        if switch is not None:
+            os.environ.pop(switch[0])
+        return y1, y2
+    return run
+
+
+def deform(iters, repeats, no_step):
+    dev = "dev" in os.path.basename(os.environ.get("MPGAN_LIB_PATH", ""))
+    print(f"ms per launch: median of {repeats} windows x {iters} calls (+- = max - min); ratio = to the affine launch")
+    for label, shape in SHAPES:
+        t1w, t2w, p, noise = make_case(shape)
+        q = A.sample_deform_params(shape[0], shape[2:], generator=torch.Generator(device="cuda").manual_seed(4),
+                                   device="cuda", **DEFORM)
+        paths = {"affine": kernel_call(t1w, t2w, p, noise), "elastic": deform_call(t1w, t2w, p, noise, q, False),
+                 "elastic + bias + gamma": deform_call(t1w, t2w, p, noise, q, True)}
+        if dev:
+            tile, form = ("MPGAN_DBG_DEFORM_TILE", "0"), ("MPGAN_DBG_DEFORM_FORM", "1")
+            paths["elastic, tile 4x8x32"] = deform_call(t1w, t2w, p, noise, q, False, tile)
+            paths["elastic + bias + gamma, tile 4x8x32"] = deform_call(t1w, t2w, p, noise, q, True, tile)
+            paths["elastic, 64 terms per voxel"] = deform_call(t1w, t2w, p, noise, q, False, form)
+            paths["elastic + bias + gamma, 64 terms per voxel"] = deform_call(t1w, t2w, p, noise, q, True, form)
+            for a, b in zip(paths["elastic + bias + gamma"](), paths["elastic + bias + gamma, 64 terms per voxel"]()):
+                if not float((a - b).abs().max()) <= 1e-6:
+                    raise SystemExit(f"{label}: the two forms disagree by {float((a - b).abs().max()):.3e}")
+        med, spr = measure(paths, iters, repeats)
+        for k in paths:
+            print(f"{label:10s} {k:44s} {med[k]:9.4f} +-{spr[k]:6.4f}   ratio {med[k] / med['affine']:5.2f}")
+        del t1w, t2w, noise, paths
+        torch.cuda.empty_cache()
+    if not no_step:
+        from mpgan_amd.gan import GAN
+        spatial = (128, 128, 128)
+        g = torch.Generator().manual_seed(6)
+        batch = {k: (torch.rand(4, 1, *spatial, generator=g) * 2 - 1).cuda() for k in ("t1w", "t2w")}
+        steps = {}
+        for name, opt in (("None", None), ("affine", OPTIONS), ("affine + deform", dict(OPTIONS, **DEFORM))):
+            torch.manual_seed(0)
+            m = GAN(1, *spatial, dimensions=3, pair_augment=opt, storage_dtype="bf16")
+            opts, _ = m.configure_optimizers()
+            steps[f"C5 4x128^3 bf16 pair_augment={name}"] = (lambda m=m, opts=opts: m.fit_batch(batch, 0, opts))
+        med, spr = measure(steps, max(iters // 2, 1), repeats)
+        for k in steps:
+            print(f"fit_batch {k:46s} {med[k]:9.4f} +-{spr[k]:6.4f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
@@ -129,7 +198,10 @@ def main():
     ap.add_argument("--no-step", action="store_true", help="skip the fit_batch rows")
     ap.add_argument("--loop", type=int, default=0, metavar="N", help="only run N launches per shape (for a kernel trace)")
     ap.add_argument("--tiles", action="store_true", help="time every tile of the development build instead")
+    ap.add_argument("--deform", action="store_true", help="time the elastic / intensity kernel beside the affine one instead")
     args = ap.parse_args()
+    if args.deform:
+        return deform(args.iters, args.repeats, args.no_step)
     if args.loop:
         return loop(args.loop)
     if args.tiles:
