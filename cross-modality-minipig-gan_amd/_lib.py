@@ -141,6 +141,16 @@ SIGNATURES = {
     "mpgan_edge_loss_workspace": (_L, [_I3, _I]),
     "mpgan_edge_loss_forward": (_I, [_P, _P, _I3, _I, _I, C.c_double, _P, _L, _I, _P, _P]),
     "mpgan_edge_loss_backward": (_I, [_P, _P, _I3, _I, _I, C.c_double, _P, _I, C.c_double, _I, _P, _P]),
+    # foreground masks (foreground.hip)
+    "mpgan_otsu_workspace": (_L, [_I, _I]),
+    "mpgan_otsu_threshold": (_I, [_P, _L, _I, _F, _F, _I, _P, _P, _P]),
+    "mpgan_foreground_mask": (_I, [_P, _I3, _I, _P, _I3, _P, _P, _P, _P]),
+    "mpgan_masked_l1_workspace": (_L, [_L, _I]),
+    "mpgan_masked_l1_forward": (_I, [_P, _P, _L, _I, _I, _P, _P, C.c_double, C.c_double, _P, _L, _P, _I, _P, _P]),
+    "mpgan_masked_l1_backward": (_I, [_P, _P, _L, _I, _I, _P, _P, C.c_double, C.c_double, _P, _P, _I, C.c_double, _P,
+                                      _P, _P]),
+    "mpgan_masked_errors_partials": (_L, [_L]),
+    "mpgan_masked_image_errors": (_I, [_P, _P, _P, _L, _F, _P, _P, _P]),
     # differentiable augmentation in front of D (diffaug.hip)
     "mpgan_diffaug_workspace": (_L, [_I, _I3]),
     "mpgan_diffaug_forward": (_I, [_P, _I, _I3, _I, _P, _P, _F, _P, _L, _P, _P]),

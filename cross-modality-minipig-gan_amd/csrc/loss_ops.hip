@@ -234,8 +234,13 @@ __global__ void loss_reduce_kernel(const double* __restrict__ item, int items, i
 void launch_loss_tail(const double* partials, long tiles, double inv, double* item, int items, int channels,
                       int reduction, bool one_minus, float* loss, hipStream_t stream) {
   hipLaunchKernelGGL(loss_item_kernel, dim3((unsigned)items), dim3(256), 0, stream, partials, tiles, inv, item);
+  launch_loss_reduce(item, items, channels, reduction, one_minus, loss, stream);
+}
+
+void launch_loss_reduce(const double* item, int items, int channels, int reduction, bool one_minus, float* loss,
+                        hipStream_t stream) {
   auto kern = one_minus ? loss_reduce_kernel<true> : loss_reduce_kernel<false>;
-  hipLaunchKernelGGL(kern, dim3(1), dim3(64), 0, stream, (const double*)item, items, channels, reduction, loss);
+  hipLaunchKernelGGL(kern, dim3(1), dim3(64), 0, stream, item, items, channels, reduction, loss);
 }
 
 // ---- Adam ----------------------------------------------------------------------

@@ -63,4 +63,8 @@ __device__ __forceinline__ double strided_serial_sum256(const T* __restrict__ x,
 void launch_loss_tail(const double* partials, long tiles, double inv, double* item, int items, int channels,
                       int reduction, bool one_minus, float* loss, hipStream_t stream);
 
+// The second of those two launches alone, for a loss whose per-item value has a divisor of its own (foreground.hip).
+void launch_loss_reduce(const double* item, int items, int channels, int reduction, bool one_minus, float* loss,
+                        hipStream_t stream);
+
 }  // namespace mpgan

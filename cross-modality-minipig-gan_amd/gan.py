@@ -15,7 +15,8 @@ import torch.nn as nn
 
 from . import ops
 from .augment import DiffAugment, PairAugment, parse_policy
-from .losses import EdgeLoss, GlobalMutualInformationLoss, SSIMLoss
+from .losses import EdgeLoss, ForegroundL1Loss, GlobalMutualInformationLoss, SSIMLoss
+from .preprocess import check_threshold
 from .networks import CasNetGenerator, Discriminator, _EngineModule
 
 
@@ -397,7 +398,8 @@ class GAN(nn.Module):
                  ssim_weight: float = 0.0, d_head: str = "linear", adv_loss: str = "bce", conditional: bool = False,
                  diff_augment: str = "", diff_augment_fill: float = 0.0, ema_decay: float = 0.0,
                  ema_warmup: bool = True, grad_clip: float = 0.0, log_grad_norm: bool = False,
-                 pair_augment: Optional[dict] = None, edge_weight: float = 0.0, edge_eps: float = 1e-6, **kwargs):
+                 pair_augment: Optional[dict] = None, edge_weight: float = 0.0, edge_eps: float = 1e-6,
+                 fg_weight: float = 0.0, fg_threshold="otsu", **kwargs):
         super().__init__()
         if adv_loss not in ADV_LOSSES:
             raise ValueError(f"adv_loss must be one of {ADV_LOSSES}, got {adv_loss!r}")
@@ -407,6 +409,11 @@ class GAN(nn.Module):
             raise ValueError(f"ssim_weight must be >= 0, got {ssim_weight!r}")
         if edge_weight < 0:
             raise ValueError(f"edge_weight must be >= 0, got {edge_weight!r}")
+        if not fg_weight >= 0:
+            raise ValueError(f"fg_weight must be >= 0, got {fg_weight!r}")
+        if isinstance(fg_threshold, torch.Tensor):
+            raise ValueError('fg_threshold must be "otsu" or a finite number, got a tensor')
+        check_threshold(fg_threshold, "GAN: fg_threshold")
         if not 0.0 <= ema_decay < 1.0:
             raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay!r}")
         if not grad_clip >= 0:
@@ -465,10 +472,15 @@ class GAN(nn.Module):
         # (DESIGN.md 7i); like every generator term it sees the pair fit_batch hands over, never DiffAugment's output
         self.edge_weight = float(edge_weight)
         self.edge_loss = EdgeLoss(eps=edge_eps) if self.edge_weight > 0 else None
+        # and fg_weight * mean |G(t1w) - t2w| over the foreground of t2w, t2w > fg_threshold ("otsu": found per image on
+        # the device, no host sync): the anatomy weighted above the air around it
+        self.fg_weight = float(fg_weight)
+        self.fg_loss = ForegroundL1Loss(fg_threshold) if self.fg_weight > 0 else None
         # the active terms as (log name, weight, module), in the order _add_generator_terms adds them to g_loss
         self._generator_terms = [(name, weight, module) for name, weight, module in (
             ("g_mi_loss", self.mi_weight, self.mi_loss), ("g_ssim_loss", self.ssim_weight, self.ssim_loss),
-            ("g_edge_loss", self.edge_weight, self.edge_loss)) if module is not None]
+            ("g_edge_loss", self.edge_weight, self.edge_loss), ("g_fg_loss", self.fg_weight, self.fg_loss))
+            if module is not None]
         # opt-in differentiable augmentation of everything D sees in training_step (augment.py); with the
         # default "" there is no module and no launch.  aug_generator: a torch.Generator on the images' device, or None
         # for torch's global one (data-parallel runs: every rank seeds its own, or all ranks draw the same parameters)
@@ -574,7 +586,8 @@ class GAN(nn.Module):
         and discriminator in eval mode (running-statistics BatchNorm) under no_grad -- no parameter, buffer, gradient or
         optimizer state is touched.  Logs and returns val_g_adv_loss, val_g_recon_loss, val_g_loss, val_d_loss as
         device scalars (no host sync); with mi_weight > 0 also val_g_mi_loss, with ssim_weight > 0 also
-        val_g_ssim_loss and with edge_weight > 0 also val_g_edge_loss, which val_g_loss then includes; with
+        val_g_ssim_loss, with edge_weight > 0 also val_g_edge_loss and with fg_weight > 0 also val_g_fg_loss, which
+        val_g_loss then includes; with
         ema_decay > 0 also val_ema_g_recon_loss, the L1 of generator_ema(t1w) against t2w."""
         t1w_images, t2w_images = batch["t1w"], batch["t2w"]
         with torch.no_grad(), eval_modes(self.generator, self.discriminator):

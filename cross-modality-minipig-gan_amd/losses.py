@@ -14,7 +14,11 @@ torch restatement tests/ssim_loss_ref.py.
 EdgeLoss is the edge-aware generator term of Ea-GAN (Yu et al. 2019): the L1 distance of the 3-D Sobel edge-magnitude
 maps of the two volumes, over a replicate border.  csrc/edge_loss.hip holds the fused stencils (the forward writes no
 map, the backward recomputes from the two inputs) and sobel_magnitude, the map itself as a differentiable op.  Ea-GAN's
-code is not available here: the definition in include/mpgan_hip.h is what is pinned, against tests/edge_loss_ref.py."""
+code is not available here: the definition in include/mpgan_hip.h is what is pinned, against tests/edge_loss_ref.py.
+
+MaskedL1Loss / ForegroundL1Loss weight the L1 by a foreground mask: an explicit mask, or
+target > threshold formed on the fly with the threshold found on the device (preprocess.otsu_threshold).
+csrc/foreground.hip holds the kernels; pinned against tests/foreground_ref.py."""
 from __future__ import annotations
 
 import torch
@@ -22,6 +26,7 @@ import torch.nn as nn
 
 from . import ops
 from .metrics import ValueRange, _ranges
+from .preprocess import _otsu_config, check_threshold, item_thresholds
 
 _REDUCTIONS = ("mean", "sum", "none")
 MAX_BINS = 32
@@ -316,3 +321,114 @@ class EdgeLoss(nn.Module):
 
     def forward(self, pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         return edge_loss(pred, target, self.eps, self.reduction)
+
+
+def _masked_l1_config(fg_weight, bg_weight, reduction, who):
+    _check_reduction(reduction, who)
+    try:
+        w_fg, w_bg = float(fg_weight), float(bg_weight)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: fg_weight and bg_weight must be numbers, got {fg_weight!r} and {bg_weight!r}") from None
+    if not (0.0 <= w_fg < float("inf") and 0.0 <= w_bg < float("inf")):
+        raise ValueError(f"{who}: fg_weight and bg_weight must be finite and >= 0, got {fg_weight!r} and {bg_weight!r}")
+    return w_fg, w_bg
+
+
+def _masked_l1_shape_error(shape):
+    if len(shape) not in (4, 5) or 0 in shape:
+        return f"expects non-empty (B, C, H, W) or (B, C, D, H, W) tensors, got {shape}"
+
+
+class _MaskedL1Fn(torch.autograd.Function):
+    """The reduced loss; saves the two inputs, the mask source and every item's denominator.  One backward launch
+    writes both gradients; it only reads what was saved, so a second backward (retain_graph) gives the same bits."""
+
+    @staticmethod
+    def forward(ctx, pred, target, mask, thr, w_fg, w_bg, reduction):
+        a, b, (batch, channels, _), loss, scale = _pair_forward(pred, target, reduction)
+        items = batch * channels
+        den = torch.empty(items, dtype=torch.float64, device=a.device)
+        ops.masked_l1_forward(a, b, items, channels, mask, thr, w_fg, w_bg, den, reduction, loss)
+        ctx.cfg = (items, channels, w_fg, w_bg, scale)
+        ctx.save_for_backward(a, b, den, mask, thr)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        a, b, den, mask, thr = ctx.saved_tensors
+        items, channels, w_fg, w_bg, scale = ctx.cfg
+        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        db = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        if da is not None or db is not None:
+            ops.masked_l1_backward(a, b, items, channels, mask, thr, w_fg, w_bg, den, gout.contiguous(), scale, da, db)
+        return (da, db) + (None,) * 5
+
+
+def masked_l1_loss(pred: torch.Tensor, target: torch.Tensor, mask: torch.Tensor = None, *, threshold=None,
+                   fg_weight: float = 1.0, bg_weight: float = 0.0, reduction: str = "mean", bins: int = 256,
+                   value_range=(-1.0, 1.0)) -> torch.Tensor:
+    """The mask-weighted L1 of two (B, C, H, W) or (B, C, D, H, W) fp32 device tensors: per (b, c) image
+    sum_i w_i |pred_i - target_i| / sum_i w_i with w_i = fg_weight inside the mask and bg_weight outside (0 for an image
+    whose weights sum to 0).  Exactly one of:
+      mask       a bool / uint8 device tensor of pred's shape, or with channel extent 1 (broadcast over the channels);
+      threshold  "otsu", a number, or an fp32 device tensor with one value per (b, c) image: the mask is
+                 target > threshold, formed on the fly -- no mask tensor exists and nothing syncs.  "otsu" takes
+                 preprocess.otsu_threshold(target, bins, value_range).
+    reduction: "mean" (a scalar over the B * C images), "sum", or "none" ((B,), each entry the mean over its channels).
+    Differentiable in pred and target (d target = -d pred); nothing flows into the mask or the threshold.  Sums are
+    fp64 in a fixed order: bitwise reproducible.  Defined in include/mpgan_hip.h, pinned against
+    tests/foreground_ref.py."""
+    who = "masked_l1_loss"
+    w_fg, w_bg = _masked_l1_config(fg_weight, bg_weight, reduction, who)
+    if (mask is None) == (threshold is None):
+        raise ValueError(f"{who}: give exactly one of mask and threshold")
+    if mask is None:
+        check_threshold(threshold, who)
+    elif not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"{who}: mask must be a bool / uint8 tensor")
+    _pair_inputs(pred, target, who, _masked_l1_shape_error)
+    thr = None
+    if mask is None:
+        thr = item_thresholds(target.contiguous(), threshold, bins, value_range, who)
+    else:
+        shape = tuple(pred.shape)
+        if mask.device != pred.device or tuple(mask.shape) not in (shape, shape[:1] + (1,) + shape[2:]):
+            raise ValueError(f"{who}: mask must lie on the inputs' device with their shape {shape} or channel extent 1, "
+                             f"got {tuple(mask.shape)}")
+        mask = mask.expand(shape).contiguous()
+        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    return _MaskedL1Fn.apply(pred, target, mask, thr, w_fg, w_bg, reduction)
+
+
+class MaskedL1Loss(nn.Module):
+    """masked_l1_loss as a module: forward(pred, target, mask=None); without a mask the module's threshold is used."""
+
+    def __init__(self, threshold=None, fg_weight: float = 1.0, bg_weight: float = 0.0, reduction: str = "mean",
+                 bins: int = 256, value_range=(-1.0, 1.0)):
+        super().__init__()
+        self.fg_weight, self.bg_weight = _masked_l1_config(fg_weight, bg_weight, reduction, "MaskedL1Loss")
+        if threshold is not None:
+            check_threshold(threshold, "MaskedL1Loss")
+        self.threshold, self.reduction, self.bins, self.value_range = threshold, reduction, bins, tuple(value_range)
+
+    def forward(self, pred: torch.Tensor, target: torch.Tensor, mask: torch.Tensor = None) -> torch.Tensor:
+        return masked_l1_loss(pred, target, mask, threshold=None if mask is not None else self.threshold,
+                              fg_weight=self.fg_weight, bg_weight=self.bg_weight, reduction=self.reduction,
+                              bins=self.bins, value_range=self.value_range)
+
+
+class ForegroundL1Loss(nn.Module):
+    """(pred, target) -> the mean |pred - target| over the foreground of target, target > threshold ("otsu": Otsu's
+    threshold of every target image over value_range, on the device; or a number): the generator term GAN's fg_weight
+    switches on.  The background carries no weight."""
+
+    def __init__(self, threshold="otsu", value_range=(-1.0, 1.0), bins: int = 256):
+        super().__init__()
+        check_threshold(threshold, "ForegroundL1Loss")
+        if isinstance(threshold, torch.Tensor):
+            raise ValueError("ForegroundL1Loss: threshold must be \"otsu\" or a finite number")
+        _otsu_config(bins, value_range, "ForegroundL1Loss")
+        self.threshold, self.value_range, self.bins = threshold, tuple(value_range), int(bins)
+
+    def forward(self, pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        return masked_l1_loss(pred, target, threshold=self.threshold, bins=self.bins, value_range=self.value_range)

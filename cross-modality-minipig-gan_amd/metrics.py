@@ -12,6 +12,7 @@ from typing import Dict, Optional, Tuple, Union
 
 import torch
 
+from . import ops
 from ._lib import check, lib
 
 
@@ -30,10 +31,29 @@ def rescale_0_255(x: torch.Tensor, do_round: bool = True) -> torch.Tensor:
     return y
 
 
-def image_errors(a: torch.Tensor, b: torch.Tensor, data_range: float = 256.0) -> Dict[str, torch.Tensor]:
-    """MAE, MSE and PSNR between two same-shape device tensors (scalars stay on the device)."""
+def _masked_image_errors(a, b, data_range, mask):
+    if a.dtype != torch.float32 or b.dtype != torch.float32 or not (a.is_cuda and b.is_cuda):
+        raise ValueError("image_errors: a mask needs two fp32 device tensors")
+    if (not isinstance(mask, torch.Tensor) or mask.shape != a.shape or mask.dtype not in (torch.bool, torch.uint8)
+            or mask.device != a.device):
+        raise ValueError("image_errors: mask must be a same-shape bool / uint8 tensor on the inputs' device")
+    if a.numel() == 0:
+        raise ValueError("image_errors: empty tensors")
+    a, b, mask = a.contiguous(), b.contiguous(), mask.contiguous()
+    mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    out = ops.masked_image_errors(a, b, mask, data_range, torch.empty(4, dtype=torch.float64, device=a.device))
+    return {"mae": out[0], "mse": out[1], "psnr": out[2], "count": out[3]}
+
+
+def image_errors(a: torch.Tensor, b: torch.Tensor, data_range: float = 256.0,
+                 mask: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """MAE, MSE and PSNR between two same-shape device tensors (scalars stay on the device).  With mask (a same-shape
+    bool / uint8 device tensor, e.g. preprocess.foreground_mask's output) the three are taken over the voxels whose
+    mask is non-zero, in float64, and "count" is their number; an empty mask gives NaN and count 0."""
     if a.shape != b.shape:
         raise ValueError("image_errors: shape mismatch")
+    if mask is not None:
+        return _masked_image_errors(a, b, data_range, mask)
     a, b = a.contiguous(), b.contiguous()
     part = torch.empty(int(lib().mpgan_metric_partials()), device=a.device)
     out = torch.empty(3, device=a.device)
@@ -43,12 +63,14 @@ def image_errors(a: torch.Tensor, b: torch.Tensor, data_range: float = 256.0) ->
 
 
 def score_volume(generated: torch.Tensor, ground_truth: torch.Tensor,
-                 mutual_information: bool = False) -> Dict[str, torch.Tensor]:
+                 mutual_information: bool = False, mask: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
     """The inference script's scoring: both volumes rescaled to 0..255 and rounded, then compared
     (MAE / MSE / PSNR; plus SSIM when the tensors are (H, W) or (D, H, W)).  mutual_information=True
-    adds "mi" and "nmi" of the two rescaled volumes (256 bins over [0, 256], nats)."""
+    adds "mi" and "nmi" of the two rescaled volumes (256 bins over [0, 256], nats).  mask (a same-shape bool / uint8
+    device tensor, e.g. preprocess.foreground_mask(ground_truth)) restricts MAE / MSE / PSNR to its voxels and adds
+    "count"; the rescaling, "ssim", "mi" and "nmi" stay whole-volume figures."""
     g, t = rescale_0_255(generated), rescale_0_255(ground_truth)
-    out = image_errors(g, t, 256.0)
+    out = image_errors(g, t, 256.0, mask)
     if g.dim() in (2, 3) and min(g.shape[-2:]) >= 7 and (g.dim() == 2 or g.shape[0] >= 7):
         out["ssim"] = ssim(g, t, 256.0)
     if mutual_information:

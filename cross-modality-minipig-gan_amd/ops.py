@@ -1071,6 +1071,56 @@ def edge_loss_backward(a, b, spatial, items, channels, eps, upstream, scale, wrt
     return grad
 
 
+# ---- foreground masks (csrc/foreground.hip; preprocess.py, losses.py and metrics.py hold the public functions) ----
+def otsu_threshold(x, items, lo, hi, bins, thr):
+    """thr[items] = Otsu's threshold of every item of the contiguous fp32 tensor x (see include/mpgan_hip.h)."""
+    need = int(lib().mpgan_otsu_workspace(int(items), int(bins)))
+    if need < 0:
+        raise ValueError(f"otsu_threshold: bad geometry ({items} items, {bins} bins; bins must lie in [2, 256])")
+    ws = torch.empty(need // 8, dtype=torch.int64, device=x.device)
+    check(lib().mpgan_otsu_threshold(x.data_ptr(), x.numel() // int(items), int(items), float(lo), float(hi), int(bins),
+                                     ws.data_ptr(), thr.data_ptr(), _stream()), "otsu_threshold")
+    return thr
+
+
+def foreground_mask(x, spatial, items, thr, margin=(0, 0, 0), mask=None, box=None, count=None):
+    """Any of mask (uint8, x's shape), box (int32 (items, 2, 3)) and count (int64 (items,)) of x > thr[item]; margin
+    is (z, y, x)."""
+    mz, my, mx = (int(m) for m in margin)
+    check(lib().mpgan_foreground_mask(x.data_ptr(), _dhw(spatial), int(items), thr.data_ptr(),
+                                      (C.c_int32 * 3)(mz, my, mx), _ptr(mask), _ptr(box), _ptr(count), _stream()),
+          "foreground_mask")
+
+
+def masked_l1_forward(a, b, items, channels, mask, thr, w_fg, w_bg, den, reduction, loss):
+    """loss (fp32, reduced on the device) and den[items] (float64) of the mask-weighted L1; one of mask, thr."""
+    per_item = a.numel() // int(items)
+    need = int(lib().mpgan_masked_l1_workspace(per_item, int(items)))
+    if need < 0:
+        raise ValueError(f"masked_l1_forward: bad geometry ({items} items of {per_item} values)")
+    ws = torch.empty(need // 8, dtype=torch.float64, device=a.device)
+    check(lib().mpgan_masked_l1_forward(a.data_ptr(), b.data_ptr(), per_item, int(items), int(channels), _ptr(mask),
+                                        _ptr(thr), float(w_fg), float(w_bg), ws.data_ptr(), _nbytes(ws), den.data_ptr(),
+                                        _REDUCTIONS[reduction], loss.data_ptr(), _stream()), "masked_l1_forward")
+    return loss
+
+
+def masked_l1_backward(a, b, items, channels, mask, thr, w_fg, w_bg, den, upstream, scale, da, db):
+    """da and / or db = +-upstream[batch entry or 0] * scale * w_i * sign(a - b) / den_item."""
+    check(lib().mpgan_masked_l1_backward(a.data_ptr(), b.data_ptr(), a.numel() // int(items), int(items), int(channels),
+                                         _ptr(mask), _ptr(thr), float(w_fg), float(w_bg), den.data_ptr(),
+                                         upstream.data_ptr(), _up_stride(upstream), float(scale), _ptr(da), _ptr(db),
+                                         _stream()), "masked_l1_backward")
+
+
+def masked_image_errors(a, b, mask, data_range, out4):
+    """out4 (float64) = (MAE, MSE, PSNR, count) over the voxels whose mask byte is non-zero."""
+    part = torch.empty(int(lib().mpgan_masked_errors_partials(a.numel())), dtype=torch.float64, device=a.device)
+    check(lib().mpgan_masked_image_errors(a.data_ptr(), b.data_ptr(), mask.data_ptr(), a.numel(), float(data_range),
+                                          part.data_ptr(), out4.data_ptr(), _stream()), "masked_image_errors")
+    return out4
+
+
 # ---- differentiable augmentation (csrc/diffaug.hip; augment.py holds the sampler and the autograd node) ----
 DIFFAUG_BRIGHTNESS, DIFFAUG_CONTRAST, DIFFAUG_TRANSLATION, DIFFAUG_CUTOUT = 1, 2, 4, 8      # MPGAN_DIFFAUG_*
 

@@ -596,6 +596,99 @@ int mpgan_edge_loss_backward(const float* a, const float* b, const int32_t* dhw,
                              double eps, const float* upstream, int32_t upstream_stride, double scale, int32_t wrt,
                              float* grad, void* stream);
 
+/* ---- foreground masks: Otsu threshold, mask / bounding box / count, mask-weighted L1, masked errors
+ * (foreground.hip; DESIGN.md 7k.  The reference imports MONAI's CropForegroundd and ThresholdIntensityd in its scoring
+ * scripts, code/GAN/minipig_inference.py:28,43, and never calls them; MONAI and skimage are not in this image: the
+ * definitions below are what is pinned, against tests/foreground_ref.py) ----
+ * An item is one (batch, channel) image of numel_per_item contiguous fp32 values; items = batch * channels.  All four
+ * groups are one-pass streams: a block of 256 threads walks a contiguous chunk of one item, thread t taking the groups
+ * of four consecutive values t, t + 256, ... of the chunk in that order -- 16 bytes wide when the item's first value is
+ * 16-byte aligned (a mask: 4-byte aligned), value by value otherwise and in a last short group; the values a thread
+ * sees, and their order, do not depend on the alignment.  The number of chunks depends on the sizes alone.
+ * Floating-point sums are fp64: a thread adds its terms in that order, the block folds its threads by a fixed tree
+ * and stores one partial, the partials of an item are added in slot order by a fixed tree.  No floating-point atomics
+ * anywhere; integer atomics (counts, minima, maxima) do not depend on order.  Results are bitwise reproducible from
+ * call to call.  The calls allocate nothing, are asynchronous on `stream` and can be captured into a graph. */
+
+/* thr[item] (device float[items]) = Otsu's threshold of the item's histogram, as skimage.filters.threshold_otsu forms
+ * it from bin counts and bin centres.
+ *   n_j   = number of the item's values in bin j of `bins` equal-width bins over [lo, hi], by mpgan_joint_histogram's
+ *           rule: j = min((int)floorf((v - lo) * s), bins - 1), s = (float)bins / (hi - lo), in fp32 exactly as written,
+ *           so v == lo falls into bin 0 and v == hi into the last bin; v < lo, v > hi and NaN are dropped.  Exact integers.
+ *   c_j   = lo + (j + 0.5) * (hi - lo) / bins          in double, evaluated left to right from the two floats
+ *   N     = sum_j n_j
+ *   for k = 0 .. bins - 2:
+ *     w0 = sum_{j <= k} n_j;  w1 = N - w0                                        (integers)
+ *     mu0 = (sum_{j <= k} n_j c_j, added for j = 0, 1, .. k) / w0                (double)
+ *     mu1 = (sum_{j > k} n_j c_j, added for j = bins - 1, bins - 2, .. k + 1) / w1
+ *     var_k = (w0 * w1) * ((mu0 - mu1) * (mu0 - mu1)), and 0 where w0 == 0 or w1 == 0
+ *   k* = the FIRST k that attains max_k var_k;  thr = (float)c_{k*}
+ * Degenerate items: N == 0 gives NaN; exactly one non-empty bin j gives (float)c_j (every var_k is 0 there, and the
+ * centre of the occupied bin is the one value that describes the image).
+ * 2 <= bins <= 256; items >= 1; numel_per_item >= 1; lo < hi, both finite and s finite; workspace >=
+ * mpgan_otsu_workspace(items, bins) bytes, 8-byte aligned (the int64 histograms; the call zeroes them).  Anything
+ * else, or a null x / workspace / thr, is MPGAN_ERR_INVALID before any launch. */
+int64_t mpgan_otsu_workspace(int32_t items, int32_t bins); /* bytes; -1 on a bad argument */
+int mpgan_otsu_threshold(const float* x, int64_t numel_per_item, int32_t items, float lo, float hi, int32_t bins,
+                         void* workspace, float* thr, void* stream);
+
+/* One pass over x[items][D][H][W] (dhw = (D, H, W), D == 1 for 2-D) against the per-item thresholds thr (device
+ * float[items], e.g. mpgan_otsu_threshold's output: no host sync in between).  A voxel is foreground when
+ * x > thr[item], strictly and in fp32: a value equal to the threshold is background, and a NaN value or a NaN
+ * threshold gives background.  Each output may be null; at least one must be asked for.
+ *   mask[items][D][H][W]  uint8, 1 for foreground and 0 otherwise
+ *   count[items]          int64, the number of foreground voxels
+ *   box[items][2][3]      int32, MONAI's generate_spatial_bounding_box per item over the axes (z, y, x):
+ *                         box[item][0][d] = start_d = max(min_d - margin[d], 0),
+ *                         box[item][1][d] = end_d   = min(max_d + 1 + margin[d], extent_d)   (exclusive),
+ *                         min_d / max_d the smallest / largest index of a foreground voxel along axis d;
+ *                         an item without foreground gives start = end = 0 on every axis.
+ * margin: host int32[3] >= 0 over (z, y, x), read at call time; null means no margin.  The call initialises box and
+ * count itself (a small launch in front, and one behind that turns the raw extremes into the box).
+ * MPGAN_ERR_INVALID before any launch: a null x / dhw / thr, no output at all, items < 1, an extent < 1, a negative
+ * margin. */
+int mpgan_foreground_mask(const float* x, const int32_t* dhw, int32_t items, const float* thr, const int32_t* margin,
+                          uint8_t* mask /* nullable */, int32_t* box /* nullable */, int64_t* count /* nullable */,
+                          void* stream);
+
+/* Mask-weighted L1 of two arrays a, b of items x numel_per_item values.  The mask has exactly ONE source:
+ *   mask  uint8[items][numel_per_item], m_i = (mask_i != 0); or
+ *   thr   device float[items],          m_i = (b_i > thr[item]) by mpgan_foreground_mask's rule -- no mask array exists.
+ *   w_i = m_i ? w_fg : w_bg   (doubles, >= 0 and finite)
+ *   num_item = sum_i w_i * |a_i - b_i|, every term in fp64 from the two floats (the difference is exact)
+ *   den_item = w_fg * n_fg + w_bg * (numel_per_item - n_fg), n_fg the exact number of i with m_i  (= sum_i w_i)
+ *   loss_item = num_item / den_item, and 0 where den_item == 0
+ *   reduction 0: loss[0] = mean over the items; 1: loss[0] = their sum; 2: loss[batch], entry b = mean over b's channels
+ *   (batch = items / channels), as the SSIM and edge losses define them.
+ * den (device double[items]) receives den_item: the backward reads it.  workspace >=
+ * mpgan_masked_l1_workspace(numel_per_item, items) bytes, 8-byte aligned.
+ * MPGAN_ERR_INVALID before any launch: a null a / b / workspace / den / loss, both mask sources or neither,
+ * items < 1, numel_per_item < 1, channels < 1 or no divisor of items, a negative or non-finite weight, an unknown
+ * reduction, a workspace that is too small. */
+int64_t mpgan_masked_l1_workspace(int64_t numel_per_item, int32_t items); /* bytes; -1 on a bad argument */
+int mpgan_masked_l1_forward(const float* a, const float* b, int64_t numel_per_item, int32_t items, int32_t channels,
+                            const uint8_t* mask, const float* thr, double w_fg, double w_bg, void* workspace,
+                            int64_t workspace_bytes, double* den, int32_t reduction, float* loss, void* stream);
+/* da_i = (float)(upstream[(item / channels) * upstream_stride] * scale * w_i / den_item) * sign(a_i - b_i), with
+ * sign(0) = 0 (and 0 for a NaN difference), the factor formed in double and rounded to fp32 once per item and weight;
+ * db_i = -da_i, bit for bit.  Either output may be null, not both.  An item with den_item == 0 gets zeros.  Nothing
+ * flows into the mask or the threshold.  upstream is a device array over the batch (stride 1) or one device scalar
+ * (stride 0); scale is the host factor of the reduction (1 for the sum, 1 / items for the mean, 1 / channels for
+ * reduction 2).  The mask source, the weights and den are those of the forward call. */
+int mpgan_masked_l1_backward(const float* a, const float* b, int64_t numel_per_item, int32_t items, int32_t channels,
+                             const uint8_t* mask, const float* thr, double w_fg, double w_bg, const double* den,
+                             const float* upstream, int32_t upstream_stride, double scale, float* da /* nullable */,
+                             float* db /* nullable */, void* stream);
+
+/* out4 (device double[4]) = (MAE, MSE, PSNR, count) of a against b over the n voxels whose mask byte is non-zero:
+ *   MAE = sum |a - b| / n;  MSE = sum (a - b)^2 / n;  PSNR = 10 log10(data_range^2 / MSE);  count = n
+ * with every term and every sum in fp64.  An empty mask gives NaN for the three and count 0.  MSE == 0 gives
+ * PSNR = +infinity, as mpgan_image_errors gives.  partials: >= mpgan_masked_errors_partials(numel) doubles, 8-byte
+ * aligned.  A null pointer or numel < 1 is MPGAN_ERR_INVALID before any launch. */
+int64_t mpgan_masked_errors_partials(int64_t numel); /* doubles of caller-supplied scratch (-1: numel < 1) */
+int mpgan_masked_image_errors(const float* a, const float* b, const uint8_t* mask, int64_t numel, float data_range,
+                              double* partials, double* out4, void* stream);
+
 /* ---- differentiable augmentation in front of the discriminator (DiffAugment, Zhao et al. 2020) ----
  * x: contiguous fp32 [n][D][H][W] (one channel; 2-D images have D = 1); N = D H W.  Per sample s, from two device tables
  * (nothing is read on the host):
