@@ -135,6 +135,12 @@ SIGNATURES = {
     "mpgan_ssim_loss_workspace": (_L, [_I3, _I, _I, C.POINTER(C.c_int64)]),
     "mpgan_ssim_loss_forward": (_I, [_P, _P, _I3, _I, _I, C.c_double, C.c_double, _I, _P, _L, _P, _L, _I, _P, _P]),
     "mpgan_ssim_loss_backward": (_I, [_P, _P, _I3, _I, _I, C.c_double, _I, _P, _L, _P, _I, C.c_double, _I, _P, _P]),
+    # masked SSIM and the per-window map (ssim_loss.hip)
+    "mpgan_masked_ssim_loss_workspace": (_L, [_I3, _I, _I, C.POINTER(C.c_int64)]),
+    "mpgan_masked_ssim_loss_forward": (_I, [_P, _P, _I3, _I, _I, C.c_double, C.c_double, _P, _P, _I, _P, _L, _P, _L, _P,
+                                            _P, _I, _P, _P]),
+    "mpgan_masked_ssim_loss_backward": (_I, [_P, _P, _I3, _I, _I, C.c_double, _I, _P, _L, _P, _P, _I, C.c_double, _I, _P,
+                                             _P]),
     # Sobel edge loss (edge_loss.hip)
     "mpgan_sobel_magnitude_forward": (_I, [_P, _I3, _I, C.c_double, _P, _P]),
     "mpgan_sobel_magnitude_backward": (_I, [_P, _I3, _I, C.c_double, _P, _P, _P]),

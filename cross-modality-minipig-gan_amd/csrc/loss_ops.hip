@@ -211,6 +211,29 @@ __global__ __launch_bounds__(256) void loss_item_kernel(const double* __restrict
   if (threadIdx.x == 0) item[blockIdx.x] = s * inv;
 }
 
+// The same with a divisor per item (masked SSIM): n = the item's counts added up (integers: exact in any order),
+// stats[i] = (s / n, n) with s taken in loss_item_kernel's order, NaN for n == 0; item[i] = s / n, and 1 for n == 0, so
+// that the ONE_MINUS reduction below adds exactly 0 for an empty item.
+__global__ __launch_bounds__(256) void loss_item_counted_kernel(const double* __restrict__ partials,
+                                                                const long long* __restrict__ counts, long tiles,
+                                                                double* __restrict__ item, double* __restrict__ stats) {
+  __shared__ double red[256];
+  __shared__ long long cnt4[4];
+  const double* w = partials + (long)blockIdx.x * tiles;
+  const long long* k = counts + (long)blockIdx.x * tiles;
+  double s = 0.0;
+  long long c = 0;
+  for (long i = threadIdx.x; i < tiles; i += 256) { s += w[i]; c += k[i]; }
+  s = block_tree_sum<256>(s, red);
+  c = block_sum4(c, cnt4);
+  if (threadIdx.x == 0) {
+    const double v = c > 0 ? s / (double)c : __longlong_as_double(0x7ff8000000000000LL);
+    stats[2 * blockIdx.x] = v;
+    stats[2 * blockIdx.x + 1] = (double)c;
+    item[blockIdx.x] = c > 0 ? v : 1.0;
+  }
+}
+
 // reduction 0: loss[0] = mean over the items of v; 1: their sum; 2: loss[b] = mean over b's channels.  v = item[i], or
 // 1.0 - item[i] with ONE_MINUS (SSIM: the subtraction comes before the sum)
 template <bool ONE_MINUS>
@@ -235,6 +258,13 @@ void launch_loss_tail(const double* partials, long tiles, double inv, double* it
                       int reduction, bool one_minus, float* loss, hipStream_t stream) {
   hipLaunchKernelGGL(loss_item_kernel, dim3((unsigned)items), dim3(256), 0, stream, partials, tiles, inv, item);
   launch_loss_reduce(item, items, channels, reduction, one_minus, loss, stream);
+}
+
+void launch_counted_loss_tail(const double* partials, const long long* counts, long tiles, double* item, double* stats,
+                              int items, int channels, int reduction, float* loss, hipStream_t stream) {
+  hipLaunchKernelGGL(loss_item_counted_kernel, dim3((unsigned)items), dim3(256), 0, stream, partials, counts, tiles,
+                     item, stats);
+  launch_loss_reduce(item, items, channels, reduction, true, loss, stream);
 }
 
 void launch_loss_reduce(const double* item, int items, int channels, int reduction, bool one_minus, float* loss,

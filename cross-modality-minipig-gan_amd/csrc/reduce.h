@@ -63,6 +63,12 @@ __device__ __forceinline__ double strided_serial_sum256(const T* __restrict__ x,
 void launch_loss_tail(const double* partials, long tiles, double inv, double* item, int items, int channels,
                       int reduction, bool one_minus, float* loss, hipStream_t stream);
 
+// The tail of a tiled pair loss whose items have a divisor of their own, found on the device (masked SSIM): per item
+// n = the sum of its int64 tile counts (integers: no order to fix), s = its tile partials by the order above,
+// stats[i] = (s / n, n) and NaN for n == 0; then over the items the sum of 1.0 - s / n, 0 for n == 0, as above.
+void launch_counted_loss_tail(const double* partials, const long long* counts, long tiles, double* item, double* stats,
+                              int items, int channels, int reduction, float* loss, hipStream_t stream);
+
 // The second of those two launches alone, for a loss whose per-item value has a divisor of its own (foreground.hip).
 void launch_loss_reduce(const double* item, int items, int channels, int reduction, bool one_minus, float* loss,
                         hipStream_t stream);

@@ -23,6 +23,15 @@
 // centred product costs.  The maps are therefore doubles: 24 B per window and image for one gradient, 32 B for both
 // (about 200 MB at 4 x 1 x 128^3), and the backward's box sums run in double too; only the final product with the
 // upstream gradient is rounded to fp32.
+//
+// The foreground-weighted form (include/mpgan_hip.h: "masked SSIM") is the same two kernels under one more
+// template parameter: a valid window carries a weight w in {0, 1} read at its centre voxel -- a byte of the mask
+// (SL_MASK), or the staged b against the item's threshold, out of LDS (SL_THR).  The forward adds w S to the block's
+// partial and w to a second, integer partial, stores w Q, w R, w P (exact: zero or the value, so the backward's box
+// sums are those of the plain form) and can write S itself as an fp32 map; launch_counted_loss_tail (loss_ops.hip) turns
+// the two partial sets into stats[item] = (ssim_item, n_item) and the loss; the backward reads its per-item factor
+// scale / (n n_item) from stats on the device.  SL_PLAIN is the code of the plain entry points, bit for bit: the
+// weighted fields live in a derived parameter struct that the plain instances never see.
 #include "mpgan_common.h"
 
 namespace mpgan {
@@ -30,6 +39,8 @@ namespace mpgan {
 constexpr int SL_W = 7, SL_TY = 8, SL_TX = 32, SL_RY = SL_TY + SL_W - 1, SL_RX = SL_TX + SL_W - 1;
 constexpr int SL_TZ3 = 4;                       // z tile of the 3-D forms (forward: window corners, backward: voxels)
 constexpr int SL_PLANE = SL_RY * SL_RX;
+
+constexpr int SL_PLAIN = 0, SL_MASK = 1, SL_THR = 2;      // where a window's weight comes from
 
 struct SlFwd {
   const float* a;
@@ -44,8 +55,21 @@ struct SlFwd {
   double* pb;
 };
 
-template <int WZ, int TZ>
-__global__ __launch_bounds__(256) void sl_forward_kernel(SlFwd p) {
+struct SlFwdW : SlFwd {                         // the weighted instances' additions
+  const uint8_t* mask;                          // SL_MASK: [items][D][H][W], or null for w = 1 everywhere
+  const float* thr;                             // SL_THR: [items]
+  long long* counts;                            // [items][tiles]: the block's number of weighted windows
+  float* smap;                                  // [items][M]: S of every valid window, or null
+};
+
+// The parameter struct of an instance, by specialisation: the kernels' mangled names then hold the template arguments
+// alone (an expression over a constant in the signature is mangled with the constant's type and name, and the host
+// and the device pass number an unnamed type differently -- the runtime then finds no such kernel).
+template <int MODE> struct SlFwdOf { using type = SlFwdW; };
+template <> struct SlFwdOf<SL_PLAIN> { using type = SlFwd; };
+
+template <int WZ, int TZ, int MODE>
+__global__ __launch_bounds__(256) void sl_forward_kernel(typename SlFwdOf<MODE>::type p) {
   constexpr int RZ = TZ + WZ - 1;
   extern __shared__ float sl_sm[];              // [2][RZ][SL_RY][SL_RX]
   __shared__ double red[256];
@@ -71,6 +95,27 @@ __global__ __launch_bounds__(256) void sl_forward_kernel(SlFwd p) {
   __syncthreads();
   const int tx = tid % SL_TX, ty = tid / SL_TX;
   const int OD = p.D - WZ + 1, OH = p.H - SL_W + 1, OW = p.W - SL_W + 1;   // window corners
+  // the weights of this column's TZ windows as one bit each, read at the centre voxel (corner + 3 on every windowed
+  // axis) ahead of the plane sums, which hide the mask bytes' latency; the scheduling barrier keeps the plane loop below
+  // what it is in the plain form
+  unsigned wbits = 0;
+  if constexpr (MODE != SL_PLAIN) {
+    constexpr int CZ = WZ / 2, CYX = SL_W / 2;
+    float thr = 0.f;
+    if constexpr (MODE == SL_THR) thr = p.thr[item];
+#pragma unroll
+    for (int zo = 0; zo < TZ; ++zo) {
+      const int cz = z0 + zo, cy = y0 + ty, cx = x0 + tx;
+      bool w = cz < OD && cy < OH && cx < OW;
+      if constexpr (MODE == SL_MASK) {
+        if (w && p.mask) w = p.mask[item * vox + ((long)(cz + CZ) * p.H + cy + CYX) * p.W + cx + CYX] != 0;
+      } else {                                  // the staged b: strict, in fp32, false for a NaN on either side
+        w = w && sb[((zo + CZ) * SL_RY + ty + CYX) * SL_RX + tx + CYX] > thr;
+      }
+      wbits |= (unsigned)w << zo;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
   // window sums of the TZ corners of this column; a plane's five sums are formed once and added to every window
   // that holds the plane (in plane order), so that only 5 TZ doubles stay live across the planes
   double wa[TZ], wb[TZ], waa[TZ], wbb[TZ], wab[TZ];
@@ -105,6 +150,7 @@ __global__ __launch_bounds__(256) void sl_forward_kernel(SlFwd p) {
   for (int zo = 0; zo < TZ; ++zo) {
     const int cz = z0 + zo, cy = y0 + ty, cx = x0 + tx;
     if (cz >= OD || cy >= OH || cx >= OW) continue;
+    const bool w = MODE == SL_PLAIN || ((wbits >> zo) & 1u);
     double s_a = wa[zo], s_b = wb[zo], s_aa = waa[zo], s_bb = wbb[zo], s_ab = wab[zo];
     // sums of the shifted samples x - lo from the sums of the raw ones (the three second moments by one expression,
     // so that identical images keep vx == vy == vxy bit for bit)
@@ -119,21 +165,31 @@ __global__ __launch_bounds__(256) void sl_forward_kernel(SlFwd p) {
     const double A1 = 2.0 * ux * uy + p.c1, A2 = 2.0 * vxy + p.c2;
     const double B1 = ux * ux + uy * uy + p.c1, B2 = vx + vy + p.c2;
     const double S = (A1 * A2) / (B1 * B2);
-    local += S;
+    if constexpr (MODE == SL_PLAIN) {
+      local += S;
+    } else {
+      local += w ? S : 0.0;
+      if (p.smap) p.smap[item * M + ((long)cz * OH + cy) * OW + cx] = (float)S;
+    }
     if (p.q) {
       const double inv = 1.0 / (B1 * B2);       // 1/B1 = B2 inv, 1/B2 = B1 inv
       const double Q = -2.0 * cn * S * (B1 * inv);
       const double R = 2.0 * cn * A1 * inv;
       const long o = item * M + ((long)cz * OH + cy) * OW + cx;
-      p.q[o] = Q;
-      p.r[o] = R;
-      if (p.pa) p.pa[o] = 2.0 * uy * A2 * inv - 2.0 * ux * S * (B2 * inv) - ux * Q - uy * R;
-      if (p.pb) p.pb[o] = 2.0 * ux * A2 * inv - 2.0 * uy * S * (B2 * inv) - uy * Q - ux * R;
+      p.q[o] = w ? Q : 0.0;                     // w is the constant true in the plain form
+      p.r[o] = w ? R : 0.0;
+      if (p.pa) p.pa[o] = w ? 2.0 * uy * A2 * inv - 2.0 * ux * S * (B2 * inv) - ux * Q - uy * R : 0.0;
+      if (p.pb) p.pb[o] = w ? 2.0 * ux * A2 * inv - 2.0 * uy * S * (B2 * inv) - uy * Q - ux * R : 0.0;
     }
     __builtin_amdgcn_sched_barrier(0);          // one window's divisions at a time
   }
   local = block_tree_sum<256>(local, red);      // block sum in a fixed order
   if (tid == 0) p.partials[item * p.tiles + blockIdx.x] = local;
+  if constexpr (MODE != SL_PLAIN) {
+    __shared__ unsigned cnt4[4];
+    const unsigned c = block_sum4((unsigned)__popc(wbits), cnt4);      // integers: no order to fix
+    if (tid == 0) p.counts[item * p.tiles + blockIdx.x] = (long long)c;
+  }
 }
 
 struct SlBwd {
@@ -149,8 +205,15 @@ struct SlBwd {
   float* grad;
 };
 
-template <int WZ, int TZ>
-__global__ __launch_bounds__(256) void sl_backward_kernel(SlBwd p) {
+struct SlBwdW : SlBwd {                         // weighted: scale = reduction factor / n, the item's divisor from stats
+  const double* stats;                          // [items][2] = (ssim_item, n_item)
+};
+
+template <bool WEIGHTED> struct SlBwdOf { using type = SlBwdW; };
+template <> struct SlBwdOf<false> { using type = SlBwd; };
+
+template <int WZ, int TZ, bool WEIGHTED>
+__global__ __launch_bounds__(256) void sl_backward_kernel(typename SlBwdOf<WEIGHTED>::type p) {
   constexpr int RZ = TZ + WZ - 1;
   extern __shared__ double sl_sd[];             // [RZ][SL_RY][SL_RX]: one map's corners, zero outside the valid ones
   const int tid = threadIdx.x;
@@ -165,6 +228,17 @@ __global__ __launch_bounds__(256) void sl_backward_kernel(SlBwd p) {
   const bool col_ok = vy < p.H && vx < p.W;
   const float* x = p.x + item * vox;
   const float* y = p.y + item * vox;
+  double item_scale = p.scale;
+  if constexpr (WEIGHTED) {
+    const double n_item = p.stats[2 * item + 1];
+    if (!(n_item > 0.0)) {                      // an empty item: exactly zero, whatever the upstream (block-uniform)
+      float* out = p.grad + item * vox;
+      for (int zo = 0; zo < TZ; ++zo)
+        if (col_ok && z0 + zo < p.D) out[((long)(z0 + zo) * p.H + vy) * p.W + vx] = 0.f;
+      return;
+    }
+    item_scale = p.scale / n_item;
+  }
   double xv[TZ], yv[TZ], acc[TZ];
 #pragma unroll
   for (int zo = 0; zo < TZ; ++zo) {
@@ -204,7 +278,7 @@ __global__ __launch_bounds__(256) void sl_backward_kernel(SlBwd p) {
       acc[zo] = m == 0 ? g : fma(m == 1 ? xv[zo] : yv[zo], g, acc[zo]);
     }
   }
-  const double up = (double)p.upstream[(item / p.channels) * p.up_stride] * p.scale;
+  const double up = (double)p.upstream[(item / p.channels) * p.up_stride] * item_scale;
   float* out = p.grad + item * vox;
 #pragma unroll
   for (int zo = 0; zo < TZ; ++zo) {
@@ -244,43 +318,78 @@ static int sl_geometry(const char* who, const int32_t* dhw, int32_t items, SlGeo
 
 static int sl_maps(int grad_mask) { return grad_mask == 0 ? 0 : (grad_mask == 3 ? 4 : 3); }
 
-}  // namespace mpgan
+// What a weighted call has beyond a plain one (the plain entry points pass null).
+struct SlWeights {
+  const uint8_t* mask;
+  const float* thr;
+  double* stats;                                // [items][2]
+  float* smap;                                  // nullable
+};
 
-using namespace mpgan;
-
-extern "C" int64_t mpgan_ssim_loss_workspace(const int32_t* dhw, int32_t items, int32_t grad_mask,
-                                             int64_t* coef_bytes) {
+// Workspace: [items][tiles] partials, then (weighted) [items][tiles] int64 counts, then [items] of the loss tail.
+static int64_t sl_workspace(const char* who, const int32_t* dhw, int32_t items, int32_t grad_mask, bool weighted,
+                            int64_t* coef_bytes) {
   SlGeom g;
-  if (grad_mask < 0 || grad_mask > 3 || sl_geometry("ssim_loss_workspace", dhw, items, &g) != MPGAN_OK) return -1;
+  if (grad_mask < 0 || grad_mask > 3 || sl_geometry(who, dhw, items, &g) != MPGAN_OK) return -1;
   if (coef_bytes) *coef_bytes = (int64_t)sl_maps(grad_mask) * items * g.M * (int64_t)sizeof(double);
-  return ((int64_t)items * g.fwd_tiles + items) * (int64_t)sizeof(double);
+  return ((int64_t)items * g.fwd_tiles * (weighted ? 2 : 1) + items) * (int64_t)sizeof(double);
 }
 
-extern "C" int mpgan_ssim_loss_forward(const float* a, const float* b, const int32_t* dhw, int32_t items,
-                                       int32_t channels, double lo, double hi, int32_t grad_mask, void* workspace,
-                                       int64_t workspace_bytes, void* coef, int64_t coef_bytes, int32_t reduction,
-                                       float* loss, void* stream) {
-  MPGAN_CHECK_ARG(a && b && workspace && loss, "ssim_loss_forward: null pointer");
+template <int MODE, typename P>
+static void sl_launch_forward(const SlGeom& g, int32_t items, const P& p, hipStream_t st) {
+  const dim3 grid((unsigned)g.fwd_tiles, (unsigned)items);
+  if (g.vol) {
+    const size_t smem = 2ul * (SL_TZ3 + SL_W - 1) * SL_PLANE * sizeof(float);
+    hipLaunchKernelGGL((sl_forward_kernel<SL_W, SL_TZ3, MODE>), grid, dim3(256), smem, st, p);
+  } else {
+    const size_t smem = 2ul * SL_PLANE * sizeof(float);
+    hipLaunchKernelGGL((sl_forward_kernel<1, 1, MODE>), grid, dim3(256), smem, st, p);
+  }
+}
+
+template <bool WEIGHTED, typename P>
+static void sl_launch_backward(const SlGeom& g, int32_t items, const P& p, hipStream_t st) {
+  const dim3 grid((unsigned)g.bwd_tiles, (unsigned)items);
+  if (g.vol) {
+    const size_t smem = (size_t)(SL_TZ3 + SL_W - 1) * SL_PLANE * sizeof(double);
+    hipLaunchKernelGGL((sl_backward_kernel<SL_W, SL_TZ3, WEIGHTED>), grid, dim3(256), smem, st, p);
+  } else {
+    const size_t smem = (size_t)SL_PLANE * sizeof(double);
+    hipLaunchKernelGGL((sl_backward_kernel<1, 1, WEIGHTED>), grid, dim3(256), smem, st, p);
+  }
+}
+
+// Both forward entry points: every check, then the launches.  wt == null is the plain form.
+static int sl_forward(const char* who, const float* a, const float* b, const int32_t* dhw, int32_t items,
+                      int32_t channels, double lo, double hi, int32_t grad_mask, void* workspace,
+                      int64_t workspace_bytes, void* coef, int64_t coef_bytes, int32_t reduction, float* loss,
+                      void* stream, const SlWeights* wt) {
+  MPGAN_CHECK_ARG(a && b && workspace && loss && (!wt || wt->stats), "%s: null pointer", who);
+  MPGAN_CHECK_ARG(!wt || !(wt->mask && wt->thr), "%s: at most one of mask and thr may be given (got both)", who);
   SlGeom g;
-  if (int rc = sl_geometry("ssim_loss_forward", dhw, items, &g)) return rc;
-  MPGAN_CHECK_ARG(channels >= 1 && items % channels == 0, "ssim_loss_forward: %d items are no multiple of %d channels",
-                  items, channels);
-  MPGAN_CHECK_ARG(hi - lo > 0.0 && (hi - lo) - (hi - lo) == 0.0, "ssim_loss_forward: value range needs finite hi > lo");
-  MPGAN_CHECK_ARG(grad_mask >= 0 && grad_mask <= 3, "ssim_loss_forward: grad_mask %d outside [0, 3]", grad_mask);
-  MPGAN_CHECK_ARG(reduction >= 0 && reduction <= 2, "ssim_loss_forward: unknown reduction %d", reduction);
+  if (int rc = sl_geometry(who, dhw, items, &g)) return rc;
+  MPGAN_CHECK_ARG(channels >= 1 && items % channels == 0, "%s: %d items are no multiple of %d channels", who, items,
+                  channels);
+  MPGAN_CHECK_ARG(hi - lo > 0.0 && (hi - lo) - (hi - lo) == 0.0, "%s: value range needs finite hi > lo", who);
+  MPGAN_CHECK_ARG(grad_mask >= 0 && grad_mask <= 3, "%s: grad_mask %d outside [0, 3]", who, grad_mask);
+  MPGAN_CHECK_ARG(reduction >= 0 && reduction <= 2, "%s: unknown reduction %d", who, reduction);
   int64_t need_coef = 0;
-  const int64_t need_ws = mpgan_ssim_loss_workspace(dhw, items, grad_mask, &need_coef);
-  MPGAN_CHECK_ARG(workspace_bytes >= need_ws, "ssim_loss_forward: workspace too small");
-  MPGAN_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "ssim_loss_forward: workspace must be 8-byte aligned");
-  MPGAN_CHECK_ARG(grad_mask == 0 || (coef && coef_bytes >= need_coef), "ssim_loss_forward: coef missing or too small");
-  MPGAN_CHECK_ARG((reinterpret_cast<uintptr_t>(coef) & 7) == 0, "ssim_loss_forward: coef must be 8-byte aligned");
+  const int64_t need_ws = sl_workspace(who, dhw, items, grad_mask, wt != nullptr, &need_coef);
+  MPGAN_CHECK_ARG(workspace_bytes >= need_ws, "%s: workspace too small", who);
+  MPGAN_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "%s: workspace must be 8-byte aligned", who);
+  MPGAN_CHECK_ARG(grad_mask == 0 || (coef && coef_bytes >= need_coef), "%s: coef missing or too small", who);
+  MPGAN_CHECK_ARG((reinterpret_cast<uintptr_t>(coef) & 7) == 0, "%s: coef must be 8-byte aligned", who);
+  MPGAN_CHECK_ARG(!wt || ((reinterpret_cast<uintptr_t>(wt->stats) & 7) == 0 &&
+                          (reinterpret_cast<uintptr_t>(wt->smap) & 3) == 0),
+                  "%s: stats must be 8-byte and smap 4-byte aligned", who);
   const double L = hi - lo;
-  SlFwd p;
+  SlFwdW p;
   p.a = a; p.b = b; p.D = g.D; p.H = g.H; p.W = g.W;
   p.tiles_x = g.fwd_tx; p.tiles_y = g.fwd_ty; p.tiles = g.fwd_tiles;
   p.lo = lo; p.c1 = (0.01 * L) * (0.01 * L); p.c2 = (0.03 * L) * (0.03 * L);
   p.partials = static_cast<double*>(workspace);
-  double* ssim_item = p.partials + (long)items * g.fwd_tiles;
+  const long slots = (long)items * g.fwd_tiles;
+  double* ssim_item = p.partials + slots * (wt ? 2 : 1);
   double* maps = static_cast<double*>(coef);
   const long per_map = (long)items * g.M;
   p.q = grad_mask ? maps : nullptr;
@@ -288,40 +397,44 @@ extern "C" int mpgan_ssim_loss_forward(const float* a, const float* b, const int
   p.pa = (grad_mask & 1) ? maps + 2 * per_map : nullptr;
   p.pb = (grad_mask & 2) ? maps + (grad_mask == 3 ? 3 : 2) * per_map : nullptr;
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)g.fwd_tiles, (unsigned)items);
-  if (g.vol) {
-    const size_t smem = 2ul * (SL_TZ3 + SL_W - 1) * SL_PLANE * sizeof(float);
-    hipLaunchKernelGGL((sl_forward_kernel<SL_W, SL_TZ3>), grid, dim3(256), smem, st, p);
-  } else {
-    const size_t smem = 2ul * SL_PLANE * sizeof(float);
-    hipLaunchKernelGGL((sl_forward_kernel<1, 1>), grid, dim3(256), smem, st, p);
+  if (!wt) {
+    sl_launch_forward<SL_PLAIN>(g, items, static_cast<const SlFwd&>(p), st);
+    // ssim_item = (sum of the item's tile partials) / M; loss = 1 - ssim over the items
+    launch_loss_tail(p.partials, g.fwd_tiles, 1.0 / (double)g.M, ssim_item, items, channels, reduction, true, loss, st);
+    return check_launch(who);
   }
-  // ssim_item = (sum of the item's tile partials) / M; loss = 1 - ssim over the items
-  launch_loss_tail(p.partials, g.fwd_tiles, 1.0 / (double)g.M, ssim_item, items, channels, reduction, true, loss, st);
-  return check_launch("ssim_loss_forward");
+  p.mask = wt->mask; p.thr = wt->thr; p.smap = wt->smap;
+  p.counts = reinterpret_cast<long long*>(p.partials + slots);
+  if (wt->thr) sl_launch_forward<SL_THR>(g, items, p, st);
+  else sl_launch_forward<SL_MASK>(g, items, p, st);       // a null mask: every window weighs 1
+  // stats[item] = (sum w S / n_item, n_item); loss = 1 - ssim over the items, an empty item adding 0
+  launch_counted_loss_tail(p.partials, p.counts, g.fwd_tiles, ssim_item, wt->stats, items, channels, reduction, loss, st);
+  return check_launch(who);
 }
 
-extern "C" int mpgan_ssim_loss_backward(const float* a, const float* b, const int32_t* dhw, int32_t items,
-                                        int32_t channels, double lo, int32_t grad_mask, const void* coef,
-                                        int64_t coef_bytes, const float* upstream, int32_t upstream_stride,
-                                        double scale, int32_t wrt, float* grad, void* stream) {
-  MPGAN_CHECK_ARG(a && b && coef && upstream && grad, "ssim_loss_backward: null pointer");
+// Both backward entry points; stats == null is the plain form.
+static int sl_backward(const char* who, const float* a, const float* b, const int32_t* dhw, int32_t items,
+                       int32_t channels, double lo, int32_t grad_mask, const void* coef, int64_t coef_bytes,
+                       const double* stats, const float* upstream, int32_t upstream_stride, double scale, int32_t wrt,
+                       float* grad, void* stream) {
+  MPGAN_CHECK_ARG(a && b && coef && upstream && grad, "%s: null pointer", who);
   SlGeom g;
-  if (int rc = sl_geometry("ssim_loss_backward", dhw, items, &g)) return rc;
-  MPGAN_CHECK_ARG(channels >= 1 && items % channels == 0, "ssim_loss_backward: %d items are no multiple of %d channels",
-                  items, channels);
-  MPGAN_CHECK_ARG(wrt == 0 || wrt == 1, "ssim_loss_backward: wrt %d is neither 0 (a) nor 1 (b)", wrt);
+  if (int rc = sl_geometry(who, dhw, items, &g)) return rc;
+  MPGAN_CHECK_ARG(channels >= 1 && items % channels == 0, "%s: %d items are no multiple of %d channels", who, items,
+                  channels);
+  MPGAN_CHECK_ARG(wrt == 0 || wrt == 1, "%s: wrt %d is neither 0 (a) nor 1 (b)", who, wrt);
   MPGAN_CHECK_ARG(grad_mask >= 1 && grad_mask <= 3 && ((grad_mask >> wrt) & 1),
-                  "ssim_loss_backward: the forward's grad_mask %d holds no maps for wrt %d", grad_mask, wrt);
-  MPGAN_CHECK_ARG(upstream_stride == 0 || upstream_stride == 1, "ssim_loss_backward: upstream_stride %d not 0 or 1",
+                  "%s: the forward's grad_mask %d holds no maps for wrt %d", who, grad_mask, wrt);
+  MPGAN_CHECK_ARG(upstream_stride == 0 || upstream_stride == 1, "%s: upstream_stride %d not 0 or 1", who,
                   upstream_stride);
-  MPGAN_CHECK_ARG(lo - lo == 0.0 && scale - scale == 0.0, "ssim_loss_backward: non-finite lo or scale");
+  MPGAN_CHECK_ARG(lo - lo == 0.0 && scale - scale == 0.0, "%s: non-finite lo or scale", who);
   const long per_map = (long)items * g.M;
-  MPGAN_CHECK_ARG(coef_bytes >= (int64_t)sl_maps(grad_mask) * per_map * (int64_t)sizeof(double),
-                  "ssim_loss_backward: coef too small");
-  MPGAN_CHECK_ARG((reinterpret_cast<uintptr_t>(coef) & 7) == 0, "ssim_loss_backward: coef must be 8-byte aligned");
+  MPGAN_CHECK_ARG(coef_bytes >= (int64_t)sl_maps(grad_mask) * per_map * (int64_t)sizeof(double), "%s: coef too small",
+                  who);
+  MPGAN_CHECK_ARG((reinterpret_cast<uintptr_t>(coef) & 7) == 0 && (reinterpret_cast<uintptr_t>(stats) & 7) == 0,
+                  "%s: coef must be 8-byte aligned", who);
   const double* maps = static_cast<const double*>(coef);
-  SlBwd p;
+  SlBwdW p;
   p.x = wrt == 0 ? a : b;
   p.y = wrt == 0 ? b : a;
   p.D = g.D; p.H = g.H; p.W = g.W; p.OD = g.OD; p.OH = g.OH; p.OW = g.OW;
@@ -330,17 +443,62 @@ extern "C" int mpgan_ssim_loss_backward(const float* a, const float* b, const in
   p.r = maps + per_map;
   p.p = maps + (wrt == 1 && grad_mask == 3 ? 3 : 2) * per_map;
   const double np = g.vol ? 343.0 : 49.0;
-  p.lo = lo; p.scale = scale / (np * (double)g.M);
+  p.lo = lo; p.scale = stats ? scale / np : scale / (np * (double)g.M);
   p.upstream = upstream; p.up_stride = upstream_stride; p.channels = channels;
   p.grad = grad;
+  p.stats = stats;
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)g.bwd_tiles, (unsigned)items);
-  if (g.vol) {
-    const size_t smem = (size_t)(SL_TZ3 + SL_W - 1) * SL_PLANE * sizeof(double);
-    hipLaunchKernelGGL((sl_backward_kernel<SL_W, SL_TZ3>), grid, dim3(256), smem, st, p);
-  } else {
-    const size_t smem = (size_t)SL_PLANE * sizeof(double);
-    hipLaunchKernelGGL((sl_backward_kernel<1, 1>), grid, dim3(256), smem, st, p);
-  }
-  return check_launch("ssim_loss_backward");
+  if (stats) sl_launch_backward<true>(g, items, p, st);
+  else sl_launch_backward<false>(g, items, static_cast<const SlBwd&>(p), st);
+  return check_launch(who);
+}
+
+}  // namespace mpgan
+
+using namespace mpgan;
+
+extern "C" int64_t mpgan_ssim_loss_workspace(const int32_t* dhw, int32_t items, int32_t grad_mask,
+                                             int64_t* coef_bytes) {
+  return sl_workspace("ssim_loss_workspace", dhw, items, grad_mask, false, coef_bytes);
+}
+
+extern "C" int mpgan_ssim_loss_forward(const float* a, const float* b, const int32_t* dhw, int32_t items,
+                                       int32_t channels, double lo, double hi, int32_t grad_mask, void* workspace,
+                                       int64_t workspace_bytes, void* coef, int64_t coef_bytes, int32_t reduction,
+                                       float* loss, void* stream) {
+  return sl_forward("ssim_loss_forward", a, b, dhw, items, channels, lo, hi, grad_mask, workspace, workspace_bytes, coef,
+                    coef_bytes, reduction, loss, stream, nullptr);
+}
+
+extern "C" int mpgan_ssim_loss_backward(const float* a, const float* b, const int32_t* dhw, int32_t items,
+                                        int32_t channels, double lo, int32_t grad_mask, const void* coef,
+                                        int64_t coef_bytes, const float* upstream, int32_t upstream_stride,
+                                        double scale, int32_t wrt, float* grad, void* stream) {
+  return sl_backward("ssim_loss_backward", a, b, dhw, items, channels, lo, grad_mask, coef, coef_bytes, nullptr,
+                     upstream, upstream_stride, scale, wrt, grad, stream);
+}
+
+extern "C" int64_t mpgan_masked_ssim_loss_workspace(const int32_t* dhw, int32_t items, int32_t grad_mask,
+                                                    int64_t* coef_bytes) {
+  return sl_workspace("masked_ssim_loss_workspace", dhw, items, grad_mask, true, coef_bytes);
+}
+
+extern "C" int mpgan_masked_ssim_loss_forward(const float* a, const float* b, const int32_t* dhw, int32_t items,
+                                              int32_t channels, double lo, double hi, const uint8_t* mask,
+                                              const float* thr, int32_t grad_mask, void* workspace,
+                                              int64_t workspace_bytes, void* coef, int64_t coef_bytes, double* stats,
+                                              float* smap, int32_t reduction, float* loss, void* stream) {
+  const SlWeights wt = {mask, thr, stats, smap};
+  return sl_forward("masked_ssim_loss_forward", a, b, dhw, items, channels, lo, hi, grad_mask, workspace,
+                    workspace_bytes, coef, coef_bytes, reduction, loss, stream, &wt);
+}
+
+extern "C" int mpgan_masked_ssim_loss_backward(const float* a, const float* b, const int32_t* dhw, int32_t items,
+                                               int32_t channels, double lo, int32_t grad_mask, const void* coef,
+                                               int64_t coef_bytes, const double* stats, const float* upstream,
+                                               int32_t upstream_stride, double scale, int32_t wrt, float* grad,
+                                               void* stream) {
+  MPGAN_CHECK_ARG(stats, "masked_ssim_loss_backward: null pointer");
+  return sl_backward("masked_ssim_loss_backward", a, b, dhw, items, channels, lo, grad_mask, coef, coef_bytes, stats,
+                     upstream, upstream_stride, scale, wrt, grad, stream);
 }

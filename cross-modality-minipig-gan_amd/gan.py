@@ -15,7 +15,7 @@ import torch.nn as nn
 
 from . import ops
 from .augment import DiffAugment, PairAugment, parse_policy
-from .losses import EdgeLoss, ForegroundL1Loss, GlobalMutualInformationLoss, SSIMLoss
+from .losses import EdgeLoss, ForegroundL1Loss, ForegroundSSIMLoss, GlobalMutualInformationLoss, SSIMLoss
 from .preprocess import check_threshold
 from .networks import CasNetGenerator, Discriminator, _EngineModule
 
@@ -399,7 +399,7 @@ class GAN(nn.Module):
                  diff_augment: str = "", diff_augment_fill: float = 0.0, ema_decay: float = 0.0,
                  ema_warmup: bool = True, grad_clip: float = 0.0, log_grad_norm: bool = False,
                  pair_augment: Optional[dict] = None, edge_weight: float = 0.0, edge_eps: float = 1e-6,
-                 fg_weight: float = 0.0, fg_threshold="otsu", **kwargs):
+                 fg_weight: float = 0.0, fg_threshold="otsu", fg_ssim_weight: float = 0.0, **kwargs):
         super().__init__()
         if adv_loss not in ADV_LOSSES:
             raise ValueError(f"adv_loss must be one of {ADV_LOSSES}, got {adv_loss!r}")
@@ -411,6 +411,8 @@ class GAN(nn.Module):
             raise ValueError(f"edge_weight must be >= 0, got {edge_weight!r}")
         if not fg_weight >= 0:
             raise ValueError(f"fg_weight must be >= 0, got {fg_weight!r}")
+        if not fg_ssim_weight >= 0:
+            raise ValueError(f"fg_ssim_weight must be >= 0, got {fg_ssim_weight!r}")
         if isinstance(fg_threshold, torch.Tensor):
             raise ValueError('fg_threshold must be "otsu" or a finite number, got a tensor')
         check_threshold(fg_threshold, "GAN: fg_threshold")
@@ -476,11 +478,15 @@ class GAN(nn.Module):
         # the device, no host sync): the anatomy weighted above the air around it
         self.fg_weight = float(fg_weight)
         self.fg_loss = ForegroundL1Loss(fg_threshold) if self.fg_weight > 0 else None
+        # and fg_ssim_weight * (1 - SSIM(G(t1w), t2w)) over the windows whose centre lies in that foreground (DESIGN.md
+        # 7l): the whole-image SSIM is mostly air, whose flat windows score 1 and give the generator no signal
+        self.fg_ssim_weight = float(fg_ssim_weight)
+        self.fg_ssim_loss = ForegroundSSIMLoss(fg_threshold) if self.fg_ssim_weight > 0 else None
         # the active terms as (log name, weight, module), in the order _add_generator_terms adds them to g_loss
         self._generator_terms = [(name, weight, module) for name, weight, module in (
             ("g_mi_loss", self.mi_weight, self.mi_loss), ("g_ssim_loss", self.ssim_weight, self.ssim_loss),
-            ("g_edge_loss", self.edge_weight, self.edge_loss), ("g_fg_loss", self.fg_weight, self.fg_loss))
-            if module is not None]
+            ("g_edge_loss", self.edge_weight, self.edge_loss), ("g_fg_loss", self.fg_weight, self.fg_loss),
+            ("g_fg_ssim_loss", self.fg_ssim_weight, self.fg_ssim_loss)) if module is not None]
         # opt-in differentiable augmentation of everything D sees in training_step (augment.py); with the
         # default "" there is no module and no launch.  aug_generator: a torch.Generator on the images' device, or None
         # for torch's global one (data-parallel runs: every rank seeds its own, or all ranks draw the same parameters)
@@ -586,8 +592,8 @@ class GAN(nn.Module):
         and discriminator in eval mode (running-statistics BatchNorm) under no_grad -- no parameter, buffer, gradient or
         optimizer state is touched.  Logs and returns val_g_adv_loss, val_g_recon_loss, val_g_loss, val_d_loss as
         device scalars (no host sync); with mi_weight > 0 also val_g_mi_loss, with ssim_weight > 0 also
-        val_g_ssim_loss, with edge_weight > 0 also val_g_edge_loss and with fg_weight > 0 also val_g_fg_loss, which
-        val_g_loss then includes; with
+        val_g_ssim_loss, with edge_weight > 0 also val_g_edge_loss, with fg_weight > 0 also val_g_fg_loss and with
+        fg_ssim_weight > 0 also val_g_fg_ssim_loss, which val_g_loss then includes; with
         ema_decay > 0 also val_ema_g_recon_loss, the L1 of generator_ema(t1w) against t2w."""
         t1w_images, t2w_images = batch["t1w"], batch["t2w"]
         with torch.no_grad(), eval_modes(self.generator, self.discriminator):

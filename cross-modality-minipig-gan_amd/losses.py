@@ -9,7 +9,9 @@ against a float64 torch restatement (tests/mi_loss_ref.py).  Forward and backwar
 SSIMLoss is 1 - the structural similarity that metrics.ssim scores a volume with (code/GAN/psnr_ssim_metric.py:88-106),
 as a loss: the forward kernel of csrc/ssim_loss.hip also leaves the per-window coefficient maps of the closed-form
 gradient, the backward kernel box-sums them.  Its definition is pinned in include/mpgan_hip.h against the float64
-torch restatement tests/ssim_loss_ref.py.
+torch restatement tests/ssim_loss_ref.py.  With a mask or a threshold (ForegroundSSIMLoss) the same two kernels weight
+every window by the foreground at its centre voxel and normalise per image on the device (pinned against
+tests/masked_ssim_ref.py).
 
 EdgeLoss is the edge-aware generator term of Ea-GAN (Yu et al. 2019): the L1 distance of the 3-D Sobel edge-magnitude
 maps of the two volumes, over a replicate border.  csrc/edge_loss.hip holds the fused stencils (the forward writes no
@@ -203,28 +205,125 @@ class _SSIMLossFn(torch.autograd.Function):
             a, b, spatial, items, channels, lo, mask, coef, g, scale, wrt, out)) + (None,) * 3
 
 
-def ssim_loss(pred: torch.Tensor, target: torch.Tensor, value_range=(0.0, 1.0), reduction: str = "mean") -> torch.Tensor:
+class _MaskedSSIMLossFn(torch.autograd.Function):
+    """_SSIMLossFn with a weight per window: one of mask (uint8, the inputs' shape) and thr (fp32, one per item), or
+    neither.  Saves the inputs, the weighted maps and stats = (ssim_item, n_item) per item; the backward reads every
+    item's divisor from stats on the device, so nothing syncs and a second backward gives the same bits."""
+
+    @staticmethod
+    def forward(ctx, pred, target, mask, thr, lo, hi, reduction):
+        a, b, (batch, channels, spatial), loss, scale = _pair_forward(pred, target, reduction)
+        items, dev = batch * channels, a.device
+        grads = int(ctx.needs_input_grad[0]) | (int(ctx.needs_input_grad[1]) << 1)
+        ws_bytes, coef_bytes = ops.masked_ssim_loss_workspace(spatial, items, grads)
+        ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+        coef = torch.empty(coef_bytes // 8, dtype=torch.float64, device=dev) if grads else None
+        stats = torch.empty((items, 2), dtype=torch.float64, device=dev)
+        ops.masked_ssim_loss_forward(a, b, spatial, items, channels, lo, hi, mask, thr, grads, ws, coef, stats, None,
+                                     reduction, loss)
+        ctx.cfg = (spatial, items, channels, lo, grads, -scale)
+        ctx.save_for_backward(a, b, coef, stats)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        a, b, coef, stats = ctx.saved_tensors
+        spatial, items, channels, lo, grads, scale = ctx.cfg
+        return _pair_backward(ctx, gout, lambda g, wrt, out: ops.masked_ssim_loss_backward(
+            a, b, spatial, items, channels, lo, grads, coef, stats, g, scale, wrt, out)) + (None,) * 5
+
+
+def _check_mask_type(mask, who):
+    if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"{who}: mask must be a bool / uint8 tensor")
+
+
+def _check_mask_place(mask, pred, who):
+    shape = tuple(pred.shape)
+    if mask.device != pred.device or tuple(mask.shape) not in (shape, shape[:1] + (1,) + shape[2:]):
+        raise ValueError(f"{who}: mask must lie on the inputs' device with their shape {shape} or channel extent 1, "
+                         f"got {tuple(mask.shape)} on {mask.device}")
+
+
+def _mask_bytes(mask, pred, who):
+    """The mask as contiguous uint8 in pred's shape; a channel extent of 1 is broadcast over the channels."""
+    _check_mask_place(mask, pred, who)
+    mask = mask.expand(pred.shape).contiguous()
+    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+
+
+def ssim_loss(pred: torch.Tensor, target: torch.Tensor, value_range=(0.0, 1.0), reduction: str = "mean", *,
+              mask: torch.Tensor = None, threshold=None, bins: int = 256) -> torch.Tensor:
     """1 - SSIM of two (B, C, H, W) or (B, C, D, H, W) fp32 device tensors: every (b, c) image is one item, scored as
     metrics.ssim scores it (7-wide uniform window on every spatial axis, K1 = 0.01, K2 = 0.03, sample covariance,
     mean over the windows inside the image) with data range hi - lo of value_range = (lo, hi); lo is subtracted from
     both tensors, nothing is clamped.  reduction: "mean" (a scalar over the B * C items), "sum", or "none" ((B,), each
-    entry the mean over its channels).  Differentiable in both arguments; bitwise reproducible."""
+    entry the mean over its channels).  Differentiable in both arguments; bitwise reproducible.
+
+    With at most one of mask and threshold the mean runs over the foreground windows alone: a window
+    counts when its centre voxel is foreground, which is the map of S cropped by its 3-sample border and averaged
+    over the mask.
+      mask       a bool / uint8 device tensor of pred's shape, or with channel extent 1 (broadcast over the channels);
+      threshold  "otsu", a number, or an fp32 device tensor with one value per (b, c) image: the foreground is
+                 target > threshold, read on the fly -- no mask tensor exists and nothing syncs.  "otsu" takes
+                 preprocess.otsu_threshold(target, bins, value_range).
+    An image without a foreground window adds a loss of 0 and an exactly-zero gradient; nothing flows into the mask or
+    the threshold.  Defined in include/mpgan_hip.h ("masked SSIM"), pinned against tests/masked_ssim_ref.py."""
     who = "ssim_loss"
     lo, hi = _ssim_config(value_range, reduction, who)
+    if mask is None and threshold is None:
+        _pair_inputs(pred, target, who, _ssim_shape_error)
+        return _SSIMLossFn.apply(pred, target, lo, hi, reduction)
+    if mask is not None and threshold is not None:
+        raise ValueError(f"{who}: give at most one of mask and threshold")
+    if mask is None:
+        check_threshold(threshold, who)
+    else:
+        _check_mask_type(mask, who)
+        if pred.shape == target.shape:                    # a mismatch of the pair itself is _pair_inputs' complaint
+            _check_mask_place(mask, pred, who)
     _pair_inputs(pred, target, who, _ssim_shape_error)
-    return _SSIMLossFn.apply(pred, target, lo, hi, reduction)
+    thr = None
+    if mask is None:
+        thr = item_thresholds(target.contiguous(), threshold, bins, value_range, who)
+    else:
+        mask = _mask_bytes(mask, pred, who)
+    return _MaskedSSIMLossFn.apply(pred, target, mask, thr, lo, hi, reduction)
 
 
 class SSIMLoss(nn.Module):
-    """ssim_loss as a module: SSIMLoss(value_range=(-1.0, 1.0)) suits a tanh output."""
+    """ssim_loss as a module: SSIMLoss(value_range=(-1.0, 1.0)) suits a tanh output.  forward(pred, target, mask=None):
+    without a mask the module's threshold is used, and without either the whole image is scored."""
 
-    def __init__(self, value_range=(0.0, 1.0), reduction: str = "mean"):
+    def __init__(self, value_range=(0.0, 1.0), reduction: str = "mean", threshold=None, bins: int = 256):
         super().__init__()
         _ssim_config(value_range, reduction, "SSIMLoss")
-        self.value_range, self.reduction = tuple(value_range), reduction
+        if threshold is not None:
+            check_threshold(threshold, "SSIMLoss")
+            _otsu_config(bins, value_range, "SSIMLoss")
+        self.value_range, self.reduction, self.threshold, self.bins = tuple(value_range), reduction, threshold, bins
+
+    def forward(self, pred: torch.Tensor, target: torch.Tensor, mask: torch.Tensor = None) -> torch.Tensor:
+        return ssim_loss(pred, target, self.value_range, self.reduction, mask=mask,
+                         threshold=None if mask is not None else self.threshold, bins=self.bins)
+
+
+class ForegroundSSIMLoss(nn.Module):
+    """(pred, target) -> 1 - the SSIM over the windows whose centre lies in the foreground of target,
+    target > threshold ("otsu": Otsu's threshold of every target image over value_range, on the device; or a number):
+    the generator term GAN's fg_ssim_weight switches on.  The air around the anatomy, whose flat windows score S = 1,
+    carries no weight."""
+
+    def __init__(self, threshold="otsu", value_range=(-1.0, 1.0), bins: int = 256):
+        super().__init__()
+        check_threshold(threshold, "ForegroundSSIMLoss")
+        if isinstance(threshold, torch.Tensor):
+            raise ValueError("ForegroundSSIMLoss: threshold must be \"otsu\" or a finite number")
+        _otsu_config(bins, value_range, "ForegroundSSIMLoss")
+        self.threshold, self.value_range, self.bins = threshold, tuple(value_range), int(bins)
 
     def forward(self, pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
-        return ssim_loss(pred, target, self.value_range, self.reduction)
+        return ssim_loss(pred, target, self.value_range, threshold=self.threshold, bins=self.bins)
 
 
 def _edge_config(eps, reduction, who):

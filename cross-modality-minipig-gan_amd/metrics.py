@@ -68,21 +68,65 @@ def score_volume(generated: torch.Tensor, ground_truth: torch.Tensor,
     (MAE / MSE / PSNR; plus SSIM when the tensors are (H, W) or (D, H, W)).  mutual_information=True
     adds "mi" and "nmi" of the two rescaled volumes (256 bins over [0, 256], nats).  mask (a same-shape bool / uint8
     device tensor, e.g. preprocess.foreground_mask(ground_truth)) restricts MAE / MSE / PSNR to its voxels and adds
-    "count"; the rescaling, "ssim", "mi" and "nmi" stay whole-volume figures."""
+    "count", and wherever "ssim" is returned also "ssim_masked": the SSIM over the windows whose centre voxel is in
+    the mask (ssim(mask=), float64; NaN without such a window).  The rescaling, "ssim" itself, "mi" and "nmi" stay
+    whole-volume figures."""
     g, t = rescale_0_255(generated), rescale_0_255(ground_truth)
     out = image_errors(g, t, 256.0, mask)
     if g.dim() in (2, 3) and min(g.shape[-2:]) >= 7 and (g.dim() == 2 or g.shape[0] >= 7):
         out["ssim"] = ssim(g, t, 256.0)
+        if mask is not None:
+            out["ssim_masked"] = ssim(g, t, 256.0, mask)
     if mutual_information:
         m = _mutual_information(g, t, bins=256, value_range=(0.0, 256.0))
         out["mi"], out["nmi"] = m["mi"], m["nmi"]
     return out
 
 
-def ssim(a: torch.Tensor, b: torch.Tensor, data_range: float = 256.0) -> torch.Tensor:
+def _weighted_ssim(who, a, b, data_range, mask, want_map):
+    """(stats, smap) of one image through the masked SSIM forward (include/mpgan_hip.h, lo = 0): stats =
+    (ssim_item, n_item) in float64, smap the fp32 map of S over the window corners when want_map."""
+    if a.shape != b.shape or a.dim() not in (2, 3):
+        raise ValueError(f"{who}: expects two same-shape (H, W) or (D, H, W) tensors")
+    if not (a.is_cuda and b.is_cuda):
+        raise ValueError(f"{who}: expects two device tensors")
+    if not float(data_range) > 0:
+        raise ValueError(f"{who}: data_range must be positive, got {data_range!r}")
+    if mask is not None:
+        if (not isinstance(mask, torch.Tensor) or mask.shape != a.shape or mask.dtype not in (torch.bool, torch.uint8)
+                or mask.device != a.device):
+            raise ValueError(f"{who}: mask must be a same-shape bool / uint8 tensor on the inputs' device")
+        mask = mask.contiguous()
+        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    a, b = a.contiguous().float(), b.contiguous().float()
+    spatial, dev = tuple(a.shape), a.device
+    ws_bytes, _ = ops.masked_ssim_loss_workspace(spatial, 1, 0)
+    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+    stats = torch.empty((1, 2), dtype=torch.float64, device=dev)
+    corners = tuple(1 if len(spatial) == 3 and i == 0 and s == 1 else s - 6 for i, s in enumerate(spatial))
+    smap = torch.empty(corners, device=dev) if want_map else None          # a depth of 1 is a slice: not windowed
+    ops.masked_ssim_loss_forward(a, b, spatial, 1, 1, 0.0, float(data_range), mask, None, 0, ws, None, stats, smap,
+                                 "mean", torch.empty((), device=dev))
+    return stats, smap
+
+
+def ssim_map(a: torch.Tensor, b: torch.Tensor, data_range: float = 256.0) -> torch.Tensor:
+    """The per-window SSIM S of two (H, W) slices or (D, H, W) volumes, as ssim() defines it: an fp32 device tensor of
+    shape (H - 6, W - 6) or (D - 6, H - 6, W - 6), entry k the window whose corner is k and whose centre is k + 3
+    (skimage's full=True map cropped by its 3-sample border).  Its mean is ssim(a, b); its mean over mask[3:-3, ...]
+    is ssim(a, b, mask=mask).  One pass of the SSIM loss's forward kernel."""
+    return _weighted_ssim("ssim_map", a, b, data_range, None, True)[1]
+
+
+def ssim(a: torch.Tensor, b: torch.Tensor, data_range: float = 256.0, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """structural_similarity(a, b, data_range=256) of two (H, W) slices or (D, H, W) volumes
     (code/GAN/psnr_ssim_metric.py:91-92): 7-wide uniform window, K1 = 0.01, K2 = 0.03, sample
-    covariance, mean over the interior.  Returns a device scalar."""
+    covariance, mean over the interior.  Returns a device scalar.  With mask (a same-shape bool / uint8 device tensor,
+    e.g. preprocess.foreground_mask's output) the mean runs over the windows whose centre voxel is in the mask --
+    the interior of the map averaged over the mask -- and comes back as a float64 device scalar; a mask without such
+    a window gives NaN."""
+    if mask is not None:
+        return _weighted_ssim("ssim", a, b, data_range, mask, False)[0][0, 0]
     if a.shape != b.shape or a.dim() not in (2, 3):
         raise ValueError("ssim: expects two same-shape (H, W) or (D, H, W) tensors")
     a, b = a.contiguous().float(), b.contiguous().float()

@@ -1032,6 +1032,38 @@ def ssim_loss_backward(a, b, spatial, items, channels, lo, grad_mask, coef, upst
     return grad
 
 
+def masked_ssim_loss_workspace(spatial, items: int, grad_mask: int):
+    """(workspace bytes, coefficient-buffer bytes) of the weighted form: one more int64 per tile for the counts."""
+    coef = C.c_int64(0)
+    need = int(lib().mpgan_masked_ssim_loss_workspace(_dhw(spatial), int(items), int(grad_mask), C.byref(coef)))
+    if need < 0:
+        raise ValueError(f"masked_ssim_loss_workspace: bad geometry ({items} items of extent {tuple(spatial)}): extents "
+                         "below the 7-wide window, or a depth that is neither 1 nor >= 7")
+    return need, int(coef.value)
+
+
+def masked_ssim_loss_forward(a, b, spatial, items, channels, lo, hi, mask, thr, grad_mask, workspace, coef, stats, smap,
+                             reduction, loss):
+    """loss and stats[items][2] = (ssim_item, n_item) (float64) of the SSIM weighted by at most one of mask (uint8) and
+    thr (fp32 per item); smap (nullable, fp32 [items][M]) receives S of every valid window."""
+    check(lib().mpgan_masked_ssim_loss_forward(a.data_ptr(), b.data_ptr(), _dhw(spatial), int(items), int(channels),
+                                               float(lo), float(hi), _ptr(mask), _ptr(thr), int(grad_mask),
+                                               workspace.data_ptr(), _nbytes(workspace), _ptr(coef), _nbytes(coef),
+                                               stats.data_ptr(), _ptr(smap), _REDUCTIONS[reduction], loss.data_ptr(),
+                                               _stream()), "masked_ssim_loss_forward")
+    return loss
+
+
+def masked_ssim_loss_backward(a, b, spatial, items, channels, lo, grad_mask, coef, stats, upstream, scale, wrt, grad):
+    """grad = upstream[batch entry or 0] * scale * d ssim_item / d (a if wrt == 0 else b); 0 for an empty item."""
+    check(lib().mpgan_masked_ssim_loss_backward(a.data_ptr(), b.data_ptr(), _dhw(spatial), int(items), int(channels),
+                                                float(lo), int(grad_mask), coef.data_ptr(), _nbytes(coef),
+                                                stats.data_ptr(), upstream.data_ptr(), _up_stride(upstream),
+                                                float(scale), int(wrt), grad.data_ptr(), _stream()),
+          "masked_ssim_loss_backward")
+    return grad
+
+
 # ---- Sobel edge loss (csrc/edge_loss.hip; losses.py holds the autograd nodes) ----
 def sobel_magnitude_forward(x, spatial, items, eps, out):
     """out = m(x), the Sobel edge magnitude of `items` contiguous fp32 images (see include/mpgan_hip.h)."""

@@ -549,6 +549,43 @@ int mpgan_ssim_loss_backward(const float* a, const float* b, const int32_t* dhw,
                              const float* upstream, int32_t upstream_stride, double scale, int32_t wrt, float* grad,
                              void* stream);
 
+/* ---- masked SSIM: the SSIM loss over a foreground, and the per-window map (ssim_loss.hip) ----
+ * Everything is as in the "SSIM loss" block above: items, dhw, the 7-wide uniform window, n, cn, C1, C2, S, Q, R, P, lo
+ * and hi.  One thing is added: every valid window k carries a weight w_k in {0, 1}, read at the window's CENTRE voxel:
+ * corner + 3 on every windowed axis (for D == 1 the z index is unchanged).  That is "take the map of S, crop the
+ * 3-sample border as skimage does, average it over the mask".  The weight has AT MOST ONE source:
+ *   mask  uint8[items][D][H][W],  w_k = (mask[centre_k] != 0): any non-zero byte counts; or
+ *   thr   device float[items],    w_k = (b[centre_k] > thr[item]) by mpgan_foreground_mask's rule: strict, in fp32, 0
+ *                                 for a NaN on either side -- no mask array exists; or
+ *   neither: w_k = 1.
+ * Per item:
+ *   n_item    = sum_k w_k, an exact count (mask voxels in the 3-wide border that the interior drops do not count)
+ *   ssim_item = (sum_k w_k S_k) / n_item, and NaN where n_item == 0
+ *   loss_item = 1 - ssim_item, and 0 where n_item == 0 (mpgan_masked_l1's convention for an empty item)
+ *   reductions 0 / 1 / 2 as for the SSIM loss.
+ *   d ssim_item / d a_p = (1 / (n n_item)) (sum w_k P_k + a_p sum w_k Q_k + b_p sum w_k R_k) over the valid windows that
+ *   contain p; for b with the roles swapped; exactly 0 for an empty item.  Nothing flows into the mask or the threshold.
+ * A block's sum of w S is fp64 in the SSIM loss's order, its count of w an integer; stats (device double[items][2])
+ * receives (ssim_item, n_item), the item's partials added in slot order by the fixed tree of the other loss tails: no
+ * atomics, bitwise reproducible.  The stored maps are w Q, w R, w P -- exact, zero or the value.  smap (nullable,
+ * float[items][M] over the window corners, 4-byte aligned) receives S of EVERY valid window, whatever its weight,
+ * rounded to fp32.  workspace >= mpgan_masked_ssim_loss_workspace(...) bytes and stats are 8-byte aligned; coef as for
+ * the SSIM loss.  The backward reads its per-item factor scale / (n n_item) from stats on the device: nothing syncs.
+ * MPGAN_ERR_INVALID before any launch: both mask sources, a null a / b / workspace / stats / loss (backward: a / b /
+ * coef / stats / upstream / grad), a geometry, grad_mask or reduction the SSIM loss refuses, a workspace that is too
+ * small or misaligned.  The calls allocate nothing, are asynchronous on `stream` and can be captured into a graph. */
+int64_t mpgan_masked_ssim_loss_workspace(const int32_t* dhw, int32_t items, int32_t grad_mask, int64_t* coef_bytes);
+int mpgan_masked_ssim_loss_forward(const float* a, const float* b, const int32_t* dhw, int32_t items, int32_t channels,
+                                   double lo, double hi, const uint8_t* mask /* nullable */,
+                                   const float* thr /* nullable */, int32_t grad_mask, void* workspace,
+                                   int64_t workspace_bytes, void* coef, int64_t coef_bytes, double* stats,
+                                   float* smap /* nullable */, int32_t reduction, float* loss, void* stream);
+/* As mpgan_ssim_loss_backward, with the forward's stats; scale is the host factor of the reduction alone. */
+int mpgan_masked_ssim_loss_backward(const float* a, const float* b, const int32_t* dhw, int32_t items,
+                                    int32_t channels, double lo, int32_t grad_mask, const void* coef,
+                                    int64_t coef_bytes, const double* stats, const float* upstream,
+                                    int32_t upstream_stride, double scale, int32_t wrt, float* grad, void* stream);
+
 /* ---- Sobel edge loss: the L1 distance of two 3-D Sobel edge-magnitude maps (the generator term of Ea-GAN, Yu et al.
  * 2019; the definition below is what is pinned; Ea-GAN's own filters are this operator times 8 in 2-D, times 32 in 3-D) ----
  * x, a, b: contiguous fp32 arrays of `items` images of dhw = (D, H, W) samples each; an item is one (batch, channel)
