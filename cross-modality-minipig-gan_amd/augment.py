@@ -1,11 +1,14 @@
 """Differentiable augmentation in front of the discriminator (Zhao et al. 2020, "Differentiable Augmentation for
 Data-Efficient GAN Training"): the same random transformation T on everything D sees, differentiable so that
 the generator's gradient flows back through it.  One channel: brightness and contrast ("color"; the paper's saturation
-does not exist), an integer translation and a cut-out box, applied in that order by csrc/diffaug.hip.
+does not exist), an integer translation and a cut-out box, applied in that order by csrc/diffaug.hip.  The policy word
+"affine" (Karras et al. 2020 found rotation and isotropic scaling the most effective augmentations for
+small data sets) puts a random rotation, scale, shift and flip in front of those: diff_affine_warp, the trilinear warp
+of csrc/pair_augment.hip with its exact adjoint as the backward.
 
-    params = sample_params(x.shape[0], x.shape[2:], "color,translation,cutout", device=x.device)
-    y = diff_augment(x, params)                     # (B, 1, *S) fp32 on the GPU; dL/dx through the backward kernel
-    c = diff_augment(cond, params, color=False)     # the spatial ops alone, the same shift and box
+    params = sample_params(x.shape[0], x.shape[2:], "color,affine,translation,cutout", device=x.device)
+    y = diff_augment(x, params)                     # (B, 1, *S) fp32 on the GPU; dL/dx through the backward kernels
+    c = diff_augment(cond, params, color=False)     # the spatial ops alone, the same map, shift and box
 """
 from __future__ import annotations
 
@@ -18,19 +21,24 @@ from . import ops
 
 BRIGHTNESS, CONTRAST, TRANSLATION, CUTOUT = (ops.DIFFAUG_BRIGHTNESS, ops.DIFFAUG_CONTRAST, ops.DIFFAUG_TRANSLATION,
                                              ops.DIFFAUG_CUTOUT)
-POLICY_BITS = {"color": BRIGHTNESS | CONTRAST, "translation": TRANSLATION, "cutout": CUTOUT}
+AFFINE = 16                                           # this module's own bit: diff_augment warps, then strips it
+POLICY_BITS = {"color": BRIGHTNESS | CONTRAST, "translation": TRANSLATION, "cutout": CUTOUT, "affine": AFFINE}
+AFFINE_KEYS = ("rotate", "scale", "shift", "flip", "prob")       # the sample_affine_params keywords "affine" may set
+DEFAULT_AFFINE = dict(rotate=0.26, scale=0.1)         # +-15 degrees about every axis, +-10 % isotropic zoom
 
 
 class DiffAugParams(NamedTuple):
     """One draw: color (B, 2) float32 = [b, c]; geom (B, 9) int32 = [t_d, t_h, t_w, lo_d, lo_h, lo_w, size_d, size_h,
-    size_w] (2-D: the D entries are 0, 0, 1); ops = the bit mask of what the policy enables."""
+    size_w] (2-D: the D entries are 0, 0, 1); ops = the bit mask of what the policy enables; theta (B, 12) float64, the
+    (A | t) of AffineParams, with the policy word "affine" and None without it."""
     color: torch.Tensor
     geom: torch.Tensor
     ops: int
+    theta: Optional[torch.Tensor] = None
 
 
 def parse_policy(policy: str) -> int:
-    """The ops bit mask of a comma-separated subset of "color", "translation", "cutout" ("" = 0)."""
+    """The ops bit mask of a comma-separated subset of "color", "affine", "translation", "cutout" ("" = 0)."""
     mask = 0
     for word in (w.strip() for w in str(policy).split(",")):
         if not word:
@@ -39,6 +47,31 @@ def parse_policy(policy: str) -> int:
             raise ValueError(f"diff_augment policy: unknown word {word!r} (a comma-separated subset of {sorted(POLICY_BITS)})")
         mask |= POLICY_BITS[word]
     return mask
+
+
+def affine_options(policy: str, affine: Optional[dict] = None) -> Optional[dict]:
+    """The sample_affine_params keywords behind the policy word "affine": None without the word (options given all the
+    same are a ValueError), DEFAULT_AFFINE when `affine` is None, else a copy of `affine`, whose keys must come from
+    AFFINE_KEYS and whose values some image must be able to take."""
+    if not parse_policy(policy) & AFFINE:
+        if affine is not None:
+            raise ValueError(f"diff_augment policy: affine options {affine!r} without the word 'affine' in {str(policy)!r}")
+        return None
+    if affine is None:
+        return dict(DEFAULT_AFFINE)
+    unknown = sorted(set(affine) - set(AFFINE_KEYS)) if isinstance(affine, dict) else None
+    if unknown is None or unknown:
+        raise ValueError(f"diff_augment policy: the affine options are a dict of the keywords {AFFINE_KEYS}, got {affine!r}")
+    o = dict(affine)
+    for ndim in (2, 3):
+        try:
+            _check_affine_options(o.get("rotate", 0.0), o.get("scale", 0.0), o.get("shift", 0.0), o.get("flip", ()),
+                                  o.get("prob", 1.0), 0.0, 1.0, (), ndim)
+            break
+        except ValueError:
+            if ndim == 3:
+                raise
+    return o
 
 
 def translation_range(size: int) -> int:
@@ -50,16 +83,20 @@ def cutout_size(size: int) -> int:
 
 
 def sample_params(n: int, spatial: Sequence[int], policy: str, generator: Optional[torch.Generator] = None,
-                  device="cpu") -> DiffAugParams:
+                  device="cpu", affine: Optional[dict] = None) -> DiffAugParams:
     """Draw the parameters of `n` samples of extent `spatial` ((H, W) or (D, H, W)) with the paper's formulas, in pure torch
     ops on `device` (no host sync): b = U[0,1) - 0.5, c = U[0,1) + 0.5; t_k = randint(-r_k, r_k + 1) with
     r_k = int(S_k/8 + 0.5); size_k = int(S_k/2 + 0.5), lo_k = randint(0, S_k + (1 - size_k % 2)) - size_k // 2.
     Draw order: one rand(n, 2) for color, then the translation's axes in order, then the cutout's axes in order; a
-    disabled op draws nothing and leaves its neutral entries (b = 0, c = 1, t = 0, lo = 0, size = 0; in 2-D size_d is 1 all the same)."""
+    disabled op draws nothing and leaves its neutral entries (b = 0, c = 1, t = 0, lo = 0, size = 0; in 2-D size_d is 1 all the same).
+    With the word "affine" theta = sample_affine_params(n, spatial, **affine).theta is drawn last, after the cutout (a
+    replay of the other words from the same seed is unchanged); `affine`: keywords from AFFINE_KEYS, by default
+    DEFAULT_AFFINE; given without the word it is a ValueError."""
     spatial = tuple(int(s) for s in spatial)
     if len(spatial) not in (2, 3) or min(spatial) < 1:
         raise ValueError(f"sample_params: spatial must be (H, W) or (D, H, W) with extents >= 1, got {spatial}")
     mask = parse_policy(policy)
+    affine = affine_options(policy, affine)
     device = torch.device(device)
     kw = dict(generator=generator, device=device)
     if mask & (BRIGHTNESS | CONTRAST):                 # (scalar updates of the columns: nothing is copied from the host)
@@ -83,7 +120,10 @@ def sample_params(n: int, spatial: Sequence[int], policy: str, generator: Option
             size = cutout_size(s)
             cols[3 + k] = torch.randint(0, s + (1 - size % 2), (n,), **kw) - size // 2
             cols[6 + k] = zero + size
-    return DiffAugParams(color.contiguous(), torch.stack(cols, 1).to(torch.int32).contiguous(), mask)
+    theta = None
+    if affine is not None:
+        theta = sample_affine_params(n, spatial, generator=generator, device=device, **affine).theta
+    return DiffAugParams(color.contiguous(), torch.stack(cols, 1).to(torch.int32).contiguous(), mask, theta)
 
 
 class _DiffAugFn(torch.autograd.Function):
@@ -117,8 +157,17 @@ def _workspace(x, n, spatial, mask):
 
 def diff_augment(x: torch.Tensor, params: DiffAugParams, *, color: bool = True, fill: float = 0.0) -> torch.Tensor:
     """T(x) for a (B, 1, *S) fp32 GPU tensor under one draw of sample_params; differentiable in x.  color=False applies
-    the spatial ops alone (what the condition of a conditional discriminator gets, under its image's parameters)."""
+    the spatial ops alone (what the condition of a conditional discriminator gets, under its image's parameters).
+    With the AFFINE bit x is first warped under params.theta (diff_affine_warp with `fill`), then the other ops run on
+    the result; without other ops the warp's output is returned."""
     mask = int(params.ops) if color else int(params.ops) & ~(BRIGHTNESS | CONTRAST)
+    if mask & AFFINE:
+        if params.theta is None:
+            raise ValueError("diff_augment: the AFFINE bit needs params.theta (sample_params with the word 'affine')")
+        x = diff_affine_warp(x, params.theta, fill=fill)
+        mask &= ~AFFINE
+        if not mask:
+            return x
     return _DiffAugFn.apply(x, params.color, params.geom, mask, float(fill))
 
 
@@ -126,21 +175,24 @@ class DiffAugment(nn.Module):
     """Draws fresh parameters on every call (`generator`: a torch.Generator on the input's device, or None for torch's
     global one; every rank of a data-parallel run seeds its own) and applies them: forward(x) -> T(x);
     forward(x, cond) -> (T(x), T_spatial(cond)) with the same parameters.  `.last_params` is the last draw.  The module
-    has no parameters and no buffers."""
+    has no parameters and no buffers.  `affine`: the options of the policy word "affine" (affine_options)."""
 
-    def __init__(self, policy: str, fill: float = 0.0, generator: Optional[torch.Generator] = None):
+    def __init__(self, policy: str, fill: float = 0.0, generator: Optional[torch.Generator] = None,
+                 affine: Optional[dict] = None):
         super().__init__()
         self.ops = parse_policy(policy)
+        self.affine = affine_options(policy, affine)
         self.policy = str(policy)
         self.fill = float(fill)
         self.generator = generator
         self.last_params: Optional[DiffAugParams] = None
 
     def extra_repr(self):
-        return f"policy={self.policy!r}, fill={self.fill}"
+        return f"policy={self.policy!r}, fill={self.fill}" + (f", affine={self.affine!r}" if self.affine is not None else "")
 
     def forward(self, x, cond=None):
-        params = sample_params(x.shape[0], tuple(x.shape[2:]), self.policy, generator=self.generator, device=x.device)
+        params = sample_params(x.shape[0], tuple(x.shape[2:]), self.policy, generator=self.generator, device=x.device,
+                               affine=self.affine)
         self.last_params = params
         y = diff_augment(x, params, fill=self.fill)
         if cond is None:
@@ -324,6 +376,61 @@ def _warp_arguments(what, x, x1, out_size, mode, fill, noise):
         raise ValueError(f"{what}: out_size {out_size} for a {x.dim() - 2}-D image")
     outs = [torch.empty((x.shape[0], 1, *out_size), dtype=torch.float32, device=x.device) for _ in planes]
     return planes, fills, noises, outs
+
+
+# ---- the differentiable warp: what the policy word "affine" applies; affine_warp above is untouched ----------
+class _AffineWarpFn(torch.autograd.Function):
+    """(y, y1) = the CONSTANT warp of (x, x1) in one launch; the map is linear in the images with weights that depend on
+    theta alone, so only theta is saved.  The backward launches ops.affine_warp_backward once per plane that needs a
+    gradient; theta gets none."""
+
+    @staticmethod
+    def forward(ctx, theta, out_size, fills, x, x1):
+        planes = [t.contiguous() for t in ((x,) if x1 is None else (x, x1))]
+        outs = [torch.empty((x.shape[0], 1, *out_size), dtype=torch.float32, device=x.device) for _ in planes]
+        ops.affine_warp(planes[0], planes[1] if x1 is not None else None, theta, ops.WARP_CONSTANT, fills[0], fills[1],
+                        None, None, None, outs[0], outs[1] if x1 is not None else None)
+        ctx.save_for_backward(theta)
+        ctx.in_shape = tuple(x.shape)
+        ctx.set_materialize_grads(False)              # an unused plane's gradient stays None: no launch for it
+        return outs[0] if x1 is None else (outs[0], outs[1])
+
+    @staticmethod
+    def backward(ctx, *gys):
+        (theta,) = ctx.saved_tensors
+        grads = [None, None]
+        for k, gy in enumerate(gys):
+            if gy is not None and ctx.needs_input_grad[3 + k]:
+                grads[k] = ops.affine_warp_backward(gy.contiguous(), theta, ops.WARP_CONSTANT,
+                                                    torch.empty(ctx.in_shape, dtype=torch.float32, device=gy.device))
+        return None, None, None, grads[0], grads[1]
+
+
+def diff_affine_warp(x: torch.Tensor, theta: torch.Tensor, x1: Optional[torch.Tensor] = None, *, out_size=None, fill=0.0,
+                     mode: str = "constant"):
+    """affine_warp(..., mode="constant") without noise, differentiable in x (and x1): the same one launch forward, its
+    bits under no_grad, and the exact adjoint of the trilinear gather as the backward (include/mpgan_hip.h:
+    mpgan_affine_warp_backward; deterministic, no atomics), one launch per plane that requires grad.  `fill` (one number,
+    or one per plane) is a constant and theta gets no gradient.  A theta that is singular or shrinks by more than
+    MPGAN_WARP_REACH_MAX per axis has a NaN gradient; none that sample_affine_params draws is.  `mode` exists to say
+    why "border" is refused: a clamped coordinate sends gradient from arbitrarily far away to the faces, and that
+    adjoint is not built."""
+    if mode != "constant":
+        raise ValueError(f"diff_affine_warp: only mode 'constant' has a backward, got {mode!r}")
+    planes = (x,) if x1 is None else (x, x1)
+    for t in planes:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError("diff_affine_warp: every tensor must be on the GPU (there is no CPU path)")
+        if t.dtype != torch.float32 or t.dim() not in (4, 5) or t.shape != x.shape:
+            raise ValueError(f"diff_affine_warp: the planes are float32 (B, 1, *S) tensors of one shape, got "
+                             f"{[(tuple(p.shape), p.dtype) for p in planes]}")
+    fills = (float(fill),) * 2 if isinstance(fill, (int, float)) else tuple(float(f) for f in fill)
+    if len(fills) != 2:
+        raise ValueError(f"diff_affine_warp: fill is one number or one per plane, got {fill!r}")
+    out_size = tuple(x.shape[2:]) if out_size is None else tuple(int(s) for s in out_size)
+    if len(out_size) != x.dim() - 2:
+        raise ValueError(f"diff_affine_warp: out_size {out_size} for a {x.dim() - 2}-D image")
+    return _AffineWarpFn.apply(theta, out_size, fills, x, x1)
 
 
 # ---- elastic deformation and MRI intensity augmentation of the same pair (DESIGN.md 7j; the same file's second kernel) ---

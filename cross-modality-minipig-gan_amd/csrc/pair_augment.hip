@@ -54,6 +54,13 @@ struct WarpDims {
   FastDiv divTW, divTH, divTD;     // tile index -> (sample, tile d, tile h, tile w)
 };
 
+// c_k = A p + t along one axis, Ak = row k of (A | t): the one expression every kernel of this file evaluates the map
+// with (the backward's weights are the forward's only if both round alike): the (h, w) part first, the d term added to it.
+__device__ __forceinline__ double warp_base(const double* Ak, int h, int w) {
+  return Ak[1] * (double)h + Ak[2] * (double)w + Ak[3];
+}
+__device__ __forceinline__ double warp_coord(const double* Ak, int d, double base) { return Ak[0] * (double)d + base; }
+
 struct WarpAxis {
   int i0, i1;      // element indices of the two corners along this axis (i1 == i0 when the far corner has weight 0)
   bool ok0, ok1;   // CONSTANT: the corner lies inside the input
@@ -123,14 +130,14 @@ __global__ __launch_bounds__(256) void affine_warp_kernel(const float* __restric
   const double sg0 = noise0 ? (double)sigma[s * 2] : 0.0, sg1 = noise1 ? (double)sigma[s * 2 + 1] : 0.0;
   double base[3];                                   // A p + t without the d term
 #pragma unroll
-  for (int k = 0; k < 3; ++k) base[k] = A[k][1] * (double)h + A[k][2] * (double)w + A[k][3];
+  for (int k = 0; k < 3; ++k) base[k] = warp_base(A[k], h, w);
 #pragma unroll
   for (int i = 0; i < T::ID; ++i) {
     const int d = (int)td * T::TD + i * T::BD + ld;
     if (d >= dm.out[0]) break;
-    const WarpAxis ad = warp_axis<BORDER>(A[0][0] * (double)d + base[0], dm.in[0]);
-    const WarpAxis ah = warp_axis<BORDER>(A[1][0] * (double)d + base[1], dm.in[1]);
-    const WarpAxis aw = warp_axis<BORDER>(A[2][0] * (double)d + base[2], dm.in[2]);
+    const WarpAxis ad = warp_axis<BORDER>(warp_coord(A[0], d, base[0]), dm.in[0]);
+    const WarpAxis ah = warp_axis<BORDER>(warp_coord(A[1], d, base[1]), dm.in[1]);
+    const WarpAxis aw = warp_axis<BORDER>(warp_coord(A[2], d, base[2]), dm.in[2]);
     const int o = (d * dm.out[1] + h) * dm.out[2] + w;
     const size_t go = (size_t)s * Nout + o;
     double v = warp_value<BORDER>(p0, ad, ah, aw, sH, sD, (double)fill0);
@@ -144,8 +151,131 @@ __global__ __launch_bounds__(256) void affine_warp_kernel(const float* __restric
   }
 }
 
+// ---- mpgan_affine_warp_backward ------------------------------------------------------------------------------------------
+// The adjoint of the CONSTANT kernel above in x, as a gather: one thread per INPUT voxel q on the forward's tiles (of
+// the input extent this time), no atomics, every sum in increasing linear order of p.
+//   weights    g_x[q] = sum_p g_y[p] tent(c_d(p) - q_d) tent(c_h(p) - q_h) tent(c_w(p) - q_w), c by warp_base / warp_coord
+//   candidates a contributor has |c(p) - q| < 1 on every axis, so p = p* + A^-1 e with p* = A^-1 (q - t), |e_j| < 1:
+//              |p_k - p*_k| < r_k = sum_j |A^-1[k][j]|.  The box is walked over (p_d, p_h); along w the three
+//              conditions are linear in p_w and cut the box's row down to one interval.  Box and interval only prune
+//              (both are widened by kWarpSlack against their own rounding): the tents decide, and a weight of exactly
+//              0 is neither read nor added.
+//   bound      a sample with det A not finite, det A == 0 or an r_k > MPGAN_WARP_REACH_MAX gets NaN everywhere and no
+//              loop at all, so a thread visits at most 9 x 9 rows of at most 9 voxels whatever theta holds.
+constexpr double kWarpSlack = 1e-6;
+
+__device__ __forceinline__ double warp_tent(double u) {
+  const double a = fabs(u);
+  return a < 1.0 ? 1.0 - a : 0.0;                   // NaN -> 0
+}
+
+// [lo, hi] = the integers of [x - r, x + r] inside [0, S - 1]; empty (hi < lo) for a NaN.  r <= MPGAN_WARP_REACH_MAX, so
+// at most 9 of them.
+__device__ __forceinline__ void warp_reach(double x, double r, int S, int& lo, int& hi) {
+  const double l = ceil(x - r - kWarpSlack), u = floor(x + r + kWarpSlack);
+  lo = l > 0.0 ? (l > (double)S ? S : (int)l) : 0;
+  hi = !(u >= -1.0) ? -1 : (u < (double)(S - 1) ? (int)u : S - 1);
+}
+
+// Cut [w0, w1] down to the p_w with |b + a p_w| < 1 (ia = 1 / a).  A bound that is NaN cuts nothing.
+__device__ __forceinline__ void warp_cut(double b, double a, double ia, int& w0, int& w1) {
+  if (a == 0.0) {
+    if (!(fabs(b) < 1.0 + kWarpSlack)) w1 = w0 - 1;
+    return;
+  }
+  const double x0 = (-1.0 - b) * ia, x1 = (1.0 - b) * ia;       // (a small |a| makes both large: the slack is relative)
+  const double xl = a > 0.0 ? x0 : x1, xu = a > 0.0 ? x1 : x0;
+  const double l = ceil(xl - kWarpSlack * (1.0 + fabs(xl))), u = floor(xu + kWarpSlack * (1.0 + fabs(xu)));
+  if (l > (double)w0) w0 = l > (double)w1 ? w1 + 1 : (int)l;
+  if (u < (double)w1) w1 = u < (double)w0 ? w0 - 1 : (int)u;
+}
+
+// dm.in: the extent of g_y (what is read: the forward's output), dm.out: the extent of g_x (what is written and tiled).
+template <class T>
+__global__ __launch_bounds__(256) void affine_warp_backward_kernel(const float* __restrict__ gy, WarpDims dm,
+                                                                   const double* __restrict__ theta,
+                                                                   float* __restrict__ gx) {
+  unsigned q, tw, th, td, s;
+  fdivmod(blockIdx.x, dm.divTW, q, tw);
+  fdivmod(q, dm.divTH, q, th);
+  fdivmod(q, dm.divTD, s, td);
+  const int lw = threadIdx.x % T::BW, lh = (threadIdx.x / T::BW) % T::BH, ld = threadIdx.x / (T::BW * T::BH);
+  const int w = (int)tw * T::TW + lw, h = (int)th * T::TH + lh;
+  if (w >= dm.out[2] || h >= dm.out[1]) return;
+  const double* __restrict__ th12 = theta + (size_t)s * 12;
+  double A[3][4];
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) A[k][j] = th12[k * 4 + j];
+  // A^-1 = adj(A) / det A, its row sums r_k, and 1 / A[k][2] for the cuts along w: once per thread, block-uniform
+  double Ai[3][3];
+  Ai[0][0] = A[1][1] * A[2][2] - A[1][2] * A[2][1];
+  Ai[0][1] = A[0][2] * A[2][1] - A[0][1] * A[2][2];
+  Ai[0][2] = A[0][1] * A[1][2] - A[0][2] * A[1][1];
+  Ai[1][0] = A[1][2] * A[2][0] - A[1][0] * A[2][2];
+  Ai[1][1] = A[0][0] * A[2][2] - A[0][2] * A[2][0];
+  Ai[1][2] = A[0][2] * A[1][0] - A[0][0] * A[1][2];
+  Ai[2][0] = A[1][0] * A[2][1] - A[1][1] * A[2][0];
+  Ai[2][1] = A[0][1] * A[2][0] - A[0][0] * A[2][1];
+  Ai[2][2] = A[0][0] * A[1][1] - A[0][1] * A[1][0];
+  const double det = A[0][0] * Ai[0][0] + A[0][1] * Ai[1][0] + A[0][2] * Ai[2][0];
+  const double idet = 1.0 / det;
+  double r[3], ia[3];
+  bool ok = det != 0.0 && fabs(det) < HUGE_VAL;     // (a NaN fails the second test)
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) Ai[k][j] *= idet;
+    r[k] = fabs(Ai[k][0]) + fabs(Ai[k][1]) + fabs(Ai[k][2]);
+    ok = ok && r[k] <= MPGAN_WARP_REACH_MAX;        // (a NaN fails)
+    ia[k] = 1.0 / A[k][2];
+  }
+  const int Ngy = dm.in[0] * dm.in[1] * dm.in[2], Ngx = dm.out[0] * dm.out[1] * dm.out[2];
+  const float* __restrict__ g = gy + (size_t)s * Ngy;
+  float* __restrict__ o = gx + (size_t)s * Ngx;
+#pragma unroll 1
+  for (int i = 0; i < T::ID; ++i) {
+    const int d = (int)td * T::TD + i * T::BD + ld;
+    if (d >= dm.out[0]) break;
+    const int at = (d * dm.out[1] + h) * dm.out[2] + w;
+    if (!ok) {
+      o[at] = __builtin_nanf("");
+      continue;
+    }
+    const double e0 = (double)d - A[0][3], e1 = (double)h - A[1][3], e2 = (double)w - A[2][3];
+    int lo[3], hi[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      warp_reach(Ai[k][0] * e0 + Ai[k][1] * e1 + Ai[k][2] * e2, r[k], dm.in[k], lo[k], hi[k]);
+    double acc = 0.0;
+    if (lo[2] <= hi[2]) {
+      for (int pd = lo[0]; pd <= hi[0]; ++pd) {
+        for (int ph = lo[1]; ph <= hi[1]; ++ph) {
+          double base[3];
+#pragma unroll
+          for (int k = 0; k < 3; ++k) base[k] = A[k][0] * (double)pd + A[k][1] * (double)ph + A[k][3];
+          int w0 = lo[2], w1 = hi[2];
+          warp_cut(base[0] - (double)d, A[0][2], ia[0], w0, w1);
+          warp_cut(base[1] - (double)h, A[1][2], ia[1], w0, w1);
+          warp_cut(base[2] - (double)w, A[2][2], ia[2], w0, w1);
+          const int row = (pd * dm.in[1] + ph) * dm.in[2];
+          for (int pw = w0; pw <= w1; ++pw) {
+            const double wd = warp_tent(warp_coord(A[0], pd, warp_base(A[0], ph, pw)) - (double)d);
+            const double wh = warp_tent(warp_coord(A[1], pd, warp_base(A[1], ph, pw)) - (double)h);
+            const double ww = warp_tent(warp_coord(A[2], pd, warp_base(A[2], ph, pw)) - (double)w);
+            if (wd == 0.0 || wh == 0.0 || ww == 0.0) continue;
+            acc += (double)g[row + pw] * wd * wh * ww;
+          }
+        }
+      }
+    }
+    o[at] = (float)acc;
+  }
+}
+
 // ---- mpgan_deform_warp ---------------------------------------------------------------------------------------------------
-constexpr int kLatticeMax = 64;                    // the largest lattice extent per axis (the LDS rows are sized by it)
+constexpr int kLatticeMax = 64;                   // the largest lattice extent per axis (the LDS rows are sized by it)
 
 struct DeformArgs {
   const double* ctrl;      // [n][3][cg0][cg1][cg2] control displacements in input voxels, or null
@@ -284,7 +414,7 @@ __global__ __launch_bounds__(256) void deform_warp_kernel(const float* __restric
   if (gl) gw = spline_axis(wc, dm.out[2], df.gg[2]);
   double base[3];                                   // A p + t without the d term
 #pragma unroll
-  for (int k = 0; k < 3; ++k) base[k] = A[k][1] * (double)h + A[k][2] * (double)w + A[k][3];
+  for (int k = 0; k < 3; ++k) base[k] = warp_base(A[k], h, w);
 #pragma unroll 1
   for (int i = 0; i < T::ID; ++i) {                 // (ID == 1 in the product: one d step per block)
     const int d = (int)td * T::TD + i;
@@ -296,9 +426,9 @@ __global__ __launch_bounds__(256) void deform_warp_kernel(const float* __restric
       __syncthreads();
     }
     if (!active) continue;
-    double c0 = A[0][0] * (double)d + base[0];
-    double c1 = A[1][0] * (double)d + base[1];
-    double c2 = A[2][0] * (double)d + base[2];
+    double c0 = warp_coord(A[0], d, base[0]);
+    double c1 = warp_coord(A[1], d, base[1]);
+    double c2 = warp_coord(A[2], d, base[2]);
     double b = 0.0;                                 // the log-gain
     if (cl) {                                       // an axis of extent 1 has no displacement
       double u[3];
@@ -429,6 +559,30 @@ extern "C" int mpgan_affine_warp(const float* x0, const float* x1, int32_t n, co
 #undef MPGAN_WARP_GO
   set_error("mpgan_affine_warp: unknown tile %d", tile);
   return MPGAN_ERR_INVALID;
+}
+
+template <class T>
+static int warp_backward_launch(const float* gy, int32_t n, const int32_t* in_dhw, const int32_t* out_dhw,
+                                const double* theta, float* gx, void* stream) {
+  WarpDims dm;                                      // the kernel reads the forward's output extent and tiles its input extent
+  const dim3 grid((unsigned)warp_dims<T>(n, out_dhw, in_dhw, &dm)), block(256);
+  hipLaunchKernelGGL((affine_warp_backward_kernel<T>), grid, block, 0, (hipStream_t)stream, gy, dm, theta, gx);
+  return check_launch("mpgan_affine_warp_backward");
+}
+
+extern "C" int mpgan_affine_warp_backward(const float* gy, int32_t n, const int32_t* in_dhw, const int32_t* out_dhw,
+                                          const double* theta, int32_t mode, float* gx, void* stream) {
+  const char* fn = "mpgan_affine_warp_backward";
+  MPGAN_CHECK_ARG(gy && gx && theta && in_dhw && out_dhw, "%s: bad argument (null gy / gx / theta / in_dhw / out_dhw)", fn);
+  MPGAN_CHECK_ARG(n > 0, "%s: bad argument (n = %d)", fn, n);
+  MPGAN_CHECK_ARG(mode == MPGAN_WARP_CONSTANT || mode == MPGAN_WARP_BORDER, "%s: unknown mode %d (constant 0)", fn, mode);
+  MPGAN_CHECK_ARG(mode != MPGAN_WARP_BORDER, "%s: the border mode has no backward (a clamped coordinate sends gradient "
+                  "from arbitrarily far away to the faces); constant 0 only", fn);
+  long Nin, Nout;
+  if (int rc = warp_count(fn, "input", n, in_dhw, &Nin)) return rc;
+  if (int rc = warp_count(fn, "output", n, out_dhw, &Nout)) return rc;
+  if (in_dhw[0] > 1) return warp_backward_launch<WarpTile3d>(gy, n, in_dhw, out_dhw, theta, gx, stream);
+  return warp_backward_launch<WarpTile2d>(gy, n, in_dhw, out_dhw, theta, gx, stream);
 }
 
 // The lattice rule of include/mpgan_hip.h over the output extent: extent 1 on an axis of extent 1, else 4 .. 64.

@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .augment import DiffAugment, PairAugment, parse_policy
+from .augment import DiffAugment, PairAugment, affine_options, parse_policy
 from .losses import EdgeLoss, ForegroundL1Loss, ForegroundSSIMLoss, GlobalMutualInformationLoss, SSIMLoss
 from .preprocess import check_threshold
 from .networks import CasNetGenerator, Discriminator, _EngineModule
@@ -370,13 +370,15 @@ class _HParams(types.SimpleNamespace):
     """GAN.hparams.  `adv_loss` reads "bce" unless the constructor was given another objective, and only then is it an
     entry of vars(hparams): a default GAN lists exactly the hyper-parameters it listed before the option existed.
     `conditional` likewise reads False unless the constructor was given True, and `diff_augment` "" (with
-    `diff_augment_fill` 0.0) unless it was given a policy, and `ema_decay` 0.0 / `ema_warmup` True / `grad_clip` 0.0 /
+    `diff_augment_fill` 0.0) unless it was given a policy, `diff_augment_affine` None unless that policy has the word
+    "affine" (then the keywords its maps are drawn with), and `ema_decay` 0.0 / `ema_warmup` True / `grad_clip` 0.0 /
     `log_grad_norm` False unless the constructor was given another value, and `pair_augment` None unless it was given
     the keywords of a PairAugment."""
     adv_loss = "bce"
     conditional = False
     diff_augment = ""
     diff_augment_fill = 0.0
+    diff_augment_affine = None
     ema_decay = 0.0
     ema_warmup = True
     grad_clip = 0.0
@@ -399,7 +401,8 @@ class GAN(nn.Module):
                  diff_augment: str = "", diff_augment_fill: float = 0.0, ema_decay: float = 0.0,
                  ema_warmup: bool = True, grad_clip: float = 0.0, log_grad_norm: bool = False,
                  pair_augment: Optional[dict] = None, edge_weight: float = 0.0, edge_eps: float = 1e-6,
-                 fg_weight: float = 0.0, fg_threshold="otsu", fg_ssim_weight: float = 0.0, **kwargs):
+                 fg_weight: float = 0.0, fg_threshold="otsu", fg_ssim_weight: float = 0.0,
+                 diff_augment_affine: Optional[dict] = None, **kwargs):
         super().__init__()
         if adv_loss not in ADV_LOSSES:
             raise ValueError(f"adv_loss must be one of {ADV_LOSSES}, got {adv_loss!r}")
@@ -421,6 +424,7 @@ class GAN(nn.Module):
         if not grad_clip >= 0:
             raise ValueError(f"grad_clip must be >= 0, got {grad_clip!r}")
         aug_ops = parse_policy(diff_augment)         # ValueError on an unknown policy word, before anything is built
+        aug_affine = affine_options(diff_augment, diff_augment_affine)     # likewise: options without the word, an unknown key
         pair_module = _pair_augment_module(pair_augment)    # likewise on an unknown keyword or a value out of range
         if dimensions is None:
             dimensions = 3 if depth is not None else 2
@@ -433,6 +437,8 @@ class GAN(nn.Module):
         if aug_ops:
             self.hparams.diff_augment = str(diff_augment)
             self.hparams.diff_augment_fill = float(diff_augment_fill)
+        if aug_affine is not None:
+            self.hparams.diff_augment_affine = dict(aug_affine)
         for name, value in (("ema_decay", float(ema_decay)), ("ema_warmup", bool(ema_warmup)),
                             ("grad_clip", float(grad_clip)), ("log_grad_norm", bool(log_grad_norm))):
             if value != getattr(_HParams, name):
@@ -490,7 +496,7 @@ class GAN(nn.Module):
         # opt-in differentiable augmentation of everything D sees in training_step (augment.py); with the
         # default "" there is no module and no launch.  aug_generator: a torch.Generator on the images' device, or None
         # for torch's global one (data-parallel runs: every rank seeds its own, or all ranks draw the same parameters)
-        self.augment = DiffAugment(diff_augment, fill=diff_augment_fill) if aug_ops else None
+        self.augment = DiffAugment(diff_augment, fill=diff_augment_fill, affine=diff_augment_affine) if aug_ops else None
         self.aug_generator: Optional[torch.Generator] = None
         # opt-in augmentation of the training pair itself (augment.PairAugment): fit_batch warps t1w and
         # t2w under one draw, with noise on the input, before the G step; both steps see that pair.  It draws from

@@ -1263,6 +1263,28 @@ def affine_warp(x0, x1, theta, mode: int, fill0: float, fill1: float, noise0, no
     return y0 if y1 is None else (y0, y1)
 
 
+def affine_warp_backward(gy, theta, mode: int, gx):
+    """gx = the gradient of affine_warp's input for the output gradient gy under the same theta (B, 12) float64: the
+    exact adjoint of the WARP_CONSTANT forward, a deterministic gather (include/mpgan_hip.h).  gx has the forward's input
+    shape and is overwritten everywhere; a sample whose theta is singular or reaches beyond MPGAN_WARP_REACH_MAX gets
+    NaN.  WARP_BORDER has no backward."""
+    n, out_spatial = _diffaug_geometry(gy, "affine_warp_backward")
+    _, spatial = _diffaug_geometry(gx, "affine_warp_backward")
+    if gx.shape[0] != n or len(out_spatial) != len(spatial) or gx.device != gy.device:
+        raise ValueError(f"affine_warp_backward: gx has shape {tuple(gx.shape)} on {gx.device}, gy {tuple(gy.shape)} on "
+                         f"{gy.device}")
+    if mode != WARP_CONSTANT:
+        raise ValueError(f"affine_warp_backward: only WARP_CONSTANT ({WARP_CONSTANT}) has a backward, got mode {mode!r}")
+    if (not isinstance(theta, torch.Tensor) or tuple(theta.shape) != (n, 12) or theta.dtype != torch.float64
+            or not theta.is_contiguous() or theta.device != gy.device):
+        raise ValueError(f"affine_warp_backward: theta must be a contiguous {torch.float64} ({n}, 12) tensor on {gy.device}, "
+                         + (f"got {tuple(theta.shape)} {theta.dtype} on {theta.device}" if isinstance(theta, torch.Tensor)
+                            else f"got {theta!r}"))
+    check(lib().mpgan_affine_warp_backward(gy.data_ptr(), n, _dhw(spatial), _dhw(out_spatial), theta.data_ptr(), int(mode),
+                                           gx.data_ptr(), _stream()), "affine_warp_backward")
+    return gx
+
+
 def deform_warp(x0, x1, theta, ctrl, gain, gain_planes: int, gamma, lo: float, hi: float, mode: int, fill0: float,
                 fill1: float, noise0, noise1, sigma, y0, y1):
     """affine_warp with c = (A p + t) + u(p), u the cubic B-spline deformation of the lattice ctrl (B, 3, g_d, g_h, g_w)

@@ -782,6 +782,33 @@ int mpgan_affine_warp(const float* x0, const float* x1, int32_t n, const int32_t
                       const double* theta, int32_t mode, float fill0, float fill1, const float* noise0,
                       const float* noise1, const float* sigma, float* y0, float* y1, void* stream);
 
+/* ---- the backward of mpgan_affine_warp in x, CONSTANT mode (pair_augment.hip) ----
+ * gy: contiguous fp32 [n][oD][oH][oW], the gradient of the forward's output; gx: [n][D][H][W], the gradient of its
+ * input, overwritten everywhere.  in_dhw, out_dhw, theta as for mpgan_affine_warp (in = the forward's input).  The
+ * exact adjoint of the CONSTANT forward in x (`fill` is a constant and gets no gradient):
+ *   c(p)    = A p + t, evaluated by the forward's own expression: A[k][0]*d + (A[k][1]*h + A[k][2]*w + A[k][3])
+ *   tent(u) = 1 - |u| if |u| < 1, else 0 (also 0 for NaN)
+ *   g_x[q]  = sum over output voxels p of g_y[p] * tent(c_d(p) - q_d) * tent(c_h(p) - q_h) * tent(c_w(p) - q_w)
+ * Weights, products and the sum are fp64, rounded to fp32 once.  A term whose weight is exactly 0 is not read and not
+ * added; the terms of one q are added in increasing linear order of p.  An integer-valued (A | t) therefore gives a
+ * permuted copy of g_y, with zeros where no p lands.
+ * Launch: one gather kernel, one thread per input voxel q on mpgan_affine_warp's tiles (of the input extent).  Per
+ * sample the 3 x 3 inverse of A gives p* = A^-1 (q - t) and the half-extents r_k = sum_j |A^-1[k][j]|; a contributor has
+ * |p_k - p*_k| < r_k, and along w the three conditions |c_k(p) - q_k| < 1 are intersected to one interval per (p_d, p_h).
+ * No atomics and no order that depends on scheduling: two runs give the same bits, and a sample's gx does not depend
+ * on the other samples of its batch.
+ * Bounded work for any theta: a sample is supported when det A is finite and non-zero and every
+ * r_k <= MPGAN_WARP_REACH_MAX (every theta of A = F R / s with s < 2 is: r_k <= 2 sqrt(3)).  An unsupported sample gets
+ * NaN over its whole gx and no candidate loop; the other samples of the batch are unaffected.  So a voxel visits at
+ * most 9 candidates per axis whatever theta holds.  (A supported A with a NaN or infinite t maps every p to a NaN c or
+ * outside: zeros.)
+ * MPGAN_ERR_INVALID before any launch: a null gy / gx / theta / in_dhw / out_dhw, n <= 0, an extent < 1, an unknown
+ * mode, MPGAN_WARP_BORDER (a clamped coordinate sends gradient from arbitrarily far away to the faces: that adjoint is
+ * not built), n * N_in or n * N_out >= 2^31. */
+#define MPGAN_WARP_REACH_MAX 4.0
+int mpgan_affine_warp_backward(const float* gy, int32_t n, const int32_t* in_dhw, const int32_t* out_dhw,
+                               const double* theta, int32_t mode, float* gx, void* stream);
+
 /* ---- elastic deformation and MRI intensity augmentation of the same pair (pair_augment.hip) ----
  * mpgan_affine_warp with a smooth non-rigid displacement added to the map (both planes alike) and, per plane, a smooth
  * multiplicative bias field and a gamma change.  Every argument the two share means what it means above.  Per output
