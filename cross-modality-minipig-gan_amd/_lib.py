@@ -164,6 +164,8 @@ SIGNATURES = {
     # paired affine augmentation of the training pair (pair_augment.hip)
     "mpgan_affine_warp": (_I, [_P, _P, _I, _I3, _I3, _P, _I, _F, _F, _P, _P, _P, _P, _P, _P]),
     "mpgan_affine_warp_backward": (_I, [_P, _I, _I3, _I3, _P, _I, _P, _P]),
+    "mpgan_affine_warp_theta_workspace": (_L, [_I, _I3]),
+    "mpgan_affine_warp_backward_theta": (_I, [_P, _P, _P, _P, _I, _I3, _I3, _P, _I, _F, _F, _P, _L, _P, _P]),
     "mpgan_deform_warp": (_I, [_P, _P, _I, _I3, _I3, _P, _P, _I3, _P, _I3, _I, _P, C.c_double, C.c_double, _I, _F, _F, _P,
                                _P, _P, _P, _P, _P]),
     "mpgan_adam_step": (_I, [_P, _P, _P, _P, _L, C.c_double, C.c_double, C.c_double, C.c_double, _I, _F, _P]),

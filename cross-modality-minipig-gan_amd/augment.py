@@ -381,8 +381,9 @@ def _warp_arguments(what, x, x1, out_size, mode, fill, noise):
 # ---- the differentiable warp: what the policy word "affine" applies; affine_warp above is untouched ----------
 class _AffineWarpFn(torch.autograd.Function):
     """(y, y1) = the CONSTANT warp of (x, x1) in one launch; the map is linear in the images with weights that depend on
-    theta alone, so only theta is saved.  The backward launches ops.affine_warp_backward once per plane that needs a
-    gradient; theta gets none."""
+    theta alone, so only theta is saved for them.  The backward launches ops.affine_warp_backward once per plane that
+    needs a gradient.  A theta that requires grad also keeps the planes and gets ops.affine_warp_backward_theta's (B, 12)
+    float64, one call over the planes that have an output gradient."""
 
     @staticmethod
     def forward(ctx, theta, out_size, fills, x, x1):
@@ -390,20 +391,31 @@ class _AffineWarpFn(torch.autograd.Function):
         outs = [torch.empty((x.shape[0], 1, *out_size), dtype=torch.float32, device=x.device) for _ in planes]
         ops.affine_warp(planes[0], planes[1] if x1 is not None else None, theta, ops.WARP_CONSTANT, fills[0], fills[1],
                         None, None, None, outs[0], outs[1] if x1 is not None else None)
-        ctx.save_for_backward(theta)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(theta, *planes)
+            ctx.fills = fills
+        else:
+            ctx.save_for_backward(theta)
         ctx.in_shape = tuple(x.shape)
         ctx.set_materialize_grads(False)              # an unused plane's gradient stays None: no launch for it
         return outs[0] if x1 is None else (outs[0], outs[1])
 
     @staticmethod
     def backward(ctx, *gys):
-        (theta,) = ctx.saved_tensors
+        theta, *planes = ctx.saved_tensors
         grads = [None, None]
         for k, gy in enumerate(gys):
             if gy is not None and ctx.needs_input_grad[3 + k]:
                 grads[k] = ops.affine_warp_backward(gy.contiguous(), theta, ops.WARP_CONSTANT,
                                                     torch.empty(ctx.in_shape, dtype=torch.float32, device=gy.device))
-        return None, None, None, grads[0], grads[1]
+        gtheta = None
+        if ctx.needs_input_grad[0]:
+            # only the planes with an output gradient; plane 1 alone goes in as plane 0 with its own fill
+            live = [(planes[k], gy.contiguous(), ctx.fills[k]) for k, gy in enumerate(gys) if gy is not None]
+            if live:
+                (p0, g0, f0), (p1, g1, f1) = live[0], (live[1] if len(live) > 1 else (None, None, live[0][2]))
+                gtheta = ops.affine_warp_backward_theta(p0, p1, g0, g1, theta, ops.WARP_CONSTANT, f0, f1)
+        return gtheta, None, None, grads[0], grads[1]
 
 
 def diff_affine_warp(x: torch.Tensor, theta: torch.Tensor, x1: Optional[torch.Tensor] = None, *, out_size=None, fill=0.0,
@@ -411,10 +423,13 @@ def diff_affine_warp(x: torch.Tensor, theta: torch.Tensor, x1: Optional[torch.Te
     """affine_warp(..., mode="constant") without noise, differentiable in x (and x1): the same one launch forward, its
     bits under no_grad, and the exact adjoint of the trilinear gather as the backward (include/mpgan_hip.h:
     mpgan_affine_warp_backward; deterministic, no atomics), one launch per plane that requires grad.  `fill` (one number,
-    or one per plane) is a constant and theta gets no gradient.  A theta that is singular or shrinks by more than
-    MPGAN_WARP_REACH_MAX per axis has a NaN gradient; none that sample_affine_params draws is.  `mode` exists to say
-    why "border" is refused: a clamped coordinate sends gradient from arbitrarily far away to the faces, and that
-    adjoint is not built."""
+    or one per plane) is a constant.  A theta that is singular or shrinks by more than MPGAN_WARP_REACH_MAX per axis
+    gives x a NaN gradient; none that sample_affine_params draws is.  A theta (B, 12) float64 that requires grad gets its
+    own gradient, (B, 12) float64 summed in fp64 (mpgan_affine_warp_backward_theta: two launches, no atomics, the
+    right-hand derivative at integer coordinates); the planes are then kept for the backward.  With a theta that
+    requires none nothing is kept and nothing more is launched.  `mode` exists to say why "border" is refused: a
+    clamped coordinate sends gradient from arbitrarily far away to the faces, and neither that adjoint nor its gradient
+    in theta is built."""
     if mode != "constant":
         raise ValueError(f"diff_affine_warp: only mode 'constant' has a backward, got {mode!r}")
     planes = (x,) if x1 is None else (x, x1)

@@ -274,6 +274,138 @@ __global__ __launch_bounds__(256) void affine_warp_backward_kernel(const float* 
   }
 }
 
+// ---- mpgan_affine_warp_backward_theta ------------------------------------------------------------------------------------
+// The derivative of the CONSTANT kernel in theta (include/mpgan_hip.h): y is trilinear in c and c_k is linear
+// in row k of theta, so g_theta[k][j] = sum_p (sum_planes g_y[p] dy/dc_k(p)) P_j(p), P = (d, h, w, 1).
+//   voxel      c by warp_base / warp_coord; dead (any c_k NaN or outside [-1, S_k]: nothing read, nothing added); else
+//              b = floor(c), f = c - b and ALL eight corners b + {0,1}^3, `fill` outside the input: the forward skips a
+//              corner of weight 0, but the derivative along an axis is the difference across it whatever f is.  At an
+//              integer c this is the right-hand derivative, on the cell [b, b + 1].
+//   launch 1   the forward's tiles of the output, one thread per (h, w) walking the tile's d steps: 12 sums per thread in
+//              increasing d, block_sum_n (reduce.h) over the 12 entries, 12 doubles to ws[sample][tile][12]
+//   launch 2   one block per (sample, entry): thread t adds tiles t, t + 256, .. in order, then block_tree_sum<256>
+// No atomics; grid and orders depend on (n, out_dhw) alone.  Cell and fractions are computed once for both planes.
+struct WarpCell {
+  int i[3][2];      // element index of the two corners along each axis (0 where the corner is outside: never read)
+  bool ok[3][2];
+  double f[3];
+};
+
+// The eight corners of one plane -> dy/dc_d, dy/dc_h, dy/dc_w.
+__device__ __forceinline__ void warp_slopes(const float* __restrict__ x, const WarpCell& c, int sH, int sD, double fill,
+                                            double& dd, double& dh, double& dw) {
+  double v[2][2][2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      const int row = c.i[0][a] * sD + c.i[1][b] * sH;
+      const bool okr = c.ok[0][a] && c.ok[1][b];
+#pragma unroll
+      for (int e = 0; e < 2; ++e) v[a][b][e] = okr && c.ok[2][e] ? (double)x[row + c.i[2][e]] : fill;
+    }
+  auto lerp = [](double p, double q, double f) { return p + f * (q - p); };
+  const double fd = c.f[0], fh = c.f[1], fw = c.f[2];
+  dd = lerp(lerp(v[1][0][0] - v[0][0][0], v[1][0][1] - v[0][0][1], fw),
+            lerp(v[1][1][0] - v[0][1][0], v[1][1][1] - v[0][1][1], fw), fh);
+  dh = lerp(lerp(v[0][1][0] - v[0][0][0], v[0][1][1] - v[0][0][1], fw),
+            lerp(v[1][1][0] - v[1][0][0], v[1][1][1] - v[1][0][1], fw), fd);
+  dw = lerp(lerp(v[0][0][1] - v[0][0][0], v[0][1][1] - v[0][1][0], fh),
+            lerp(v[1][0][1] - v[1][0][0], v[1][1][1] - v[1][1][0], fh), fd);
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void affine_warp_theta_tile_kernel(const float* __restrict__ x0,
+                                                                     const float* __restrict__ x1,
+                                                                     const float* __restrict__ gy0,
+                                                                     const float* __restrict__ gy1, WarpDims dm,
+                                                                     const double* __restrict__ theta, float fill0,
+                                                                     float fill1, double* __restrict__ ws) {
+  static_assert(T::BD == 1, "one thread per (h, w)");
+  __shared__ double sh[12 * 256];
+  unsigned q, tw, th, td, s;
+  fdivmod(blockIdx.x, dm.divTW, q, tw);
+  fdivmod(q, dm.divTH, q, th);
+  fdivmod(q, dm.divTD, s, td);
+  const int lw = threadIdx.x % T::BW, lh = threadIdx.x / T::BW;
+  const int w = (int)tw * T::TW + lw, h = (int)th * T::TH + lh;
+  double acc[12];                                     // [k][j], row-major like theta
+#pragma unroll
+  for (int e = 0; e < 12; ++e) acc[e] = 0.0;
+  if (w < dm.out[2] && h < dm.out[1]) {               // (a thread outside the output stays for the block sums)
+    const double* __restrict__ th12 = theta + (size_t)s * 12;
+    double A[3][4];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) A[k][j] = th12[k * 4 + j];
+    const int Nin = dm.in[0] * dm.in[1] * dm.in[2], Nout = dm.out[0] * dm.out[1] * dm.out[2];
+    const int sH = dm.in[2], sD = dm.in[1] * dm.in[2];
+    const float* __restrict__ p0 = x0 + (size_t)s * Nin;
+    const float* __restrict__ p1 = x1 ? x1 + (size_t)s * Nin : nullptr;
+    double base[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) base[k] = warp_base(A[k], h, w);
+#pragma unroll
+    for (int i = 0; i < T::ID; ++i) {
+      const int d = (int)td * T::TD + i;
+      if (d >= dm.out[0]) break;
+      WarpCell cell;
+      bool alive = true;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const double c = warp_coord(A[k], d, base[k]);
+        alive = alive && c >= -1.0 && c <= (double)dm.in[k];       // a NaN fails
+        const double fl = floor(alive ? c : 0.0);
+        const int b = (int)fl;                                     // in [-1, S]
+        cell.f[k] = (alive ? c : 0.0) - fl;
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          cell.ok[k][e] = b + e >= 0 && b + e < dm.in[k];
+          cell.i[k][e] = cell.ok[k][e] ? b + e : 0;
+        }
+      }
+      if (!alive) continue;
+      const size_t go = (size_t)s * Nout + (size_t)((d * dm.out[1] + h) * dm.out[2] + w);
+      double dd, dh, dw;
+      warp_slopes(p0, cell, sH, sD, (double)fill0, dd, dh, dw);
+      const double g0 = (double)gy0[go];
+      double G[3] = {g0 * dd, g0 * dh, g0 * dw};
+      if (p1) {
+        warp_slopes(p1, cell, sH, sD, (double)fill1, dd, dh, dw);
+        const double g1 = (double)gy1[go];
+        G[0] += g1 * dd;
+        G[1] += g1 * dh;
+        G[2] += g1 * dw;
+      }
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        acc[k * 4 + 0] += G[k] * (double)d;
+        acc[k * 4 + 1] += G[k] * (double)h;
+        acc[k * 4 + 2] += G[k] * (double)w;
+        acc[k * 4 + 3] += G[k];
+      }
+    }
+  }
+  const double t = block_sum_n<12>(acc, sh);                        // entry threadIdx.x / 16 in the threads < 192
+  if (threadIdx.x < 192 && (threadIdx.x & 15) == 0)
+    ws[(size_t)blockIdx.x * 12 + (threadIdx.x >> 4)] = t;            // blockIdx.x = sample * tiles + tile
+}
+
+// g_theta[s][e] = the sum over the sample's tiles of ws[s][tile][e], one block per (sample, entry): thread t takes tiles
+// t, t + 256, .. in order, then block_tree_sum<256> (loss_item_kernel's scheme; a block per entry instead of twelve trees
+// in a row in one block: the same order per entry, a twelfth of the barriers in a row).
+__global__ __launch_bounds__(256) void affine_warp_theta_sum_kernel(const double* __restrict__ ws, int tiles,
+                                                                    double* __restrict__ gtheta) {
+  __shared__ double red[256];
+  const unsigned s = blockIdx.x / 12, e = blockIdx.x % 12;
+  const double* __restrict__ p = ws + (size_t)s * tiles * 12 + e;
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < tiles; i += 256) acc += p[(size_t)i * 12];
+  acc = block_tree_sum<256>(acc, red);
+  if (threadIdx.x == 0) gtheta[blockIdx.x] = acc;
+}
+
 // ---- mpgan_deform_warp ---------------------------------------------------------------------------------------------------
 constexpr int kLatticeMax = 64;                   // the largest lattice extent per axis (the LDS rows are sized by it)
 
@@ -583,6 +715,67 @@ extern "C" int mpgan_affine_warp_backward(const float* gy, int32_t n, const int3
   if (int rc = warp_count(fn, "output", n, out_dhw, &Nout)) return rc;
   if (in_dhw[0] > 1) return warp_backward_launch<WarpTile3d>(gy, n, in_dhw, out_dhw, theta, gx, stream);
   return warp_backward_launch<WarpTile2d>(gy, n, in_dhw, out_dhw, theta, gx, stream);
+}
+
+// The forward's tiles of one sample's output (the forward's choice: 4 x 8 x 32 for volumes, 1 x 8 x 32 for D = 1).
+static long warp_theta_tiles(const int32_t* out_dhw) {
+  const long td = out_dhw[0] > 1 ? WarpTile3d::TD : WarpTile2d::TD;
+  return ((out_dhw[0] + td - 1) / td) * ((out_dhw[1] + WarpTile3d::TH - 1) / WarpTile3d::TH) *
+         ((out_dhw[2] + WarpTile3d::TW - 1) / WarpTile3d::TW);
+}
+static_assert(WarpTile3d::TH == WarpTile2d::TH && WarpTile3d::TW == WarpTile2d::TW, "one (h, w) tiling");
+
+extern "C" int64_t mpgan_affine_warp_theta_workspace(int32_t n, const int32_t* out_dhw) {
+  const char* fn = "mpgan_affine_warp_theta_workspace";
+  long Nout;
+  if (!out_dhw || n <= 0) {
+    set_error("%s: bad argument (null out_dhw or n = %d)", fn, n);
+    return -1;
+  }
+  if (warp_count(fn, "output", n, out_dhw, &Nout) != MPGAN_OK) return -1;
+  return (int64_t)n * warp_theta_tiles(out_dhw) * 12 * (int64_t)sizeof(double);
+}
+
+template <class T>
+static int warp_theta_launch(const float* x0, const float* x1, const float* gy0, const float* gy1, int32_t n,
+                             const int32_t* in_dhw, const int32_t* out_dhw, const double* theta, float fill0, float fill1,
+                             double* ws, double* gtheta, void* stream) {
+  const char* fn = "mpgan_affine_warp_backward_theta";
+  WarpDims dm;
+  const long blocks = warp_dims<T>(n, in_dhw, out_dhw, &dm);
+  hipLaunchKernelGGL((affine_warp_theta_tile_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x0, x1,
+                     gy0, gy1, dm, theta, fill0, fill1, ws);
+  if (int rc = check_launch(fn)) return rc;
+  hipLaunchKernelGGL(affine_warp_theta_sum_kernel, dim3((unsigned)n * 12), dim3(256), 0, (hipStream_t)stream, ws,
+                     (int)(blocks / n), gtheta);
+  return check_launch(fn);
+}
+
+extern "C" int mpgan_affine_warp_backward_theta(const float* x0, const float* x1, const float* gy0, const float* gy1,
+                                                int32_t n, const int32_t* in_dhw, const int32_t* out_dhw,
+                                                const double* theta, int32_t mode, float fill0, float fill1, void* ws,
+                                                int64_t ws_bytes, double* gtheta, void* stream) {
+  const char* fn = "mpgan_affine_warp_backward_theta";
+  MPGAN_CHECK_ARG(x0 && gy0 && theta && gtheta && in_dhw && out_dhw,
+                  "%s: bad argument (null x0 / gy0 / theta / gtheta / in_dhw / out_dhw)", fn);
+  MPGAN_CHECK_ARG((x1 != nullptr) == (gy1 != nullptr), "%s: bad argument (x1 and gy1 go together: %s alone)", fn,
+                  x1 ? "x1" : "gy1");
+  MPGAN_CHECK_ARG(n > 0, "%s: bad argument (n = %d)", fn, n);
+  MPGAN_CHECK_ARG(mode == MPGAN_WARP_CONSTANT || mode == MPGAN_WARP_BORDER, "%s: unknown mode %d (constant 0)", fn, mode);
+  MPGAN_CHECK_ARG(mode != MPGAN_WARP_BORDER, "%s: the border mode has no gradient in theta here (the clamp makes it a "
+                  "different function of c: not built); constant 0 only", fn);
+  long Nin, Nout;
+  if (int rc = warp_count(fn, "input", n, in_dhw, &Nin)) return rc;
+  if (int rc = warp_count(fn, "output", n, out_dhw, &Nout)) return rc;
+  const int64_t need = (int64_t)n * warp_theta_tiles(out_dhw) * 12 * (int64_t)sizeof(double);
+  MPGAN_CHECK_ARG(ws != nullptr, "%s: bad argument (null workspace)", fn);
+  MPGAN_CHECK_ARG(ws_bytes >= need, "%s: workspace of %lld bytes, needs %lld", fn, (long long)ws_bytes, (long long)need);
+  MPGAN_CHECK_ARG((reinterpret_cast<uintptr_t>(ws) & 7) == 0, "%s: workspace must be 8-byte aligned", fn);
+  if (out_dhw[0] > 1)
+    return warp_theta_launch<WarpTile3d>(x0, x1, gy0, gy1, n, in_dhw, out_dhw, theta, fill0, fill1,
+                                         static_cast<double*>(ws), gtheta, stream);
+  return warp_theta_launch<WarpTile2d>(x0, x1, gy0, gy1, n, in_dhw, out_dhw, theta, fill0, fill1,
+                                       static_cast<double*>(ws), gtheta, stream);
 }
 
 // The lattice rule of include/mpgan_hip.h over the output extent: extent 1 on an axis of extent 1, else 4 .. 64.

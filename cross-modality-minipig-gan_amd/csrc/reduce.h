@@ -27,6 +27,29 @@ __device__ __forceinline__ T block_sum4(T v, T* sh) {
   return r;
 }
 
+// 256 threads, N <= 16 values each, through LDS (a dozen wave_sums per block cost more LDS cycles in their cross-lane
+// permutes than this costs in all).  Order: thread t stores sh[j * 256 + t] = v[j], barrier; thread t < 16 N, with
+// j = t / 16 and p = t % 16, adds sh[j * 256 + p], sh[j * 256 + p + 16], .. sh[j * 256 + p + 240] in that order (onto 0),
+// then the 16 lanes of a value fold by xor butterfly, offsets 8, 4, 2, 1.  Returns the sum of value t / 16 in the
+// threads t < 16 N (all 16 lanes of a value hold the same bits) and 0 in the others.  sh holds 256 * N values.
+template <int N, typename T>
+__device__ __forceinline__ T block_sum_n(const T (&v)[N], T* sh) {
+  static_assert(N >= 1 && N <= 16, "16 lanes per value");
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int j = 0; j < N; ++j) sh[j * 256 + t] = v[j];
+  __syncthreads();
+  T s = T(0);
+  if (t < 16 * N) {
+    const T* p = sh + (t >> 4) * 256 + (t & 15);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) s += p[i * 16];
+  }
+#pragma unroll
+  for (int off = 8; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  return s;
+}
+
 // N threads, N a power of two.  Order: red[tid] = v, then for s = N/2, N/4, .. 1: red[tid] += red[tid + s] for
 // tid < s, a barrier behind every level; returns red[0].  LEAD puts a barrier in front, for a red that the block may
 // still be reading (a second sum through the same array).

@@ -1285,6 +1285,50 @@ def affine_warp_backward(gy, theta, mode: int, gx):
     return gx
 
 
+def affine_warp_theta_workspace(n: int, out_spatial) -> int:
+    """Bytes of fp64 tile partials affine_warp_backward_theta needs for n samples of output extent out_spatial."""
+    need = int(lib().mpgan_affine_warp_theta_workspace(int(n), _dhw(out_spatial)))
+    if need < 0:
+        check(-1, "affine_warp_theta_workspace")
+    return need
+
+
+def affine_warp_backward_theta(x0, x1, gy0, gy1, theta, mode: int, fill0: float, fill1: float, gtheta=None):
+    """gtheta (B, 12) float64 = the gradient of affine_warp's theta for the inputs x0 (and x1) and the output gradients
+    gy0 (and gy1) under WARP_CONSTANT: fp64 throughout, two launches, no atomics, bitwise reproducible
+    (include/mpgan_hip.h).  x1 and gy1 are both tensors or both None.  All eight corners of a cell count, so at an
+    integer coordinate the derivative is the right-hand one.  gtheta is overwritten (allocated when None); the
+    workspace is allocated here.  WARP_BORDER has no gradient in theta."""
+    what = "affine_warp_backward_theta"
+    n, spatial = _diffaug_geometry(x0, what)
+    _, out_spatial = _diffaug_geometry(gy0, what)
+    if gy0.shape[0] != n or len(out_spatial) != len(spatial) or gy0.device != x0.device:
+        raise ValueError(f"{what}: gy0 has shape {tuple(gy0.shape)} on {gy0.device}, x0 {tuple(x0.shape)} on {x0.device}")
+    if (x1 is None) != (gy1 is None):
+        raise ValueError(f"{what}: x1 and gy1 go together")
+    if x1 is not None:
+        _diffaug_geometry(x1, what)
+        _diffaug_geometry(gy1, what)
+        if x1.shape != x0.shape or gy1.shape != gy0.shape or x1.device != x0.device or gy1.device != x0.device:
+            raise ValueError(f"{what}: the second plane has shapes {tuple(x1.shape)} / {tuple(gy1.shape)}, the first "
+                             f"{tuple(x0.shape)} / {tuple(gy0.shape)}")
+    if mode != WARP_CONSTANT:
+        raise ValueError(f"{what}: only WARP_CONSTANT ({WARP_CONSTANT}) has a gradient in theta, got mode {mode!r}")
+    if gtheta is None:
+        gtheta = torch.empty((n, 12), dtype=torch.float64, device=x0.device)
+    for t, name in ((theta, "theta"), (gtheta, "gtheta")):
+        if (not isinstance(t, torch.Tensor) or tuple(t.shape) != (n, 12) or t.dtype != torch.float64
+                or not t.is_contiguous() or t.device != x0.device):
+            raise ValueError(f"{what}: {name} must be a contiguous {torch.float64} ({n}, 12) tensor on {x0.device}, "
+                             + (f"got {tuple(t.shape)} {t.dtype} on {t.device}" if isinstance(t, torch.Tensor)
+                                else f"got {t!r}"))
+    ws = torch.empty(affine_warp_theta_workspace(n, out_spatial) // 8, dtype=torch.float64, device=x0.device)
+    check(lib().mpgan_affine_warp_backward_theta(x0.data_ptr(), _ptr(x1), gy0.data_ptr(), _ptr(gy1), n, _dhw(spatial),
+                                                 _dhw(out_spatial), theta.data_ptr(), int(mode), float(fill0), float(fill1),
+                                                 ws.data_ptr(), ws.numel() * 8, gtheta.data_ptr(), _stream()), what)
+    return gtheta
+
+
 def deform_warp(x0, x1, theta, ctrl, gain, gain_planes: int, gamma, lo: float, hi: float, mode: int, fill0: float,
                 fill1: float, noise0, noise1, sigma, y0, y1):
     """affine_warp with c = (A p + t) + u(p), u the cubic B-spline deformation of the lattice ctrl (B, 3, g_d, g_h, g_w)

@@ -809,6 +809,40 @@ int mpgan_affine_warp(const float* x0, const float* x1, int32_t n, const int32_t
 int mpgan_affine_warp_backward(const float* gy, int32_t n, const int32_t* in_dhw, const int32_t* out_dhw,
                                const double* theta, int32_t mode, float* gx, void* stream);
 
+/* ---- the gradient of mpgan_affine_warp in theta, CONSTANT mode (pair_augment.hip) ----
+ * x0, x1: the forward's inputs [n][D][H][W]; gy0, gy1: the gradients of its outputs [n][oD][oH][oW]; x1 and gy1 are both
+ * given or both null (one plane).  gtheta: double [n][12], row-major [k][j] like theta, overwritten.  in_dhw, out_dhw,
+ * theta, fill0, fill1 as for the forward.  Per sample and output voxel p = (d, h, w), with P = (d, h, w, 1):
+ *   c        = A p + t by the forward's own expression, A[k][0]*d + (A[k][1]*h + A[k][2]*w + A[k][3]); c' = c clamped to
+ *              [-1, S_k] per axis (the forward's CONSTANT clamp); b = floor(c'), f = c' - b
+ *   v_ijl    = x[b + (i, j, l)] where that index lies inside the input, else fill.  ALL eight corners count, also those
+ *              whose forward weight is exactly 0: the forward skips them, the derivative may not.  At an integer
+ *              coordinate this makes the derivative the right-hand one, on the cell [b, b + 1].
+ *   dy/dc_w  = lerp_d(lerp_h(v001 - v000, v011 - v010; f_h), lerp_h(v101 - v100, v111 - v110; f_h); f_d), and the d and h
+ *              derivatives alike with the axes exchanged; lerp(a, b; f) = a + f (b - a)
+ *   dead     a voxel with any c_k NaN or outside [-1, S_k]: all three derivatives are 0 (every corner around it is
+ *              fill) and nothing is read for it
+ *   g_theta[k][j] = sum_p (sum_planes gy_plane[p] * dy_plane/dc_k(p)) * P_j(p)
+ * Everything is fp64 and nothing is rounded to fp32.  Any theta is legal; a NaN entry kills every voxel it reaches (a
+ * sample with one gets zeros where its c is NaN).  A 2-D image (D = 1) is no special case: the j = 0 column is 0 because
+ * d = 0, and the k = 0 row follows the rule above (its d corner pair is (x, fill)); the 2-D parametrisations never read
+ * it.
+ * Launches: two, no atomics.  (1) On the forward's tiles of the output (4 x 8 x 32, D = 1: 1 x 8 x 32), one thread per
+ * (h, w) walking the tile's d steps: a thread adds its 12 products in increasing d, the block sums each entry in a
+ * fixed order through LDS (16 threads per entry add 16 strided values each in index order, then fold by xor butterfly)
+ * and stores 12 doubles to ws[sample][tile][12].  (2) One block per sample and entry: thread t adds tiles t, t + 256, ..
+ * in order, then a fixed tree over the 256 threads.  Grid and orders depend on (n, out_dhw) alone: two runs give the
+ * same bits, whatever ws held, and a sample's g_theta does not depend on the rest of its batch.  Coordinates, cell and
+ * fractions are computed once per voxel for both planes.
+ * mpgan_affine_warp_theta_workspace: the bytes of ws (n * tiles * 12 doubles), -1 for bad geometry.
+ * MPGAN_ERR_INVALID before any launch: a null x0 / gy0 / theta / gtheta / in_dhw / out_dhw, x1 without gy1 or the
+ * reverse, n <= 0, an extent < 1, an unknown mode, MPGAN_WARP_BORDER (the clamp of c makes it another function of theta:
+ * that gradient is not built), a null, short or misaligned (8 bytes) ws, n * N_in or n * N_out >= 2^31. */
+int64_t mpgan_affine_warp_theta_workspace(int32_t n, const int32_t* out_dhw);
+int mpgan_affine_warp_backward_theta(const float* x0, const float* x1, const float* gy0, const float* gy1, int32_t n,
+                                     const int32_t* in_dhw, const int32_t* out_dhw, const double* theta, int32_t mode,
+                                     float fill0, float fill1, void* ws, int64_t ws_bytes, double* gtheta, void* stream);
+
 /* ---- elastic deformation and MRI intensity augmentation of the same pair (pair_augment.hip) ----
  * mpgan_affine_warp with a smooth non-rigid displacement added to the map (both planes alike) and, per plane, a smooth
  * multiplicative bias field and a gamma change.  Every argument the two share means what it means above.  Per output
