@@ -62,16 +62,16 @@ def affine_options(policy: str, affine: Optional[dict] = None) -> Optional[dict]
     unknown = sorted(set(affine) - set(AFFINE_KEYS)) if isinstance(affine, dict) else None
     if unknown is None or unknown:
         raise ValueError(f"diff_augment policy: the affine options are a dict of the keywords {AFFINE_KEYS}, got {affine!r}")
-    o = dict(affine)
-    for ndim in (2, 3):
-        try:
-            _check_affine_options(o.get("rotate", 0.0), o.get("scale", 0.0), o.get("shift", 0.0), o.get("flip", ()),
-                                  o.get("prob", 1.0), 0.0, 1.0, (), ndim)
-            break
-        except ValueError:
-            if ndim == 3:
-                raise
-    return o
+    _check_some_image(**affine)
+    return dict(affine)
+
+
+def _spatial(what: str, spatial) -> tuple:
+    """The samplers' extent: (H, W) or (D, H, W) as a tuple of ints."""
+    spatial = tuple(int(s) for s in spatial)
+    if len(spatial) not in (2, 3) or min(spatial) < 1:
+        raise ValueError(f"{what}: spatial must be (H, W) or (D, H, W) with extents >= 1, got {spatial}")
+    return spatial
 
 
 def translation_range(size: int) -> int:
@@ -92,9 +92,7 @@ def sample_params(n: int, spatial: Sequence[int], policy: str, generator: Option
     With the word "affine" theta = sample_affine_params(n, spatial, **affine).theta is drawn last, after the cutout (a
     replay of the other words from the same seed is unchanged); `affine`: keywords from AFFINE_KEYS, by default
     DEFAULT_AFFINE; given without the word it is a ValueError."""
-    spatial = tuple(int(s) for s in spatial)
-    if len(spatial) not in (2, 3) or min(spatial) < 1:
-        raise ValueError(f"sample_params: spatial must be (H, W) or (D, H, W) with extents >= 1, got {spatial}")
+    spatial = _spatial("sample_params", spatial)
     mask = parse_policy(policy)
     affine = affine_options(policy, affine)
     device = torch.device(device)
@@ -257,6 +255,14 @@ def _check_affine_options(rotate, scale, shift, flip, prob, noise_std, noise_pro
     return rot, float(scale), sh, [a + 3 - ndim for a in axes], planes
 
 
+def _check_some_image(rotate=0.0, scale=0.0, shift=0.0, flip=(), prob=1.0, noise_std=0.0, noise_prob=1.0, noise_planes=()):
+    """ValueError unless some image, 2-D or 3-D, can take these options (the 3-D refusal is the one reported)."""
+    try:
+        _check_affine_options(rotate, scale, shift, flip, prob, noise_std, noise_prob, noise_planes, 2)
+    except ValueError:
+        _check_affine_options(rotate, scale, shift, flip, prob, noise_std, noise_prob, noise_planes, 3)
+
+
 def sample_affine_params(n: int, spatial: Sequence[int], *, rotate=0.0, scale: float = 0.0, shift=0.0,
                          flip: Sequence[int] = (), prob: float = 1.0, noise_std: float = 0.0, noise_prob: float = 1.0,
                          noise_planes: Sequence[int] = (0,), generator: Optional[torch.Generator] = None,
@@ -283,9 +289,7 @@ def sample_affine_params(n: int, spatial: Sequence[int], *, rotate=0.0, scale: f
 
 def _sample_affine(n, spatial, rotate, scale, shift, flip, prob, noise_std, noise_prob, noise_planes, generator, device):
     """sample_affine_params and the boolean (n,) gate of its `prob` draw (None when 0 < prob < 1 does not hold)."""
-    spatial = tuple(int(s) for s in spatial)
-    if len(spatial) not in (2, 3) or min(spatial) < 1:
-        raise ValueError(f"sample_affine_params: spatial must be (H, W) or (D, H, W) with extents >= 1, got {spatial}")
+    spatial = _spatial("sample_affine_params", spatial)
     ndim = len(spatial)
     rot, a, sh, axes, planes = _check_affine_options(rotate, scale, shift, flip, prob, noise_std, noise_prob,
                                                      noise_planes, ndim)
@@ -348,33 +352,45 @@ def affine_warp(x: torch.Tensor, theta: torch.Tensor, x1: Optional[torch.Tensor]
     output's shape for plane 0, or a pair (field or None, field or None); plane k then gets + sigma[:, k] * noise_k
     (sigma (B, 2) float32).  Not differentiable: an input that requires grad is refused."""
     planes, fills, noises, outs = _warp_arguments("affine_warp", x, x1, out_size, mode, fill, noise)
-    ops.affine_warp(planes[0], planes[1] if x1 is not None else None, theta, WARP_MODES[mode], fills[0], fills[1],
-                    noises[0], noises[1], sigma, outs[0], outs[1] if x1 is not None else None)
-    return outs[0] if x1 is None else (outs[0], outs[1])
+    ops.affine_warp(planes[0], planes[1], theta, WARP_MODES[mode], fills[0], fills[1], noises[0], noises[1], sigma,
+                    outs[0], outs[1])
+    return _planes_out(outs)
+
+
+def _warp_io(what, x, x1, out_size, fill, differentiable: bool):
+    """What every warp of this module makes of (x, x1, out_size, fill): the contiguous planes [x, x1] (detached unless
+    `differentiable`; without it an input that requires grad under grad mode is refused), the two fills, and the new
+    outputs [y, y1] of extent out_size.  x1 None stays None in both lists, which is how ops takes a single plane."""
+    for t in (x,) if x1 is None else (x, x1):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"{what}: every tensor must be on the GPU (there is no CPU path)")
+        if not differentiable and t.requires_grad and torch.is_grad_enabled():
+            raise ValueError(f"{what}: not differentiable (an input requires grad); call it under torch.no_grad() "
+                             "or on detached tensors")
+    fills = (float(fill),) * 2 if isinstance(fill, (int, float)) else tuple(float(f) for f in fill)
+    if len(fills) != 2:
+        raise ValueError(f"{what}: fill is one number or one per plane, got {fill!r}")
+    out_size = tuple(x.shape[2:]) if out_size is None else tuple(int(s) for s in out_size)
+    if len(out_size) != x.dim() - 2:
+        raise ValueError(f"{what}: out_size {out_size} for a {x.dim() - 2}-D image")
+    planes = [None if t is None else (t if differentiable else t.detach()).contiguous() for t in (x, x1)]
+    outs = [None if t is None else torch.empty((x.shape[0], 1, *out_size), dtype=torch.float32, device=x.device)
+            for t in planes]
+    return planes, fills, outs
+
+
+def _planes_out(outs):
+    return outs[0] if outs[1] is None else (outs[0], outs[1])
 
 
 def _warp_arguments(what, x, x1, out_size, mode, fill, noise):
     """The checks affine_warp and deform_warp share: (detached contiguous planes, fills, noises, new outputs)."""
-    planes = [x] if x1 is None else [x, x1]
-    for t in planes:
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ValueError(f"{what}: every tensor must be on the GPU (there is no CPU path)")
-        if t.requires_grad and torch.is_grad_enabled():
-            raise ValueError(f"{what}: not differentiable (an input requires grad); call it under torch.no_grad() "
-                             "or on detached tensors")
+    planes, fills, outs = _warp_io(what, x, x1, out_size, fill, differentiable=False)
     if mode not in WARP_MODES:
         raise ValueError(f"{what}: mode must be one of {sorted(WARP_MODES)}, got {mode!r}")
-    fills = (float(fill),) * 2 if isinstance(fill, (int, float)) else tuple(float(f) for f in fill)
-    if len(fills) != 2:
-        raise ValueError(f"{what}: fill is one number or one per plane, got {fill!r}")
     noises = [noise, None] if noise is None or isinstance(noise, torch.Tensor) else list(noise)
     if len(noises) != 2:
         raise ValueError(f"{what}: noise is one field (plane 0) or a pair")
-    planes = [t.detach().contiguous() for t in planes]
-    out_size = tuple(x.shape[2:]) if out_size is None else tuple(int(s) for s in out_size)
-    if len(out_size) != x.dim() - 2:
-        raise ValueError(f"{what}: out_size {out_size} for a {x.dim() - 2}-D image")
-    outs = [torch.empty((x.shape[0], 1, *out_size), dtype=torch.float32, device=x.device) for _ in planes]
     return planes, fills, noises, outs
 
 
@@ -386,19 +402,17 @@ class _AffineWarpFn(torch.autograd.Function):
     float64, one call over the planes that have an output gradient."""
 
     @staticmethod
-    def forward(ctx, theta, out_size, fills, x, x1):
-        planes = [t.contiguous() for t in ((x,) if x1 is None else (x, x1))]
-        outs = [torch.empty((x.shape[0], 1, *out_size), dtype=torch.float32, device=x.device) for _ in planes]
-        ops.affine_warp(planes[0], planes[1] if x1 is not None else None, theta, ops.WARP_CONSTANT, fills[0], fills[1],
-                        None, None, None, outs[0], outs[1] if x1 is not None else None)
+    def forward(ctx, theta, fills, outs, x, x1):
+        """x and x1 (or None): contiguous; outs: diff_affine_warp's new [y, y1 or None], filled and returned here."""
+        ops.affine_warp(x, x1, theta, ops.WARP_CONSTANT, fills[0], fills[1], None, None, None, outs[0], outs[1])
         if ctx.needs_input_grad[0]:
-            ctx.save_for_backward(theta, *planes)
+            ctx.save_for_backward(theta, *((x,) if x1 is None else (x, x1)))
             ctx.fills = fills
         else:
             ctx.save_for_backward(theta)
         ctx.in_shape = tuple(x.shape)
         ctx.set_materialize_grads(False)              # an unused plane's gradient stays None: no launch for it
-        return outs[0] if x1 is None else (outs[0], outs[1])
+        return _planes_out(outs)
 
     @staticmethod
     def backward(ctx, *gys):
@@ -432,20 +446,11 @@ def diff_affine_warp(x: torch.Tensor, theta: torch.Tensor, x1: Optional[torch.Te
     in theta is built."""
     if mode != "constant":
         raise ValueError(f"diff_affine_warp: only mode 'constant' has a backward, got {mode!r}")
-    planes = (x,) if x1 is None else (x, x1)
-    for t in planes:
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ValueError("diff_affine_warp: every tensor must be on the GPU (there is no CPU path)")
-        if t.dtype != torch.float32 or t.dim() not in (4, 5) or t.shape != x.shape:
-            raise ValueError(f"diff_affine_warp: the planes are float32 (B, 1, *S) tensors of one shape, got "
-                             f"{[(tuple(p.shape), p.dtype) for p in planes]}")
-    fills = (float(fill),) * 2 if isinstance(fill, (int, float)) else tuple(float(f) for f in fill)
-    if len(fills) != 2:
-        raise ValueError(f"diff_affine_warp: fill is one number or one per plane, got {fill!r}")
-    out_size = tuple(x.shape[2:]) if out_size is None else tuple(int(s) for s in out_size)
-    if len(out_size) != x.dim() - 2:
-        raise ValueError(f"diff_affine_warp: out_size {out_size} for a {x.dim() - 2}-D image")
-    return _AffineWarpFn.apply(theta, out_size, fills, x, x1)
+    planes, fills, outs = _warp_io("diff_affine_warp", x, x1, out_size, fill, differentiable=True)
+    if any(t is not None and (t.dtype != torch.float32 or t.dim() not in (4, 5) or t.shape != x.shape) for t in planes):
+        raise ValueError(f"diff_affine_warp: the planes are float32 (B, 1, *S) tensors of one shape, got "
+                         f"{[(tuple(p.shape), p.dtype) for p in planes if p is not None]}")
+    return _AffineWarpFn.apply(theta, fills, outs, planes[0], planes[1])
 
 
 # ---- elastic deformation and MRI intensity augmentation of the same pair (DESIGN.md 7j; the same file's second kernel) ---
@@ -518,9 +523,7 @@ def sample_deform_params(n: int, spatial: Sequence[int], *, elastic: float = 0.0
     Draw order, one torch.rand each: ctrl (n, ndim, *elastic_grid), gain (n, *bias_grid), gamma (n, number of planes),
     then the intensity gate (n,) when 0 < intensity_prob < 1 and gain or gamma is on.  A disabled option (elastic 0;
     bias_field 0, gamma 0, no plane or intensity_prob 0) draws nothing and returns None for its table."""
-    spatial = tuple(int(s) for s in spatial)
-    if len(spatial) not in (2, 3) or min(spatial) < 1:
-        raise ValueError(f"sample_deform_params: spatial must be (H, W) or (D, H, W) with extents >= 1, got {spatial}")
+    spatial = _spatial("sample_deform_params", spatial)
     eg, bg, planes = _check_deform_options(elastic, elastic_grid, bias_field, bias_grid, gamma, intensity_prob,
                                            intensity_planes, spatial)
     device = torch.device(device)
@@ -578,11 +581,10 @@ def deform_warp(x: torch.Tensor, theta: torch.Tensor, x1: Optional[torch.Tensor]
             raise ValueError(f"deform_warp: gain_planes is a subset of (0, 1), got {tuple(gain_planes)!r}")
         mask = sum(1 << k for k in {int(k) for k in gain_planes})
     lo, hi = (float(v) for v in value_range)
-    ops.deform_warp(planes[0], planes[1] if x1 is not None else None, theta,
-                    None if ctrl is None else ctrl.contiguous(), None if gain is None else gain.contiguous(), mask, gamma,
-                    lo, hi, WARP_MODES[mode], fills[0], fills[1], noises[0], noises[1], sigma, outs[0],
-                    outs[1] if x1 is not None else None)
-    return outs[0] if x1 is None else (outs[0], outs[1])
+    ops.deform_warp(planes[0], planes[1], theta, None if ctrl is None else ctrl.contiguous(),
+                    None if gain is None else gain.contiguous(), mask, gamma, lo, hi, WARP_MODES[mode], fills[0], fills[1],
+                    noises[0], noises[1], sigma, outs[0], outs[1])
+    return _planes_out(outs)
 
 
 class PairAugment(nn.Module):
@@ -625,13 +627,7 @@ class PairAugment(nn.Module):
         if mode not in WARP_MODES:
             raise ValueError(f"PairAugment: mode must be one of {sorted(WARP_MODES)}, got {mode!r}")
         self.noise_planes = sorted({PAIR_KEYS.index(k) for k in noise_keys})
-        for ndim in (2, 3):                           # ValueError on a value no image could take
-            try:
-                _check_affine_options(rotate, scale, shift, flip, prob, noise_std, noise_prob, self.noise_planes, ndim)
-                break
-            except ValueError:
-                if ndim == 3:
-                    raise
+        _check_some_image(rotate, scale, shift, flip, prob, noise_std, noise_prob, self.noise_planes)
         self.options = dict(rotate=rotate, scale=float(scale), shift=shift, flip=tuple(flip), prob=float(prob),
                             noise_std=float(noise_std), noise_prob=float(noise_prob))
         self.mode, self.fill = mode, float(fill)
@@ -654,16 +650,12 @@ class PairAugment(nn.Module):
         t1w, t2w = batch["t1w"], batch["t2w"]
         with torch.no_grad():
             n, spatial = t1w.shape[0], tuple(t1w.shape[2:])
-            if not self.deforms:
-                p = sample_affine_params(n, spatial, noise_planes=self.noise_planes, generator=self.generator,
-                                         device=t1w.device, **self.options)
-                q = None
-            else:
-                o = self.options
-                p, gate = _sample_affine(n, spatial, o["rotate"], o["scale"], o["shift"], o["flip"], o["prob"],
-                                         o["noise_std"], o["noise_prob"], self.noise_planes, self.generator, t1w.device)
+            p, gate = _sample_affine(n, spatial, noise_planes=self.noise_planes, generator=self.generator,
+                                     device=t1w.device, **self.options)
+            q = None
+            if self.deforms:
                 q = dict(self.deform_options)
-                if o["prob"] == 0.0:                  # no spatial op draws at all
+                if self.options["prob"] == 0.0:       # no spatial op draws at all
                     q["elastic"] = 0.0
                 q = sample_deform_params(n, spatial, intensity_planes=self.intensity_planes, spatial_gate=gate,
                                          generator=self.generator, device=t1w.device, **q)

@@ -189,17 +189,7 @@ static inline bool da_al16(const void* p) { return (reinterpret_cast<uintptr_t>(
 static int da_geometry(const char* who, int32_t n, const int32_t* dhw, long* N) {
   MPGAN_CHECK_ARG(dhw != nullptr, "%s: bad argument (null dhw)", who);
   MPGAN_CHECK_ARG(n > 0, "%s: bad argument (n = %d)", who, n);
-  MPGAN_CHECK_ARG(dhw[0] >= 1 && dhw[1] >= 1 && dhw[2] >= 1, "%s: bad argument (extent %d x %d x %d)", who, dhw[0], dhw[1],
-                  dhw[2]);
-  const long cap = 0x7fffffffL;
-  long e = n;
-  for (int k = 0; k < 3; ++k) {
-    MPGAN_CHECK_ARG(e <= cap / dhw[k], "%s: n * D * H * W = %d * %d * %d * %d exceeds the 32-bit element count", who, n,
-                    dhw[0], dhw[1], dhw[2]);
-    e *= dhw[k];
-  }
-  *N = e / n;
-  return MPGAN_OK;
+  return element_count(who, "", n, dhw, N);
 }
 
 extern "C" int64_t mpgan_diffaug_workspace(int32_t n, const int32_t* dhw) {

@@ -84,6 +84,22 @@ inline int check_launch(const char* what) {
   return MPGAN_OK;
 }
 
+// Host only: *N = D * H * W of one of n > 0 items of extent dhw, and 0; or -1 with the error set when an extent is below 1
+// or n * D * H * W exceeds the 32-bit element count.  `side` names the extent in the message ("input ", "output " or "").
+inline int element_count(const char* fn, const char* side, int32_t n, const int32_t* dhw, long* N) {
+  MPGAN_CHECK_ARG(dhw[0] >= 1 && dhw[1] >= 1 && dhw[2] >= 1, "%s: bad argument (%sextent %d x %d x %d)", fn, side, dhw[0],
+                  dhw[1], dhw[2]);
+  const long cap = 0x7fffffffL;
+  long e = n;
+  for (int k = 0; k < 3; ++k) {
+    MPGAN_CHECK_ARG(e <= cap / dhw[k], "%s: %sn * D * H * W = %d * %d * %d * %d exceeds the 32-bit element count", fn, side, n,
+                    dhw[0], dhw[1], dhw[2]);
+    e *= dhw[k];
+  }
+  *N = e / n;
+  return MPGAN_OK;
+}
+
 // The one-time preamble of a launcher whose instance KERN may need more dynamic LDS than the default limit: raised
 // once per instantiation.
 template <auto KERN>

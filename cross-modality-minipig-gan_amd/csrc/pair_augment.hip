@@ -608,36 +608,44 @@ __global__ __launch_bounds__(256) void deform_warp_kernel(const float* __restric
 
 using namespace mpgan;
 
-// n * D * H * W of one side: 0 and *N, or -1 with the error set (fn: the entry point's name, for the message).
-static int warp_count(const char* fn, const char* side, int32_t n, const int32_t* dhw, long* N) {
-  MPGAN_CHECK_ARG(dhw[0] >= 1 && dhw[1] >= 1 && dhw[2] >= 1, "%s: bad argument (%s extent %d x %d x %d)", fn,
-                  side, dhw[0], dhw[1], dhw[2]);
-  const long cap = 0x7fffffffL;
-  long e = n;
-  for (int k = 0; k < 3; ++k) {
-    MPGAN_CHECK_ARG(e <= cap / dhw[k], "%s: %s n * D * H * W = %d * %d * %d * %d exceeds the 32-bit element count", fn,
-                    side, n, dhw[0], dhw[1], dhw[2]);
-    e *= dhw[k];
-  }
-  *N = e / n;
-  return MPGAN_OK;
+// What every warp entry point refuses: a null required pointer (`given`: the entry point's own, spelled out in `names`),
+// n, the mode, and an extent or element count of either side.  An entry point without a border mode passes what the
+// border mode lacks there and why as `constant_only`; null: both modes are taken.
+static int warp_check(const char* fn, bool given, const char* names, int32_t n, const int32_t* in_dhw,
+                      const int32_t* out_dhw, int32_t mode, const char* constant_only) {
+  MPGAN_CHECK_ARG(given && in_dhw && out_dhw, "%s: bad argument (null %s / in_dhw / out_dhw)", fn, names);
+  MPGAN_CHECK_ARG(n > 0, "%s: bad argument (n = %d)", fn, n);
+  MPGAN_CHECK_ARG(mode == MPGAN_WARP_CONSTANT || mode == MPGAN_WARP_BORDER, "%s: unknown mode %d (constant 0%s)", fn, mode,
+                  constant_only ? "" : ", border 1");
+  MPGAN_CHECK_ARG(!constant_only || mode != MPGAN_WARP_BORDER, "%s: the border mode has no %s; constant 0 only", fn,
+                  constant_only);
+  long N;
+  if (int rc = element_count(fn, "input ", n, in_dhw, &N)) return rc;
+  return element_count(fn, "output ", n, out_dhw, &N);
 }
 
-// What both entry points refuse.
-static int warp_check(const char* fn, const float* x0, const float* x1, int32_t n, const int32_t* in_dhw,
-                      const int32_t* out_dhw, const double* theta, int32_t mode, const float* noise0, const float* noise1,
-                      const float* sigma, const float* y0, const float* y1) {
-  MPGAN_CHECK_ARG(x0 && y0 && theta && in_dhw && out_dhw, "%s: bad argument (null x0 / y0 / theta / in_dhw / out_dhw)", fn);
-  MPGAN_CHECK_ARG((x1 != nullptr) == (y1 != nullptr), "%s: bad argument (x1 and y1 go together: %s alone)", fn,
-                  x1 ? "x1" : "y1");
-  MPGAN_CHECK_ARG(n > 0, "%s: bad argument (n = %d)", fn, n);
-  MPGAN_CHECK_ARG(mode == MPGAN_WARP_CONSTANT || mode == MPGAN_WARP_BORDER, "%s: unknown mode %d (constant 0, border 1)", fn, mode);
+// The second plane's two pointers (a, b: their names) are both given or both null.
+#define MPGAN_WARP_PAIR(fn, a, b) \
+  MPGAN_CHECK_ARG((a != nullptr) == (b != nullptr), "%s: bad argument (" #a " and " #b " go together: %s alone)", fn, a ? #a : #b)
+
+// What both forward entry points refuse.
+static int warp_forward_check(const char* fn, const float* x0, const float* x1, int32_t n, const int32_t* in_dhw,
+                              const int32_t* out_dhw, const double* theta, int32_t mode, const float* noise0,
+                              const float* noise1, const float* sigma, const float* y0, const float* y1) {
+  if (int rc = warp_check(fn, x0 && y0 && theta, "x0 / y0 / theta", n, in_dhw, out_dhw, mode, nullptr)) return rc;
+  MPGAN_WARP_PAIR(fn, x1, y1);
   MPGAN_CHECK_ARG(!(noise0 || noise1) || sigma, "%s: bad argument (noise without sigma)", fn);
   MPGAN_CHECK_ARG(!sigma || noise0 || noise1, "%s: bad argument (sigma without noise)", fn);
   MPGAN_CHECK_ARG(!noise1 || x1, "%s: bad argument (noise1 without the second plane)", fn);
-  long Nin, Nout;
-  if (int rc = warp_count(fn, "input", n, in_dhw, &Nin)) return rc;
-  return warp_count(fn, "output", n, out_dhw, &Nout);
+  return MPGAN_OK;
+}
+
+// The tile of a launch over an extent of this depth, the forward's choice by measurement: 4 x 8 x 32 for
+// volumes, 1 x 8 x 32 for depth 1.  go(T{}) launches with the tile T.
+template <class Go>
+static int warp_tile(int32_t depth, Go&& go) {
+  if (depth > 1) return go(WarpTile3d{});
+  return go(WarpTile2d{});
 }
 
 // The tiling of the output: dm and the number of tiles (= blocks).
@@ -652,76 +660,62 @@ static long warp_dims(int32_t n, const int32_t* in_dhw, const int32_t* out_dhw, 
   return (long)n * tD * tH * tW;                    // every tile holds an output voxel of its own: <= n * N_out < 2^31
 }
 
-template <class T>
-static int warp_launch(const float* x0, const float* x1, int32_t n, const int32_t* in_dhw, const int32_t* out_dhw,
-                       const double* theta, int32_t mode, float fill0, float fill1, const float* noise0,
-                       const float* noise1, const float* sigma, float* y0, float* y1, void* stream) {
-  WarpDims dm;
-  const dim3 grid((unsigned)warp_dims<T>(n, in_dhw, out_dhw, &dm)), block(256);
-  if (mode == MPGAN_WARP_BORDER)
-    hipLaunchKernelGGL((affine_warp_kernel<T, true>), grid, block, 0, (hipStream_t)stream, x0, x1, dm, theta, fill0, fill1,
-                       noise0, noise1, sigma, y0, y1);
-  else
-    hipLaunchKernelGGL((affine_warp_kernel<T, false>), grid, block, 0, (hipStream_t)stream, x0, x1, dm, theta, fill0, fill1,
-                       noise0, noise1, sigma, y0, y1);
-  return check_launch("mpgan_affine_warp");
-}
-
 extern "C" int mpgan_affine_warp(const float* x0, const float* x1, int32_t n, const int32_t* in_dhw,
                                  const int32_t* out_dhw, const double* theta, int32_t mode, float fill0, float fill1,
                                  const float* noise0, const float* noise1, const float* sigma, float* y0, float* y1,
                                  void* stream) {
-  if (int rc = warp_check("mpgan_affine_warp", x0, x1, n, in_dhw, out_dhw, theta, mode, noise0, noise1, sigma, y0, y1)) return rc;
-  int tile = out_dhw[0] > 1 ? 0 : 1;
-  if (const char* e = dev_env("MPGAN_DBG_WARP_TILE")) tile = atoi(e);
-#define MPGAN_WARP_GO(T) return warp_launch<T>(x0, x1, n, in_dhw, out_dhw, theta, mode, fill0, fill1, noise0, noise1, sigma, y0, y1, stream)
-  switch (tile) {
-    case 0: MPGAN_WARP_GO(WarpTile3d);
-    case 1: MPGAN_WARP_GO(WarpTile2d);
+  if (int rc = warp_forward_check("mpgan_affine_warp", x0, x1, n, in_dhw, out_dhw, theta, mode, noise0, noise1, sigma, y0, y1)) return rc;
+  auto go = [&](auto tile) {
+    using T = decltype(tile);
+    WarpDims dm;
+    const dim3 grid((unsigned)warp_dims<T>(n, in_dhw, out_dhw, &dm)), block(256);
+    if (mode == MPGAN_WARP_BORDER)
+      hipLaunchKernelGGL((affine_warp_kernel<T, true>), grid, block, 0, (hipStream_t)stream, x0, x1, dm, theta, fill0, fill1,
+                         noise0, noise1, sigma, y0, y1);
+    else
+      hipLaunchKernelGGL((affine_warp_kernel<T, false>), grid, block, 0, (hipStream_t)stream, x0, x1, dm, theta, fill0, fill1,
+                         noise0, noise1, sigma, y0, y1);
+    return check_launch("mpgan_affine_warp");
+  };
 #ifdef MPGAN_DEV_SWITCHES
-    case 2: MPGAN_WARP_GO(WarpTileRow);
-    case 3: MPGAN_WARP_GO(WarpTileSq);
-    case 4: MPGAN_WARP_GO(WarpTileCube);
-    case 5: MPGAN_WARP_GO(WarpTileDeep);
-    case 6: MPGAN_WARP_GO(WarpTileWave);
-    case 7: MPGAN_WARP_GO(WarpTileWave4);
-    case 8: MPGAN_WARP_GO(WarpTileHalf);
-#endif
+  if (const char* e = dev_env("MPGAN_DBG_WARP_TILE")) {
+    switch (atoi(e)) {
+      case 0: return go(WarpTile3d{});
+      case 1: return go(WarpTile2d{});
+      case 2: return go(WarpTileRow{});
+      case 3: return go(WarpTileSq{});
+      case 4: return go(WarpTileCube{});
+      case 5: return go(WarpTileDeep{});
+      case 6: return go(WarpTileWave{});
+      case 7: return go(WarpTileWave4{});
+      case 8: return go(WarpTileHalf{});
+    }
+    set_error("mpgan_affine_warp: unknown tile %s", e);
+    return MPGAN_ERR_INVALID;
   }
-#undef MPGAN_WARP_GO
-  set_error("mpgan_affine_warp: unknown tile %d", tile);
-  return MPGAN_ERR_INVALID;
-}
-
-template <class T>
-static int warp_backward_launch(const float* gy, int32_t n, const int32_t* in_dhw, const int32_t* out_dhw,
-                                const double* theta, float* gx, void* stream) {
-  WarpDims dm;                                      // the kernel reads the forward's output extent and tiles its input extent
-  const dim3 grid((unsigned)warp_dims<T>(n, out_dhw, in_dhw, &dm)), block(256);
-  hipLaunchKernelGGL((affine_warp_backward_kernel<T>), grid, block, 0, (hipStream_t)stream, gy, dm, theta, gx);
-  return check_launch("mpgan_affine_warp_backward");
+#endif
+  return warp_tile(out_dhw[0], go);
 }
 
 extern "C" int mpgan_affine_warp_backward(const float* gy, int32_t n, const int32_t* in_dhw, const int32_t* out_dhw,
                                           const double* theta, int32_t mode, float* gx, void* stream) {
-  const char* fn = "mpgan_affine_warp_backward";
-  MPGAN_CHECK_ARG(gy && gx && theta && in_dhw && out_dhw, "%s: bad argument (null gy / gx / theta / in_dhw / out_dhw)", fn);
-  MPGAN_CHECK_ARG(n > 0, "%s: bad argument (n = %d)", fn, n);
-  MPGAN_CHECK_ARG(mode == MPGAN_WARP_CONSTANT || mode == MPGAN_WARP_BORDER, "%s: unknown mode %d (constant 0)", fn, mode);
-  MPGAN_CHECK_ARG(mode != MPGAN_WARP_BORDER, "%s: the border mode has no backward (a clamped coordinate sends gradient "
-                  "from arbitrarily far away to the faces); constant 0 only", fn);
-  long Nin, Nout;
-  if (int rc = warp_count(fn, "input", n, in_dhw, &Nin)) return rc;
-  if (int rc = warp_count(fn, "output", n, out_dhw, &Nout)) return rc;
-  if (in_dhw[0] > 1) return warp_backward_launch<WarpTile3d>(gy, n, in_dhw, out_dhw, theta, gx, stream);
-  return warp_backward_launch<WarpTile2d>(gy, n, in_dhw, out_dhw, theta, gx, stream);
+  if (int rc = warp_check("mpgan_affine_warp_backward", gy && gx && theta, "gy / gx / theta", n, in_dhw, out_dhw, mode,
+                          "backward (a clamped coordinate sends gradient from arbitrarily far away to the faces)"))
+    return rc;
+  return warp_tile(in_dhw[0], [&](auto tile) {
+    WarpDims dm;                                    // the kernel reads the forward's output extent and tiles its input extent
+    const dim3 grid((unsigned)warp_dims<decltype(tile)>(n, out_dhw, in_dhw, &dm)), block(256);
+    hipLaunchKernelGGL((affine_warp_backward_kernel<decltype(tile)>), grid, block, 0, (hipStream_t)stream, gy, dm, theta, gx);
+    return check_launch("mpgan_affine_warp_backward");
+  });
 }
 
-// The forward's tiles of one sample's output (the forward's choice: 4 x 8 x 32 for volumes, 1 x 8 x 32 for D = 1).
-static long warp_theta_tiles(const int32_t* out_dhw) {
+// Bytes of the theta gradient's workspace: 12 doubles per forward tile (warp_tile's) of the n samples' outputs.
+static int64_t warp_theta_bytes(int32_t n, const int32_t* out_dhw) {
   const long td = out_dhw[0] > 1 ? WarpTile3d::TD : WarpTile2d::TD;
-  return ((out_dhw[0] + td - 1) / td) * ((out_dhw[1] + WarpTile3d::TH - 1) / WarpTile3d::TH) *
-         ((out_dhw[2] + WarpTile3d::TW - 1) / WarpTile3d::TW);
+  const long tiles = ((out_dhw[0] + td - 1) / td) * ((out_dhw[1] + WarpTile3d::TH - 1) / WarpTile3d::TH) *
+                     ((out_dhw[2] + WarpTile3d::TW - 1) / WarpTile3d::TW);
+  return (int64_t)n * tiles * 12 * (int64_t)sizeof(double);
 }
 static_assert(WarpTile3d::TH == WarpTile2d::TH && WarpTile3d::TW == WarpTile2d::TW, "one (h, w) tiling");
 
@@ -732,23 +726,8 @@ extern "C" int64_t mpgan_affine_warp_theta_workspace(int32_t n, const int32_t* o
     set_error("%s: bad argument (null out_dhw or n = %d)", fn, n);
     return -1;
   }
-  if (warp_count(fn, "output", n, out_dhw, &Nout) != MPGAN_OK) return -1;
-  return (int64_t)n * warp_theta_tiles(out_dhw) * 12 * (int64_t)sizeof(double);
-}
-
-template <class T>
-static int warp_theta_launch(const float* x0, const float* x1, const float* gy0, const float* gy1, int32_t n,
-                             const int32_t* in_dhw, const int32_t* out_dhw, const double* theta, float fill0, float fill1,
-                             double* ws, double* gtheta, void* stream) {
-  const char* fn = "mpgan_affine_warp_backward_theta";
-  WarpDims dm;
-  const long blocks = warp_dims<T>(n, in_dhw, out_dhw, &dm);
-  hipLaunchKernelGGL((affine_warp_theta_tile_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x0, x1,
-                     gy0, gy1, dm, theta, fill0, fill1, ws);
-  if (int rc = check_launch(fn)) return rc;
-  hipLaunchKernelGGL(affine_warp_theta_sum_kernel, dim3((unsigned)n * 12), dim3(256), 0, (hipStream_t)stream, ws,
-                     (int)(blocks / n), gtheta);
-  return check_launch(fn);
+  if (element_count(fn, "output ", n, out_dhw, &Nout) != MPGAN_OK) return -1;
+  return warp_theta_bytes(n, out_dhw);
 }
 
 extern "C" int mpgan_affine_warp_backward_theta(const float* x0, const float* x1, const float* gy0, const float* gy1,
@@ -756,26 +735,24 @@ extern "C" int mpgan_affine_warp_backward_theta(const float* x0, const float* x1
                                                 const double* theta, int32_t mode, float fill0, float fill1, void* ws,
                                                 int64_t ws_bytes, double* gtheta, void* stream) {
   const char* fn = "mpgan_affine_warp_backward_theta";
-  MPGAN_CHECK_ARG(x0 && gy0 && theta && gtheta && in_dhw && out_dhw,
-                  "%s: bad argument (null x0 / gy0 / theta / gtheta / in_dhw / out_dhw)", fn);
-  MPGAN_CHECK_ARG((x1 != nullptr) == (gy1 != nullptr), "%s: bad argument (x1 and gy1 go together: %s alone)", fn,
-                  x1 ? "x1" : "gy1");
-  MPGAN_CHECK_ARG(n > 0, "%s: bad argument (n = %d)", fn, n);
-  MPGAN_CHECK_ARG(mode == MPGAN_WARP_CONSTANT || mode == MPGAN_WARP_BORDER, "%s: unknown mode %d (constant 0)", fn, mode);
-  MPGAN_CHECK_ARG(mode != MPGAN_WARP_BORDER, "%s: the border mode has no gradient in theta here (the clamp makes it a "
-                  "different function of c: not built); constant 0 only", fn);
-  long Nin, Nout;
-  if (int rc = warp_count(fn, "input", n, in_dhw, &Nin)) return rc;
-  if (int rc = warp_count(fn, "output", n, out_dhw, &Nout)) return rc;
-  const int64_t need = (int64_t)n * warp_theta_tiles(out_dhw) * 12 * (int64_t)sizeof(double);
+  if (int rc = warp_check(fn, x0 && gy0 && theta && gtheta, "x0 / gy0 / theta / gtheta", n, in_dhw, out_dhw, mode,
+                          "gradient in theta here (the clamp makes it a different function of c: not built)"))
+    return rc;
+  MPGAN_WARP_PAIR(fn, x1, gy1);
+  const int64_t need = warp_theta_bytes(n, out_dhw);
   MPGAN_CHECK_ARG(ws != nullptr, "%s: bad argument (null workspace)", fn);
   MPGAN_CHECK_ARG(ws_bytes >= need, "%s: workspace of %lld bytes, needs %lld", fn, (long long)ws_bytes, (long long)need);
   MPGAN_CHECK_ARG((reinterpret_cast<uintptr_t>(ws) & 7) == 0, "%s: workspace must be 8-byte aligned", fn);
-  if (out_dhw[0] > 1)
-    return warp_theta_launch<WarpTile3d>(x0, x1, gy0, gy1, n, in_dhw, out_dhw, theta, fill0, fill1,
-                                         static_cast<double*>(ws), gtheta, stream);
-  return warp_theta_launch<WarpTile2d>(x0, x1, gy0, gy1, n, in_dhw, out_dhw, theta, fill0, fill1,
-                                       static_cast<double*>(ws), gtheta, stream);
+  return warp_tile(out_dhw[0], [&](auto tile) {
+    WarpDims dm;
+    const long blocks = warp_dims<decltype(tile)>(n, in_dhw, out_dhw, &dm);
+    hipLaunchKernelGGL((affine_warp_theta_tile_kernel<decltype(tile)>), dim3((unsigned)blocks), dim3(256), 0,
+                       (hipStream_t)stream, x0, x1, gy0, gy1, dm, theta, fill0, fill1, static_cast<double*>(ws));
+    if (int rc = check_launch(fn)) return rc;
+    hipLaunchKernelGGL(affine_warp_theta_sum_kernel, dim3((unsigned)n * 12), dim3(256), 0, (hipStream_t)stream,
+                       static_cast<const double*>(ws), (int)(blocks / n), gtheta);
+    return check_launch(fn);
+  });
 }
 
 // The lattice rule of include/mpgan_hip.h over the output extent: extent 1 on an axis of extent 1, else 4 .. 64.
@@ -815,7 +792,7 @@ extern "C" int mpgan_deform_warp(const float* x0, const float* x1, int32_t n, co
                                  int32_t gain_planes, const double* gamma, double lo, double hi, int32_t mode,
                                  float fill0, float fill1, const float* noise0, const float* noise1,
                                  const float* sigma, float* y0, float* y1, void* stream) {
-  if (int rc = warp_check("mpgan_deform_warp", x0, x1, n, in_dhw, out_dhw, theta, mode, noise0, noise1, sigma, y0, y1)) return rc;
+  if (int rc = warp_forward_check("mpgan_deform_warp", x0, x1, n, in_dhw, out_dhw, theta, mode, noise0, noise1, sigma, y0, y1)) return rc;
   if (int rc = lattice_check("ctrl", ctrl, ctrl_dhw, out_dhw)) return rc;
   if (int rc = lattice_check("gain", gain, gain_dhw, out_dhw)) return rc;
   MPGAN_CHECK_ARG(!(gain_planes & ~3), "mpgan_deform_warp: unknown gain_planes bits %#x (1 = plane 0, 2 = plane 1)", gain_planes);

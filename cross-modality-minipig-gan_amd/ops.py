@@ -1170,17 +1170,24 @@ def _diffaug_geometry(x, what: str):
     return int(x.shape[0]), tuple(int(s) for s in x.shape[2:])
 
 
+def _table(what: str, name: str, t, dtype, shape, device, required: bool = False):
+    """The one check of a table argument: a contiguous `dtype` tensor of `shape` on `device`; None passes unless
+    `required`."""
+    if t is None and not required:
+        return
+    if (not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous()
+            or t.device != device):
+        got = f"{tuple(t.shape)} {t.dtype} on {t.device}" if isinstance(t, torch.Tensor) else repr(t)
+        raise ValueError(f"{what}: {name} must be a contiguous {dtype} {tuple(shape)} tensor on {device}, got {got}")
+
+
 def _diffaug_tables(x, n, ops_mask, color, geom, workspace, spatial, what):
     if ops_mask & ~15:
         raise ValueError(f"{what}: unknown ops bits {ops_mask:#x}")
     for t, dtype, cols, name, used in ((color, torch.float32, 2, "color", ops_mask & 3), (geom, torch.int32, 9, "geom", ops_mask & 12)):
-        if t is None:
-            if used:
-                raise ValueError(f"{what}: ops {ops_mask:#x} need the {name} table")
-            continue
-        if tuple(t.shape) != (n, cols) or t.dtype != dtype or not t.is_contiguous() or t.device != x.device:
-            raise ValueError(f"{what}: {name} must be a contiguous {dtype} ({n}, {cols}) tensor on {x.device}, got "
-                             f"{tuple(t.shape)} {t.dtype} on {t.device}")
+        if t is None and used:
+            raise ValueError(f"{what}: ops {ops_mask:#x} need the {name} table")
+        _table(what, name, t, dtype, (n, cols), x.device)
     if ops_mask & DIFFAUG_CONTRAST:
         need = diffaug_workspace(n, spatial)
         if (workspace is None or workspace.dtype != torch.float64 or not workspace.is_contiguous()
@@ -1227,36 +1234,53 @@ def diffaug_backward(gy, ops_mask: int, color, geom, workspace, gx):
 WARP_CONSTANT, WARP_BORDER = 0, 1                                                            # MPGAN_WARP_*
 
 
+def _warp_planes(what, names, a0, b0, a1=None, b1=None):
+    """The planes of a warp call, `names` = what the caller calls (a0, b0, a1, b1): a0 and b0 are images
+    (_diffaug_geometry) of one batch, rank and device; the second plane's a1 and b1 are both tensors or both None and have
+    the first plane's shapes and device.  Returns (n, a0's spatial extent, b0's spatial extent)."""
+    n, spatial_a = _diffaug_geometry(a0, what)
+    _, spatial_b = _diffaug_geometry(b0, what)
+    if b0.shape[0] != n or len(spatial_b) != len(spatial_a) or b0.device != a0.device:
+        raise ValueError(f"{what}: {names[1]} has shape {tuple(b0.shape)} on {b0.device}, {names[0]} {tuple(a0.shape)} on "
+                         f"{a0.device}")
+    if (a1 is None) != (b1 is None):
+        raise ValueError(f"{what}: {names[2]} and {names[3]} go together")
+    if a1 is not None:
+        _diffaug_geometry(a1, what)
+        _diffaug_geometry(b1, what)
+        if a1.shape != a0.shape or b1.shape != b0.shape or a1.device != a0.device or b1.device != a0.device:
+            raise ValueError(f"{what}: the second plane has shapes {tuple(a1.shape)} / {tuple(b1.shape)}, the first "
+                             f"{tuple(a0.shape)} / {tuple(b0.shape)}")
+    return n, spatial_a, spatial_b
+
+
+def _warp_mode_noise(what, mode, x1, noise0, noise1, sigma):
+    """The forward warps' mode, and their one rule for noise: plane 1's field needs plane 1, sigma needs a field and a
+    field sigma."""
+    if mode not in (WARP_CONSTANT, WARP_BORDER):
+        raise ValueError(f"{what}: unknown mode {mode!r}")
+    if noise1 is not None and x1 is None:
+        raise ValueError(f"{what}: noise1 without a second plane")
+    if (sigma is None) != (noise0 is None and noise1 is None):
+        raise ValueError(f"{what}: sigma goes with a noise field, and a noise field with sigma")
+
+
+def _warp_tables(what, n, y0, theta, sigma, noise0, noise1, gamma=None):
+    """The forward warps' tables, in the order they have always been checked in."""
+    _table(what, "theta", theta, torch.float64, (n, 12), y0.device, required=True)
+    _table(what, "sigma", sigma, torch.float32, (n, 2), y0.device)
+    _table(what, "gamma", gamma, torch.float64, (n, 2), y0.device)
+    _table(what, "noise0", noise0, torch.float32, y0.shape, y0.device)
+    _table(what, "noise1", noise1, torch.float32, y0.shape, y0.device)
+
+
 def affine_warp(x0, x1, theta, mode: int, fill0: float, fill1: float, noise0, noise1, sigma, y0, y1):
     """y_k = the trilinear resampling of x_k at c = A p + t under the per-sample theta (B, 12) float64, plus
     sigma[:, k] * noise_k where plane k has a noise field (include/mpgan_hip.h).  x1 / y1 None: one plane.  The
     outputs may have another spatial extent than the inputs."""
-    n, spatial = _diffaug_geometry(x0, "affine_warp")
-    _, out_spatial = _diffaug_geometry(y0, "affine_warp")
-    if y0.shape[0] != n or len(out_spatial) != len(spatial) or y0.device != x0.device:
-        raise ValueError(f"affine_warp: y0 has shape {tuple(y0.shape)} on {y0.device}, x0 {tuple(x0.shape)} on {x0.device}")
-    if (x1 is None) != (y1 is None):
-        raise ValueError("affine_warp: x1 and y1 go together")
-    if x1 is not None:
-        _diffaug_geometry(x1, "affine_warp")
-        _diffaug_geometry(y1, "affine_warp")
-        if x1.shape != x0.shape or y1.shape != y0.shape or x1.device != x0.device or y1.device != x0.device:
-            raise ValueError(f"affine_warp: the second plane has shapes {tuple(x1.shape)} -> {tuple(y1.shape)}, the first "
-                             f"{tuple(x0.shape)} -> {tuple(y0.shape)}")
-    if mode not in (WARP_CONSTANT, WARP_BORDER):
-        raise ValueError(f"affine_warp: unknown mode {mode!r}")
-    if noise1 is not None and x1 is None:
-        raise ValueError("affine_warp: noise1 without a second plane")
-    if (sigma is None) != (noise0 is None and noise1 is None):
-        raise ValueError("affine_warp: sigma goes with a noise field, and a noise field with sigma")
-    tables = [(theta, torch.float64, (n, 12), "theta"), (sigma, torch.float32, (n, 2), "sigma"),
-              (noise0, torch.float32, tuple(y0.shape), "noise0"), (noise1, torch.float32, tuple(y0.shape), "noise1")]
-    for t, dtype, shape, name in tables:
-        if t is None and name != "theta":
-            continue
-        if t is None or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != x0.device:
-            raise ValueError(f"affine_warp: {name} must be a contiguous {dtype} {shape} tensor on {x0.device}, got "
-                             + (f"{tuple(t.shape)} {t.dtype} on {t.device}" if t is not None else "None"))
+    n, spatial, out_spatial = _warp_planes("affine_warp", ("x0", "y0", "x1", "y1"), x0, y0, x1, y1)
+    _warp_mode_noise("affine_warp", mode, x1, noise0, noise1, sigma)
+    _warp_tables("affine_warp", n, y0, theta, sigma, noise0, noise1)
     check(lib().mpgan_affine_warp(x0.data_ptr(), _ptr(x1), n, _dhw(spatial), _dhw(out_spatial), theta.data_ptr(), int(mode),
                                   float(fill0), float(fill1), _ptr(noise0), _ptr(noise1), _ptr(sigma), y0.data_ptr(),
                                   _ptr(y1), _stream()), "affine_warp")
@@ -1268,18 +1292,10 @@ def affine_warp_backward(gy, theta, mode: int, gx):
     exact adjoint of the WARP_CONSTANT forward, a deterministic gather (include/mpgan_hip.h).  gx has the forward's input
     shape and is overwritten everywhere; a sample whose theta is singular or reaches beyond MPGAN_WARP_REACH_MAX gets
     NaN.  WARP_BORDER has no backward."""
-    n, out_spatial = _diffaug_geometry(gy, "affine_warp_backward")
-    _, spatial = _diffaug_geometry(gx, "affine_warp_backward")
-    if gx.shape[0] != n or len(out_spatial) != len(spatial) or gx.device != gy.device:
-        raise ValueError(f"affine_warp_backward: gx has shape {tuple(gx.shape)} on {gx.device}, gy {tuple(gy.shape)} on "
-                         f"{gy.device}")
+    n, out_spatial, spatial = _warp_planes("affine_warp_backward", ("gy", "gx"), gy, gx)
     if mode != WARP_CONSTANT:
         raise ValueError(f"affine_warp_backward: only WARP_CONSTANT ({WARP_CONSTANT}) has a backward, got mode {mode!r}")
-    if (not isinstance(theta, torch.Tensor) or tuple(theta.shape) != (n, 12) or theta.dtype != torch.float64
-            or not theta.is_contiguous() or theta.device != gy.device):
-        raise ValueError(f"affine_warp_backward: theta must be a contiguous {torch.float64} ({n}, 12) tensor on {gy.device}, "
-                         + (f"got {tuple(theta.shape)} {theta.dtype} on {theta.device}" if isinstance(theta, torch.Tensor)
-                            else f"got {theta!r}"))
+    _table("affine_warp_backward", "theta", theta, torch.float64, (n, 12), gy.device, required=True)
     check(lib().mpgan_affine_warp_backward(gy.data_ptr(), n, _dhw(spatial), _dhw(out_spatial), theta.data_ptr(), int(mode),
                                            gx.data_ptr(), _stream()), "affine_warp_backward")
     return gx
@@ -1300,28 +1316,13 @@ def affine_warp_backward_theta(x0, x1, gy0, gy1, theta, mode: int, fill0: float,
     integer coordinate the derivative is the right-hand one.  gtheta is overwritten (allocated when None); the
     workspace is allocated here.  WARP_BORDER has no gradient in theta."""
     what = "affine_warp_backward_theta"
-    n, spatial = _diffaug_geometry(x0, what)
-    _, out_spatial = _diffaug_geometry(gy0, what)
-    if gy0.shape[0] != n or len(out_spatial) != len(spatial) or gy0.device != x0.device:
-        raise ValueError(f"{what}: gy0 has shape {tuple(gy0.shape)} on {gy0.device}, x0 {tuple(x0.shape)} on {x0.device}")
-    if (x1 is None) != (gy1 is None):
-        raise ValueError(f"{what}: x1 and gy1 go together")
-    if x1 is not None:
-        _diffaug_geometry(x1, what)
-        _diffaug_geometry(gy1, what)
-        if x1.shape != x0.shape or gy1.shape != gy0.shape or x1.device != x0.device or gy1.device != x0.device:
-            raise ValueError(f"{what}: the second plane has shapes {tuple(x1.shape)} / {tuple(gy1.shape)}, the first "
-                             f"{tuple(x0.shape)} / {tuple(gy0.shape)}")
+    n, spatial, out_spatial = _warp_planes(what, ("x0", "gy0", "x1", "gy1"), x0, gy0, x1, gy1)
     if mode != WARP_CONSTANT:
         raise ValueError(f"{what}: only WARP_CONSTANT ({WARP_CONSTANT}) has a gradient in theta, got mode {mode!r}")
     if gtheta is None:
         gtheta = torch.empty((n, 12), dtype=torch.float64, device=x0.device)
-    for t, name in ((theta, "theta"), (gtheta, "gtheta")):
-        if (not isinstance(t, torch.Tensor) or tuple(t.shape) != (n, 12) or t.dtype != torch.float64
-                or not t.is_contiguous() or t.device != x0.device):
-            raise ValueError(f"{what}: {name} must be a contiguous {torch.float64} ({n}, 12) tensor on {x0.device}, "
-                             + (f"got {tuple(t.shape)} {t.dtype} on {t.device}" if isinstance(t, torch.Tensor)
-                                else f"got {t!r}"))
+    _table(what, "theta", theta, torch.float64, (n, 12), x0.device, required=True)
+    _table(what, "gtheta", gtheta, torch.float64, (n, 12), x0.device, required=True)
     ws = torch.empty(affine_warp_theta_workspace(n, out_spatial) // 8, dtype=torch.float64, device=x0.device)
     check(lib().mpgan_affine_warp_backward_theta(x0.data_ptr(), _ptr(x1), gy0.data_ptr(), _ptr(gy1), n, _dhw(spatial),
                                                  _dhw(out_spatial), theta.data_ptr(), int(mode), float(fill0), float(fill1),
@@ -1336,24 +1337,8 @@ def deform_warp(x0, x1, theta, ctrl, gain, gain_planes: int, gamma, lo: float, h
     log-gain lattice gain (B, b_d, b_h, b_w) float64, then v = lo + (hi - lo) * ((v - lo) / (hi - lo)) ** gamma[:, k]
     (gamma (B, 2) float64), then the noise term (include/mpgan_hip.h).  ctrl, gain and gamma may each be None: that
     term is absent.  A 2-D image has lattices with g_d = 1."""
-    n, spatial = _diffaug_geometry(x0, "deform_warp")
-    _, out_spatial = _diffaug_geometry(y0, "deform_warp")
-    if y0.shape[0] != n or len(out_spatial) != len(spatial) or y0.device != x0.device:
-        raise ValueError(f"deform_warp: y0 has shape {tuple(y0.shape)} on {y0.device}, x0 {tuple(x0.shape)} on {x0.device}")
-    if (x1 is None) != (y1 is None):
-        raise ValueError("deform_warp: x1 and y1 go together")
-    if x1 is not None:
-        _diffaug_geometry(x1, "deform_warp")
-        _diffaug_geometry(y1, "deform_warp")
-        if x1.shape != x0.shape or y1.shape != y0.shape or x1.device != x0.device or y1.device != x0.device:
-            raise ValueError(f"deform_warp: the second plane has shapes {tuple(x1.shape)} -> {tuple(y1.shape)}, the first "
-                             f"{tuple(x0.shape)} -> {tuple(y0.shape)}")
-    if mode not in (WARP_CONSTANT, WARP_BORDER):
-        raise ValueError(f"deform_warp: unknown mode {mode!r}")
-    if noise1 is not None and x1 is None:
-        raise ValueError("deform_warp: noise1 without a second plane")
-    if (sigma is None) != (noise0 is None and noise1 is None):
-        raise ValueError("deform_warp: sigma goes with a noise field, and a noise field with sigma")
+    n, spatial, out_spatial = _warp_planes("deform_warp", ("x0", "y0", "x1", "y1"), x0, y0, x1, y1)
+    _warp_mode_noise("deform_warp", mode, x1, noise0, noise1, sigma)
     gain_planes = int(gain_planes)
     if gain_planes & ~3 or (gain is not None and not gain_planes) or (gain_planes & 2 and x1 is None):
         raise ValueError(f"deform_warp: gain_planes {gain_planes:#x} is a mask of the planes given (1 = plane 0, 2 = plane 1), "
@@ -1375,15 +1360,7 @@ def deform_warp(x0, x1, theta, ctrl, gain, gain_planes: int, gamma, lo: float, h
             raise ValueError(f"deform_warp: the {name} lattice {g} over the output extent {out3}: 1 on an axis of extent 1, "
                              "else 4 .. 64")
         grids[name] = g
-    tables = [(theta, torch.float64, (n, 12), "theta"), (sigma, torch.float32, (n, 2), "sigma"),
-              (gamma, torch.float64, (n, 2), "gamma"), (noise0, torch.float32, tuple(y0.shape), "noise0"),
-              (noise1, torch.float32, tuple(y0.shape), "noise1")]
-    for t, dtype, shape, name in tables:
-        if t is None and name != "theta":
-            continue
-        if t is None or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != x0.device:
-            raise ValueError(f"deform_warp: {name} must be a contiguous {dtype} {shape} tensor on {x0.device}, got "
-                             + (f"{tuple(t.shape)} {t.dtype} on {t.device}" if t is not None else "None"))
+    _warp_tables("deform_warp", n, y0, theta, sigma, noise0, noise1, gamma)
     check(lib().mpgan_deform_warp(x0.data_ptr(), _ptr(x1), n, _dhw(spatial), _dhw(out_spatial), theta.data_ptr(),
                                   _ptr(ctrl), _dhw(grids["ctrl"]) if ctrl is not None else None,
                                   _ptr(gain), _dhw(grids["gain"]) if gain is not None else None,
