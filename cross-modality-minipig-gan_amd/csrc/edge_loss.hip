@@ -20,6 +20,7 @@
 // that touches no face of the image runs the gather with the constant interior weights (a block-uniform branch).
 // Rows are staged and stored 16 bytes wide wherever a group of four samples lies inside the row and its address is
 // 16-byte aligned, sample by sample otherwise: any W and any 4-byte-aligned pointer work.
+// The entry points' items / reduction / wrt / upstream_stride / scale / workspace checks are mpgan_common.h's.
 #include "mpgan_common.h"
 
 namespace mpgan {
@@ -339,7 +340,7 @@ extern "C" int mpgan_sobel_magnitude_forward(const float* x, const int32_t* dhw,
   MPGAN_CHECK_ARG(x && out, "sobel_magnitude_forward: null pointer");
   ElGeom g;
   if (int rc = el_geometry("sobel_magnitude_forward", dhw, items, &g)) return rc;
-  MPGAN_CHECK_ARG((float)eps > 0.f && eps - eps == 0.0, "sobel_magnitude_forward: eps must be positive and finite");
+  MPGAN_CHECK_ARG((float)eps > 0.f && is_finite(eps), "sobel_magnitude_forward: eps must be positive and finite");
   ElFwd p;
   p.a = x; p.b = nullptr; p.D = g.D; p.H = g.H; p.W = g.W;
   p.tiles_x = g.tiles_x; p.tiles_y = g.tiles_y; p.tiles = g.tiles;
@@ -359,7 +360,7 @@ extern "C" int mpgan_sobel_magnitude_backward(const float* x, const int32_t* dhw
   MPGAN_CHECK_ARG(x && dy && dx, "sobel_magnitude_backward: null pointer");
   ElGeom g;
   if (int rc = el_geometry("sobel_magnitude_backward", dhw, items, &g)) return rc;
-  MPGAN_CHECK_ARG((float)eps > 0.f && eps - eps == 0.0, "sobel_magnitude_backward: eps must be positive and finite");
+  MPGAN_CHECK_ARG((float)eps > 0.f && is_finite(eps), "sobel_magnitude_backward: eps must be positive and finite");
   ElBwd p;
   p.x = x; p.y = nullptr; p.dy = dy; p.D = g.D; p.H = g.H; p.W = g.W;
   p.tiles_x = g.tiles_x; p.tiles_y = g.tiles_y;
@@ -384,15 +385,14 @@ extern "C" int64_t mpgan_edge_loss_workspace(const int32_t* dhw, int32_t items) 
 extern "C" int mpgan_edge_loss_forward(const float* a, const float* b, const int32_t* dhw, int32_t items,
                                        int32_t channels, double eps, void* workspace, int64_t workspace_bytes,
                                        int32_t reduction, float* loss, void* stream) {
-  MPGAN_CHECK_ARG(a && b && workspace && loss, "edge_loss_forward: null pointer");
+  MPGAN_CHECK_ARG(a && b && loss, "edge_loss_forward: null pointer");
   ElGeom g;
   if (int rc = el_geometry("edge_loss_forward", dhw, items, &g)) return rc;
-  MPGAN_CHECK_ARG(channels >= 1 && items % channels == 0, "edge_loss_forward: %d items are no multiple of %d channels",
-                  items, channels);
-  MPGAN_CHECK_ARG((float)eps > 0.f && eps - eps == 0.0, "edge_loss_forward: eps must be positive and finite");
-  MPGAN_CHECK_ARG(reduction >= 0 && reduction <= 2, "edge_loss_forward: unknown reduction %d", reduction);
-  MPGAN_CHECK_ARG(workspace_bytes >= mpgan_edge_loss_workspace(dhw, items), "edge_loss_forward: workspace too small");
-  MPGAN_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "edge_loss_forward: workspace must be 8-byte aligned");
+  if (int rc = check_items("edge_loss_forward", items, channels)) return rc;
+  MPGAN_CHECK_ARG((float)eps > 0.f && is_finite(eps), "edge_loss_forward: eps must be positive and finite");
+  if (int rc = check_reduction("edge_loss_forward", reduction)) return rc;
+  if (int rc = check_workspace("edge_loss_forward", workspace, workspace_bytes, mpgan_edge_loss_workspace(dhw, items)))
+    return rc;
   ElFwd p;
   p.a = a; p.b = b; p.D = g.D; p.H = g.H; p.W = g.W;
   p.tiles_x = g.tiles_x; p.tiles_y = g.tiles_y; p.tiles = g.tiles;
@@ -416,13 +416,11 @@ extern "C" int mpgan_edge_loss_backward(const float* a, const float* b, const in
   MPGAN_CHECK_ARG(a && b && upstream && grad, "edge_loss_backward: null pointer");
   ElGeom g;
   if (int rc = el_geometry("edge_loss_backward", dhw, items, &g)) return rc;
-  MPGAN_CHECK_ARG(channels >= 1 && items % channels == 0, "edge_loss_backward: %d items are no multiple of %d channels",
-                  items, channels);
-  MPGAN_CHECK_ARG((float)eps > 0.f && eps - eps == 0.0, "edge_loss_backward: eps must be positive and finite");
-  MPGAN_CHECK_ARG(wrt == 0 || wrt == 1, "edge_loss_backward: wrt %d is neither 0 (a) nor 1 (b)", wrt);
-  MPGAN_CHECK_ARG(upstream_stride == 0 || upstream_stride == 1, "edge_loss_backward: upstream_stride %d not 0 or 1",
-                  upstream_stride);
-  MPGAN_CHECK_ARG(scale - scale == 0.0, "edge_loss_backward: non-finite scale");
+  if (int rc = check_items("edge_loss_backward", items, channels)) return rc;
+  MPGAN_CHECK_ARG((float)eps > 0.f && is_finite(eps), "edge_loss_backward: eps must be positive and finite");
+  if (int rc = check_wrt("edge_loss_backward", wrt)) return rc;
+  if (int rc = check_upstream_stride("edge_loss_backward", upstream_stride)) return rc;
+  if (int rc = check_scale("edge_loss_backward", scale)) return rc;
   ElBwd p;
   p.x = wrt == 0 ? a : b;                       // -sign(m(a) - m(b)) = sign(m(b) - m(a)): one form for both
   p.y = wrt == 0 ? b : a;

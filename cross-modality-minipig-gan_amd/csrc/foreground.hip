@@ -1,7 +1,7 @@
 // Foreground masks (include/mpgan_hip.h: "foreground masks" states every definition):
 //
-//   fg_hist_kernel            an item's histogram: a block counts its chunk into 256 LDS counters (integer atomics, a
-//                             crowded counter taken by one lane for the wave) and flushes the non-zero ones with 64-bit
+//   fg_hist_kernel            an item's histogram: a block counts its chunk into 256 LDS counters (image_stats.h: the
+//                             joint histogram's bin rule and wave peel) and flushes the non-zero ones with 64-bit
 //                             integer atomics.
 //   fg_otsu_kernel            Otsu's method over an item's <= 256 counts, one block, in the order the header states.
 //   fg_mask_kernel            mask / count / raw box extremes in one pass: per-thread minima and maxima, folded over
@@ -13,37 +13,19 @@
 //   fg_l1_backward_kernel     da and/or db, one factor per item and weight.
 //   fg_err_kernel / fg_err_final_kernel   masked MAE / MSE / PSNR / count.
 //
-// fg_chunks is the ONE place the grid of every stream is decided, fg_load4 / fg_mask4 the one place a group of four
-// values is read: a thread's values and their order do not depend on the pointers' alignment.
+// fg_chunks (image_stats.h's planner with this file's constants) is the ONE place the grid of every stream is decided,
+// fg_load4 / fg_mask4 the one place a group of four values is read: a thread's values and their order do not depend on
+// the pointers' alignment.
 #include <limits.h>
-#include "mpgan_common.h"
+#include "image_stats.h"
 
 namespace mpgan {
 
 constexpr long FG_CHUNK_MIN = 4096;             // values a block walks at least: four groups per thread
-constexpr long FG_CHUNK_MAX = 1L << 30;         // ... and at most: a block's uint32 counters cannot overflow
 constexpr int FG_TARGET_BLOCKS = 2048;          // eight 4-wave blocks per CU
 constexpr int FG_PEEL_ROUNDS = 2;
 
-struct FgChunks {
-  long chunks, per_chunk;                       // per item; per_chunk is a multiple of 4
-};
-
-static FgChunks fg_chunks(long n, long items) {
-  long cap = FG_TARGET_BLOCKS / items;
-  if (cap < 1) cap = 1;
-  long chunks = (n + FG_CHUNK_MIN - 1) / FG_CHUNK_MIN;
-  if (chunks > cap) chunks = cap;
-  const long floor_chunks = (n + FG_CHUNK_MAX - 1) / FG_CHUNK_MAX;
-  if (chunks < floor_chunks) chunks = floor_chunks;
-  if (chunks < 1) chunks = 1;
-  FgChunks c;
-  c.chunks = chunks;
-  c.per_chunk = (((n + chunks - 1) / chunks) + 3) & ~3L;
-  return c;
-}
-
-static bool fg_finite(double v) { return v - v == 0.0; }
+static StreamChunks fg_chunks(long n, long items) { return stream_chunks(n, items, FG_CHUNK_MIN, FG_TARGET_BLOCKS); }
 
 // The block's chunk of an item: first value c0, len values (0 when the rounding of per_chunk left none).
 struct FgSpan {
@@ -106,24 +88,6 @@ struct FgHist {
   unsigned long long* hist;                     // [items][bins]
 };
 
-// One value per lane, called by every lane of the wave (the scheme of metric_ops.hip's joint histogram): up to
-// FG_PEEL_ROUNDS times the leading pending lane adds the number of lanes that share its counter in ONE LDS atomic --
-// the background of an MRI volume is one bin -- and the lanes still pending after that issue their own.
-__device__ __forceinline__ void fg_submit(unsigned* lh, bool pend, unsigned key) {
-#pragma unroll
-  for (int r = 0; r < FG_PEEL_ROUNDS; ++r) {
-    const unsigned long long act = __ballot(pend);
-    if (act == 0ull) return;
-    const int leader = __ffsll((long long)act) - 1;
-    const unsigned lk = (unsigned)__shfl((int)key, leader, 64);
-    const bool same = pend && key == lk;
-    const unsigned long long m = __ballot(same);
-    if ((int)(threadIdx.x & 63) == leader) atomicAdd(&lh[lk], (unsigned)__popcll(m));
-    pend = pend && !same;
-  }
-  if (pend) atomicAdd(&lh[key], 1u);
-}
-
 __global__ __launch_bounds__(256) void fg_hist_kernel(FgHist p) {
   __shared__ unsigned lh[256];
   const int tid = threadIdx.x;
@@ -132,7 +96,7 @@ __global__ __launch_bounds__(256) void fg_hist_kernel(FgHist p) {
   const FgSpan sp = fg_span(p.n, p.chunks, p.per_chunk);
   const float* x = p.x + sp.item * p.n + sp.c0;
   const bool vec = fg_aligned(x, 16);
-  // block-uniform trip count: fg_submit needs every lane of a wave
+  // block-uniform trip count: hist_submit needs every lane of a wave
   for (long g0 = 0; 4 * g0 < sp.len; g0 += 256) {
     const long e = 4 * (g0 + tid);
     float v[4] = {0.f, 0.f, 0.f, 0.f};
@@ -140,12 +104,8 @@ __global__ __launch_bounds__(256) void fg_hist_kernel(FgHist p) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const bool ok = k < cnt && v[k] >= p.lo && v[k] <= p.hi;   // NaN fails both comparisons
-      int j = 0;
-      if (ok) {
-        j = (int)floorf(__fmul_rn(__fsub_rn(v[k], p.lo), p.s));
-        j = j < p.bins - 1 ? j : p.bins - 1;
-      }
-      fg_submit(lh, ok, (unsigned)j);
+      const int j = ok ? hist_bin(v[k], p.lo, p.s, p.bins) : 0;
+      hist_submit<FG_PEEL_ROUNDS>(lh, ok, (unsigned)j);
     }
   }
   __syncthreads();
@@ -532,15 +492,14 @@ __global__ __launch_bounds__(256) void fg_err_final_kernel(const double* __restr
 
 // The checks the two masked-L1 entry points share.  Status as the entry points return it.
 static int fg_l1_args(const char* who, const float* a, const float* b, int64_t n, int32_t items, int32_t channels,
-                      const uint8_t* mask, const float* thr, double w_fg, double w_bg, FgChunks* c) {
+                      const uint8_t* mask, const float* thr, double w_fg, double w_bg, StreamChunks* c) {
   MPGAN_CHECK_ARG(a && b, "%s: null input", who);
   MPGAN_CHECK_ARG(items >= 1, "%s: items %d < 1", who, items);
   MPGAN_CHECK_ARG(n >= 1, "%s: numel_per_item %ld < 1", who, (long)n);
-  MPGAN_CHECK_ARG(channels >= 1 && items % channels == 0, "%s: %d items are no multiple of %d channels", who, items,
-                  channels);
+  if (int rc = check_items(who, items, channels)) return rc;
   MPGAN_CHECK_ARG((mask != nullptr) != (thr != nullptr), "%s: exactly one of mask and thr must be given (got %s)", who,
                   mask ? "both" : "neither");
-  MPGAN_CHECK_ARG(fg_finite(w_fg) && fg_finite(w_bg) && w_fg >= 0.0 && w_bg >= 0.0,
+  MPGAN_CHECK_ARG(is_finite(w_fg) && is_finite(w_bg) && w_fg >= 0.0 && w_bg >= 0.0,
                   "%s: weights must be finite and >= 0", who);
   *c = fg_chunks(n, items);
   MPGAN_CHECK_ARG(c->chunks * (long)items < (1L << 31), "%s: too many blocks", who);
@@ -562,13 +521,10 @@ extern "C" int mpgan_otsu_threshold(const float* x, int64_t numel_per_item, int3
   MPGAN_CHECK_ARG(bins >= 2 && bins <= 256, "otsu_threshold: bins %d outside [2, 256]", bins);
   MPGAN_CHECK_ARG(items >= 1, "otsu_threshold: items %d < 1", items);
   MPGAN_CHECK_ARG(numel_per_item >= 1, "otsu_threshold: numel_per_item %ld < 1", (long)numel_per_item);
-  const float span = hi - lo;
-  MPGAN_CHECK_ARG(fg_finite(lo) && fg_finite(hi) && fg_finite(span), "otsu_threshold: non-finite value range");
-  MPGAN_CHECK_ARG(hi > lo, "otsu_threshold: value range needs hi > lo");
-  const float s = (float)bins / span;
-  MPGAN_CHECK_ARG(fg_finite(s), "otsu_threshold: value range too narrow for fp32 binning");
+  float s;
+  if (int rc = check_bin_range("otsu_threshold", lo, hi, bins, &s)) return rc;
   MPGAN_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "otsu_threshold: workspace must be 8-byte aligned");
-  const FgChunks c = fg_chunks(numel_per_item, items);
+  const StreamChunks c = fg_chunks(numel_per_item, items);
   MPGAN_CHECK_ARG(c.chunks * (long)items < (1L << 31), "otsu_threshold: too many blocks");
   hipStream_t st = (hipStream_t)stream;
   hipError_t e = hipMemsetAsync(workspace, 0, (size_t)mpgan_otsu_workspace(items, bins), st);
@@ -597,7 +553,7 @@ extern "C" int mpgan_foreground_mask(const float* x, const int32_t* dhw, int32_t
       mg[d] = margin[d];
     }
   const long n = (long)dhw[0] * dhw[1] * dhw[2];
-  const FgChunks c = fg_chunks(n, items);
+  const StreamChunks c = fg_chunks(n, items);
   MPGAN_CHECK_ARG(c.chunks * (long)items < (1L << 31), "foreground_mask: too many blocks");
   FgMask p;
   p.x = x; p.thr = thr; p.n = n; p.chunks = c.chunks; p.per_chunk = c.per_chunk;
@@ -620,7 +576,7 @@ extern "C" int mpgan_foreground_mask(const float* x, const int32_t* dhw, int32_t
 
 extern "C" int64_t mpgan_masked_l1_workspace(int64_t numel_per_item, int32_t items) {
   if (numel_per_item < 1 || items < 1) return -1;
-  const FgChunks c = fg_chunks(numel_per_item, items);
+  const StreamChunks c = fg_chunks(numel_per_item, items);
   return (2 * c.chunks * (int64_t)items + items) * (int64_t)sizeof(double);
 }
 
@@ -628,15 +584,15 @@ extern "C" int mpgan_masked_l1_forward(const float* a, const float* b, int64_t n
                                        int32_t channels, const uint8_t* mask, const float* thr, double w_fg,
                                        double w_bg, void* workspace, int64_t workspace_bytes, double* den,
                                        int32_t reduction, float* loss, void* stream) {
-  FgChunks c;
+  StreamChunks c;
   if (int rc = fg_l1_args("masked_l1_forward", a, b, numel_per_item, items, channels, mask, thr, w_fg, w_bg, &c))
     return rc;
-  MPGAN_CHECK_ARG(workspace && den && loss, "masked_l1_forward: null pointer");
-  MPGAN_CHECK_ARG(reduction >= 0 && reduction <= 2, "masked_l1_forward: unknown reduction %d", reduction);
-  MPGAN_CHECK_ARG(workspace_bytes >= mpgan_masked_l1_workspace(numel_per_item, items),
-                  "masked_l1_forward: workspace too small");
-  MPGAN_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0 && (reinterpret_cast<uintptr_t>(den) & 7) == 0,
-                  "masked_l1_forward: workspace and den must be 8-byte aligned");
+  MPGAN_CHECK_ARG(den && loss, "masked_l1_forward: null pointer");
+  if (int rc = check_reduction("masked_l1_forward", reduction)) return rc;
+  if (int rc = check_workspace("masked_l1_forward", workspace, workspace_bytes,
+                               mpgan_masked_l1_workspace(numel_per_item, items)))
+    return rc;
+  MPGAN_CHECK_ARG((reinterpret_cast<uintptr_t>(den) & 7) == 0, "masked_l1_forward: den must be 8-byte aligned");
   FgL1 p;
   p.a = a; p.b = b; p.mask = mask; p.thr = thr;
   p.n = numel_per_item; p.chunks = c.chunks; p.per_chunk = c.per_chunk;
@@ -662,14 +618,13 @@ extern "C" int mpgan_masked_l1_backward(const float* a, const float* b, int64_t 
                                         int32_t channels, const uint8_t* mask, const float* thr, double w_fg,
                                         double w_bg, const double* den, const float* upstream,
                                         int32_t upstream_stride, double scale, float* da, float* db, void* stream) {
-  FgChunks c;
+  StreamChunks c;
   if (int rc = fg_l1_args("masked_l1_backward", a, b, numel_per_item, items, channels, mask, thr, w_fg, w_bg, &c))
     return rc;
   MPGAN_CHECK_ARG(den && upstream, "masked_l1_backward: null pointer");
   MPGAN_CHECK_ARG(da || db, "masked_l1_backward: no gradient asked for");
-  MPGAN_CHECK_ARG(upstream_stride == 0 || upstream_stride == 1, "masked_l1_backward: upstream_stride %d not 0 or 1",
-                  upstream_stride);
-  MPGAN_CHECK_ARG(fg_finite(scale), "masked_l1_backward: non-finite scale");
+  if (int rc = check_upstream_stride("masked_l1_backward", upstream_stride)) return rc;
+  if (int rc = check_scale("masked_l1_backward", scale)) return rc;
   FgL1 p;
   p.a = a; p.b = b; p.mask = mask; p.thr = thr;
   p.n = numel_per_item; p.chunks = c.chunks; p.per_chunk = c.per_chunk;
@@ -697,7 +652,7 @@ extern "C" int mpgan_masked_image_errors(const float* a, const float* b, const u
   MPGAN_CHECK_ARG(numel >= 1, "masked_image_errors: numel %ld < 1", (long)numel);
   MPGAN_CHECK_ARG((reinterpret_cast<uintptr_t>(partials) & 7) == 0 && (reinterpret_cast<uintptr_t>(out4) & 7) == 0,
                   "masked_image_errors: partials and out4 must be 8-byte aligned");
-  const FgChunks c = fg_chunks(numel, 1);
+  const StreamChunks c = fg_chunks(numel, 1);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(fg_err_kernel, dim3((unsigned)c.chunks), dim3(256), 0, st, a, b, mask, (long)numel, c.chunks,
                      c.per_chunk, partials);

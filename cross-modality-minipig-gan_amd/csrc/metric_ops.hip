@@ -1,9 +1,11 @@
 // Evaluation metrics of the reference's offline scripts, on the device:
 //   inferrence.py:188-204  rescale a volume to 0..255 (ScaleIntensityRangePercentiles 0/100 ==
 //                          min/max), round, then MAE against the ground truth;
-//   metrics.py:213-223, psnr_ssim_metric.py:88-106  MSE, PSNR and SSIM with data_range = 256.
-// HBM-bound two-stage reductions (fixed order, no atomics).
-#include "mpgan_common.h"
+//   metrics.py:213-223, psnr_ssim_metric.py:88-106  MSE and PSNR with data_range = 256 (SSIM: ssim_loss.hip, whose
+//                          forward kernel serves the metric and the loss).
+// HBM-bound two-stage reductions (fixed order, no atomics).  The joint histogram's bin rule, wave peel, chunk planner
+// and value-range refusals are image_stats.h's, shared with Otsu's histogram (foreground.hip).
+#include "image_stats.h"
 
 namespace mpgan {
 
@@ -94,88 +96,6 @@ __global__ __launch_bounds__(64) void err_final_kernel(const float* __restrict__
     out3[1] = (float)mse;
     out3[2] = mse > 0.0 ? (float)(10.0 * log10((double)data_range * data_range / mse)) : INFINITY;
   }
-}
-
-// ---- SSIM (skimage.metrics.structural_similarity as psnr_ssim_metric.py:91-92 calls it) -------
-// 7-wide uniform window (7x7 for a slice, 7x7x7 for a volume), K1 = 0.01, K2 = 0.03, sample
-// covariance (NP/(NP-1)), mean of S over the interior that excludes the 3 border samples per
-// windowed axis.  A block stages the (TZ+WZ-1) x 14 x 38 input region of both images in LDS;
-// a thread owns one (y, x) column of the 8 x 32 tile: it forms the 7x7 plane sums of
-// (a, b, a^2, b^2, ab) for every staged z once (double precision: sums of 343 products of
-// 0..255 values would cost fp32 its variance digits) and slides the z window over them.
-constexpr int SS_W = 7, SS_TY = 8, SS_TX = 32, SS_RY = SS_TY + SS_W - 1, SS_RX = SS_TX + SS_W - 1;
-
-template <int WZ, int TZ>
-__global__ __launch_bounds__(256) void ssim_partial_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                           int D, int H, int W, int tiles_x, int tiles_y,
-                                                           double c1, double c2, double* __restrict__ partials) {
-  constexpr int RZ = TZ + WZ - 1;
-  extern __shared__ float sm[];                 // [2][RZ][SS_RY][SS_RX]
-  float* sa = sm;
-  float* sb = sm + RZ * SS_RY * SS_RX;
-  const int tid = threadIdx.x;
-  const int bx = blockIdx.x % tiles_x;
-  const int by = (blockIdx.x / tiles_x) % tiles_y;
-  const int bz = blockIdx.x / (tiles_x * tiles_y);
-  const int z0 = bz * TZ, y0 = by * SS_TY, x0 = bx * SS_TX;   // origin of the tile = first window corner
-  for (int i = tid; i < RZ * SS_RY * SS_RX; i += 256) {
-    const int rx = i % SS_RX, ry = (i / SS_RX) % SS_RY, rz = i / (SS_RX * SS_RY);
-    const int z = z0 + rz, y = y0 + ry, x = x0 + rx;
-    const bool ok = z < D && y < H && x < W;
-    const long off = ((long)z * H + y) * W + x;
-    sa[i] = ok ? a[off] : 0.f;
-    sb[i] = ok ? b[off] : 0.f;
-  }
-  __syncthreads();
-  const int tx = tid % SS_TX, ty = tid / SS_TX;
-  const int OD = D - WZ + 1, OH = H - SS_W + 1, OW = W - SS_W + 1;   // outputs = window corners
-  double pa[RZ], pb[RZ], paa[RZ], pbb[RZ], pab[RZ];
-#pragma unroll
-  for (int rz = 0; rz < RZ; ++rz) {
-    double s_a = 0, s_b = 0, s_aa = 0, s_bb = 0, s_ab = 0;
-    for (int dy = 0; dy < SS_W; ++dy) {
-      const float* ra = sa + (rz * SS_RY + ty + dy) * SS_RX + tx;
-      const float* rb = sb + (rz * SS_RY + ty + dy) * SS_RX + tx;
-#pragma unroll
-      for (int dx = 0; dx < SS_W; ++dx) {
-        const double u = (double)ra[dx], v = (double)rb[dx];
-        s_a += u; s_b += v;
-        s_aa = fma(u, u, s_aa); s_bb = fma(v, v, s_bb); s_ab = fma(u, v, s_ab);
-      }
-    }
-    pa[rz] = s_a; pb[rz] = s_b; paa[rz] = s_aa; pbb[rz] = s_bb; pab[rz] = s_ab;
-  }
-  constexpr double NP = (double)(WZ * SS_W * SS_W);
-  constexpr double cov_norm = NP / (NP - 1.0);
-  double local = 0.0;
-#pragma unroll
-  for (int zo = 0; zo < TZ; ++zo) {
-    if (z0 + zo >= OD || y0 + ty >= OH || x0 + tx >= OW) continue;
-    double s_a = 0, s_b = 0, s_aa = 0, s_bb = 0, s_ab = 0;
-#pragma unroll
-    for (int dz = 0; dz < WZ; ++dz) {
-      s_a += pa[zo + dz]; s_b += pb[zo + dz]; s_aa += paa[zo + dz]; s_bb += pbb[zo + dz]; s_ab += pab[zo + dz];
-    }
-    const double ux = s_a / NP, uy = s_b / NP;
-    const double vx = cov_norm * (s_aa / NP - ux * ux), vy = cov_norm * (s_bb / NP - uy * uy);
-    const double vxy = cov_norm * (s_ab / NP - ux * uy);
-    const double A1 = 2.0 * ux * uy + c1, A2 = 2.0 * vxy + c2;
-    const double B1 = ux * ux + uy * uy + c1, B2 = vx + vy + c2;
-    local += (A1 * A2) / (B1 * B2);
-  }
-  // block sum in a fixed order
-  __shared__ double red[256];
-  local = block_tree_sum<256>(local, red);
-  if (tid == 0) partials[blockIdx.x] = local;
-}
-
-__global__ __launch_bounds__(256) void ssim_final_kernel(const double* __restrict__ partials, int nb, double inv_count,
-                                                         float* __restrict__ out1) {
-  __shared__ double red[256];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < nb; i += 256) s += partials[i];
-  s = block_tree_sum<256>(s, red);
-  if (threadIdx.x == 0) out1[0] = (float)(s * inv_count);
 }
 
 // ---- np.percentile on the device (ScaleIntensityRangePercentilesd, GAN_final.py:386-394) --------
@@ -290,52 +210,9 @@ __global__ __launch_bounds__(256) void scale_range_kernel(const float* __restric
   }
 }
 
-constexpr int SS_TZ3 = 4;
-
-static long ssim_blocks(const int32_t* dhw, bool vol) {
-  const int OD = vol ? dhw[0] - SS_W + 1 : dhw[0], OH = dhw[1] - SS_W + 1, OW = dhw[2] - SS_W + 1;
-  const long tz = vol ? (OD + SS_TZ3 - 1) / SS_TZ3 : OD;
-  return tz * ((OH + SS_TY - 1) / SS_TY) * ((OW + SS_TX - 1) / SS_TX);
-}
-
 }  // namespace mpgan
 
 using namespace mpgan;
-
-extern "C" int64_t mpgan_ssim_workspace(const int32_t* dhw) {
-  if (!dhw || dhw[1] < SS_W || dhw[2] < SS_W || dhw[0] < 1) return -1;
-  const bool vol = dhw[0] >= SS_W;
-  return ssim_blocks(dhw, vol) * (int64_t)sizeof(double);
-}
-
-extern "C" int mpgan_ssim(const float* a, const float* b, const int32_t* dhw, float data_range, void* workspace,
-                          int64_t workspace_bytes, float* out1, void* stream) {
-  MPGAN_CHECK_ARG(a && b && dhw && workspace && out1, "ssim: null pointer");
-  MPGAN_CHECK_ARG(dhw[1] >= SS_W && dhw[2] >= SS_W && dhw[0] >= 1, "ssim: extents below the 7-wide window");
-  MPGAN_UNSUPPORTED(dhw[0] > 1 && dhw[0] < SS_W, "ssim: depth %d is neither a slice (1) nor >= 7", dhw[0]);
-  const bool vol = dhw[0] >= SS_W;
-  const long blocks = ssim_blocks(dhw, vol);
-  MPGAN_CHECK_ARG(workspace_bytes >= blocks * (int64_t)sizeof(double), "ssim: workspace too small");
-  MPGAN_CHECK_ARG(blocks < (1L << 31), "ssim: too many tiles");
-  const int OD = vol ? dhw[0] - SS_W + 1 : dhw[0], OH = dhw[1] - SS_W + 1, OW = dhw[2] - SS_W + 1;
-  const int tiles_x = (OW + SS_TX - 1) / SS_TX, tiles_y = (OH + SS_TY - 1) / SS_TY;
-  const double c1 = (0.01 * (double)data_range) * (0.01 * (double)data_range);
-  const double c2 = (0.03 * (double)data_range) * (0.03 * (double)data_range);
-  double* part = static_cast<double*>(workspace);
-  hipStream_t st = (hipStream_t)stream;
-  if (vol) {
-    const size_t smem = 2ul * (SS_TZ3 + SS_W - 1) * SS_RY * SS_RX * sizeof(float);
-    hipLaunchKernelGGL((ssim_partial_kernel<SS_W, SS_TZ3>), dim3((unsigned)blocks), dim3(256), smem, st, a, b, dhw[0],
-                       dhw[1], dhw[2], tiles_x, tiles_y, c1, c2, part);
-  } else {
-    const size_t smem = 2ul * SS_RY * SS_RX * sizeof(float);
-    hipLaunchKernelGGL((ssim_partial_kernel<1, 1>), dim3((unsigned)blocks), dim3(256), smem, st, a, b, dhw[0], dhw[1],
-                       dhw[2], tiles_x, tiles_y, c1, c2, part);
-  }
-  hipLaunchKernelGGL(ssim_final_kernel, dim3(1), dim3(256), 0, st, part, (int)blocks,
-                     1.0 / ((double)OD * OH * OW), out1);
-  return check_launch("ssim");
-}
 
 extern "C" int32_t mpgan_metric_partials(void) { return 2 * MET_BLOCKS; }
 
@@ -512,9 +389,8 @@ extern "C" int mpgan_resample_to_identity_grid(const float* vol, const int32_t* 
 // ---------------------------------------------------------------------------------------------------
 // Joint histogram and mutual information (the reference's third stored quality figure).
 //   hist[item][ia][ib] = number of admitted voxels whose a-value falls into bin ia and b-value into bin ib, with
-//   idx = min((int)floorf((v - lo) * s), bins - 1), s = (float)bins / (hi - lo), all in fp32 as written (s is
-//   formed on the host; the device subtracts and multiplies with explicit round-to-nearest operations, so no
-//   contraction can change a bin).  A voxel outside either range, NaN, or refused by the mask is dropped.
+//   idx = hist_bin(v) = min((int)floorf((v - lo) * s), bins - 1), s = (float)bins / (hi - lo), all in fp32 as
+//   written (image_stats.h).  A voxel outside either range, NaN, or refused by the mask is dropped.
 // A block privatises a band of a-rows in LDS as uint32 counters (LDS integer atomics), walks its chunk of the
 // voxels, and flushes its non-zero counters once with 64-bit integer atomics: consecutive lanes flush consecutive
 // counters, so the global atomics are contiguous 512-byte wave-instructions instead of one scattered atomic per
@@ -525,10 +401,8 @@ namespace mpgan {
 constexpr int JH_THREADS = 1024;
 constexpr int JH_LDS_COUNTERS = 16384;          // 64 KB of uint32: two blocks share a CU's 160 KB
 constexpr long JH_CHUNK_MIN = 16384;            // voxels a block walks at least (its zero + flush pass is 16 K counters)
-constexpr long JH_CHUNK_MAX = 1L << 30;         // ... and at most: a uint32 counter cannot overflow
 constexpr int JH_TARGET_BLOCKS = 512;           // two 16-wave blocks per CU
 constexpr int JH_PEEL_ROUNDS = 4;
-
 enum { JH_MASK_NONE = 0, JH_MASK_BOTH_NONZERO = 1, JH_MASK_EITHER_NONZERO = 2, JH_MASK_EXPLICIT = 3 };
 
 // The ONE place the form of a joint-histogram launch is decided: how many a-rows a block keeps in LDS (all of them
@@ -539,21 +413,13 @@ struct JhChoice {
   long chunks, per_chunk;                       // per_chunk is a multiple of 4: every chunk starts float4-aligned
 };
 
-static bool jh_finite(float v) { return v - v == 0.f; }   // false for NaN and the infinities
-
 static JhChoice choose_joint_hist(int bins, long n, int batch) {
   JhChoice c;
   c.band_rows = bins * bins <= JH_LDS_COUNTERS ? bins : JH_LDS_COUNTERS / bins;
   c.bands = (bins + c.band_rows - 1) / c.band_rows;
-  long cap = JH_TARGET_BLOCKS / ((long)batch * c.bands);
-  if (cap < 1) cap = 1;
-  long chunks = (n + JH_CHUNK_MIN - 1) / JH_CHUNK_MIN;
-  if (chunks > cap) chunks = cap;
-  const long floor_chunks = (n + JH_CHUNK_MAX - 1) / JH_CHUNK_MAX;
-  if (chunks < floor_chunks) chunks = floor_chunks;
-  if (chunks < 1) chunks = 1;
-  c.chunks = chunks;
-  c.per_chunk = (((n + chunks - 1) / chunks) + 3) & ~3L;
+  const StreamChunks sc = stream_chunks(n, (long)batch * c.bands, JH_CHUNK_MIN, JH_TARGET_BLOCKS);
+  c.chunks = sc.chunks;
+  c.per_chunk = sc.per_chunk;
   return c;
 }
 
@@ -568,30 +434,6 @@ struct JhParams {
   unsigned long long* hist;
 };
 
-__device__ __forceinline__ int jh_bin(float v, float lo, float s, int bins) {
-  const int i = (int)floorf(__fmul_rn(__fsub_rn(v, lo), s));
-  return i < bins - 1 ? i : bins - 1;
-}
-
-// One voxel per lane, called by every lane of the wave (pend = this lane has a counter to bump).  A wave whose lanes
-// crowd one counter (the background bin of an MRI pair, a constant image) would serialise on an LDS atomic: up to
-// JH_PEEL_ROUNDS times, the leading pending lane adds the number of lanes that share its counter in ONE atomic and
-// all of them retire; lanes still pending after that issue their own.
-__device__ __forceinline__ void jh_submit(unsigned* lh, bool pend, unsigned key) {
-#pragma unroll
-  for (int r = 0; r < JH_PEEL_ROUNDS; ++r) {
-    const unsigned long long act = __ballot(pend);
-    if (act == 0ull) return;
-    const int leader = __ffsll((long long)act) - 1;
-    const unsigned lk = (unsigned)__shfl((int)key, leader, 64);
-    const bool same = pend && key == lk;
-    const unsigned long long m = __ballot(same);
-    if ((int)(threadIdx.x & 63) == leader) atomicAdd(&lh[lk], (unsigned)__popcll(m));
-    pend = pend && !same;
-  }
-  if (pend) atomicAdd(&lh[key], 1u);
-}
-
 __device__ __forceinline__ void jh_voxel(unsigned* lh, const JhParams& p, int r0, int r1, bool valid, float va, float vb,
                                          unsigned mk) {
   bool ok = valid && va >= p.lo_a && va <= p.hi_a && vb >= p.lo_b && vb <= p.hi_b;   // NaN fails every comparison
@@ -600,11 +442,11 @@ __device__ __forceinline__ void jh_voxel(unsigned* lh, const JhParams& p, int r0
   else if (p.mask_mode == JH_MASK_EXPLICIT) ok = ok && mk != 0u;
   unsigned key = 0;
   if (ok) {
-    const int ia = jh_bin(va, p.lo_a, p.s_a, p.bins), ib = jh_bin(vb, p.lo_b, p.s_b, p.bins);
+    const int ia = hist_bin(va, p.lo_a, p.s_a, p.bins), ib = hist_bin(vb, p.lo_b, p.s_b, p.bins);
     ok = ia >= r0 && ia < r1;
     key = (unsigned)((ia - r0) * p.bins + ib);
   }
-  jh_submit(lh, ok, ok ? key : 0u);
+  hist_submit<JH_PEEL_ROUNDS>(lh, ok, ok ? key : 0u);
 }
 
 __global__ __launch_bounds__(JH_THREADS) void joint_hist_kernel(JhParams p) {
@@ -629,7 +471,7 @@ __global__ __launch_bounds__(JH_THREADS) void joint_hist_kernel(JhParams p) {
     const uint8_t* mk = p.mask_mode == JH_MASK_EXPLICIT ? p.mask + item * p.n : nullptr;
     const long len = c1 - c0;
     // 16-byte loads when both item bases are 16-byte aligned (c0 is a multiple of 4); the scalar loop takes every
-    // other alignment and the tail.  Trip counts are block-uniform: jh_submit needs every lane of a wave.
+    // other alignment and the tail.  Trip counts are block-uniform: hist_submit needs every lane of a wave.
     const bool vec = ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15u) == 0;
     const long nvec = vec ? len >> 2 : 0;
     for (long j0 = 0; j0 < nvec; j0 += JH_THREADS) {
@@ -749,13 +591,9 @@ extern "C" int mpgan_joint_histogram(const float* a, const float* b, const uint8
   MPGAN_CHECK_ARG((a && b) || numel_per_item == 0, "joint_histogram: null input");
   MPGAN_CHECK_ARG(mask || mask_mode != JH_MASK_EXPLICIT || numel_per_item == 0,
                   "joint_histogram: mask_mode 3 needs a mask array");
-  const float span_a = hi_a - lo_a, span_b = hi_b - lo_b;
-  MPGAN_CHECK_ARG(jh_finite(lo_a) && jh_finite(hi_a) && jh_finite(lo_b) && jh_finite(hi_b) && jh_finite(span_a) &&
-                      jh_finite(span_b),
-                  "joint_histogram: non-finite value range");
-  MPGAN_CHECK_ARG(hi_a > lo_a && hi_b > lo_b, "joint_histogram: value range needs hi > lo");
-  const float s_a = (float)bins / span_a, s_b = (float)bins / span_b;
-  MPGAN_CHECK_ARG(jh_finite(s_a) && jh_finite(s_b), "joint_histogram: value range too narrow for fp32 binning");
+  float s_a, s_b;
+  if (int rc = check_bin_range("joint_histogram", lo_a, hi_a, bins, &s_a)) return rc;
+  if (int rc = check_bin_range("joint_histogram", lo_b, hi_b, bins, &s_b)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const JhChoice c = choose_joint_hist(bins, numel_per_item, batch);
   const int64_t blocks = c.chunks * c.bands * (int64_t)batch;

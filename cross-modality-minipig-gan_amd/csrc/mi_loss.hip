@@ -20,7 +20,9 @@
 //
 // (The other normaliser strategy -- one voxel per lane, K exps, normalised weights transposed through LDS -- was not
 // built: the reduction is ten DPP adds and two swizzles in a step of about forty vector instructions.)
-#include "mpgan_common.h"
+// The value-range refusals are image_stats.h's (without the fp32 binning rule: nothing is binned here), the reduction,
+// wrt, upstream_stride and workspace checks mpgan_common.h's.
+#include "image_stats.h"
 #include "conv_geom.h"
 
 namespace mpgan {
@@ -265,8 +267,6 @@ __global__ __launch_bounds__(256) void pmi_backward_kernel(PmiBwd q) {
   }
 }
 
-static bool pmi_finite(float v) { return v - v == 0.f; }
-
 }  // namespace mpgan
 
 using namespace mpgan;
@@ -281,11 +281,9 @@ static int pmi_check_geometry(const char* who, int64_t n, int32_t batch, float l
   MPGAN_CHECK_ARG(bins >= 2 && bins <= PMI_T, "%s: bins %d outside [2, 32]", who, bins);
   MPGAN_CHECK_ARG(batch >= 1 && batch <= 65535, "%s: batch %d outside [1, 65535]", who, batch);
   MPGAN_CHECK_ARG(n >= 1, "%s: numel_per_item < 1", who);
-  MPGAN_CHECK_ARG(pmi_finite(lo_a) && pmi_finite(hi_a) && pmi_finite(lo_b) && pmi_finite(hi_b) &&
-                      pmi_finite(hi_a - lo_a) && pmi_finite(hi_b - lo_b),
-                  "%s: non-finite value range", who);
-  MPGAN_CHECK_ARG(hi_a > lo_a && hi_b > lo_b, "%s: value range needs hi > lo", who);
-  MPGAN_CHECK_ARG(sigma_ratio > 0.0 && sigma_ratio - sigma_ratio == 0.0, "%s: sigma_ratio must be positive and finite",
+  if (int rc = check_bin_range(who, lo_a, hi_a, bins, nullptr)) return rc;
+  if (int rc = check_bin_range(who, lo_b, hi_b, bins, nullptr)) return rc;
+  MPGAN_CHECK_ARG(sigma_ratio > 0.0 && is_finite(sigma_ratio), "%s: sigma_ratio must be positive and finite",
                   who);
   return MPGAN_OK;
 }
@@ -301,13 +299,13 @@ extern "C" int mpgan_parzen_mi_forward(const float* a, const float* b, int64_t n
                                        double smooth_nr, double smooth_dr, void* workspace, int64_t workspace_bytes,
                                        double* joint, double* mi, float* coef, int32_t reduction, float* loss,
                                        void* stream) {
-  MPGAN_CHECK_ARG(a && b && workspace && mi, "parzen_mi_forward: null pointer");
+  MPGAN_CHECK_ARG(a && b && mi, "parzen_mi_forward: null pointer");
   if (int rc = pmi_check_geometry("parzen_mi_forward", numel_per_item, batch, lo_a, hi_a, lo_b, hi_b, bins, sigma_ratio))
     return rc;
-  MPGAN_CHECK_ARG(reduction >= 0 && reduction <= 2, "parzen_mi_forward: unknown reduction %d", reduction);
-  MPGAN_CHECK_ARG(workspace_bytes >= mpgan_parzen_mi_workspace(batch, numel_per_item, bins),
-                  "parzen_mi_forward: workspace too small");
-  MPGAN_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "parzen_mi_forward: workspace must be 8-byte aligned");
+  if (int rc = check_reduction("parzen_mi_forward", reduction)) return rc;
+  if (int rc = check_workspace("parzen_mi_forward", workspace, workspace_bytes,
+                               mpgan_parzen_mi_workspace(batch, numel_per_item, bins)))
+    return rc;
   PmiJoint q;
   q.a = a; q.b = b; q.n = numel_per_item;
   q.slots = pmi_slots(numel_per_item);
@@ -333,9 +331,8 @@ extern "C" int mpgan_parzen_mi_backward(const float* a, const float* b, int64_t 
   MPGAN_CHECK_ARG(a && b && coef && upstream && grad, "parzen_mi_backward: null pointer");
   if (int rc = pmi_check_geometry("parzen_mi_backward", numel_per_item, batch, lo_a, hi_a, lo_b, hi_b, bins, sigma_ratio))
     return rc;
-  MPGAN_CHECK_ARG(wrt == 0 || wrt == 1, "parzen_mi_backward: wrt %d is neither 0 (a) nor 1 (b)", wrt);
-  MPGAN_CHECK_ARG(upstream_stride == 0 || upstream_stride == 1, "parzen_mi_backward: upstream_stride %d not 0 or 1",
-                  upstream_stride);
+  if (int rc = check_wrt("parzen_mi_backward", wrt)) return rc;
+  if (int rc = check_upstream_stride("parzen_mi_backward", upstream_stride)) return rc;
   MPGAN_CHECK_ARG((reinterpret_cast<uintptr_t>(coef) & 15) == 0, "parzen_mi_backward: coef must be 16-byte aligned");
   PmiBwd q;
   q.x = wrt == 0 ? a : b;

@@ -100,6 +100,48 @@ inline int element_count(const char* fn, const char* side, int32_t n, const int3
   return MPGAN_OK;
 }
 
+// false for NaN and the infinities.  (Not `finite`: <math.h> declares one in the global namespace, and the entry points
+// see both through their using-directive.)
+inline bool is_finite(float v) { return v - v == 0.f; }
+inline bool is_finite(double v) { return v - v == 0.0; }
+
+// ---- the argument checks the pair losses share (host; status as the entry points return it) ------------------------
+// Every (b, c) image is an item: the items must fill whole batch entries.
+inline int check_items(const char* fn, int32_t items, int32_t channels) {
+  MPGAN_CHECK_ARG(channels >= 1 && items % channels == 0, "%s: %d items are no multiple of %d channels", fn, items, channels);
+  return MPGAN_OK;
+}
+
+inline int check_reduction(const char* fn, int32_t reduction) {
+  MPGAN_CHECK_ARG(reduction >= 0 && reduction <= 2, "%s: unknown reduction %d", fn, reduction);
+  return MPGAN_OK;
+}
+
+// A backward's arguments: which image the gradient is for (0: a, 1: b); the upstream gradient's stride (0: one for
+// every item, 1: one per batch entry); the factor on it.
+inline int check_wrt(const char* fn, int32_t wrt) {
+  MPGAN_CHECK_ARG(wrt == 0 || wrt == 1, "%s: wrt %d is neither 0 (a) nor 1 (b)", fn, wrt);
+  return MPGAN_OK;
+}
+
+inline int check_upstream_stride(const char* fn, int32_t upstream_stride) {
+  MPGAN_CHECK_ARG(upstream_stride == 0 || upstream_stride == 1, "%s: upstream_stride %d not 0 or 1", fn, upstream_stride);
+  return MPGAN_OK;
+}
+
+inline int check_scale(const char* fn, double scale) {
+  MPGAN_CHECK_ARG(is_finite(scale), "%s: non-finite scale", fn);
+  return MPGAN_OK;
+}
+
+// A workspace of doubles: `need` bytes at an 8-byte-aligned address.
+inline int check_workspace(const char* fn, const void* workspace, int64_t workspace_bytes, int64_t need) {
+  MPGAN_CHECK_ARG(workspace != nullptr, "%s: null pointer (workspace)", fn);
+  MPGAN_CHECK_ARG(workspace_bytes >= need, "%s: workspace too small", fn);
+  MPGAN_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "%s: workspace must be 8-byte aligned", fn);
+  return MPGAN_OK;
+}
+
 // The one-time preamble of a launcher whose instance KERN may need more dynamic LDS than the default limit: raised
 // once per instantiation.
 template <auto KERN>

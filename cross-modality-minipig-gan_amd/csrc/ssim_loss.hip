@@ -1,14 +1,20 @@
-// Differentiable SSIM loss (include/mpgan_hip.h: "SSIM loss" states the definition and the closed-form gradient).
-// Two kernels of its own and the shared loss tail, no floating-point atomics, no scatter; every sum is taken in a
-// fixed order in fp64 (reduce.h):
+// SSIM, the metric and the differentiable loss (include/mpgan_hip.h: "SSIM loss" states the definition and the
+// closed-form gradient; the metric is skimage.metrics.structural_similarity as psnr_ssim_metric.py:91-92 calls it:
+// 7-wide uniform window, 7x7 for a slice and 7x7x7 for a volume, K1 = 0.01, K2 = 0.03, sample covariance NP/(NP-1),
+// mean of S over the interior that excludes the 3 border samples per windowed axis).  Two kernels of its own, the
+// metric's one-block tail and the shared loss tail, no floating-point atomics, no scatter; every sum is taken in a fixed order in fp64 (reduce.h):
 //
-//   sl_forward_kernel   the pattern of ssim_partial_kernel (metric_ops.hip): a block stages the (TZ+WZ-1) x 14 x 38
-//                       region of both images of ONE item in LDS, a thread owns one (y, x) column of the 8 x 32 tile,
-//                       forms the 7x7 plane sums of (a, b, a^2, b^2, ab) of every staged z once in double and adds
-//                       them to the windows that hold the plane (the z slide).  The sums are taken over the raw samples and shifted by `lo` once per
-//                       window, in double (exactly what a per-sample x - lo in double gives, to 1e-14).  When a
-//                       gradient is wanted the same pass writes the per-window coefficient maps Q, R and P of each
-//                       differentiated image, as doubles (see "storage" below).  Block partial -> workspace slot.
+//   sl_forward_kernel   THE SSIM forward, of the metric too: a block stages the (TZ+WZ-1) x 14 x 38 region of both
+//                       images of ONE item in LDS, a thread owns one (y, x) column of the 8 x 32 tile, forms the 7x7
+//                       plane sums of (a, b, a^2, b^2, ab) of every staged z once in double (sums of 343 products of
+//                       0..255 values would cost fp32 its variance digits) and adds them to the windows that hold the
+//                       plane (the z slide).  The sums are taken over the raw samples and shifted by `lo` once per
+//                       window, in double (exactly what a per-sample x - lo in double gives, to 1e-14; with lo = 0,
+//                       the metric, the shift adds and subtracts exact zeros).  When a gradient is wanted the same pass
+//                       writes the per-window coefficient maps Q, R and P of each differentiated image, as doubles
+//                       (see "storage" below).  Block partial -> workspace slot.
+//   ssim_final_kernel   mpgan_ssim's tail: one block adds the one item's tile partials in slot order + a fixed tree
+//                       and rounds the mean to fp32.
 //   launch_loss_tail    (loss_ops.hip) loss_item_kernel, one block per item: its tiles' partials in slot order + a fixed
 //                       tree -> ssim_item (double); loss_reduce_kernel<true>: loss = 1 - ssim over the items in item
 //                       order: mean, sum, or per batch entry over its channels.
@@ -295,13 +301,9 @@ struct SlGeom {
   int fwd_tx, fwd_ty, bwd_tx, bwd_ty;
 };
 
-// The ONE place the tiling of both launches is decided.  Status as the entry points return it.
-static int sl_geometry(const char* who, const int32_t* dhw, int32_t items, SlGeom* g) {
-  MPGAN_CHECK_ARG(dhw != nullptr, "%s: null dhw", who);
-  MPGAN_CHECK_ARG(items >= 1 && items <= 65535, "%s: %d items outside [1, 65535]", who, items);
-  MPGAN_CHECK_ARG(dhw[0] >= 1 && dhw[1] >= SL_W && dhw[2] >= SL_W, "%s: extents (%d, %d, %d) below the 7-wide window",
-                  who, dhw[0], dhw[1], dhw[2]);
-  MPGAN_UNSUPPORTED(dhw[0] > 1 && dhw[0] < SL_W, "%s: depth %d is neither a slice (1) nor >= 7", who, dhw[0]);
+// The ONE place the tiling of both launches is decided: extents (D >= 1, H and W >= 7) -> *g.  A depth below 7 tiles as
+// that many slices (which is what mpgan_ssim_workspace sizes a depth of 2..6 by; the launches refuse it).
+static void sl_tiling(const int32_t* dhw, SlGeom* g) {
   g->vol = dhw[0] >= SL_W;
   g->D = dhw[0]; g->H = dhw[1]; g->W = dhw[2];
   g->OD = g->vol ? g->D - SL_W + 1 : g->D; g->OH = g->H - SL_W + 1; g->OW = g->W - SL_W + 1;
@@ -312,6 +314,17 @@ static int sl_geometry(const char* who, const int32_t* dhw, int32_t items, SlGeo
   g->fwd_tiles = (long)((g->OD + tz - 1) / tz) * g->fwd_ty * g->fwd_tx;
   g->bwd_tx = (g->W + SL_TX - 1) / SL_TX; g->bwd_ty = (g->H + SL_TY - 1) / SL_TY;
   g->bwd_tiles = (long)((g->D + tz - 1) / tz) * g->bwd_ty * g->bwd_tx;
+}
+
+static bool sl_extents_ok(const int32_t* dhw) { return dhw && dhw[0] >= 1 && dhw[1] >= SL_W && dhw[2] >= SL_W; }
+
+// Every launch's geometry checks, then the tiling.  Status as the entry points return it; *g is valid on MPGAN_OK alone.
+static int sl_geometry(const char* who, const int32_t* dhw, int32_t items, SlGeom* g) {
+  MPGAN_CHECK_ARG(dhw != nullptr, "%s: null dhw", who);
+  MPGAN_CHECK_ARG(items >= 1 && items <= 65535, "%s: %d items outside [1, 65535]", who, items);
+  MPGAN_CHECK_ARG(sl_extents_ok(dhw), "%s: extents (%d, %d, %d) below the 7-wide window", who, dhw[0], dhw[1], dhw[2]);
+  MPGAN_UNSUPPORTED(dhw[0] > 1 && dhw[0] < SL_W, "%s: depth %d is neither a slice (1) nor >= 7", who, dhw[0]);
+  sl_tiling(dhw, g);
   MPGAN_CHECK_ARG(g->fwd_tiles < (1L << 31) && g->bwd_tiles < (1L << 31), "%s: too many tiles", who);
   return MPGAN_OK;
 }
@@ -359,35 +372,40 @@ static void sl_launch_backward(const SlGeom& g, int32_t items, const P& p, hipSt
   }
 }
 
-// Both forward entry points: every check, then the launches.  wt == null is the plain form.
+// What every forward launch reads: the images, the tiling, lo and the two constants of the data range L; no maps.
+static void sl_forward_params(SlFwd* p, const float* a, const float* b, const SlGeom& g, double lo, double L,
+                              void* workspace) {
+  p->a = a; p->b = b; p->D = g.D; p->H = g.H; p->W = g.W;
+  p->tiles_x = g.fwd_tx; p->tiles_y = g.fwd_ty; p->tiles = g.fwd_tiles;
+  p->lo = lo; p->c1 = (0.01 * L) * (0.01 * L); p->c2 = (0.03 * L) * (0.03 * L);
+  p->partials = static_cast<double*>(workspace);
+  p->q = p->r = p->pa = p->pb = nullptr;
+}
+
+// Both forward entry points of the loss: every check, then the launches.  wt == null is the plain form.
 static int sl_forward(const char* who, const float* a, const float* b, const int32_t* dhw, int32_t items,
                       int32_t channels, double lo, double hi, int32_t grad_mask, void* workspace,
                       int64_t workspace_bytes, void* coef, int64_t coef_bytes, int32_t reduction, float* loss,
                       void* stream, const SlWeights* wt) {
-  MPGAN_CHECK_ARG(a && b && workspace && loss && (!wt || wt->stats), "%s: null pointer", who);
+  MPGAN_CHECK_ARG(a && b && loss && (!wt || wt->stats), "%s: null pointer", who);
   MPGAN_CHECK_ARG(!wt || !(wt->mask && wt->thr), "%s: at most one of mask and thr may be given (got both)", who);
   SlGeom g;
   if (int rc = sl_geometry(who, dhw, items, &g)) return rc;
-  MPGAN_CHECK_ARG(channels >= 1 && items % channels == 0, "%s: %d items are no multiple of %d channels", who, items,
-                  channels);
-  MPGAN_CHECK_ARG(hi - lo > 0.0 && (hi - lo) - (hi - lo) == 0.0, "%s: value range needs finite hi > lo", who);
+  if (int rc = check_items(who, items, channels)) return rc;
+  MPGAN_CHECK_ARG(hi - lo > 0.0 && is_finite(hi - lo), "%s: value range needs finite hi > lo", who);
   MPGAN_CHECK_ARG(grad_mask >= 0 && grad_mask <= 3, "%s: grad_mask %d outside [0, 3]", who, grad_mask);
-  MPGAN_CHECK_ARG(reduction >= 0 && reduction <= 2, "%s: unknown reduction %d", who, reduction);
+  if (int rc = check_reduction(who, reduction)) return rc;
   int64_t need_coef = 0;
-  const int64_t need_ws = sl_workspace(who, dhw, items, grad_mask, wt != nullptr, &need_coef);
-  MPGAN_CHECK_ARG(workspace_bytes >= need_ws, "%s: workspace too small", who);
-  MPGAN_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "%s: workspace must be 8-byte aligned", who);
+  if (int rc = check_workspace(who, workspace, workspace_bytes,
+                               sl_workspace(who, dhw, items, grad_mask, wt != nullptr, &need_coef)))
+    return rc;
   MPGAN_CHECK_ARG(grad_mask == 0 || (coef && coef_bytes >= need_coef), "%s: coef missing or too small", who);
   MPGAN_CHECK_ARG((reinterpret_cast<uintptr_t>(coef) & 7) == 0, "%s: coef must be 8-byte aligned", who);
   MPGAN_CHECK_ARG(!wt || ((reinterpret_cast<uintptr_t>(wt->stats) & 7) == 0 &&
                           (reinterpret_cast<uintptr_t>(wt->smap) & 3) == 0),
                   "%s: stats must be 8-byte and smap 4-byte aligned", who);
-  const double L = hi - lo;
   SlFwdW p;
-  p.a = a; p.b = b; p.D = g.D; p.H = g.H; p.W = g.W;
-  p.tiles_x = g.fwd_tx; p.tiles_y = g.fwd_ty; p.tiles = g.fwd_tiles;
-  p.lo = lo; p.c1 = (0.01 * L) * (0.01 * L); p.c2 = (0.03 * L) * (0.03 * L);
-  p.partials = static_cast<double*>(workspace);
+  sl_forward_params(&p, a, b, g, lo, hi - lo, workspace);
   const long slots = (long)items * g.fwd_tiles;
   double* ssim_item = p.partials + slots * (wt ? 2 : 1);
   double* maps = static_cast<double*>(coef);
@@ -420,14 +438,13 @@ static int sl_backward(const char* who, const float* a, const float* b, const in
   MPGAN_CHECK_ARG(a && b && coef && upstream && grad, "%s: null pointer", who);
   SlGeom g;
   if (int rc = sl_geometry(who, dhw, items, &g)) return rc;
-  MPGAN_CHECK_ARG(channels >= 1 && items % channels == 0, "%s: %d items are no multiple of %d channels", who, items,
-                  channels);
-  MPGAN_CHECK_ARG(wrt == 0 || wrt == 1, "%s: wrt %d is neither 0 (a) nor 1 (b)", who, wrt);
+  if (int rc = check_items(who, items, channels)) return rc;
+  if (int rc = check_wrt(who, wrt)) return rc;
+  if (int rc = check_upstream_stride(who, upstream_stride)) return rc;
+  if (int rc = check_scale(who, scale)) return rc;
+  MPGAN_CHECK_ARG(is_finite(lo), "%s: non-finite lo", who);
   MPGAN_CHECK_ARG(grad_mask >= 1 && grad_mask <= 3 && ((grad_mask >> wrt) & 1),
                   "%s: the forward's grad_mask %d holds no maps for wrt %d", who, grad_mask, wrt);
-  MPGAN_CHECK_ARG(upstream_stride == 0 || upstream_stride == 1, "%s: upstream_stride %d not 0 or 1", who,
-                  upstream_stride);
-  MPGAN_CHECK_ARG(lo - lo == 0.0 && scale - scale == 0.0, "%s: non-finite lo or scale", who);
   const long per_map = (long)items * g.M;
   MPGAN_CHECK_ARG(coef_bytes >= (int64_t)sl_maps(grad_mask) * per_map * (int64_t)sizeof(double), "%s: coef too small",
                   who);
@@ -453,9 +470,43 @@ static int sl_backward(const char* who, const float* a, const float* b, const in
   return check_launch(who);
 }
 
+// The metric's tail: the mean of S over the one item's windows, rounded to fp32.
+__global__ __launch_bounds__(256) void ssim_final_kernel(const double* __restrict__ partials, int nb, double inv_count,
+                                                         float* __restrict__ out1) {
+  __shared__ double red[256];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < nb; i += 256) s += partials[i];
+  s = block_tree_sum<256>(s, red);
+  if (threadIdx.x == 0) out1[0] = (float)(s * inv_count);
+}
+
 }  // namespace mpgan
 
 using namespace mpgan;
+
+// One double per tile of the forward; a query: it leaves the last error alone.
+extern "C" int64_t mpgan_ssim_workspace(const int32_t* dhw) {
+  if (!sl_extents_ok(dhw)) return -1;
+  SlGeom g;
+  sl_tiling(dhw, &g);
+  return g.fwd_tiles * (int64_t)sizeof(double);
+}
+
+// The plain forward over one item with lo = 0 and hi = data_range, no maps, then the metric's own tail.
+extern "C" int mpgan_ssim(const float* a, const float* b, const int32_t* dhw, float data_range, void* workspace,
+                          int64_t workspace_bytes, float* out1, void* stream) {
+  MPGAN_CHECK_ARG(a && b && workspace && out1, "ssim: null pointer");
+  SlGeom g;
+  if (int rc = sl_geometry("ssim", dhw, 1, &g)) return rc;
+  MPGAN_CHECK_ARG(workspace_bytes >= g.fwd_tiles * (int64_t)sizeof(double), "ssim: workspace too small");
+  SlFwd p;
+  sl_forward_params(&p, a, b, g, 0.0, (double)data_range, workspace);
+  hipStream_t st = (hipStream_t)stream;
+  sl_launch_forward<SL_PLAIN>(g, 1, p, st);
+  hipLaunchKernelGGL(ssim_final_kernel, dim3(1), dim3(256), 0, st, (const double*)p.partials, (int)g.fwd_tiles,
+                     1.0 / (double)g.M, out1);
+  return check_launch("ssim");
+}
 
 extern "C" int64_t mpgan_ssim_loss_workspace(const int32_t* dhw, int32_t items, int32_t grad_mask,
                                              int64_t* coef_bytes) {

@@ -28,7 +28,7 @@ import torch.nn as nn
 
 from . import ops
 from .metrics import ValueRange, _ranges
-from .preprocess import _otsu_config, check_threshold, item_thresholds
+from .preprocess import _otsu_config, check_threshold, item_thresholds, mask_bytes
 
 _REDUCTIONS = ("mean", "sum", "none")
 MAX_BINS = 32
@@ -182,45 +182,23 @@ def _ssim_shape_error(shape):
 
 class _SSIMLossFn(torch.autograd.Function):
     """The reduced loss 1 - ssim; saves the two inputs and the float64 coefficient maps of the gradients that
-    needs_input_grad asks for.  backward only reads them, so a second backward (retain_graph) gives the same bits."""
-
-    @staticmethod
-    def forward(ctx, pred, target, lo, hi, reduction):
-        a, b, (batch, channels, spatial), loss, scale = _pair_forward(pred, target, reduction)
-        items, dev = batch * channels, a.device
-        mask = int(ctx.needs_input_grad[0]) | (int(ctx.needs_input_grad[1]) << 1)
-        ws_bytes, coef_bytes = ops.ssim_loss_workspace(spatial, items, mask)
-        ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
-        coef = torch.empty(coef_bytes // 8, dtype=torch.float64, device=dev) if mask else None
-        ops.ssim_loss_forward(a, b, spatial, items, channels, lo, hi, mask, ws, coef, reduction, loss)
-        ctx.cfg = (spatial, items, channels, lo, mask, -scale)
-        ctx.save_for_backward(a, b, coef)
-        return loss
-
-    @staticmethod
-    def backward(ctx, gout):
-        a, b, coef = ctx.saved_tensors
-        spatial, items, channels, lo, mask, scale = ctx.cfg
-        return _pair_backward(ctx, gout, lambda g, wrt, out: ops.ssim_loss_backward(
-            a, b, spatial, items, channels, lo, mask, coef, g, scale, wrt, out)) + (None,) * 3
-
-
-class _MaskedSSIMLossFn(torch.autograd.Function):
-    """_SSIMLossFn with a weight per window: one of mask (uint8, the inputs' shape) and thr (fp32, one per item), or
-    neither.  Saves the inputs, the weighted maps and stats = (ssim_item, n_item) per item; the backward reads every
-    item's divisor from stats on the device, so nothing syncs and a second backward gives the same bits."""
+    needs_input_grad asks for.  With a weight per window -- one of mask (uint8, the inputs' shape) and thr (fp32, one per
+    item) -- it also saves stats = (ssim_item, n_item) per item, from which the backward reads every item's divisor on
+    the device; without one there is no stats tensor and the plain entry points run.  backward only reads what was
+    saved, so nothing syncs and a second backward (retain_graph) gives the same bits."""
 
     @staticmethod
     def forward(ctx, pred, target, mask, thr, lo, hi, reduction):
         a, b, (batch, channels, spatial), loss, scale = _pair_forward(pred, target, reduction)
         items, dev = batch * channels, a.device
+        weighted = mask is not None or thr is not None
         grads = int(ctx.needs_input_grad[0]) | (int(ctx.needs_input_grad[1]) << 1)
-        ws_bytes, coef_bytes = ops.masked_ssim_loss_workspace(spatial, items, grads)
+        ws_bytes, coef_bytes = ops.ssim_loss_workspace(spatial, items, grads, weighted)
         ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
         coef = torch.empty(coef_bytes // 8, dtype=torch.float64, device=dev) if grads else None
-        stats = torch.empty((items, 2), dtype=torch.float64, device=dev)
-        ops.masked_ssim_loss_forward(a, b, spatial, items, channels, lo, hi, mask, thr, grads, ws, coef, stats, None,
-                                     reduction, loss)
+        stats = torch.empty((items, 2), dtype=torch.float64, device=dev) if weighted else None
+        ops.ssim_loss_forward(a, b, spatial, items, channels, lo, hi, grads, ws, coef, reduction, loss, mask=mask,
+                              thr=thr, stats=stats)
         ctx.cfg = (spatial, items, channels, lo, grads, -scale)
         ctx.save_for_backward(a, b, coef, stats)
         return loss
@@ -229,27 +207,8 @@ class _MaskedSSIMLossFn(torch.autograd.Function):
     def backward(ctx, gout):
         a, b, coef, stats = ctx.saved_tensors
         spatial, items, channels, lo, grads, scale = ctx.cfg
-        return _pair_backward(ctx, gout, lambda g, wrt, out: ops.masked_ssim_loss_backward(
-            a, b, spatial, items, channels, lo, grads, coef, stats, g, scale, wrt, out)) + (None,) * 5
-
-
-def _check_mask_type(mask, who):
-    if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8):
-        raise ValueError(f"{who}: mask must be a bool / uint8 tensor")
-
-
-def _check_mask_place(mask, pred, who):
-    shape = tuple(pred.shape)
-    if mask.device != pred.device or tuple(mask.shape) not in (shape, shape[:1] + (1,) + shape[2:]):
-        raise ValueError(f"{who}: mask must lie on the inputs' device with their shape {shape} or channel extent 1, "
-                         f"got {tuple(mask.shape)} on {mask.device}")
-
-
-def _mask_bytes(mask, pred, who):
-    """The mask as contiguous uint8 in pred's shape; a channel extent of 1 is broadcast over the channels."""
-    _check_mask_place(mask, pred, who)
-    mask = mask.expand(pred.shape).contiguous()
-    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+        return _pair_backward(ctx, gout, lambda g, wrt, out: ops.ssim_loss_backward(
+            a, b, spatial, items, channels, lo, grads, coef, g, scale, wrt, out, stats)) + (None,) * 5
 
 
 def ssim_loss(pred: torch.Tensor, target: torch.Tensor, value_range=(0.0, 1.0), reduction: str = "mean", *,
@@ -271,24 +230,15 @@ def ssim_loss(pred: torch.Tensor, target: torch.Tensor, value_range=(0.0, 1.0), 
     the threshold.  Defined in include/mpgan_hip.h ("masked SSIM"), pinned against tests/masked_ssim_ref.py."""
     who = "ssim_loss"
     lo, hi = _ssim_config(value_range, reduction, who)
-    if mask is None and threshold is None:
-        _pair_inputs(pred, target, who, _ssim_shape_error)
-        return _SSIMLossFn.apply(pred, target, lo, hi, reduction)
     if mask is not None and threshold is not None:
         raise ValueError(f"{who}: give at most one of mask and threshold")
-    if mask is None:
+    if mask is not None and pred.shape == target.shape:   # a mismatch of the pair itself is _pair_inputs' complaint
+        mask = mask_bytes(mask, pred, who, broadcast_channels=True)
+    elif threshold is not None:
         check_threshold(threshold, who)
-    else:
-        _check_mask_type(mask, who)
-        if pred.shape == target.shape:                    # a mismatch of the pair itself is _pair_inputs' complaint
-            _check_mask_place(mask, pred, who)
     _pair_inputs(pred, target, who, _ssim_shape_error)
-    thr = None
-    if mask is None:
-        thr = item_thresholds(target.contiguous(), threshold, bins, value_range, who)
-    else:
-        mask = _mask_bytes(mask, pred, who)
-    return _MaskedSSIMLossFn.apply(pred, target, mask, thr, lo, hi, reduction)
+    thr = None if threshold is None else item_thresholds(target.contiguous(), threshold, bins, value_range, who)
+    return _SSIMLossFn.apply(pred, target, mask, thr, lo, hi, reduction)
 
 
 class SSIMLoss(nn.Module):
@@ -483,19 +433,10 @@ def masked_l1_loss(pred: torch.Tensor, target: torch.Tensor, mask: torch.Tensor 
         raise ValueError(f"{who}: give exactly one of mask and threshold")
     if mask is None:
         check_threshold(threshold, who)
-    elif not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8):
-        raise ValueError(f"{who}: mask must be a bool / uint8 tensor")
+    elif pred.shape == target.shape:                      # a mismatch of the pair itself is _pair_inputs' complaint
+        mask = mask_bytes(mask, pred, who, broadcast_channels=True)
     _pair_inputs(pred, target, who, _masked_l1_shape_error)
-    thr = None
-    if mask is None:
-        thr = item_thresholds(target.contiguous(), threshold, bins, value_range, who)
-    else:
-        shape = tuple(pred.shape)
-        if mask.device != pred.device or tuple(mask.shape) not in (shape, shape[:1] + (1,) + shape[2:]):
-            raise ValueError(f"{who}: mask must lie on the inputs' device with their shape {shape} or channel extent 1, "
-                             f"got {tuple(mask.shape)}")
-        mask = mask.expand(shape).contiguous()
-        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    thr = None if mask is not None else item_thresholds(target.contiguous(), threshold, bins, value_range, who)
     return _MaskedL1Fn.apply(pred, target, mask, thr, w_fg, w_bg, reduction)
 
 

@@ -14,6 +14,7 @@ import torch
 
 from . import ops
 from ._lib import check, lib
+from .preprocess import mask_bytes
 
 
 def _stream():
@@ -34,14 +35,11 @@ def rescale_0_255(x: torch.Tensor, do_round: bool = True) -> torch.Tensor:
 def _masked_image_errors(a, b, data_range, mask):
     if a.dtype != torch.float32 or b.dtype != torch.float32 or not (a.is_cuda and b.is_cuda):
         raise ValueError("image_errors: a mask needs two fp32 device tensors")
-    if (not isinstance(mask, torch.Tensor) or mask.shape != a.shape or mask.dtype not in (torch.bool, torch.uint8)
-            or mask.device != a.device):
-        raise ValueError("image_errors: mask must be a same-shape bool / uint8 tensor on the inputs' device")
+    mask = mask_bytes(mask, a, "image_errors")
     if a.numel() == 0:
         raise ValueError("image_errors: empty tensors")
-    a, b, mask = a.contiguous(), b.contiguous(), mask.contiguous()
-    mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
-    out = ops.masked_image_errors(a, b, mask, data_range, torch.empty(4, dtype=torch.float64, device=a.device))
+    out = ops.masked_image_errors(a.contiguous(), b.contiguous(), mask, data_range,
+                                  torch.empty(4, dtype=torch.float64, device=a.device))
     return {"mae": out[0], "mse": out[1], "psnr": out[2], "count": out[3]}
 
 
@@ -83,30 +81,31 @@ def score_volume(generated: torch.Tensor, ground_truth: torch.Tensor,
     return out
 
 
-def _weighted_ssim(who, a, b, data_range, mask, want_map):
-    """(stats, smap) of one image through the masked SSIM forward (include/mpgan_hip.h, lo = 0): stats =
-    (ssim_item, n_item) in float64, smap the fp32 map of S over the window corners when want_map."""
+def _ssim_inputs(who, a, b):
+    """The two images of ssim / ssim_map as contiguous fp32, and their extents."""
     if a.shape != b.shape or a.dim() not in (2, 3):
         raise ValueError(f"{who}: expects two same-shape (H, W) or (D, H, W) tensors")
     if not (a.is_cuda and b.is_cuda):
         raise ValueError(f"{who}: expects two device tensors")
+    return a.contiguous().float(), b.contiguous().float(), tuple(a.shape)
+
+
+def _weighted_ssim(who, a, b, data_range, mask, want_map):
+    """(stats, smap) of one image through the masked SSIM forward (include/mpgan_hip.h, lo = 0): stats =
+    (ssim_item, n_item) in float64, smap the fp32 map of S over the window corners when want_map."""
+    a, b, spatial = _ssim_inputs(who, a, b)
     if not float(data_range) > 0:
         raise ValueError(f"{who}: data_range must be positive, got {data_range!r}")
     if mask is not None:
-        if (not isinstance(mask, torch.Tensor) or mask.shape != a.shape or mask.dtype not in (torch.bool, torch.uint8)
-                or mask.device != a.device):
-            raise ValueError(f"{who}: mask must be a same-shape bool / uint8 tensor on the inputs' device")
-        mask = mask.contiguous()
-        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
-    a, b = a.contiguous().float(), b.contiguous().float()
-    spatial, dev = tuple(a.shape), a.device
-    ws_bytes, _ = ops.masked_ssim_loss_workspace(spatial, 1, 0)
+        mask = mask_bytes(mask, a, who)
+    dev = a.device
+    ws_bytes, _ = ops.ssim_loss_workspace(spatial, 1, 0, weighted=True)
     ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
     stats = torch.empty((1, 2), dtype=torch.float64, device=dev)
     corners = tuple(1 if len(spatial) == 3 and i == 0 and s == 1 else s - 6 for i, s in enumerate(spatial))
     smap = torch.empty(corners, device=dev) if want_map else None          # a depth of 1 is a slice: not windowed
-    ops.masked_ssim_loss_forward(a, b, spatial, 1, 1, 0.0, float(data_range), mask, None, 0, ws, None, stats, smap,
-                                 "mean", torch.empty((), device=dev))
+    ops.ssim_loss_forward(a, b, spatial, 1, 1, 0.0, float(data_range), 0, ws, None, "mean", torch.empty((), device=dev),
+                          mask=mask, stats=stats, smap=smap)
     return stats, smap
 
 
@@ -124,16 +123,14 @@ def ssim(a: torch.Tensor, b: torch.Tensor, data_range: float = 256.0, mask: Opti
     covariance, mean over the interior.  Returns a device scalar.  With mask (a same-shape bool / uint8 device tensor,
     e.g. preprocess.foreground_mask's output) the mean runs over the windows whose centre voxel is in the mask --
     the interior of the map averaged over the mask -- and comes back as a float64 device scalar; a mask without such
-    a window gives NaN."""
+    a window gives NaN.  Either way one pass of the SSIM loss's forward kernel (csrc/ssim_loss.hip)."""
     if mask is not None:
         return _weighted_ssim("ssim", a, b, data_range, mask, False)[0][0, 0]
-    if a.shape != b.shape or a.dim() not in (2, 3):
-        raise ValueError("ssim: expects two same-shape (H, W) or (D, H, W) tensors")
-    a, b = a.contiguous().float(), b.contiguous().float()
-    dhw = (C.c_int32 * 3)(*((1,) * (3 - a.dim()) + tuple(a.shape)))
+    a, b, spatial = _ssim_inputs("ssim", a, b)
+    dhw = (C.c_int32 * 3)(*((1,) * (3 - len(spatial)) + spatial))
     need = int(lib().mpgan_ssim_workspace(dhw))
     if need < 0:
-        raise ValueError(f"ssim: extents {tuple(a.shape)} are below the 7-wide window")
+        raise ValueError(f"ssim: extents {spatial} are below the 7-wide window")
     ws = torch.empty(max(need // 8, 1), dtype=torch.float64, device=a.device)
     out = torch.empty(1, device=a.device)
     check(lib().mpgan_ssim(a.data_ptr(), b.data_ptr(), dhw, float(data_range), ws.data_ptr(), ws.numel() * 8,
@@ -175,10 +172,7 @@ def joint_histogram(a: torch.Tensor, b: torch.Tensor, bins: int = 256, value_ran
     a, b = a.contiguous(), b.contiguous()          # a contiguous view keeps its (possibly unaligned) offset
     mask_ptr = None
     if isinstance(mask, torch.Tensor):
-        if mask.shape != a.shape or mask.dtype not in (torch.bool, torch.uint8) or mask.device != a.device:
-            raise ValueError("joint_histogram: mask must be a same-shape bool / uint8 tensor on the inputs' device")
-        mask = mask.contiguous()
-        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+        mask = mask_bytes(mask, a, "joint_histogram")
         mode, mask_ptr = 3, mask.data_ptr()
     elif mask in _MASK_MODES:
         mode = _MASK_MODES[mask]

@@ -114,6 +114,20 @@ def check_threshold(threshold, who: str):
         raise ValueError(f"{who}: threshold must be finite, got {threshold!r}")
 
 
+def mask_bytes(mask, like: torch.Tensor, who: str, broadcast_channels: bool = False) -> torch.Tensor:
+    """The mask argument of every masked statistic as contiguous uint8 in like's shape: a bool / uint8 tensor on like's
+    device with like's shape, or (broadcast_channels, the losses' (B, C, *spatial) tensors) with channel extent 1."""
+    shape = tuple(like.shape)
+    shapes = (shape, shape[:1] + (1,) + shape[2:]) if broadcast_channels else (shape,)
+    if (not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8) or mask.device != like.device
+            or tuple(mask.shape) not in shapes):
+        got = f"{tuple(mask.shape)} {mask.dtype} on {mask.device}" if isinstance(mask, torch.Tensor) else repr(type(mask))
+        raise ValueError(f"{who}: mask must be a same-shape bool / uint8 tensor on the inputs' device, shape {shape}"
+                         + (" or with channel extent 1" if broadcast_channels else "") + f", got {got}")
+    mask = mask.expand(shape).contiguous()
+    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+
+
 def item_thresholds(x: torch.Tensor, threshold, bins, value_range, who: str) -> torch.Tensor:
     """The fp32 device tensor of one threshold per (b, c) item of the contiguous (B, C, *spatial) tensor x."""
     check_threshold(threshold, who)

@@ -1,5 +1,7 @@
 """sha256 of the raw bytes of every output that passes through a block sum of csrc/reduce.h (the pair losses with both
-gradients, the metrics, grad_norm, l1_loss, adv_loss, DiffAugment, both heads), inputs from fixed CPU seeds.
+gradients, the metrics, grad_norm, l1_loss, adv_loss, DiffAugment, both heads) or through the image statistics of
+csrc/image_stats.h (Otsu, the foreground mask / box / count, the masked L1, errors and SSIM, the banded joint
+histogram), inputs from fixed CPU seeds.
 
     python tools/reduction_bits.py OUT.txt
 
@@ -13,9 +15,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch  # noqa: E402
-from mpgan_amd import losses, metrics, ops  # noqa: E402
+from mpgan_amd import losses, metrics, ops, preprocess  # noqa: E402
 from mpgan_amd.augment import DiffAugment  # noqa: E402
 from mpgan_amd.gan import reconstruction_loss  # noqa: E402
+import metric_small_ref as MS  # noqa: E402
 import ssim_loss_ref as SR  # noqa: E402
 
 lines = []
@@ -64,6 +67,17 @@ for shape in ((136, 544), (9, 17, 39)):
         rec(f"metrics.errors {shape} {k}", v)
     for k, v in metrics.score_volume(a * 0.01 - 1, b * 0.01 - 1, mutual_information=True).items():
         rec(f"metrics.score_volume {shape} {k}", v)
+    m = (torch.rand(shape, generator=g) < 0.6).cuda()
+    for k, v in metrics.image_errors(a, b, mask=m).items():
+        rec(f"metrics.errors masked {shape} {k}", v)
+    rec(f"metrics.ssim_map {shape}", metrics.ssim_map(a, b, 256.0))
+    rec(f"metrics.ssim masked {shape}", metrics.ssim(a, b, 256.0, mask=m))
+    rec(f"metrics.joint_histogram bins200 masked {shape}", metrics.joint_histogram(a, b, 200, mask=m))
+
+for shape in MS.SSIM_SHAPES:                              # every tile edge of the SSIM forward, every degenerate pair
+    for kind in MS.SSIM_KINDS:
+        a, b, data_range = MS.ssim_pair(shape, kind)
+        rec(f"metrics.ssim small {shape} {kind}", metrics.ssim(torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda(), data_range))
 
 # grad_norm
 for n in (300003, 1000):
@@ -131,6 +145,20 @@ ops.linear1_backward(z, pro, wp, dlogit, g_a, dw, db)
 rec("linear1 g_a", g_a)
 rec("linear1 dw", dw)
 rec("linear1 dbias", db)
+
+# foreground statistics and the masked losses: the mask form and the threshold form
+for shape in ((2, 2, 136, 544), (2, 2, 9, 17, 39)):
+    _, t = pair(shape, 7)
+    for bins in (64, 256):
+        rec(f"otsu {shape} bins{bins}", preprocess.otsu_threshold(t, bins))
+    rec(f"foreground_mask {shape}", preprocess.foreground_mask(t))
+    rec(f"foreground_bbox {shape}", preprocess.foreground_bbox(t, margin=1))
+    rec(f"foreground_count {shape}", preprocess.foreground_count(t))
+    m = (torch.rand(shape, generator=torch.Generator().manual_seed(13)) < 0.6).cuda()
+    for tag, kw in (("mask", dict(mask=m)), ("otsu", dict(threshold="otsu"))):
+        pair_loss(f"masked_l1 {tag}", lambda r, kw=kw: lambda p, t: losses.masked_l1_loss(p, t, bg_weight=0.25, reduction=r, **kw),
+                  [shape])
+        pair_loss(f"ssim_loss {tag}", lambda r, kw=kw: lambda p, t: losses.ssim_loss(p, t, (-1.0, 1.0), r, **kw), [shape])
 
 torch.cuda.synchronize()
 with open(sys.argv[1], "w") as f:
