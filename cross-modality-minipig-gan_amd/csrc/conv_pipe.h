@@ -7,6 +7,7 @@
 #include "mpgan_common.h"
 #include "conv_geom.h"
 #include "lds_dma.h"
+#include "norm_rows.h"
 
 namespace mpgan {
 
@@ -20,18 +21,20 @@ constexpr int PITCH = BK + 4;
 #define MPGAN_BWD_EPILOGUE_WALK 0
 #endif
 
-// One element of the fused norm-backward sums (BwdStats), as norm_bwd_reduce_kernel (norm_ops.hip) forms them.  In the
-// instances of conv_epilogue that have output path C, both paths that leave these sums add through here.  The roundings
-// are spelled out (two fused multiply-adds, everything else rounded on its own: what the compiler made of the walk in
-// those instances before path C existed) instead of left to its contraction, which differs with the surrounding code,
-// so that a channel's sums are the same bits whichever path a launch takes.
+// One element of the fused norm-backward sums (BwdStats): norm_rows.h's formula without a peer.  In the instances of
+// conv_epilogue that have output path C, both paths that leave these sums add through here.  The roundings are spelled
+// out (two fused multiply-adds, everything else rounded on its own: what the compiler made of the walk in those
+// instances before path C existed) instead of left to its contraction, which differs with the surrounding code, so that
+// a channel's sums are the same bits whichever path of THIS epilogue a launch takes.  norm_bwd_reduce_kernel (norm_ops.hip)
+// shares the formula but leaves its roundings to the compiler (its scalar instance does not fuse the second sum) and has
+// its own order over the pixels: the two agree to rounding, not to the bit.
 __device__ __forceinline__ void bwd_sums_add(float v, float zz, float sc, float sh, float mu, float is, bool leaky, float slope,
                                              float& b1, float& b2, float& b3) {
 #pragma clang fp contract(off)
   const float y = __builtin_fmaf(zz, sc, sh);
   const float zh = (zz - mu) * is;
   const bool neg = leaky && y < 0.f;
-  const float gy = neg ? v * slope : v;
+  const float gy = norm_bwd_gy(v, y, leaky, slope);
   const float t3 = neg ? v * y : 0.f;
   b1 += gy;
   b2 = __builtin_fmaf(gy, zh, b2);

@@ -6,8 +6,10 @@
 // in a FIXED order, and leave one partial row per (sample, chunk); a tiny
 // finalize kernel combines partials in double precision.  No atomics anywhere,
 // so statistics (and therefore the whole forward) are bitwise reproducible.
+// Row vectors, the backward formula, the element-wise grid and the vector predicate: norm_rows.h; block sums: reduce.h.
 #include "mpgan_common.h"
 #include "norm_fold.h"
+#include "norm_rows.h"
 
 namespace mpgan {
 
@@ -28,25 +30,6 @@ static inline int stats_chunks_host(long pixels_per_sample, int C = 0) {
   if (c > 256) c = 256;
   return (int)c;
 }
-
-template <int V>
-struct Vec;
-template <>
-struct Vec<4> {
-  using T = float4;
-  static __device__ __forceinline__ void load(const float* p, float (&v)[4]) {
-    float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  }
-  static __device__ __forceinline__ void store(float* p, const float (&v)[4]) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  }
-};
-template <>
-struct Vec<1> {
-  static __device__ __forceinline__ void load(const float* p, float (&v)[1]) { v[0] = *p; }
-  static __device__ __forceinline__ void store(float* p, const float (&v)[1]) { *p = v[0]; }
-};
 
 // ---------------------------------------------------------------------------
 // Generic per-channel partial reduction over pixel chunks.
@@ -130,7 +113,10 @@ __global__ __launch_bounds__(256) void channel_stats_kernel(const float* __restr
 
 // Perceptual-loss taps of a peer pass (test_runs/GAN.py:288-298: L1 between the two passes'
 // activations) enter the backward as:  g_a = g - ca*sign(a_peer - a),
-// gy = g_a*act'(y) - cy*sign(y_peer - y), and a dz term -cz*sign(z_peer - z) that bypasses the norm.
+// gy = g_a*act'(y) - cy*sign(y_peer - y), and a dz term -cz*sign(z_peer - z) that bypasses the norm (norm_rows.h).
+// y and the second sum stay contracted by the compiler: named as fused multiply-adds (bwd_sums_add, conv_pipe.h), the
+// Vec<1> instance's second sums get other bits (the compiler keeps its product and addition apart; Vec<4> fuses both).
+// (Not a chunk_reduce functor: that takes one row per call, and the four rows' loads issued together are the speed here.)
 template <int V>
 __global__ __launch_bounds__(256) void norm_bwd_reduce_kernel(const float* __restrict__ gr, int ldg,
                                                               const float* __restrict__ z, int ldz, Pro p,
@@ -140,8 +126,8 @@ __global__ __launch_bounds__(256) void norm_bwd_reduce_kernel(const float* __res
   extern __shared__ float red[];  // [R][3][C]
   const float slope = pro_slope(p);
   const bool leaky = p.act == MPGAN_ACT_LEAKY;
-  float cz = 0.f, cy = 0.f, ca = 0.f;
-  if (pr.coef) { cz = pr.coef[0]; cy = pr.coef[1]; ca = pr.coef[2]; }
+  float cy = 0.f, ca = 0.f;
+  if (pr.coef) { cy = pr.coef[1]; ca = pr.coef[2]; }
   const int tid = threadIdx.x;
   const int q = tid % g.CG, r = tid / g.CG;
   const int chunk = blockIdx.x, n = blockIdx.y;
@@ -184,19 +170,16 @@ __global__ __launch_bounds__(256) void norm_bwd_reduce_kernel(const float* __res
         for (int e = 0; e < V; ++e) {
           const float y = zv[u][e] * sc[e] + sh[e];
           const float zh = (zv[u][e] - mu[e]) * is[e];
-          float ga = gv[u][e], gy_extra = 0.f;
+          float ga = gv[u][e], gy_extra = 0.f;      // (the peer function's two halves: the third sum needs g_a)
           if (pr.coef) {
             const float yp = zp[u][e] * psc[e] + psh[e];
-            const float ap = (leaky && yp < 0.f) ? yp * slope : yp;
-            const float a = (leaky && y < 0.f) ? y * slope : y;
-            ga -= ca * sgn(ap - a);
-            gy_extra = -cy * sgn(yp - y);
+            ga += norm_bwd_ga_peer(y, yp, leaky, slope, ca);
+            gy_extra = norm_bwd_gy_tap(y, yp, cy);
           }
-          const bool neg = leaky && y < 0.f;
-          const float gy = (neg ? ga * slope : ga) + gy_extra;
+          const float gy = norm_bwd_gy(ga, y, leaky, slope) + gy_extra;
           acc[0][e] += gy;
           acc[1][e] += gy * zh;
-          acc[2][e] += neg ? ga * y : 0.f;
+          acc[2][e] += (leaky && y < 0.f) ? ga * y : 0.f;
         }
       }
     }
@@ -217,7 +200,59 @@ __global__ __launch_bounds__(256) void norm_bwd_reduce_kernel(const float* __res
     t = wave_sum(t);
     if (tid == 0) partials[(long)gridDim.x * gridDim.y * 3 * g.C + rowi] = t;
   }
-  (void)cz;
+}
+
+// (sum, sum of squares, count) of statistic i of channel c -> its scale, shift, mean and invstd, and the running
+// statistics' update with the unbiased variance (null running_mean: none).  One thread per statistic calls this.
+__device__ __forceinline__ void norm_finalize_one(double s, double ss, double cnt, int i, int c,
+                                                  const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                  float eps, float momentum, float* running_mean, float* running_var,
+                                                  float* __restrict__ scale, float* __restrict__ shift,
+                                                  float* __restrict__ mean, float* __restrict__ invstd) {
+  const double m = s / cnt;
+  double var = ss / cnt - m * m;
+  if (var < 0.0) var = 0.0;
+  const float istd = (float)(1.0 / sqrt(var + (double)eps));
+  const float ga = gamma ? gamma[c] : 1.f, be = beta ? beta[c] : 0.f;
+  const float sc = ga * istd;
+  scale[i] = sc;
+  shift[i] = be - (float)m * sc;
+  mean[i] = (float)m;
+  invstd[i] = istd;
+  if (running_mean) {
+    const double unbiased = cnt > 1.0 ? var * cnt / (cnt - 1.0) : var;
+    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)m;
+    running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
+  }
+}
+
+// Columns c and c2 of `rows` partial rows of pitch `ld` by 256 threads: thread t adds rows t, t + 256, ... in order, four
+// rows (eight loads) in flight, then block_tree_sum2<256> (reduce.h: both columns' trees behind the same barriers -- a
+// tree of its own per column cost these latency-bound kernels 0.4-0.6 us).  Every thread gets both sums.
+__device__ __forceinline__ void wide_column_sums(const float* __restrict__ partials, int rows, long ld, int c, int c2,
+                                                 double& sum1, double& sum2) {
+  __shared__ double r1[256], r2[256];
+  const int t = threadIdx.x;
+  double s1 = 0.0, s2 = 0.0;
+  for (int r = t; r < rows; r += 1024) {
+    float v[4][2];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int rr = r + u * 256;
+      const float* row = partials + (long)(rr < rows ? rr : r) * ld;
+      const float m = rr < rows ? 1.f : 0.f;
+      v[u][0] = row[c] * m;
+      v[u][1] = row[c2] * m;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      s1 += (double)v[u][0];
+      s2 += (double)v[u][1];
+    }
+  }
+  block_tree_sum2<256>(s1, s2, r1, r2);
+  sum1 = s1;
+  sum2 = s2;
 }
 
 // One wave per statistic: lanes stride over the partial rows (fixed assignment),
@@ -248,22 +283,8 @@ __global__ __launch_bounds__(256) void norm_finalize_kernel(const float* __restr
   s = wave_sum(s);
   ss = wave_sum(ss);
   if (lane != 0) return;
-  const double cnt = (double)P * (ne - nb);
-  const double m = s / cnt;
-  double var = ss / cnt - m * m;
-  if (var < 0.0) var = 0.0;
-  const float istd = (float)(1.0 / sqrt(var + (double)eps));
-  const float ga = gamma ? gamma[c] : 1.f, be = beta ? beta[c] : 0.f;
-  const float sc = ga * istd;
-  scale[i] = sc;
-  shift[i] = be - (float)m * sc;
-  mean[i] = (float)m;
-  invstd[i] = istd;
-  if (running_mean && !instance) {
-    const double unbiased = cnt > 1.0 ? var * cnt / (cnt - 1.0) : var;
-    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)m;
-    running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
-  }
+  norm_finalize_one(s, ss, (double)P * (ne - nb), i, c, gamma, beta, eps, momentum, instance ? nullptr : running_mean,
+                    running_var, scale, shift, mean, invstd);
 }
 
 // BatchNorm with >= 256 partial rows: ONE BLOCK per channel (lanes stride over the rows, fixed
@@ -275,49 +296,12 @@ __global__ __launch_bounds__(256) void norm_finalize_wide_kernel(const float* __
                                                                  float* running_var, int64_t* nbt,
                                                                  float* __restrict__ scale, float* __restrict__ shift,
                                                                  float* __restrict__ mean, float* __restrict__ invstd) {
-  __shared__ double rs[256], rq[256];
   const int c = blockIdx.x, t = threadIdx.x;
   if (c == 0 && t == 0 && nbt) *nbt += 1;
-  double s = 0.0, ss = 0.0;
-  for (int r = t; r < rows; r += 1024) {          // four rows per trip: eight independent loads in flight
-    float v[4][2];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int rr = r + u * 256;
-      const float* row = partials + (long)(rr < rows ? rr : r) * 2 * W;
-      const float m = rr < rows ? 1.f : 0.f;
-      v[u][0] = row[c] * m;
-      v[u][1] = row[W + c] * m;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      s += (double)v[u][0];
-      ss += (double)v[u][1];
-    }
-  }
-  rs[t] = s;
-  rq[t] = ss;
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if (t < h) { rs[t] += rs[t + h]; rq[t] += rq[t + h]; }
-    __syncthreads();
-  }
+  double s, ss;
+  wide_column_sums(partials, rows, 2L * W, c, W + c, s, ss);
   if (t != 0) return;
-  const double m = rs[0] / cnt;
-  double var = rq[0] / cnt - m * m;
-  if (var < 0.0) var = 0.0;
-  const float istd = (float)(1.0 / sqrt(var + (double)eps));
-  const float ga = gamma ? gamma[c] : 1.f, be = beta ? beta[c] : 0.f;
-  const float sc = ga * istd;
-  scale[c] = sc;
-  shift[c] = be - (float)m * sc;
-  mean[c] = (float)m;
-  invstd[c] = istd;
-  if (running_mean) {
-    const double unbiased = cnt > 1.0 ? var * cnt / (cnt - 1.0) : var;
-    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)m;
-    running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
-  }
+  norm_finalize_one(s, ss, cnt, c, c, gamma, beta, eps, momentum, running_mean, running_var, scale, shift, mean, invstd);
 }
 
 // Thousands of partial rows (a conv's fused statistics leave one per pixel tile) are first
@@ -354,13 +338,8 @@ __device__ __forceinline__ void slope_grad_block(const float* __restrict__ parti
 #pragma unroll
     for (int u = 0; u < 8; ++u) s += (double)v[u];
   }
-  red[t] = s;
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if (t < h) red[t] += red[t + h];
-    __syncthreads();
-  }
-  if (t == 0) *dslope += (float)red[0];
+  s = block_tree_sum<256>(s, red);
+  if (t == 0) *dslope += (float)s;
 }
 
 // BatchNorm with >= 512 partial rows (the 128^2 / 256^2 levels of the generator: 1024-4096 rows; the rows a
@@ -375,37 +354,14 @@ __global__ __launch_bounds__(256) void norm_bwd_finalize_wide_kernel(const float
     slope_grad_block(partials, rows, C, dslope);
     return;
   }
-  __shared__ double r1[256], r2[256];
-  const int c = blockIdx.x, t = threadIdx.x;
-  double s1 = 0.0, s2 = 0.0;
-  for (int r = t; r < rows; r += 1024) {
-    float v[4][2];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int rr = r + u * 256;
-      const float* row = partials + (long)(rr < rows ? rr : r) * 3 * C;
-      const float m = rr < rows ? 1.f : 0.f;
-      v[u][0] = row[c] * m;
-      v[u][1] = row[C + c] * m;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      s1 += (double)v[u][0];
-      s2 += (double)v[u][1];
-    }
-  }
-  r1[t] = s1;
-  r2[t] = s2;
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if (t < h) { r1[t] += r1[t + h]; r2[t] += r2[t + h]; }
-    __syncthreads();
-  }
-  if (t != 0) return;
-  c1[c] = (float)(r1[0] / cnt);
-  c2[c] = (float)(r2[0] / cnt);
-  if (dgamma) dgamma[c] += (float)r2[0];
-  if (dbeta) dbeta[c] += (float)r1[0];
+  const int c = blockIdx.x;
+  double s1, s2;
+  wide_column_sums(partials, rows, 3L * C, c, C + c, s1, s2);
+  if (threadIdx.x != 0) return;
+  c1[c] = (float)(s1 / cnt);
+  c2[c] = (float)(s2 / cnt);
+  if (dgamma) dgamma[c] += (float)s2;
+  if (dbeta) dbeta[c] += (float)s1;
 }
 
 // One wave per channel (dgamma, dbeta, c1, c2).
@@ -535,7 +491,6 @@ __global__ __launch_bounds__(256) void norm_act_add_kernel(const float* __restri
       Vec<V>::store(out + row * ldo + c, o);
     }
   }
-  (void)rows;
 }
 
 // gr and dz may alias (in-place): every element is read before it is written by the same thread.
@@ -592,19 +547,16 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_kernel(const float* gr, in
         float ga = gv[u][e], gy_extra = 0.f, dz_extra = 0.f;
         if (pr.coef) {
           const float yp = zp[u][e] * psc[e] + psh[e];
-          const float ap = (leaky && yp < 0.f) ? yp * slope : yp;
-          const float a = (leaky && y < 0.f) ? y * slope : y;
-          ga -= ca * sgn(ap - a);
-          gy_extra = -cy * sgn(yp - y);
-          dz_extra = -cz * sgn(zp[u][e] - zv[u][e]);
+          ga += norm_bwd_ga_peer(y, yp, leaky, slope, ca);
+          gy_extra = norm_bwd_gy_tap(y, yp, cy);
+          dz_extra = norm_bwd_dz_peer(cz, zv[u][e], zp[u][e]);
         }
-        const float gy = ((leaky && y < 0.f) ? ga * slope : ga) + gy_extra;
-        o[e] = sc[e] * (gy - k1[e] - zh * k2[e]) + dz_extra;
+        const float gy = norm_bwd_gy(ga, y, leaky, slope) + gy_extra;
+        o[e] = norm_bwd_dz(sc[e], gy, zh, k1[e], k2[e]) + dz_extra;
       }
       Vec<V>::store(dz + row * lddz + c, o);
     }
   }
-  (void)rows;
 }
 
 // Perceptual-loss value of one conv+norm+act layer: sums of |z-z'|, |y-y'|, |a-a'| (block partials).
@@ -625,13 +577,13 @@ __global__ __launch_bounds__(256) void tap_l1_kernel(const float* __restrict__ z
     s1 += fabsf(y1 - y2);
     s2 += fabsf(a1 - a2);
   }
-  s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) { sh[0][w] = s0; sh[1][w] = s1; sh[2][w] = s2; }
-  __syncthreads();
-  if (threadIdx.x < 3) partials[blockIdx.x * 3 + threadIdx.x] = sh[threadIdx.x][0] + sh[threadIdx.x][1] + sh[threadIdx.x][2] + sh[threadIdx.x][3];
+  s0 = block_sum4(s0, sh[0]); s1 = block_sum4(s1, sh[1]); s2 = block_sum4(s2, sh[2]);
+  if (threadIdx.x == 0) {
+    partials[blockIdx.x * 3 + 0] = s0; partials[blockIdx.x * 3 + 1] = s1; partials[blockIdx.x * 3 + 2] = s2;
+  }
 }
 
+// (norm_bf16.hip's final divides by numel instead of multiplying by its inverse: other bits, so the two stay two kernels.)
 __global__ __launch_bounds__(64) void tap_l1_final_kernel(const float* __restrict__ partials, int nblocks, double inv_numel,
                                                           float* __restrict__ out3) {
   const int q = threadIdx.x;
@@ -673,8 +625,6 @@ __global__ __launch_bounds__(256) void copy_slice_kernel(const float* __restrict
   }
 }
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 static int make_reduce_geom(ReduceGeom& g, int C, long P, bool vec, const char* what) {
   const int V = vec ? 4 : 1;
   g.C = C;
@@ -702,7 +652,7 @@ extern "C" int32_t mpgan_stats_chunks(int64_t pixels_per_sample, int32_t c) { re
 extern "C" int mpgan_channel_stats(const float* z, int32_t ldz, int32_t n, int64_t P, int32_t c, float* partials,
                                    void* stream) {
   MPGAN_CHECK_ARG(z && partials && n > 0 && P > 0 && c > 0 && ldz >= c, "channel_stats: bad argument");
-  const bool vec = (c % 4 == 0) && (ldz % 4 == 0) && aligned16(z);
+  const bool vec = vec4_rows(c, {ldz}, {z});
   ReduceGeom g;
   int rc = make_reduce_geom(g, c, P, vec, "channel_stats");
   if (rc) return rc;
@@ -754,29 +704,31 @@ extern "C" int mpgan_norm_finalize(const float* partials, int32_t n, int32_t chu
                                      running_var, nbt, scale, shift, mean, invstd, stream);
 }
 
+// The launch behind mpgan_norm_act_add and its fold form (fz.acc != null: the z side's scale / shift come from the fold).
+template <bool FOLD>
+static int launch_norm_act_add(const char* what, const float* z, int32_t ldz, const Pro& a, const NormFold& fz,
+                               const float* r, int32_t ldr, const Pro& b, int32_t n, int64_t P, int32_t c,
+                               int32_t tanh_out, float* out, int32_t ldo, void* stream) {
+  const bool vec = vec4_rows(c, {ldz, ldo, r ? ldr : 0}, {z, out, r});
+  const int CG = vec ? c / 4 : c;
+  MPGAN_UNSUPPORTED(CG > 256, "%s: C=%d too wide", what, c);
+  const dim3 grid = ew_rows_grid(P, n, 256 / CG);
+  if (vec)
+    hipLaunchKernelGGL((norm_act_add_kernel<4, FOLD>), grid, dim3(256), 0, (hipStream_t)stream, z, ldz, a, r, ldr, b,
+                       (long)n * P, (long)P, c, tanh_out, out, ldo, fz);
+  else
+    hipLaunchKernelGGL((norm_act_add_kernel<1, FOLD>), grid, dim3(256), 0, (hipStream_t)stream, z, ldz, a, r, ldr, b,
+                       (long)n * P, (long)P, c, tanh_out, out, ldo, fz);
+  return check_launch(what);
+}
+
 extern "C" int mpgan_norm_act_add(const float* z, int32_t ldz, const mpgan_prologue* pz, const float* r, int32_t ldr,
                                   const mpgan_prologue* pr, int32_t n, int64_t P, int32_t c, int32_t tanh_out,
                                   float* out, int32_t ldo, void* stream) {
   MPGAN_CHECK_ARG(z && out && n > 0 && P > 0 && c > 0 && ldz >= c && ldo >= c && (!r || ldr >= c),
                   "norm_act_add: bad argument");
-  const bool vec = (c % 4 == 0) && (ldz % 4 == 0) && (ldo % 4 == 0) && aligned16(z) && aligned16(out) &&
-                   (!r || ((ldr % 4 == 0) && aligned16(r)));
-  const long rows = (long)n * P;
-  Pro a = make_pro(pz), b = make_pro(pr);
-  const int CGa = vec ? c / 4 : c;
-  MPGAN_UNSUPPORTED(CGa > 256, "norm_act_add: C=%d too wide", c);
-  const int Ra = 256 / CGa;
-  long gxa = (P + 4L * Ra - 1) / (4L * Ra);          // four rows per thread (the kernel batches their loads)
-  const long capa = 4096 / n > 1 ? 4096 / n : 1;
-  if (gxa > capa) gxa = capa;
-  dim3 grida((unsigned)gxa, (unsigned)n);
-  if (vec)
-    hipLaunchKernelGGL((norm_act_add_kernel<4, false>), grida, dim3(256), 0, (hipStream_t)stream, z, ldz, a, r, ldr, b,
-                       rows, (long)P, c, tanh_out, out, ldo, NormFold{});
-  else
-    hipLaunchKernelGGL((norm_act_add_kernel<1, false>), grida, dim3(256), 0, (hipStream_t)stream, z, ldz, a, r, ldr, b,
-                       rows, (long)P, c, tanh_out, out, ldo, NormFold{});
-  return check_launch("norm_act_add");
+  return launch_norm_act_add<false>("norm_act_add", z, ldz, make_pro(pz), NormFold{}, r, ldr, make_pro(pr), n, P, c,
+                                    tanh_out, out, ldo, stream);
 }
 
 extern "C" int mpgan_norm_act_add_fold(const float* z, int32_t ldz, const mpgan_prologue* pz,
@@ -788,27 +740,13 @@ extern "C" int mpgan_norm_act_add_fold(const float* z, int32_t ldz, const mpgan_
   MPGAN_CHECK_ARG(z && out && pz && n > 0 && P > 0 && c > 0 && ldz >= c && ldo >= c && (!r || ldr >= c) &&
                       fz.rep > 0 && fz.cstride >= c && fz.cnt > 0 && fz.scale && fz.shift && fz.mean && fz.invstd,
                   "norm_act_add_fold: bad argument");
-  MPGAN_UNSUPPORTED(c > 256, "norm_act_add_fold: C=%d too wide", c);
-  const bool vec = (c % 4 == 0) && (ldz % 4 == 0) && (ldo % 4 == 0) && aligned16(z) && aligned16(out) &&
-                   (!r || ((ldr % 4 == 0) && aligned16(r)));
-  const long rows = (long)n * P;
-  Pro a = make_pro(pz), b = make_pro(pr);
+  MPGAN_UNSUPPORTED(c > 256, "norm_act_add_fold: C=%d too wide", c);   // (the fold's LDS vectors hold 256 channels)
+  Pro a = make_pro(pz);
   a.scale = fz.scale;            // "has a prologue": the values come from the fold
   a.shift = fz.shift;
   a.n_stride = 0;
-  const int CGa = vec ? c / 4 : c;
-  const int Ra = 256 / CGa;
-  long gxa = (P + 4L * Ra - 1) / (4L * Ra);          // four rows per thread (the kernel batches their loads)
-  const long capa = 4096 / n > 1 ? 4096 / n : 1;
-  if (gxa > capa) gxa = capa;
-  dim3 grida((unsigned)gxa, (unsigned)n);
-  if (vec)
-    hipLaunchKernelGGL((norm_act_add_kernel<4, true>), grida, dim3(256), 0, (hipStream_t)stream, z, ldz, a, r, ldr, b,
-                       rows, (long)P, c, tanh_out, out, ldo, fz);
-  else
-    hipLaunchKernelGGL((norm_act_add_kernel<1, true>), grida, dim3(256), 0, (hipStream_t)stream, z, ldz, a, r, ldr, b,
-                       rows, (long)P, c, tanh_out, out, ldo, fz);
-  return check_launch("norm_act_add_fold");
+  return launch_norm_act_add<true>("norm_act_add_fold", z, ldz, a, fz, r, ldr, make_pro(pr), n, P, c, tanh_out, out, ldo,
+                                   stream);
 }
 
 extern "C" int mpgan_norm_bwd_reduce(const float* g, int32_t ldg, const float* z, int32_t ldz,
@@ -818,7 +756,7 @@ extern "C" int mpgan_norm_bwd_reduce(const float* g, int32_t ldg, const float* z
   MPGAN_CHECK_ARG(g && z && p && p->scale && mean && invstd && partials && n > 0 && P > 0 && c > 0 && ldg >= c &&
                       ldz >= c,
                   "norm_bwd_reduce: bad argument");
-  const bool vec = (c % 4 == 0) && (ldz % 4 == 0) && (ldg % 4 == 0) && aligned16(z) && aligned16(g);
+  const bool vec = vec4_rows(c, {ldz, ldg}, {z, g});
   ReduceGeom geo;
   int rc = make_reduce_geom(geo, c, P, vec, "norm_bwd_reduce");
   if (rc) return rc;
@@ -861,24 +799,18 @@ extern "C" int mpgan_norm_bwd_apply(const float* g, int32_t ldg, const float* z,
   MPGAN_CHECK_ARG(g && z && p && p->scale && mean && invstd && c1 && c2 && dz && n > 0 && P > 0 && c > 0 &&
                       ldg >= c && ldz >= c && lddz >= c,
                   "norm_bwd_apply: bad argument");
-  const bool vec = (c % 4 == 0) && (ldz % 4 == 0) && (ldg % 4 == 0) && (lddz % 4 == 0) && aligned16(z) &&
-                   aligned16(g) && aligned16(dz);
-  const long rows = (long)n * P;
+  const bool vec = vec4_rows(c, {ldz, ldg, lddz}, {z, g, dz});
   Pro pp = make_pro(p);
   Peer pe = make_peer(peer);
-  const int CGa = vec ? c / 4 : c;
-  MPGAN_UNSUPPORTED(CGa > 256, "norm_bwd_apply: C=%d too wide", c);
-  const int Ra = 256 / CGa;
-  long gxa = (P + 4L * Ra - 1) / (4L * Ra);          // four rows per thread (the kernel batches their loads)
-  const long capa = 4096 / n > 1 ? 4096 / n : 1;
-  if (gxa > capa) gxa = capa;
-  dim3 grida((unsigned)gxa, (unsigned)n);
+  const int CG = vec ? c / 4 : c;
+  MPGAN_UNSUPPORTED(CG > 256, "norm_bwd_apply: C=%d too wide", c);
+  const dim3 grid = ew_rows_grid(P, n, 256 / CG);
   if (vec)
-    hipLaunchKernelGGL(norm_bwd_apply_kernel<4>, grida, dim3(256), 0, (hipStream_t)stream, g, ldg, z, ldz, pp, mean,
-                       invstd, c1, c2, pe, rows, (long)P, c, dz, lddz);
+    hipLaunchKernelGGL(norm_bwd_apply_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, g, ldg, z, ldz, pp, mean,
+                       invstd, c1, c2, pe, (long)n * P, (long)P, c, dz, lddz);
   else
-    hipLaunchKernelGGL(norm_bwd_apply_kernel<1>, grida, dim3(256), 0, (hipStream_t)stream, g, ldg, z, ldz, pp, mean,
-                       invstd, c1, c2, pe, rows, (long)P, c, dz, lddz);
+    hipLaunchKernelGGL(norm_bwd_apply_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, g, ldg, z, ldz, pp, mean,
+                       invstd, c1, c2, pe, (long)n * P, (long)P, c, dz, lddz);
   return check_launch("norm_bwd_apply");
 }
 
@@ -893,7 +825,7 @@ extern "C" int mpgan_reduce_partials(const float* partials, int32_t rows, int32_
 extern "C" int mpgan_copy_slice(const float* src, int32_t lds_, float* dst, int32_t ldd, int64_t pixels, int32_t c,
                                 int32_t accumulate, void* stream) {
   MPGAN_CHECK_ARG(src && dst && pixels > 0 && c > 0 && lds_ >= c && ldd >= c, "copy_slice: bad argument");
-  const bool vec = (c % 4 == 0) && (lds_ % 4 == 0) && (ldd % 4 == 0) && aligned16(src) && aligned16(dst);
+  const bool vec = vec4_rows(c, {lds_, ldd}, {src, dst});
   if (vec)
     hipLaunchKernelGGL(copy_slice_kernel<4>, dim3(ew_blocks(pixels * (c / 4))), dim3(256), 0, (hipStream_t)stream, src,
                        lds_, dst, ldd, (long)pixels, c, accumulate);
@@ -905,18 +837,23 @@ extern "C" int mpgan_copy_slice(const float* src, int32_t lds_, float* dst, int3
 
 // eval-mode BatchNorm: scale/shift from the running statistics (inferrence.py:97-110 runs the
 // generator under .eval()); mean/invstd are filled too so the vectors are complete.
-__global__ void norm_from_running_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
-                                         const float* __restrict__ rm, const float* __restrict__ rv, float eps, int c,
-                                         float* __restrict__ scale, float* __restrict__ shift,
-                                         float* __restrict__ mean, float* __restrict__ invstd) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= c) return;
+__device__ __forceinline__ void norm_from_running_one(int i, const float* gamma, const float* beta, const float* rm,
+                                                      const float* rv, float eps, float* scale, float* shift,
+                                                      float* mean, float* invstd) {
   const float istd = 1.f / sqrtf(rv[i] + eps);
   const float sc = (gamma ? gamma[i] : 1.f) * istd;
   scale[i] = sc;
   shift[i] = (beta ? beta[i] : 0.f) - rm[i] * sc;
   mean[i] = rm[i];
   invstd[i] = istd;
+}
+
+__global__ void norm_from_running_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
+                                         const float* __restrict__ rm, const float* __restrict__ rv, float eps, int c,
+                                         float* __restrict__ scale, float* __restrict__ shift,
+                                         float* __restrict__ mean, float* __restrict__ invstd) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < c) norm_from_running_one(i, gamma, beta, rm, rv, eps, scale, shift, mean, invstd);
 }
 
 extern "C" int mpgan_norm_from_running(const float* gamma, const float* beta, const float* running_mean,
@@ -943,14 +880,7 @@ __global__ __launch_bounds__(256) void norm_from_running_multi_kernel(const long
   float* invstd = reinterpret_cast<float*>(e[7]);
   const int c = (int)e[8];
   const float eps = __uint_as_float((unsigned)e[9]);
-  for (int i = threadIdx.x; i < c; i += 256) {
-    const float istd = 1.f / sqrtf(rv[i] + eps);
-    const float sc = (gamma ? gamma[i] : 1.f) * istd;
-    scale[i] = sc;
-    shift[i] = (beta ? beta[i] : 0.f) - rm[i] * sc;
-    mean[i] = rm[i];
-    invstd[i] = istd;
-  }
+  for (int i = threadIdx.x; i < c; i += 256) norm_from_running_one(i, gamma, beta, rm, rv, eps, scale, shift, mean, invstd);
 }
 
 extern "C" int mpgan_norm_from_running_multi(const int64_t* table, int32_t n_layers, void* stream) {

@@ -66,6 +66,21 @@ __device__ __forceinline__ double block_tree_sum(double v, double* red) {
   return red[0];
 }
 
+// Two sums at once through two arrays, one barrier per level: each sum's order is block_tree_sum<N>'s.
+template <int N>
+__device__ __forceinline__ void block_tree_sum2(double& a, double& b, double* ra, double* rb) {
+  const int tid = threadIdx.x;
+  ra[tid] = a;
+  rb[tid] = b;
+  __syncthreads();
+  for (int s = N / 2; s > 0; s >>= 1) {
+    if (tid < s) { ra[tid] += ra[tid + s]; rb[tid] += rb[tid + s]; }
+    __syncthreads();
+  }
+  a = ra[0];
+  b = rb[0];
+}
+
 // 256 threads over n values.  Order: thread t adds x[t], x[t + 256], .. in index order into sh[t], barrier, thread 0
 // adds sh[0 .. 255] in index order.  The sum is thread 0's alone.
 template <typename T>

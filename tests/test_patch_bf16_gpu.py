@@ -186,6 +186,45 @@ def test_peer_norm_backward_bf16(g_dtype, case):
         np.testing.assert_allclose(b[3].numpy(), b[0].sum(red).numpy(), rtol=1e-3, atol=1e-3)
 
 
+@pytest.mark.parametrize("g_dtype", [BF, torch.float32], ids=["g_bf16", "g_f32"])
+@pytest.mark.parametrize("which", ["z", "g", "dz"])
+def test_plain_norm_backward_bf16_refuses_misaligned_views(which, g_dtype):
+    """The entries without peer read and write z, g and dz with 16-byte accesses like the peer entries, and refuse like
+    them: a view offset by one element is a RuntimeError that names the alignment rule, raised before any launch (the
+    NaN-filled outputs stay as they were)."""
+    from mpgan_amd import ops
+    n, c, sp = 2, 24, (1, 5, 7)
+    z, _, g, nbv, _ = _norm_bwd_inputs(n, c, sp, g_dtype)
+    scale, shift, mean, invstd = (_dev(t) for t in nbv)
+
+    def view(t, shifted):
+        base = torch.zeros(t.numel() + 8, dtype=t.dtype, device="cuda")
+        v = base[1 if shifted else 0:][:t.numel()].view(t.shape)
+        v.copy_(t)
+        return v
+
+    zc, gc = view(to_cl(z).to(BF), which == "z"), view(to_cl(g).to(g_dtype), which == "g")
+    rows = z.numel() // c
+    brow = ops.norm_bwd_rows_bf16(rows, c)
+    part = torch.full((brow * 3 * c + c,), float("nan"), device="cuda")
+    bias_part = torch.full((brow * c,), float("nan"), device="cuda")
+    c1, c2 = torch.zeros(c, device="cuda"), torch.zeros(c, device="cuda")
+    dz = view(torch.full_like(to_cl(z).to(BF), float("nan")), which == "dz")
+    if which != "dz":
+        with pytest.raises(RuntimeError, match="16-byte aligned"):
+            ops.norm_bwd_reduce_bf16(gc, zc, scale, shift, mean, invstd, 0.2, part)
+    with pytest.raises(RuntimeError, match="16-byte aligned"):
+        ops.norm_bwd_apply_bf16(gc, zc, scale, shift, mean, invstd, c1, c2, 0.2, dz, bias_part)
+    torch.cuda.synchronize()
+    assert torch.isnan(part).all() and torch.isnan(bias_part).all() and torch.isnan(dz.float()).all()
+    # the same tensors at aligned addresses are served
+    zc, gc, dz = view(zc, False), view(gc, False), view(dz, False)
+    ops.norm_bwd_reduce_bf16(gc, zc, scale, shift, mean, invstd, 0.2, part)
+    ops.norm_bwd_apply_bf16(gc, zc, scale, shift, mean, invstd, c1, c2, 0.2, dz, bias_part)
+    torch.cuda.synchronize()
+    assert torch.isfinite(part[:brow * 3 * c]).all() and torch.isfinite(bias_part).all() and torch.isfinite(dz.float()).all()
+
+
 # ---- 3. / 4. / 7. the whole patch discriminator ----------------------------------------------------------------
 def _inputs(n, seed):
     gen = torch.Generator().manual_seed(seed)
